@@ -1,8 +1,12 @@
 #!/usr/bin/env python
 """Headline benchmark: scenes/sec on 80k-point synthetic scans (BASELINE.json metric, config 2).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; the side measurements listed
+below as `--full only` (extra passes, profiler children, the CPU oracle, the training step, figures read from files) run
+with --full and are null without it.
 
 One "step" = one synthetic 80k-voxel scene through the eval_joint.py path (eval_joint.py:163-280) with its inputs
 already resident in HBM: coordinate manager + kernel maps, sparse MinkUNet34C forward, head split, vote, greedy
@@ -20,26 +24,27 @@ shared counter.  The threads are created, bound to their streams and parked on a
 starts.  Per-scene work and results are unchanged (tests assert bit-identity with the one-at-a-time path).
 
 The JSON line also carries
-  roofline      the vote op (every launch of cv_hv_forward_f32) timed with HIP events on the stream it runs on,
+  roofline      (--full only) the vote op (every launch of cv_hv_forward_f32) timed with HIP events on the stream it runs on,
                 INSIDE the timed region, priced with the algorithmic bytes of SURVEY.md 8d:
                 B_vote = 40 N + 192 V_in + 68 G.  With S > 1 the events include the stretch from co-running scenes;
                 `isolated_*` give the same op from a one-scene-in-flight pass after the timed region.
-  stage_ms      per-stage event times inside the timed region (and `stage_ms_isolated` from that second pass): DEVICE times -
+  stage_ms      per-stage event times inside the timed region (and, --full only, `stage_ms_isolated` from that second pass): DEVICE times -
                 every boundary event sits behind the stage's last launch (the decode's in front of its host wait)
-  parity        match flags of the SAME run against the CPU oracle on one scene, UNDER THE LAUNCH SIZING OF THE TIMED REGION
+  parity        (--full only) match flags of the SAME run against the CPU oracle on one scene, UNDER THE LAUNCH SIZING OF THE TIMED REGION
                 (`parity.config`): grid shape, in-bounds vote count, candidate cells, box count, classes exact; network max
                 abs error.  `parity_one_in_flight`: the same under the library's one-scene sizing, plus whether the two runs
                 agree bit for bit on the grids and every integer output.
   launch sizing the three choices that depend on the scenes in flight (`config.conv_split_target`, `vote_part_records`,
                 `masked_min_rows`) travel with every call (pipeline.ScenePolicy -> cv_scene_desc): nothing process-wide
-  steady_state  side field (one rank, --steps below --steady-steps): the same scene threads, streams and launch policy over 160
+  steady_state  (--full only) side field (one rank, --steps below --steady-steps): the same scene threads, streams and launch policy over 160
                 more steps right after the timed region - the driver's 20-step region spends ~9 % of its 37 ms filling and
                 draining a seven-deep pipeline; never `value`
   cu_busy_in_flight, roofline_conv.mfma_busy_in_flight, in_flight_counters
-                counters of the regime that is timed, collected offline (dispatch counters serialise the kernels) by
+                (--full only) counters of the regime that is timed, collected offline (dispatch counters serialise the kernels) by
                 profiles/in_flight_counters.sh and read from profiles/r6/in_flight_counters.json (labelled as such)
-  cpu_baseline  the CPU oracle (oracle/, a port - the reference has no CPU path) on a bounded sample of the same
+  cpu_baseline  (--full only) the CPU oracle (oracle/, a port - the reference has no CPU path) on a bounded sample of the same
                 scenes, rank 0 only: best of --cpu-reps after one warm-up on all host threads, plus one 1-thread run.
+  train_step_ms (--full only) a few train_joint.py steps on this GPU after the timed region.
 """
 import argparse
 import json
@@ -74,9 +79,9 @@ def parse():
     ap.add_argument("--scenes", type=int, default=4, help="distinct resident scenes per rank")
     ap.add_argument("--points", type=int, default=N_POINTS)
     ap.add_argument("--algo", type=int, default=0, help="vote algorithm: 0 auto, 1 direct, 2 tiles")
-    ap.add_argument("--cpu-scenes", type=int, default=1, help="scenes timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--cpu-scenes", type=int, default=1, help="--full: scenes timed on the CPU oracle (0 = skip)")
     ap.add_argument("--cpu-reps", type=int, default=None,
-                    help="repetitions of the CPU oracle at its best torch thread count (after a warm-up and one run per "
+                    help="--full: repetitions of the CPU oracle at its best torch thread count (after a warm-up and one run per "
                          "thread count; best is reported).  Default 3, or 1 with WORLD_SIZE > 1 - the other ranks wait "
                          "for rank 0 behind the final barrier")
     ap.add_argument("--stage", default="full", choices=["vote_decode", "full"],
@@ -117,7 +122,7 @@ def parse():
                          "start together stay in the same stage (all in the convolutions, then all in the vote) and share the chip "
                          "worse than scenes a fraction of a scene apart")
     ap.add_argument("--measure-traffic", type=int, default=-1,
-                    help="roofline.traffic from the PMC counters IN this run (rank 0, single process, default 80k workload): "
+                    help="--full: roofline.traffic from the PMC counters IN this run (rank 0, single process, default 80k workload): "
                          "two child runs of `bench.py --stage vote_decode` under rocprofv3 (--kernel-trace --pmc FETCH_SIZE, "
                          "then WRITE_SIZE: separate passes), after the timed region.  -1 = when rocprofv3 is on PATH; 0 = "
                          "never (the value of profiles/r*/vote_hbm_traffic.json is reported, labelled as read from a file)")
@@ -127,7 +132,7 @@ def parse():
                          "counter runs out, so favouring them shortens the drain of a short region (longest remaining work "
                          "first); fill and drain stay inside the timed region, results are bit-identical.  0 = off")
     ap.add_argument("--steady-steps", type=int, default=160,
-                    help="side field `steady_state`: when --steps is smaller than this, the scene threads run this many more steps "
+                    help="--full: side field `steady_state`: when --steps is smaller than this, the scene threads run this many more steps "
                          "after the timed region (one rank only); 0 = off")
     ap.add_argument("--xcd-partition", type=int, default=0,
                     help="experiment: the scene streams are created with CU masks (hipExtStreamCreateWithCUMask) of this many XCDs "
@@ -145,7 +150,7 @@ def parse():
                          "training; outside the 1e-4 parity bar, reported as dtype bf16)")
     ap.add_argument("--train-batch", type=int, default=3, help="scenes per GPU-step in --mode train (config.yaml:15)")
     ap.add_argument("--train-steps", type=int, default=None,
-                    help="eval mode, rank 0: train_joint.py steps timed AFTER the timed region for the `train_step_ms` side "
+                    help="eval mode with --full, rank 0: train_joint.py steps timed AFTER the timed region for the `train_step_ms` side "
                          "field (0 = skip).  Default 5, or 0 with WORLD_SIZE > 1")
     ap.add_argument("--sync-bn", action="store_true", help="--mode train: BatchNorm statistics over all ranks' rows "
                                                            "(the reference's batch-of-3 semantics under scene-parallel DDP)")
@@ -169,6 +174,14 @@ def parse():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="launch-path check without a GPU: parse, rendezvous (CV_DIST_BACKEND=gloo on CPU), barrier, "
                          "max-reduce, print the JSON skeleton")
+    ap.add_argument("--full", action="store_true",
+                    help="eval mode: also the side measurements after the timed region (steady_state, the one-scene-in-flight "
+                         "pass and its isolated_* / stage_ms_isolated figures, roofline traffic and roofline_conv, "
+                         "in_flight_counters, train_step_ms, cpu_baseline with parity / parity_one_in_flight).  Off: set up, "
+                         "warm up, time --steps steps, write --dump-outputs, print the line (those fields null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="eval mode: write what the last timed step returned (detections, raw decode arrays, network output) "
+                         "as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     a = ap.parse_args()
     if a.teacher_forced:
         a.predictions = "teacher"
@@ -323,9 +336,10 @@ TIMED_POLICY = None     # the policy of the timed region (the parity object is c
 POLICY = None           # pipeline.ScenePolicy of every run_step call (launch sizing per call: cv_scene_desc / the thread's values)
 
 
-def run_step(model, hv, s, ev=None, teacher=False, keep=None):
+def run_step(model, hv, s, ev=None, teacher=False, keep=None, out=None):
     """One scene through eval_joint.py:163-280: network -> head -> vote -> decode -> per-class NMS.
-    keep: optional dict that receives the device tensors of the step (the parity check reads them)."""
+    keep: optional dict that receives the device tensors of the step (the parity check reads them).
+    out: optional dict that receives the network output `y` [N, C] of the step (--dump-outputs)."""
     rec = (lambda i: ev[i].record()) if ev is not None else (lambda i: None)
     if SCENE_CALL == "c" and model is not None and not ABLATE and model.USE_PROGRAM:
         # the whole scene behind ONE C call (cv_detect_scene_f32): same kernels, same order, bit-identical results; the
@@ -340,12 +354,14 @@ def run_step(model, hv, s, ev=None, teacher=False, keep=None):
         finally:
             if ev is not None and len(ev) > 6:
                 _lib.lib().cv_hv_set_kernel_events(None, None)
+        if out is not None:
+            out["y"] = y
         return dets, raw
     with pipeline.scene_policy(POLICY):
-        return _run_step_calls(model, hv, s, ev, rec, teacher, keep)
+        return _run_step_calls(model, hv, s, ev, rec, teacher, keep, out)
 
 
-def _run_step_calls(model, hv, s, ev, rec, teacher, keep):
+def _run_step_calls(model, hv, s, ev, rec, teacher, keep, out=None):
     """run_step, call by call (the Python pipeline: --scene-call py, the timing ablations, vote-only stages)"""
     with torch.no_grad():
         rec(0)
@@ -397,7 +413,40 @@ def _run_step_calls(model, hv, s, ev, rec, teacher, keep):
     if keep is not None:
         keep.update(y=y.F if model is not None else None, net_pred=net_pred if model is not None else None,
                     grids=(grid_obj, grid_rot, grid_scale), raw=raw)
+    if out is not None and model is not None:
+        out["y"] = y.F
     return decode.nms_per_class(raw["boxes"], raw["scores"], raw["classes"]), raw
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_Y_BYTES = 48 << 20         # the network output beyond this is written as a fixed, seeded sample of its rows
+
+
+def dump_outputs(path, last):
+    """--dump-outputs: what the last timed step returned to its caller, as path/<name>.npy (float32 / float64):
+    det_class / det_box / det_score (the per-class NMS detections, in order), raw_<key> (the decode arrays) and y (the
+    network output [N, C]; y_rows holds the row indices when y is a seeded sample of a larger output)"""
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    dets = last.get("dets", [])
+    arrays["det_class"] = np.array([d[0] for d in dets], dtype=np.float64)
+    arrays["det_box"] = np.array([np.asarray(d[1], dtype=np.float32) for d in dets], dtype=np.float32).reshape(-1, 8, 3)
+    arrays["det_score"] = np.array([d[2] for d in dets], dtype=np.float64)
+    for k, v in sorted(last.get("raw", {}).items()):
+        if isinstance(v, np.ndarray):
+            arrays["raw_" + k] = v.astype(np.float32 if v.dtype == np.float32 else np.float64)
+    if last.get("y") is not None:
+        y = last["y"].detach().float().cpu().numpy()
+        rows = max(1, DUMP_Y_BYTES // max(1, y.shape[1] * 4))
+        if y.shape[0] > rows:
+            idx = np.sort(np.random.default_rng(0).choice(y.shape[0], rows, replace=False))
+            arrays["y_rows"] = idx.astype(np.float64)
+            y = y[idx]
+        arrays["y"] = y
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "--dump-outputs: %d bytes" % total
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v))
 
 
 def cpu_oracle_scene(s, sd, full, teacher):
@@ -721,6 +770,8 @@ def main_rendezvous_only(a):
 
 def main():
     a = parse()
+    if a.dump_outputs and (a.rendezvous_only or a.mode != "eval"):
+        raise SystemExit("bench.py: --dump-outputs writes the outputs of the eval mode's timed path")
     if a.rendezvous_only:
         return main_rendezvous_only(a)
     if a.mode == "train":
@@ -747,7 +798,7 @@ def main():
     # scene i of rank r uses seed r*1000 + i: every rank owns different scenes
     scenes = [ResidentScene(seed, a.points, dev, a.large) for seed in cvd.scene_seeds(rank, a.scenes)]
     net_flops = None
-    if full:
+    if full and a.full:                                  # (roofline_conv and the roofline's byte counts: --full only)
         with torch.no_grad():
             x0 = ME.SparseTensor(scenes[0].feats_in, scenes[0].coords4, device=dev)
             net_flops = model.forward_flops(x0)       # (pairs-based, dense-equivalent), untimed
@@ -793,6 +844,7 @@ def main():
     step_log = [None] * a.steps         # (thread, host time at start, at end) of every timed step
     host_us = [None] * a.steps          # cv_scene_result.host_us of every timed step
     warm_steps = [0] * S
+    last = {}                           # what the last timed step returned (--dump-outputs)
     errors = []
     # the K steps are handed out from one counter: a thread whose scene was cheap takes the next step at once
     ticket, ticket_lock = itertools.count(), threading.Lock()
@@ -838,11 +890,14 @@ def main():
                     if k >= a.steps:
                         break
                     ts = time.perf_counter()
+                    out = last if a.dump_outputs and k == a.steps - 1 else None
                     if hi_streams is not None and k >= a.steps - abs(a.tail_priority):
                         with torch.cuda.stream(hi_streams[i]):
-                            dets, _ = run_step(model, hvs[i], scenes[k % len(scenes)], events[k], teacher)
+                            dets, raw = run_step(model, hvs[i], scenes[k % len(scenes)], events[k], teacher, out=out)
                     else:
-                        dets, _ = run_step(model, hvs[i], scenes[k % len(scenes)], events[k], teacher)
+                        dets, raw = run_step(model, hvs[i], scenes[k % len(scenes)], events[k], teacher, out=out)
+                    if out is not None:
+                        out.update(dets=dets, raw=raw)
                     step_log[k] = (i, ts, time.perf_counter())
                     if SCENE_CALL == "c" and model is not None:
                         host_us[k] = pipeline.last_scene_host_us(dev)
@@ -895,6 +950,8 @@ def main():
                   file=sys.stderr)
     dt = cvd.reduce_scalar(dt, "max", dev)
     torch.cuda.synchronize()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last)
     coll = collective_info()
 
     def stage_times(evs, stat=np.mean):
@@ -926,7 +983,7 @@ def main():
     # driver's 20-step region is 37 ms of a seven-deep pipeline whose scenes take 11 ms each under load - fill and drain cost
     # it ~9 % against the steady state; this region shows the steady state from inside the same process.  Never `value`.
     steady = None
-    if S > 1 and world == 1 and a.steady_steps > a.steps and not ABLATE:
+    if a.full and S > 1 and world == 1 and a.steady_steps > a.steps and not ABLATE:
         n_side = int(a.steady_steps)
         ticket2, lock2, gate2, errors2 = itertools.count(), threading.Lock(), threading.Barrier(S + 1), []
 
@@ -969,7 +1026,7 @@ def main():
                       "note": "side field, not `value`: the same threads, streams and launch policy over a longer region right after "
                               "the timed one (fill and drain of the seven-deep pipeline amortised)"}
     iso_stage = iso_achieved = iso_vote = iso_op = None
-    if S > 1:
+    if a.full and S > 1:
         # kernels of concurrent scenes stretch each other's event-to-event times: the same steps once more with ONE
         # scene in flight, after the timed region, give the op on its own (side fields; `frac` is the timed region's).
         # This pass runs on the main thread's stream, which has its own allocator pool and scratch: two passes over the
@@ -995,11 +1052,11 @@ def main():
     # own passes, profiles/r*/vote_hbm_traffic.json) for the default 80k workload; null otherwise
     traffic = traffic_source = None
     default_workload = a.points == N_POINTS and not a.large and a.algo in (0, 2)
-    if rank == 0 and world == 1 and a.measure_traffic != 0 and default_workload:
+    if a.full and rank == 0 and world == 1 and a.measure_traffic != 0 and default_workload:
         m = measure_vote_traffic(a)
         if m is not None:
             traffic, traffic_source = m
-    for rnd in (() if traffic is not None else ("r6", "r5", "r4", "r3", "r2", "r1")):
+    for rnd in (() if traffic is not None or not a.full else ("r6", "r5", "r4", "r3", "r2", "r1")):
         tj = os.path.join(ROOT, "profiles", rnd, "vote_hbm_traffic.json")
         if os.path.exists(tj) and a.points == N_POINTS and not a.large and a.algo in (0, 2):
             traffic = json.load(open(tj))["hbm_bytes_per_launch"]
@@ -1011,7 +1068,7 @@ def main():
     # chip to themselves, over the chip time a scene gets at the in-flight rate.  Reported as read from a file.
     in_flight = None
     ifj = os.path.join(ROOT, "profiles", "r6", "in_flight_counters.json")
-    if default_workload and full and S >= 4 and os.path.exists(ifj):
+    if a.full and default_workload and full and S >= 4 and os.path.exists(ifj):
         j = json.load(open(ifj))
         in_flight = {k: j[k] for k in ("cu_busy_in_flight", "mfma_busy_in_flight", "mean_kernels_running",
                                        "wall_share_with_at_least_1024_workgroups_running", "kernels_running_at_once",
@@ -1033,6 +1090,7 @@ def main():
         "vs_baseline": None,
         "dtype": a.dtype,
         "data": "synthetic",
+        "full": bool(a.full),
         "config": {"workload": ("single %d-point synthetic scene per GPU-step, eval_joint.py path: "
                                 "HIP sparse MinkUNet34C forward (%s, random init) + head + HIP vote "
                                 "accumulation + decode + NMS" % (a.points, "bf16 conv products" if a.dtype == "bf16"
@@ -1048,7 +1106,7 @@ def main():
                    "conv_split_target": "adaptive: 768 below four scenes in flight, 256 from four on" if ADAPTIVE_SPLIT else (split_target or 768),
                    "vote_part_records": part_records or 4096, "masked_min_rows": masked_min_rows,
                    **({"ablate": a.ablate, "INVALID": "timing ablation: results are wrong, not a reportable number"} if a.ablate else {})},
-        "roofline": {"bound": "hbm",
+        "roofline": None if not a.full else {"bound": "hbm",
                      "kernel": "hv_fwd_tiles (the accumulation kernel of cv_hv_forward_f32)" if kernel_timed
                                else "vote op (all launches of cv_hv_forward_f32)",
                      "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1067,7 +1125,7 @@ def main():
                      "isolated_op_avg_ms": iso_op,
                      "note": "algorithmic-byte model of the reference's scatter (48 fp32 atomics per vote); the tile "
                              "kernel accumulates in LDS, its real HBM traffic is `traffic`"},
-        "roofline_conv": None if not full else {
+        "roofline_conv": None if not (full and a.full) else {
             "bound": "mfma", "kernel": "sparse MinkUNet34C forward (all conv launches + coordinate manager)",
             "achieved": net_flops[0] / (net_ms * 1e-3) / 1e12, "peak": conv_peak, "unit": "TFLOP/s",
             "frac": net_flops[0] / (net_ms * 1e-3) / 1e12 / conv_peak,
@@ -1111,9 +1169,9 @@ def main():
             [float(np.median([x[i] for x in h])) * 1e-3 for i in range(4)])))([x for x in host_us if x is not None]),
     }
     out["cpu_baseline"] = out["parity"] = out["parity_one_in_flight"] = out["train_step_ms"] = None
-    if rank == 0 and full and a.train_steps > 0 and not a.large:
+    if a.full and rank == 0 and full and a.train_steps > 0 and not a.large:
         out["train_step_ms"] = train_side_field(a, scenes, dev)
-    if rank == 0 and a.cpu_scenes > 0:
+    if a.full and rank == 0 and a.cpu_scenes > 0:
         out["cpu_baseline"], out["parity"], out["parity_one_in_flight"] = cpu_baseline(a, scenes, model, hv, full, teacher)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r6; mkdir -p $O
 for rep in 1 2; do
 for walk in lds reg; do for prio in 0 1; do
-  CV_DEC_GREEDY=$walk CV_DEC_PRIO=$prio python bench.py --steps ${STEPS:-120} --cpu-scenes 0 --train-steps 0 --measure-traffic 0 2>/dev/null | tail -1 > $O/dec_${walk}_p${prio}_$rep.json
+  CV_DEC_GREEDY=$walk CV_DEC_PRIO=$prio python bench.py --steps ${STEPS:-120} --cpu-scenes 0 --train-steps 0 --measure-traffic 0 --full 2>/dev/null | tail -1 > $O/dec_${walk}_p${prio}_$rep.json
   python - <<PY
 import json
 d = json.load(open("$O/dec_${walk}_p${prio}_$rep.json"))

@@ -7,10 +7,10 @@
 # profiles/in_flight_summary.py turns the four outputs into profiles/r6/in_flight_counters.txt.
 cd /tmp && export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6; mkdir -p $O
 STEPS=${STEPS:-240}
-CMD="python $R/bench.py --steps $STEPS --cpu-scenes 0 --train-steps 0 --measure-traffic 0"
+CMD="python $R/bench.py --steps $STEPS --cpu-scenes 0 --train-steps 0 --measure-traffic 0 --full"
 rm -rf /tmp/ifT /tmp/ifA /tmp/ifB /tmp/ifC
 timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/ifT -- $CMD > $O/if_trace_bench.json 2> /tmp/ifT.err
-PCMD="python $R/bench.py --steps 56 --warmup 14 --min-warm-seconds 0 --cpu-scenes 0 --train-steps 0 --measure-traffic 0"
+PCMD="python $R/bench.py --steps 56 --warmup 14 --min-warm-seconds 0 --cpu-scenes 0 --train-steps 0 --measure-traffic 0 --full"
 timeout 1500 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_BUSY_CU_CYCLES SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES -d /tmp/ifA --output-format csv -- $PCMD > /tmp/ifA.log 2>&1
 timeout 1500 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/ifB --output-format csv -- $PCMD > /tmp/ifB.log 2>&1
 timeout 1500 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d /tmp/ifC --output-format csv -- $PCMD > /tmp/ifC.log 2>&1

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out/r2n
 mkdir -p $O
-python bench.py > $O/bench.log 2>$O/bench.err; tail -1 $O/bench.log > $O/bench.json
+python bench.py --full > $O/bench.log 2>$O/bench.err; tail -1 $O/bench.log > $O/bench.json
 python bench.py --steps 20 --cpu-scenes 0 2>/dev/null | tail -1 > $O/bench_20steps.json
 python bench.py --streams 1 --cpu-scenes 0 2>/dev/null | tail -1 > $O/bench_streams1.json
 python bench.py --streams 1 --cpu-scenes 0 --predictions network 2>/dev/null | tail -1 > $O/bench_streams1_network_predictions.json
@@ -19,6 +19,6 @@ bash profiles/conv_l2_pmc.sh > $O/conv_l2_pmc.txt 2>&1
 bash profiles/vote_pmc.sh > $O/vote_pmc.log 2>&1; cp gpurun_out/vote_pmc/* $O/
 for s in 4 6 8 10; do
   echo "streams=$s" >> $O/sweep_streams.txt
-  python bench.py --steps 240 --cpu-scenes 0 --streams $s 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['value'],1), d['stage_ms'], round(d['roofline']['frac'],4))" >> $O/sweep_streams.txt
+  python bench.py --steps 240 --cpu-scenes 0 --streams $s --full 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['value'],1), d['stage_ms'], round(d['roofline']['frac'],4))" >> $O/sweep_streams.txt
 done
 ls -la $O

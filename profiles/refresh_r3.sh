@@ -9,7 +9,7 @@ python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 
 # the driver's exact command, twice (fresh process each), then the 240-step line with the CPU baseline and parity objects
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd_2.json 2>> $O/bench_driver_cmd.err
-python bench.py --steps 240 > $O/bench.log 2>$O/bench.err; tail -1 $O/bench.log > $O/bench.json
+python bench.py --steps 240 --full > $O/bench.log 2>$O/bench.err; tail -1 $O/bench.log > $O/bench.json
 python bench.py --streams 1 --steps 60 --cpu-scenes 0 --train-steps 0 2>/dev/null | tail -1 > $O/bench_streams1.json
 python bench.py --streams 1 --steps 40 --cpu-scenes 0 --train-steps 0 --large --points 300000 2>/dev/null | tail -1 > $O/bench_streams1_300k.json
 python bench.py --mode separate --large --points 300000 --steps 6 --warmup 2 2>/dev/null | tail -1 > $O/bench_separate_300k.json

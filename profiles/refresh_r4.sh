@@ -8,7 +8,7 @@ python -m pytest tests -m gpu -q > $O/pytest_gpu_final.log 2>&1; tail -3 $O/pyte
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
 # the driver's exact command, three fresh processes, then the 240-step line with the CPU baseline and parity objects
 for i in 1 2 3; do python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd_$i.json 2>> $O/bench_driver_cmd.err; done
-python bench.py --steps 240 > $O/bench.log 2>$O/bench.err; tail -1 $O/bench.log > $O/bench.json
+python bench.py --steps 240 --full > $O/bench.log 2>$O/bench.err; tail -1 $O/bench.log > $O/bench.json
 python bench.py --streams 1 --steps 60 --cpu-scenes 0 --train-steps 0 2>/dev/null | tail -1 > $O/bench_streams1.json
 python bench.py --streams 1 --steps 40 --cpu-scenes 0 --train-steps 0 --large --points 300000 2>/dev/null | tail -1 > $O/bench_streams1_300k.json
 python bench.py --mode train --steps 10 --warmup 2 2>/dev/null | tail -1 > $O/bench_train.json

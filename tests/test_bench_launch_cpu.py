@@ -65,3 +65,30 @@ def test_eight_rank_launch_and_scene_thread_cap():
     cores = len(os.sched_getaffinity(0))
     assert out["scene_threads_per_rank"] == max(1, min(4, max(2, cores // 8)))
     assert out["max_seconds"] >= 0.08                       # rank 7 sleeps 80 ms: the max over ranks
+
+
+def test_dump_outputs_writes_float_arrays_within_64_mb(tmp_path):
+    """--dump-outputs without a GPU: the arrays a caller of the timed path receives, as float32 / float64 .npy files; a
+    network output beyond the budget is written as the same seeded sample of rows every time"""
+    import numpy as np
+    import torch
+    import bench
+    rng = np.random.default_rng(1)
+    raw = dict(boxes=rng.random((3, 8, 3), dtype=np.float32), scores=rng.random(3, dtype=np.float32),
+               classes=np.array([1, 2, 1], np.int32), cand_idx=np.array([7, 11, 40, 2 ** 40], np.int64),
+               verdict=np.array([1, 0, 1, 1], np.int32), truncated=False)
+    dets = [(1, raw["boxes"][0], float(raw["scores"][0])), (2, raw["boxes"][1], float(raw["scores"][1]))]
+    y = torch.randn(300000, 64, generator=torch.Generator().manual_seed(0))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), dict(dets=dets, raw=raw, y=y))
+    files = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert set(files) == {"det_class.npy", "det_box.npy", "det_score.npy", "raw_boxes.npy", "raw_scores.npy", "raw_classes.npy",
+                          "raw_cand_idx.npy", "raw_verdict.npy", "y.npy", "y_rows.npy"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files["det_class.npy"].tolist() == [1.0, 2.0] and np.array_equal(files["det_box.npy"], raw["boxes"][:2])
+    assert files["raw_cand_idx.npy"].tolist() == [7.0, 11.0, 40.0, 2.0 ** 40]
+    rows = files["y_rows.npy"].astype(np.int64)
+    assert np.array_equal(files["y.npy"], y.numpy()[rows])
+    for name, a in files.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / name)), name

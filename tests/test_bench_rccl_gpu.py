@@ -2,7 +2,7 @@
 --nproc-per-node 1 ... bench.py --gpus 1 --steps 20 --warmup 5` with CV_DIST_FORCE=1 creates a one-rank `nccl` (= RCCL on
 ROCm) group, so the default (eval) mode runs what an 8-GPU launch runs per rank: cvd.init("nccl"), the barriers around the
 timed region, the max-reduction of the wall time.  One JSON line comes back with librccl mapped, and its parity object -
-the HIP path of scene 0 against the CPU oracle - equals the plain single-process run's."""
+the HIP path of scene 0 against the CPU oracle, a --full side field - equals the plain single-process run's."""
 import json
 import os
 import socket
@@ -14,7 +14,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-reps", "1", "--train-steps", "0", "--min-warm-seconds", "0.3",
-        "--measure-traffic", "0"]
+        "--measure-traffic", "0", "--full"]
 
 
 def _free_port():
