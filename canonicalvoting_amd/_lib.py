@@ -84,6 +84,34 @@ class SceneDesc(ctypes.Structure):
                 ("conv_split_target", ctypes.c_int), ("vote_part_records", ctypes.c_int)]
 
 
+MAX_CATEGORIES = 16      # CV_MAX_CATEGORIES
+
+
+class SceneSeparateDesc(ctypes.Structure):
+    """struct cv_scene_separate_desc (include/cv_hip.h)"""
+    _fields_ = [("d_coords4", vp), ("n", ctypes.c_longlong), ("d_feats", vp), ("feats_ld", ctypes.c_int), ("d_points", vp),
+                ("res", ctypes.c_float), ("num_rots", ctypes.c_int), ("num_models", ctypes.c_int),
+                ("ops", vp), ("n_ops", vp), ("bufs", vp), ("n_bufs", vp),
+                ("stem_k", ctypes.c_int), ("mask_groups", ctypes.c_int), ("masked_min_rows", ctypes.c_longlong),
+                ("max_channels", ctypes.c_int), ("use_range_flag", ctypes.c_int),
+                ("d_out_feats", vp), ("out_ld", ctypes.c_int), ("out_channels", ctypes.c_int), ("log_scale", ctypes.c_int),
+                ("d_xyz_in", vp), ("d_scale_in", vp), ("d_prob_in", vp), ("vote_algo", ctypes.c_int), ("decode", DecodeParams),
+                ("max_candidates", ctypes.c_int), ("nms_threshold", ctypes.c_double), ("d_ws", vp), ("ws_bytes", ctypes.c_size_t),
+                ("h_pinned", vp), ("pinned_bytes", ctypes.c_size_t), ("h_cand_idx", vp), ("h_verdict", vp), ("h_boxes", vp),
+                ("h_scores", vp), ("h_det_cat", vp), ("h_det_box", vp), ("events", vp * 5),
+                ("conv_split_target", ctypes.c_int), ("vote_part_records", ctypes.c_int)]
+
+
+class SceneSeparateResult(ctypes.Structure):
+    """struct cv_scene_separate_result (include/cv_hip.h)"""
+    _fields_ = [("n_cand", ctypes.c_int * MAX_CATEGORIES), ("n_boxes", ctypes.c_int * MAX_CATEGORIES),
+                ("truncated", ctypes.c_int * MAX_CATEGORIES), ("n_det", ctypes.c_int), ("range_flag", ctypes.c_int),
+                ("duplicates", ctypes.c_int), ("out_of_window", ctypes.c_int), ("dims", ctypes.c_int * 3),
+                ("corner", ctypes.c_float * 3), ("level_rows", ctypes.c_longlong * 5), ("needed_ws_bytes", ctypes.c_size_t),
+                ("d_grid_obj", vp), ("d_grid_rot", vp), ("d_grid_scale", vp), ("d_xyz", vp), ("d_scale", vp), ("d_prob", vp),
+                ("host_us", ctypes.c_float * 4)]
+
+
 class PackJob(ctypes.Structure):
     """struct cv_pack_job (include/cv_hip.h)"""
     _fields_ = [("w", vp), ("wp", vp), ("K", ctypes.c_int), ("cin", ctypes.c_int), ("cout", ctypes.c_int), ("trans", ctypes.c_int),
@@ -112,6 +140,9 @@ SIGNATURES = {
     "cv_hv_forward_f32": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_float, ctypes.c_int,
                                          c_float_p, c_int_p, vp, vp, vp, vp, ctypes.c_size_t,
                                          ctypes.c_int, vp]),
+    "cv_hv_forward_cat_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, c_int_p, ctypes.c_int, ctypes.c_int]),
+    "cv_hv_forward_cat_f32": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_float, ctypes.c_int, c_float_p, c_int_p,
+                                             ctypes.c_int, vp, vp, vp, vp, ctypes.c_size_t, ctypes.c_int, vp]),
     "cv_hv_set_kernel_events": (ctypes.c_int, [vp, vp]),
     "cv_hv_backward_f32": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_float,
                                           ctypes.c_int, c_float_p, c_int_p, vp, vp, vp, vp]),
@@ -122,6 +153,11 @@ SIGNATURES = {
                                      ctypes.c_int64, ctypes.POINTER(DecodeParams), ctypes.c_int, vp,
                                      ctypes.c_size_t, c_int_p, c_i64_p, c_i32_p, c_int_p, c_float_p,
                                      c_float_p, c_i32_p, c_int_p, vp]),
+    "cv_decode_cat_workspace_bytes": (ctypes.c_size_t, [c_int_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    "cv_decode_cat_f32": (ctypes.c_int, [vp, vp, vp, c_int_p, c_float_p, ctypes.c_float, vp, vp, vp, vp, ctypes.c_int64,
+                                         ctypes.c_int, ctypes.POINTER(DecodeParams), ctypes.c_int, vp, ctypes.c_size_t, c_int_p,
+                                         c_i64_p, c_i32_p, c_int_p, c_float_p, c_float_p, c_i32_p, c_int_p, vp]),
+    "cv_detect_scene_separate_f32": (ctypes.c_int, [ctypes.POINTER(SceneSeparateDesc), ctypes.POINTER(SceneSeparateResult), vp]),
     "cv_sp_table_capacity": (ctypes.c_longlong, [ctypes.c_longlong]),
     "cv_sp_levels_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "cv_sp_build_levels": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),

@@ -73,6 +73,20 @@ struct List {
     int64_t cap;
 };
 
+// Category axis (cv_decode_cat_f32): category k's workspace (list, counters, candidates, statistics) is a carve of the
+// single-category layout `ws` bytes behind category k - 1's, its grids `cells` cells and its predictions `n` points behind
+// (scan points and class input shared).  K = 1 (cv_decode_f32): k = 0, every offset is zero.
+struct CatStride { int64_t ws, n, cells; };
+template <class T>
+__device__ __forceinline__ T* cat_ws(T* p, int64_t bytes, int k) {
+    return (T*)((const char*)p + (int64_t)k * bytes);
+}
+__device__ __forceinline__ List cat_list(List L, int64_t bytes, int k) {
+    L.idx = cat_ws(L.idx, bytes, k); L.val = cat_ws(L.val, bytes, k); L.xy = cat_ws(L.xy, bytes, k);
+    L.z = cat_ws(L.z, bytes, k); L.geo = cat_ws(L.geo, bytes, k);
+    return L;
+}
+
 // workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding GLOBAL access
 // (vmcnt(0)): with the candidate records stored from inside the greedy loop each barrier then cost a store round
 // trip to L2 (~2 us per candidate).  Nothing the loop communicates between threads goes through global memory.
@@ -89,7 +103,10 @@ __global__ __launch_bounds__(256) void dec_compact(const float* __restrict__ g_o
                                                    const float* __restrict__ g_rot,
                                                    const float* __restrict__ g_scale, Geo geo,
                                                    int64_t G, float thresh, List L,
-                                                   unsigned* __restrict__ list_n) {
+                                                   unsigned* __restrict__ list_n, CatStride ks) {
+    const int kc = blockIdx.y;
+    g_obj = g_obj + kc * ks.cells; g_rot = g_rot + kc * 2 * ks.cells; g_scale = g_scale + kc * 3 * ks.cells;
+    L = cat_list(L, ks.ws, kc); list_n = cat_ws(list_n, ks.ws, kc);
     for (int64_t base = blockIdx.x * 256ll; base < G; base += (int64_t)gridDim.x * 256) {
         const int64_t i = base + threadIdx.x;
         float v = 0.f;
@@ -632,7 +649,10 @@ __device__ __forceinline__ void dec_greedy_sorted(Geo geo, cv_decode_params prm,
 __global__ __launch_bounds__(GREEDY_T) void dec_greedy_dispatch(Geo geo, cv_decode_params prm, List L,
                                                                 const unsigned* __restrict__ list_n,
                                                                 Cand* __restrict__ cands, Stats* __restrict__ stats,
-                                                                int* __restrict__ n_cand_out) {
+                                                                int* __restrict__ n_cand_out, int64_t ks_ws) {
+    // one walker workgroup per category (blockIdx.y): the K walks run side by side
+    L = cat_list(L, ks_ws, blockIdx.y); list_n = cat_ws(list_n, ks_ws, blockIdx.y); cands = cat_ws(cands, ks_ws, blockIdx.y);
+    stats = cat_ws(stats, ks_ws, blockIdx.y); n_cand_out = cat_ws(n_cand_out, ks_ws, blockIdx.y);
     if (*list_n <= (unsigned)GREEDY_CAP) dec_greedy<1, GREEDY_T>(geo, prm, L, list_n, cands, stats, n_cand_out);
     else dec_greedy<0, GREEDY_T>(geo, prm, L, list_n, cands, stats, n_cand_out);
 }
@@ -644,7 +664,9 @@ constexpr int GREEDY_G_BIG = 64;
 __global__ __launch_bounds__(GREEDY_T_BIG) void dec_greedy_dispatch_big(Geo geo, cv_decode_params prm, List L,
                                                                         const unsigned* __restrict__ list_n,
                                                                         Cand* __restrict__ cands, Stats* __restrict__ stats,
-                                                                        int* __restrict__ n_cand_out) {
+                                                                        int* __restrict__ n_cand_out, int64_t ks_ws) {
+    L = cat_list(L, ks_ws, blockIdx.y); list_n = cat_ws(list_n, ks_ws, blockIdx.y); cands = cat_ws(cands, ks_ws, blockIdx.y);
+    stats = cat_ws(stats, ks_ws, blockIdx.y); n_cand_out = cat_ws(n_cand_out, ks_ws, blockIdx.y);
     if (*list_n <= (unsigned)(GREEDY_E_BIG * GREEDY_T_BIG))
         dec_greedy_sorted<GREEDY_T_BIG, GREEDY_E_BIG, GREEDY_G_BIG>(geo, prm, L, (int)*list_n, cands, stats, n_cand_out);
     else dec_greedy<0, GREEDY_T_BIG>(geo, prm, L, list_n, cands, stats, n_cand_out);
@@ -725,7 +747,11 @@ __device__ void finalize_block(const Cand* __restrict__ cands, const Stats* __re
 __global__ __launch_bounds__(256) void dec_backproject(
     const float* __restrict__ pts, const float* __restrict__ xyz, const float* __restrict__ prob,
     const int* __restrict__ cls, int64_t n, float prob_thresh, const Cand* __restrict__ cands,
-    const int* __restrict__ n_cand, Stats* __restrict__ stats) {
+    const int* __restrict__ n_cand, Stats* __restrict__ stats, CatStride ks) {
+    // category: blockIdx.z (blockIdx.y strides over the candidate groups)
+    const int kc = blockIdx.z;
+    xyz = xyz + kc * 3 * ks.n; prob = prob + kc * ks.n;
+    cands = cat_ws(cands, ks.ws, kc); n_cand = cat_ws(n_cand, ks.ws, kc); stats = cat_ws(stats, ks.ws, kc);
     const int64_t i = blockIdx.x * 256ll + threadIdx.x;
     const bool have = i < n;
     float p0 = 0, p1 = 0, p2 = 0, x0 = 0, x1 = 0, x2 = 0, pr = 0;
@@ -734,7 +760,7 @@ __global__ __launch_bounds__(256) void dec_backproject(
         p0 = pts[i * 3]; p1 = pts[i * 3 + 1]; p2 = pts[i * 3 + 2];
         x0 = xyz[i * 3]; x1 = xyz[i * 3 + 1]; x2 = xyz[i * 3 + 2];
         pr = prob[i];
-        cl = cls[i];
+        cl = cls ? cls[i] : 0;          // (no class input: class 0, separate mode)
     }
     const int nc = n_cand[0];
     // A workgroup takes its 256 points through GROUPS of CB candidates (blockIdx.y, strided): with all candidates
@@ -800,7 +826,9 @@ __global__ __launch_bounds__(256) void dec_backproject(
 // agent-scope release writes the XCD's L2 back: the fused version ran 4x slower)
 __global__ __launch_bounds__(256) void dec_finalize(const Cand* __restrict__ cands, const Stats* __restrict__ stats,
                                                     const int* __restrict__ n_cand, cv_decode_params prm,
-                                                    char* result, int M) {
+                                                    char* result, int M, int64_t ks_ws, int64_t result_stride) {
+    cands = cat_ws(cands, ks_ws, blockIdx.y); stats = cat_ws(stats, ks_ws, blockIdx.y); n_cand = cat_ws(n_cand, ks_ws, blockIdx.y);
+    result += (int64_t)blockIdx.y * result_stride;
     __shared__ int s_scan[256];
     finalize_block(cands, stats, n_cand[0], n_cand[1], prm, result, M, s_scan);
 }
@@ -808,7 +836,9 @@ __global__ __launch_bounds__(256) void dec_finalize(const Cand* __restrict__ can
 // optional: replay the zeroing on the real grid (the reference mutates grid_obj in place)
 __global__ __launch_bounds__(256) void dec_apply(float* __restrict__ g_obj, Geo geo,
                                                  cv_decode_params prm, const Cand* __restrict__ cands,
-                                                 const int* __restrict__ n_cand) {
+                                                 const int* __restrict__ n_cand, CatStride ks) {
+    g_obj = g_obj + (int64_t)blockIdx.y * ks.cells;
+    cands = cat_ws(cands, ks.ws, blockIdx.y); n_cand = cat_ws(n_cand, ks.ws, blockIdx.y);
     const int k = blockIdx.x;
     if (k >= *n_cand) return;
     const Cand& cd = cands[k];
@@ -833,6 +863,12 @@ __global__ __launch_bounds__(256) void dec_apply(float* __restrict__ g_obj, Geo 
                        (float)(z - cd.c[2]) * geo.res, cd.cs, cd.sn, cd.sc, w0, w1, w2))
             g_obj[((int64_t)x * geo.Y + y) * geo.Z + z] = 0.f;
     }
+}
+
+// the counters of K workspace carves zeroed in one launch (16 words each)
+__global__ __launch_bounds__(64) void dec_zero_counters(unsigned* __restrict__ counters, int64_t ks_ws) {
+    counters = cat_ws(counters, ks_ws, blockIdx.y);
+    if (threadIdx.x < 16) counters[threadIdx.x] = 0u;
 }
 
 struct WsLayout {
@@ -914,16 +950,12 @@ int cv_decode_f32(float* d_grid_obj, const float* d_grid_rot, const float* d_gri
 
 }  // extern "C"
 
-int cv_decode_f32_ev(float* d_grid_obj, const float* d_grid_rot, const float* d_grid_scale,
-                     const int dims[3], const float h_corner3[3], float res, const float* d_points,
-                     const float* d_xyz, const float* d_prob, const int32_t* d_class, int64_t n,
-                     const cv_decode_params* params, int mutate_grid, void* d_ws, size_t ws_bytes,
-                     int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes,
-                     float* h_boxes, float* h_scores, int32_t* h_classes, int* h_truncated, void* stream, void* ev_done) {
-    CV_REQUIRE(d_grid_obj && d_grid_rot && d_grid_scale && dims && h_corner3 && d_points && d_xyz &&
-                   d_prob && d_class && params && d_ws && h_n_cand && h_cand_idx && h_verdict &&
-                   h_n_boxes && h_boxes && h_scores && h_classes,
-               CV_EINVAL, "null pointer argument");
+// K categories (K = 1: cv_decode_f32).  Validation is the caller's; category k's host outputs at k, k * M, k * M * 24.
+static int decode_cats(float* d_grid_obj, const float* d_grid_rot, const float* d_grid_scale, const int dims[3],
+                       const float h_corner3[3], float res, const float* d_points, const float* d_xyz, const float* d_prob,
+                       const int32_t* d_class, int64_t n, int K, const cv_decode_params* params, int mutate_grid, void* d_ws,
+                       size_t ws_bytes, int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes, float* h_boxes,
+                       float* h_scores, int32_t* h_classes, int* h_truncated, hipStream_t st, void* ev_done) {
     CV_REQUIRE(n > 0, CV_EINVAL, "n must be positive");
     CV_REQUIRE(res > 0.f, CV_EINVAL, "res must be positive");
     CV_REQUIRE(dims[0] > 0 && dims[1] > 0 && dims[2] > 0, CV_EINVAL, "bad grid dims");
@@ -937,8 +969,8 @@ int cv_decode_f32_ev(float* d_grid_obj, const float* d_grid_rot, const float* d_
     // threshold <= 0 it never ends
     CV_REQUIRE(params->thresh_high > 0.f, CV_EINVAL, "thresh_high must be positive");
     const WsLayout W(G, M);
-    CV_REQUIRE(ws_bytes >= W.total, CV_ENOMEM, "workspace too small (%zu < %zu)", ws_bytes, W.total);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t need = (size_t)K * W.total;
+    CV_REQUIRE(ws_bytes >= need, CV_ENOMEM, "workspace too small (%zu < %zu)", ws_bytes, need);
     char* ws = static_cast<char*>(d_ws);
     List L;
     L.idx = reinterpret_cast<int*>(ws + W.off_list_idx);
@@ -952,19 +984,24 @@ int cv_decode_f32_ev(float* d_grid_obj, const float* d_grid_rot, const float* d_
     Cand* cands = reinterpret_cast<Cand*>(ws + W.off_cands);
     Stats* stats = reinterpret_cast<Stats*>(ws + W.off_stats);
     const ResultLayout RL(M);
-    char* host = g_pinned.take(RL.total);
-    CV_REQUIRE(host != nullptr, CV_ENOMEM, "pinned host buffer of %zu bytes", RL.total);
+    char* host = g_pinned.take((size_t)K * RL.total);
+    CV_REQUIRE(host != nullptr, CV_ENOMEM, "pinned host buffer of %zu bytes", (size_t)K * RL.total);
     const size_t host_cap = PinnedPool::cap_of_last;
     struct Giveback {
         char* p; size_t cap;
         ~Giveback() { g_pinned.give(p, cap); }
     } giveback{host, host_cap};
+    const CatStride ks{K > 1 ? (int64_t)W.total : 0, n, G};
 
-    CV_HIP_CHECK(hipMemsetAsync(ws + W.off_counters, 0, 64, st));
+    if (K == 1) CV_HIP_CHECK(hipMemsetAsync(ws + W.off_counters, 0, 64, st));
+    else {
+        dec_zero_counters<<<dim3(1, K), 64, 0, st>>>(list_n, ks.ws);
+        CV_LAUNCH_CHECK();
+    }
     Geo geo{dims[0], dims[1], dims[2], {h_corner3[0], h_corner3[1], h_corner3[2]}, res};
     const int cblocks = (int)std::min<int64_t>((G + 255) / 256, 2048);
-    dec_compact<<<cblocks, 256, 0, st>>>(d_grid_obj, d_grid_rot, d_grid_scale, geo, G, params->thresh_high, L,
-                                         list_n);
+    dec_compact<<<dim3(cblocks, K), 256, 0, st>>>(d_grid_obj, d_grid_rot, d_grid_scale, geo, G, params->thresh_high, L,
+                                                  list_n, ks);
     CV_LAUNCH_CHECK();
     // the list length is only known on the device: the LDS-resident walker takes lists up to GREEDY_CAP, longer ones
     // the same code over the global arrays - both are launched, the one that does not apply returns at once
@@ -975,34 +1012,86 @@ int cv_decode_f32_ev(float* d_grid_obj, const float* d_grid_rot, const float* d_
     // 0.198 ms in the timed region, 0.163 against 0.147 alone, no change of the scene rate; what round 5 read as "decode takes
     // 4-14 x longer under load" was the host's wake-up behind the stream wait, inside the stage's event pair - the event now sits
     // in front of the wait)
-    if (G > big_cells) dec_greedy_dispatch_big<<<1, GREEDY_T_BIG, 0, st>>>(geo, *params, L, list_n, cands, stats, n_cand);
-    else dec_greedy_dispatch<<<1, GREEDY_T, 0, st>>>(geo, *params, L, list_n, cands, stats, n_cand);
+    if (G > big_cells)
+        dec_greedy_dispatch_big<<<dim3(1, K), GREEDY_T_BIG, 0, st>>>(geo, *params, L, list_n, cands, stats, n_cand, ks.ws);
+    else dec_greedy_dispatch<<<dim3(1, K), GREEDY_T, 0, st>>>(geo, *params, L, list_n, cands, stats, n_cand, ks.ws);
     CV_LAUNCH_CHECK();
     // candidate groups of 8 over blockIdx.y (the count is only known on the device: groups beyond it return at once)
-    const dim3 bgrid((unsigned)((n + 255) / 256), (unsigned)std::min((M + 7) / 8, 8));
+    const dim3 bgrid((unsigned)((n + 255) / 256), (unsigned)std::min((M + 7) / 8, 8), (unsigned)K);
     dec_backproject<<<bgrid, 256, 0, st>>>(
-        d_points, d_xyz, d_prob, d_class, n, params->prob_thresh, cands, n_cand, stats);
+        d_points, d_xyz, d_prob, d_class, n, params->prob_thresh, cands, n_cand, stats, ks);
     CV_LAUNCH_CHECK();
-    dec_finalize<<<1, 256, 0, st>>>(cands, stats, n_cand, *params, host, M);
+    dec_finalize<<<dim3(1, K), 256, 0, st>>>(cands, stats, n_cand, *params, host, M, ks.ws, (int64_t)RL.total);
     CV_LAUNCH_CHECK();
     if (mutate_grid) {
-        dec_apply<<<M, 256, 0, st>>>(d_grid_obj, geo, *params, cands, n_cand);
+        dec_apply<<<dim3(M, K), 256, 0, st>>>(d_grid_obj, geo, *params, cands, n_cand, ks);
         CV_LAUNCH_CHECK();
     }
     if (ev_done) CV_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(ev_done), st));
     CV_HIP_CHECK(hipStreamSynchronize(st));
-    const int* hdr = reinterpret_cast<const int*>(host);
-    const int nc = hdr[0], nb = hdr[1];
-    CV_REQUIRE(nc >= 0 && nc <= M && nb >= 0 && nb <= nc, CV_ERANGE, "corrupt decode result");
-    *h_n_cand = nc;
-    *h_n_boxes = nb;
-    if (h_truncated) *h_truncated = hdr[2];
-    std::memcpy(h_cand_idx, host + RL.off_cand, sizeof(int64_t) * nc);
-    std::memcpy(h_verdict, host + RL.off_verdict, sizeof(int32_t) * nc);
-    std::memcpy(h_boxes, host + RL.off_boxes, sizeof(float) * 24 * nb);
-    std::memcpy(h_scores, host + RL.off_scores, sizeof(float) * nb);
-    std::memcpy(h_classes, host + RL.off_classes, sizeof(int32_t) * nb);
+    for (int k = 0; k < K; ++k) {
+        const char* hk = host + (size_t)k * RL.total;
+        const int* hdr = reinterpret_cast<const int*>(hk);
+        const int nc = hdr[0], nb = hdr[1];
+        CV_REQUIRE(nc >= 0 && nc <= M && nb >= 0 && nb <= nc, CV_ERANGE, "corrupt decode result");
+        h_n_cand[k] = nc;
+        h_n_boxes[k] = nb;
+        if (h_truncated) h_truncated[k] = hdr[2];
+        std::memcpy(h_cand_idx + (size_t)k * M, hk + RL.off_cand, sizeof(int64_t) * nc);
+        std::memcpy(h_verdict + (size_t)k * M, hk + RL.off_verdict, sizeof(int32_t) * nc);
+        std::memcpy(h_boxes + (size_t)k * M * 24, hk + RL.off_boxes, sizeof(float) * 24 * nb);
+        std::memcpy(h_scores + (size_t)k * M, hk + RL.off_scores, sizeof(float) * nb);
+        std::memcpy(h_classes + (size_t)k * M, hk + RL.off_classes, sizeof(int32_t) * nb);
+    }
     return CV_OK;
 }
 
+int cv_decode_f32_ev(float* d_grid_obj, const float* d_grid_rot, const float* d_grid_scale,
+                     const int dims[3], const float h_corner3[3], float res, const float* d_points,
+                     const float* d_xyz, const float* d_prob, const int32_t* d_class, int64_t n,
+                     const cv_decode_params* params, int mutate_grid, void* d_ws, size_t ws_bytes,
+                     int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes,
+                     float* h_boxes, float* h_scores, int32_t* h_classes, int* h_truncated, void* stream, void* ev_done) {
+    CV_REQUIRE(d_grid_obj && d_grid_rot && d_grid_scale && dims && h_corner3 && d_points && d_xyz &&
+                   d_prob && d_class && params && d_ws && h_n_cand && h_cand_idx && h_verdict &&
+                   h_n_boxes && h_boxes && h_scores && h_classes,
+               CV_EINVAL, "null pointer argument");
+    return decode_cats(d_grid_obj, d_grid_rot, d_grid_scale, dims, h_corner3, res, d_points, d_xyz, d_prob, d_class, n, 1, params,
+                       mutate_grid, d_ws, ws_bytes, h_n_cand, h_cand_idx, h_verdict, h_n_boxes, h_boxes, h_scores, h_classes,
+                       h_truncated, static_cast<hipStream_t>(stream), ev_done);
+}
 
+// (C++ linkage, cv_common.h) the scene call's K-category decode with its "decode done" event
+int cv_decode_cat_f32_ev(float* d_grid_obj, const float* d_grid_rot, const float* d_grid_scale, const int dims[3],
+                         const float h_corner3[3], float res, const float* d_points, const float* d_xyz, const float* d_prob,
+                         const int32_t* d_class, int64_t n, int num_cats, const cv_decode_params* params, int mutate_grid,
+                         void* d_ws, size_t ws_bytes, int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes,
+                         float* h_boxes, float* h_scores, int32_t* h_classes, int* h_truncated, void* stream, void* ev_done) {
+    CV_REQUIRE(num_cats >= 1 && num_cats <= CV_MAX_CATEGORIES, CV_EINVAL, "num_cats out of range (%d, 1..%d)", num_cats,
+               CV_MAX_CATEGORIES);
+    CV_REQUIRE(d_grid_obj && d_grid_rot && d_grid_scale && dims && h_corner3 && d_points && d_xyz && d_prob && params && d_ws &&
+                   h_n_cand && h_cand_idx && h_verdict && h_n_boxes && h_boxes && h_scores && h_classes,
+               CV_EINVAL, "null pointer argument");
+    return decode_cats(d_grid_obj, d_grid_rot, d_grid_scale, dims, h_corner3, res, d_points, d_xyz, d_prob, d_class, n, num_cats,
+                       params, mutate_grid, d_ws, ws_bytes, h_n_cand, h_cand_idx, h_verdict, h_n_boxes, h_boxes, h_scores,
+                       h_classes, h_truncated, static_cast<hipStream_t>(stream), ev_done);
+}
+
+extern "C" {
+
+size_t cv_decode_cat_workspace_bytes(const int dims[3], int64_t n, int max_iters, int num_cats) {
+    if (num_cats < 1 || num_cats > CV_MAX_CATEGORIES) return 0;
+    return (size_t)num_cats * cv_decode_workspace_bytes(dims, n, max_iters);
+}
+
+int cv_decode_cat_f32(float* d_grid_obj, const float* d_grid_rot, const float* d_grid_scale, const int dims[3],
+                      const float h_corner3[3], float res, const float* d_points, const float* d_xyz, const float* d_prob,
+                      const int32_t* d_class, int64_t n, int num_cats, const cv_decode_params* params, int mutate_grid, void* d_ws,
+                      size_t ws_bytes, int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes, float* h_boxes,
+                      float* h_scores, int32_t* h_classes, int* h_truncated, void* stream) {
+    return cv_decode_cat_f32_ev(d_grid_obj, d_grid_rot, d_grid_scale, dims, h_corner3, res, d_points, d_xyz, d_prob, d_class, n,
+                                num_cats, params, mutate_grid, d_ws, ws_bytes, h_n_cand, h_cand_idx, h_verdict, h_n_boxes, h_boxes,
+                                h_scores, h_classes, h_truncated, stream, nullptr);
+}
+
+}  // extern "C"

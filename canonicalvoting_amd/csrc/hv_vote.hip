@@ -244,10 +244,26 @@ constexpr int LIST_CHUNK_RECORDS = 1024;     // records of one y-bin per work-li
 constexpr int PREP_MAX_Y = 4096;
 constexpr int PREP_THREADS = 1024;
 
+// Category axis (cv_hv_forward_cat_f32): launch dimension y is the category.  Every category has its own workspace carve
+// with the layout of category 0's (records, counters, lists, partials), `ws` bytes behind the previous one, its predictions
+// `n` points and its grids `cells` cells behind the previous category's.  The scan points, the grid origin and shape and
+// the rotation table are shared.  K = 1 (cv_hv_forward_f32) has blockIdx.y = 0: every offset is zero.
+struct CatStride { int64_t ws, n, cells; };
+template <class T>
+__device__ __forceinline__ T* cat_ws(T* p, int64_t bytes) {
+    return (T*)((const char*)p + (int64_t)blockIdx.y * bytes);
+}
+template <class T>
+__device__ __forceinline__ T* cat_el(T* p, int64_t elems) {
+    return p + (int64_t)blockIdx.y * elems;
+}
+
 __global__ __launch_bounds__(PREP_THREADS) void hv_prep_count(
     const float* __restrict__ pts, const float* __restrict__ xyz, const float* __restrict__ scl,
-    int64_t n, float res, float corner_y, int Y, int* __restrict__ fy_out, int* __restrict__ ycount) {
+    int64_t n, float res, float corner_y, int Y, int* __restrict__ fy_out, int* __restrict__ ycount, CatStride ks) {
     __shared__ int lh[PREP_MAX_Y];
+    xyz = cat_el(xyz, 3 * ks.n); scl = cat_el(scl, 3 * ks.n);
+    fy_out = cat_ws(fy_out, ks.ws); ycount = cat_ws(ycount, ks.ws);
     const bool use_lds = Y <= PREP_MAX_Y;
     if (use_lds) {
         for (int i = threadIdx.x; i < Y; i += PREP_THREADS) lh[i] = 0;
@@ -301,7 +317,10 @@ __global__ __launch_bounds__(256) void hv_prep_scan(const int* __restrict__ ycou
                                                     int* __restrict__ cursor,
                                                     int* __restrict__ part_start, int4* __restrict__ q_info, int max_q,
                                                     int* __restrict__ chunk_start, int* __restrict__ bin_of_chunk,
-                                                    int part_records) {
+                                                    int part_records, int64_t ks_ws) {
+    ycount = cat_ws(ycount, ks_ws); ystart = cat_ws(ystart, ks_ws); cursor = cat_ws(cursor, ks_ws);
+    part_start = cat_ws(part_start, ks_ws); q_info = cat_ws(q_info, ks_ws);
+    chunk_start = cat_ws(chunk_start, ks_ws); bin_of_chunk = cat_ws(bin_of_chunk, ks_ws);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (wave == 0) {
         const int total = wave_excl_scan(Y, [&](int i) { return ycount[i]; },
@@ -346,8 +365,10 @@ constexpr int REC_F = 13;
 __global__ __launch_bounds__(PREP_THREADS) void hv_prep_scatter(
     const float* __restrict__ pts, const float* __restrict__ xyz, const float* __restrict__ scl,
     const float* __restrict__ obj, const int* __restrict__ fy_in, int64_t n, int Y, float res,
-    F3 corner, int* __restrict__ cursor, float* __restrict__ rec, int64_t rec_stride) {
+    F3 corner, int* __restrict__ cursor, float* __restrict__ rec, int64_t rec_stride, CatStride ks) {
     __shared__ int lh[PREP_MAX_Y];     // per-workgroup count, then the workgroup's base in the bin
+    xyz = cat_el(xyz, 3 * ks.n); scl = cat_el(scl, 3 * ks.n); obj = cat_el(obj, ks.n);
+    fy_in = cat_ws(fy_in, ks.ws); cursor = cat_ws(cursor, ks.ws); rec = cat_ws(rec, ks.ws);
     const bool use_lds = Y <= PREP_MAX_Y;
     const int64_t c = blockIdx.x * (int64_t)PREP_THREADS + threadIdx.x;
     const int fy = c < n ? fy_in[c] : -1;
@@ -447,7 +468,12 @@ __global__ __launch_bounds__(1024) void hv_list_pass(const int* __restrict__ yst
                                                      const float* __restrict__ rec, int64_t rec_stride, int R, int tiles_x,
                                                      int tiles_z, const int* __restrict__ list_ctl, int* __restrict__ list_cnt,
                                                      const int* __restrict__ list_start, int* __restrict__ chunk_off,
-                                                     int2* __restrict__ entries, int* __restrict__ tile_w, int want_lists) {
+                                                     int2* __restrict__ entries, int* __restrict__ tile_w, int want_lists,
+                                                     int64_t ks_ws) {
+    ystart = cat_ws(ystart, ks_ws); chunk_start = cat_ws(chunk_start, ks_ws); bin_of_chunk = cat_ws(bin_of_chunk, ks_ws);
+    rec = cat_ws(rec, ks_ws); list_ctl = cat_ws(list_ctl, ks_ws); list_cnt = cat_ws(list_cnt, ks_ws);
+    list_start = cat_ws(list_start, ks_ws); chunk_off = cat_ws(chunk_off, ks_ws); entries = cat_ws(entries, ks_ws);
+    tile_w = cat_ws(tile_w, ks_ws);
     __shared__ int cnt[LIST_MAX_TILES];
     __shared__ int wsum[FILL ? 1 : LIST_MAX_TILES];
     const int ntiles = tiles_x * tiles_z;
@@ -499,7 +525,8 @@ __global__ __launch_bounds__(1024) void hv_list_pass(const int* __restrict__ yst
 
 // list_ctl[0] = total entries, list_ctl[1] = overflow flag (zeroed by the caller's fill)
 __global__ __launch_bounds__(1024) void hv_list_scan(const int* __restrict__ list_cnt, int Y, int ntiles, long long list_cap,
-                                                     int* __restrict__ list_ctl, int* __restrict__ list_start) {
+                                                     int* __restrict__ list_ctl, int* __restrict__ list_start, int64_t ks_ws) {
+    list_cnt = cat_ws(list_cnt, ks_ws); list_ctl = cat_ws(list_ctl, ks_ws); list_start = cat_ws(list_start, ks_ws);
     __shared__ int s[1024];
     __shared__ long long carry_s;      // 64 bits: a total past 2^31 must raise the overflow flag, not wrap
     if (threadIdx.x == 0) carry_s = 0;
@@ -541,7 +568,8 @@ constexpr int QUEUE_MAX_PARTS = 32;
 
 __global__ __launch_bounds__(1024) void hv_build_queue(const int* __restrict__ tile_w, int Y, int ntiles, int max_items,
                                                        int max_slots, int* __restrict__ list_ctl /*[2] = items*/,
-                                                       int4* __restrict__ items) {
+                                                       int4* __restrict__ items, int64_t ks_ws) {
+    tile_w = cat_ws(tile_w, ks_ws); list_ctl = cat_ws(list_ctl, ks_ws); items = cat_ws(items, ks_ws);
     __shared__ unsigned long long s[1024];
     __shared__ unsigned long long carry_s;
     __shared__ int single_s;
@@ -782,7 +810,12 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
     float* __restrict__ g_scale, unsigned long long* __restrict__ prof,
     const int* __restrict__ list_ctl, const int* __restrict__ list_start, const int* __restrict__ list_cnt,
     const int2* __restrict__ entries, int list_mode /* 1: stream the bins, 2: work lists */,
-    const int4* __restrict__ q_info) {
+    const int4* __restrict__ q_info, CatStride ks) {
+    ystart = cat_ws(ystart, ks.ws); items = cat_ws(items, ks.ws); rec = cat_ws(rec, ks.ws);
+    partials = cat_ws(partials, ks.ws); arrivals = cat_ws(arrivals, ks.ws); list_ctl = cat_ws(list_ctl, ks.ws);
+    list_start = cat_ws(list_start, ks.ws); list_cnt = cat_ws(list_cnt, ks.ws); entries = cat_ws(entries, ks.ws);
+    q_info = cat_ws(q_info, ks.ws);
+    g_obj = cat_el(g_obj, ks.cells); g_rot = cat_el(g_rot, 2 * ks.cells); g_scale = cat_el(g_scale, 3 * ks.cells);
     __shared__ TileShared sh;
     __shared__ int last_flag;
     // VARIANT 4: shader-clock ticks per phase, summed over waves into prof[0..7], prof[8] = waves
@@ -1230,6 +1263,13 @@ __global__ __launch_bounds__(256) void hv_count_votes(
     if (threadIdx.x == 0 && s[0]) atomicAdd(count, (unsigned long long)s[0]);
 }
 
+// the zero-initialised words of K workspace carves in one launch (hipMemsetAsync covers one contiguous range: K of them
+// would make the launch count grow with K)
+__global__ __launch_bounds__(256) void hv_zero_cat(int* __restrict__ base, int64_t words, int64_t ks_ws) {
+    base = cat_ws(base, ks_ws);
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < words; i += (int64_t)gridDim.x * 256) base[i] = 0;
+}
+
 int check_common(const void* a, const void* b, const void* c, int64_t n, float res, int num_rots,
                  const float* corner, const int* dims) {
     CV_REQUIRE(a && b && c && corner && dims, CV_EINVAL, "null pointer argument");
@@ -1394,15 +1434,23 @@ int cv_hv_set_kernel_events(void* ev_start, void* ev_stop) {
     return CV_OK;
 }
 
-int cv_hv_forward_f32(const float* d_points, const float* d_xyz, const float* d_scale,
-                      const float* d_obj, int64_t n, float res, int num_rots,
-                      const float h_corner3[3], const int dims[3], float* d_grid_obj,
-                      float* d_grid_rot, float* d_grid_scale, void* d_ws, size_t ws_bytes, int algo,
-                      void* stream) {
-    int rc = check_common(d_points, d_xyz, d_scale, n, res, num_rots, h_corner3, dims);
-    if (rc) return rc;
-    CV_REQUIRE(d_obj && d_grid_obj && d_grid_rot && d_grid_scale, CV_EINVAL, "null pointer argument");
-    hipStream_t st = static_cast<hipStream_t>(stream);
+// byte distance of two categories' workspace carves (cv_hv_forward_cat_f32); the last category needs only the single carve
+static size_t cat_ws_stride(int64_t n, int num_rots, const int dims[3], int algo) {
+    return cv_align_up(cv_hv_forward_workspace_bytes(n, num_rots, dims, algo), 256);
+}
+
+size_t cv_hv_forward_cat_workspace_bytes(int64_t n, int num_rots, const int dims[3], int algo, int num_cats) {
+    if (!dims || n <= 0 || num_cats < 1 || num_cats > CV_MAX_CATEGORIES) return 0;
+    return (size_t)(num_cats - 1) * cat_ws_stride(n, num_rots, dims, algo) + cv_hv_forward_workspace_bytes(n, num_rots, dims, algo);
+}
+
+// K categories over the same scan points and grid (K = 1: cv_hv_forward_f32).  Category k reads d_xyz / d_scale + 3 n k,
+// d_obj + n k and writes the grids + (1, 2, 3) * cells * k; its workspace carve starts cat_ws_stride() * k bytes into d_ws.
+static int hv_forward_cats(const float* d_points, const float* d_xyz, const float* d_scale, const float* d_obj, int64_t n,
+                           float res, int num_rots, const float h_corner3[3], const int dims[3], float* d_grid_obj,
+                           float* d_grid_rot, float* d_grid_scale, void* d_ws, size_t ws_bytes, int algo, int K,
+                           hipStream_t st) {
+    int rc = CV_OK;
     const float2* tab = nullptr;
     rc = get_rot_table(num_rots, &tab);
     if (rc) return rc;
@@ -1412,23 +1460,30 @@ int cv_hv_forward_f32(const float* d_points, const float* d_xyz, const float* d_
     const int a = pick_algo(algo, n, num_rots, dims);
     if (a == 2) CV_REQUIRE(num_rots <= MAX_R_TILES, CV_EINVAL, "tiles algorithm needs num_rots <= %d", MAX_R_TILES);
     if (a == 1) {
-        CV_HIP_CHECK(hipMemsetAsync(d_grid_obj, 0, sizeof(float) * cells, st));
-        CV_HIP_CHECK(hipMemsetAsync(d_grid_rot, 0, sizeof(float) * cells * 2, st));
-        CV_HIP_CHECK(hipMemsetAsync(d_grid_scale, 0, sizeof(float) * cells * 3, st));
-        const int64_t total = n * num_rots;
-        hv_fwd_direct<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(
-            d_points, d_xyz, d_scale, d_obj, n, num_rots, res, corner, d3, tab, d_grid_obj,
-            d_grid_rot, d_grid_scale);
-        CV_LAUNCH_CHECK();
-        hv_normalise<<<(unsigned)((cells + 255) / 256), 256, 0, st>>>(d_grid_obj, d_grid_rot,
-                                                                     d_grid_scale, cells);
-        CV_LAUNCH_CHECK();
+        // (not the hot path: the categories one after another)
+        for (int k = 0; k < K; ++k) {
+            float* g_obj = d_grid_obj + (int64_t)k * cells;
+            float* g_rot = d_grid_rot + (int64_t)k * cells * 2;
+            float* g_scale = d_grid_scale + (int64_t)k * cells * 3;
+            CV_HIP_CHECK(hipMemsetAsync(g_obj, 0, sizeof(float) * cells, st));
+            CV_HIP_CHECK(hipMemsetAsync(g_rot, 0, sizeof(float) * cells * 2, st));
+            CV_HIP_CHECK(hipMemsetAsync(g_scale, 0, sizeof(float) * cells * 3, st));
+            const int64_t total = n * num_rots;
+            hv_fwd_direct<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(
+                d_points, d_xyz + (int64_t)k * n * 3, d_scale + (int64_t)k * n * 3, d_obj + (int64_t)k * n, n, num_rots, res,
+                corner, d3, tab, g_obj, g_rot, g_scale);
+            CV_LAUNCH_CHECK();
+            hv_normalise<<<(unsigned)((cells + 255) / 256), 256, 0, st>>>(g_obj, g_rot, g_scale, cells);
+            CV_LAUNCH_CHECK();
+        }
         return CV_OK;
     }
     // (sized by the SAME algo value that decides the launch shape below: ablation algo 23 takes the streaming launch on
     // grids where algo 2 would take the work queue, and the two carve different workspaces)
-    CV_REQUIRE(d_ws && ws_bytes >= cv_hv_forward_workspace_bytes(n, num_rots, dims, algo == 23 ? 23 : 2), CV_ENOMEM,
+    const int ws_algo = algo == 23 ? 23 : 2;
+    CV_REQUIRE(d_ws && ws_bytes >= cv_hv_forward_cat_workspace_bytes(n, num_rots, dims, ws_algo, K), CV_ENOMEM,
                "workspace too small for the tiles algorithm");
+    const CatStride ks{K > 1 ? (int64_t)cat_ws_stride(n, num_rots, dims, ws_algo) : 0, n, cells};
     const int Y = dims[1];
     CvCarver cv(d_ws);
     int* fy = cv.take<int>(n);
@@ -1461,38 +1516,46 @@ int cv_hv_forward_f32(const float* d_points, const float* d_xyz, const float* d_
     const int list_mode = queue ? 2 : 1;
     // (the streaming launch only needs ycount and the arrival counters zeroed)
     int* zero_from = queue ? list_ctl : ycount;
-    CV_HIP_CHECK(hipMemsetAsync(zero_from, 0, (size_t)(reinterpret_cast<char*>(arrivals + (size_t)Y * ntiles) -
-                                                       reinterpret_cast<char*>(zero_from)), st));
-    hv_prep_count<<<(unsigned)((n + PREP_THREADS - 1) / PREP_THREADS), PREP_THREADS, 0, st>>>(
-        d_points, d_xyz, d_scale, n, res, corner.y, Y, fy, ycount);
+    const size_t zero_bytes = (size_t)(reinterpret_cast<char*>(arrivals + (size_t)Y * ntiles) - reinterpret_cast<char*>(zero_from));
+    if (K == 1) CV_HIP_CHECK(hipMemsetAsync(zero_from, 0, zero_bytes, st));
+    else {
+        hv_zero_cat<<<dim3((unsigned)std::min<size_t>((zero_bytes / 4 + 255) / 256, 1024), K), 256, 0, st>>>(zero_from, zero_bytes / 4,
+                                                                                                        ks.ws);
+        CV_LAUNCH_CHECK();
+    }
+    const unsigned prep_wgs = (unsigned)((n + PREP_THREADS - 1) / PREP_THREADS);
+    hv_prep_count<<<dim3(prep_wgs, K), PREP_THREADS, 0, st>>>(d_points, d_xyz, d_scale, n, res, corner.y, Y, fy, ycount, ks);
     CV_LAUNCH_CHECK();
-    hv_prep_scan<<<1, 256, 0, st>>>(ycount, Y, ystart, cursor, part_start, q_info, (int)max_q, chunk_start, bin_of_chunk,
-                                    (int)(t_part_records > 0 ? t_part_records : g_part_records.load(std::memory_order_relaxed)));
+    hv_prep_scan<<<dim3(1, K), 256, 0, st>>>(ycount, Y, ystart, cursor, part_start, q_info, (int)max_q, chunk_start, bin_of_chunk,
+                                             (int)(t_part_records > 0 ? t_part_records : g_part_records.load(std::memory_order_relaxed)),
+                                             ks.ws);
     CV_LAUNCH_CHECK();
-    hv_prep_scatter<<<(unsigned)((n + PREP_THREADS - 1) / PREP_THREADS), PREP_THREADS, 0, st>>>(
-        d_points, d_xyz, d_scale, d_obj, fy, n, Y, res, corner, cursor, rec, n);
+    hv_prep_scatter<<<dim3(prep_wgs, K), PREP_THREADS, 0, st>>>(d_points, d_xyz, d_scale, d_obj, fy, n, Y, res, corner, cursor, rec,
+                                                                 n, ks);
     CV_LAUNCH_CHECK();
     if (queue) {
-        hv_list_pass<false><<<(unsigned)max_chunks, 1024, 0, st>>>(ystart, chunk_start, bin_of_chunk, Y, rec, n, num_rots, tiles_x,
-                                                               tiles_z, list_ctl, list_cnt, list_start, chunk_off, entries, tile_w, 1);
+        hv_list_pass<false><<<dim3((unsigned)max_chunks, K), 1024, 0, st>>>(ystart, chunk_start, bin_of_chunk, Y, rec, n, num_rots,
+                                                                             tiles_x, tiles_z, list_ctl, list_cnt, list_start,
+                                                                             chunk_off, entries, tile_w, 1, ks.ws);
         CV_LAUNCH_CHECK();
-        hv_build_queue<<<1, 1024, 0, st>>>(tile_w, Y, ntiles, (int)max_items, (int)max_slots, list_ctl, items);
+        hv_build_queue<<<dim3(1, K), 1024, 0, st>>>(tile_w, Y, ntiles, (int)max_items, (int)max_slots, list_ctl, items, ks.ws);
         CV_LAUNCH_CHECK();
-        hv_list_scan<<<1, 1024, 0, st>>>(list_cnt, Y, ntiles, list_cap, list_ctl, list_start);
+        hv_list_scan<<<dim3(1, K), 1024, 0, st>>>(list_cnt, Y, ntiles, list_cap, list_ctl, list_start, ks.ws);
         CV_LAUNCH_CHECK();
-        hv_list_pass<true><<<(unsigned)max_chunks, 1024, 0, st>>>(ystart, chunk_start, bin_of_chunk, Y, rec, n, num_rots, tiles_x,
-                                                              tiles_z, list_ctl, list_cnt, list_start, chunk_off, entries, tile_w, 1);
+        hv_list_pass<true><<<dim3((unsigned)max_chunks, K), 1024, 0, st>>>(ystart, chunk_start, bin_of_chunk, Y, rec, n, num_rots,
+                                                                            tiles_x, tiles_z, list_ctl, list_cnt, list_start,
+                                                                            chunk_off, entries, tile_w, 1, ks.ws);
         CV_LAUNCH_CHECK();
     }
     const int64_t wgs = queue ? max_items : max_q * ntiles;
     CV_REQUIRE(wgs < (1ll << 31), CV_EINVAL, "grid too large");
 #define CV_TILES_ARGS num_rots, res, corner, d3, tab, ystart, items, rec, n, tiles_x, tiles_z, partials, arrivals, d_grid_obj, \
-                      d_grid_rot, d_grid_scale, prof, list_ctl, list_start, list_cnt, entries, list_mode, q_info
+                      d_grid_rot, d_grid_scale, prof, list_ctl, list_start, list_cnt, entries, list_mode, q_info, ks
 #define CV_TILES_LAUNCH(V)                                                                                   \
     do {                                                                                                     \
         if (t_ev_start) CV_HIP_CHECK(hipEventRecord(t_ev_start, st));                                         \
-        if (queue) hv_fwd_tiles<V, true><<<(unsigned)wgs, TW * 64, 0, st>>>(CV_TILES_ARGS);                   \
-        else hv_fwd_tiles<V, false><<<(unsigned)wgs, TW * 64, 0, st>>>(CV_TILES_ARGS);                        \
+        if (queue) hv_fwd_tiles<V, true><<<dim3((unsigned)wgs, K), TW * 64, 0, st>>>(CV_TILES_ARGS);          \
+        else hv_fwd_tiles<V, false><<<dim3((unsigned)wgs, K), TW * 64, 0, st>>>(CV_TILES_ARGS);               \
         if (t_ev_stop) CV_HIP_CHECK(hipEventRecord(t_ev_stop, st));                                           \
     } while (0)
     unsigned long long* prof = nullptr;
@@ -1522,6 +1585,30 @@ int cv_hv_forward_f32(const float* d_points, const float* d_xyz, const float* d_
 #undef CV_TILES_ARGS
     CV_LAUNCH_CHECK();
     return CV_OK;
+}
+
+int cv_hv_forward_f32(const float* d_points, const float* d_xyz, const float* d_scale,
+                      const float* d_obj, int64_t n, float res, int num_rots,
+                      const float h_corner3[3], const int dims[3], float* d_grid_obj,
+                      float* d_grid_rot, float* d_grid_scale, void* d_ws, size_t ws_bytes, int algo,
+                      void* stream) {
+    int rc = check_common(d_points, d_xyz, d_scale, n, res, num_rots, h_corner3, dims);
+    if (rc) return rc;
+    CV_REQUIRE(d_obj && d_grid_obj && d_grid_rot && d_grid_scale, CV_EINVAL, "null pointer argument");
+    return hv_forward_cats(d_points, d_xyz, d_scale, d_obj, n, res, num_rots, h_corner3, dims, d_grid_obj, d_grid_rot, d_grid_scale,
+                           d_ws, ws_bytes, algo, 1, static_cast<hipStream_t>(stream));
+}
+
+int cv_hv_forward_cat_f32(const float* d_points, const float* d_xyz, const float* d_scale, const float* d_obj, int64_t n,
+                          float res, int num_rots, const float h_corner3[3], const int dims[3], int num_cats, float* d_grid_obj,
+                          float* d_grid_rot, float* d_grid_scale, void* d_ws, size_t ws_bytes, int algo, void* stream) {
+    CV_REQUIRE(num_cats >= 1 && num_cats <= CV_MAX_CATEGORIES, CV_EINVAL, "num_cats out of range (%d, 1..%d)", num_cats,
+               CV_MAX_CATEGORIES);
+    int rc = check_common(d_points, d_xyz, d_scale, n, res, num_rots, h_corner3, dims);
+    if (rc) return rc;
+    CV_REQUIRE(d_obj && d_grid_obj && d_grid_rot && d_grid_scale, CV_EINVAL, "null pointer argument");
+    return hv_forward_cats(d_points, d_xyz, d_scale, d_obj, n, res, num_rots, h_corner3, dims, d_grid_obj, d_grid_rot, d_grid_scale,
+                           d_ws, ws_bytes, algo, num_cats, static_cast<hipStream_t>(stream));
 }
 
 int cv_hv_backward_f32(const float* d_grad_obj, const float* d_points, const float* d_xyz,

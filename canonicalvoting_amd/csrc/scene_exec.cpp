@@ -256,4 +256,183 @@ int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream
     return CV_OK;
 }
 
+// eval_separate.py:162-264 as one call: the coordinate plan once, the K programs on it one after another (one shared arena:
+// they are ordered on the stream), K heads into [K][n] arrays, ONE vote and ONE decode over the category axis, NMS per category.
+int cv_detect_scene_separate_f32(const cv_scene_separate_desc* d, cv_scene_separate_result* r, void* stream) {
+    CV_REQUIRE(d && r, CV_EINVAL, "null scene descriptor / result");
+    std::memset(r, 0, sizeof(*r));
+    const int K = d->num_models;
+    CV_REQUIRE(K >= 1 && K <= CV_MAX_CATEGORIES, CV_EINVAL, "num_models out of range (%d, 1..%d)", K, CV_MAX_CATEGORIES);
+    CV_REQUIRE(d->d_coords4 && d->d_feats && d->d_points && d->n > 0 && d->ops && d->n_ops && d->bufs && d->n_bufs && d->d_out_feats,
+               CV_EINVAL, "bad scene descriptor");
+    for (int k = 0; k < K; ++k)
+        CV_REQUIRE(d->ops[k] && d->bufs[k] && d->n_ops[k] > 0 && d->n_bufs[k] > 0 && d->d_out_feats[k], CV_EINVAL,
+                   "bad program or output buffer of model %d", k);
+    CV_REQUIRE(d->out_ld >= d->out_channels && d->out_channels >= 8, CV_EINVAL, "bad network output buffer");
+    CV_REQUIRE(d->h_pinned && d->pinned_bytes >= 64 + 64 * (size_t)K && d->d_ws, CV_EINVAL,
+               "pinned scratch (>= 64 + 64 K bytes) and a device workspace are required");
+    CV_REQUIRE(d->h_boxes && d->h_scores && d->h_cand_idx && d->h_verdict && d->h_det_cat && d->h_det_box && d->max_candidates > 0,
+               CV_EINVAL, "null result arrays");
+    CV_REQUIRE(!!d->d_xyz_in == !!d->d_scale_in && !!d->d_xyz_in == !!d->d_prob_in, CV_EINVAL, "predictions: all three or none");
+    CV_REQUIRE(d->conv_split_target >= 0 && d->vote_part_records >= 0, CV_EINVAL, "negative launch sizing");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long long n = d->n;
+    const int NL = 5;
+    SceneCount in_flight(false, d->conv_split_target, d->vote_part_records);
+    Carver cv(d->d_ws, d->ws_bytes);
+    auto mark = [&](int i) { return d->events[i] ? hipEventRecord(static_cast<hipEvent_t>(d->events[i]), st) : hipSuccess; };
+    auto t_prev = std::chrono::steady_clock::now();
+    auto lap = [&](int i) {
+        const auto t = std::chrono::steady_clock::now();
+        r->host_us[i] += std::chrono::duration<float, std::micro>(t - t_prev).count();
+        t_prev = t;
+    };
+    CV_HIP_CHECK(mark(0));
+
+    // ---- bounds + coordinate plan, exactly as cv_detect_scene_f32 (one plan for all K models)
+    float* h_minmax = static_cast<float*>(d->h_pinned);
+    int32_t* h_flags = reinterpret_cast<int32_t*>(static_cast<char*>(d->h_pinned) + 64);     // 16 words per model
+    void* mm_ws = cv.take<char>(cv_hv_minmax_workspace_bytes());
+    const long long cap = cv_sp_table_capacity(n);
+    const size_t words = cv_sp_scene_plan_words(n, d->stem_k, d->mask_groups, d->masked_min_rows);
+    const size_t o_perm = 0, o_inv = up64((size_t)n);
+    size_t o_coords[NL], o_vals[NL];
+    for (int i = 0; i < NL; ++i) o_coords[i] = o_inv + up64((size_t)n) + (size_t)i * up64(4 * (size_t)n);
+    for (int i = 0; i < NL; ++i) o_vals[i] = o_coords[NL - 1] + up64(4 * (size_t)n) + (size_t)i * up64((size_t)cap);
+    const size_t o_counts = o_vals[NL - 1] + up64((size_t)cap), o_arena = o_counts + 64;
+    int32_t* ibuf = cv.take<int32_t>(o_arena + words);
+    unsigned long long* kbuf = cv.take<unsigned long long>((size_t)NL * (size_t)cap);
+    const size_t sws_b = cv_sp_sort_workspace_bytes(n), lws_b = cv_sp_levels_workspace_bytes(n);
+    char* sort_ws = cv.take<char>(sws_b);
+    char* lev_ws = cv.take<char>(lws_b);
+    float* xyz = cv.take<float>((size_t)K * n * 3);
+    float* scale = cv.take<float>((size_t)K * n * 3);
+    float* prob = cv.take<float>((size_t)K * n);
+    int32_t* d_flags = cv.take<int32_t>(16 * (size_t)K);
+    const size_t fixed_end = cv.off;
+    if (!mm_ws || !ibuf || !kbuf || !sort_ws || !lev_ws || !xyz || !scale || !prob || !d_flags) {
+        r->needed_ws_bytes = fixed_end * 2 + ((size_t)256 << 20);
+        CV_REQUIRE(false, CV_ENOMEM, "scene workspace too small (needs at least %zu bytes)", r->needed_ws_bytes);
+    }
+    if (d->use_range_flag) CV_HIP_CHECK(hipMemsetAsync(d_flags, 0, sizeof(int32_t) * 16 * K, st));
+    int rc = cv_hv_minmax_async_ex(d->d_points, n, h_minmax, mm_ws, cv_hv_minmax_workspace_bytes(), nullptr,
+                                   reinterpret_cast<int32_t*>(sort_ws), stream);
+    if (rc != CV_OK) return rc;
+    int32_t* c_coords[NL];
+    unsigned long long* c_keys[NL];
+    int32_t* c_vals[NL];
+    for (int i = 0; i < NL; ++i) {
+        c_coords[i] = ibuf + o_coords[i];
+        c_keys[i] = kbuf + (size_t)cap * i;
+        c_vals[i] = ibuf + o_vals[i];
+    }
+    int32_t counts_h[8] = {0};
+    cv_scene_maps off;
+    rc = cv_sp_scene_plan_ex(d->d_coords4, n, ibuf + o_perm, ibuf + o_inv, c_coords, c_keys, c_vals, cap, ibuf + o_counts, counts_h,
+                             d->stem_k, d->mask_groups, d->masked_min_rows, ibuf + o_arena, words, &off, sort_ws, sws_b, lev_ws, lws_b,
+                             true, stream, true);
+    if (rc != CV_OK) return rc;
+    r->duplicates = counts_h[5];
+    r->out_of_window = counts_h[6];
+    CV_REQUIRE(counts_h[5] == 0 && counts_h[6] == 0, CV_EINVAL,
+               "duplicate coordinates (%d) or coordinates outside the 16-bit key window (%d)", counts_h[5], counts_h[6]);
+    lap(0);
+    long long rows[NL];
+    for (int i = 0; i < NL; ++i) { rows[i] = counts_h[i]; r->level_rows[i] = counts_h[i]; }
+    float mn[3], mx[3];
+    for (int k = 0; k < 3; ++k) { mn[k] = h_minmax[k]; mx[k] = h_minmax[3 + k]; r->corner[k] = mn[k]; }
+    int dims[3];
+    rc = cv_hv_grid_dims_f32(mn, mx, d->res, dims);
+    if (rc != CV_OK) return rc;
+    for (int k = 0; k < 3; ++k) r->dims[k] = dims[k];
+    const size_t cells = (size_t)dims[0] * dims[1] * dims[2];
+
+    // ---- what depends on the level sizes and the grid shape: one arena (the largest of the K programs'), K vote / decode carves
+    size_t arena_b = 0;
+    for (int k = 0; k < K; ++k) arena_b = std::max(arena_b, cv_net_arena_bytes(d->bufs[k], d->n_bufs[k], rows, NL));
+    size_t conv_ws_b = 0;
+    for (int i = 0; i < NL; ++i) {
+        if (off.mask_perm[i] >= 0) conv_ws_b = std::max(conv_ws_b, (size_t)4 * d->mask_groups * (size_t)rows[i] * d->max_channels + 256);
+        conv_ws_b = std::max(conv_ws_b, cv_sp_conv_workspace_bytes(std::min<long long>(rows[i], 128 * 384 - 1), d->max_channels, 27));
+    }
+    conv_ws_b += 16384 + 256;
+    const size_t vote_ws_b = cv_hv_forward_cat_workspace_bytes(n, d->num_rots, dims, d->vote_algo, K);
+    const size_t dec_ws_b = cv_decode_cat_workspace_bytes(dims, n, d->max_candidates, K);
+    char* arena = cv.take<char>(arena_b);
+    char* conv_ws = cv.take<char>(conv_ws_b);
+    char* vote_ws = cv.take<char>(std::max<size_t>(vote_ws_b, 256));
+    char* dec_ws = cv.take<char>(dec_ws_b);
+    float* grids = cv.take<float>(6 * cells * (size_t)K);
+    r->needed_ws_bytes = cv.off + 4096;
+    CV_REQUIRE(arena && conv_ws && vote_ws && dec_ws && grids, CV_ENOMEM, "scene workspace too small (needs %zu bytes)", r->needed_ws_bytes);
+    float* g_obj = grids;
+    float* g_rot = grids + cells * K;
+    float* g_scale = grids + 3 * cells * K;
+    r->d_grid_obj = g_obj; r->d_grid_rot = g_rot; r->d_grid_scale = g_scale;
+
+    // ---- K network programs on the shared plan (slot layout as cv_detect_scene_f32)
+    const int32_t* ap = ibuf + o_arena;
+    const int32_t* maps[15];
+    maps[0] = ap + off.stem;
+    for (int i = 0; i < 4; ++i) maps[1 + i] = ap + off.down[i];
+    for (int i = 0; i < 5; ++i) maps[5 + i] = ap + off.k3[i];
+    for (int i = 0; i < 4; ++i) maps[10 + i] = ap + off.up[i];
+    maps[14] = ibuf + o_inv;
+    const int32_t* perms[9];
+    for (int i = 0; i < 5; ++i) perms[i] = (off.mask_perm[i] >= 0 && rows[i] >= d->masked_min_rows) ? ap + off.mask_perm[i] : nullptr;
+    for (int i = 0; i < 4; ++i) perms[5 + i] = ap + off.up_perm[i];
+    for (int k = 0; k < K; ++k) {
+        const void* ext_ptr[2] = {d->d_feats, d->d_out_feats[k]};
+        const int ext_ld[2] = {d->feats_ld, d->out_ld};
+        rc = cv_net_run_f32(d->ops[k], d->n_ops[k], d->bufs[k], d->n_bufs[k], rows, NL, arena, arena_b, ext_ptr, ext_ld, maps, 15, perms,
+                            9, conv_ws, conv_ws_b, d->use_range_flag ? d_flags + 16 * k : nullptr, stream);
+        if (rc != CV_OK) return rc;
+    }
+    lap(1);
+    CV_HIP_CHECK(mark(1));
+    for (int k = 0; k < K; ++k) {
+        rc = cv_head_separate_f32(d->d_out_feats[k], n, d->out_ld, d->log_scale, xyz + (size_t)k * n * 3, scale + (size_t)k * n * 3,
+                                  prob + (size_t)k * n, stream);
+        if (rc != CV_OK) return rc;
+    }
+    if (d->use_range_flag) CV_HIP_CHECK(hipMemcpyAsync(h_flags, d_flags, sizeof(int32_t) * 16 * K, hipMemcpyDeviceToHost, st));
+    r->d_xyz = xyz; r->d_scale = scale; r->d_prob = prob;
+    CV_HIP_CHECK(mark(2));
+
+    // ---- one vote and one decode over the category axis
+    const float* v_xyz = d->d_xyz_in ? d->d_xyz_in : xyz;
+    const float* v_scale = d->d_xyz_in ? d->d_scale_in : scale;
+    const float* v_prob = d->d_xyz_in ? d->d_prob_in : prob;
+    rc = cv_hv_forward_cat_f32(d->d_points, v_xyz, v_scale, v_prob, n, d->res, d->num_rots, mn, dims, K, g_obj, g_rot, g_scale, vote_ws,
+                               std::max<size_t>(vote_ws_b, 256), d->vote_algo, stream);
+    if (rc != CV_OK) return rc;
+    CV_HIP_CHECK(mark(3));
+    lap(2);
+    cv_decode_params prm = d->decode;
+    prm.max_iters = d->max_candidates;
+    const int M = d->max_candidates;
+    std::vector<int32_t> classes((size_t)K * M);
+    rc = cv_decode_cat_f32_ev(g_obj, g_rot, g_scale, dims, mn, d->res, d->d_points, v_xyz, v_prob, nullptr, n, K, &prm, 0, dec_ws,
+                              dec_ws_b, r->n_cand, d->h_cand_idx, d->h_verdict, r->n_boxes, d->h_boxes, d->h_scores, classes.data(),
+                              r->truncated, stream, d->events[4]);
+    if (rc != CV_OK) return rc;
+    // (the decode waited for the stream: the range flags of the K programs have landed)
+    if (d->use_range_flag)
+        for (int k = 0; k < K; ++k) r->range_flag |= h_flags[16 * k] ? (1 << k) : 0;
+
+    // ---- NMS per category (eval_separate.py): detections in category order, highest score first within a category
+    int n_det = 0;
+    std::vector<int32_t> pick((size_t)M);
+    for (int k = 0; k < K; ++k) {
+        const int nb = r->n_boxes[k];
+        if (nb == 0) continue;
+        const int kept = cv_nms_obb(d->h_boxes + (size_t)k * M * 24, d->h_scores + (size_t)k * M, nb, d->nms_threshold, pick.data());
+        if (kept < 0) return kept;
+        for (int j = 0; j < kept; ++j) { d->h_det_cat[n_det] = k; d->h_det_box[n_det] = pick[(size_t)j]; ++n_det; }
+    }
+    r->n_det = n_det;
+    lap(3);
+    return CV_OK;
+}
+
 }  // extern "C"

@@ -87,6 +87,67 @@ def decode_boxes(grid_obj, grid_rot, grid_scale, scan_points, xyz_pred, prob_pre
                 cand_idx=cand[:m].copy(), verdict=verdict[:m].copy(), truncated=bool(truncated.value))
 
 
+def decode_boxes_categories(grid_obj, grid_rot, grid_scale, scan_points, xyz_pred, prob_pred, res, class_pred=None,
+                            corner=None, thresh_high=thresh_high, thresh_low=thresh_low, valid_ratio=valid_ratio,
+                            elimination=elimination, prob_thresh=0.3, err_thresh=0.3, separate_variant=False,
+                            max_candidates=512, mutate_grid=False, allow_truncation=False):
+    """decode_boxes over K categories with ONE host sync (cv_decode_cat_f32): grids [K,X,Y,Z] (+[2], [3]) as
+    hv_cuda.forward_categories returns them, xyz_pred [K,N,3], prob_pred [K,N], scan_points [N,3]; ``class_pred`` [N]
+    shared by the categories, None = class 0 everywhere (separate mode, eval_separate.py:195-264).  Returns a list of K
+    dicts, entry k exactly what decode_boxes returns for category k alone (same keys, same truncation rule: a walk that
+    fills ``max_candidates`` with a live cell >= thresh_high is redone with eight times the room)."""
+    L = _lib.lib()
+    dev = grid_obj.device
+    for t, name in ((grid_obj, "grid_obj"), (grid_rot, "grid_rot"), (grid_scale, "grid_scale"),
+                    (scan_points, "scan_points"), (xyz_pred, "xyz_pred"), (prob_pred, "prob_pred")):
+        if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32:
+            raise RuntimeError("%s must be a contiguous float32 CUDA tensor" % name)
+    K, n = grid_obj.shape[0], scan_points.shape[0]
+    if grid_obj.dim() != 4 or tuple(xyz_pred.shape) != (K, n, 3) or tuple(prob_pred.shape) != (K, n):
+        raise RuntimeError("expected grid_obj [K,X,Y,Z], xyz_pred [K,N,3] and prob_pred [K,N]")
+    cls = None if class_pred is None else class_pred.to(torch.int32).contiguous()
+    if corner is None:
+        corner = hv_cuda.recent_corner(grid_obj)            # set by hv_cuda.forward_categories (same points)
+    if corner is None:
+        corner, _, _ = hv_cuda.grid_geometry(scan_points, float(res))
+    dims = (ctypes.c_int * 3)(*grid_obj.shape[1:])
+    p = _lib.DecodeParams(float(thresh_high), float(thresh_low), float(valid_ratio),
+                          int(elimination), float(prob_thresh), 0 if separate_variant else 1,
+                          int(max_candidates), float(err_thresh))
+    M = int(max_candidates)
+    while True:
+        p.max_iters = M
+        ws = _lib.scratch(dev, "decode", L.cv_decode_cat_workspace_bytes(dims, n, M, K))
+        n_cand, n_boxes, truncated = np.zeros(K, np.int32), np.zeros(K, np.int32), np.zeros(K, np.int32)
+        cand = np.zeros((K, M), np.int64)
+        verdict = np.zeros((K, M), np.int32)
+        boxes = np.zeros((K, M, 8, 3), np.float32)
+        scores = np.zeros((K, M), np.float32)
+        classes = np.zeros((K, M), np.int32)
+        with torch.cuda.device(dev):
+            rc = L.cv_decode_cat_f32(
+                _ptr(grid_obj), _ptr(grid_rot), _ptr(grid_scale), dims,
+                (ctypes.c_float * 3)(*[float(v) for v in corner]), ctypes.c_float(float(res)),
+                _ptr(scan_points), _ptr(xyz_pred), _ptr(prob_pred), None if cls is None else _ptr(cls), n, K,
+                ctypes.byref(p), 1 if mutate_grid else 0, _ptr(ws), ws.numel(), n_cand.ctypes.data_as(_lib.c_int_p),
+                cand.ctypes.data_as(_lib.c_i64_p), verdict.ctypes.data_as(_lib.c_i32_p),
+                n_boxes.ctypes.data_as(_lib.c_int_p), boxes.ctypes.data_as(_lib.c_float_p),
+                scores.ctypes.data_as(_lib.c_float_p), classes.ctypes.data_as(_lib.c_i32_p),
+                truncated.ctypes.data_as(_lib.c_int_p), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        _lib.check(rc, "cv_decode_cat_f32")
+        if not truncated.any() or allow_truncation:
+            break
+        if M >= 65536 or mutate_grid:
+            raise RuntimeError("decode_boxes_categories: more than %d candidate cells >= thresh_high (max_candidates)" % M)
+        M = min(M * 8, 65536)
+    out = []
+    for k in range(K):
+        b, m = int(n_boxes[k]), int(n_cand[k])
+        out.append(dict(boxes=boxes[k, :b].copy(), scores=scores[k, :b].copy(), classes=classes[k, :b].copy(),
+                        cand_idx=cand[k, :m].copy(), verdict=verdict[k, :m].copy(), truncated=bool(truncated[k])))
+    return out
+
+
 def get_iou_obb(bbox1, bbox2):
     """utils/calc_map.py:6-21 on two [8,3] corner arrays."""
     a = np.ascontiguousarray(bbox1, np.float32)

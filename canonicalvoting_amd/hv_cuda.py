@@ -4,6 +4,8 @@
         -> [grid_obj[X,Y,Z], grid_rot[X,Y,Z,2], grid_scale[X,Y,Z,3]]      (hv_cuda.cpp:30-45)
     backward(grad_grid, points, xyz_labels, scale_labels, obj_labels, res, num_rots)
         -> [d_xyz_labels, d_scale_labels, d_obj_labels]                    (hv_cuda.cpp:47-71)
+    forward_categories(points, xyz[K,N,3], scale[K,N,3], obj[K,N], res, num_rots)
+        -> [K,...] grids: K separate-mode categories in one launch sequence (no reference counterpart)
 
 Same argument meaning, same input checks and messages (``"<name> must be a CUDA tensor"``,
 ``"<name> must be contiguous"``, hv_cuda.cpp:26-28), same fresh writable outputs on the inputs'
@@ -220,6 +222,45 @@ def forward(points, xyz_labels, scale_labels, obj_labels, res, num_rots, corners
                                        _ptr(ws), ws.numel(), _algo, _stream(dev)),
                    "cv_hv_forward_f32")
     # remember the grid origin of this grid so the decode that follows does not reduce the points again
+    _remember_corner(grid_obj, mn)
+    return [grid_obj, grid_rot, grid_scale]
+
+
+def forward_categories(points, xyz_labels, scale_labels, obj_labels, res, num_rots):
+    """K categories' votes over the same scan points in ONE launch sequence (cv_hv_forward_cat_f32; separate mode,
+    eval_separate.py:166-186): xyz_labels / scale_labels [K,N,3], obj_labels [K,N] -> [grid_obj[K,X,Y,Z],
+    grid_rot[K,X,Y,Z,2], grid_scale[K,X,Y,Z,3]].  Category k is bit for bit forward(points, xyz_labels[k], ...).
+    ``res`` / ``num_rots`` are 0-dim tensors (as forward takes them) or numbers."""
+    for t, name in ((points, "points"), (xyz_labels, "xyz_labels"), (scale_labels, "scale_labels"), (obj_labels, "obj_labels")):
+        _check_input(t, name)
+        if t.dtype != torch.float32:
+            raise RuntimeError("%s must be float32 (got %s)" % (name, t.dtype))
+    n = points.shape[0]
+    if xyz_labels.dim() != 3:
+        raise RuntimeError("expected xyz_labels / scale_labels [K,N,3] and obj_labels [K,N]")
+    K = xyz_labels.shape[0]
+    if points.dim() != 2 or points.shape[1] != 3 or xyz_labels.shape != (K, n, 3) or scale_labels.shape != (K, n, 3) \
+            or obj_labels.shape != (K, n):
+        raise RuntimeError("expected points [N,3], xyz_labels / scale_labels [K,N,3] and obj_labels [K,N]")
+    if n == 0:
+        raise RuntimeError("hv_cuda: cannot vote with zero points")
+    res_v = _scalar(res, "f") if torch.is_tensor(res) else float(res)
+    nrot = _scalar(num_rots, "i") if torch.is_tensor(num_rots) else int(num_rots)
+    L = _lib.lib()
+    dev = points.device
+    mn, _, dims = grid_geometry(points, res_v)
+    X, Y, Z = dims
+    grid_obj = torch.empty((K, X, Y, Z), dtype=torch.float32, device=dev)
+    grid_rot = torch.empty((K, X, Y, Z, 2), dtype=torch.float32, device=dev)
+    grid_scale = torch.empty((K, X, Y, Z, 3), dtype=torch.float32, device=dev)
+    cdims = (ctypes.c_int * 3)(*dims)
+    wsb = L.cv_hv_forward_cat_workspace_bytes(n, nrot, cdims, _algo, K)
+    ws = _lib.scratch(dev, "hv_forward", wsb)
+    with torch.cuda.device(dev):
+        _lib.check(L.cv_hv_forward_cat_f32(_ptr(points), _ptr(xyz_labels), _ptr(scale_labels), _ptr(obj_labels), n,
+                                           ctypes.c_float(res_v), nrot, _f3(mn), cdims, K, _ptr(grid_obj), _ptr(grid_rot),
+                                           _ptr(grid_scale), _ptr(ws), ws.numel(), _algo, _stream(dev)),
+                   "cv_hv_forward_cat_f32")
     _remember_corner(grid_obj, mn)
     return [grid_obj, grid_rot, grid_scale]
 

@@ -150,6 +150,140 @@ def detect_scene_separate(models, hv, coords4, feats, res, log_scale=True, overl
     return out
 
 
+def _separate_by_calls(hv, scan_points, xyz, scale, prob, res, categories, overlap_threshold=0.3, **decode_kw):
+    """vote + decode + NMS of detect_scene_separate on given per-category predictions ([K,N,3], [K,N,3], [K,N])"""
+    zeros_cls = torch.zeros(scan_points.shape[0], dtype=torch.int32, device=scan_points.device)
+    out = []
+    for k, category in enumerate(categories):
+        with torch.no_grad():
+            g = hv(scan_points, xyz[k].contiguous(), scale[k].contiguous(), prob[k].contiguous())
+        raw = decode.decode_boxes(g[0], g[1], g[2], scan_points, xyz[k].contiguous(), prob[k].contiguous(), zeros_cls, res,
+                                  **decode_kw)
+        for i in decode.nms(raw["boxes"], raw["scores"], overlap_threshold):
+            out.append((category, raw["boxes"][i], float(raw["scores"][i])))
+    return out
+
+
+_sep_hosts = {}
+
+
+def detect_scene_separate_c(models, hv, coords4, feats, res, predictions=None, policy=None, keep=None, events=None,
+                            log_scale=True, overlap_threshold=0.3, max_candidates=512, scan_points=None, **decode_kw):
+    """detect_scene_separate through ONE C call (cv_detect_scene_separate_f32: the coordinate plan once, the K models'
+    programs, K heads, ONE vote and ONE decode over the category axis - one host wait for the decode - and NMS per category;
+    the GIL released for the whole call).  Returns what detect_scene_separate returns, [(category, box[8,3], score)], in the
+    same order and the same bits.  ``predictions`` = (xyz [K,N,3], scale [K,N,3], prob [K,N]) fed to vote + decode instead of
+    the networks'.  A scene with a model's input beyond the fp16 range, or a category whose walk fills ``max_candidates``,
+    is redone by the call-by-call path.  ``keep`` receives the per-model outputs (``y``), the head outputs (``net_pred``),
+    the [K,...] grids, the per-category raw decode (``raw``), dims and corner.  ``events``: five recorded torch.cuda.Event
+    re-recorded at the stage boundaries.  ``policy``: ScenePolicy of this call."""
+    import numpy as np
+    decode_kw.setdefault("separate_variant", True)
+    decode_kw.setdefault("err_thresh", float(np.float32(0.3)))
+    L = _lib.lib()
+    dev = feats.device
+    n = coords4.shape[0]
+    categories = list(models.keys())
+    mods = [models[c] for c in categories]
+    K = len(mods)
+    if not 1 <= K <= _lib.MAX_CATEGORIES:
+        raise ValueError("detect_scene_separate_c: 1..%d models (got %d)" % (_lib.MAX_CATEGORIES, K))
+    if scan_points is None:
+        scan_points = (coords4[:, 1:].to(dev) * res).float().contiguous()
+    pieces = 1 if ME.COMPUTE_DTYPE == "bf16" else mods[0].PIECES
+    progs = [m._program(dev, pieces) for m in mods]
+    cm_cls = ME.CoordinateManager
+    G = cm_cls.MASK_GROUPS if (27 + cm_cls.MASK_GROUPS - 1) // cm_cls.MASK_GROUPS <= 10 else 0
+    coords4 = coords4.to(device=dev, dtype=torch.int32).contiguous()
+    feats = feats.contiguous()
+    ys = [torch.empty((n, m.final.out_channels), dtype=torch.float32, device=dev) for m in mods]
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    M = int(max_candidates)
+    with _scene_lock:
+        host = _sep_hosts.get(key)
+        if host is None or host["M"] < M or host["K"] < K:
+            host = _sep_hosts[key] = dict(
+                M=M, K=K, ws_hint=0, pinned=torch.empty(64 + 64 * _lib.MAX_CATEGORIES, dtype=torch.uint8).pin_memory(),
+                cand=np.zeros((K, M), np.int64), verdict=np.zeros((K, M), np.int32), boxes=np.zeros((K, M, 8, 3), np.float32),
+                scores=np.zeros((K, M), np.float32), det_cat=np.zeros(K * M, np.int32), det_box=np.zeros(K * M, np.int32))
+    Mh = host["M"]
+    vp = ctypes.c_void_p
+    d = _lib.SceneSeparateDesc()
+    d.d_coords4, d.n, d.d_feats, d.feats_ld = vp(coords4.data_ptr()), n, vp(feats.data_ptr()), feats.stride(0)
+    d.d_points, d.res, d.num_rots, d.num_models = vp(scan_points.data_ptr()), float(res), hv_cuda._scalar(hv.num_rots, "i"), K
+    ops = (vp * K)(*[ctypes.cast(p[0], vp) for p in progs])
+    n_ops = (ctypes.c_int * K)(*[len(p[0]) for p in progs])
+    bufs = (vp * K)(*[ctypes.cast(p[1], vp) for p in progs])
+    n_bufs = (ctypes.c_int * K)(*[len(p[1]) for p in progs])
+    outs = (vp * K)(*[y.data_ptr() for y in ys])
+    d.ops, d.n_ops, d.bufs, d.n_bufs = ctypes.cast(ops, vp), ctypes.cast(n_ops, vp), ctypes.cast(bufs, vp), ctypes.cast(n_bufs, vp)
+    d.stem_k, d.mask_groups = mods[0].conv0p1s1.kernel_size, G
+    d.masked_min_rows = policy.masked_min_rows if policy is not None else mods[0].masked_min_rows()
+    if policy is not None:
+        d.conv_split_target, d.vote_part_records = int(policy.conv_split_target), int(policy.vote_part_records)
+    d.max_channels, d.use_range_flag = max(max(m.PLANES) for m in mods), 1 if pieces == 2 else 0
+    d.d_out_feats, d.out_ld, d.out_channels = ctypes.cast(outs, vp), ys[0].stride(0), ys[0].shape[1]
+    d.log_scale = 1 if log_scale else 0
+    if predictions is not None:
+        px, ps, pp = [a.contiguous() for a in predictions]
+        d.d_xyz_in, d.d_scale_in, d.d_prob_in = vp(px.data_ptr()), vp(ps.data_ptr()), vp(pp.data_ptr())
+    d.vote_algo = hv_cuda._algo
+    p = d.decode
+    p.thresh_high = float(decode_kw.get("thresh_high", decode.thresh_high))
+    p.thresh_low = float(decode_kw.get("thresh_low", decode.thresh_low))
+    p.valid_ratio = float(decode_kw.get("valid_ratio", decode.valid_ratio))
+    p.elimination = int(decode_kw.get("elimination", decode.elimination))
+    p.prob_thresh = float(decode_kw.get("prob_thresh", 0.3))
+    p.elim_hi_plus1 = 0 if decode_kw.get("separate_variant", True) else 1
+    p.err_thresh = float(decode_kw.get("err_thresh", 0.3))
+    d.max_candidates, d.nms_threshold = Mh, float(overlap_threshold)
+    if events is not None:
+        for i in range(5):
+            d.events[i] = events[i].cuda_event
+    d.h_pinned, d.pinned_bytes = vp(host["pinned"].data_ptr()), host["pinned"].numel()
+    d.h_cand_idx, d.h_verdict = vp(host["cand"].ctypes.data), vp(host["verdict"].ctypes.data)
+    d.h_boxes, d.h_scores = vp(host["boxes"].ctypes.data), vp(host["scores"].ctypes.data)
+    d.h_det_cat, d.h_det_box = vp(host["det_cat"].ctypes.data), vp(host["det_box"].ctypes.data)
+    r = _lib.SceneSeparateResult()
+    need = max(host["ws_hint"], 64 << 20)
+    for attempt in range(4):
+        ws = _lib.scratch(dev, "scene_call_separate", need)
+        d.d_ws, d.ws_bytes = vp(ws.data_ptr()), ws.numel()
+        with torch.cuda.device(dev):
+            rc = L.cv_detect_scene_separate_f32(ctypes.byref(d), ctypes.byref(r), vp(torch.cuda.current_stream(dev).cuda_stream))
+        if rc == -12 and r.needed_ws_bytes > ws.numel():            # CV_ENOMEM: grow the scratch and run the scene again
+            torch.cuda.current_stream(dev).synchronize()
+            need = int(r.needed_ws_bytes)
+            continue
+        _lib.check(rc, "cv_detect_scene_separate_f32")
+        break
+    else:
+        _lib.check(rc, "cv_detect_scene_separate_f32")
+    host["ws_hint"] = max(host["ws_hint"], int(r.needed_ws_bytes))
+    if r.range_flag or any(r.truncated[k] for k in range(K)):
+        # rare: a convolution input beyond the fp16 range, or more candidate cells than the result arrays hold
+        kw = dict(decode_kw, max_candidates=M)
+        if predictions is None:
+            return detect_scene_separate(models, hv, coords4, feats, res, log_scale=log_scale,
+                                         overlap_threshold=overlap_threshold, **kw)
+        return _separate_by_calls(hv, scan_points, predictions[0], predictions[1], predictions[2], res, categories,
+                                  overlap_threshold, **kw)
+    dets = [(categories[int(c)], host["boxes"][int(c), int(b)].copy(), float(host["scores"][int(c), int(b)]))
+            for c, b in zip(host["det_cat"][:r.n_det], host["det_box"][:r.n_det])]
+    if keep is not None:
+        X, Y, Z = r.dims
+        view = lambda ptr, shape: _device_view(ptr, shape, torch.float32, dev, ws)
+        raw = [dict(boxes=host["boxes"][k, :r.n_boxes[k]].copy(), scores=host["scores"][k, :r.n_boxes[k]].copy(),
+                    cand_idx=host["cand"][k, :r.n_cand[k]].copy(), verdict=host["verdict"][k, :r.n_cand[k]].copy())
+               for k in range(K)]
+        keep.update(y=ys, dims=(X, Y, Z), corner=tuple(r.corner), level_rows=list(r.level_rows), raw=raw,
+                    grids=(view(r.d_grid_obj, (K, X, Y, Z)), view(r.d_grid_rot, (K, X, Y, Z, 2)),
+                           view(r.d_grid_scale, (K, X, Y, Z, 3))),
+                    net_pred=(view(r.d_xyz, (K, n, 3)), view(r.d_scale, (K, n, 3)), view(r.d_prob, (K, n))),
+                    host_us=tuple(r.host_us))
+    return dets
+
+
 class _SceneHost:
     """per-(device, stream) host-side scratch of detect_scene_c: pinned landing words and the result arrays"""
 

@@ -80,6 +80,18 @@ int cv_hv_forward_f32(const float* d_points, const float* d_xyz, const float* d_
                       float* d_grid_rot, float* d_grid_scale, void* d_ws, size_t ws_bytes,
                       int algo, void* stream);
 
+/* Category axis (separate mode, eval_separate.py:166-186: one grid triple per category over the SAME scan points, corner and
+ * grid shape).  K = num_cats categories, 1 <= K <= CV_MAX_CATEGORIES, in one launch sequence whose launch count does not depend
+ * on K: d_xyz / d_scale [K][n][3], d_obj [K][n] in; d_grid_obj [K][X][Y][Z], d_grid_rot [K][X][Y][Z][2],
+ * d_grid_scale [K][X][Y][Z][3] out.  Category k is bit for bit what cv_hv_forward_f32 writes for that category alone
+ * (cv_hv_forward_f32 is the K = 1 case of the same launches).  The workspace is K carves of the single-category size
+ * (cv_hv_forward_cat_workspace_bytes(.., 1) == cv_hv_forward_workspace_bytes).  Asynchronous on `stream`. */
+#define CV_MAX_CATEGORIES 16
+size_t cv_hv_forward_cat_workspace_bytes(int64_t n, int num_rots, const int dims[3], int algo, int num_cats);
+int cv_hv_forward_cat_f32(const float* d_points, const float* d_xyz, const float* d_scale, const float* d_obj, int64_t n,
+                          float res, int num_rots, const float h_corner3[3], const int dims[3], int num_cats, float* d_grid_obj,
+                          float* d_grid_rot, float* d_grid_scale, void* d_ws, size_t ws_bytes, int algo, void* stream);
+
 /* Launch sizing of the vote's streaming launch: records of a plane's two y-bins that one workgroup of a (tile, plane) takes; a
  * plane with more is split over up to 8 workgroups per tile whose partial tiles the last arriver adds (integer sums: the grids
  * are the same bits under every setting).  Default 4096 (or CV_HV_PART_RECORDS) - the fastest kernel for ONE scene in flight;
@@ -145,6 +157,19 @@ int cv_decode_f32(float* d_grid_obj, const float* d_grid_rot, const float* d_gri
                   const cv_decode_params* params, int mutate_grid, void* d_ws, size_t ws_bytes,
                   int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes,
                   float* h_boxes, float* h_scores, int32_t* h_classes, int* h_truncated, void* stream);
+
+/* cv_decode_f32 over K = num_cats categories with ONE host wait (separate mode: each category's grid triple is decoded on
+ * its own, eval_separate.py:195-264).  Grids [K][X][Y][Z] (+[2], [3]) as cv_hv_forward_cat_f32 writes them, d_xyz [K][n][3],
+ * d_prob [K][n]; d_points [n][3] and d_class [n] are shared (d_class NULL: class 0 for every point, as separate mode passes
+ * it).  Per category k the host outputs land at h_n_cand[k], h_n_boxes[k], h_truncated[k] (may be NULL) and the arrays at
+ * k * max_iters entries (h_boxes: k * max_iters * 24 floats): category k is exactly what cv_decode_f32 returns for it
+ * alone.  The greedy walks of the K categories run side by side (one walker workgroup each).  Synchronises once. */
+size_t cv_decode_cat_workspace_bytes(const int dims[3], int64_t n, int max_iters, int num_cats);
+int cv_decode_cat_f32(float* d_grid_obj, const float* d_grid_rot, const float* d_grid_scale, const int dims[3],
+                      const float h_corner3[3], float res, const float* d_points, const float* d_xyz, const float* d_prob,
+                      const int32_t* d_class, int64_t n, int num_cats, const cv_decode_params* params, int mutate_grid, void* d_ws,
+                      size_t ws_bytes, int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes, float* h_boxes,
+                      float* h_scores, int32_t* h_classes, int* h_truncated, void* stream);
 
 /* utils/calc_map.py:6-21 on two [8][3] corner sets (host). */
 double cv_iou_obb(const float* h_box1, const float* h_box2);
@@ -578,6 +603,57 @@ typedef struct cv_scene_result {
     float host_us[4];
 } cv_scene_result;
 int cv_detect_scene_f32(const cv_scene_desc* desc, cv_scene_result* result, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * One call per SEPARATE-mode scene: eval_separate.py:162-264 (K per-category 8-channel models on one scan) behind one entry
+ * point: the coordinate plan once, K network programs (cv_net_run_f32, one after another on the stream, sharing the plan and
+ * one arena), K heads (cv_head_separate_f32), ONE vote over the category axis (cv_hv_forward_cat_f32), ONE decode over it
+ * (cv_decode_cat_f32: one host wait) and NMS per category on the host.  Category k is bit for bit the call-by-call path of
+ * model k.  1 <= num_models <= CV_MAX_CATEGORIES; every field is validated before the first device call.
+ * ------------------------------------------------------------------------ */
+typedef struct cv_scene_separate_desc {
+    const int32_t* d_coords4; long long n;     /* as cv_scene_desc */
+    const float* d_feats; int feats_ld;
+    const float* d_points; float res; int num_rots;
+    int num_models;                            /* K */
+    const cv_net_op* const* ops; const int* n_ops;        /* [K]: program of model k */
+    const cv_net_buf* const* bufs; const int* n_bufs;     /* [K] */
+    int stem_k, mask_groups;
+    long long masked_min_rows;
+    int max_channels;                          /* widest convolution output over the K programs */
+    int use_range_flag;                        /* 1: the programs run on fp16 pairs; result.range_flag bit k reports model k */
+    float* const* d_out_feats;                 /* [K] network outputs [n][out_ld], caller's buffers, caller's row order */
+    int out_ld, out_channels;
+    int log_scale;                             /* head (eval_separate.py:170-181) */
+    /* optional: predictions fed to vote + decode instead of the networks' (NULL = the networks'): [K][n][3], [K][n][3], [K][n] */
+    const float* d_xyz_in; const float* d_scale_in; const float* d_prob_in;
+    int vote_algo;
+    cv_decode_params decode;                   /* max_iters is taken from max_candidates; separate mode: elim_hi_plus1 = 0 */
+    int max_candidates;                        /* per category */
+    double nms_threshold;                      /* eval_separate.py (0.3) */
+    void* d_ws; size_t ws_bytes;               /* grown by the caller to result.needed_ws_bytes after CV_ENOMEM */
+    void* h_pinned; size_t pinned_bytes;       /* >= 64 + 64 * K bytes of page-locked host memory */
+    /* host results, category k at k * max_candidates entries */
+    int64_t* h_cand_idx; int32_t* h_verdict;   /* [K][max_candidates] */
+    float* h_boxes; float* h_scores;           /* [K][max_candidates][8][3], [K][max_candidates] */
+    int32_t* h_det_cat; int32_t* h_det_box;    /* [K * max_candidates]: detection j = box h_det_box[j] of category h_det_cat[j] */
+    void* events[5];                           /* optional: scene start, behind the networks, the heads, the vote, the decode */
+    int conv_split_target, vote_part_records;  /* launch sizing of this call (0 = thread / process-wide), as cv_scene_desc */
+} cv_scene_separate_desc;
+typedef struct cv_scene_separate_result {
+    int n_cand[CV_MAX_CATEGORIES], n_boxes[CV_MAX_CATEGORIES], truncated[CV_MAX_CATEGORIES];
+    int n_det, range_flag, duplicates, out_of_window;     /* range_flag: bit k = model k's input beyond the fp16 range */
+    int dims[3];
+    float corner[3];
+    long long level_rows[5];
+    size_t needed_ws_bytes;
+    /* device views into d_ws, valid until the next call that uses the same scratch: grids [K][X][Y][Z] (+[2], [3]), the networks'
+     * head outputs [K][n][3], [K][n][3], [K][n] */
+    float* d_grid_obj; float* d_grid_rot; float* d_grid_scale;
+    float* d_xyz; float* d_scale; float* d_prob;
+    float host_us[4];                          /* plan + wait, network enqueue, heads + vote enqueue, decode + wait + NMS */
+} cv_scene_separate_result;
+int cv_detect_scene_separate_f32(const cv_scene_separate_desc* desc, cv_scene_separate_result* result, void* stream);
 
 #ifdef __cplusplus
 }
