@@ -2770,6 +2770,11 @@ int cv_sp_conv_f32(const cv_conv_desc* d, void* stream) {
              ((reinterpret_cast<uintptr_t>(d->out) | reinterpret_cast<uintptr_t>(d->residual) |
                reinterpret_cast<uintptr_t>(d->acc_in) | reinterpret_cast<uintptr_t>(d->scale) |
                reinterpret_cast<uintptr_t>(d->shift) | reinterpret_cast<uintptr_t>(d->ws)) & 15) == 0;
+    // the word-by-word epilogues (epilogue_store, conv_finish's scalar branch, conv_finish_scalar) know only fp32 operands:
+    // an hl output or residual needs the float4 epilogues (as an hl input already does, launch_rows)
+    CV_REQUIRE(a.wide || (!d->out_hl && !d->res_hl), CV_EINVAL,
+               "hl-format output / residual: Cout, leading dimensions %% 4 == 0 and 16-byte aligned out, residual, acc_in, "
+               "scale, shift and ws");
     const bool vec = (d->cin % KC == 0) && (d->in_ld % 4 == 0) && (d->cout % 4 == 0) &&
                      ((reinterpret_cast<uintptr_t>(d->in) & 15) == 0) &&
                      ((reinterpret_cast<uintptr_t>(d->weight) & 15) == 0);
@@ -3041,14 +3046,19 @@ static long long wgrad_plan(long long n_out, int cin, int cout, int K, WgradPlan
         }
         // splits per offset class (centre / face / edge+corner of an odd cubic kernel); CV_WGRAD_MULT="c,f,o" overrides (experiment)
         static int m_c = 2, m_f = 2, m_o = 1;
-        static const bool m_env = [] { const char* e = getenv("CV_WGRAD_MULT"); if (e) sscanf(e, "%d,%d,%d", &m_c, &m_f, &m_o); return true; }();
+        static const bool m_env = [] {
+            const char* e = getenv("CV_WGRAD_MULT");
+            if (e) sscanf(e, "%d,%d,%d", &m_c, &m_f, &m_o);
+            m_c = std::max(1, m_c); m_f = std::max(1, m_f); m_o = std::max(1, m_o);      // msum divides below
+            return true;
+        }();
         (void)m_env;
         mult[j] = !cubic ? 1 : d1 == 0 ? m_c : d1 == 1 ? m_f : m_o;
         cls[j] = !cubic ? 2 : d1 == 0 ? 0 : d1 == 1 ? 1 : 2;
         msum += mult[j];
     }
-    static const long long target_tasks = getenv("CV_WGRAD_TASKS") ? atoll(getenv("CV_WGRAD_TASKS")) : WGRAD_TARGET_TASKS;
-    static const long long cap_env = getenv("CV_WGRAD_CAP") ? atoll(getenv("CV_WGRAD_CAP")) : 64;
+    static const long long target_tasks = std::max(1ll, getenv("CV_WGRAD_TASKS") ? atoll(getenv("CV_WGRAD_TASKS")) : WGRAD_TARGET_TASKS);
+    static const long long cap_env = std::max(1ll, getenv("CV_WGRAD_CAP") ? atoll(getenv("CV_WGRAD_CAP")) : 64);
     const long long want = (target_tasks + (long long)msum * tiles - 1) / ((long long)msum * tiles);
     // partial tiles <= 96 MB (they are written once and read once by wgrad_reduce); few-offset kernels (1x1, 2x2x2)
     // have few (offset, block) tasks and get their parallelism from the rows instead: up to 1024 row splits

@@ -308,3 +308,162 @@ def make_state_dict(in_channels=3, out_channels=64, seed=0):
     conv_w("final", 1, PLANES[7], out_channels)
     sd["final.bias"] = 0.1 * torch.randn(1, out_channels, generator=g)
     return sd
+
+
+# ---- float64 convolution with per-element error bounds (tests/test_conv_paths_gpu.py) ---------------------------------
+ERROR_MODEL = """Error model of the HIP convolution paths, per output element e.
+
+The exact result is y64 = sum over the (row, offset, input channel) terms t of x_t * w_t, computed here in float64
+(its own error, ~2^-53 * mag, is far below everything else).  mag[e] = sum |x_t| * |w_t| over the same terms.  A
+path that forms every product to relative accuracy u_prod and adds the products with n_seq fp32 roundings on the way
+to the element (standard first-order model: every rounded addition is off by at most 2^-24 of the partial sums it
+combines, and a partial sum never exceeds mag) stays within
+
+    |got - y64| <= (u_prod + (n_seq + 2) * 2^-24) * mag + floor
+
+n_seq: every matrix-core instruction that accumulates into the element rounds once (the instruction's own k-products
+are summed inside it), so one 32-channel unit (one kernel offset x one 32-channel chunk of the input) costs
+STEPS_PER_UNIT[path] roundings; on top come the additions of the split-K partial tiles (at most SPLIT_CAP = 64, the
+dispatcher's cap) and the finish launch's tree of 4 quarter sums.  Taking the whole offset range's units instead of
+a workgroup's share keeps the count independent of how the dispatcher splits the launch:
+
+    n_seq = STEPS_PER_UNIT[path] * units + SPLIT_CAP + 4,    units = (kernel offsets) * ceil(Cin / 32)
+
+The price of that independence is looseness on split launches at wide Cin: a 27-way split of a 256-channel 3x3x3
+convolution walks about 8 units per workgroup, but the bound charges all 216 (n_seq 2660 instead of about 130 on
+"h2").  Errors that grow linearly with the reduction length - products of fp16 high pieces alone, say - can then fall
+inside the bound at such shapes.  What keeps the tests sensitive is that mag is per element: rows with one or two
+neighbours (isolated voxels, sheet edges, the partial last layer of a box) and narrow inputs (Cin 32, 1x1 kernels)
+have a small mag and a small n_seq, and there one dropped contribution or one missing low piece is far outside the
+bound (tests/test_conv_bound.py shows both at Cin 32).
+
+Per path (u_prod, STEPS_PER_UNIT), from the kernel comments:
+  "f32"   v_mfma_f32_32x32x2_f32, exact fp32 products (conv_rows, the wgrad pieces = 0 mode): u_prod = 0, 16 steps
+  "x6"    bf16 triples x = h + m + l (24 significant bits), six of the nine piece products (sparse_conv.hip, the
+          bf16x6 comment): the representation is exact and the three dropped products are <= 2^-24 relative each,
+          u_prod = 2^-22; six 32x32x16 instructions per 16 channels: 12 steps
+  "h2"    fp16 pairs x = h + l, h = RNE16(x), l = RNE16(x - h) (sparse_conv_common.h): each operand to 2^-24
+          relative, the dropped l*l product <= 2^-22 relative, u_prod = 2^-22; three instructions per 16 channels:
+          6 steps.  Below 2^-14 an activation's pair carries an absolute error of up to 2^-25, hence the floor
+          2^-25 * sum |w_t| (weights are scaled by a power of two into the fp16 range before they are split)
+  "bf16"  the opt-in bf16 mode (pieces = 1): compared with y64 of the bf16-RNE-rounded operands, whose products
+          the matrix core forms exactly: u_prod = 0, two instructions per 32 channels: 2 steps
+An hl-format output stores h + l of the fp32 value: 2^-24 * |y| more, and 2^-25 absolute below 2^-14.
+
+The fused epilogue z = (y + acc_in) * scale + shift + residual is propagated explicitly: |scale| * bound(y) plus three
+roundings of at most 2^-24 * (|y * scale| + |shift| + |residual|) each (and an hl residual's own 2^-24 relative /
+2^-25 absolute).  ReLU is 1-Lipschitz, so |got - relu(z64)| <= bound(z) holds for every element, also where z64 lies
+within the bound of zero (there it only says that |got| is within the bound).
+
+The weight gradient dW[j, ci, co] = sum_u x[nbr[u, j], ci] * dy[u, co] follows the same model with the rows as the
+reduction axis: units of 16 rows (the k of one 32x32x16 instruction; 8 instructions of k = 2 for "f32"), plus the row
+splits of the plan (at most WGRAD_SPLIT_CAP = 1024) and the reduce launch.
+"""
+U24 = 2.0 ** -24
+SPLIT_CAP = 64
+WGRAD_SPLIT_CAP = 1024
+PATHS = {"f32": (0.0, 16), "x6": (2.0 ** -22, 12), "h2": (2.0 ** -22, 6), "bf16": (0.0, 2)}
+WGRAD_STEPS_PER_16_ROWS = {"f32": 8, "x6": 6, "bf16": 1}
+
+
+def bf16_round(a):
+    """float32 array rounded to the nearest bf16 (ties to even), returned as float32"""
+    a = np.ascontiguousarray(a, np.float32)
+    b = a.view(np.uint32).astype(np.uint64)
+    b = (b + 0x7FFF + ((b >> 16) & 1)) & 0xFFFF0000
+    return b.astype(np.uint32).view(np.float32).reshape(a.shape)
+
+
+def conv64(x, w, nbr, j_begin=0, j_end=None):
+    """float64 sparse convolution on any map.  x [N_in, Cin], w [K, Cin, Cout] (or [Cin, Cout]), nbr [N_out, K] (None:
+    K = 1 and the identity map).  Returns (y64, mag, wabs): y64 [N_out, Cout]; mag = sum |x| |w| over the same terms;
+    wabs = sum |w| over the same terms (the fp16-pair floor)."""
+    x = np.asarray(x, np.float64)
+    w = np.asarray(w, np.float64)
+    if w.ndim == 2:
+        w = w[None]
+    if nbr is None:
+        nbr = np.arange(x.shape[0], dtype=np.int64)[:, None]
+    nbr = np.asarray(nbr)
+    j_end = w.shape[0] if j_end is None else j_end
+    n_out, cout = nbr.shape[0], w.shape[2]
+    y = np.zeros((n_out, cout))
+    mag = np.zeros((n_out, cout))
+    wabs = np.zeros((n_out, cout))
+    for j in range(j_begin, j_end):
+        src = nbr[:, j]
+        sel = np.nonzero(src >= 0)[0]
+        if sel.size:
+            xs = x[src[sel]]
+            y[sel] += xs @ w[j]
+            mag[sel] += np.abs(xs) @ np.abs(w[j])
+            wabs[sel] += np.abs(w[j]).sum(0)[None]
+    return y, mag, wabs
+
+
+def conv_bound(mag, wabs, path, units, hl_out=False, y=None):
+    """per-element bound of |got - y64| for a convolution on `path` (see the model above) of `units` 32-channel units"""
+    u_prod, steps = PATHS[path]
+    n_seq = steps * units + SPLIT_CAP + 4
+    b = (u_prod + (n_seq + 2) * U24) * mag
+    if path == "h2":
+        b = b + 2.0 ** -25 * wabs
+    if hl_out:
+        b = b + U24 * np.abs(y) + 2.0 ** -25
+    return b
+
+
+def conv_units(K, cin):
+    return K * ((cin + 31) // 32)
+
+
+def epilogue64(y, b, acc_in=None, b_acc=None, scale=None, shift=None, res=None, res_hl=False, relu=False,
+               hl_out=False):
+    """float64 epilogue z = relu((y + acc_in) * scale + shift + res) with its propagated bound (b: bound of y)"""
+    y = np.asarray(y, np.float64)
+    if acc_in is not None:
+        y = y + acc_in
+        b = b + b_acc + U24 * np.abs(y)
+    sc = np.ones(y.shape[1]) if scale is None else np.asarray(scale, np.float64)
+    sh = np.zeros(y.shape[1]) if shift is None else np.asarray(shift, np.float64)
+    r = np.zeros_like(y) if res is None else np.asarray(res, np.float64)
+    z = y * sc + sh + r
+    bz = np.abs(sc) * b + 3 * U24 * (np.abs(y * sc) + np.abs(sh) + np.abs(r))
+    if res is not None and res_hl:
+        bz = bz + U24 * np.abs(r) + 2.0 ** -25
+    if relu:
+        z = np.maximum(z, 0.0)
+    if hl_out:
+        bz = bz + U24 * np.abs(z) + 2.0 ** -25
+    return z, bz
+
+
+def wgrad64(x, dy, nbr, K):
+    """float64 weight gradient dW [K, Cin, Cout] = sum_u x[nbr[u, j]]^T dy[u] and mag = sum_u |x| |dy|"""
+    x = np.asarray(x, np.float64)
+    dy = np.asarray(dy, np.float64)
+    if nbr is None:
+        nbr = np.arange(dy.shape[0], dtype=np.int64)[:, None]
+    dw = np.zeros((K, x.shape[1], dy.shape[1]))
+    mag = np.zeros_like(dw)
+    for j in range(K):
+        sel = np.nonzero(nbr[:, j] >= 0)[0]
+        if sel.size:
+            xs = x[nbr[sel, j]]
+            dw[j] = xs.T @ dy[sel]
+            mag[j] = np.abs(xs).T @ np.abs(dy[sel])
+    return dw, mag
+
+
+def wgrad_bound(mag, path, n_out):
+    u_prod = PATHS["x6"][0] if path == "x6" else 0.0
+    n_seq = WGRAD_STEPS_PER_16_ROWS[path] * ((n_out + 15) // 16) + WGRAD_SPLIT_CAP + 4
+    return (u_prod + (n_seq + 2) * U24) * mag
+
+
+def within(got, ref, bound):
+    """(ok, worst index, worst excess ratio) of |got - ref| <= bound, element by element"""
+    err = np.abs(np.asarray(got, np.float64) - ref)
+    ratio = err / np.maximum(bound, 1e-300)
+    i = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+    return bool((err <= bound).all()) and bool(np.isfinite(got).all()), i, float(ratio[i])
