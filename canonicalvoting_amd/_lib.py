@@ -163,6 +163,11 @@ SIGNATURES = {
     "cv_sp_build_levels": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
                                           ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, vp,
                                           c_i32_p, vp, ctypes.c_size_t, vp]),
+    "cv_sp_quantize_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "cv_sp_quantize_f32": (ctypes.c_int, [vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_float, ctypes.c_int, c_i64_p,
+                                          ctypes.c_int, vp, vp, vp, vp, c_i32_p, vp, ctypes.c_size_t, vp]),
+    "cv_sp_quantize_f64": (ctypes.c_int, [vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_double, ctypes.c_int, c_i64_p,
+                                          ctypes.c_int, vp, vp, vp, vp, c_i32_p, vp, ctypes.c_size_t, vp]),
     "cv_sp_morton_keys": (ctypes.c_int, [vp, ctypes.c_longlong, vp, vp]),
     "cv_sp_sort_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "cv_sp_sort_rows": (ctypes.c_int, [vp, ctypes.c_longlong, vp, vp, vp, vp, ctypes.c_size_t, vp]),

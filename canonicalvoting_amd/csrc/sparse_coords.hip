@@ -11,7 +11,11 @@
 // first appearance of a child (deterministic, like a sequential insert).  All five levels are
 // built back to back with the level sizes kept ON THE DEVICE; the host reads the four counts
 // with a single copy at the end (one sync per scene).
+// The voxelisation of raw clouds (ME.utils.sparse_quantize on the device, cv_sp_quantize_f32 / _f64: floor(p / q) -> unique
+// voxels in first-point order, bit-reproducible) is the same construction one step earlier; see quantize_insert below.
 #include "cv_common.h"
+
+#include <limits>
 
 namespace {
 
@@ -605,9 +609,226 @@ __global__ __launch_bounds__(SORT_T) void sort_scatter(const unsigned* __restric
     }
 }
 
+// ---- voxelisation of raw point clouds (cv_sp_quantize_f32 / _f64) ---------------------------------------------------
+// The level build one step earlier: key = (cloud, floor(p / q)) -> smallest row, then the rows that find themselves in the
+// table are the first points of their voxels and their rank is the output row - the order of np.sort(np.unique(...,
+// return_index=True)[1]), ME.utils.sparse_quantize.
+//   quantize_insert   voxel of row i, checked BEFORE any conversion to int or table access (a non-finite component or a voxel
+//                     outside the key window: counted, slot -1, never touches the table); key -> min(i).  Consecutive scan
+//                     points often share a voxel: a lane whose key equals its left neighbour's cannot hold the minimum,
+//                     skips the atomics and takes the slot from the first lane of its run.
+//   quantize_flag     row i is first iff vals[slot[i]] == i; the others get their slot stored as -2 - slot (the emit pass
+//                     overwrites the table values, the flags must not be read from them again); block sums.
+//   quantize_emit     rank of a first row = output row: coords4 (unpacked from the stored key), index, vals[slot] := rank;
+//                     the last block writes N.
+//   quantize_inverse  inverse[i] = vals[slot of row i]        (only when asked for)
+// Only atomicMin over row indices and ordered scans decide the outputs: they are bit-reproducible.
+// The quotient is the correctly rounded IEEE division of the input's own precision followed by floor - what numpy computes.
+// No reciprocal, and this file must not be built with -ffast-math / -fno-hip-fp32-correctly-rounded-divide-sqrt.
+constexpr int QUANT_LO = -32704, QUANT_HI = 32703;      // the key window CoordinateManager documents
+struct QuantClouds { int n; int begin[CV_QUANTIZE_MAX_CLOUDS]; };      // first row of every cloud (n == 0: one cloud)
+
+__global__ __launch_bounds__(256) void quantize_clear(unsigned long long* keys, int* vals, long long cap, int* counts) {
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < cap; i += (long long)gridDim.x * 256) {
+        keys[i] = EMPTY_KEY;
+        vals[i] = 0x7fffffff;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 2) counts[threadIdx.x] = 0;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void quantize_insert(const T* __restrict__ pts, long long ld, int m, T q, int floor_only,
+                                                       const QuantClouds clouds, unsigned long long* keys, int* vals,
+                                                       long long mask, int* __restrict__ slots, int* counts) {
+    const int lane = threadIdx.x & 63;
+    const int m_pad = (m + 255) / 256 * 256;            // whole waves stay in the loop (the shuffles need them)
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m_pad; i += gridDim.x * 256) {
+        const bool have = i < m;
+        unsigned long long key = EMPTY_KEY;             // EMPTY_KEY: no voxel (past the end, or rejected)
+        if (have) {
+            const T* p = pts + (long long)i * ld;
+            const T px = p[0], py = p[1], pz = p[2];
+            const T vx = floor_only ? floor(px) : floor(px / q), vy = floor_only ? floor(py) : floor(py / q),
+                    vz = floor_only ? floor(pz) : floor(pz / q);
+            const T lo = (T)QUANT_LO, hi = (T)QUANT_HI;
+            // (comparisons with NaN are false: a NaN quotient is rejected by the window test as well)
+            const bool ok = isfinite(px) && isfinite(py) && isfinite(pz) && vx >= lo && vx <= hi && vy >= lo && vy <= hi &&
+                            vz >= lo && vz <= hi;
+            if (ok) {
+                int b = 0;
+                if (clouds.n > 1) {                      // last cloud whose first row is <= i
+                    int l = 0, h = clouds.n - 1;
+                    while (l < h) {
+                        const int mid = (l + h + 1) >> 1;
+                        if (clouds.begin[mid] <= i) l = mid; else h = mid - 1;
+                    }
+                    b = l;
+                }
+                key = pack_key(b, (int)vx, (int)vy, (int)vz);
+            } else {
+                atomicAdd(counts + 1, 1);
+            }
+        }
+        const bool valid = key != EMPTY_KEY;
+        const unsigned long long left = __shfl_up(key, 1);
+        const bool leader = valid && (lane == 0 || left != key);
+        int slot = -1;
+        if (leader) slot = (int)table_insert_min(keys, vals, mask, key, i);
+        // the other lanes of a run of equal keys: the slot of the run's first lane (the nearest leader at or below this lane)
+        const unsigned long long leaders = __ballot(leader);
+        const unsigned long long below = leaders & (~0ull >> (63 - lane));
+        const int src = below ? 63 - __clzll((long long)below) : lane;
+        const int run_slot = __shfl(slot, src);
+        if (have) slots[i] = valid ? run_slot : -1;
+    }
+}
+
+// rows (blockIdx.x * 1024 + threadIdx.x) * per + [0, per)
+__global__ __launch_bounds__(1024) void quantize_flag(int m, int per, const int* __restrict__ vals, int* __restrict__ slots,
+                                                      int* __restrict__ bsum /*[1024]*/) {
+    __shared__ int s[1024];
+    const long long b0 = ((long long)blockIdx.x * 1024 + threadIdx.x) * per;
+    int sum = 0;
+    for (int j = 0; j < per; ++j)
+        if (b0 + j < m) {
+            const int slot = slots[b0 + j];
+            if (slot >= 0) {
+                if (vals[slot] == (int)(b0 + j)) sum += 1;
+                else slots[b0 + j] = -2 - slot;
+            }
+        }
+    s[threadIdx.x] = sum;
+    __syncthreads();
+    for (int st = 512; st > 0; st >>= 1) {
+        if (threadIdx.x < st) s[threadIdx.x] += s[threadIdx.x + st];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) bsum[blockIdx.x] = s[0];
+}
+
+__global__ __launch_bounds__(1024) void quantize_emit(int m, int per, const unsigned long long* __restrict__ keys,
+                                                      int* __restrict__ vals, const int* __restrict__ slots,
+                                                      const int* __restrict__ bsum, int* __restrict__ coords4,
+                                                      int* __restrict__ index, int* __restrict__ counts) {
+    __shared__ int s[1024];
+    __shared__ int wsum[16];
+    const long long b0 = ((long long)blockIdx.x * 1024 + threadIdx.x) * per;
+    int sum = 0;
+    for (int j = 0; j < per; ++j) sum += (b0 + j < m) && slots[b0 + j] >= 0;
+    int before = (int)threadIdx.x < (int)blockIdx.x ? bsum[threadIdx.x] : 0;       // (at most 1024 blocks)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = before;
+    __syncthreads();
+    int boff = 0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) boff += wsum[w];
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) counts[0] = boff + bsum[blockIdx.x];
+    int run = block_exclusive_scan(sum, s) + boff;
+    for (int j = 0; j < per; ++j) {
+        if (b0 + j >= m) break;
+        const int slot = slots[b0 + j];
+        if (slot >= 0) {
+            const unsigned long long key = keys[slot];
+            reinterpret_cast<int4*>(coords4)[run] =
+                make_int4((int)(key >> 48), (int)((key >> 32) & 0xffff) - 32768, (int)((key >> 16) & 0xffff) - 32768,
+                          (int)(key & 0xffff) - 32768);
+            index[run] = (int)(b0 + j);
+            vals[slot] = run;                            // table now maps voxel key -> output row
+            ++run;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void quantize_inverse(int m, const int* __restrict__ vals, const int* __restrict__ slots,
+                                                        int* __restrict__ inverse) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) {
+        const int s = slots[i];
+        inverse[i] = s == -1 ? -1 : vals[s >= 0 ? s : -2 - s];
+    }
+}
+
 int grid_for(long long n) { return (int)std::min<long long>((n + 255) / 256, 4096); }
 
+template <typename T>
+int quantize_run(const T* d_points, long long m, long long ld, T q, int floor_only, const long long* h_offsets, int n_clouds,
+                 int32_t* d_coords4, int32_t* d_index, int32_t* d_inverse, int32_t* d_counts, int32_t* h_counts, void* d_ws,
+                 size_t ws_bytes, void* stream) {
+    CV_REQUIRE(d_points && d_coords4 && d_index && d_counts && d_ws, CV_EINVAL, "null pointer argument");
+    CV_REQUIRE(m > 0 && m <= (1ll << 29), CV_EINVAL, "bad point count %lld", m);      // (slots and -2 - slot stay in 32 bits)
+    CV_REQUIRE(ld >= 3, CV_EINVAL, "bad row stride %lld", ld);
+    CV_REQUIRE(floor_only || (q > (T)0 && q <= std::numeric_limits<T>::max()), CV_EINVAL,
+               "quantization_size must be positive and finite (got %g)", (double)q);
+    QuantClouds clouds;
+    clouds.n = 0;
+    if (h_offsets) {
+        CV_REQUIRE(n_clouds >= 1 && n_clouds <= CV_QUANTIZE_MAX_CLOUDS, CV_EINVAL, "bad cloud count %d (1..%d)", n_clouds,
+                   CV_QUANTIZE_MAX_CLOUDS);
+        CV_REQUIRE(h_offsets[0] == 0, CV_EINVAL, "batch offsets must start at row 0 (got %lld)", h_offsets[0]);
+        for (int b = 0; b < n_clouds; ++b) {
+            CV_REQUIRE(h_offsets[b] >= 0 && h_offsets[b] <= m, CV_EINVAL, "batch offset %d out of range (%lld, %lld rows)", b,
+                       h_offsets[b], m);
+            CV_REQUIRE(b == 0 || h_offsets[b] >= h_offsets[b - 1], CV_EINVAL, "batch offsets are not sorted (offset %d)", b);
+            clouds.begin[b] = (int)h_offsets[b];
+        }
+        clouds.n = n_clouds;
+    }
+    CV_REQUIRE(ws_bytes >= cv_sp_quantize_workspace_bytes(m), CV_ENOMEM, "workspace too small");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long long cap = cv_sp_table_capacity(m);
+    CvCarver cv(d_ws);
+    unsigned long long* keys = cv.take<unsigned long long>((size_t)cap);
+    int* vals = cv.take<int>((size_t)cap);
+    int* slots = cv.take<int>((size_t)m);
+    int* bsum = cv.take<int>(1024);
+    const int per = (int)((m + (1ll << 20) - 1) >> 20);                 // at most 1024 scan blocks of 1024 threads
+    const int nsb = (int)((m + 1024ll * per - 1) / (1024ll * per));
+    quantize_clear<<<grid_for(cap), 256, 0, st>>>(keys, vals, cap, d_counts);
+    CV_LAUNCH_CHECK();
+    quantize_insert<T><<<grid_for(m), 256, 0, st>>>(d_points, ld, (int)m, q, floor_only, clouds, keys, vals, cap - 1, slots,
+                                                    d_counts);
+    CV_LAUNCH_CHECK();
+    quantize_flag<<<nsb, 1024, 0, st>>>((int)m, per, vals, slots, bsum);
+    CV_LAUNCH_CHECK();
+    quantize_emit<<<nsb, 1024, 0, st>>>((int)m, per, keys, vals, slots, bsum, d_coords4, d_index, d_counts);
+    CV_LAUNCH_CHECK();
+    if (d_inverse) {
+        quantize_inverse<<<grid_for(m), 256, 0, st>>>((int)m, vals, slots, d_inverse);
+        CV_LAUNCH_CHECK();
+    }
+    if (h_counts) {
+        CV_HIP_CHECK(hipMemcpyAsync(h_counts, d_counts, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
+        CV_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    return CV_OK;
+}
+
 }  // namespace
+
+extern "C" {
+
+size_t cv_sp_quantize_workspace_bytes(long long m) {
+    if (m <= 0) return 0;
+    // table keys + values, the table slot of every point, block sums of the scan
+    const size_t cap = (size_t)cv_sp_table_capacity(m);
+    return cv_align_up(cap * 8, 256) + cv_align_up(cap * 4, 256) + cv_align_up((size_t)m * 4, 256) + 4096 + 256;
+}
+
+int cv_sp_quantize_f32(const float* d_points, long long m, long long ld, float quantization_size, int floor_only,
+                       const long long* h_offsets, int n_clouds, int32_t* d_coords4, int32_t* d_index, int32_t* d_inverse,
+                       int32_t* d_counts, int32_t* h_counts, void* d_ws, size_t ws_bytes, void* stream) {
+    return quantize_run<float>(d_points, m, ld, quantization_size, floor_only, h_offsets, n_clouds, d_coords4, d_index,
+                               d_inverse, d_counts, h_counts, d_ws, ws_bytes, stream);
+}
+
+int cv_sp_quantize_f64(const double* d_points, long long m, long long ld, double quantization_size, int floor_only,
+                       const long long* h_offsets, int n_clouds, int32_t* d_coords4, int32_t* d_index, int32_t* d_inverse,
+                       int32_t* d_counts, int32_t* h_counts, void* d_ws, size_t ws_bytes, void* stream) {
+    return quantize_run<double>(d_points, m, ld, quantization_size, floor_only, h_offsets, n_clouds, d_coords4, d_index,
+                                d_inverse, d_counts, h_counts, d_ws, ws_bytes, stream);
+}
+
+}  // extern "C"
 
 int cv_sp_kernel_maps_batch(const CvMapJob* jobs, int n_jobs, void* stream) {
     CV_REQUIRE(jobs && n_jobs > 0 && n_jobs <= CV_MAX_MAP_JOBS, CV_EINVAL, "bad kernel map batch");

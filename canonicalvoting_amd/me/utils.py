@@ -1,5 +1,6 @@
 """``ME.utils`` subset: batched_coordinates (train_joint.py:82), sparse_quantize
-(utils/dataloader.py:197), kaiming_normal_ (utils/resnet.py:112)."""
+(utils/dataloader.py:197, sunrgbd/brnetcanon.py:218; on the device: quantize_device / quantize_batch), kaiming_normal_
+(utils/resnet.py:112)."""
 import math
 
 import numpy as np
@@ -14,27 +15,133 @@ def batched_coordinates(coords, dtype=torch.int32, device=None):
         if c.is_floating_point():
             c = torch.floor(c)
         c = c.to(dtype)
-        out.append(torch.cat([torch.full((c.shape[0], 1), b, dtype=dtype), c], 1))
+        out.append(torch.cat([torch.full((c.shape[0], 1), b, dtype=dtype, device=c.device), c], 1))
     r = torch.cat(out, 0)
     return r.to(device) if device is not None else r
 
 
-def sparse_quantize(coordinates, features=None, labels=None, quantization_size=None, return_index=False,
-                    **_):
-    """floor(coords / quantization_size), one (the first) point per voxel."""
-    c = np.asarray(coordinates)
+def _quantize_host(c, quantization_size, return_inverse=False):
+    """(voxels [M,3] int32, first point of every voxel ascending, inverse or None) - numpy, the reference path"""
     if quantization_size is not None:
         c = np.floor(c / quantization_size)
     c = c.astype(np.int32)
-    _, idx = np.unique(c, axis=0, return_index=True)
-    idx = np.sort(idx)
+    if not return_inverse:
+        _, idx = np.unique(c, axis=0, return_index=True)
+        return c, np.sort(idx), None
+    _, idx, inv = np.unique(c, axis=0, return_index=True, return_inverse=True)
+    order = np.argsort(idx)                      # np.unique's (lexicographic) row -> its place in first-occurrence order
+    rank = np.empty_like(order)
+    rank[order] = np.arange(order.size)
+    return c, idx[order], rank[np.asarray(inv).reshape(-1)]
+
+
+def quantize_device(points, quantization_size=None, offsets=None, return_inverse=False):
+    """Voxelisation on the GPU (cv_sp_quantize_f32 / _f64, on torch's current stream, one host wait for the voxel count).
+
+    points [M, 3] on the device, fp32 or fp64 (other dtypes are computed in fp64, as numpy promotes them), rows may be
+    strided; ``offsets``: first rows of the clouds when the rows are several clouds one after the other (batch index =
+    cloud).  Voxel = floor(p / quantization_size) in the input's precision, floor(p) when quantization_size is None.
+    Returns (coords4 [N, 4] int32 = (batch, x, y, z), index [N] int32 = first point of every voxel, ascending,
+    inverse [M] int32 or None).  Raises RuntimeError when points are non-finite or outside the coordinate window."""
+    import ctypes
+
+    from .. import _lib
+    L = _lib.lib()
+    assert points.is_cuda and points.dim() == 2 and points.shape[1] == 3, "points: a [M, 3] device tensor"
+    if points.dtype not in (torch.float32, torch.float64):
+        points = points.to(torch.float64)
+    if points.stride(1) != 1 or points.stride(0) < 3:
+        points = points.contiguous()
+    dev, m = points.device, points.shape[0]
+    if m == 0:
+        raise RuntimeError("sparse_quantize: empty point cloud")
+    f64 = points.dtype == torch.float64
+    h_off, n_clouds = None, 0
+    if offsets is not None:
+        offsets = [int(o) for o in (offsets.tolist() if hasattr(offsets, "tolist") else offsets)]
+        h_off, n_clouds = (ctypes.c_int64 * len(offsets))(*offsets), len(offsets)
+    coords4 = torch.empty((m, 4), dtype=torch.int32, device=dev)
+    index = torch.empty(m, dtype=torch.int32, device=dev)
+    inverse = torch.empty(m, dtype=torch.int32, device=dev) if return_inverse else None
+    counts_d = torch.empty(2, dtype=torch.int32, device=dev)
+    counts_h = (ctypes.c_int32 * 2)()
+    ws = _lib.scratch(dev, "quantize", int(L.cv_sp_quantize_workspace_bytes(m)))
+    vp = ctypes.c_void_p
+    fn = L.cv_sp_quantize_f64 if f64 else L.cv_sp_quantize_f32
+    q = 0.0 if quantization_size is None else float(np.float64(quantization_size) if f64 else np.float32(quantization_size))
+    with torch.cuda.device(dev):
+        stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
+        _lib.check(fn(vp(points.data_ptr()), m, points.stride(0), q, 1 if quantization_size is None else 0, h_off, n_clouds,
+                      vp(coords4.data_ptr()), vp(index.data_ptr()), vp(inverse.data_ptr()) if return_inverse else None,
+                      vp(counts_d.data_ptr()), counts_h, vp(ws.data_ptr()), ws.numel(), stream),
+                   "cv_sp_quantize_f64" if f64 else "cv_sp_quantize_f32")
+    n, rejected = int(counts_h[0]), int(counts_h[1])
+    if rejected != 0:
+        raise RuntimeError("sparse_quantize: %d points rejected (a non-finite component, or a voxel outside the supported "
+                           "window: spatial coordinates in [-32704, 32703])" % rejected)
+    return coords4[:n], index[:n], inverse
+
+
+def quantize_batch(clouds, quantization_size, return_inverse=False, offsets=None):
+    """Several clouds voxelised by ONE pass: ``clouds`` is a list of [Mi, 3] device tensors, or one [M, 3] tensor with
+    ``offsets`` (first row of every cloud).  Returns coords4 [N, 4] (batch, x, y, z), index [N] (rows of the concatenated
+    clouds) and, with return_inverse, inverse [M] - what sparse_quantize per cloud followed by batched_coordinates gives;
+    equal points of different clouds stay separate voxels."""
+    if torch.is_tensor(clouds):
+        if offsets is None:
+            offsets = [0]
+        pts = clouds
+    else:
+        assert offsets is None, "offsets come with ONE tensor of concatenated clouds"
+        offsets = [0]
+        for c in clouds[:-1]:
+            offsets.append(offsets[-1] + c.shape[0])
+        dt = torch.float64 if any(c.dtype != torch.float32 for c in clouds) else torch.float32
+        pts = torch.cat([c.to(dt) for c in clouds], 0)
+    coords4, index, inverse = quantize_device(pts, quantization_size, offsets, return_inverse)
+    return (coords4, index, inverse) if return_inverse else (coords4, index)
+
+
+def sparse_quantize(coordinates, features=None, labels=None, quantization_size=None, return_index=False,
+                    return_inverse=False, device=None, **_):
+    """floor(coords / quantization_size), one (the first) point per voxel, voxels in the order of their first points.
+
+    numpy in and ``device=None``: numpy out, on the host.  A torch tensor in, or ``device=`` given (sunrgbd/brnetcanon.py:218):
+    torch tensors out - int32 coords [N, 3], features / labels gathered by the first-point index - on ``device``, else on the
+    input's device; a device result is computed by the HIP kernels (quantize_device), a CPU result by the host path.
+    ``return_inverse=True`` appends the map point -> output row as the last element.
+    (quantization_size=None: the host path converts with astype - it truncates towards zero - while the device floors, as
+    MinkowskiEngine does; the two agree on non-negative and on integer-valued coordinates.)"""
+    as_torch = torch.is_tensor(coordinates) or device is not None
+    if as_torch:
+        dev = torch.device(device) if device is not None else coordinates.device
+        if dev.type == "cuda":
+            pts = coordinates if torch.is_tensor(coordinates) else torch.from_numpy(np.ascontiguousarray(coordinates))
+            c4, idx, inv = quantize_device(pts.to(dev), quantization_size, None, return_inverse)
+            c, gi = c4[:, 1:].contiguous(), idx.long()
+            take = lambda a: torch.as_tensor(a).to(dev)[gi]
+        else:
+            c, idx, inv = _quantize_host(coordinates.numpy() if torch.is_tensor(coordinates) else np.asarray(coordinates),
+                                         quantization_size, return_inverse)
+            c, idx = torch.from_numpy(c[idx]), torch.from_numpy(idx.astype(np.int32))
+            inv = torch.from_numpy(inv.astype(np.int32)) if inv is not None else None
+            gi = idx.long()
+            take = lambda a: torch.as_tensor(a)[gi]
+    else:
+        c, idx, inv = _quantize_host(np.asarray(coordinates), quantization_size, return_inverse)
+        c = c[idx]
+        take = lambda a: np.asarray(a)[idx]
     if return_index:
-        return c[idx], idx
-    if features is None:
-        return c[idx]
-    if labels is None:
-        return c[idx], np.asarray(features)[idx]
-    return c[idx], np.asarray(features)[idx], np.asarray(labels)[idx]
+        out = (c, idx)
+    elif features is None:
+        out = (c,)
+    elif labels is None:
+        out = (c, take(features))
+    else:
+        out = (c, take(features), take(labels))
+    if return_inverse:
+        out = out + (inv,)
+    return out[0] if len(out) == 1 else out
 
 
 def kaiming_normal_(tensor, a=0, mode="fan_in", nonlinearity="leaky_relu"):

@@ -417,6 +417,23 @@ def detect_scene_c(model, hv, coords4, feats, res, nclasses=9, log_scale=True, s
     return dets, raw, y
 
 
+def detect_points(model, hv, points, feats, res, predictions=None, return_inverse=False, **kw):
+    """detect_scene_c from a RAW device cloud: ``points`` [M, 3] (fp32 or fp64) are voxelised on the device at ``res``
+    (ME.utils.quantize_device: one point - the first - per voxel), ``feats`` [M, C] and, if given, the raw-point-aligned
+    ``predictions`` (xyz, scale, prob, class) are gathered by the first-point index, and the scene runs as detect_scene_c
+    runs it - world points formed from the integer coordinates - so the results are bit for bit those of quantising on
+    the host and calling detect_scene_c.  Returns detect_scene_c's (detections, raw, network output) plus ``index`` [N]
+    (and ``inverse`` [M] with return_inverse)."""
+    coords4, index, inverse = ME.utils.quantize_device(points, res, None, return_inverse)
+    gi = index.long()
+    dev = coords4.device
+    f = feats.to(dev)[gi]
+    if predictions is not None:
+        predictions = tuple(p.to(dev)[gi].contiguous() for p in predictions)
+    out = detect_scene_c(model, hv, coords4, f, res, predictions=predictions, **kw)
+    return out + ((index, inverse) if return_inverse else (index,))
+
+
 def last_scene_host_us(dev=None):
     """(plan + wait, network enqueue, head + vote enqueue, decode + wait) host microseconds of the calling thread's last
     detect_scene_c call on its current stream"""

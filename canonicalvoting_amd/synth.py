@@ -47,10 +47,10 @@ def _sample_rect(rng, n, origin, u, v):
     return origin[None] + a * u[None] + b * v[None]
 
 
-def make_scene(seed, n_points=80000, res=0.03, room=(5.2, 2.6, 5.2), n_boxes=12,
-               origin_shift=True, margin=1.0, box_scale=1.0):
-    """SURVEY 8d generator: room shell + K oriented boxes on the floor -> exactly n_points voxels."""
-    rng = np.random.default_rng(seed)
+def _scene_sampler(rng, room, n_boxes, margin, box_scale):
+    """layout of a scene (room shell + boxes, drawn from ``rng``) -> (draw, ctr, yaw, half, cls); ``draw(m)`` samples m
+    jittered surface points with their labels and colours.  Shared by make_scene and make_raw_scene: the order of the
+    generator's calls is part of make_scene's output."""
     W, H, D = room
     # --- objects -------------------------------------------------------------
     # Boxes are placed one at a time without overlap (bounding circles in the xz plane):
@@ -129,6 +129,14 @@ def make_scene(seed, n_points=80000, res=0.03, room=(5.2, 2.6, 5.2), n_boxes=12,
                 xyz[sel] = ((pts[sel] - ctr[b][None]) @ _ry(yaw[b])) / half[b][None]
         return pts, xyz, sc, cl, np.clip(rgb, 0, 1)
 
+    return draw, ctr, yaw, half, cls
+
+
+def make_scene(seed, n_points=80000, res=0.03, room=(5.2, 2.6, 5.2), n_boxes=12,
+               origin_shift=True, margin=1.0, box_scale=1.0):
+    """SURVEY 8d generator: room shell + K oriented boxes on the floor -> exactly n_points voxels."""
+    rng = np.random.default_rng(seed)
+    draw, ctr, yaw, half, cls = _scene_sampler(rng, room, n_boxes, margin, box_scale)
     need = n_points
     P, Xl, Sl, Rg = np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 3))
     Cl = np.zeros(0, np.int32)
@@ -161,6 +169,29 @@ def make_scene(seed, n_points=80000, res=0.03, room=(5.2, 2.6, 5.2), n_boxes=12,
                  class_labels=Cl[first].astype(np.int32), boxes=gt.astype(np.float32))
 
 
+@dataclass
+class RawScene:
+    seed: int
+    points: np.ndarray        # [M,3] float64 jittered surface samples (metres), several per voxel
+    feats: np.ndarray         # [M,3] float32 rgb in [0,1]
+    xyz_labels: np.ndarray    # [M,3] float32
+    scale_labels: np.ndarray  # [M,3] float32
+    class_labels: np.ndarray  # [M]   int32, 9 = background
+    boxes: np.ndarray         # [K,8] float32 ground truth
+
+
+def make_raw_scene(seed, n_samples=300000, room=(5.2, 2.6, 5.2), n_boxes=12, margin=1.0, box_scale=1.0):
+    """The raw cloud of a make_scene-style scene BEFORE the unique step: n_samples jittered surface samples with their
+    per-sample rgb and labels (what a scan hands to ME.utils.sparse_quantize / pipeline.detect_points).  Same layout
+    generator as make_scene(seed); deterministic per seed."""
+    rng = np.random.default_rng(seed)
+    draw, ctr, yaw, half, cls = _scene_sampler(rng, room, n_boxes, margin, box_scale)
+    p, x, s, c, g = draw(int(n_samples))
+    gt = np.concatenate([ctr, yaw[:, None], half, cls[:, None].astype(float)], -1)
+    return RawScene(seed=seed, points=p, feats=g.astype(np.float32), xyz_labels=x.astype(np.float32),
+                    scale_labels=s.astype(np.float32), class_labels=c.astype(np.int32), boxes=gt.astype(np.float32))
+
+
 def synth_predictions(scene, seed=None):
     """Per-point network outputs synthesised from the labels (vote/decode-only runs).
 
@@ -168,7 +199,7 @@ def synth_predictions(scene, seed=None):
     background:     xyz ~ U(-1,1)^3,         scale ~ U(0.2,0.8),          prob ~ U(0,0.1)
     Returns xyz[N,3], scale[N,3], prob[N] (float32) and class[N] (int32, in 0..8)."""
     rng = np.random.default_rng(1000003 + (scene.seed if seed is None else seed))
-    n = scene.coords.shape[0]
+    n = scene.class_labels.shape[0]
     is_obj = scene.class_labels != BACKGROUND
     xyz = rng.uniform(-1, 1, (n, 3))
     scale = rng.uniform(0.2, 0.8, (n, 3))

@@ -200,6 +200,32 @@ int cv_sp_build_levels(int32_t* const* d_coords, unsigned long long* const* d_ke
                        int32_t* const* d_vals, long long n, long long cap, int num_levels,
                        int32_t* d_counts, int32_t* h_counts, void* d_ws, size_t ws_bytes, void* stream);
 
+/* Voxelisation of raw point clouds (ME.utils.sparse_quantize, utils/dataloader.py:197, sunrgbd/brnetcanon.py:218): voxel
+ * = floor(p / quantization_size) per component - the correctly rounded quotient in the input's own precision, then floor
+ * (what numpy computes; no reciprocal) - or floor(p) when floor_only != 0 (quantization_size is then ignored).  One
+ * output row per occupied voxel, in the order of each voxel's FIRST point (np.sort of np.unique's return_index):
+ *   d_points  [m][ld] device, the three coordinates in the first columns of a row (ld >= 3, in elements)
+ *   h_offsets host array of n_clouds first rows (h_offsets[0] == 0, non-decreasing, <= m) when the rows are n_clouds
+ *             clouds one after the other - cloud b's rows get batch index b, 1 <= n_clouds <= CV_QUANTIZE_MAX_CLOUDS - or NULL
+ *             (n_clouds ignored): one cloud, batch index 0
+ *   d_coords4 [m][4] int32 (batch, x, y, z), the first N rows written      d_index [m] int32, the first N written:
+ *             row of the first point of each voxel, ascending              d_inverse [m] int32 or NULL: output row of every
+ *             point's voxel (-1 for a rejected point)
+ *   d_counts  int32[2] device: [0] = N, [1] = rejected points.  A point is rejected - counted, kept out of the table and
+ *             of every index computation - when a component is not finite or its voxel lies outside the key window of the
+ *             coordinate manager (spatial coordinates in [-32704, 32703]); callers treat [1] != 0 as an error.
+ *   h_counts  receives the same two ints (one synchronisation of `stream`), or NULL: no host wait.
+ *   d_ws      cv_sp_quantize_workspace_bytes(m) bytes; m <= 2^29.
+ * Every reduction is a minimum over row indices or an ordered scan: the outputs are bit-reproducible, whatever the schedule. */
+#define CV_QUANTIZE_MAX_CLOUDS 256
+size_t cv_sp_quantize_workspace_bytes(long long m);
+int cv_sp_quantize_f32(const float* d_points, long long m, long long ld, float quantization_size, int floor_only,
+                       const long long* h_offsets, int n_clouds, int32_t* d_coords4, int32_t* d_index, int32_t* d_inverse,
+                       int32_t* d_counts, int32_t* h_counts, void* d_ws, size_t ws_bytes, void* stream);
+int cv_sp_quantize_f64(const double* d_points, long long m, long long ld, double quantization_size, int floor_only,
+                       const long long* h_offsets, int n_clouds, int32_t* d_coords4, int32_t* d_index, int32_t* d_inverse,
+                       int32_t* d_counts, int32_t* h_counts, void* d_ws, size_t ws_bytes, void* stream);
+
 /* Spatial row order of a coordinate set (what the fused network runs on; replaces the sort of Morton keys by the
  * caller): stable sort on (batch index, Z-order of the 2^shift cubes), rows of one cube in the caller's order.
  * d_sorted[n][4] = rows in that order, d_perm[n] = original row of each sorted row, d_inv[n] = sorted row of each

@@ -2,10 +2,12 @@
 """eval_joint.py counterpart (reference eval_joint.py:137-312) on synthetic scans: network -> head -> vote ->
 decode -> NMS per scene, then mAP @0.25 / @0.5.  argparse instead of hydra (absent here).
 
-    python scripts/eval_joint.py [--scenes 4] [--points 80000] [--weights joint.pth] [--teacher]
+    python scripts/eval_joint.py [--scenes 4] [--points 80000] [--weights joint.pth] [--teacher] [--raw-points [M]]
 
 --teacher feeds the vote/decode stage with predictions synthesised from the labels (there is no trained
 checkpoint offline); the network forward still runs.
+--raw-points (synthetic scenes only): every scene is a RAW cloud of M surface samples (default 300000) that
+pipeline.detect_points voxelises on the device before the scene runs.
 """
 import argparse
 import os
@@ -21,7 +23,8 @@ from canonicalvoting_amd.data import (ScanNetXYZProbMultiDataset, SyntheticScanD
                                      load_config)
 from canonicalvoting_amd.hough import HoughVoting  # noqa: E402
 from canonicalvoting_amd.minkunet import MinkUNet34C  # noqa: E402
-from canonicalvoting_amd.synth import synth_predictions  # noqa: E402
+from canonicalvoting_amd.data import parse_gt_lines  # noqa: E402
+from canonicalvoting_amd.synth import make_raw_scene, synth_predictions  # noqa: E402
 
 
 def evaluate(model, dataset, res=0.03, teacher=False, nclasses=9, device="cuda"):
@@ -45,6 +48,23 @@ def evaluate(model, dataset, res=0.03, teacher=False, nclasses=9, device="cuda")
     return {thr: calc_map.compute_map(pred_map_cls, gt_map_cls, thr) for thr in (0.25, 0.5)}
 
 
+def evaluate_raw(model, n_scenes, n_samples, seed0=100, res=0.03, teacher=False, nclasses=9, device="cuda"):
+    """the synthetic evaluation from raw clouds: voxelised on the device by pipeline.detect_points"""
+    hv = HoughVoting(res)
+    pred_map_cls, gt_map_cls = {}, {}
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    for index in range(n_scenes):
+        raw = make_raw_scene(seed0 + index, n_samples)
+        id_scan = "synth%04d" % (seed0 + index)
+        pred = tuple(t(a) for a in synth_predictions(raw)) if teacher else None
+        dets = pipeline.detect_points(model, hv, t(raw.points), t(raw.feats) * 2.0 - 1.0, res, predictions=pred,
+                                      nclasses=nclasses)[0]
+        pred_map_cls[id_scan] = dets
+        lines = ["%f %f %f %f %f %f %f %d" % tuple(list(b[:7]) + [int(b[7])]) for b in raw.boxes]
+        gt_map_cls[id_scan] = [(c, calc_map.gt_box(*p)) for c, p in parse_gt_lines(lines)]
+    return {thr: calc_map.compute_map(pred_map_cls, gt_map_cls, thr) for thr in (0.25, 0.5)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", type=int, default=4)
@@ -52,7 +72,11 @@ def main():
     ap.add_argument("--weights", default=None)
     ap.add_argument("--teacher", action="store_true")
     ap.add_argument("--config", default=None, help="the reference's config.yaml: evaluate on real ScanNet/Scan2CAD files")
+    ap.add_argument("--raw-points", type=int, nargs="?", const=300000, default=0, metavar="M",
+                    help="synthetic scenes as raw clouds of M samples, voxelised on the device (pipeline.detect_points)")
     a = ap.parse_args()
+    if a.raw_points and a.config:
+        ap.error("--raw-points runs on the synthetic scenes only")
     cfg = load_config(a.config, category="all") if a.config else None
     model = MinkUNet34C(6 if (cfg and cfg.use_xyz) else 3, 6 * 9 + 9 + 1)
     if a.weights:
@@ -60,6 +84,8 @@ def main():
     model = model.cuda().eval()
     if cfg:
         res = evaluate(model, ScanNetXYZProbMultiDataset(cfg, training=False, augment=False), res=cfg.scannet_res)
+    elif a.raw_points:
+        res = evaluate_raw(model, a.scenes, a.raw_points, seed0=100, teacher=a.teacher)
     else:
         res = evaluate(model, SyntheticScanDataset(a.scenes, a.points, seed0=100), teacher=a.teacher)
     for thr, r in res.items():
