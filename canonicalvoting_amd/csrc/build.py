@@ -38,7 +38,7 @@ def _sources():
         "hv_vote.hip": STRICT + env("CV_HV_DEFS"),       # tile-shape experiments (-DHV_TX=16 -DHV_TW=8)
         "hv_decode.hip": STRICT + env("CV_DEC_DEFS"),    # greedy-walk experiments (-DDEC_BLOCKED=0)
         "sparse_coords.hip": [],
-        "sparse_conv.hip": env("CV_SC_DEFS"),            # kernel experiments (-DCV_WP_CLAMPED_GATHER=1)
+        "sparse_conv.hip": env("CV_SC_DEFS"),            # kernel experiments (-DCV_WP_NPRE=27)
         "net_exec.cpp": [],
         "scene_exec.cpp": [],
     }

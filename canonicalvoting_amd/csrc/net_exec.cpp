@@ -280,22 +280,12 @@ int cv_net_run_f32(const cv_net_op* ops, int n_ops, const cv_net_buf* bufs, int 
             }
         }
     }
-    // split-K tickets of the hl-format convolutions (cv_conv_desc.split_tickets): the last 16 KB of the workspace,
-    // zeroed once per forward (the launches leave them at zero; the fill keeps a failed forward from poisoning the next)
-    int32_t* tickets = nullptr;
-    size_t conv_ws_bytes = ws_bytes;
-    const size_t ticket_bytes = sizeof(int32_t) * CV_SPLIT_TICKETS;
-    // OFF unless CV_HL_FUSE_FINISH=1.  Round 2 published with plain stores + an agent-scope release per workgroup: 2.50 -> 3.79 ms
-    // per forward.  Round 4 publishes write-through (sc1 stores, no release fence): the publish is cheap now, but the LAST
-    // ARRIVER reads splits x 32 KB alone (~65 GB/s per workgroup): one scene in flight 2.43 -> 3.21 ms per forward (16-32
-    // splits), eight in flight 555 -> 545 scenes/s (2-8 splits) - profiles/r4/throughput_ablations.txt.  A finish launch
-    // spreads the same reads over the chip.
-    static const bool fuse_on = getenv("CV_HL_FUSE_FINISH") && atoi(getenv("CV_HL_FUSE_FINISH")) != 0;
-    if (fuse_on && d_ws && ws_bytes > ((size_t)1 << 20) + ticket_bytes) {
-        conv_ws_bytes = (ws_bytes - ticket_bytes) & ~(size_t)255;
-        tickets = reinterpret_cast<int32_t*>(static_cast<char*>(d_ws) + conv_ws_bytes);
-        CV_HIP_CHECK(hipMemsetAsync(tickets, 0, ticket_bytes, static_cast<hipStream_t>(stream)));
-    }
+    // The split-K launches of the program are reduced by finish launches: no cv_conv_desc.split_tickets.  Round 2's in-launch
+    // reduction published with plain stores + an agent-scope release per workgroup: 2.50 -> 3.79 ms per forward.  Round 4
+    // publishes write-through (sc1 stores, no release fence): the publish is cheap now, but the LAST ARRIVER reads
+    // splits x 32 KB alone (~65 GB/s per workgroup): one scene in flight 2.43 -> 3.21 ms per forward (16-32 splits), eight in
+    // flight 555 -> 545 scenes/s (2-8 splits) - profiles/r4/throughput_ablations.txt.  A finish launch spreads the same
+    // reads over the chip.
     for (int k = 0; k < n_ops; ++k) {
         const cv_net_op& o = ops[k];
         CV_REQUIRE(o.in_buf >= 0 && o.in_buf < n_bufs && o.out_buf >= 0 && o.out_buf < n_bufs &&
@@ -337,9 +327,8 @@ int cv_net_run_f32(const cv_net_op* ops, int n_ops, const cv_net_buf* bufs, int 
         d.out = reinterpret_cast<float*>(out.ptr) + o.out_col;
         d.out_ld = out.ld;
         d.ws = d_ws;
-        d.ws_bytes = conv_ws_bytes;
+        d.ws_bytes = ws_bytes;
         const int32_t* perm = o.perm >= 0 ? perms[o.perm] : nullptr;
-        d.split_tickets = d.in_hl ? tickets : nullptr;
         if (perm) {
             d.row_perm = perm;
             d.perm_groups = o.perm_groups;

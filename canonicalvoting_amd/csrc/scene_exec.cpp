@@ -15,7 +15,6 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 #include "cv_common.h"
@@ -36,8 +35,6 @@ struct Carver {
     }
 };
 
-// CV_SCENE_SERIALIZE=1 (experiment): the pure-enqueue part of a scene (network program, head, vote: ~110 launches) is issued
-// under one process-wide lock, as the interpreter lock did for the call-by-call path
 std::atomic<int> g_scenes_inside{0};
 struct SceneCount {
     int before;
@@ -59,11 +56,6 @@ struct SceneCount {
         g_scenes_inside.fetch_sub(1, std::memory_order_relaxed);
     }
 };
-std::mutex g_enqueue_mu;
-bool serialize_enqueue() {
-    static const bool on = getenv("CV_SCENE_SERIALIZE") && atoi(getenv("CV_SCENE_SERIALIZE")) != 0;
-    return on;
-}
 
 }  // namespace
 
@@ -165,7 +157,6 @@ int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream
         if (off.mask_perm[i] >= 0) conv_ws_b = std::max(conv_ws_b, (size_t)4 * d->mask_groups * (size_t)rows[i] * d->max_channels + 256);
         conv_ws_b = std::max(conv_ws_b, cv_sp_conv_workspace_bytes(std::min<long long>(rows[i], 128 * 384 - 1), d->max_channels, 27));
     }
-    conv_ws_b += 16384 + 256;                                            // + the split-K tickets the executor keeps at the tail
     const size_t vote_ws_b = cv_hv_forward_workspace_bytes(n, d->num_rots, dims, d->vote_algo);
     const size_t dec_ws_b = cv_decode_workspace_bytes(dims, n, d->max_candidates);
     char* arena = cv.take<char>(arena_b);
@@ -194,8 +185,6 @@ int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream
     const int32_t* perms[9];
     for (int i = 0; i < 5; ++i) perms[i] = (off.mask_perm[i] >= 0 && rows[i] >= d->masked_min_rows) ? ap + off.mask_perm[i] : nullptr;
     for (int i = 0; i < 4; ++i) perms[5 + i] = ap + off.up_perm[i];
-    std::unique_lock<std::mutex> enq(g_enqueue_mu, std::defer_lock);
-    if (serialize_enqueue()) enq.lock();
     const void* ext_ptr[2] = {d->d_feats, d->d_out_feats};
     const int ext_ld[2] = {d->feats_ld, d->out_ld};
     rc = cv_net_run_f32(d->ops, d->n_ops, d->bufs, d->n_bufs, rows, NL, arena, arena_b, ext_ptr, ext_ld, maps, 15, perms, 9, conv_ws,
@@ -219,7 +208,6 @@ int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream
     if (rc != CV_OK) return rc;
     CV_HIP_CHECK(mark(3));
     lap(2);
-    if (enq.owns_lock()) enq.unlock();
     cv_decode_params prm = d->decode;
     prm.max_iters = d->max_candidates;
     int n_cand = 0, n_boxes = 0, truncated = 0;
@@ -355,7 +343,6 @@ int cv_detect_scene_separate_f32(const cv_scene_separate_desc* d, cv_scene_separ
         if (off.mask_perm[i] >= 0) conv_ws_b = std::max(conv_ws_b, (size_t)4 * d->mask_groups * (size_t)rows[i] * d->max_channels + 256);
         conv_ws_b = std::max(conv_ws_b, cv_sp_conv_workspace_bytes(std::min<long long>(rows[i], 128 * 384 - 1), d->max_channels, 27));
     }
-    conv_ws_b += 16384 + 256;
     const size_t vote_ws_b = cv_hv_forward_cat_workspace_bytes(n, d->num_rots, dims, d->vote_algo, K);
     const size_t dec_ws_b = cv_decode_cat_workspace_bytes(dims, n, d->max_candidates, K);
     char* arena = cv.take<char>(arena_b);

@@ -344,9 +344,6 @@ __device__ __forceinline__ long long xcd_tile(const ConvArgs& a) {
 // The map entries of all the workgroup's offsets (<= NPRE: 10 in the default instance - the host splits a launch further - and
 // 28 in the instance for unsplit 3x3x3 launches; beyond that the fp32 kernel conv_rows) come in with one round of loads, a bit mask of the offsets that exist for the
 // tile is reduced once, and dead offsets are skipped without a barrier.
-#ifndef CV_WP_ABL
-#define CV_WP_ABL 0       // timing ablations of conv_rows_wp (wrong results): 1 no fp16 split, 2 no MFMA, 4 no weight tile, 8 no gathers
-#endif
 #ifndef CV_WP_NPRE
 #define CV_WP_NPRE 10
 #endif
@@ -492,16 +489,11 @@ __global__ __launch_bounds__(THREADS, (NB >= 3 ? 3 : NB == 2 ? 4 : 5)) void conv
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int src = nb_j[a_row + 8 * i];
-#if (CV_WP_ABL & 8)
-            ra[i] = make_float4((float)src, 0.f, 0.f, 0.f);
-#else
             ra[i] = src >= 0 ? *reinterpret_cast<const float4*>(src_base + (long long)src * src_ld + kc + a_col)
                              : make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
         }
         const unsigned short* slab = second ? a.wp6_2 + (long long)c * P * a.cout * 32
                                             : a.wp6 + (long long)(j * nch + c) * P * a.cout * 32;
-#if !(CV_WP_ABL & 4)
 #pragma unroll
         for (int i = 0; i < B_PER; ++i) {
             const int f = tid + i * THREADS;
@@ -513,7 +505,6 @@ __global__ __launch_bounds__(THREADS, (NB >= 3 ? 3 : NB == 2 ? 4 : 5)) void conv
                             : make_uint4(0u, 0u, 0u, 0u);
             }
         }
-#endif
     };
     auto stage = [&](unsigned char* Bb) {
 #pragma unroll
@@ -530,18 +521,13 @@ __global__ __launch_bounds__(THREADS, (NB >= 3 ? 3 : NB == 2 ? 4 : 5)) void conv
                 *reinterpret_cast<uint2*>(dst + TM * 64) = make_uint2(m0, m1);
                 *reinterpret_cast<uint2*>(dst + 2 * TM * 64) = make_uint2(l0, l1);
             } else {
-#if (CV_WP_ABL & 1)
-                h0 = __float_as_uint(ra[i].x); l0 = __float_as_uint(ra[i].y); h1 = __float_as_uint(ra[i].z); l1 = __float_as_uint(ra[i].w);
-#else
                 in_max = fmaxf(fmaxf(in_max, fmaxf(fabsf(ra[i].x), fabsf(ra[i].y))), fmaxf(fabsf(ra[i].z), fabsf(ra[i].w)));
                 split2h(ra[i].x, ra[i].y, h0, l0);
                 split2h(ra[i].z, ra[i].w, h1, l1);
-#endif
                 *reinterpret_cast<uint2*>(dst) = make_uint2(h0, h1);
                 *reinterpret_cast<uint2*>(dst + TM * 64) = make_uint2(l0, l1);
             }
         }
-#if !(CV_WP_ABL & 4)
 #pragma unroll
         for (int i = 0; i < B_PER; ++i) {
             const int f = tid + i * THREADS;
@@ -551,7 +537,6 @@ __global__ __launch_bounds__(THREADS, (NB >= 3 ? 3 : NB == 2 ? 4 : 5)) void conv
                 *reinterpret_cast<uint4*>(Bb + (p * NB * 32 + col) * 64 + ((ch ^ ((col >> 2) & 3)) << 4)) = rb[i];
             }
         }
-#endif
     };
     int j = j_first, c = c_first, buf = 0;
     if (njl > 0) skip_dead(j, c); else j = j_last + 1;
@@ -565,11 +550,7 @@ __global__ __launch_bounds__(THREADS, (NB >= 3 ? 3 : NB == 2 ? 4 : 5)) void conv
         const bool wave_live = __any(nbr_all[j - j_first][wave * 32 + l31] >= 0);
         advance(j, c);
         if (j < j_done) load(j, c);                  // in flight while the matrix cores run
-#if !(CV_WP_ABL & 2)
         if (wave_live) compute(Bb);
-#else
-        if (wave_live && in_max == 12345.f) compute(Bb);
-#endif
         buf ^= 1;
     }
     __syncthreads();                                 // operand tiles are dead: the epilogue tile reuses their LDS
@@ -597,78 +578,43 @@ __global__ __launch_bounds__(THREADS, (NB >= 3 ? 3 : NB == 2 ? 4 : 5)) void conv
 // barrier per (offset, 32-channel) unit) with the gathered operand taken straight from global memory: in the hl format
 // a lane's MFMA A fragments of a unit are four contiguous 16-byte pieces of its row's 128-byte chunk, so the gather IS
 // the fragment load - no fp16 split (it was 2/3 of the VALU work of conv_rows_wp: 17.8 VALU instructions per MFMA,
-// profiles/r1/conv_pmc_wp.txt), no LDS staging of A, no in_max scan.  That frees the registers for a three-deep
-// software pipeline: the fragments of unit u + 2 are requested before the MFMAs of unit u run (conv_rows_wp: u + 1,
-// and the wave-time ablations of profiles/wp_ablate_trace.sh put most of the small layers' 20 us in that dependent
-// chain of load round trips).  Same units, same MFMA sequence per accumulator as conv_rows_wp on the same h / l
+// profiles/r1/conv_pmc_wp.txt), no LDS staging of A, no in_max scan.  That frees the registers for a deeper software
+// pipeline: two units' fragments are in flight (conv_rows_wp: one, and the wave-time ablations of round 2,
+// profiles/r2/hl_ablate_trace.txt, put most of the small layers' 20 us in that dependent chain of load round trips).
+// Same units, same MFMA sequence per accumulator as conv_rows_wp on the same h / l
 // pieces: bit-identical accumulators.
-#ifndef CV_HL_ABL
-#define CV_HL_ABL 0       // timing ablations of conv_hl (wrong results): 1 no gathers, 2 no MFMA, 4 no weight tile, 8 no epilogue, 16 no map reads
-#endif
-// NS = unit slots (registers for the A fragments and this thread's share of the weight tile, one LDS weight tile each):
-// the loads of unit u + NS - 1 are requested while unit u multiplies.  Workgroups of the split coarse levels have no more
-// than NS units: all their loads are in flight after the prologue (two dependent round trips - map entries, fragments -
-// instead of one per unit).
-// NW = waves per workgroup (4: 128 rows; 8: 256 rows, measured slower - profiles/r2/hl_nw8.txt).
+// Two unit slots (registers for the A fragments and this thread's share of the weight tile, one LDS weight tile each):
+// the loads of unit u + 2 are requested once unit u has multiplied.  Workgroups of the split coarse levels have no more
+// than two units: all their loads are in flight after the prologue (two dependent round trips - map entries, fragments -
+// instead of one per unit).  Four waves = 128 rows per workgroup.
+// (Measured and removed, git fdb3db3 holds the code: one and three unit slots, 8-wave workgroups - profiles/r2/hl_slots.txt,
+// hl_nw8.txt, LABNOTES "Round 3" - and the line-coalesced gather through a wave-private LDS tile: bit-identical, net
+// 2.445 -> 2.54 ms, 506 -> 475 scenes/s six in flight, profiles/r3/hl_coal_ab.txt - the LDS round trip on every unit's
+// critical path costs more than the faster gather returns.)
 // The unit walk is resolved once, before the loop: wave 0 compacts the workgroup's live (offset, chunk) units into a
 // list in LDS, the loop is a counted loop over that list with per-thread invariants (weight-tile source / LDS offsets,
 // 32-bit row offsets) hoisted - the first version spent ~150 vector and ~250 scalar instructions per unit on the walk
 // (advance / skip_dead, 64-bit address arithmetic, spilled scalars) around 18 MFMAs.
-#ifndef HL_CB_MIN_NB
-#define HL_CB_MIN_NB 3
-#endif
-#ifndef HL_OCC1
-#define HL_OCC1 4
-#endif
-#ifndef HL_OCC2
-#define HL_OCC2 4
-#endif
-#ifndef HL_OCC3
-#define HL_OCC3 4
-#endif
-// HL_COAL (round-3 experiment, OFF: measured slower; bit NB - 1 switches the NB x 32-column kernel): the row gather
-// line-coalesced - 8 lanes fetch the 8 x 16-byte pieces of one row's 128-byte chunk (4 instructions x 8 rows) and a
-// wave-private 4 KB LDS tile turns the [32 rows][128 B] image into the MFMA A layout (lane = row, 4 pieces per lane).
-// Why it was tried (profiles/r3/gather_rate.txt): with lane = row every 16-byte access of a load instruction is its own
-// line look-up in the vector cache and a pure gather tops out at 15 B/clk/CU (9.2 TB/s) even when everything hits the
-// L2; line-coalesced it reaches 36 B/clk/CU (22 TB/s).  The piece a lane fetches is XOR-swizzled with (row >> 1) & 7,
-// so the b128 stores (lane-contiguous) and the b128 reads (row stride 128 B) are conflict-free in the lane groups of
-// ds_read_b128.  Same bytes into the same MFMAs: bit-identical results (82 network tests pass with it).  Measured
-// (profiles/r3/hl_coal_ab.txt): net 2.445 -> 2.54 ms, 506 -> 475 scenes/s six in flight; on the 32 / 64-column kernels
-// alone (occupancy unchanged) 2.56 ms: the vector cache's look-up rate is not what bounds conv_hl - the LDS round trip
-// on every unit's critical path costs more than the faster gather returns.
-#ifndef HL_COAL
-#define HL_COAL 0
-#endif
-#ifndef HL_SETPRIO
-#define HL_SETPRIO 0      // experiment: s_setprio 1 around a unit's MFMA cluster
-#endif
 constexpr int HL_MAX_UNITS = 512;      // live units of one workgroup: <= 10 offsets x Cin / 32 chunks + the second source's (host-checked)
 // workgroups per CU the register allocation aims at (the second __launch_bounds__ argument; the waves-per-SIMD attribute
 // restates it, because an explicit amdgpu_waves_per_eu replaces the bound __launch_bounds__ implies - a (1, 8) range
 // silently cost the 96-column kernel a workgroup per CU for most of round 3)
-constexpr int hl_blocks(int NB, int NS, int NW) {
-    return NW > 4 ? (NS == 2 ? 2 : 1) : NS == 1 ? (NB == 1 ? 7 : 5) : NS == 2 ? (NB == 1 ? HL_OCC1 : NB == 2 ? HL_OCC2 : NB == 3 ? HL_OCC3 : 2) : 3;
-}
-template <int NB, int NS, int NW>
-__global__ __attribute__((amdgpu_waves_per_eu(hl_blocks(NB, NS, NW) * NW / 4 > 8 ? 8 : hl_blocks(NB, NS, NW) * NW / 4, 8)))
-__launch_bounds__(NW * 64, hl_blocks(NB, NS, NW)) void conv_hl(ConvArgs a) {
-    static_assert(NS == 3 || NS == 2 || NS == 1, "three unit slots, two (the loads of unit k + 2 follow the MFMAs of unit k) or one (no prefetch: more workgroups per CU)");
-    constexpr int TMv = NW * 32, THv = NW * 64;
+constexpr int hl_blocks(int NB) { return NB <= 3 ? 4 : 2; }
+template <int NB>
+__global__ __attribute__((amdgpu_waves_per_eu(hl_blocks(NB), 8)))
+__launch_bounds__(THREADS, hl_blocks(NB)) void conv_hl(ConvArgs a) {
+    constexpr int NS = 2, NW = THREADS / 64;                                // unit slots, waves
     constexpr int B_BYTES = 2 * NB * 32 * 64, EP_BYTES = NW * 32 * EP_LD * 4;
-    constexpr bool COAL = (HL_COAL >> (NB - 1)) & 1;
-    constexpr int A_STAGE = COAL ? NW * 4096 : 0;                           // per wave: [32 rows][8 pieces x 16 B], swizzled
-    constexpr int NT = NS == 1 ? 2 : NS;                                    // weight tiles in LDS (one register slot still alternates two)
-    constexpr int SM_BYTES = NT * B_BYTES + A_STAGE > EP_BYTES ? NT * B_BYTES + A_STAGE : EP_BYTES;
-    __shared__ __attribute__((aligned(16))) unsigned char sm[SM_BYTES];     // NS x weight tile [plane][col][64 B], the A tiles; then the epilogue tile
-    __shared__ int rows_s[TMv];
-    __shared__ int nbr_all[WP_NPRE + 1][TMv];
+    constexpr int SM_BYTES = NS * B_BYTES > EP_BYTES ? NS * B_BYTES : EP_BYTES;
+    __shared__ __attribute__((aligned(16))) unsigned char sm[SM_BYTES];     // NS x weight tile [plane][col][64 B]; then the epilogue tile
+    __shared__ int rows_s[TM];
+    __shared__ int nbr_all[WP_NPRE + 1][TM];
     __shared__ unsigned wave_mask[NW];
     __shared__ unsigned short units_s[HL_MAX_UNITS + 4];      // (jj << 8) | chunk of every live unit, in processing order; [HL_MAX_UNITS] = count
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n0 = blockIdx.y * (NB * 32);
     const long long tile_id = xcd_tile(a);
-    if (tile_id * TMv >= a.n_out) return;             // padding of the XCD-aware grid
+    if (tile_id * TM >= a.n_out) return;             // padding of the XCD-aware grid
     const int half = lane >> 5, l31 = lane & 31;
     const int nj = a.j_end - a.j_begin;
     const int nch = a.cin / KC;
@@ -686,8 +632,8 @@ __launch_bounds__(NW * 64, hl_blocks(NB, NS, NW)) void conv_hl(ConvArgs a) {
 
     // order and map entries in one phase (independent unless a single order comes without its map rows), one barrier
     const int* perm = a.row_perm ? a.row_perm + (a.perm_per_split ? (long long)blockIdx.z * a.n_out : 0) : nullptr;
-    if (tid < TMv) {
-        const long long t = tile_id * TMv + tid;
+    if (tid < TM) {
+        const long long t = tile_id * TM + tid;
         const int row = t < a.n_out ? (perm ? perm[t] : (int)t) : -1;
         rows_s[tid] = row;
         if (a.in2) nbr_all[njl][tid] = row;
@@ -695,9 +641,9 @@ __launch_bounds__(NW * 64, hl_blocks(NB, NS, NW)) void conv_hl(ConvArgs a) {
     {
         unsigned m = 0u;
         const int jg0 = a.j_begin + (int)((long long)nj * blockIdx.z / a.splits);      // first offset of this mask group
-        for (int e = tid; e < njl * TMv; e += THv) {
-            const int jj = e / TMv, t = e - jj * TMv;
-            const long long pos = tile_id * TMv + t;
+        for (int e = tid; e < njl * TM; e += THREADS) {
+            const int jj = e / TM, t = e - jj * TM;
+            const long long pos = tile_id * TM + t;
             int v = -1;
             if (pos < a.n_out) {
                 if (a.nbr_perm) {
@@ -706,7 +652,6 @@ __launch_bounds__(NW * 64, hl_blocks(NB, NS, NW)) void conv_hl(ConvArgs a) {
                     const int row = perm ? perm[pos] : (int)pos;
                     v = a.nbr ? a.nbr[(long long)row * a.K + j_first + jj] : row;
                 }
-                if (CV_HL_ABL & 16) v = (int)pos;
             }
             nbr_all[jj][t] = v;
             if (v >= 0) m |= 1u << jj;
@@ -752,11 +697,11 @@ __launch_bounds__(NW * 64, hl_blocks(NB, NS, NW)) void conv_hl(ConvArgs a) {
     // per-thread invariants of the weight tile: this thread's 16-byte pieces (source offset inside a unit's slab in 16-bit
     // words, or -1 beyond Cout; LDS offset with the XOR swizzle)
     constexpr int B_U4 = 2 * NB * 32 * 4;
-    constexpr int B_PER = (B_U4 + THv - 1) / THv;
+    constexpr int B_PER = (B_U4 + THREADS - 1) / THREADS;
     int b_src[B_PER], b_dst[B_PER];
 #pragma unroll
     for (int i = 0; i < B_PER; ++i) {
-        const int f = tid + i * THv;
+        const int f = tid + i * THREADS;
         const int p = f / (NB * 32 * 4), rem = f - p * (NB * 32 * 4);
         const int col = rem >> 2, ch = rem & 3;
         b_src[i] = (f < B_U4 && n0 + col < a.cout) ? (p * a.cout + n0 + col) * 32 + ch * 8 : -1;
@@ -777,24 +722,9 @@ __launch_bounds__(NW * 64, hl_blocks(NB, NS, NW)) void conv_hl(ConvArgs a) {
         const int code = __builtin_amdgcn_readfirstlane((int)units_s[k]);
         const int jj = code >> 8, c = code & 255;
         const bool second = jj == njl;
-        if constexpr (COAL) {
-            // instruction q: rows (lane >> 3) + 8 q of the wave, lane & 7 = LDS slot of the row, slot ^ ((row >> 1) & 7) = piece
-            const unsigned rb_ = second ? in2_row_bytes : in_row_bytes;
-            const unsigned char* const base = (second ? in2_b : in_b) + (unsigned)(c * 128);
-            bool any = false;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int src = nbr_all[jj][wave * 32 + (lane >> 3) + 8 * q];
-                any |= src >= 0;
-                if (src >= 0 && !(CV_HL_ABL & 1))
-                    ra[sl][q] = *reinterpret_cast<const uint4*>(base + ((unsigned)src * rb_ + (unsigned)((((lane & 7) ^ (((lane >> 4) + 4 * q) & 7))) << 4)));
-                else ra[sl][q] = make_uint4(0u, 0u, 0u, 0u);
-            }
-            live[sl] = __any(any);
-        } else {
         const int src = nbr_all[jj][my_row];
         live[sl] = __any(src >= 0);
-        if (src >= 0 && !(CV_HL_ABL & 1)) {
+        if (src >= 0) {
             const unsigned off = (unsigned)src * (second ? in2_row_bytes : in_row_bytes) + (unsigned)(c * 128 + half * 16);
             const unsigned char* p = (second ? in2_b : in_b) + off;
             ra[sl][0] = *reinterpret_cast<const uint4*>(p);
@@ -805,19 +735,17 @@ __launch_bounds__(NW * 64, hl_blocks(NB, NS, NW)) void conv_hl(ConvArgs a) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) ra[sl][q] = make_uint4(0u, 0u, 0u, 0u);
         }
-        }
         const unsigned short* slab = second ? a.wp6_2 + (size_t)c * slab_words
                                             : a.wp6 + (size_t)((j_first + jj) * nch + c) * slab_words;
 #pragma unroll
         for (int i = 0; i < B_PER; ++i)
-            rb[sl][i] = (b_src[i] >= 0 && !(CV_HL_ABL & 4)) ? *reinterpret_cast<const uint4*>(slab + b_src[i])
-                                                            : make_uint4(0u, 0u, 0u, 0u);
+            rb[sl][i] = b_src[i] >= 0 ? *reinterpret_cast<const uint4*>(slab + b_src[i]) : make_uint4(0u, 0u, 0u, 0u);
     };
-    auto stage_b = [&](auto S, int toff) {            // toff: byte offset of the LDS weight tile (slot * B_BYTES; NS == 1: (k & 1) * B_BYTES)
+    auto stage_b = [&](auto S, int toff) {            // toff: byte offset of the LDS weight tile (slot * B_BYTES)
         constexpr int sl = decltype(S)::value;
 #pragma unroll
         for (int i = 0; i < B_PER; ++i)
-            if (b_dst[i] >= 0 && !(CV_HL_ABL & 4)) *reinterpret_cast<uint4*>(sm + toff + b_dst[i]) = rb[sl][i];
+            if (b_dst[i] >= 0) *reinterpret_cast<uint4*>(sm + toff + b_dst[i]) = rb[sl][i];
     };
     const int b_rd = l31 * 64;
     const int bswz = (l31 >> 2) & 3;
@@ -825,24 +753,6 @@ __launch_bounds__(NW * 64, hl_blocks(NB, NS, NW)) void conv_hl(ConvArgs a) {
         constexpr int sl = decltype(S)::value;
         const unsigned char* Bb = sm + toff + b_rd;
         uint4 (&fa)[4] = ra[sl];
-        if constexpr (COAL) {
-            // [32 rows][128 B] image of the wave's gathered chunk -> lane = row, pieces half, 2 + half, 4 + half, 6 + half,
-            // back into the slot's own registers.  The tile is the wave's own: program order + the in-order LDS pipe are
-            // the only synchronisation needed.
-            unsigned char* st = sm + NT * B_BYTES + wave * 4096;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) *reinterpret_cast<uint4*>(st + q * 1024 + lane * 16) = ra[sl][q];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const unsigned char* rd = st + l31 * 128;
-            const int g = (l31 >> 1) & 7;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) fa[k] = *reinterpret_cast<const uint4*>(rd + (((2 * k + half) ^ g) << 4));
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-        if (HL_SETPRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const int piece = ((2 * ks + half) ^ bswz) << 4;
@@ -854,64 +764,32 @@ __launch_bounds__(NW * 64, hl_blocks(NB, NS, NW)) void conv_hl(ConvArgs a) {
                 acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, acc[nb], 0, 0, 0);
                 acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, acc[nb], 0, 0, 0);
                 acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, acc[nb], 0, 0, 0);
-                if constexpr (NB >= HL_CB_MIN_NB && NS == 2) asm volatile("" ::: "memory");   // keep the next fragments' reads behind these MFMAs (registers)
+                if constexpr (NB >= 3) asm volatile("" ::: "memory");   // keep the next fragments' reads behind these MFMAs (registers)
             }
         }
-        if (HL_SETPRIO) __builtin_amdgcn_s_setprio(0);
     };
     typedef std::integral_constant<int, 0> S0;
     typedef std::integral_constant<int, 1> S1;
-    typedef std::integral_constant<int, 2> S2;
-    if constexpr (NS == 1) {
-        // one register slot, two LDS tiles: nothing of unit k + 1 is requested before unit k has multiplied - the latency of a
-        // unit's loads is covered by the OTHER workgroups of the CU (fewer registers: one more of them fits)
-#pragma unroll 1
-        for (int k = 0; k < n_units; ++k) {
-            const int toff = (k & 1) * B_BYTES;
-            load(S0{}, k);
-            stage_b(S0{}, toff);
-            __syncthreads();         // tile k visible; everyone is past the MFMAs of unit k - 2, whose tile unit k + ... reuses next
-            if (live[0] && (!(CV_HL_ABL & 2) || a.acc_scale == 12345.f)) compute(S0{}, toff);
-        }
-    } else {
     if (n_units > 0) load(S0{}, 0);
     if (n_units > 1) load(S1{}, 1);
     if (n_units > 0) stage_b(S0{}, 0);
-    // step: unit k in slot s.  barrier: tile k visible, tile k - 1 consumed by everyone (its slot takes the loads of unit
-    // k + 2); the tile of unit k + 1 goes to LDS; MFMAs of unit k
-    if constexpr (NS == 3) {
-        auto step = [&](auto S, auto SN, auto SP, int k) {
-            constexpr int sl = decltype(S)::value;
-            __syncthreads();
-            if (k + 1 < n_units) stage_b(SN, decltype(SN)::value * B_BYTES);
-            if (k + 2 < n_units) load(SP, k + 2);
-            if (live[sl] && (!(CV_HL_ABL & 2) || a.acc_scale == 12345.f)) compute(S, sl * B_BYTES);
-        };
+    // step: unit k in slot s.  barrier: tile k visible, tile k - 1 consumed by everyone; the tile of unit k + 1 goes to LDS;
+    // MFMAs of unit k; the registers of unit k take the loads of unit k + 2 once its MFMAs are issued (85 / 113 / 128 VGPRs for
+    // 32 / 64 / 96 columns: four workgroups per CU; net 2.53 -> 2.48 ms against three slots for the first two, 2.52 -> 2.48 ms for
+    // the third once a compiler barrier keeps its fragment reads from being hoisted - its remaining spills are outside the
+    // unit loop)
+    auto step = [&](auto S, auto SN, int k) {
+        constexpr int sl = decltype(S)::value;
+        __syncthreads();
+        if (k + 1 < n_units) stage_b(SN, decltype(SN)::value * B_BYTES);
+        if (live[sl]) compute(S, sl * B_BYTES);
+        if (k + 2 < n_units) load(S, k + 2);
+    };
 #pragma unroll 1
-        for (int k = 0; k < n_units; k += 3) {
-            step(S0{}, S1{}, S2{}, k);
-            if (k + 1 >= n_units) break;
-            step(S1{}, S2{}, S0{}, k + 1);
-            if (k + 2 >= n_units) break;
-            step(S2{}, S0{}, S1{}, k + 2);
-        }
-    } else {
-        // two slots: the registers of unit k take the loads of unit k + 2 once its MFMAs are issued (fewer registers:
-        // four workgroups per CU instead of three)
-        auto step = [&](auto S, auto SN, int k) {
-            constexpr int sl = decltype(S)::value;
-            __syncthreads();
-            if (k + 1 < n_units) stage_b(SN, decltype(SN)::value * B_BYTES);
-            if (live[sl] && (!(CV_HL_ABL & 2) || a.acc_scale == 12345.f)) compute(S, sl * B_BYTES);
-            if (k + 2 < n_units) load(S, k + 2);
-        };
-#pragma unroll 1
-        for (int k = 0; k < n_units; k += 2) {
-            step(S0{}, S1{}, k);
-            if (k + 1 >= n_units) break;
-            step(S1{}, S0{}, k + 1);
-        }
-    }
+    for (int k = 0; k < n_units; k += 2) {
+        step(S0{}, S1{}, k);
+        if (k + 1 >= n_units) break;
+        step(S1{}, S0{}, k + 1);
     }
     __syncthreads();                                 // weight tiles are dead: the epilogue tile reuses their LDS
     {
@@ -922,7 +800,6 @@ __launch_bounds__(NW * 64, hl_blocks(NB, NS, NW)) void conv_hl(ConvArgs a) {
             for (int r = 0; r < 16; ++r) acc[nb][r] *= sc;
     }
     float (*ep)[EP_LD] = reinterpret_cast<float (*)[EP_LD]>(sm + wave * 32 * EP_LD * 4);
-    if ((CV_HL_ABL & 8) && a.acc_scale != 12345.f) return;
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) epilogue_store_wide(a, acc[nb], rows_s + wave * 32, n0 + nb * 32, lane, ep);
     if (a.splits > 1 && a.tickets) {
@@ -990,16 +867,9 @@ __launch_bounds__(NW * 64, hl_blocks(NB, NS, NW)) void conv_hl(ConvArgs a) {
 //    vmcnt (the LDS-DMA instructions a wave issued for the units behind the one it needs stay in flight);
 //  * the accumulators are the only long-lived registers: one workgroup of 8 waves per CU (LDS-bound), two waves per SIMD.
 // Dead rows of a live wave fetch a row of zeros (one line, all lanes); dead waves issue nothing for the unit.
-#ifndef CV_HD_ABL
-#define CV_HD_ABL 0
-#endif
 // LDS of one workgroup: NSTG ring stages (gathered rows of NW waves + the weight tile), the tile's row / map tables, unit list
-#ifndef HD_LDS_PAD
-#define HD_LDS_PAD 0        // experiment: LDS the workgroup does not use, to control what else fits on its CU (profiles/r5/hd_lds_pad.txt)
-#endif
 constexpr int hd_lds_bytes(int NB, int NW, int NSTG) {
-    return NSTG * (NW * 4096 + 2 * NB * 32 * 64) + NW * 32 * 4 + (WP_NPRE + 1) * NW * 32 * 4 + NW * 4 + (HL_MAX_UNITS + 4) * 2 +
-           ((NB == 3 && NW == 8 && NSTG == 2) ? HD_LDS_PAD : 0);
+    return NSTG * (NW * 4096 + 2 * NB * 32 * 64) + NW * 32 * 4 + (WP_NPRE + 1) * NW * 32 * 4 + NW * 4 + (HL_MAX_UNITS + 4) * 2;
 }
 constexpr int hd_blocks(int NB, int NW, int NSTG) {          // workgroups per CU (LDS-bound), at most 8 waves per SIMD
     const int b = (160 * 1024) / hd_lds_bytes(NB, NW, NSTG);
@@ -1007,36 +877,6 @@ constexpr int hd_blocks(int NB, int NW, int NSTG) {          // workgroups per C
 }
 // NW waves x 32 rows per workgroup, NSTG ring stages: <8, 3> one workgroup per CU with the requests of two units in flight
 // behind the one that multiplies; <4, 2> two workgroups per CU, one unit of prefetch each
-// All sixteen fragment reads of a 96-column unit in one go (no wait inside), then two waits that name the registers they
-// release: the second k-step's fragments travel while the first one multiplies, and the requests of the next unit are
-// issued while the first ones travel (conv_hd, HD_EARLY).
-#ifndef HD_EARLY
-#define HD_EARLY 0      // measured (profiles/r4/hd2_grid.txt): 562-565 scenes/s with it against 573-575 without
-#endif
-__device__ __forceinline__ void hd_reads3_issue(const unsigned (&aa)[4], const unsigned (&ab)[2], u32x4v (&A)[4],
-                                                u32x4v (&B0)[2][3], u32x4v (&B1)[2][3]) {
-    constexpr int P1 = 3 * 32 * 64;
-    asm volatile("ds_read_b128 %0, %16\n\tds_read_b128 %1, %17\n\t"
-                 "ds_read_b128 %2, %20\n\tds_read_b128 %3, %20 offset:%22\n\t"
-                 "ds_read_b128 %4, %20 offset:%23\n\tds_read_b128 %5, %20 offset:%24\n\t"
-                 "ds_read_b128 %6, %20 offset:%25\n\tds_read_b128 %7, %20 offset:%26\n\t"
-                 "ds_read_b128 %8, %18\n\tds_read_b128 %9, %19\n\t"
-                 "ds_read_b128 %10, %21\n\tds_read_b128 %11, %21 offset:%22\n\t"
-                 "ds_read_b128 %12, %21 offset:%23\n\tds_read_b128 %13, %21 offset:%24\n\t"
-                 "ds_read_b128 %14, %21 offset:%25\n\tds_read_b128 %15, %21 offset:%26"
-                 : "=&v"(A[0]), "=&v"(A[2]), "=&v"(B0[0][0]), "=&v"(B1[0][0]), "=&v"(B0[0][1]), "=&v"(B1[0][1]), "=&v"(B0[0][2]),
-                   "=&v"(B1[0][2]), "=&v"(A[1]), "=&v"(A[3]), "=&v"(B0[1][0]), "=&v"(B1[1][0]), "=&v"(B0[1][1]), "=&v"(B1[1][1]),
-                   "=&v"(B0[1][2]), "=&v"(B1[1][2])
-                 : "v"(aa[0]), "v"(aa[2]), "v"(aa[1]), "v"(aa[3]), "v"(ab[0]), "v"(ab[1]), "i"(P1), "i"(2048), "i"(P1 + 2048),
-                   "i"(4096), "i"(P1 + 4096)
-                 : "memory");
-}
-template <int N>
-__device__ __forceinline__ void hd_reads3_wait(u32x4v& a0, u32x4v& a1, u32x4v (&b0)[3], u32x4v (&b1)[3]) {
-    asm volatile("s_waitcnt lgkmcnt(%8)"
-                 : "+v"(a0), "+v"(a1), "+v"(b0[0]), "+v"(b1[0]), "+v"(b0[1]), "+v"(b1[1]), "+v"(b0[2]), "+v"(b1[2])
-                 : "n"(N) : "memory");
-}
 template <int NB, int NW, int NSTG>
 __global__ __launch_bounds__(NW * 64, (hd_blocks(NB, NW, NSTG) * NW + 3) / 4) void conv_hd(ConvArgs a) {
     static_assert(NSTG == 2 || NSTG == 3, "two or three ring stages");
@@ -1048,7 +888,7 @@ __global__ __launch_bounds__(NW * 64, (hd_blocks(NB, NW, NSTG) * NW + 3) / 4) vo
     static_assert(EP_BYTES <= NSTG * STAGE, "the epilogue tile aliases the ring");
     constexpr int OFF_ROWS = NSTG * STAGE, OFF_NBR = OFF_ROWS + TMv * 4, OFF_MASK = OFF_NBR + (WP_NPRE + 1) * TMv * 4,
                   OFF_UNITS = OFF_MASK + NW * 4,
-                  LDS_TOTAL = OFF_UNITS + (HL_MAX_UNITS + 4) * 2 + ((NB == 3 && NW == 8 && NSTG == 2) ? HD_LDS_PAD : 0);
+                  LDS_TOTAL = OFF_UNITS + (HL_MAX_UNITS + 4) * 2;
     static_assert(LDS_TOTAL == hd_lds_bytes(NB, NW, NSTG) && LDS_TOTAL <= 160 * 1024, "LDS budget");
     // ONE __shared__ object (a second one makes hipcc drain vmcnt in front of the LDS reads of an LDS-DMA pipeline)
     __shared__ __attribute__((aligned(1024))) unsigned char lds[LDS_TOTAL];
@@ -1129,8 +969,8 @@ __global__ __launch_bounds__(NW * 64, (hd_blocks(NB, NW, NSTG) * NW + 3) / 4) vo
         if (lane == 0) units_s[HL_MAX_UNITS] = (unsigned short)cnt;
     }
     __syncthreads();
-    const int n_units = (CV_HD_ABL & 8) ? 0 : __builtin_amdgcn_readfirstlane((int)units_s[HL_MAX_UNITS]);      // (8: no unit loop)
-    if (n_units == 0 && a.gvalid && !(CV_HD_ABL & 8)) return;     // no row of the tile has a neighbour in this group (zskip)
+    const int n_units = __builtin_amdgcn_readfirstlane((int)units_s[HL_MAX_UNITS]);
+    if (n_units == 0 && a.gvalid) return;                          // no row of the tile has a neighbour in this group (zskip)
 
     f32x16 acc[NB];
 #pragma unroll
@@ -1182,7 +1022,7 @@ __global__ __launch_bounds__(NW * 64, (hd_blocks(NB, NW, NSTG) * NW + 3) / 4) vo
         }
         const bool lv = __any(any);
         live[st] = lv;
-        if (lv && !(CV_HD_ABL & 1)) {
+        if (lv) {
             const unsigned rb_ = second ? in2_row_bytes : in_row_bytes;
             const unsigned char* const base = (second ? in2_b : in_b) + (unsigned)(c * 128);
 #pragma unroll
@@ -1197,7 +1037,7 @@ __global__ __launch_bounds__(NW * 64, (hd_blocks(NB, NW, NSTG) * NW + 3) / 4) vo
 #pragma unroll
         for (int i = 0; i < B_PER_WAVE; ++i) {
             const int t = wave + i * NW;                            // wave-uniform
-            if (t < B_INSTR && !(CV_HD_ABL & 4)) {
+            if (t < B_INSTR) {
                 lds_dma16(slab + b_src[i], sm + st * STAGE + A_BYTES + t * 1024);
                 ++n_issued;
             }
@@ -1224,36 +1064,9 @@ __global__ __launch_bounds__(NW * 64, (hd_blocks(NB, NW, NSTG) * NW + 3) / 4) vo
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
                 const f16x8 b0 = __builtin_bit_cast(f16x8, B0[nb]), b1 = __builtin_bit_cast(f16x8, B1[nb]);
-                if (!(CV_HD_ABL & 2)) {
-                    acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, acc[nb], 0, 0, 0);
-                    acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, acc[nb], 0, 0, 0);
-                    acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, acc[nb], 0, 0, 0);
-                }
-            }
-        }
-    };
-    auto reads_early = [&](auto S, u32x4v (&A)[4], u32x4v (&B0)[2][3], u32x4v (&B1)[2][3]) {
-        constexpr int st = decltype(S)::value;
-        const unsigned aa[4] = {a_off[0] + st * STAGE, a_off[1] + st * STAGE, a_off[2] + st * STAGE, a_off[3] + st * STAGE};
-        const unsigned ab[2] = {b_off[0] + st * STAGE, b_off[1] + st * STAGE};
-        if constexpr (NB == 3) hd_reads3_issue(aa, ab, A, B0, B1);
-    };
-    auto mfma_early = [&](u32x4v (&A)[4], u32x4v (&B0)[2][3], u32x4v (&B1)[2][3]) {
-        if constexpr (NB == 3) {
-            hd_reads3_wait<8>(A[0], A[2], B0[0], B1[0]);
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                if (ks == 1) hd_reads3_wait<0>(A[1], A[3], B0[1], B1[1]);
-                const f16x8 a0 = __builtin_bit_cast(f16x8, A[ks]), a1 = __builtin_bit_cast(f16x8, A[2 + ks]);
-#pragma unroll
-                for (int nb = 0; nb < 3; ++nb) {
-                    const f16x8 b0 = __builtin_bit_cast(f16x8, B0[ks][nb]), b1 = __builtin_bit_cast(f16x8, B1[ks][nb]);
-                    if (!(CV_HD_ABL & 2)) {
-                        acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, acc[nb], 0, 0, 0);
-                        acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, acc[nb], 0, 0, 0);
-                        acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, acc[nb], 0, 0, 0);
-                    }
-                }
+                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, acc[nb], 0, 0, 0);
+                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, acc[nb], 0, 0, 0);
+                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, acc[nb], 0, 0, 0);
             }
         }
     };
@@ -1272,17 +1085,9 @@ __global__ __launch_bounds__(NW * 64, (hd_blocks(NB, NW, NSTG) * NW + 3) / 4) vo
             constexpr int st = decltype(S)::value;
             wait_vmcnt_dyn(__builtin_amdgcn_readfirstlane(k + 1 < n_units ? pend1 : 0));
             __builtin_amdgcn_s_barrier();
-            if constexpr (NB == 3 && HD_EARLY) {
-                u32x4v A[4], B0[2][3], B1[2][3];
-                if (live[st]) reads_early(S, A, B0, B1);
-                if (k + 2 < n_units) pend1 = issue(SP, k + 2);
-                else pend1 = 0;
-                if (live[st]) mfma_early(A, B0, B1);
-            } else {
-                if (k + 2 < n_units) pend1 = issue(SP, k + 2);
-                else pend1 = 0;
-                if (live[st]) compute(S);
-            }
+            if (k + 2 < n_units) pend1 = issue(SP, k + 2);
+            else pend1 = 0;
+            if (live[st]) compute(S);
         };
 #pragma unroll 1
         for (int k = 0; k < n_units; k += 3) {
@@ -1299,15 +1104,8 @@ __global__ __launch_bounds__(NW * 64, (hd_blocks(NB, NW, NSTG) * NW + 3) / 4) vo
             constexpr int st = decltype(S)::value;
             wait_vmcnt_le<0>();
             __builtin_amdgcn_s_barrier();
-            if constexpr (NB == 3 && HD_EARLY) {
-                u32x4v A[4], B0[2][3], B1[2][3];
-                if (live[st]) reads_early(S, A, B0, B1);
-                if (k + 1 < n_units) issue(SN, k + 1);
-                if (live[st]) mfma_early(A, B0, B1);
-            } else {
-                if (k + 1 < n_units) issue(SN, k + 1);
-                if (live[st]) compute(S);
-            }
+            if (k + 1 < n_units) issue(SN, k + 1);
+            if (live[st]) compute(S);
         };
 #pragma unroll 1
         for (int k = 0; k < n_units; k += 2) {
@@ -1326,7 +1124,6 @@ __global__ __launch_bounds__(NW * 64, (hd_blocks(NB, NW, NSTG) * NW + 3) / 4) vo
             for (int r = 0; r < 16; ++r) acc[nb][r] *= sc;
     }
     float (*ep)[EP_LD] = reinterpret_cast<float (*)[EP_LD]>(sm + wave * 32 * EP_LD * 4);
-    if ((CV_HD_ABL & 16) && a.acc_scale != 12345.f) return;      // (16: no epilogue)
     ConvArgs ae = a;
     ae.tickets = nullptr;                            // (the in-launch split-K reduction is conv_hl's)
 #pragma unroll
@@ -2498,8 +2295,6 @@ int launch_rows(const ConvArgs& a, bool vec, hipStream_t st) {
         // requested at once through global_load_lds and two dependent round trips instead of 3 + units - no faster)
         // (NS = 8 / 6 / 4 slots for NB = 1 / 2 / 3 measured: every layer 25-45 % slower - two workgroups per CU
         // instead of three or four cost more than the deeper prefetch gains, profiles/r2/hl_slots.txt)
-        // 256-row workgroups where the launch has plenty of tiles and no split-K: an experiment (CV_HL_NW8=1), off by
-        // default - measured slower, profiles/r2/hl_nw8.txt
         // conv_hd (round 4): LDS-DMA operand rings, 256-row workgroups; CV_HD bit NB - 1 switches the NB x 32-column kernel on
         // for launches of at least CV_HD_MIN_ROWS output rows
         const int hd_mask = (int)g_opt_hd_mask.load(std::memory_order_relaxed);
@@ -2519,37 +2314,13 @@ int launch_rows(const ConvArgs& a, bool vec, hipStream_t st) {
                 return CV_OK;
             }
         }
-        static const int nw8_mask = getenv("CV_HL_NW8") ? atoi(getenv("CV_HL_NW8")) : 0;        // bit NB - 1
-        const bool nw8_on = (nw8_mask >> (NB - 1)) & 1;
-        if constexpr (NB <= 4) {
-            if (nw8_on && !ax.xcd_tiles && a.n_out >= 16384 && (a.splits == 1 || a.perm_per_split)) {
-                dim3 g8((unsigned)((a.n_out + 255) / 256), grid.y, grid.z);
-                conv_hl<NB, 2, 8><<<g8, 512, 0, st>>>(ax);
-            } else {
-                // two unit slots (85 / 113 / 128 VGPRs for 32 / 64 / 96 columns: five / four / four workgroups per CU instead
-                // of four / three / three; net 2.53 -> 2.48 ms for the first two, 2.52 -> 2.48 ms for the third once a compiler
-                // barrier keeps its fragment reads from being hoisted - its remaining spills are outside the unit loop).
-                // CV_HL_NS2: bit nb-1 = two slots for NB = nb
-                static const int ns2 = getenv("CV_HL_NS2") ? atoi(getenv("CV_HL_NS2")) : 7;
-                // split-K reduced by the last-arriving workgroup (cv_conv_desc.split_tickets): correct and bit-identical
-                // (tests), but every workgroup's agent-scope release writes the XCD's L2 back and the forward takes 3.79
-                // instead of 2.50 ms (profiles/r2/fused_finish.txt) - the executor only hands the tickets over when
-                // CV_HL_FUSE_FINISH=1; direct callers of cv_sp_conv_f32 get what they ask for
-                static const bool fuse_on = !(getenv("CV_HL_FUSE_FINISH") && atoi(getenv("CV_HL_FUSE_FINISH")) == 0);
-                if (!(fuse_on && ax.splits > 1 && !ax.perm_per_split && !ax.xcd_tiles &&
-                      (long long)gridx.x * gridx.y <= CV_SPLIT_TICKETS)) ax.tickets = nullptr;
-                // CV_HL_NS1 (round-3 experiment): bit nb-1 = ONE slot for NB = nb
-                static const int ns1 = getenv("CV_HL_NS1") ? atoi(getenv("CV_HL_NS1")) : 0;
-                if ((ns1 >> (NB - 1)) & 1) conv_hl<NB, 1, 4><<<gridx, THREADS, 0, st>>>(ax);
-                else if ((ns2 >> (NB - 1)) & 1) conv_hl<NB, 2, 4><<<gridx, THREADS, 0, st>>>(ax);
-                else conv_hl<NB, 3, 4><<<gridx, THREADS, 0, st>>>(ax);
-                CV_LAUNCH_CHECK();
-                if (a.splits > 1 && !ax.tickets) return launch_finish(a, st);
-                return CV_OK;
-            }
-        }
+        // split-K reduced by the last-arriving workgroup for callers that pass cv_conv_desc.split_tickets: bit-identical to the
+        // finish launch (tests); the network executor does not hand tickets over (net_exec.cpp: measured slower)
+        if (!(ax.splits > 1 && !ax.perm_per_split && !ax.xcd_tiles && (long long)gridx.x * gridx.y <= CV_SPLIT_TICKETS))
+            ax.tickets = nullptr;
+        conv_hl<NB><<<gridx, THREADS, 0, st>>>(ax);
         CV_LAUNCH_CHECK();
-        if (a.splits > 1) return launch_finish(a, st);
+        if (a.splits > 1 && !ax.tickets) return launch_finish(a, st);
         return CV_OK;
     }
     if (vec && a.wp6 && per_wg <= WP_NPRE) {
@@ -2586,18 +2357,13 @@ namespace cvsc {
 int nb_full(int cout) { return cout <= 32 ? 1 : cout <= 64 ? 2 : cout <= 96 ? 3 : 4; }
 }  // namespace cvsc
 namespace {
-int nb_for(int cout, long long n_out) {
+int nb_for(int cout) {
     static const int nb_max = getenv("CV_NB_MAX") ? atoi(getenv("CV_NB_MAX")) : 0;
     if (nb_max > 0) return std::min(nb_max, nb_full(cout));
     if (cout <= 32) return 1;
     if (cout <= 64) return 2;
     if (cout <= 96) return 3;
     static const int nb_wide = getenv("CV_NB_WIDE") ? atoi(getenv("CV_NB_WIDE")) : 2;      // 128 / 256 columns: 64-column workgroups
-    // CV_NB_COARSE (round-3 experiment): column blocks per workgroup on the levels below CV_NB_COARSE_ROWS rows - their
-    // launches have two workgroups per CU at most, so wider workgroups cost no occupancy and halve the row gathers
-    static const int nb_coarse = getenv("CV_NB_COARSE") ? atoi(getenv("CV_NB_COARSE")) : 0;
-    static const long long coarse_rows = getenv("CV_NB_COARSE_ROWS") ? atoll(getenv("CV_NB_COARSE_ROWS")) : 16384;
-    if (nb_coarse > 0 && n_out < coarse_rows) return std::max(1, std::min(nb_coarse, 4));
     // (until round 5 the levels below 1024 rows took 32-column workgroups - measured with the fp32-row kernels of round 1; on the hl
     // kernels 64 columns are better alone and with scenes in flight: net 2.32 -> 2.29-2.30 ms, 592 -> 599-600 scenes/s,
     // profiles/r5/nb_coarse.txt; 96 / 128 columns: 591 / 583)
@@ -2620,7 +2386,7 @@ long long split_target() { return t_split_target > 0 ? t_split_target : process_
 // Enough workgroups to fill 256 CUs a few times with short dependent chains: split the (offset,
 // chunk) units over blockIdx.z; the partial tiles cost 8 bytes of traffic per output element per split.
 int pick_splits(long long n_out, int cout, int K, int cin, bool vec) {
-    const int nb = nb_for(cout, n_out);
+    const int nb = nb_for(cout);
     const long long tiles = ((n_out + TM - 1) / TM) * ((cout + nb * 32 - 1) / (nb * 32));
     const long long units = vec ? (long long)K * (cin / KC) : ((long long)K * cin + KC - 1) / KC;
     if (tiles >= 384 || units <= 1) return 1;
@@ -2819,42 +2585,6 @@ int cv_sp_conv_f32(const cv_conv_desc* d, void* stream) {
             if (g_opt_zskip.load(std::memory_order_relaxed) && !d->in2 && a.wide && d->perm_groups <= FINISH_SMALL_MAX && d->in_hl)
                 a.gvalid = reinterpret_cast<const unsigned char*>(a.nbr_perm + (long long)d->perm_groups * d->n_out * a.nbr_perm_w);
         }
-        // Chain of group launches (CV_GROUP_CHAIN=1, round-3 experiment): group 0 writes its sums to the workspace, every
-        // later group adds its own to what it reads back (acc_in, same thread, same element: in place), the last one runs
-        // the epilogue - no partial tile per group, no finish launch (w 1 + (r 1 + w 1) (G - 2) + r 1 + w out instead of
-        // w G + r G + w out tile sets); the price is G launches of n_out / 128 workgroups instead of one of G times that.
-        static const bool chain_on = getenv("CV_GROUP_CHAIN") && atoi(getenv("CV_GROUP_CHAIN")) != 0;
-        if (chain_on && d->in_hl && d->flavour == 0 && !d->acc_in && a.wide) {
-            const int G = d->perm_groups, nj = je - jb;
-            float* tmp = static_cast<float*>(d->ws);
-            for (int g = 0; g < G; ++g) {
-                ConvArgs ag = a;
-                ag.splits = 1;
-                ag.perm_per_split = 0;
-                ag.partial = nullptr;
-                ag.tickets = nullptr;
-                ag.gvalid = nullptr;                 // (every launch of the chain writes every row)
-                ag.j_begin = jb + (int)((long long)nj * g / G);
-                ag.j_end = jb + (int)((long long)nj * (g + 1) / G);
-                ag.row_perm = d->row_perm + (long long)g * d->n_out;
-                if (a.nbr_perm) ag.nbr_perm = a.nbr_perm + (long long)g * d->n_out * a.nbr_perm_w;
-                if (g > 0) { ag.acc_in = tmp; ag.acc_ld = d->cout; ag.in2 = nullptr; ag.cin2 = 0; }
-                if (g < G - 1) {
-                    ag.out = tmp; ag.out_ld = d->cout; ag.out_hl = 0;
-                    ag.scale = nullptr; ag.shift = nullptr; ag.res = nullptr; ag.relu = 0; ag.range_flag = nullptr;
-                }
-                if (ag.j_end <= ag.j_begin) continue;
-                int rc2;
-                switch (nb_for(d->cout, d->n_out)) {
-                    case 1: rc2 = launch_rows<1>(ag, vec, st); break;
-                    case 2: rc2 = launch_rows<2>(ag, vec, st); break;
-                    case 3: rc2 = launch_rows<3>(ag, vec, st); break;
-                    default: rc2 = launch_rows<4>(ag, vec, st); break;
-                }
-                if (rc2) return rc2;
-            }
-            return CV_OK;
-        }
     } else if (d->flavour == 0) {
         int sp = pick_splits(d->n_out, d->cout, je - jb, d->cin, vec);
         if (d->in_hl || (vec && a.wp6)) {
@@ -2873,7 +2603,7 @@ int cv_sp_conv_f32(const cv_conv_desc* d, void* stream) {
             a.partial = static_cast<float*>(d->ws);
         }
     }
-    switch (nb_for(d->cout, d->n_out)) {
+    switch (nb_for(d->cout)) {
         case 1: return launch_rows<1>(a, vec, st);
         case 2: return launch_rows<2>(a, vec, st);
         case 3: return launch_rows<3>(a, vec, st);

@@ -84,21 +84,14 @@ __device__ __forceinline__ bool hl_out_of_range(float4 v) {
 }
 
 // Partial tiles (split-K / mask-group sums) are written once and read once by the finish launch: streamed past the
-// caches with the nontemporal policy (CV_NT_PARTIAL bit 0: the stores, bit 1: the finish launch's loads) so that they do
-// not push the activations and weight slabs, which ARE re-read, out of the 4 MB L2s.  Measured (profiles/r3/nt_partial_ab.txt):
+// caches with the nontemporal policy (the stores and the finish launch's loads) so that they do not push the activations
+// and weight slabs, which ARE re-read, out of the 4 MB L2s.  Measured (profiles/r3/nt_partial_ab.txt):
 // net 2.42 -> 2.375 ms one scene in flight, 483 -> 495 scenes/s six in flight with both; the XCD-aware tile numbering on top of
 // either: 2.61-2.64 ms (still slower - the cost ordering of the tiles is worth more than the L2 hits).
-#ifndef CV_NT_PARTIAL
-#define CV_NT_PARTIAL 3
-#endif
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void partial_store4(float* p, float4 v) {
-    if (CV_NT_PARTIAL & 1) {
-        f32x4v t; t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
-        __builtin_nontemporal_store(t, reinterpret_cast<f32x4v*>(p));
-    } else {
-        *reinterpret_cast<float4*>(p) = v;
-    }
+    f32x4v t; t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
+    __builtin_nontemporal_store(t, reinterpret_cast<f32x4v*>(p));
 }
 // split-K partial tiles that the LAST-ARRIVING workgroup of the output tile reduces inside the same launch
 // (ConvArgs.tickets): written through to memory with sc1 stores - visible to every XCD once the wave's vmcnt has drained,
@@ -109,11 +102,8 @@ __device__ __forceinline__ void partial_store4_wt(float* p, float4 v) {
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(t) : "memory");
 }
 __device__ __forceinline__ float4 partial_load4(const float4* p) {
-    if (CV_NT_PARTIAL & 2) {
-        const f32x4v t = __builtin_nontemporal_load(reinterpret_cast<const f32x4v*>(p));
-        return make_float4(t[0], t[1], t[2], t[3]);
-    }
-    return *p;
+    const f32x4v t = __builtin_nontemporal_load(reinterpret_cast<const f32x4v*>(p));
+    return make_float4(t[0], t[1], t[2], t[3]);
 }
 
 __device__ __forceinline__ void epilogue_store(const ConvArgs& a, const f32x16& acc, const int* rows,

@@ -255,7 +255,7 @@ def expected_splits(n_out, cout, K, cin):
 
 @pytest.fixture(scope="module", autouse=True)
 def _pinned_split_target(cuda, built_lib):
-    for env in ("CV_SPLIT_TARGET", "CV_SPLIT_TRAFFIC_MB", "CV_NB_MAX", "CV_NB_WIDE", "CV_NB_COARSE"):
+    for env in ("CV_SPLIT_TARGET", "CV_SPLIT_TRAFFIC_MB", "CV_NB_MAX", "CV_NB_WIDE"):
         assert env not in os.environ, "%s changes the launch routes these tests pin" % env
     L = _lib.lib()
     prev = ME.set_split_target(SPLIT_TARGET)
