@@ -58,6 +58,10 @@ struct CvMapJob {            // kernel map: out set looked up in an input set's 
     const int32_t* bbox;     // hash probes, see cv_sp_occupancy_bitmap; bbox = the 8 ints of cv_sp_sort_rows' bounds
     int up;                  // 1: transposed k2s2 map instead - out_coords are the FINE rows (tensor stride ts), keys / vals the
                              // table of the next coarser level, nbr[n_out][8] = parent row in the octant column, -1 elsewhere
+    int32_t* nbr3;           // optional (k == 5, ts == 1): the 3x3x3 map of the same set [n_out][27] (rows NOT composed) is built
+                             // by the same job - with a trusted bitmap one lane reads a whole (dx, dy) line of five z-bits
+    int32_t* mask_words;     // optional (where a 3x3x3 map is built: nbr3, or k == 3): [n_out] bit j = entry j of the row's
+                             // 3x3x3 map >= 0 (what the mask orders sort by, CvPermJob.mask_words)
 };
 constexpr int CV_MAX_MAP_JOBS = 12;
 int cv_sp_kernel_maps_batch(const CvMapJob* jobs, int n_jobs, void* stream);
@@ -80,7 +84,10 @@ int cv_sp_build_levels_zero(int32_t* const* d_coords, unsigned long long* const*
 struct CvUpJob { const int32_t* nbr_down; long long n_coarse; int32_t* up; };
 int cv_sp_up_maps_batch(const CvUpJob* jobs, int n_jobs, void* stream);      // the up arrays must be pre-filled with -1
 
-struct CvPermJob { const int32_t* nbr; long long n; int K, groups; int32_t* perm; int with_map; };
+struct CvPermJob {
+    const int32_t* nbr; long long n; int K, groups; int32_t* perm; int with_map;
+    const int32_t* mask_words;   // optional (K <= 32): bit j of word [row] = nbr[row][j] >= 0, from the map builder (CvMapJob)
+};
 constexpr int CV_MAX_PERM_JOBS = 8;
 // d_ws: (sum of groups) * 1024 ints, zero-filled by the call (unless pre_zeroed)
 int cv_hv_minmax_async_ex(const float* d_points, int64_t n, float* h_minmax6, void* d_ws, size_t ws_bytes, int32_t* d_zero_word,

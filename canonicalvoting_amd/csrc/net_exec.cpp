@@ -31,7 +31,9 @@ static void scene_maps_layout(const long long* rows, long long n_orig, int stem_
     const size_t mp_w = mask_groups > 1 ? (size_t)mask_groups * (1 + (27 + mask_groups - 1) / mask_groups) + (mask_groups + 3) / 4 : 0;
     // what depends on the caller's row count only comes first: cv_sp_scene_plan builds it before the coarse counts are known
     o->stem = take((size_t)rows[0] * K5);
-    o->k3[0] = take((size_t)rows[0] * 27);
+    // behind every 3x3x3 map [rows][27]: one validity word per row (bit j = entry j >= 0), written by the map builder and
+    // read by the mask orders (scene_mask_words)
+    o->k3[0] = take((size_t)rows[0] * 28);
     o->mask_perm[0] = (mask_groups > 1 && rows[0] >= masked_min_rows) ? take(mp_w * rows[0]) : -1;
     // bin counts + running counts of the mask orders (cv_sp_mask_perms_batch: 2 x 1024 words per group): level 0, then <= 4
     // coarse levels and the 4 up-map orders
@@ -40,11 +42,15 @@ static void scene_maps_layout(const long long* rows, long long n_orig, int stem_
     o->out = -1;                       // (the sort's inverse permutation is the final map)
     (void)n_orig;
     for (int i = 0; i < 4; ++i) o->down[i] = take((size_t)rows[i + 1] * 8);
-    for (int i = 1; i < 5; ++i) o->k3[i] = take((size_t)rows[i] * 27);
+    for (int i = 1; i < 5; ++i) o->k3[i] = take((size_t)rows[i] * 28);
     for (int i = 0; i < 4; ++i) o->up[i] = take((size_t)rows[3 - i] * 8);            // up[i]: level 4-i -> 3-i
     for (int i = 1; i < 5; ++i) o->mask_perm[i] = (mask_groups > 1 && rows[i] >= masked_min_rows) ? take(mp_w * rows[i]) : -1;
     for (int i = 0; i < 4; ++i) o->up_perm[i] = take((size_t)rows[3 - i]);
     *total = off;
+}
+
+static int32_t* scene_mask_words(int32_t* d_arena, const cv_scene_maps& o, int level, long long rows) {
+    return d_arena + o.k3[level] + rows * 27;
 }
 
 size_t cv_sp_scene_maps_words(const long long* level_rows, long long n_orig, int stem_k, int mask_groups,
@@ -71,14 +77,21 @@ static int scene_maps_level0(int32_t* const* d_coords, const unsigned long long*
         }
     }
     CvMapJob mj[2];
+    int32_t* mw = scene_mask_words(d_arena, o, 0, n);
     // stem: sorted rows <- rows of the ORIGINAL order = the sorted set's own map with the permutation folded in
     // (the caller's set needs no hash table of its own); the final original <- sorted map is the sort's inverse
-    mj[0] = {d_coords[0], n, d_keys[0], d_vals[0], cap, stem_k, 1, d_arena + o.stem, d_perm, bits, d_bbox, 0};
-    mj[1] = {d_coords[0], n, d_keys[0], d_vals[0], cap, 3, 1, d_arena + o.k3[0], nullptr, bits, d_bbox, 0};
-    int rc = cv_sp_kernel_maps_batch(mj, 2, stream);
+    int nm = 1;
+    if (stem_k == 5) {      // one job for both level-0 maps: the 27 offsets of the 3x3x3 map are the inner cube of the stem's 125
+        mj[0] = {d_coords[0], n, d_keys[0], d_vals[0], cap, 5, 1, d_arena + o.stem, d_perm, bits, d_bbox, 0, d_arena + o.k3[0], mw};
+    } else {
+        mj[0] = {d_coords[0], n, d_keys[0], d_vals[0], cap, stem_k, 1, d_arena + o.stem, d_perm, bits, d_bbox, 0, nullptr, nullptr};
+        mj[1] = {d_coords[0], n, d_keys[0], d_vals[0], cap, 3, 1, d_arena + o.k3[0], nullptr, bits, d_bbox, 0, nullptr, mw};
+        nm = 2;
+    }
+    int rc = cv_sp_kernel_maps_batch(mj, nm, stream);
     if (rc != CV_OK) return rc;
     if (o.mask_perm[0] >= 0) {
-        CvPermJob pj = {d_arena + o.k3[0], n, 27, mask_groups, d_arena + o.mask_perm[0], 1};
+        CvPermJob pj = {d_arena + o.k3[0], n, 27, mask_groups, d_arena + o.mask_perm[0], 1, mw};
         rc = cv_sp_mask_perms_batch(&pj, 1, d_arena + o.scratch, sizeof(int) * (size_t)mask_groups * 2048, stream, pre_cleared);
         if (rc != CV_OK) return rc;
     }
@@ -93,13 +106,15 @@ static int scene_maps_coarse(int32_t* const* d_coords, const unsigned long long*
     CvMapJob mj[CV_MAX_MAP_JOBS];
     int nm = 0;
     for (int i = 0; i < 4; ++i)
-        mj[nm++] = {d_coords[i + 1], level_rows[i + 1], d_keys[i], d_vals[i], cap, 2, 1 << i, d_arena + o.down[i], nullptr, nullptr, nullptr, 0};
-    for (int i = 1; i < 5; ++i)
-        mj[nm++] = {d_coords[i], level_rows[i], d_keys[i], d_vals[i], cap, 3, 1 << i, d_arena + o.k3[i], nullptr, nullptr, nullptr, 0};
+        mj[nm++] = {d_coords[i + 1], level_rows[i + 1], d_keys[i], d_vals[i], cap, 2, 1 << i, d_arena + o.down[i], nullptr, nullptr, nullptr, 0,
+                    nullptr, nullptr};
+    for (int i = 1; i < 5; ++i)         // (validity words only where a mask order will read them)
+        mj[nm++] = {d_coords[i], level_rows[i], d_keys[i], d_vals[i], cap, 3, 1 << i, d_arena + o.k3[i], nullptr, nullptr, nullptr, 0,
+                    nullptr, o.mask_perm[i] >= 0 ? scene_mask_words(d_arena, o, i, level_rows[i]) : nullptr};
     for (int i = 0; i < 4; ++i) {       // up[i]: level 4 - i -> 3 - i; the fine rows look their parent up in the coarser table
         const int fine = 3 - i;
         mj[nm++] = {d_coords[fine], level_rows[fine], d_keys[fine + 1], d_vals[fine + 1], cap, 2, 1 << fine, d_arena + o.up[i],
-                    nullptr, nullptr, nullptr, 1};
+                    nullptr, nullptr, nullptr, 1, nullptr, nullptr};
     }
     int rc = cv_sp_kernel_maps_batch(mj, nm, stream);
     if (rc != CV_OK) return rc;
@@ -107,11 +122,12 @@ static int scene_maps_coarse(int32_t* const* d_coords, const unsigned long long*
     int np = 0, groups = 0;
     for (int i = 1; i < 5; ++i)
         if (o.mask_perm[i] >= 0) {
-            pj[np++] = {d_arena + o.k3[i], level_rows[i], 27, mask_groups, d_arena + o.mask_perm[i], 1};
+            pj[np++] = {d_arena + o.k3[i], level_rows[i], 27, mask_groups, d_arena + o.mask_perm[i], 1,
+                        scene_mask_words(d_arena, o, i, level_rows[i])};
             groups += mask_groups;
         }
     for (int i = 0; i < 4; ++i) {
-        pj[np++] = {d_arena + o.up[i], level_rows[3 - i], 8, 1, d_arena + o.up_perm[i], 0};
+        pj[np++] = {d_arena + o.up[i], level_rows[3 - i], 8, 1, d_arena + o.up_perm[i], 0, nullptr};
         groups += 1;
     }
     return cv_sp_mask_perms_batch(pj, np, d_arena + o.scratch + (size_t)std::max(mask_groups, 1) * 2048,

@@ -1699,6 +1699,13 @@ __device__ __forceinline__ int group_mask(const int* __restrict__ nbr, long long
     return m;
 }
 
+// the same key from the row's validity word (bit j = entry j >= 0, stored by the map builder: one load instead of je - jb)
+__device__ __forceinline__ int group_mask_of_word(int word, int jb, int je) {
+    int m = (int)(((unsigned)word >> jb) & ((1u << (je - jb)) - 1u));
+    if (je - jb <= 7) m |= __popc(m) << 7;
+    return m;
+}
+
 __global__ __launch_bounds__(MP_THREADS) void mp_hist(const int* __restrict__ nbr, long long n, int K, int groups,
                                                       int* __restrict__ hist /*[groups][MP_BINS]*/) {
     __shared__ int lh[MP_BINS];
@@ -1782,7 +1789,8 @@ __global__ __launch_bounds__(MP_THREADS) void mp_hist_batch(const PermJobsDev jo
     const int jlo = jb.K * g / jb.groups, jhi = jb.K * (g + 1) / jb.groups;
     for (int i = threadIdx.x; i < MP_BINS; i += MP_THREADS) lh[i] = 0;
     __syncthreads();
-    if (row < jb.n) atomicAdd(&lh[group_mask(jb.nbr, row, jb.n, jb.K, jlo, jhi)], 1);
+    if (row < jb.n)
+        atomicAdd(&lh[jb.mask_words ? group_mask_of_word(jb.mask_words[row], jlo, jhi) : group_mask(jb.nbr, row, jb.n, jb.K, jlo, jhi)], 1);
     __syncthreads();
     for (int i = threadIdx.x; i < MP_BINS; i += MP_THREADS)
         if (lh[i]) atomicAdd(&hist[blockIdx.y * MP_BINS + i], lh[i]);
@@ -1823,20 +1831,42 @@ __global__ __launch_bounds__(MP_THREADS) void mp_scatter_batch(const PermJobsDev
     const long long row = blockIdx.x * (long long)MP_THREADS + threadIdx.x;
     int key = 0, rank = 0;
     if (row < jb.n) {
-        key = group_mask(jb.nbr, row, jb.n, K, jlo, jhi);
+        key = jb.mask_words ? group_mask_of_word(jb.mask_words[row], jlo, jhi) : group_mask(jb.nbr, row, jb.n, K, jlo, jhi);
         rank = atomicAdd(&lh[key], 1);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < MP_BINS; i += MP_THREADS)
         if (lh[i]) lh[i] = pre[i] + atomicAdd(&cursor[blockIdx.y * MP_BINS + i], lh[i]);
     __syncthreads();
+    long long pos = 0;
     if (row < jb.n) {
-        const long long pos = (long long)g * jb.n + lh[key] + rank;
+        pos = (long long)g * jb.n + lh[key] + rank;
         jb.perm[pos] = (int)row;
-        if (nbrp) {
-            for (int j = jlo; j < jhi; ++j) nbrp[pos * W + (j - jlo)] = jb.nbr[row * K + j];
-            reinterpret_cast<unsigned char*>(nbrp + (long long)jb.groups * jb.n * W)[(long long)g * jb.n + row] = key != 0;
+        if (nbrp) reinterpret_cast<unsigned char*>(nbrp + (long long)jb.groups * jb.n * W)[(long long)g * jb.n + row] = key != 0;
+    }
+    if (!nbrp) return;
+    // the map rows in processing order, copied by the whole workgroup: adjacent lanes read and write a row's adjacent entries
+    // (a thread copying its own row issued jhi - jlo scattered 4-byte stores one after the other).  Places of the workgroup's
+    // rows through LDS (`pre` is free: its last readers are in front of the barrier above), 32 bits: pos - g * n < n < 2^31
+    pre[threadIdx.x] = (int)(pos - (long long)g * jb.n);
+    __syncthreads();
+    const long long row0 = blockIdx.x * (long long)MP_THREADS;
+    const int nrow = (int)((jb.n - row0 < MP_THREADS) ? jb.n - row0 : MP_THREADS), Wg = jhi - jlo;
+    const int total = nrow * Wg;
+    const int* src0 = jb.nbr + row0 * K + jlo;
+    int* dst0 = nbrp + (long long)g * jb.n * W;
+    for (int e0 = threadIdx.x; e0 < total; e0 += 3 * MP_THREADS) {       // three entries in flight per thread
+        int v[3], r[3], jj[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const int e = e0 + q * MP_THREADS;
+            r[q] = Wg == 9 ? (int)((unsigned)e / 9u) : (int)((unsigned)e / (unsigned)Wg);
+            jj[q] = e - r[q] * Wg;
+            v[q] = e < total ? src0[(long long)r[q] * K + jj[q]] : 0;
         }
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+            if (e0 + q * MP_THREADS < total) dst0[(long long)pre[r[q]] * W + jj[q]] = v[q];
     }
 }
 
@@ -2455,6 +2485,7 @@ int cv_sp_mask_perms_batch(const CvPermJob* jobs, int n_jobs, void* d_ws, size_t
         CV_REQUIRE(j.nbr && j.perm && j.n > 0 && j.K > 0 && j.groups >= 1 && j.groups <= j.K, CV_EINVAL,
                    "bad mask perm job %d", i);
         CV_REQUIRE((j.K + j.groups - 1) / j.groups <= 10, CV_EINVAL, "at most 10 kernel offsets per group");
+        CV_REQUIRE(!j.mask_words || j.K <= 32, CV_EINVAL, "validity words hold at most 32 kernel offsets");
         d.j[i] = j;
         d.group_begin[i] = groups;
         groups += j.groups;

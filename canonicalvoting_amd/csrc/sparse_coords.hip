@@ -358,6 +358,136 @@ __device__ __forceinline__ void map_job(const CvMapJob& jb, int nblk, int blk) {
     }
 }
 
+// 3x3x3 map together with the row's validity word (bit j = entry j >= 0, what the mask orders sort by): 32 lanes per row,
+// 27 of them active, two rows per wave, so that a ballot holds the row's bits; the lookups are those of map_job<27>
+__device__ __forceinline__ void map_rows27(const CvMapJob& jb, int* __restrict__ nbr, const int* __restrict__ compose, int nblk,
+                                           int blk) {
+    const int ts = jb.ts;
+    const long long mask = jb.cap - 1;
+    BitBox bb;
+    bb.ok = false;
+    if (jb.bitmap && ts == 1) bb = bitbox(jb.bbox);
+    const int lane = threadIdx.x & 63, hl = lane & 31;
+    const int ox = hl % 3 - 1, oy = (hl / 3) % 3 - 1, oz = hl / 9 - 1;
+    for (long long u0 = blk * 8ll; u0 < jb.n_out; u0 += nblk * 8ll) {      // (the bound is the workgroup's: whole waves ballot)
+        const long long u = u0 + (threadIdx.x >> 5);
+        const bool act = u < jb.n_out && hl < 27;
+        int r = -1;
+        if (act) {
+            const int4 c = reinterpret_cast<const int4*>(jb.out_coords)[u];
+            bool probe = true;
+            if (bb.ok) {
+                const long long bit = bitbox_index(bb, c.x, c.y + ox, c.z + oy, c.w + oz);
+                probe = bit >= 0 && ((jb.bitmap[bit >> 5] >> (bit & 31)) & 1u);
+            }
+            if (probe) {
+                const long long slot = table_find(jb.keys, mask, pack_key(c.x, c.y + ox * ts, c.z + oy * ts, c.w + oz * ts));
+                r = slot >= 0 ? jb.vals[slot] : -1;
+                if (compose && r >= 0) r = compose[r];
+            }
+            nbr[u * 27 + hl] = r;
+        }
+        const unsigned long long b = __ballot(r >= 0);
+        if (act && hl == 0 && jb.mask_words) jb.mask_words[u] = (int)((unsigned)(b >> (lane & 32)) & 0x7ffffffu);
+    }
+}
+
+// the 5x5x5 and the 3x3x3 map of one set (ts = 1) in one pass over the bitmap's z-lines.  The bitmap runs z fastest, so the
+// five z-neighbours of a (dx, dy) line are five adjacent bits: a lane owns one of the row's 25 lines (32 lanes per row, two
+// rows per wave), reads the line with one word load (two where it straddles), and probes the table for the set bits only -
+// 2.0 M line reads per 80k-row scene carry what 10.0 M + 2.16 M per-entry bit tests carried, 58 % of the lines are empty,
+// and the probes of a line are independent loads issued together.  Per (row, dz) the row's lanes store 25 consecutive words
+// of the stem map (compose applied) and the nine inner lines 9 consecutive words of the 3x3x3 map (rows as they are) for
+// dz in {-1, 0, 1}; the 27 validity bits of the row come from three ballots.  Without a trusted bitmap (box beyond
+// CV_BITMAP_WORDS, mm[7] == 0, no bitmap at all): the per-entry lookups, decided on the device like map_job does.
+__device__ __forceinline__ void line_job(const CvMapJob& jb, int nblk, int blk) {
+    BitBox bb;
+    bb.ok = false;
+    if (jb.bitmap) bb = bitbox(jb.bbox);
+    if (!bb.ok) {
+        map_job<125>(jb, nblk, blk);
+        map_rows27(jb, jb.nbr3, nullptr, nblk, blk);
+        return;
+    }
+    const long long mask = jb.cap - 1;
+    const int lane = threadIdx.x & 63, hl = lane & 31;
+    const bool line = hl < 25;
+    const int dx = hl % 5 - 2, dy = hl / 5 - 2;
+    const bool inner = line && dx >= -1 && dx <= 1 && dy >= -1 && dy <= 1;     // lanes 6-8, 11-13, 16-18 of the row
+    const int line3 = (dx + 1) + 3 * (dy + 1);
+    for (long long u0 = blk * 8ll; u0 < jb.n_out; u0 += nblk * 8ll) {      // (the bound is the workgroup's: whole waves ballot)
+        const long long u = u0 + (threadIdx.x >> 5);
+        const bool have = u < jb.n_out && line;
+        int4 c = make_int4(0, 0, 0, 0);
+        unsigned m5 = 0;                    // bit k: the voxel at dz = k - 2 of this line exists
+        if (have) {
+            c = reinterpret_cast<const int4*>(jb.out_coords)[u];
+            const int ux = c.y + dx - bb.mn[0], uy = c.z + dy - bb.mn[1], uz = c.w - bb.mn[2];
+            const int zlo = max(uz - 2, 0), zhi = min(uz + 2, bb.d[2] - 1);        // the part of the line inside the box
+            if ((unsigned)ux < (unsigned)bb.d[0] && (unsigned)uy < (unsigned)bb.d[1] && (unsigned)c.x < (unsigned)bb.nb &&
+                zlo <= zhi) {
+                const long long first = (((long long)c.x * bb.d[0] + ux) * bb.d[1] + uy) * bb.d[2] + zlo;
+                const int sh = (int)(first & 31), nbits = zhi - zlo + 1;
+                unsigned long long v = jb.bitmap[first >> 5];
+                if (sh + nbits > 32) v |= (unsigned long long)jb.bitmap[(first >> 5) + 1] << 32;
+                m5 = ((unsigned)(v >> sh) & ((1u << nbits) - 1u)) << (zlo - (uz - 2));
+            }
+        }
+        // probes of the set bits: every load below is issued for all five dz at once (a clear bit reads slot 0 and drops it;
+        // so do the seven idle lanes of a row and a tail row - 22 % of a wave's lanes, all on the same cached words: the loads
+        // stay unconditional so that the five of a lane leave together instead of one branch and one round trip per dz)
+        unsigned long long key[5], kk[5];
+        long long sl[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            key[k] = pack_key(c.x, c.y + dx, c.z + dy, c.w + k - 2);
+            sl[k] = ((m5 >> k) & 1u) ? (long long)(mix64(key[k]) & (unsigned long long)mask) : 0;
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k) kk[k] = jb.keys[sl[k]];
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+            if ((m5 >> k) & 1u)
+                while (kk[k] != key[k] && kk[k] != EMPTY_KEY) {       // linear probing past a collision
+                    sl[k] = (sl[k] + 1) & mask;
+                    kk[k] = jb.keys[sl[k]];
+                }
+        int r[5], rc[5];
+        bool hit[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            hit[k] = ((m5 >> k) & 1u) && kk[k] == key[k];
+            r[k] = jb.vals[hit[k] ? sl[k] : 0];
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            r[k] = hit[k] ? r[k] : -1;
+            rc[k] = r[k];
+        }
+        if (jb.compose) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) rc[k] = jb.compose[r[k] >= 0 ? r[k] : 0];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) rc[k] = r[k] >= 0 ? rc[k] : -1;
+        }
+        if (have) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) jb.nbr[u * 125 + k * 25 + hl] = rc[k];
+        }
+        if (have && inner) {
+#pragma unroll
+            for (int k = 1; k < 4; ++k) jb.nbr3[u * 27 + (k - 1) * 9 + line3] = r[k];
+        }
+        unsigned w = 0;
+#pragma unroll
+        for (int k = 1; k < 4; ++k) {
+            const unsigned h = (unsigned)(__ballot(have && inner && r[k] >= 0) >> (lane & 32));
+            w |= (((h >> 6) & 7u) | (((h >> 11) & 7u) << 3) | (((h >> 16) & 7u) << 6)) << ((k - 1) * 9);
+        }
+        if (have && hl == 0 && jb.mask_words) jb.mask_words[u] = (int)w;
+    }
+}
+
 // transposed k2s2 map by lookup: fine row f -> its parent's row in the octant column (no pre-fill, no down map needed)
 __device__ __forceinline__ void up_job(const CvMapJob& jb, int nblk, int blk) {
     const long long mask = jb.cap - 1;
@@ -384,6 +514,8 @@ __global__ __launch_bounds__(256) void build_kernel_maps(const MapJobsDev jobs) 
     const CvMapJob& jb = jobs.j[ji];
     const int nblk = jobs.block_begin[ji + 1] - jobs.block_begin[ji], blk = blockIdx.x - jobs.block_begin[ji];
     if (jb.up) { up_job(jb, nblk, blk); return; }
+    if (jb.nbr3) { line_job(jb, nblk, blk); return; }
+    if (jb.mask_words) { map_rows27(jb, jb.nbr, jb.compose, nblk, blk); return; }
     switch (jb.k) {
         case 5: map_job<125>(jb, nblk, blk); break;
         case 3: map_job<27>(jb, nblk, blk); break;
@@ -839,9 +971,13 @@ int cv_sp_kernel_maps_batch(const CvMapJob* jobs, int n_jobs, void* stream) {
         const CvMapJob& j = jobs[i];
         CV_REQUIRE(j.out_coords && j.keys && j.vals && j.nbr && j.n_out > 0 && j.k >= 1 && j.k <= 7 && j.ts >= 1,
                    CV_EINVAL, "bad kernel map job %d", i);
+        CV_REQUIRE(!j.nbr3 || (j.k == 5 && j.ts == 1 && !j.up), CV_EINVAL, "job %d: the combined 5x5x5 + 3x3x3 map is a ts = 1 map", i);
+        CV_REQUIRE(!j.mask_words || j.nbr3 || (j.k == 3 && !j.up), CV_EINVAL, "job %d: validity words belong to a 3x3x3 map", i);
         d.j[i] = j;
         d.block_begin[i] = total;
-        total += j.up ? grid_for(j.n_out) : grid_for(j.n_out * j.k * j.k * j.k);
+        // (nbr3 / mask_words: 32 lanes per row, 8 rows per workgroup and turn; one turn up to 131072 rows)
+        total += j.up ? grid_for(j.n_out) : (j.nbr3 || j.mask_words) ? (int)std::min<long long>((j.n_out + 7) / 8, 16384)
+                                                                       : grid_for(j.n_out * j.k * j.k * j.k);
     }
     d.block_begin[n_jobs] = total;
     build_kernel_maps<<<total, 256, 0, static_cast<hipStream_t>(stream)>>>(d);

@@ -397,6 +397,8 @@ int cv_sp_get_option(const char* name, long long* value);
  *                            sorted <- original permutation of cv_sp_sort_rows, folded in)
  *   out                      always -1: the caller's rows <- sorted rows map is cv_sp_sort_rows' d_inv
  *   down[i] [rows(i+1)][8]   k2s2 conv level i -> i+1;   k3[i] [rows(i)][27];   up[i] [rows(3-i)][8] level 4-i -> 3-i
+ *                            (behind k3[i]: rows(i) validity words, bit j = k3[i][row][j] >= 0, at k3[i] + 27 * rows(i);
+ *                            written for level 0 and for the levels that have a mask_perm)
  *   mask_perm[i] [groups][rows(i)] for levels with >= masked_min_rows rows;  up_perm[i] [rows(3-i)] octant order
  * d_coords / d_keys / d_vals: the five levels of the (Z-order sorted) coordinate set from cv_sp_build_levels. */
 typedef struct cv_scene_maps {
