@@ -15,7 +15,7 @@ c_int_p = ctypes.POINTER(ctypes.c_int)
 c_i32_p = ctypes.POINTER(ctypes.c_int32)
 c_i64_p = ctypes.POINTER(ctypes.c_int64)
 vp = ctypes.c_void_p
-ABI_VERSION = 3          # CV_ABI_VERSION of include/cv_hip.h that these ctypes signatures were written against
+ABI_VERSION = 4          # CV_ABI_VERSION of include/cv_hip.h that these ctypes signatures were written against
 
 
 class CvError(RuntimeError):
@@ -50,6 +50,17 @@ class SceneMaps(ctypes.Structure):
     _fields_ = [("stem", ctypes.c_longlong), ("out", ctypes.c_longlong), ("down", ctypes.c_longlong * 4),
                 ("k3", ctypes.c_longlong * 5), ("up", ctypes.c_longlong * 4), ("mask_perm", ctypes.c_longlong * 5),
                 ("up_perm", ctypes.c_longlong * 4), ("scratch", ctypes.c_longlong), ("bitmap", ctypes.c_longlong)]
+
+
+class ScenePlanLayout(ctypes.Structure):
+    """struct cv_scene_plan_layout (include/cv_hip.h): int32-word offsets of a scene plan's buffers"""
+    _fields_ = [("cap", ctypes.c_longlong), ("perm", ctypes.c_longlong), ("inv", ctypes.c_longlong),
+                ("coords", ctypes.c_longlong * 5), ("vals", ctypes.c_longlong * 5), ("counts", ctypes.c_longlong),
+                ("arena", ctypes.c_longlong), ("int_words", ctypes.c_longlong), ("key_words", ctypes.c_longlong),
+                ("sort_ws_bytes", ctypes.c_size_t), ("levels_ws_bytes", ctypes.c_size_t)]
+
+
+NET_MAP_SLOTS, NET_PERM_SLOTS = 15, 9      # CV_NET_MAP_SLOTS, CV_NET_PERM_SLOTS
 
 
 class NetBuf(ctypes.Structure):
@@ -202,6 +213,11 @@ SIGNATURES = {
                                         ctypes.POINTER(vp), ctypes.c_longlong, vp, c_i32_p, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_longlong, vp, ctypes.c_size_t, ctypes.POINTER(SceneMaps), vp,
                                         ctypes.c_size_t, vp, ctypes.c_size_t, vp]),
+    "cv_sp_scene_plan_layout": (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
+                                               ctypes.POINTER(ScenePlanLayout)]),
+    "cv_sp_scene_plan_slots": (ctypes.c_int, [ctypes.POINTER(ScenePlanLayout), ctypes.POINTER(SceneMaps), c_i64_p,
+                                              ctypes.c_longlong, vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]),
+    "cv_sp_scene_conv_workspace_bytes": (ctypes.c_size_t, [c_i64_p, c_int_p, ctypes.c_int, ctypes.c_int]),
     "cv_net_arena_bytes": (ctypes.c_size_t, [ctypes.POINTER(NetBuf), ctypes.c_int, c_i64_p, ctypes.c_int]),
     "cv_net_run_f32": (ctypes.c_int, [ctypes.POINTER(NetOp), ctypes.c_int, ctypes.POINTER(NetBuf), ctypes.c_int,
                                       c_i64_p, ctypes.c_int, vp, ctypes.c_size_t, ctypes.POINTER(vp), c_int_p,

@@ -199,6 +199,46 @@ size_t cv_sp_scene_plan_words(long long n, int stem_k, int mask_groups, long lon
     return total;
 }
 
+int cv_sp_scene_plan_layout(long long n, int stem_k, int mask_groups, long long masked_min_rows, cv_scene_plan_layout* out) {
+    CV_REQUIRE(out && n > 0, CV_EINVAL, "bad scene plan layout arguments");
+    auto up64 = [](long long v) { return (v + 63) / 64 * 64; };
+    cv_scene_plan_layout& l = *out;
+    l.cap = cv_sp_table_capacity(n);
+    l.perm = 0, l.inv = up64(n);
+    for (int i = 0; i < 5; ++i) l.coords[i] = l.inv + up64(n) + i * up64(4 * n);
+    for (int i = 0; i < 5; ++i) l.vals[i] = l.coords[4] + up64(4 * n) + i * up64(l.cap);
+    l.counts = l.vals[4] + up64(l.cap), l.arena = l.counts + 64;
+    l.int_words = l.arena + (long long)cv_sp_scene_plan_words(n, stem_k, mask_groups, masked_min_rows);
+    l.key_words = 5 * l.cap;
+    l.sort_ws_bytes = cv_sp_sort_workspace_bytes(n), l.levels_ws_bytes = cv_sp_levels_workspace_bytes(n);
+    return CV_OK;
+}
+
+int cv_sp_scene_plan_slots(const cv_scene_plan_layout* layout, const cv_scene_maps* offsets, const long long* level_rows,
+                           long long min_rows, const int32_t* d_ibuf, const int32_t** maps, const int32_t** perms) {
+    CV_REQUIRE(layout && offsets && level_rows && maps && perms, CV_EINVAL, "null pointer argument");
+    const cv_scene_maps& off = *offsets;
+    const int32_t* ap = d_ibuf + layout->arena;
+    maps[0] = ap + off.stem;
+    for (int i = 0; i < 4; ++i) maps[1 + i] = ap + off.down[i];
+    for (int i = 0; i < 5; ++i) maps[5 + i] = ap + off.k3[i];
+    for (int i = 0; i < 4; ++i) maps[10 + i] = ap + off.up[i];
+    maps[14] = d_ibuf + layout->inv;
+    for (int i = 0; i < 5; ++i) perms[i] = (off.mask_perm[i] >= 0 && level_rows[i] >= min_rows) ? ap + off.mask_perm[i] : nullptr;
+    for (int i = 0; i < 4; ++i) perms[5 + i] = ap + off.up_perm[i];
+    return CV_OK;
+}
+
+size_t cv_sp_scene_conv_workspace_bytes(const long long* level_rows, const int* masked, int mask_groups, int max_channels) {
+    if (!level_rows || !masked) return 0;
+    size_t bytes = 0;
+    for (int i = 0; i < 5; ++i) {
+        if (masked[i]) bytes = std::max(bytes, (size_t)4 * mask_groups * (size_t)level_rows[i] * max_channels + 256);
+        bytes = std::max(bytes, cv_sp_conv_workspace_bytes(std::min<long long>(level_rows[i], 128 * 384 - 1), max_channels, 27));
+    }
+    return bytes;
+}
+
 int cv_sp_scene_plan(const int32_t* d_input, long long n, int32_t* d_perm, int32_t* d_inv, int32_t* const* d_coords,
                      unsigned long long* const* d_keys, int32_t* const* d_vals, long long cap, int32_t* d_counts,
                      int32_t* h_counts, int stem_k, int mask_groups, long long masked_min_rows, int32_t* d_arena,

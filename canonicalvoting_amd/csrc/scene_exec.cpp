@@ -21,8 +21,6 @@
 
 namespace {
 
-inline size_t up64(size_t v) { return (v + 63) / 64 * 64; }
-
 struct Carver {
     char* base; size_t off = 0, cap;
     Carver(void* p, size_t c) : base(static_cast<char*>(p)), cap(c) {}
@@ -57,6 +55,98 @@ struct SceneCount {
     }
 };
 
+// stage marks (the caller's events, recorded on the stream) and host laps (result.host_us) of one scene call
+struct StageClock {
+    void* const* events; hipStream_t st; float* host_us;
+    std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+    hipError_t mark(int i) const { return events[i] ? hipEventRecord(static_cast<hipEvent_t>(events[i]), st) : hipSuccess; }
+    void lap(int i) {
+        const auto t = std::chrono::steady_clock::now();
+        host_us[i] += std::chrono::duration<float, std::micro>(t - t_prev).count();
+        t_prev = t;
+    }
+};
+
+// The front of a scene call, the same for the joint and the separate mode: bounds of the points, coordinate plan, level
+// sizes, vote grid shape, and what the network programs need from them.
+struct SceneFront {
+    // from either descriptor
+    const int32_t* d_coords4; long long n; const float* d_points; float res;
+    int stem_k, mask_groups; long long masked_min_rows; int max_channels;
+    float* h_minmax;                    // pinned: 6 floats (the landing words of the range flags follow at +64 bytes)
+    // carve(): the plan's buffers (cv_sp_scene_plan_layout)
+    cv_scene_plan_layout lay;
+    void* mm_ws; int32_t* ibuf; unsigned long long* kbuf; char* sort_ws; char* lev_ws;
+    // run()
+    cv_scene_maps off;
+    long long rows[5];
+    float mn[3]; int dims[3]; size_t cells;
+    const int32_t* maps[CV_NET_MAP_SLOTS]; const int32_t* perms[CV_NET_PERM_SLOTS];
+    size_t conv_ws_b;
+
+    template <class D> explicit SceneFront(const D* d)
+        : d_coords4(d->d_coords4), n(d->n), d_points(d->d_points), res(d->res), stem_k(d->stem_k), mask_groups(d->mask_groups),
+          masked_min_rows(d->masked_min_rows), max_channels(d->max_channels), h_minmax(static_cast<float*>(d->h_pinned)) {}
+
+    // the first five carves of both modes; false when one of them did not fit
+    bool carve(Carver& cv) {
+        mm_ws = cv.take<char>(cv_hv_minmax_workspace_bytes());
+        cv_sp_scene_plan_layout(n, stem_k, mask_groups, masked_min_rows, &lay);
+        ibuf = cv.take<int32_t>((size_t)lay.int_words);
+        kbuf = cv.take<unsigned long long>((size_t)lay.key_words);
+        sort_ws = cv.take<char>(lay.sort_ws_bytes);
+        lev_ws = cv.take<char>(lay.levels_ws_bytes);
+        return mm_ws && ibuf && kbuf && sort_ws && lev_ws;
+    }
+
+    // d_zero_word: a device word that the bounds reduction's final launch zeroes on its way (or NULL)
+    template <class R> int run(int32_t* d_zero_word, R* r, StageClock& clock, void* stream) {
+        // ---- bounds of the points (the vote grid's origin and shape): reduced first, read after the plan's own host wait
+        // (the one-workgroup final launch of the bounds also fills the eight bound words at the head of the sort's workspace)
+        int rc = cv_hv_minmax_async_ex(d_points, n, h_minmax, mm_ws, cv_hv_minmax_workspace_bytes(), d_zero_word,
+                                       reinterpret_cast<int32_t*>(sort_ws), stream);
+        if (rc != CV_OK) return rc;
+        int32_t *c_coords[5], *c_vals[5];
+        unsigned long long* c_keys[5];
+        for (int i = 0; i < 5; ++i) {
+            c_coords[i] = ibuf + lay.coords[i];
+            c_keys[i] = kbuf + (size_t)lay.cap * i;
+            c_vals[i] = ibuf + lay.vals[i];
+        }
+        int32_t counts_h[8] = {0};
+        rc = cv_sp_scene_plan_ex(d_coords4, n, ibuf + lay.perm, ibuf + lay.inv, c_coords, c_keys, c_vals, lay.cap, ibuf + lay.counts,
+                                 counts_h, stem_k, mask_groups, masked_min_rows, ibuf + lay.arena, (size_t)(lay.int_words - lay.arena),
+                                 &off, sort_ws, lay.sort_ws_bytes, lev_ws, lay.levels_ws_bytes,
+                                 /* one scene: the sort skips its batch digit */ true, stream, /* bound words filled above */ true);
+        if (rc != CV_OK) return rc;
+        r->duplicates = counts_h[5];
+        r->out_of_window = counts_h[6];
+        CV_REQUIRE(counts_h[5] == 0 && counts_h[6] == 0, CV_EINVAL,
+                   "duplicate coordinates (%d) or coordinates outside the 16-bit key window (%d)", counts_h[5], counts_h[6]);
+        clock.lap(0);
+        for (int i = 0; i < 5; ++i) { rows[i] = counts_h[i]; r->level_rows[i] = counts_h[i]; }
+        // (the plan waited for an event recorded behind the bounds reduction: the pinned bounds are valid)
+        float mx[3];
+        for (int k = 0; k < 3; ++k) { mn[k] = h_minmax[k]; mx[k] = h_minmax[3 + k]; r->corner[k] = mn[k]; }
+        rc = cv_hv_grid_dims_f32(mn, mx, res, dims);
+        if (rc != CV_OK) return rc;
+        for (int k = 0; k < 3; ++k) r->dims[k] = dims[k];
+        cells = (size_t)dims[0] * dims[1] * dims[2];
+        // ---- for the network programs: map / order slots (mask orders NULL below masked_min_rows) and the convolution workspace
+        int masked[5];
+        for (int i = 0; i < 5; ++i) masked[i] = off.mask_perm[i] >= 0;
+        conv_ws_b = cv_sp_scene_conv_workspace_bytes(rows, masked, mask_groups, max_channels);
+        return cv_sp_scene_plan_slots(&lay, &off, rows, masked_min_rows, ibuf, maps, perms);
+    }
+};
+
+// the part of the workspace that depends on the level sizes is not known yet: ask for the fixed part plus a generous guess
+template <class R> int fixed_part_too_small(R* r, size_t fixed_end) {
+    r->needed_ws_bytes = fixed_end * 2 + ((size_t)256 << 20);
+    cv_set_error("scene workspace too small (needs at least %zu bytes)", r->needed_ws_bytes);
+    return CV_ENOMEM;
+}
+
 }  // namespace
 
 extern "C" {
@@ -71,96 +161,34 @@ int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream
                CV_EINVAL, "null result arrays");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long n = d->n;
-    const int NL = 5;
     std::memset(r, 0, sizeof(*r));
     CV_REQUIRE(d->conv_split_target >= 0 && d->vote_part_records >= 0, CV_EINVAL, "negative launch sizing");
     SceneCount in_flight(d->adaptive_split != 0, d->conv_split_target, d->vote_part_records);
     r->scenes_in_flight = in_flight.before + 1;
     Carver cv(d->d_ws, d->ws_bytes);
-    auto mark = [&](int i) { return d->events[i] ? hipEventRecord(static_cast<hipEvent_t>(d->events[i]), st) : hipSuccess; };
-    auto t_prev = std::chrono::steady_clock::now();
-    auto lap = [&](int i) {
-        const auto t = std::chrono::steady_clock::now();
-        r->host_us[i] += std::chrono::duration<float, std::micro>(t - t_prev).count();
-        t_prev = t;
-    };
-    CV_HIP_CHECK(mark(0));
+    StageClock clock{d->events, st, r->host_us};
+    CV_HIP_CHECK(clock.mark(0));
 
-    // ---- bounds of the points (the vote grid's origin and shape): reduced first, read after the plan's own host wait
-    float* h_minmax = static_cast<float*>(d->h_pinned);               // 6 floats; [8] = range flag landing word
-    int32_t* h_flag = reinterpret_cast<int32_t*>(static_cast<char*>(d->h_pinned) + 64);
-    void* mm_ws = cv.take<char>(cv_hv_minmax_workspace_bytes());
-    // ---- coordinate plan buffers (the layout of CoordinateManager.fused_fast)
-    const long long cap = cv_sp_table_capacity(n);
-    const size_t words = cv_sp_scene_plan_words(n, d->stem_k, d->mask_groups, d->masked_min_rows);
-    const size_t o_perm = 0, o_inv = up64((size_t)n);
-    size_t o_coords[NL], o_vals[NL];
-    for (int i = 0; i < NL; ++i) o_coords[i] = o_inv + up64((size_t)n) + (size_t)i * up64(4 * (size_t)n);
-    for (int i = 0; i < NL; ++i) o_vals[i] = o_coords[NL - 1] + up64(4 * (size_t)n) + (size_t)i * up64((size_t)cap);
-    const size_t o_counts = o_vals[NL - 1] + up64((size_t)cap), o_arena = o_counts + 64;
-    int32_t* ibuf = cv.take<int32_t>(o_arena + words);
-    unsigned long long* kbuf = cv.take<unsigned long long>((size_t)NL * (size_t)cap);
-    const size_t sws_b = cv_sp_sort_workspace_bytes(n), lws_b = cv_sp_levels_workspace_bytes(n);
-    char* sort_ws = cv.take<char>(sws_b);
-    char* lev_ws = cv.take<char>(lws_b);
+    SceneFront f(d);
+    int32_t* h_flag = reinterpret_cast<int32_t*>(static_cast<char*>(d->h_pinned) + 64);      // range flag landing word
+    const bool plan_fits = f.carve(cv);
     float* xyz = cv.take<float>((size_t)n * 3);
     float* scale = cv.take<float>((size_t)n * 3);
     float* prob = cv.take<float>((size_t)n);
     int32_t* cls = cv.take<int32_t>((size_t)n);
     int32_t* d_flag = cv.take<int32_t>(64);
-    const size_t fixed_end = cv.off;
-    if (!mm_ws || !ibuf || !kbuf || !sort_ws || !lev_ws || !xyz || !scale || !prob || !cls || !d_flag) {
-        // the part that depends on the level sizes is not known yet: ask for the fixed part plus a generous guess
-        r->needed_ws_bytes = fixed_end * 2 + ((size_t)256 << 20);
-        CV_REQUIRE(false, CV_ENOMEM, "scene workspace too small (needs at least %zu bytes)", r->needed_ws_bytes);
-    }
-    // (the one-workgroup final launch of the bounds also zeroes the range flag and fills the eight bound words at the head of the
-    // sort's workspace: two fill launches fewer)
-    int rc = cv_hv_minmax_async_ex(d->d_points, n, h_minmax, mm_ws, cv_hv_minmax_workspace_bytes(), d_flag,
-                                   reinterpret_cast<int32_t*>(sort_ws), stream);
+    if (!plan_fits || !xyz || !scale || !prob || !cls || !d_flag) return fixed_part_too_small(r, cv.off);
+    // (the bounds reduction zeroes the range flag: no fill launch)
+    int rc = f.run(d_flag, r, clock, stream);
     if (rc != CV_OK) return rc;
-
-    int32_t* c_coords[NL];
-    unsigned long long* c_keys[NL];
-    int32_t* c_vals[NL];
-    for (int i = 0; i < NL; ++i) {
-        c_coords[i] = ibuf + o_coords[i];
-        c_keys[i] = kbuf + (size_t)cap * i;
-        c_vals[i] = ibuf + o_vals[i];
-    }
-    int32_t counts_h[8] = {0};
-    cv_scene_maps off;
-    rc = cv_sp_scene_plan_ex(d->d_coords4, n, ibuf + o_perm, ibuf + o_inv, c_coords, c_keys, c_vals, cap, ibuf + o_counts, counts_h,
-                          d->stem_k, d->mask_groups, d->masked_min_rows, ibuf + o_arena, words, &off, sort_ws, sws_b, lev_ws, lws_b, /* one scene: the sort skips its batch digit */ true,
-                          stream, /* bound words filled above */ true);
-    if (rc != CV_OK) return rc;
-    r->duplicates = counts_h[5];
-    r->out_of_window = counts_h[6];
-    CV_REQUIRE(counts_h[5] == 0 && counts_h[6] == 0, CV_EINVAL,
-               "duplicate coordinates (%d) or coordinates outside the 16-bit key window (%d)", counts_h[5], counts_h[6]);
-    lap(0);
-    long long rows[NL];
-    for (int i = 0; i < NL; ++i) { rows[i] = counts_h[i]; r->level_rows[i] = counts_h[i]; }
-    // (the plan waited for an event recorded behind the bounds reduction: the pinned bounds are valid)
-    float mn[3], mx[3];
-    for (int k = 0; k < 3; ++k) { mn[k] = h_minmax[k]; mx[k] = h_minmax[3 + k]; r->corner[k] = mn[k]; }
-    int dims[3];
-    rc = cv_hv_grid_dims_f32(mn, mx, d->res, dims);
-    if (rc != CV_OK) return rc;
-    for (int k = 0; k < 3; ++k) r->dims[k] = dims[k];
-    const size_t cells = (size_t)dims[0] * dims[1] * dims[2];
+    const size_t cells = f.cells;
 
     // ---- what depends on the level sizes and the grid shape
-    const size_t arena_b = cv_net_arena_bytes(d->bufs, d->n_bufs, rows, NL);
-    size_t conv_ws_b = 0;
-    for (int i = 0; i < NL; ++i) {
-        if (off.mask_perm[i] >= 0) conv_ws_b = std::max(conv_ws_b, (size_t)4 * d->mask_groups * (size_t)rows[i] * d->max_channels + 256);
-        conv_ws_b = std::max(conv_ws_b, cv_sp_conv_workspace_bytes(std::min<long long>(rows[i], 128 * 384 - 1), d->max_channels, 27));
-    }
-    const size_t vote_ws_b = cv_hv_forward_workspace_bytes(n, d->num_rots, dims, d->vote_algo);
-    const size_t dec_ws_b = cv_decode_workspace_bytes(dims, n, d->max_candidates);
+    const size_t arena_b = cv_net_arena_bytes(d->bufs, d->n_bufs, f.rows, 5);
+    const size_t vote_ws_b = cv_hv_forward_workspace_bytes(n, d->num_rots, f.dims, d->vote_algo);
+    const size_t dec_ws_b = cv_decode_workspace_bytes(f.dims, n, d->max_candidates);
     char* arena = cv.take<char>(arena_b);
-    char* conv_ws = cv.take<char>(conv_ws_b);
+    char* conv_ws = cv.take<char>(f.conv_ws_b);
     char* vote_ws = cv.take<char>(std::max<size_t>(vote_ws_b, 256));
     char* dec_ws = cv.take<char>(dec_ws_b);
     float* grids = d->d_grids ? d->d_grids : cv.take<float>(6 * cells);
@@ -173,46 +201,35 @@ int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream
     float* g_scale = grids + 3 * cells;
     r->d_grid_obj = g_obj; r->d_grid_rot = g_rot; r->d_grid_scale = g_scale;
 
-    // ---- network forward: the program's map / order slots are [stem, down 0-3, k3 0-4, up 0-3, out] and
-    //      [mask orders of levels 0-4 (NULL below masked_min_rows), octant orders of the four transposed convs]
-    const int32_t* ap = ibuf + o_arena;
-    const int32_t* maps[15];
-    maps[0] = ap + off.stem;
-    for (int i = 0; i < 4; ++i) maps[1 + i] = ap + off.down[i];
-    for (int i = 0; i < 5; ++i) maps[5 + i] = ap + off.k3[i];
-    for (int i = 0; i < 4; ++i) maps[10 + i] = ap + off.up[i];
-    maps[14] = ibuf + o_inv;
-    const int32_t* perms[9];
-    for (int i = 0; i < 5; ++i) perms[i] = (off.mask_perm[i] >= 0 && rows[i] >= d->masked_min_rows) ? ap + off.mask_perm[i] : nullptr;
-    for (int i = 0; i < 4; ++i) perms[5 + i] = ap + off.up_perm[i];
+    // ---- network forward
     const void* ext_ptr[2] = {d->d_feats, d->d_out_feats};
     const int ext_ld[2] = {d->feats_ld, d->out_ld};
-    rc = cv_net_run_f32(d->ops, d->n_ops, d->bufs, d->n_bufs, rows, NL, arena, arena_b, ext_ptr, ext_ld, maps, 15, perms, 9, conv_ws,
-                        conv_ws_b, d->use_range_flag ? d_flag : nullptr, stream);
+    rc = cv_net_run_f32(d->ops, d->n_ops, d->bufs, d->n_bufs, f.rows, 5, arena, arena_b, ext_ptr, ext_ld, f.maps, CV_NET_MAP_SLOTS,
+                        f.perms, CV_NET_PERM_SLOTS, conv_ws, f.conv_ws_b, d->use_range_flag ? d_flag : nullptr, stream);
     if (rc != CV_OK) return rc;
-    lap(1);
-    CV_HIP_CHECK(mark(1));
+    clock.lap(1);
+    CV_HIP_CHECK(clock.mark(1));
     rc = cv_head_joint_f32(d->d_out_feats, n, d->out_ld, d->nclasses, d->log_scale, xyz, scale, prob, cls, stream);
     if (rc != CV_OK) return rc;
     if (d->use_range_flag) CV_HIP_CHECK(hipMemcpyAsync(h_flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     r->d_xyz = xyz; r->d_scale = scale; r->d_prob = prob; r->d_class = cls;
-    CV_HIP_CHECK(mark(2));
+    CV_HIP_CHECK(clock.mark(2));
 
     // ---- vote + decode, on the network's predictions or on the caller's (bench.py --predictions teacher)
     const float* v_xyz = d->d_xyz_in ? d->d_xyz_in : xyz;
     const float* v_scale = d->d_scale_in ? d->d_scale_in : scale;
     const float* v_prob = d->d_prob_in ? d->d_prob_in : prob;
     const int32_t* v_cls = d->d_class_in ? d->d_class_in : cls;
-    rc = cv_hv_forward_f32(d->d_points, v_xyz, v_scale, v_prob, n, d->res, d->num_rots, mn, dims, g_obj, g_rot, g_scale, vote_ws,
+    rc = cv_hv_forward_f32(d->d_points, v_xyz, v_scale, v_prob, n, d->res, d->num_rots, f.mn, f.dims, g_obj, g_rot, g_scale, vote_ws,
                            std::max<size_t>(vote_ws_b, 256), d->vote_algo, stream);
     if (rc != CV_OK) return rc;
-    CV_HIP_CHECK(mark(3));
-    lap(2);
+    CV_HIP_CHECK(clock.mark(3));
+    clock.lap(2);
     cv_decode_params prm = d->decode;
     prm.max_iters = d->max_candidates;
     int n_cand = 0, n_boxes = 0, truncated = 0;
     // (events[4] is recorded behind the decode's last launch, in front of its host wait: a device time)
-    rc = cv_decode_f32_ev(g_obj, g_rot, g_scale, dims, mn, d->res, d->d_points, v_xyz, v_prob, v_cls, n, &prm, 0, dec_ws, dec_ws_b, &n_cand,
+    rc = cv_decode_f32_ev(g_obj, g_rot, g_scale, f.dims, f.mn, d->res, d->d_points, v_xyz, v_prob, v_cls, n, &prm, 0, dec_ws, dec_ws_b, &n_cand,
                           d->h_cand_idx, d->h_verdict, &n_boxes, d->h_boxes, d->h_scores, d->h_classes, &truncated, stream, d->events[4]);
     if (rc != CV_OK) return rc;
     r->n_cand = n_cand;
@@ -240,7 +257,7 @@ int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream
         for (int j = 0; j < k; ++j) d->h_pick[n_det++] = idx[(size_t)pick[j]];
     }
     r->n_det = n_det;
-    lap(3);
+    clock.lap(3);
     return CV_OK;
 }
 
@@ -265,88 +282,32 @@ int cv_detect_scene_separate_f32(const cv_scene_separate_desc* d, cv_scene_separ
     CV_REQUIRE(d->conv_split_target >= 0 && d->vote_part_records >= 0, CV_EINVAL, "negative launch sizing");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long n = d->n;
-    const int NL = 5;
     SceneCount in_flight(false, d->conv_split_target, d->vote_part_records);
     Carver cv(d->d_ws, d->ws_bytes);
-    auto mark = [&](int i) { return d->events[i] ? hipEventRecord(static_cast<hipEvent_t>(d->events[i]), st) : hipSuccess; };
-    auto t_prev = std::chrono::steady_clock::now();
-    auto lap = [&](int i) {
-        const auto t = std::chrono::steady_clock::now();
-        r->host_us[i] += std::chrono::duration<float, std::micro>(t - t_prev).count();
-        t_prev = t;
-    };
-    CV_HIP_CHECK(mark(0));
+    StageClock clock{d->events, st, r->host_us};
+    CV_HIP_CHECK(clock.mark(0));
 
     // ---- bounds + coordinate plan, exactly as cv_detect_scene_f32 (one plan for all K models)
-    float* h_minmax = static_cast<float*>(d->h_pinned);
+    SceneFront f(d);
     int32_t* h_flags = reinterpret_cast<int32_t*>(static_cast<char*>(d->h_pinned) + 64);     // 16 words per model
-    void* mm_ws = cv.take<char>(cv_hv_minmax_workspace_bytes());
-    const long long cap = cv_sp_table_capacity(n);
-    const size_t words = cv_sp_scene_plan_words(n, d->stem_k, d->mask_groups, d->masked_min_rows);
-    const size_t o_perm = 0, o_inv = up64((size_t)n);
-    size_t o_coords[NL], o_vals[NL];
-    for (int i = 0; i < NL; ++i) o_coords[i] = o_inv + up64((size_t)n) + (size_t)i * up64(4 * (size_t)n);
-    for (int i = 0; i < NL; ++i) o_vals[i] = o_coords[NL - 1] + up64(4 * (size_t)n) + (size_t)i * up64((size_t)cap);
-    const size_t o_counts = o_vals[NL - 1] + up64((size_t)cap), o_arena = o_counts + 64;
-    int32_t* ibuf = cv.take<int32_t>(o_arena + words);
-    unsigned long long* kbuf = cv.take<unsigned long long>((size_t)NL * (size_t)cap);
-    const size_t sws_b = cv_sp_sort_workspace_bytes(n), lws_b = cv_sp_levels_workspace_bytes(n);
-    char* sort_ws = cv.take<char>(sws_b);
-    char* lev_ws = cv.take<char>(lws_b);
+    const bool plan_fits = f.carve(cv);
     float* xyz = cv.take<float>((size_t)K * n * 3);
     float* scale = cv.take<float>((size_t)K * n * 3);
     float* prob = cv.take<float>((size_t)K * n);
     int32_t* d_flags = cv.take<int32_t>(16 * (size_t)K);
-    const size_t fixed_end = cv.off;
-    if (!mm_ws || !ibuf || !kbuf || !sort_ws || !lev_ws || !xyz || !scale || !prob || !d_flags) {
-        r->needed_ws_bytes = fixed_end * 2 + ((size_t)256 << 20);
-        CV_REQUIRE(false, CV_ENOMEM, "scene workspace too small (needs at least %zu bytes)", r->needed_ws_bytes);
-    }
+    if (!plan_fits || !xyz || !scale || !prob || !d_flags) return fixed_part_too_small(r, cv.off);
     if (d->use_range_flag) CV_HIP_CHECK(hipMemsetAsync(d_flags, 0, sizeof(int32_t) * 16 * K, st));
-    int rc = cv_hv_minmax_async_ex(d->d_points, n, h_minmax, mm_ws, cv_hv_minmax_workspace_bytes(), nullptr,
-                                   reinterpret_cast<int32_t*>(sort_ws), stream);
+    int rc = f.run(nullptr, r, clock, stream);
     if (rc != CV_OK) return rc;
-    int32_t* c_coords[NL];
-    unsigned long long* c_keys[NL];
-    int32_t* c_vals[NL];
-    for (int i = 0; i < NL; ++i) {
-        c_coords[i] = ibuf + o_coords[i];
-        c_keys[i] = kbuf + (size_t)cap * i;
-        c_vals[i] = ibuf + o_vals[i];
-    }
-    int32_t counts_h[8] = {0};
-    cv_scene_maps off;
-    rc = cv_sp_scene_plan_ex(d->d_coords4, n, ibuf + o_perm, ibuf + o_inv, c_coords, c_keys, c_vals, cap, ibuf + o_counts, counts_h,
-                             d->stem_k, d->mask_groups, d->masked_min_rows, ibuf + o_arena, words, &off, sort_ws, sws_b, lev_ws, lws_b,
-                             true, stream, true);
-    if (rc != CV_OK) return rc;
-    r->duplicates = counts_h[5];
-    r->out_of_window = counts_h[6];
-    CV_REQUIRE(counts_h[5] == 0 && counts_h[6] == 0, CV_EINVAL,
-               "duplicate coordinates (%d) or coordinates outside the 16-bit key window (%d)", counts_h[5], counts_h[6]);
-    lap(0);
-    long long rows[NL];
-    for (int i = 0; i < NL; ++i) { rows[i] = counts_h[i]; r->level_rows[i] = counts_h[i]; }
-    float mn[3], mx[3];
-    for (int k = 0; k < 3; ++k) { mn[k] = h_minmax[k]; mx[k] = h_minmax[3 + k]; r->corner[k] = mn[k]; }
-    int dims[3];
-    rc = cv_hv_grid_dims_f32(mn, mx, d->res, dims);
-    if (rc != CV_OK) return rc;
-    for (int k = 0; k < 3; ++k) r->dims[k] = dims[k];
-    const size_t cells = (size_t)dims[0] * dims[1] * dims[2];
+    const size_t cells = f.cells;
 
     // ---- what depends on the level sizes and the grid shape: one arena (the largest of the K programs'), K vote / decode carves
     size_t arena_b = 0;
-    for (int k = 0; k < K; ++k) arena_b = std::max(arena_b, cv_net_arena_bytes(d->bufs[k], d->n_bufs[k], rows, NL));
-    size_t conv_ws_b = 0;
-    for (int i = 0; i < NL; ++i) {
-        if (off.mask_perm[i] >= 0) conv_ws_b = std::max(conv_ws_b, (size_t)4 * d->mask_groups * (size_t)rows[i] * d->max_channels + 256);
-        conv_ws_b = std::max(conv_ws_b, cv_sp_conv_workspace_bytes(std::min<long long>(rows[i], 128 * 384 - 1), d->max_channels, 27));
-    }
-    const size_t vote_ws_b = cv_hv_forward_cat_workspace_bytes(n, d->num_rots, dims, d->vote_algo, K);
-    const size_t dec_ws_b = cv_decode_cat_workspace_bytes(dims, n, d->max_candidates, K);
+    for (int k = 0; k < K; ++k) arena_b = std::max(arena_b, cv_net_arena_bytes(d->bufs[k], d->n_bufs[k], f.rows, 5));
+    const size_t vote_ws_b = cv_hv_forward_cat_workspace_bytes(n, d->num_rots, f.dims, d->vote_algo, K);
+    const size_t dec_ws_b = cv_decode_cat_workspace_bytes(f.dims, n, d->max_candidates, K);
     char* arena = cv.take<char>(arena_b);
-    char* conv_ws = cv.take<char>(conv_ws_b);
+    char* conv_ws = cv.take<char>(f.conv_ws_b);
     char* vote_ws = cv.take<char>(std::max<size_t>(vote_ws_b, 256));
     char* dec_ws = cv.take<char>(dec_ws_b);
     float* grids = cv.take<float>(6 * cells * (size_t)K);
@@ -357,26 +318,17 @@ int cv_detect_scene_separate_f32(const cv_scene_separate_desc* d, cv_scene_separ
     float* g_scale = grids + 3 * cells * K;
     r->d_grid_obj = g_obj; r->d_grid_rot = g_rot; r->d_grid_scale = g_scale;
 
-    // ---- K network programs on the shared plan (slot layout as cv_detect_scene_f32)
-    const int32_t* ap = ibuf + o_arena;
-    const int32_t* maps[15];
-    maps[0] = ap + off.stem;
-    for (int i = 0; i < 4; ++i) maps[1 + i] = ap + off.down[i];
-    for (int i = 0; i < 5; ++i) maps[5 + i] = ap + off.k3[i];
-    for (int i = 0; i < 4; ++i) maps[10 + i] = ap + off.up[i];
-    maps[14] = ibuf + o_inv;
-    const int32_t* perms[9];
-    for (int i = 0; i < 5; ++i) perms[i] = (off.mask_perm[i] >= 0 && rows[i] >= d->masked_min_rows) ? ap + off.mask_perm[i] : nullptr;
-    for (int i = 0; i < 4; ++i) perms[5 + i] = ap + off.up_perm[i];
+    // ---- K network programs on the shared plan
     for (int k = 0; k < K; ++k) {
         const void* ext_ptr[2] = {d->d_feats, d->d_out_feats[k]};
         const int ext_ld[2] = {d->feats_ld, d->out_ld};
-        rc = cv_net_run_f32(d->ops[k], d->n_ops[k], d->bufs[k], d->n_bufs[k], rows, NL, arena, arena_b, ext_ptr, ext_ld, maps, 15, perms,
-                            9, conv_ws, conv_ws_b, d->use_range_flag ? d_flags + 16 * k : nullptr, stream);
+        rc = cv_net_run_f32(d->ops[k], d->n_ops[k], d->bufs[k], d->n_bufs[k], f.rows, 5, arena, arena_b, ext_ptr, ext_ld, f.maps,
+                            CV_NET_MAP_SLOTS, f.perms, CV_NET_PERM_SLOTS, conv_ws, f.conv_ws_b,
+                            d->use_range_flag ? d_flags + 16 * k : nullptr, stream);
         if (rc != CV_OK) return rc;
     }
-    lap(1);
-    CV_HIP_CHECK(mark(1));
+    clock.lap(1);
+    CV_HIP_CHECK(clock.mark(1));
     for (int k = 0; k < K; ++k) {
         rc = cv_head_separate_f32(d->d_out_feats[k], n, d->out_ld, d->log_scale, xyz + (size_t)k * n * 3, scale + (size_t)k * n * 3,
                                   prob + (size_t)k * n, stream);
@@ -384,22 +336,22 @@ int cv_detect_scene_separate_f32(const cv_scene_separate_desc* d, cv_scene_separ
     }
     if (d->use_range_flag) CV_HIP_CHECK(hipMemcpyAsync(h_flags, d_flags, sizeof(int32_t) * 16 * K, hipMemcpyDeviceToHost, st));
     r->d_xyz = xyz; r->d_scale = scale; r->d_prob = prob;
-    CV_HIP_CHECK(mark(2));
+    CV_HIP_CHECK(clock.mark(2));
 
     // ---- one vote and one decode over the category axis
     const float* v_xyz = d->d_xyz_in ? d->d_xyz_in : xyz;
     const float* v_scale = d->d_xyz_in ? d->d_scale_in : scale;
     const float* v_prob = d->d_xyz_in ? d->d_prob_in : prob;
-    rc = cv_hv_forward_cat_f32(d->d_points, v_xyz, v_scale, v_prob, n, d->res, d->num_rots, mn, dims, K, g_obj, g_rot, g_scale, vote_ws,
+    rc = cv_hv_forward_cat_f32(d->d_points, v_xyz, v_scale, v_prob, n, d->res, d->num_rots, f.mn, f.dims, K, g_obj, g_rot, g_scale, vote_ws,
                                std::max<size_t>(vote_ws_b, 256), d->vote_algo, stream);
     if (rc != CV_OK) return rc;
-    CV_HIP_CHECK(mark(3));
-    lap(2);
+    CV_HIP_CHECK(clock.mark(3));
+    clock.lap(2);
     cv_decode_params prm = d->decode;
     prm.max_iters = d->max_candidates;
     const int M = d->max_candidates;
     std::vector<int32_t> classes((size_t)K * M);
-    rc = cv_decode_cat_f32_ev(g_obj, g_rot, g_scale, dims, mn, d->res, d->d_points, v_xyz, v_prob, nullptr, n, K, &prm, 0, dec_ws,
+    rc = cv_decode_cat_f32_ev(g_obj, g_rot, g_scale, f.dims, f.mn, d->res, d->d_points, v_xyz, v_prob, nullptr, n, K, &prm, 0, dec_ws,
                               dec_ws_b, r->n_cand, d->h_cand_idx, d->h_verdict, r->n_boxes, d->h_boxes, d->h_scores, classes.data(),
                               r->truncated, stream, d->events[4]);
     if (rc != CV_OK) return rc;
@@ -418,7 +370,7 @@ int cv_detect_scene_separate_f32(const cv_scene_separate_desc* d, cv_scene_separ
         for (int j = 0; j < kept; ++j) { d->h_det_cat[n_det] = k; d->h_det_box[n_det] = pick[(size_t)j]; ++n_det; }
     }
     r->n_det = n_det;
-    lap(3);
+    clock.lap(3);
     return CV_OK;
 }
 

@@ -217,6 +217,11 @@ class CoordinateManager:
     MASKED_MIN_ROWS = int(os.environ.get("CV_MASKED_MIN_ROWS", "16384"))      # process-wide; a thread's own: masked_min_rows()
     LIB_MASKED_MIN_ROWS = MASKED_MIN_ROWS          # the one-scene-at-a-time default (pipeline.policy_for_scenes_in_flight)
 
+    @classmethod
+    def plan_mask_groups(cls):
+        """mask groups the scene plan builds orders for (0: groups too wide for its counting sort - built lazily, mask_perms)"""
+        return cls.MASK_GROUPS if (27 + cls.MASK_GROUPS - 1) // cls.MASK_GROUPS <= 10 else 0
+
     def fused_fast(self, stem_k=5):
         """The coordinate plan of the fused network as raw device pointers (what MinkUNet.program_forward hands to the
         C executor): .counts rows per level, .map_ptrs [stem, down 0-3, k3 0-4, up 0-3, out], .perm_ptrs [mask orders of
@@ -231,44 +236,37 @@ class CoordinateManager:
         dev = self.device
         n = self._input.shape[0]
         NL = CoordinateManager.NUM_LEVELS
-        G = self.MASK_GROUPS if (27 + self.MASK_GROUPS - 1) // self.MASK_GROUPS <= 10 else 0   # wide groups: lazily
-        cap = int(L.cv_sp_table_capacity(n))
-        words = int(L.cv_sp_scene_plan_words(n, stem_k, G, mmr))
-        up64 = lambda v: (v + 63) // 64 * 64
-        # int32 buffer: perm | inv | coords of the 5 levels | table values of the 5 levels | counts | arena (sized for
-        # the worst case, every coarse level bounded by n: the call does not come back between the levels and the maps)
-        o_perm, o_inv = 0, up64(n)
-        o_coords = [o_inv + up64(n) + i * up64(4 * n) for i in range(NL)]
-        o_vals = [o_coords[-1] + up64(4 * n) + i * up64(cap) for i in range(NL)]
-        o_counts = o_vals[-1] + up64(cap)
-        o_arena = o_counts + 64
-        ibuf = torch.empty(o_arena + words, dtype=torch.int32, device=dev)
-        kbuf = torch.empty(NL * cap, dtype=torch.int64, device=dev)
-        sws_b, lws_b = int(L.cv_sp_sort_workspace_bytes(n)), int(L.cv_sp_levels_workspace_bytes(n))
-        wbuf = _lib.scratch(dev, "scene_plan", up64(sws_b) + lws_b)      # sort + level workspaces: dead when the call returns
+        G = self.plan_mask_groups()
+        # int32 buffer perm | inv | coords of 5 levels | table values of 5 levels | counts | arena (cv_sp_scene_plan_layout)
+        lay = _lib.ScenePlanLayout()
+        _lib.check(L.cv_sp_scene_plan_layout(n, stem_k, G, mmr, ctypes.byref(lay)), "cv_sp_scene_plan_layout")
+        ibuf = torch.empty(lay.int_words, dtype=torch.int32, device=dev)
+        kbuf = torch.empty(lay.key_words, dtype=torch.int64, device=dev)
+        sws_b, lws_b = lay.sort_ws_bytes, lay.levels_ws_bytes
+        o_lws = (sws_b + 63) & ~63
+        wbuf = _lib.scratch(dev, "scene_plan", o_lws + lws_b)      # sort + level workspaces: dead when the call returns
         ib, kb, wb = ibuf.data_ptr(), kbuf.data_ptr(), wbuf.data_ptr()
         vp = ctypes.c_void_p
-        c_coords = (vp * NL)(*[ib + 4 * o for o in o_coords])
-        c_keys = (vp * NL)(*[kb + 8 * cap * i for i in range(NL)])
-        c_vals = (vp * NL)(*[ib + 4 * o for o in o_vals])
+        c_coords = (vp * NL)(*[ib + 4 * o for o in lay.coords])
+        c_keys = (vp * NL)(*[kb + 8 * lay.cap * i for i in range(NL)])
+        c_vals = (vp * NL)(*[ib + 4 * o for o in lay.vals])
         counts_h = (ctypes.c_int32 * 8)()
         off = _lib.SceneMaps()
         with _on(dev):
-            _lib.check(L.cv_sp_scene_plan(_ptr(self._input), n, vp(ib + 4 * o_perm), vp(ib + 4 * o_inv), c_coords, c_keys,
-                                          c_vals, cap, vp(ib + 4 * o_counts), counts_h, stem_k, G, mmr,
-                                          vp(ib + 4 * o_arena), words, ctypes.byref(off), vp(wb), sws_b, vp(wb + up64(sws_b)),
-                                          lws_b, _stream(dev)), "cv_sp_scene_plan")
+            _lib.check(L.cv_sp_scene_plan(_ptr(self._input), n, vp(ib + 4 * lay.perm), vp(ib + 4 * lay.inv), c_coords, c_keys,
+                                          c_vals, lay.cap, vp(ib + 4 * lay.counts), counts_h, stem_k, G, mmr,
+                                          vp(ib + 4 * lay.arena), lay.int_words - lay.arena, ctypes.byref(off), vp(wb), sws_b,
+                                          vp(wb + o_lws), lws_b, _stream(dev)), "cv_sp_scene_plan")
         self._raise_on_dups(counts_h[5], counts_h[6])
         plan = _FusedPlan()
         plan.keep = (ibuf, kbuf)
         plan.counts = [int(counts_h[i]) for i in range(NL)]
-        plan.cap, plan.stem_k, plan.groups, plan.off = cap, stem_k, G, off
-        plan.layout = (o_perm, o_inv, o_coords, o_vals, o_counts, o_arena)
-        ap = lambda o: ib + 4 * (o_arena + o)
-        plan.map_ptrs = [ap(off.stem)] + [ap(off.down[i]) for i in range(4)] + [ap(off.k3[i]) for i in range(5)] + \
-                        [ap(off.up[i]) for i in range(4)] + [ib + 4 * o_inv]
-        plan.perm_ptrs = [ap(off.mask_perm[i]) if off.mask_perm[i] >= 0 else None for i in range(5)] + \
-                         [ap(off.up_perm[i]) for i in range(4)]
+        plan.cap, plan.stem_k, plan.groups, plan.off, plan.layout = lay.cap, stem_k, G, off, lay
+        maps, perms = (vp * _lib.NET_MAP_SLOTS)(), (vp * _lib.NET_PERM_SLOTS)()
+        # (every mask order the plan has: the per-model row threshold is applied by MinkUNet.program_forward)
+        _lib.check(L.cv_sp_scene_plan_slots(ctypes.byref(lay), ctypes.byref(off), (ctypes.c_int64 * NL)(*plan.counts), 0, vp(ib),
+                                            maps, perms), "cv_sp_scene_plan_slots")
+        plan.map_ptrs, plan.perm_ptrs = list(maps), list(perms)
         plan.views = None
         cache[(stem_k, mmr)] = plan
         self._fused = plan
@@ -284,12 +282,12 @@ class CoordinateManager:
         if plan.views is None:
             ibuf, kbuf = plan.keep
             n, cap, G, off = self._input.shape[0], plan.cap, plan.groups, plan.off
-            o_perm, o_inv, o_coords, o_vals, o_counts, o_arena = plan.layout
+            lay, o_inv, o_counts, o_arena = plan.layout, plan.layout.inv, plan.layout.counts, plan.layout.arena
             c = plan.counts
             NL = len(c)
-            coords_buf = [ibuf[o:o + 4 * n].view(n, 4) for o in o_coords]
+            coords_buf = [ibuf[o:o + 4 * n].view(n, 4) for o in lay.coords]
             keys = [kbuf[i * cap:(i + 1) * cap] for i in range(NL)]
-            vals = [ibuf[o:o + cap] for o in o_vals]
+            vals = [ibuf[o:o + cap] for o in lay.vals]
             cm_s = CoordinateManager._from_levels(coords_buf, keys, vals, ibuf[o_counts:o_counts + 8], c, cap)
             arena = ibuf[o_arena:]
             view = lambda o, r, k: arena[o:o + r * k].view(r, k)

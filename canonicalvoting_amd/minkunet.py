@@ -437,10 +437,8 @@ class MinkUNetBase(ResNetBase):
         rows = (ctypes.c_int64 * 5)(*n)
         # activations of the executor: scratch of this stream (dead when `y` is written; sizes differ from scene to scene)
         arena = _lib.scratch(dev, "net_arena", L.cv_net_arena_bytes(c_bufs, len(c_bufs), rows, 5))
-        cmax = max(self.PLANES)
-        ws_bytes = max([4 * self.MASK_GROUPS * n[i] * cmax + 256 for i in range(5) if perm_ptrs[i] is not None] +
-                       [int(L.cv_sp_conv_workspace_bytes(min(n[i], 128 * 384 - 1), cmax, 27)) for i in range(5)])
-        ws = ME._workspace(dev, ws_bytes)
+        sorted_levels = (ctypes.c_int * 5)(*[p is not None for p in perm_ptrs[:5]])
+        ws = ME._workspace(dev, L.cv_sp_scene_conv_workspace_bytes(rows, sorted_levels, self.MASK_GROUPS, max(self.PLANES)))
         vp = ctypes.c_void_p
         ext_ptr = (vp * 2)(feats.data_ptr(), y.data_ptr())
         ext_ld = (ctypes.c_int * 2)(feats.stride(0), y.stride(0))

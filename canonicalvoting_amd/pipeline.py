@@ -11,6 +11,8 @@ import torch
 from . import _lib, decode, hv_cuda
 from . import me as ME
 
+vp = ctypes.c_void_p
+
 
 class ScenePolicy(collections.namedtuple("ScenePolicy", "conv_split_target vote_part_records masked_min_rows")):
     """Launch sizing of ONE scene call - the three choices that depend on how many scenes the host keeps in flight:
@@ -164,6 +166,54 @@ def _separate_by_calls(hv, scan_points, xyz, scale, prob, res, categories, overl
     return out
 
 
+def _fill_decode_params(p, decode_kw, separate_variant):
+    """cv_decode_params from the keyword arguments of decode.decode_boxes (separate_variant: the caller's default)"""
+    p.thresh_high = float(decode_kw.get("thresh_high", decode.thresh_high))
+    p.thresh_low = float(decode_kw.get("thresh_low", decode.thresh_low))
+    p.valid_ratio = float(decode_kw.get("valid_ratio", decode.valid_ratio))
+    p.elimination = int(decode_kw.get("elimination", decode.elimination))
+    p.prob_thresh = float(decode_kw.get("prob_thresh", 0.3))
+    p.elim_hi_plus1 = 0 if decode_kw.get("separate_variant", separate_variant) else 1
+    p.err_thresh = float(decode_kw.get("err_thresh", 0.3))
+
+
+def _set_events(d, events):
+    """five recorded torch.cuda.Event (their handles exist): scene start, after the network, the head split, the vote, the decode"""
+    if events is not None:
+        for i in range(5):
+            d.events[i] = events[i].cuda_event
+
+
+def _fill_scene_desc(d, model, hv, coords4, feats, scan_points, res, policy, pieces, max_channels, log_scale):
+    """the fields cv_scene_desc and cv_scene_separate_desc share (model: the one, or the first of the K, that the plan follows)"""
+    d.d_coords4, d.n, d.d_feats, d.feats_ld = vp(coords4.data_ptr()), coords4.shape[0], vp(feats.data_ptr()), feats.stride(0)
+    d.d_points, d.res, d.num_rots = vp(scan_points.data_ptr()), float(res), hv_cuda._scalar(hv.num_rots, "i")
+    d.stem_k, d.mask_groups = model.conv0p1s1.kernel_size, ME.CoordinateManager.plan_mask_groups()
+    d.masked_min_rows = policy.masked_min_rows if policy is not None else model.masked_min_rows()
+    if policy is not None:
+        d.conv_split_target, d.vote_part_records = int(policy.conv_split_target), int(policy.vote_part_records)
+    d.max_channels, d.use_range_flag = max_channels, 1 if pieces == 2 else 0
+    d.log_scale = 1 if log_scale else 0
+    d.vote_algo = hv_cuda._algo
+
+
+def _call_growing(fn, name, d, r, dev, scratch_name, ws_hint):
+    """fn(d, r, stream) on a device scratch of at least ws_hint bytes; CV_ENOMEM: grow the scratch to result.needed_ws_bytes and
+    run the scene again (four attempts).  Returns the scratch the results' device views point into."""
+    need = max(ws_hint, 64 << 20)
+    for attempt in range(4):
+        ws = _lib.scratch(dev, scratch_name, need)
+        d.d_ws, d.ws_bytes = vp(ws.data_ptr()), ws.numel()
+        with torch.cuda.device(dev):
+            rc = fn(ctypes.byref(d), ctypes.byref(r), vp(torch.cuda.current_stream(dev).cuda_stream))
+        if rc != -12 or r.needed_ws_bytes <= ws.numel():
+            break
+        torch.cuda.current_stream(dev).synchronize()
+        need = int(r.needed_ws_bytes)
+    _lib.check(rc, name)          # (still CV_ENOMEM after four growing attempts: not an empty scene)
+    return ws
+
+
 _sep_hosts = {}
 
 
@@ -192,8 +242,6 @@ def detect_scene_separate_c(models, hv, coords4, feats, res, predictions=None, p
         scan_points = (coords4[:, 1:].to(dev) * res).float().contiguous()
     pieces = 1 if ME.COMPUTE_DTYPE == "bf16" else mods[0].PIECES
     progs = [m._program(dev, pieces) for m in mods]
-    cm_cls = ME.CoordinateManager
-    G = cm_cls.MASK_GROUPS if (27 + cm_cls.MASK_GROUPS - 1) // cm_cls.MASK_GROUPS <= 10 else 0
     coords4 = coords4.to(device=dev, dtype=torch.int32).contiguous()
     feats = feats.contiguous()
     ys = [torch.empty((n, m.final.out_channels), dtype=torch.float32, device=dev) for m in mods]
@@ -207,58 +255,29 @@ def detect_scene_separate_c(models, hv, coords4, feats, res, predictions=None, p
                 cand=np.zeros((K, M), np.int64), verdict=np.zeros((K, M), np.int32), boxes=np.zeros((K, M, 8, 3), np.float32),
                 scores=np.zeros((K, M), np.float32), det_cat=np.zeros(K * M, np.int32), det_box=np.zeros(K * M, np.int32))
     Mh = host["M"]
-    vp = ctypes.c_void_p
     d = _lib.SceneSeparateDesc()
-    d.d_coords4, d.n, d.d_feats, d.feats_ld = vp(coords4.data_ptr()), n, vp(feats.data_ptr()), feats.stride(0)
-    d.d_points, d.res, d.num_rots, d.num_models = vp(scan_points.data_ptr()), float(res), hv_cuda._scalar(hv.num_rots, "i"), K
+    _fill_scene_desc(d, mods[0], hv, coords4, feats, scan_points, res, policy, pieces, max(max(m.PLANES) for m in mods), log_scale)
+    d.num_models = K
     ops = (vp * K)(*[ctypes.cast(p[0], vp) for p in progs])
     n_ops = (ctypes.c_int * K)(*[len(p[0]) for p in progs])
     bufs = (vp * K)(*[ctypes.cast(p[1], vp) for p in progs])
     n_bufs = (ctypes.c_int * K)(*[len(p[1]) for p in progs])
     outs = (vp * K)(*[y.data_ptr() for y in ys])
     d.ops, d.n_ops, d.bufs, d.n_bufs = ctypes.cast(ops, vp), ctypes.cast(n_ops, vp), ctypes.cast(bufs, vp), ctypes.cast(n_bufs, vp)
-    d.stem_k, d.mask_groups = mods[0].conv0p1s1.kernel_size, G
-    d.masked_min_rows = policy.masked_min_rows if policy is not None else mods[0].masked_min_rows()
-    if policy is not None:
-        d.conv_split_target, d.vote_part_records = int(policy.conv_split_target), int(policy.vote_part_records)
-    d.max_channels, d.use_range_flag = max(max(m.PLANES) for m in mods), 1 if pieces == 2 else 0
     d.d_out_feats, d.out_ld, d.out_channels = ctypes.cast(outs, vp), ys[0].stride(0), ys[0].shape[1]
-    d.log_scale = 1 if log_scale else 0
     if predictions is not None:
         px, ps, pp = [a.contiguous() for a in predictions]
         d.d_xyz_in, d.d_scale_in, d.d_prob_in = vp(px.data_ptr()), vp(ps.data_ptr()), vp(pp.data_ptr())
-    d.vote_algo = hv_cuda._algo
-    p = d.decode
-    p.thresh_high = float(decode_kw.get("thresh_high", decode.thresh_high))
-    p.thresh_low = float(decode_kw.get("thresh_low", decode.thresh_low))
-    p.valid_ratio = float(decode_kw.get("valid_ratio", decode.valid_ratio))
-    p.elimination = int(decode_kw.get("elimination", decode.elimination))
-    p.prob_thresh = float(decode_kw.get("prob_thresh", 0.3))
-    p.elim_hi_plus1 = 0 if decode_kw.get("separate_variant", True) else 1
-    p.err_thresh = float(decode_kw.get("err_thresh", 0.3))
+    _fill_decode_params(d.decode, decode_kw, True)
     d.max_candidates, d.nms_threshold = Mh, float(overlap_threshold)
-    if events is not None:
-        for i in range(5):
-            d.events[i] = events[i].cuda_event
+    _set_events(d, events)
     d.h_pinned, d.pinned_bytes = vp(host["pinned"].data_ptr()), host["pinned"].numel()
     d.h_cand_idx, d.h_verdict = vp(host["cand"].ctypes.data), vp(host["verdict"].ctypes.data)
     d.h_boxes, d.h_scores = vp(host["boxes"].ctypes.data), vp(host["scores"].ctypes.data)
     d.h_det_cat, d.h_det_box = vp(host["det_cat"].ctypes.data), vp(host["det_box"].ctypes.data)
     r = _lib.SceneSeparateResult()
-    need = max(host["ws_hint"], 64 << 20)
-    for attempt in range(4):
-        ws = _lib.scratch(dev, "scene_call_separate", need)
-        d.d_ws, d.ws_bytes = vp(ws.data_ptr()), ws.numel()
-        with torch.cuda.device(dev):
-            rc = L.cv_detect_scene_separate_f32(ctypes.byref(d), ctypes.byref(r), vp(torch.cuda.current_stream(dev).cuda_stream))
-        if rc == -12 and r.needed_ws_bytes > ws.numel():            # CV_ENOMEM: grow the scratch and run the scene again
-            torch.cuda.current_stream(dev).synchronize()
-            need = int(r.needed_ws_bytes)
-            continue
-        _lib.check(rc, "cv_detect_scene_separate_f32")
-        break
-    else:
-        _lib.check(rc, "cv_detect_scene_separate_f32")
+    ws = _call_growing(L.cv_detect_scene_separate_f32, "cv_detect_scene_separate_f32", d, r, dev, "scene_call_separate",
+                       host["ws_hint"])
     host["ws_hint"] = max(host["ws_hint"], int(r.needed_ws_bytes))
     if r.range_flag or any(r.truncated[k] for k in range(K)):
         # rare: a convolution input beyond the fp16 range, or more candidate cells than the result arrays hold
@@ -323,8 +342,6 @@ def detect_scene_c(model, hv, coords4, feats, res, nclasses=9, log_scale=True, s
         scan_points = (coords4[:, 1:].to(dev) * res).float().contiguous()
     pieces = 1 if ME.COMPUTE_DTYPE == "bf16" else model.PIECES
     c_ops, c_bufs, _ = model._program(dev, pieces)
-    cm_cls = ME.CoordinateManager
-    G = cm_cls.MASK_GROUPS if (27 + cm_cls.MASK_GROUPS - 1) // cm_cls.MASK_GROUPS <= 10 else 0
     coords4 = coords4.to(device=dev, dtype=torch.int32).contiguous()
     feats = feats.contiguous()
     y = torch.empty((n, model.final.out_channels), dtype=torch.float32, device=dev)
@@ -334,55 +351,25 @@ def detect_scene_c(model, hv, coords4, feats, res, nclasses=9, log_scale=True, s
         if host is None or host.M < max_candidates:
             host = _scene_hosts[key] = _SceneHost(max_candidates)
     d = _lib.SceneDesc()
-    vp = ctypes.c_void_p
-    d.d_coords4, d.n, d.d_feats, d.feats_ld = vp(coords4.data_ptr()), n, vp(feats.data_ptr()), feats.stride(0)
-    d.d_points, d.res, d.num_rots = vp(scan_points.data_ptr()), float(res), hv_cuda._scalar(hv.num_rots, "i")
+    _fill_scene_desc(d, model, hv, coords4, feats, scan_points, res, policy, pieces, max(model.PLANES), log_scale)
     d.ops, d.n_ops, d.bufs, d.n_bufs = ctypes.cast(c_ops, vp), len(c_ops), ctypes.cast(c_bufs, vp), len(c_bufs)
-    d.stem_k, d.mask_groups = model.conv0p1s1.kernel_size, G
-    d.masked_min_rows = policy.masked_min_rows if policy is not None else model.masked_min_rows()
-    if policy is not None:
-        d.conv_split_target, d.vote_part_records = int(policy.conv_split_target), int(policy.vote_part_records)
-    d.max_channels, d.use_range_flag = max(model.PLANES), 1 if pieces == 2 else 0
     d.d_out_feats, d.out_ld, d.out_channels = vp(y.data_ptr()), y.stride(0), y.shape[1]
-    d.nclasses, d.log_scale = nclasses, 1 if log_scale else 0
+    d.nclasses = nclasses
     if predictions is not None:
         px, ps, pp, pc = predictions
         pc = pc.to(torch.int32).contiguous()
         d.d_xyz_in, d.d_scale_in, d.d_prob_in, d.d_class_in = (vp(px.data_ptr()), vp(ps.data_ptr()), vp(pp.data_ptr()),
                                                                  vp(pc.data_ptr()))
-    d.vote_algo = hv_cuda._algo
-    p = d.decode
-    p.thresh_high = float(decode_kw.get("thresh_high", decode.thresh_high))
-    p.thresh_low = float(decode_kw.get("thresh_low", decode.thresh_low))
-    p.valid_ratio = float(decode_kw.get("valid_ratio", decode.valid_ratio))
-    p.elimination = int(decode_kw.get("elimination", decode.elimination))
-    p.prob_thresh = float(decode_kw.get("prob_thresh", 0.3))
-    p.elim_hi_plus1 = 0 if decode_kw.get("separate_variant", False) else 1
-    p.err_thresh = float(decode_kw.get("err_thresh", 0.3))
+    _fill_decode_params(d.decode, decode_kw, False)
     d.max_candidates, d.nms_threshold = host.M, 0.3
     d.adaptive_split = 1 if adaptive_split else 0
-    if events is not None:          # five torch.cuda.Event (recorded once, so that their handles exist): scene start, after
-        for i in range(5):          # the network, after the head split, after the vote, after the decode
-            d.events[i] = events[i].cuda_event
+    _set_events(d, events)
     d.h_pinned, d.pinned_bytes = vp(host.pinned.data_ptr()), host.pinned.numel()
     d.h_cand_idx, d.h_verdict = vp(host.cand.ctypes.data), vp(host.verdict.ctypes.data)
     d.h_boxes, d.h_scores, d.h_classes, d.h_pick = (vp(host.boxes.ctypes.data), vp(host.scores.ctypes.data),
                                                     vp(host.classes.ctypes.data), vp(host.pick.ctypes.data))
     r = _lib.SceneResult()
-    need = max(host.ws_hint, 64 << 20)
-    for attempt in range(4):
-        ws = _lib.scratch(dev, "scene_call", need)
-        d.d_ws, d.ws_bytes = vp(ws.data_ptr()), ws.numel()
-        with torch.cuda.device(dev):
-            rc = L.cv_detect_scene_f32(ctypes.byref(d), ctypes.byref(r), vp(torch.cuda.current_stream(dev).cuda_stream))
-        if rc == -12 and r.needed_ws_bytes > ws.numel():            # CV_ENOMEM: grow the scratch and run the scene again
-            torch.cuda.current_stream(dev).synchronize()
-            need = int(r.needed_ws_bytes)
-            continue
-        _lib.check(rc, "cv_detect_scene_f32")
-        break
-    else:
-        _lib.check(rc, "cv_detect_scene_f32")          # still CV_ENOMEM after four growing attempts: not an empty scene
+    ws = _call_growing(L.cv_detect_scene_f32, "cv_detect_scene_f32", d, r, dev, "scene_call", host.ws_hint)
     host.ws_hint = max(host.ws_hint, int(r.needed_ws_bytes))
     host.last_host_us = tuple(r.host_us)            # where the call's host time went (plan + wait, network enqueue, head + vote, decode + wait)
     if r.range_flag or r.truncated:

@@ -37,8 +37,9 @@ extern "C" {
  * 3 (round 6): launch sizing per call - cv_scene_desc.conv_split_target / vote_part_records, cv_hv_set_part_records_thread;
  *    cv_sp_copy_unless_flag, cv_sp_pack_weights_h2_batch_f32; the neighbour windows of round 5 (conv_win: exact, measured slower
  *    than the mask-sorted kernels at every level, LABNOTES round 5) are gone - cv_sp_build_windows, cv_conv_desc.win,
- *    cv_scene_maps.win, the win_levels arguments and cv_net_win_levels. */
-#define CV_ABI_VERSION 3
+ *    cv_scene_maps.win, the win_levels arguments and cv_net_win_levels.
+ * 4: cv_sp_scene_plan_layout, cv_sp_scene_plan_slots, cv_sp_scene_conv_workspace_bytes (additive: no struct or signature moved). */
+#define CV_ABI_VERSION 4
 int cv_abi_version(void);
 const char* cv_last_error(void);
 
@@ -425,6 +426,29 @@ int cv_sp_scene_plan(const int32_t* d_input, long long n, int32_t* d_perm, int32
                      int32_t* h_counts, int stem_k, int mask_groups, long long masked_min_rows, int32_t* d_arena,
                      size_t arena_words, cv_scene_maps* offsets, void* d_sort_ws, size_t sort_ws_bytes, void* d_levels_ws,
                      size_t levels_ws_bytes, void* stream);
+
+/* THE definition of the buffers a scene plan lives in (pure host functions; cv_detect_scene_f32, cv_detect_scene_separate_f32
+ * and the Python coordinate manager all take them from here).  One int32 buffer of int_words words holds, at these word
+ * offsets (each span rounded up to 64 words, `counts` 64 words): perm [n] | inv [n] | coords[i] [n][4] | vals[i] [cap] |
+ * counts [8] | arena (cv_sp_scene_plan_words: every coarse level bounded by n); one 64-bit buffer of key_words words holds
+ * the five tables' keys, table i at i * cap. */
+typedef struct cv_scene_plan_layout {
+    long long cap;                                      /* cv_sp_table_capacity(n) */
+    long long perm, inv, coords[5], vals[5], counts, arena;
+    long long int_words, key_words;
+    size_t sort_ws_bytes, levels_ws_bytes;              /* cv_sp_sort_workspace_bytes(n), cv_sp_levels_workspace_bytes(n) */
+} cv_scene_plan_layout;
+int cv_sp_scene_plan_layout(long long n, int stem_k, int mask_groups, long long masked_min_rows, cv_scene_plan_layout* out);
+/* The pointer tables of cv_net_run_f32 for a plan in d_ibuf: maps = [stem, down 0-3, k3 0-4, up 0-3, out (= inv)], perms =
+ * [mask orders of levels 0-4, octant orders of the four transposed convs]; a mask order is NULL where the plan has none or
+ * the level has fewer than min_rows rows. */
+#define CV_NET_MAP_SLOTS 15
+#define CV_NET_PERM_SLOTS 9
+int cv_sp_scene_plan_slots(const cv_scene_plan_layout* layout, const cv_scene_maps* offsets, const long long* level_rows,
+                           long long min_rows, const int32_t* d_ibuf, const int32_t** maps, const int32_t** perms);
+/* cv_net_run_f32's d_ws for the five levels: the partial sums of the mask-sorted levels (masked[i] != 0) and the split-K
+ * workspace of the others (cv_sp_conv_workspace_bytes at the largest row count that still splits). */
+size_t cv_sp_scene_conv_workspace_bytes(const long long* level_rows, const int* masked, int mask_groups, int max_channels);
 
 /* Fused eval-mode network as ONE call per scene (host-side executor over cv_sp_conv_f32; replaces the reference's
  * module-by-module MinkUNet34C.forward, utils/minkunet.py:122-180, for inference).  The program is symbolic and built

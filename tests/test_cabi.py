@@ -131,6 +131,47 @@ def test_host_side_layout_functions(built_lib):
     # arena of a two-buffer program: one external, one level-1 buffer of 96 channels
     bufs = (_lib.NetBuf * 2)(_lib.NetBuf(-1, 3, 0), _lib.NetBuf(1, 96, 1))
     assert L.cv_net_arena_bytes(bufs, 2, rows, 5) >= 36822 * 96 * 4
+    # buffers of a scene plan (cv_sp_scene_plan_layout): perm | inv | coords x 5 | table values x 5 | counts | arena, every span
+    # rounded up to 64 words and `counts` 64 words - the formula written out
+    up64 = lambda v: (v + 63) // 64 * 64
+    for n in (80000, 1000):
+        lay = _lib.ScenePlanLayout()
+        assert L.cv_sp_scene_plan_layout(n, 5, 3, 16384, ctypes.byref(lay)) == 0
+        cap = L.cv_sp_table_capacity(n)
+        o_perm, o_inv = 0, up64(n)
+        o_coords = [o_inv + up64(n) + i * up64(4 * n) for i in range(5)]
+        o_vals = [o_coords[-1] + up64(4 * n) + i * up64(cap) for i in range(5)]
+        o_counts = o_vals[-1] + up64(cap)
+        o_arena = o_counts + 64
+        assert (lay.cap, lay.perm, lay.inv, list(lay.coords), list(lay.vals), lay.counts, lay.arena) == \
+               (cap, o_perm, o_inv, o_coords, o_vals, o_counts, o_arena)
+        assert lay.int_words == lay.arena + L.cv_sp_scene_plan_words(n, 5, 3, 16384) and lay.key_words == 5 * cap
+        assert lay.sort_ws_bytes == L.cv_sp_sort_workspace_bytes(n) and lay.levels_ws_bytes == L.cv_sp_levels_workspace_bytes(n)
+        spans = [(lay.perm, n), (lay.inv, n)] + [(o, 4 * n) for o in lay.coords] + [(o, cap) for o in lay.vals] + \
+                [(lay.counts, 8), (lay.arena, lay.int_words - lay.arena)]
+        for (a, la), (b, _) in zip(spans[:-1], spans[1:]):
+            assert a % 64 == 0 and a + la <= b                           # aligned, non-overlapping, in this order
+        assert spans[-1][0] % 64 == 0
+    assert L.cv_sp_scene_plan_layout(0, 5, 3, 16384, ctypes.byref(lay)) == -22
+    # pointer tables of the executor (cv_sp_scene_plan_slots) on a fake base: [stem, down, k3, up, inv] / [mask orders, octant orders]
+    assert (_lib.NET_MAP_SLOTS, _lib.NET_PERM_SLOTS) == (15, 9)
+    lay, base = _lib.ScenePlanLayout(), 1 << 40
+    assert L.cv_sp_scene_plan_layout(80000, 5, 4, 16384, ctypes.byref(lay)) == 0
+    at = lambda o: base + 4 * (lay.arena + o)
+    for thr in (0, 16384, 50000, 10 ** 9):
+        maps, perms = (ctypes.c_void_p * 15)(), (ctypes.c_void_p * 9)()
+        assert L.cv_sp_scene_plan_slots(ctypes.byref(lay), ctypes.byref(off), rows, thr, ctypes.c_void_p(base), maps, perms) == 0
+        assert maps[14] == base + 4 * lay.inv and maps[0] == at(off.stem)
+        assert list(maps[1:14]) == [at(off.down[i]) for i in range(4)] + [at(off.k3[i]) for i in range(5)] + \
+                                   [at(off.up[i]) for i in range(4)]
+        for i in range(5):           # NULL exactly where the plan has no order (rows below the plan's 16384) or rows < threshold
+            assert perms[i] == (at(off.mask_perm[i]) if rows[i] >= max(thr, 16384) else None)
+        assert list(perms[5:]) == [at(off.up_perm[i]) for i in range(4)]
+    # convolution workspace of the executor over the five levels (launches split below 49152 = 128 x 384 rows)
+    for flags in ((1, 1, 0, 0, 0), (0, 0, 0, 0, 0), (1, 1, 1, 1, 1)):
+        want = max([4 * 4 * rows[i] * 256 + 256 for i in range(5) if flags[i]] +
+                   [L.cv_sp_conv_workspace_bytes(min(rows[i], 49152 - 1), 256, 27) for i in range(5)])
+        assert L.cv_sp_scene_conv_workspace_bytes(rows, (ctypes.c_int * 5)(*flags), 4, 256) == want
 
 
 def test_no_packed_fp32_instructions_in_device_code(built_lib, tmp_path):

@@ -64,6 +64,10 @@ def run_plan(coords, dev, mmr):
     o_vals = [o_coords[-1] + up64(4 * n) + i * up64(cap) for i in range(NL)]
     o_counts = o_vals[-1] + up64(cap)
     o_arena = o_counts + 64
+    lay = _lib.ScenePlanLayout()          # the library's definition of the same layout (this test keeps its own restatement)
+    assert L.cv_sp_scene_plan_layout(n, 5, G, mmr, ctypes.byref(lay)) == 0
+    assert (lay.cap, lay.perm, lay.inv, list(lay.coords), list(lay.vals), lay.counts, lay.arena, lay.int_words, lay.key_words) == \
+           (cap, o_perm, o_inv, o_coords, o_vals, o_counts, o_arena, o_arena + words, NL * cap)
     ibuf = torch.full((o_arena + words,), -77, dtype=torch.int32, device=dev)
     kbuf = torch.empty(NL * cap, dtype=torch.int64, device=dev)
     sws_b, lws_b = int(L.cv_sp_sort_workspace_bytes(n)), int(L.cv_sp_levels_workspace_bytes(n))
