@@ -18,11 +18,12 @@
 //            are counting-sorted by their vote's y cell (80k keys, not 9.6M).  One
 //            workgroup owns a 32x32 (x,z) tile of ONE y plane in LDS (6 channels,
 //            24 KB), pulls the points of y-bins {y-1, y}, culls them with a
-//            ring-vs-tile test, wave-compacts survivors (ballot + mbcnt), expands
-//            survivors x rotations densely over lanes, wave-compacts the votes that
-//            land in the tile, and drains them with LDS float atomics.  The tile is
-//            then normalised and stored once: no memset, no global atomics, no
-//            second pass over the 63 MB grid.
+//            ring-vs-tile test into one survivor list of the workgroup (ballot +
+//            mbcnt, one LDS reservation per hand-out), computes the arcs with one
+//            survivor per lane, expands survivors x rotations densely over all lanes,
+//            wave-compacts the votes that land in the tile, and drains them with LDS
+//            fixed-point atomics.  The tile is then normalised and stored once: no
+//            memset, no global atomics, no second pass over the 63 MB grid.
 #include "cv_common.h"
 
 #include <atomic>
@@ -225,9 +226,15 @@ __global__ __launch_bounds__(256) void hv_normalise(const float* __restrict__ g_
 #endif
 constexpr int TX = HV_TX, TZ = 32, TCELLS = TX * TZ;   // TZ = 32 is built into acc_idx
 constexpr int TW = HV_TW;    // waves per workgroup
-constexpr int PQ = 64;       // surviving points per wave chunk
+constexpr int LQ = TW * 64;  // surviving records per round of the workgroup: one per lane
+#ifndef HV_CULL_BATCH
+#define HV_CULL_BATCH 4
+#endif
+constexpr int CULL_BATCH = HV_CULL_BATCH;     // 64-record chunks a wave culls per hand-out
+static_assert(CULL_BATCH >= 1 && CULL_BATCH <= 8, "one carry bit and one record index per sub-chunk and lane");
 constexpr int VQ = 128;      // vote queue entries per wave
 constexpr int MAX_R_TILES = 256;
+static_assert(MAX_R_TILES <= TW * 64, "the rotation table is staged by one load per lane");
 #ifndef HV_LIST_PART_ENTRIES
 #define HV_LIST_PART_ENTRIES 384
 #endif
@@ -235,6 +242,7 @@ constexpr int MAX_R_TILES = 256;
 #define HV_LIST_CHUNK 16
 #endif
 constexpr int LIST_CHUNK = HV_LIST_CHUNK;                  // list entries a wave takes per hand-out
+static_assert(64 % LIST_CHUNK == 0, "a wave takes 64 / LIST_CHUNK list chunks per hand-out, one entry per lane");
 constexpr int LIST_PART_ENTRIES = HV_LIST_PART_ENTRIES;    // work-list entries one part of a hot (tile, plane) takes
 
 // y cell of every vote of a point (theta-independent: offset.y = -corr.y, :38-39).
@@ -623,8 +631,9 @@ __device__ __forceinline__ int lanes_below(uint64_t mask) {
 }
 
 // LDS atomic add rates on gfx950 (lane-ops/clk/CU, measured: profiles/microbench/lds_atomic_rate.hip):
-// f32 0.33, f64 3.1, u64 5.6, u32 7.4.  The LDS atomics are 63 % of this kernel's time (ablation: 0.68 ms ->
-// 0.25 ms without them).  The objectness channel - the one the decode thresholds and takes argmax of, and the
+// f32 0.33, f64 3.1, u64 5.6, u32 7.4.  (Round 2's ablation - 0.68 ms -> 0.25 ms without the atomics - also removed the
+// conversions in front of them; by the round-6 counters the kernel issues vector ALU instructions 80 % of its time and waits
+// for LDS 4.5 % of its wave cycles: LABNOTES round 8.)  The objectness channel - the one the decode thresholds and takes argmax of, and the
 // one that defines which cells are touched at all - accumulates in f64 (exact sums of the fp32 contributions).
 // The five quotient numerators (rot cos/sin, scale xyz) accumulate in 64-bit FIXED POINT with ds_add_u64: every
 // fp32 contribution is rounded once to a multiple of 2^-36 (1.5e-11; |sum| < 1.3e8 per cell and channel) and
@@ -714,14 +723,17 @@ __device__ __forceinline__ int acc_idx(int ch, int cell) { return ch * ACC_CH + 
 struct TileShared {
     unsigned long long acc[ACC_WORDS];   // channel 0: objectness weight, 1..5: rot.cos, rot.sin, scale.xyz - all
                                          // in 2^-36 fixed point
-    float pq[TW][9][PQ];       // px, pz, cx, cz, wy, obj, s0, s1, s2 of surviving points
-    int arc_start[TW][PQ];     // first rotation whose vote can reach the tile
-    int arc_cum[TW][PQ];       // inclusive prefix sum of the arc lengths
-    uint32_t vq_rec[TW][VQ];   // entry | rot<<6 | (lx+1)<<14 | (lz+1)<<20
+    float pq[9][LQ];           // px, pz, cx, cz, wy, obj, s0, s1, s2 of the round's surviving records (workgroup-wide list)
+    int arc_start[LQ];         // phase A: record index | bin << 31; from phase B on: first rotation whose vote can reach the tile
+    int arc_cum[LQ];           // (list mode, phase A: the entry's packed arc) inclusive prefix sum of the arc lengths
+    uint32_t vq_rec[TW][VQ];   // entry | rot<<9 | (lx+1)<<17 | (lz+1)<<23
     float vq_rx[TW][VQ];
     float vq_rz[TW][VQ];
     float2 tab[MAX_R_TILES];
     int next_chunk[2];         // dynamic hand-out of 64-record chunks of the two y-bins to the waves
+    int wtot[TW];              // summed arc lengths of each wave's 64 list entries (workgroup scan of phase B)
+    int list_len;              // entries reserved in the list this round (may run past LQ: the surplus is carried over)
+    int more;                  // a wave stopped for lack of room: another round follows
 #ifdef HV_LDS_PAD
     char lds_pad[HV_LDS_PAD];  // experiment: LDS the workgroup does not use, to control what else fits on its CU
 #endif
@@ -762,10 +774,10 @@ __device__ __forceinline__ void drain64(TileShared& sh, int wave, int slot, bool
     if (active) {
         const uint32_t rec = sh.vq_rec[wave][slot];
         rx = sh.vq_rx[wave][slot]; rz = sh.vq_rz[wave][slot];
-        const int e = rec & 63, rot = (rec >> 6) & 255;
-        lx = (int)((rec >> 14) & 63) - 1; lz = (int)((rec >> 20) & 63) - 1;
-        wy = sh.pq[wave][4][e]; ob = sh.pq[wave][5][e];
-        s0 = sh.pq[wave][6][e]; s1 = sh.pq[wave][7][e]; s2 = sh.pq[wave][8][e];
+        const int e = rec & 511, rot = (rec >> 9) & 255;
+        lx = (int)((rec >> 17) & 63) - 1; lz = (int)((rec >> 23) & 63) - 1;
+        wy = sh.pq[4][e]; ob = sh.pq[5][e];
+        s0 = sh.pq[6][e]; s1 = sh.pq[7][e]; s2 = sh.pq[8][e];
         cs = sh.tab[rot];
     }
     // every contribution of a vote is bounded by |obj| * max(1, |scale|) (the trilinear weights are <= 1); the
@@ -798,6 +810,56 @@ __device__ __forceinline__ float arc_atan2(float y, float x) {
     r = ay > ax ? 1.57079637f - r : r;
     r = x < 0.f ? 3.14159274f - r : r;
     return y < 0.f ? -r : r;
+}
+
+// A second conservative arc, for rings that the corner arc serves badly: a centre inside the rectangle (or within half a
+// cell) gets all R rotations and 54 % of the expanded items of an 80k scene come from such rings, although a ring larger
+// than the tile spends most of its circumference outside (profiles/r8/vote_chunk_pricing.txt: 2.49 items per in-tile vote,
+// 1.38 with this arc in the model).  Beyond the edge line with outward normal at angle k pi/2 and distance d < r from the centre
+// the ring runs for the angles within acos(d / r) of the normal.  Neighbouring outside arcs that overlap merge into runs; the
+// complement of the LONGEST run is one interval that holds every vote inside the rectangle.  Everything errs to the safe
+// side: the rectangle grown by `slack`, every outside arc shortened by 0.01 rad per side (the atan2 polynomial is good to
+// 2e-4), arcs linked only where the shortened ones still overlap, rings under two cells left to the corner arc (there the
+// rounding of the centre is not small against the radius), and the usual two rotation steps of slack per side.
+__device__ __forceinline__ void edge_arc(float ux, float uz, float r, float a0, int R, float xlo, float xhi, float zlo,
+                                         float zhi, int& a_start, int& a_len) {
+    if (!(r >= 2.f)) return;
+    const float slack = 0.05f, half_pi = 1.57079637f, two_pi = 6.28318531f;
+    const float d4[4] = {xhi - ux, zhi - uz, ux - xlo, uz - zlo};          // outward normals at 0, pi/2, pi, 3 pi/2
+    const float inv_r = 1.f / r;
+    float h[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float t = (d4[k] + slack) * inv_r;
+        const float hk = arc_atan2(sqrtf(fmaxf(1.f - t * t, 0.f)), t) - 0.01f;      // acos(t), t <= -1: pi
+        h[k] = (t < 1.f && hk > 0.f) ? hk : -1.f;                                   // -1: the ring does not cross this line
+    }
+    float best = 0.f, best_end = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float lo = -h[k], hi = h[k];
+        bool ok = h[k] > 0.f;
+        if (ok && hi - lo > best) { best = hi - lo; best_end = (float)k * half_pi + hi; }
+#pragma unroll
+        for (int j = 1; j < 4; ++j) {
+            const float hp = h[(k + j - 1) & 3], hn = h[(k + j) & 3];
+            ok = ok && hn > 0.f && hp + hn >= half_pi;
+            if (ok) {
+                lo = fminf(lo, (float)j * half_pi - hn);
+                hi = fmaxf(hi, (float)j * half_pi + hn);
+                if (hi - lo > best) { best = hi - lo; best_end = (float)k * half_pi + hi; }
+            }
+        }
+    }
+    const float inside = fmaxf(two_pi - best, 0.f);
+    const float inv_step = (float)R * 0.159154943f;
+    const int len = (int)(inside * inv_step) + 6;
+    if (len < a_len) {
+        float first = (best_end - a0) * inv_step - 2.f;
+        first -= (float)R * floorf(first / (float)R);
+        a_start = min(max((int)first, 0), R - 1);
+        a_len = len;
+    }
 }
 
 // VARIANT (ablations for profiling only): 0 full, 1 no LDS atomics, 2 no dense phase, 3 no record streaming
@@ -890,9 +952,21 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
         __syncthreads();
     }
 #endif
+    // first and last record (list entry) of the two bins and the rotation table: loads issued before the accumulators are
+    // zeroed, so that their latency passes under the zeroing and not in front of phase A
+    int bin_beg[2], bin_end[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int s = y - 1 + k;
+        const bool valid = s >= 0 && s <= Y - 2 && VARIANT != 3;
+        bin_beg[k] = !valid ? 0 : (use_list ? lbeg[k] : ystart[s]);
+        bin_end[k] = !valid ? 0 : (use_list ? lbeg[k] + llen[k] : ystart[s + 1]);
+    }
+    const float2 tab_mine = (int)threadIdx.x < R ? tab[threadIdx.x] : make_float2(0.f, 0.f);      // (R <= MAX_R_TILES <= TW * 64)
     for (int i = threadIdx.x; i < ACC_WORDS; i += TW * 64) sh.acc[i] = 0ull;
-    for (int i = threadIdx.x; i < R; i += TW * 64) sh.tab[i] = tab[i];
+    if ((int)threadIdx.x < R) sh.tab[threadIdx.x] = tab_mine;
     if (threadIdx.x < 2) sh.next_chunk[threadIdx.x] = 0;
+    if (threadIdx.x == 2) { sh.list_len = 0; sh.more = 0; }
     __syncthreads();
     HV_TICK(0);
 
@@ -903,180 +977,283 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
                 zhi = (float)(z0 + TZ);
     int vq_len = 0;   // wave-uniform
 
-    for (int s = y - 1; s <= y; ++s) {
-        if (s < 0 || s > Y - 2 || VARIANT == 3) continue;
-        const int beg = use_list ? lbeg[s - (y - 1)] : ystart[s];
-        const int end = use_list ? beg + llen[s - (y - 1)] : ystart[s + 1];
-        // waves take chunks from a shared counter: a wave whose chunk expands into many votes takes fewer chunks
-        // (static striding left the waves of a workgroup waiting 22 % of their time for the slowest one)
-        for (;;) {
+    // Rounds of three phases over ONE survivor list of the workgroup (until round 8 every wave culled a 64-record chunk,
+    // kept ~5 records of it and paid the arc, the scan, the search and a queue flush for those five):
+    //   A  the waves take chunks of both y-bins from the shared counters, run only the ring-vs-rectangle test and append the
+    //      kept records (ballot, mbcnt, one LDS reservation per wave and hand-out) to the list;
+    //   B  one survivor per lane: arc, record fields, workgroup-wide inclusive scan of the arc lengths;
+    //   C  the round's items split evenly over all lanes of the workgroup, one binary search per lane, votes queued per
+    //      wave and drained 64 at a time; a wave flushes its queue once per round.
+    // A round ends when the list cannot take another full chunk.  Survivors of a chunk that found the list full stay in the
+    // wave's registers (c_*) and open its next round: no record is dropped or taken twice.
+    const int per = use_list ? LIST_CHUNK : 64;           // records (list entries) of a chunk: the unit of the part split
+    int sb = 0;                               // bin (0: y - 1, 1: y) this wave takes chunks of; wave-uniform
+    // A wave takes CULL_BATCH chunks per hand-out and has the loads of all of them in flight at once: phase A is a chain of
+    // (LDS counter, global loads, test, LDS reservation) per hand-out and nothing of the workgroup overlaps it.
+    // carried survivors: bit j of c_mask = this lane's record of sub-chunk j (c_idx[j]; list mode: packed arc c_arc), c_k their bin
+    int c_mask = 0, c_idx[CULL_BATCH], c_arc = 0, c_k = 0;
+#pragma unroll
+    for (int j = 0; j < CULL_BATCH; ++j) c_idx[j] = 0;
+    // appends the kept records of a hand-out behind ONE reservation; returns the bits the list had no room for
+    auto append = [&](int mask, const int (&idx)[CULL_BATCH], int arc, int k) -> int {
+        int tot = 0, before[CULL_BATCH];
+#pragma unroll
+        for (int j = 0; j < CULL_BATCH; ++j) {
+            const uint64_t m = __ballot((mask >> j) & 1);
+            before[j] = tot + lanes_below(m);
+            tot += __popcll(m);
+        }
+        if (tot == 0) return 0;
+        int p0 = 0;
+        if (lane == 0) p0 = atomicAdd(&sh.list_len, tot);
+        p0 = __builtin_amdgcn_readfirstlane(p0);
+#pragma unroll
+        for (int j = 0; j < CULL_BATCH; ++j) {
+            const int pos = p0 + before[j];
+            if (((mask >> j) & 1) && pos < LQ) {
+                sh.arc_start[pos] = idx[j] | (int)((unsigned)k << 31);
+                if (use_list) sh.arc_cum[pos] = arc;
+                mask &= ~(1 << j);
+            }
+        }
+        return mask;
+    };
+
+    for (;;) {
+        // ---- phase A: cull chunks into the list
+        bool more = false;                    // wave-uniform: this wave stopped for lack of room
+        if (__ballot(c_mask != 0) != 0) {
+            c_mask = append(c_mask, c_idx, c_arc, c_k);
+            more = __ballot(c_mask != 0) != 0;
+        }
+        while (!more && sb < 2) {
+            if (bin_beg[sb] >= bin_end[sb]) { ++sb; continue; }
+            const int len = __builtin_amdgcn_readfirstlane(
+                __hip_atomic_load(&sh.list_len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+            if (len > LQ - 64) { more = true; break; }       // no room for another full chunk: the round ends
+            // waves take chunks from a shared counter: a wave whose chunks are slow to cull takes fewer of them
+            const int take = use_list ? 64 / LIST_CHUNK : CULL_BATCH;
             int c = 0;
-            if (lane == 0) c = atomicAdd(&sh.next_chunk[s - (y - 1)], 1);
+            if (lane == 0) c = atomicAdd(&sh.next_chunk[sb], take);
             c = __builtin_amdgcn_readfirstlane(c);
-            // list entries are all kept and each expands into an arc: 16 per hand-out keep the waves of a workgroup even
-            const int per = use_list ? LIST_CHUNK : 64;
-            const int base = beg + (c * nparts + part) * per;
-            if (base >= end) break;
-            int idx = base + lane;
-            bool keep = false;
-            int a_start = 0, a_len = 0;
+            const int end = bin_end[sb];
+            if (bin_beg[sb] + (c * nparts + part) * per >= end) { ++sb; continue; }
+            int idx[CULL_BATCH], mask = 0, arc = 0;
+#pragma unroll
+            for (int j = 0; j < CULL_BATCH; ++j) idx[j] = 0;
             if (use_list) {
-                if (lane < per && idx < end) {
-                    const int2 en = entries[idx];
-                    idx = en.x;
-                    a_start = en.y & 0xffff;
-                    a_len = en.y >> 16;
-                    keep = true;
+                // 64 / LIST_CHUNK chunks of LIST_CHUNK entries: one entry per lane
+                const int e = bin_beg[sb] + ((c + lane / LIST_CHUNK) * nparts + part) * LIST_CHUNK + lane % LIST_CHUNK;
+                if (e < end) {
+                    const int2 en = entries[e];
+                    idx[0] = en.x;
+                    arc = en.y;
+                    mask = 1;
                 }
-            } else if (idx < end) {
-                const float ux = rec[9 * rec_stride + idx], uz = rec[10 * rec_stride + idx],
-                            r = rec[11 * rec_stride + idx];
-                // conservative ring-vs-rectangle test in grid units
+            } else {
+                float ux[CULL_BATCH], uz[CULL_BATCH], r[CULL_BATCH];
+#pragma unroll
+                for (int j = 0; j < CULL_BATCH; ++j) {
+                    idx[j] = bin_beg[sb] + ((c + j) * nparts + part) * 64 + lane;
+                    const bool in = idx[j] < end;
+                    ux[j] = in ? rec[9 * rec_stride + idx[j]] : 0.f;
+                    uz[j] = in ? rec[10 * rec_stride + idx[j]] : 0.f;
+                    r[j] = in ? rec[11 * rec_stride + idx[j]] : 0.f;
+                }
+#pragma unroll
+                for (int j = 0; j < CULL_BATCH; ++j) {
+                    // conservative ring-vs-rectangle test in grid units
+                    const float dxn = fmaxf(0.f, fmaxf(xlo - ux[j], ux[j] - xhi));
+                    const float dzn = fmaxf(0.f, fmaxf(zlo - uz[j], uz[j] - zhi));
+                    const float dxf = fmaxf(fabsf(ux[j] - xlo), fabsf(ux[j] - xhi));
+                    const float dzf = fmaxf(fabsf(uz[j] - zlo), fabsf(uz[j] - zhi));
+                    const float dmin = sqrtf(dxn * dxn + dzn * dzn), dmax = sqrtf(dxf * dxf + dzf * dzf);
+                    const float tol = slack + 1e-5f * (r[j] + fabsf(ux[j]) + fabsf(uz[j]));
+                    bool keep = idx[j] < end && (r[j] >= dmin - tol) && (r[j] <= dmax + tol);
+                    if (VARIANT == 2) keep = keep && (ux[j] == 1234.5f);
+                    mask |= (int)keep << j;
+                }
+            }
+            c_mask = append(mask, idx, arc, sb);
+            if (__ballot(c_mask != 0) != 0) {
+#pragma unroll
+                for (int j = 0; j < CULL_BATCH; ++j) c_idx[j] = idx[j];
+                c_arc = arc; c_k = sb;
+                more = true;
+            }
+        }
+        if (more && lane == 0) sh.more = 1;
+        HV_TICK(1);
+        __syncthreads();
+        const int n = min(sh.list_len, LQ);
+        const bool again = sh.more != 0;      // (implies n > 0: room runs out only in a list that holds entries)
+        HV_TICK(3);
+        if (n == 0) break;
+
+        // ---- phase B: one survivor per lane
+        const int p = threadIdx.x;
+        int a_start = 0, a_len = 0;
+        if (p < n) {
+            const int w = sh.arc_start[p];
+            const int idx = w & 0x7fffffff;
+            if (use_list) {
+                const int arc = sh.arc_cum[p];
+                a_start = arc & 0xffff;
+                a_len = arc >> 16;
+            } else {
+                // rotations whose vote can fall in the rectangle: the rectangle subtends an arc
+                // [b0+lo, b0+hi] seen from the ring centre unless the centre is (nearly) inside it
+                const float ux = rec[9 * rec_stride + idx], uz = rec[10 * rec_stride + idx];
                 const float dxn = fmaxf(0.f, fmaxf(xlo - ux, ux - xhi));
                 const float dzn = fmaxf(0.f, fmaxf(zlo - uz, uz - zhi));
-                const float dxf = fmaxf(fabsf(ux - xlo), fabsf(ux - xhi));
-                const float dzf = fmaxf(fabsf(uz - zlo), fabsf(uz - zhi));
-                const float dmin = sqrtf(dxn * dxn + dzn * dzn), dmax = sqrtf(dxf * dxf + dzf * dzf);
-                const float tol = slack + 1e-5f * (r + fabsf(ux) + fabsf(uz));
-                keep = (r >= dmin - tol) && (r <= dmax + tol);
-                if (VARIANT == 2) keep = keep && (ux == 1234.5f);
-                if (keep) {
-                    // rotations whose vote can fall in the rectangle: the rectangle subtends an arc
-                    // [b0+lo, b0+hi] seen from the ring centre unless the centre is (nearly) inside it
-                    a_len = R;
-                    if (dxn + dzn > 0.5f) {
-                        const float b0 = arc_atan2(0.5f * (zlo + zhi) - uz, 0.5f * (xlo + xhi) - ux);
-                        float lo = 0.f, hi = 0.f;
+                a_len = R;
+                if (dxn + dzn > 0.5f) {
+                    const float b0 = arc_atan2(0.5f * (zlo + zhi) - uz, 0.5f * (xlo + xhi) - ux);
+                    float lo = 0.f, hi = 0.f;
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            float d = arc_atan2(((k & 2) ? zhi : zlo) - uz, ((k & 1) ? xhi : xlo) - ux) - b0;
-                            d -= 6.28318531f * rintf(d * 0.159154943f);
-                            lo = fminf(lo, d);
-                            hi = fmaxf(hi, d);
-                        }
-                        const float a0 = rec[12 * rec_stride + idx];
-                        const float inv_step = (float)R * 0.159154943f;          // 1 / rot_interval
-                        float first = (b0 + lo - a0) * inv_step - 2.f;           // 2 steps of slack per side
-                        const int len = (int)((hi - lo) * inv_step) + 6;
-                        first -= (float)R * floorf(first / (float)R);
-                        a_start = min(max((int)first, 0), R - 1);
-                        a_len = min(len, R);
+                    for (int k = 0; k < 4; ++k) {
+                        float d = arc_atan2(((k & 2) ? zhi : zlo) - uz, ((k & 1) ? xhi : xlo) - ux) - b0;
+                        d -= 6.28318531f * rintf(d * 0.159154943f);
+                        lo = fminf(lo, d);
+                        hi = fmaxf(hi, d);
                     }
+                    const float a0 = rec[12 * rec_stride + idx];
+                    const float inv_step = (float)R * 0.159154943f;          // 1 / rot_interval
+                    float first = (b0 + lo - a0) * inv_step - 2.f;           // 2 steps of slack per side
+                    const int len = (int)((hi - lo) * inv_step) + 6;
+                    first -= (float)R * floorf(first / (float)R);
+                    a_start = min(max((int)first, 0), R - 1);
+                    a_len = min(len, R);
                 }
+                edge_arc(ux, uz, rec[11 * rec_stride + idx], rec[12 * rec_stride + idx], R, xlo, xhi, zlo, zhi, a_start, a_len);
             }
-            const uint64_t m = __ballot(keep);
-            const int nq = __popcll(m);
-            HV_TICK(1);
-            if (nq == 0) continue;
-            // inclusive scan of the arc lengths in compacted (lane) order
-            int cum = keep ? a_len : 0;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const int t = __shfl_up(cum, off);
-                if (lane >= off) cum += t;
-            }
-            const int items = __shfl(cum, 63);
-            if (keep) {
-                const int p = lanes_below(m);
-                const float ry = rec[4 * rec_stride + idx];
-                sh.pq[wave][0][p] = rec[0 * rec_stride + idx];
-                sh.pq[wave][1][p] = rec[1 * rec_stride + idx];
-                sh.pq[wave][2][p] = rec[2 * rec_stride + idx];
-                sh.pq[wave][3][p] = rec[3 * rec_stride + idx];
-                sh.pq[wave][4][p] = (s == y) ? (1.f - ry) : ry;
-                sh.pq[wave][5][p] = rec[5 * rec_stride + idx];
-                sh.pq[wave][6][p] = rec[6 * rec_stride + idx];
-                sh.pq[wave][7][p] = rec[7 * rec_stride + idx];
-                sh.pq[wave][8][p] = rec[8 * rec_stride + idx];
-                sh.arc_start[wave][p] = a_start;
-                sh.arc_cum[wave][p] = cum;
-            }
-            wave_sync_lds();
-            HV_TICK(2);
-
-            // lane l walks items [l*S, (l+1)*S): at any step the 64 lanes sit on 64 different arcs
-            // (different cells -> few same-address LDS atomic collisions), and a lane only advances
-            // along its arc, so the (entry, step) pair is found by ONE binary search per chunk.
-            const int S = (items + 63) >> 6;
-            int it0 = lane * S;
-            const int it1 = min(it0 + S, items);
-            int e = 0;
-            {
-                int lo = 0, hi = nq - 1;                     // smallest e with cum[e] > it0
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (sh.arc_cum[wave][mid] > it0) hi = mid; else lo = mid + 1;
-                }
-                e = lo;
-            }
-            int e_end = it0 < items ? sh.arc_cum[wave][e] : 0;          // first item of the next entry
-            int rot = 0;
-            // the entry's point stays in registers while the lane walks its arc (4 LDS reads per entry instead of
-            // per step: the LDS pipe is what the expansion shares with the f64 atomics)
-            float epx = 0.f, epz = 0.f, ecx = 0.f, ecz = 0.f;
-            if (it0 < items) {
-                const int e_beg = e > 0 ? sh.arc_cum[wave][e - 1] : 0;
-                rot = sh.arc_start[wave][e] + (it0 - e_beg);
-                if (rot >= R) rot -= R;
-                epx = sh.pq[wave][0][e]; epz = sh.pq[wave][1][e];
-                ecx = sh.pq[wave][2][e]; ecz = sh.pq[wave][3][e];
-            }
-            HV_TICK(2);
-            for (int step = 0; step < S; ++step, ++it0) {
-                bool isvote = false;
-                uint32_t vrec = 0;
-                float rx = 0, rz = 0;
-                if (it0 < it1) {
-                    if (it0 == e_end) {                      // next arc
-                        ++e;
-                        e_end = sh.arc_cum[wave][e];
-                        rot = sh.arc_start[wave][e];
-                        epx = sh.pq[wave][0][e]; epz = sh.pq[wave][1][e];
-                        ecx = sh.pq[wave][2][e]; ecz = sh.pq[wave][3][e];
-                    }
-                    const float2 cs = sh.tab[rot];
-                    const float ox = (-cs.x) * ecx + cs.y * ecz;
-                    const float oz = (-cs.y) * ecx - cs.x * ecz;
-                    const float gx = grid_pos(epx, ox, corner.x, res);
-                    const float gz = grid_pos(epz, oz, corner.z, res);
-                    if (gx >= 0 && gz >= 0 && gx < (float)(X - 1) && gz < (float)(Z - 1)) {
-                        const int lx = (int)gx - x0, lz = (int)gz - z0;
-                        if (lx >= -1 && lx < TX && lz >= -1 && lz < TZ) {
-                            isvote = true;
-                            rx = gx - floorf(gx);
-                            rz = gz - floorf(gz);
-                            vrec = (uint32_t)e | ((uint32_t)rot << 6) | ((uint32_t)(lx + 1) << 14) |
-                                   ((uint32_t)(lz + 1) << 20);
-                        }
-                    }
-                    if (++rot == R) rot = 0;
-                }
-                const uint64_t mv = __ballot(isvote);
-                if (isvote) {
-                    const int p = vq_len + lanes_below(mv);
-                    sh.vq_rec[wave][p] = vrec;
-                    sh.vq_rx[wave][p] = rx;
-                    sh.vq_rz[wave][p] = rz;
-                }
-                vq_len += __popcll(mv);
-                wave_sync_lds();
-                HV_TICK(4);
-                if (vq_len >= 64) {
-                    vq_len -= 64;
-                    if (VARIANT != 1) drain64(sh, wave, vq_len + lane, true);
-                    HV_TICK(5);
-                }
-            }
-            // queued votes index this chunk's pq entries: flush before pq is overwritten
-            if (vq_len > 0) {
-                if (VARIANT != 1) drain64(sh, wave, lane, lane < vq_len);
-                else if (lane < vq_len)
-                    sh.acc[ACC_CH + lane] = (unsigned long long)(sh.vq_rx[wave][lane] + sh.vq_rz[wave][lane] + (float)sh.vq_rec[wave][lane]);
-                vq_len = 0;
-            }
-            wave_sync_lds();
-            HV_TICK(6);
+            const float ry = rec[4 * rec_stride + idx];
+            sh.pq[0][p] = rec[0 * rec_stride + idx];
+            sh.pq[1][p] = rec[1 * rec_stride + idx];
+            sh.pq[2][p] = rec[2 * rec_stride + idx];
+            sh.pq[3][p] = rec[3 * rec_stride + idx];
+            sh.pq[4][p] = (w < 0) ? (1.f - ry) : ry;       // bin y : bin y - 1
+            sh.pq[5][p] = rec[5 * rec_stride + idx];
+            sh.pq[6][p] = rec[6 * rec_stride + idx];
+            sh.pq[7][p] = rec[7 * rec_stride + idx];
+            sh.pq[8][p] = rec[8 * rec_stride + idx];
+            sh.arc_start[p] = a_start;
         }
+        // inclusive scan of the arc lengths in list order: per wave, then over the wave totals
+        int cum = a_len;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int t = __shfl_up(cum, off);
+            if (lane >= off) cum += t;
+        }
+        if (lane == 63) sh.wtot[wave] = cum;
+        HV_TICK(2);
+        __syncthreads();
+        HV_TICK(3);
+        if (threadIdx.x == 0) { sh.list_len = 0; sh.more = 0; }      // (every lane has read both; next written after the
+                                                                     // barrier that ends the round)
+        int items = 0;
+#pragma unroll
+        for (int w = 0; w < TW; ++w) {
+            const int t = sh.wtot[w];
+            if (w < wave) cum += t;
+            items += t;
+        }
+        if (p < n) sh.arc_cum[p] = cum;
+        HV_TICK(2);
+        __syncthreads();
+        HV_TICK(3);
+
+        // ---- phase C: slice j walks items [j*S, (j+1)*S): at any step the lanes of a wave sit on different arcs
+        // (different cells -> few same-address LDS atomic collisions), and a lane only advances along its arc, so the
+        // (entry, step) pair is found by ONE binary search per round.
+        const int S = (items + LQ - 1) / LQ;
+#ifdef HV_SLICE_INTERLEAVED
+        const int slice = lane * TW + wave;          // the waves' slices interleave: each wave samples the whole list
+#else
+        const int slice = wave * 64 + lane;          // a wave walks one contiguous run of the list
+#endif
+        int it0 = slice * S;
+        const int it1 = min(it0 + S, items);
+        int e = 0;
+        {
+            int lo = 0, hi = n - 1;                      // smallest e with cum[e] > it0
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (sh.arc_cum[mid] > it0) hi = mid; else lo = mid + 1;
+            }
+            e = lo;
+        }
+        int e_end = it0 < items ? sh.arc_cum[e] : 0;          // first item of the next entry
+        int rot = 0;
+        // the entry's point stays in registers while the lane walks its arc (4 LDS reads per entry instead of
+        // per step: the LDS pipe is what the expansion shares with the atomics)
+        float epx = 0.f, epz = 0.f, ecx = 0.f, ecz = 0.f;
+        if (it0 < items) {
+            const int e_beg = e > 0 ? sh.arc_cum[e - 1] : 0;
+            rot = sh.arc_start[e] + (it0 - e_beg);
+            if (rot >= R) rot -= R;
+            epx = sh.pq[0][e]; epz = sh.pq[1][e];
+            ecx = sh.pq[2][e]; ecz = sh.pq[3][e];
+        }
+        HV_TICK(2);
+        for (int step = 0; step < S; ++step, ++it0) {
+            bool isvote = false;
+            uint32_t vrec = 0;
+            float rx = 0, rz = 0;
+            if (it0 < it1) {
+                if (it0 == e_end) {                      // next arc
+                    ++e;
+                    e_end = sh.arc_cum[e];
+                    rot = sh.arc_start[e];
+                    epx = sh.pq[0][e]; epz = sh.pq[1][e];
+                    ecx = sh.pq[2][e]; ecz = sh.pq[3][e];
+                }
+                const float2 cs = sh.tab[rot];
+                const float ox = (-cs.x) * ecx + cs.y * ecz;
+                const float oz = (-cs.y) * ecx - cs.x * ecz;
+                const float gx = grid_pos(epx, ox, corner.x, res);
+                const float gz = grid_pos(epz, oz, corner.z, res);
+                if (gx >= 0 && gz >= 0 && gx < (float)(X - 1) && gz < (float)(Z - 1)) {
+                    const int lx = (int)gx - x0, lz = (int)gz - z0;
+                    if (lx >= -1 && lx < TX && lz >= -1 && lz < TZ) {
+                        isvote = true;
+                        rx = gx - floorf(gx);
+                        rz = gz - floorf(gz);
+                        vrec = (uint32_t)e | ((uint32_t)rot << 9) | ((uint32_t)(lx + 1) << 17) |
+                               ((uint32_t)(lz + 1) << 23);
+                    }
+                }
+                if (++rot == R) rot = 0;
+            }
+            const uint64_t mv = __ballot(isvote);
+            if (isvote) {
+                const int q = vq_len + lanes_below(mv);
+                sh.vq_rec[wave][q] = vrec;
+                sh.vq_rx[wave][q] = rx;
+                sh.vq_rz[wave][q] = rz;
+            }
+            vq_len += __popcll(mv);
+            wave_sync_lds();
+            HV_TICK(4);
+            if (vq_len >= 64) {
+                vq_len -= 64;
+                if (VARIANT != 1) drain64(sh, wave, vq_len + lane, true);
+                HV_TICK(5);
+            }
+        }
+        // queued votes index this round's list entries: flush before the list is overwritten
+        if (vq_len > 0) {
+            if (VARIANT != 1) drain64(sh, wave, lane, lane < vq_len);
+            else if (lane < vq_len)
+                sh.acc[ACC_CH + lane] = (unsigned long long)(sh.vq_rx[wave][lane] + sh.vq_rz[wave][lane] + (float)sh.vq_rec[wave][lane]);
+            vq_len = 0;
+        }
+        wave_sync_lds();
+        HV_TICK(6);
+        if (!again) break;
+        __syncthreads();
+        HV_TICK(3);
     }
     HV_TICK(1);
     __syncthreads();
@@ -1568,8 +1745,8 @@ static int hv_forward_cats(const float* d_points, const float* d_xyz, const floa
         unsigned long long h[16];
         CV_HIP_CHECK(hipMemcpyAsync(h, d_prof, sizeof h, hipMemcpyDeviceToHost, st));
         CV_HIP_CHECK(hipStreamSynchronize(st));
-        static const char* names[8] = {"init", "stream+cull", "scan+pq+arc-search", "end-wait", "walk", "drain",
-                                       "tail-flush", "merge+store"};
+        static const char* names[8] = {"init", "cull", "arcs+scan+search", "barrier-wait", "walk", "drain",
+                                       "round-flush", "merge+store"};
         double tot = 0;
         for (int p2 = 0; p2 < 8; ++p2) tot += (double)h[p2];
         fprintf(stderr, "hv_fwd_tiles waves %llu ticks/wave %.0f:", h[8], tot / (double)std::max(1ull, h[8]));
