@@ -15,7 +15,7 @@ c_int_p = ctypes.POINTER(ctypes.c_int)
 c_i32_p = ctypes.POINTER(ctypes.c_int32)
 c_i64_p = ctypes.POINTER(ctypes.c_int64)
 vp = ctypes.c_void_p
-ABI_VERSION = 4          # CV_ABI_VERSION of include/cv_hip.h that these ctypes signatures were written against
+ABI_VERSION = 5          # CV_ABI_VERSION of include/cv_hip.h that these ctypes signatures were written against
 
 
 class CvError(RuntimeError):
@@ -78,6 +78,12 @@ class NetOp(ctypes.Structure):
                 ("in2_col", ctypes.c_int), ("cin2", ctypes.c_int), ("weight2_x6", vp), ("weight_pieces", ctypes.c_int), ("acc_scale", ctypes.c_float)]
 
 
+class NetModelParams(ctypes.Structure):
+    """struct cv_net_model_params (include/cv_hip.h)"""
+    _fields_ = [("weight_x6", vp), ("weight2_x6", vp), ("scale", vp), ("shift", vp), ("acc_scale", ctypes.c_float),
+                ("reserved", ctypes.c_int * 3)]
+
+
 class SceneDesc(ctypes.Structure):
     """struct cv_scene_desc (include/cv_hip.h)"""
     _fields_ = [("d_coords4", vp), ("n", ctypes.c_longlong), ("d_feats", vp), ("feats_ld", ctypes.c_int), ("d_points", vp),
@@ -110,7 +116,8 @@ class SceneSeparateDesc(ctypes.Structure):
                 ("max_candidates", ctypes.c_int), ("nms_threshold", ctypes.c_double), ("d_ws", vp), ("ws_bytes", ctypes.c_size_t),
                 ("h_pinned", vp), ("pinned_bytes", ctypes.c_size_t), ("h_cand_idx", vp), ("h_verdict", vp), ("h_boxes", vp),
                 ("h_scores", vp), ("h_det_cat", vp), ("h_det_box", vp), ("events", vp * 5),
-                ("conv_split_target", ctypes.c_int), ("vote_part_records", ctypes.c_int)]
+                ("conv_split_target", ctypes.c_int), ("vote_part_records", ctypes.c_int),
+                ("models_per_pass", ctypes.c_int), ("d_model_params", vp)]
 
 
 class SceneSeparateResult(ctypes.Structure):
@@ -223,6 +230,16 @@ SIGNATURES = {
                                       c_i64_p, ctypes.c_int, vp, ctypes.c_size_t, ctypes.POINTER(vp), c_int_p,
                                       ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int,
                                       vp, ctypes.c_size_t, vp, vp]),
+    "cv_net_models_params_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "cv_net_models_params_fill": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t]),
+    "cv_net_models_arena_bytes": (ctypes.c_size_t, [ctypes.POINTER(NetBuf), ctypes.c_int, c_i64_p, ctypes.c_int, ctypes.c_int]),
+    "cv_net_models_workspace_bytes": (ctypes.c_size_t, [ctypes.c_size_t, ctypes.c_int]),
+    "cv_net_run_models_f32": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             c_i64_p, ctypes.c_int, vp, ctypes.c_size_t, ctypes.POINTER(vp), c_int_p,
+                                             ctypes.POINTER(vp), ctypes.c_int, ctypes.POINTER(vp), ctypes.c_int,
+                                             vp, ctypes.c_size_t, vp, vp, ctypes.c_int, vp]),
+    "cv_head_separate_models_f32": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
+                                                   vp, vp, vp, vp]),
     "cv_sp_mask_keys": (ctypes.c_int, [vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
     "cv_sp_mask_perms": (ctypes.c_int, [vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_size_t,
                                         ctypes.c_int, vp]),

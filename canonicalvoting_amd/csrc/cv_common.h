@@ -116,3 +116,15 @@ int cv_sp_scene_plan_ex(const int32_t* d_input, long long n, int32_t* d_perm, in
 int cv_sp_mask_perms_batch(const CvPermJob* jobs, int n_jobs, void* d_ws, size_t ws_bytes, void* stream,
                            bool pre_zeroed = false);
 
+// cv_sp_conv_f32 over the model axis (cv_net_run_models_f32): `d` describes model 0; the operands of model m are model 0's
+// plus m x the byte strides (0 = shared), its packed weights / affine / acc_scale row m of d_params, its workspace
+// d->ws + m x ws_stride (d->ws_bytes is ONE model's share), its range flag d->range_flag + 16 m.  out_ext: the output is the
+// caller's tensor ext_out[m].  fp16-pair hl programs only (and their matrix-core stem); CV_EINVAL otherwise.
+struct CvConvModels {
+    int models;
+    const cv_net_model_params* d_params;
+    long long in_stride, in2_stride, res_stride, out_stride, ws_stride;
+    int out_ext;
+    float* ext_out[CV_MAX_CATEGORIES];
+};
+int cv_sp_conv_models_f32(const cv_conv_desc* d, const CvConvModels* mm, void* stream);          // sparse_conv.hip

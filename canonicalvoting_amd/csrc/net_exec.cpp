@@ -14,7 +14,22 @@
 
 namespace {
 
-struct Slot { char* ptr; int ld; long long rows; };
+struct Slot { char* ptr; int ld; long long rows; int ext; };      // ext: index into ext_ptr, -1 for an arena buffer
+
+// cv_net_run_models_f32: the K programs behind one launch sequence (net_run below issues model 0's program, every launch
+// covering all K)
+struct NetModels {
+    int K;
+    const void* const* const* ext_ptr;      // [K] tables as cv_net_run_f32's ext_ptr
+    size_t arena_stride, ws_stride;         // bytes between the models' arenas / convolution workspaces
+    const cv_net_model_params* d_params;    // device: row k (params_ld entries apart) holds op k's parameters of the K models
+    int params_ld;
+};
+
+int net_run(const cv_net_op* ops, int n_ops, const cv_net_buf* bufs, int n_bufs, const long long* level_rows, int n_levels,
+            void* d_arena, size_t arena_bytes, const void* const* ext_ptr, const int* ext_ld, const int32_t* const* maps,
+            int n_maps, const int32_t* const* perms, int n_perms, void* d_ws, size_t ws_bytes, int32_t* range_flag,
+            const NetModels* nm, void* stream);
 
 }  // namespace
 
@@ -316,6 +331,97 @@ int cv_net_run_f32(const cv_net_op* ops, int n_ops, const cv_net_buf* bufs, int 
                    int n_levels, void* d_arena, size_t arena_bytes, const void* const* ext_ptr, const int* ext_ld,
                    const int32_t* const* maps, int n_maps, const int32_t* const* perms, int n_perms,
                    void* d_ws, size_t ws_bytes, int32_t* range_flag, void* stream) {
+    return net_run(ops, n_ops, bufs, n_bufs, level_rows, n_levels, d_arena, arena_bytes, ext_ptr, ext_ld, maps, n_maps, perms,
+                   n_perms, d_ws, ws_bytes, range_flag, nullptr, stream);
+}
+
+// ---- K structurally identical programs as one launch sequence -------------------------------------------------------
+size_t cv_net_models_params_bytes(int n_ops, int K) {
+    if (n_ops <= 0 || K < 1 || K > CV_MAX_CATEGORIES) return 0;
+    return sizeof(cv_net_model_params) * (size_t)n_ops * (size_t)K;
+}
+
+int cv_net_models_params_fill(const cv_net_op* const* ops, int n_ops, int K, void* h_params, size_t params_bytes) {
+    CV_REQUIRE(K >= 1 && K <= CV_MAX_CATEGORIES, CV_EINVAL, "number of models out of range (%d, 1..%d)", K, CV_MAX_CATEGORIES);
+    CV_REQUIRE(ops && h_params && n_ops > 0, CV_EINVAL, "bad model table arguments");
+    CV_REQUIRE(params_bytes >= cv_net_models_params_bytes(n_ops, K), CV_ENOMEM, "model table too small (cv_net_models_params_bytes)");
+    for (int m = 0; m < K; ++m) CV_REQUIRE(ops[m], CV_EINVAL, "model %d: null program", m);
+    cv_net_model_params* t = static_cast<cv_net_model_params*>(h_params);
+    for (int k = 0; k < n_ops; ++k)
+        for (int m = 0; m < K; ++m) {
+            const cv_net_op& o = ops[m][k];
+            // (acc_scale as cv_sp_conv_f32 reads it: 0 means 1)
+            t[(size_t)k * K + m] = {o.weight_x6, o.weight2_x6, o.scale, o.shift, o.acc_scale != 0.f ? o.acc_scale : 1.f, {0, 0, 0}};
+        }
+    return CV_OK;
+}
+
+size_t cv_net_models_arena_bytes(const cv_net_buf* bufs, int n_bufs, const long long* level_rows, int n_levels, int K) {
+    if (K < 1 || K > CV_MAX_CATEGORIES) return 0;
+    return (size_t)K * cv_net_arena_bytes(bufs, n_bufs, level_rows, n_levels);       // (a multiple of 256 bytes)
+}
+
+size_t cv_net_models_workspace_bytes(size_t one_model_bytes, int K) {
+    if (K < 1 || K > CV_MAX_CATEGORIES) return 0;
+    return (size_t)(K - 1) * cv_align_up(one_model_bytes, 256) + one_model_bytes;
+}
+
+int cv_net_run_models_f32(const cv_net_op* const* ops, const cv_net_buf* const* bufs, int n_ops, int n_bufs, int K,
+                          const long long* level_rows, int n_levels, void* d_arena, size_t arena_bytes,
+                          const void* const* const* ext_ptr, const int* ext_ld, const int32_t* const* maps, int n_maps,
+                          const int32_t* const* perms, int n_perms, void* d_ws, size_t ws_bytes, int32_t* range_flag,
+                          const void* d_params, int params_ld, void* stream) {
+    CV_REQUIRE(K >= 1 && K <= CV_MAX_CATEGORIES, CV_EINVAL, "number of models out of range (%d, 1..%d)", K, CV_MAX_CATEGORIES);
+    CV_REQUIRE(ops && bufs && level_rows && d_arena && ext_ptr && n_ops > 0 && n_bufs > 0 && n_levels > 0, CV_EINVAL,
+               "bad network program arguments");
+    CV_REQUIRE(d_params, CV_EINVAL, "null model parameter table (cv_net_models_params_fill)");
+    CV_REQUIRE(params_ld >= K, CV_EINVAL, "params_ld (%d) is smaller than the number of models (%d)", params_ld, K);
+    for (int m = 0; m < K; ++m)
+        CV_REQUIRE(ops[m] && bufs[m] && ext_ptr[m], CV_EINVAL, "model %d: null program, buffer list or pointer table", m);
+    // the K programs must be ONE program: every integer field equal, a pointer NULL in all models or in none
+    for (int m = 1; m < K; ++m) {
+        for (int i = 0; i < n_bufs; ++i) {
+            const cv_net_buf &x = bufs[0][i], &y = bufs[m][i];
+            CV_REQUIRE(x.level == y.level && x.channels == y.channels && x.rows_level == y.rows_level && x.hl == y.hl, CV_EINVAL,
+                       "buffer %d of model %d differs from model 0's: the programs are not structurally identical", i, m);
+        }
+        for (int k = 0; k < n_ops; ++k) {
+            const cv_net_op &x = ops[0][k], &y = ops[m][k];
+            const bool same = x.in_buf == y.in_buf && x.in_col == y.in_col && x.cin == y.cin && x.out_buf == y.out_buf &&
+                              x.out_col == y.out_col && x.cout == y.cout && x.res_buf == y.res_buf && x.res_col == y.res_col &&
+                              x.map == y.map && x.K == y.K && x.perm == y.perm && x.perm_groups == y.perm_groups &&
+                              x.relu == y.relu && x.in2_buf == y.in2_buf && x.in2_col == y.in2_col && x.cin2 == y.cin2 &&
+                              x.weight_pieces == y.weight_pieces && !x.weight == !y.weight && !x.scale == !y.scale &&
+                              !x.shift == !y.shift && !x.weight_x6 == !y.weight_x6 && !x.weight2_x6 == !y.weight2_x6;
+            CV_REQUIRE(same, CV_EINVAL, "op %d of model %d differs from model 0's: the programs are not structurally identical", k, m);
+        }
+    }
+    for (int k = 0; k < n_ops; ++k)
+        for (int m = 0; m < K; ++m) {
+            const cv_net_op& o = ops[m][k];
+            CV_REQUIRE(o.weight_pieces == 2, CV_EINVAL, "op %d: the model axis runs fp16-pair programs only (weight_pieces == 2)", k);
+            CV_REQUIRE(((reinterpret_cast<uintptr_t>(o.scale) | reinterpret_cast<uintptr_t>(o.shift) |
+                         reinterpret_cast<uintptr_t>(o.weight_x6) | reinterpret_cast<uintptr_t>(o.weight2_x6)) & 15) == 0, CV_EINVAL,
+                       "op %d of model %d: scale, shift and packed weights must be 16-byte aligned", k, m);
+        }
+    const size_t arena_one = cv_net_arena_bytes(bufs[0], n_bufs, level_rows, n_levels);
+    CV_REQUIRE(arena_bytes >= (size_t)K * arena_one, CV_ENOMEM, "arena too small (cv_net_models_arena_bytes)");
+    // one model's share of the workspace: what cv_net_run_f32 would be handed
+    const size_t ws_stride = K > 1 ? (ws_bytes / (size_t)K) & ~(size_t)255 : 0;
+    const size_t ws_one = K > 1 ? ws_stride : ws_bytes;
+    NetModels nm = {K, ext_ptr, arena_one, ws_stride, static_cast<const cv_net_model_params*>(d_params), params_ld};
+    return net_run(ops[0], n_ops, bufs[0], n_bufs, level_rows, n_levels, d_arena, arena_one, ext_ptr[0], ext_ld, maps, n_maps,
+                   perms, n_perms, d_ws, ws_one, range_flag, &nm, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+int net_run(const cv_net_op* ops, int n_ops, const cv_net_buf* bufs, int n_bufs, const long long* level_rows, int n_levels,
+            void* d_arena, size_t arena_bytes, const void* const* ext_ptr, const int* ext_ld, const int32_t* const* maps,
+            int n_maps, const int32_t* const* perms, int n_perms, void* d_ws, size_t ws_bytes, int32_t* range_flag,
+            const NetModels* nm, void* stream) {
     CV_REQUIRE(ops && bufs && level_rows && d_arena && n_ops > 0 && n_bufs > 0 && n_levels > 0, CV_EINVAL,
                "bad network program arguments");
     CV_REQUIRE(arena_bytes >= cv_net_arena_bytes(bufs, n_bufs, level_rows, n_levels), CV_ENOMEM, "arena too small");
@@ -328,11 +434,14 @@ int cv_net_run_f32(const cv_net_op* ops, int n_ops, const cv_net_buf* bufs, int 
             if (lv < 0 || lv >= n_levels) {                                   // external: caller's tensor
                 CV_REQUIRE(ext_ptr && ext_ld && ext_ptr[ext], CV_EINVAL, "external buffer %d has no pointer", ext);
                 slot[i] = {static_cast<char*>(const_cast<void*>(ext_ptr[ext])), ext_ld[ext], bufs[i].rows_level >= 0 &&
-                           bufs[i].rows_level < n_levels ? level_rows[bufs[i].rows_level] : 0};
+                           bufs[i].rows_level < n_levels ? level_rows[bufs[i].rows_level] : 0, ext};
+                if (nm)
+                    for (int m = 1; m < nm->K; ++m)
+                        CV_REQUIRE(nm->ext_ptr[m][ext], CV_EINVAL, "external buffer %d of model %d has no pointer", ext, m);
                 ++ext;
             } else {
                 slot[i] = {reinterpret_cast<char*>(cv.take<float>((size_t)level_rows[lv] * bufs[i].channels)),
-                           bufs[i].channels, level_rows[lv]};
+                           bufs[i].channels, level_rows[lv], -1};
             }
         }
     }
@@ -390,10 +499,43 @@ int cv_net_run_f32(const cv_net_op* ops, int n_ops, const cv_net_buf* bufs, int 
             d.perm_groups = o.perm_groups;
             d.perm_has_map = o.perm_groups > 1;      /* scene maps build the orders with their map rows */
         }
-        const int rc = cv_sp_conv_f32(&d, stream);
+        int rc;
+        if (nm) {
+            // the model axis: arena operands one arena apart, a tensor of the caller read by every model shared (stride 0), the
+            // caller's output per model
+            CvConvModels cm = {};
+            cm.models = nm->K;
+            cm.d_params = nm->d_params + (size_t)k * nm->params_ld;
+            cm.ws_stride = (long long)nm->ws_stride;
+            auto stride_of = [&](int buf, long long* stride) -> int {
+                const int e = slot[buf].ext;
+                if (e < 0) { *stride = (long long)nm->arena_stride; return CV_OK; }
+                for (int m = 1; m < nm->K; ++m)
+                    CV_REQUIRE(nm->ext_ptr[m][e] == nm->ext_ptr[0][e], CV_EINVAL,
+                               "op %d: the external buffer it reads must be the same tensor for every model (model %d differs)", k, m);
+                *stride = 0;
+                return CV_OK;
+            };
+            if ((rc = stride_of(o.in_buf, &cm.in_stride)) != CV_OK) return rc;
+            if (o.in2_buf >= 0 && (rc = stride_of(o.in2_buf, &cm.in2_stride)) != CV_OK) return rc;
+            if (o.res_buf >= 0 && (rc = stride_of(o.res_buf, &cm.res_stride)) != CV_OK) return rc;
+            if (out.ext >= 0) {
+                cm.out_ext = 1;
+                for (int m = 0; m < nm->K; ++m) {
+                    float* p = reinterpret_cast<float*>(const_cast<void*>(nm->ext_ptr[m][out.ext])) + o.out_col;
+                    CV_REQUIRE((reinterpret_cast<uintptr_t>(p) & 15) == 0, CV_EINVAL, "op %d: output of model %d is not 16-byte aligned", k, m);
+                    cm.ext_out[m] = p;
+                }
+            } else {
+                cm.out_stride = (long long)nm->arena_stride;
+            }
+            rc = cv_sp_conv_models_f32(&d, &cm, stream);
+        } else {
+            rc = cv_sp_conv_f32(&d, stream);
+        }
         if (rc != CV_OK) return rc;
     }
     return CV_OK;
 }
 
-}  // extern "C"
+}  // namespace

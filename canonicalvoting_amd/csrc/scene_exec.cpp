@@ -262,7 +262,7 @@ int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream
 }
 
 // eval_separate.py:162-264 as one call: the coordinate plan once, the K programs on it one after another (one shared arena:
-// they are ordered on the stream), K heads into [K][n] arrays, ONE vote and ONE decode over the category axis, NMS per category.
+// they are ordered on the stream) or, with models_per_pass, as launches over a model axis (cv_net_run_models_f32), K heads into [K][n] arrays, ONE vote and ONE decode over the category axis, NMS per category.
 int cv_detect_scene_separate_f32(const cv_scene_separate_desc* d, cv_scene_separate_result* r, void* stream) {
     CV_REQUIRE(d && r, CV_EINVAL, "null scene descriptor / result");
     std::memset(r, 0, sizeof(*r));
@@ -280,6 +280,14 @@ int cv_detect_scene_separate_f32(const cv_scene_separate_desc* d, cv_scene_separ
                CV_EINVAL, "null result arrays");
     CV_REQUIRE(!!d->d_xyz_in == !!d->d_scale_in && !!d->d_xyz_in == !!d->d_prob_in, CV_EINVAL, "predictions: all three or none");
     CV_REQUIRE(d->conv_split_target >= 0 && d->vote_part_records >= 0, CV_EINVAL, "negative launch sizing");
+    CV_REQUIRE(d->models_per_pass >= 0, CV_EINVAL, "negative models_per_pass (%d)", d->models_per_pass);
+    const int G = std::min(d->models_per_pass, K);          // models per pass of the batched network (0: one after another)
+    if (G > 0) {
+        CV_REQUIRE(d->d_model_params, CV_EINVAL, "models_per_pass needs d_model_params (cv_net_models_params_fill)");
+        for (int k = 1; k < K; ++k)
+            CV_REQUIRE(d->n_ops[k] == d->n_ops[0] && d->n_bufs[k] == d->n_bufs[0], CV_EINVAL,
+                       "models_per_pass: the program of model %d has another length than model 0's", k);
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long n = d->n;
     SceneCount in_flight(false, d->conv_split_target, d->vote_part_records);
@@ -306,8 +314,11 @@ int cv_detect_scene_separate_f32(const cv_scene_separate_desc* d, cv_scene_separ
     for (int k = 0; k < K; ++k) arena_b = std::max(arena_b, cv_net_arena_bytes(d->bufs[k], d->n_bufs[k], f.rows, 5));
     const size_t vote_ws_b = cv_hv_forward_cat_workspace_bytes(n, d->num_rots, f.dims, d->vote_algo, K);
     const size_t dec_ws_b = cv_decode_cat_workspace_bytes(f.dims, n, d->max_candidates, K);
-    char* arena = cv.take<char>(arena_b);
-    char* conv_ws = cv.take<char>(f.conv_ws_b);
+    // (batched: G arenas and G convolution workspaces live at once)
+    const size_t arena_all = G > 0 ? (size_t)G * arena_b : arena_b;
+    const size_t conv_ws_all = G > 0 ? cv_net_models_workspace_bytes(f.conv_ws_b, G) : f.conv_ws_b;
+    char* arena = cv.take<char>(arena_all);
+    char* conv_ws = cv.take<char>(conv_ws_all);
     char* vote_ws = cv.take<char>(std::max<size_t>(vote_ws_b, 256));
     char* dec_ws = cv.take<char>(dec_ws_b);
     float* grids = cv.take<float>(6 * cells * (size_t)K);
@@ -318,8 +329,23 @@ int cv_detect_scene_separate_f32(const cv_scene_separate_desc* d, cv_scene_separ
     float* g_scale = grids + 3 * cells * K;
     r->d_grid_obj = g_obj; r->d_grid_rot = g_rot; r->d_grid_scale = g_scale;
 
-    // ---- K network programs on the shared plan
-    for (int k = 0; k < K; ++k) {
+    // ---- K network programs on the shared plan: in passes of up to G over the model axis, or one after another
+    for (int m0 = 0; G > 0 && m0 < K; m0 += G) {
+        const int g = std::min(G, K - m0);
+        const void* ext_ptr[CV_MAX_CATEGORIES][2];
+        const void* const* ext_tab[CV_MAX_CATEGORIES];
+        for (int m = 0; m < g; ++m) {
+            ext_ptr[m][0] = d->d_feats, ext_ptr[m][1] = d->d_out_feats[m0 + m];
+            ext_tab[m] = ext_ptr[m];
+        }
+        const int ext_ld[2] = {d->feats_ld, d->out_ld};
+        rc = cv_net_run_models_f32(d->ops + m0, d->bufs + m0, d->n_ops[0], d->n_bufs[0], g, f.rows, 5, arena, arena_all, ext_tab, ext_ld,
+                                   f.maps, CV_NET_MAP_SLOTS, f.perms, CV_NET_PERM_SLOTS, conv_ws, conv_ws_all,
+                                   d->use_range_flag ? d_flags + 16 * m0 : nullptr,
+                                   static_cast<const cv_net_model_params*>(d->d_model_params) + m0, K, stream);
+        if (rc != CV_OK) return rc;
+    }
+    for (int k = 0; G == 0 && k < K; ++k) {
         const void* ext_ptr[2] = {d->d_feats, d->d_out_feats[k]};
         const int ext_ld[2] = {d->feats_ld, d->out_ld};
         rc = cv_net_run_f32(d->ops[k], d->n_ops[k], d->bufs[k], d->n_bufs[k], f.rows, 5, arena, arena_b, ext_ptr, ext_ld, f.maps,
@@ -329,7 +355,11 @@ int cv_detect_scene_separate_f32(const cv_scene_separate_desc* d, cv_scene_separ
     }
     clock.lap(1);
     CV_HIP_CHECK(clock.mark(1));
-    for (int k = 0; k < K; ++k) {
+    if (G > 0) {        // one head launch over the model axis
+        rc = cv_head_separate_models_f32(d->d_out_feats, K, n, d->out_ld, d->log_scale, xyz, scale, prob, stream);
+        if (rc != CV_OK) return rc;
+    }
+    for (int k = 0; G == 0 && k < K; ++k) {
         rc = cv_head_separate_f32(d->d_out_feats[k], n, d->out_ld, d->log_scale, xyz + (size_t)k * n * 3, scale + (size_t)k * n * 3,
                                   prob + (size_t)k * n, stream);
         if (rc != CV_OK) return rc;

@@ -600,9 +600,12 @@ constexpr int HL_MAX_UNITS = 512;      // live units of one workgroup: <= 10 off
 // restates it, because an explicit amdgpu_waves_per_eu replaces the bound __launch_bounds__ implies - a (1, 8) range
 // silently cost the 96-column kernel a workgroup per CU for most of round 3)
 constexpr int hl_blocks(int NB) { return NB <= 3 ? 4 : 2; }
-template <int NB>
+// MA: empty - the kernel as it always was - or one ModelArgs (the model axis of cv_net_run_models_f32, a separate
+// instantiation): blockIdx.y = model * ma.ncb + column block, and model_enter swaps the model's operands into `a` at entry.
+template <int NB, class... MA>
 __global__ __attribute__((amdgpu_waves_per_eu(hl_blocks(NB), 8)))
-__launch_bounds__(THREADS, hl_blocks(NB)) void conv_hl(ConvArgs a) {
+__launch_bounds__(THREADS, hl_blocks(NB)) void conv_hl(ConvArgs a, MA... ma) {
+    const unsigned by = model_enter(a, blockIdx.y, ma...);                  // column block
     constexpr int NS = 2, NW = THREADS / 64;                                // unit slots, waves
     constexpr int B_BYTES = 2 * NB * 32 * 64, EP_BYTES = NW * 32 * EP_LD * 4;
     constexpr int SM_BYTES = NS * B_BYTES > EP_BYTES ? NS * B_BYTES : EP_BYTES;
@@ -612,7 +615,7 @@ __launch_bounds__(THREADS, hl_blocks(NB)) void conv_hl(ConvArgs a) {
     __shared__ unsigned wave_mask[NW];
     __shared__ unsigned short units_s[HL_MAX_UNITS + 4];      // (jj << 8) | chunk of every live unit, in processing order; [HL_MAX_UNITS] = count
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n0 = blockIdx.y * (NB * 32);
+    const int n0 = by * (NB * 32);
     const long long tile_id = xcd_tile(a);
     if (tile_id * TM >= a.n_out) return;             // padding of the XCD-aware grid
     const int half = lane >> 5, l31 = lane & 31;
@@ -792,6 +795,7 @@ __launch_bounds__(THREADS, hl_blocks(NB)) void conv_hl(ConvArgs a) {
         step(S1{}, S0{}, k + 1);
     }
     __syncthreads();                                 // weight tiles are dead: the epilogue tile reuses their LDS
+    model_epilogue(a, blockIdx.y, ma...);
     {
         const float sc = a.acc_scale_dev ? a.acc_scale * *a.acc_scale_dev : a.acc_scale;
 #pragma unroll
@@ -813,7 +817,7 @@ __launch_bounds__(THREADS, hl_blocks(NB)) void conv_hl(ConvArgs a) {
         __shared__ int last_flag;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        int* ticket = a.tickets + tile_id * gridDim.y + blockIdx.y;
+        int* ticket = a.tickets + tile_id * gridDim.y + by;
         if (tid == 0) {
             const int old = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             last_flag = old == a.splits - 1;
@@ -877,8 +881,9 @@ constexpr int hd_blocks(int NB, int NW, int NSTG) {          // workgroups per C
 }
 // NW waves x 32 rows per workgroup, NSTG ring stages: <8, 3> one workgroup per CU with the requests of two units in flight
 // behind the one that multiplies; <4, 2> two workgroups per CU, one unit of prefetch each
-template <int NB, int NW, int NSTG>
-__global__ __launch_bounds__(NW * 64, (hd_blocks(NB, NW, NSTG) * NW + 3) / 4) void conv_hd(ConvArgs a) {
+template <int NB, int NW, int NSTG, class... MA>       // (MA: see conv_hl)
+__global__ __launch_bounds__(NW * 64, (hd_blocks(NB, NW, NSTG) * NW + 3) / 4) void conv_hd(ConvArgs a, MA... ma) {
+    const unsigned by = model_enter(a, blockIdx.y, ma...);
     static_assert(NSTG == 2 || NSTG == 3, "two or three ring stages");
     constexpr int TMv = NW * 32, THv = NW * 64;
     constexpr int A_BYTES = NW * 4096, B_BYTES = 2 * NB * 32 * 64, STAGE = A_BYTES + B_BYTES;
@@ -898,7 +903,7 @@ __global__ __launch_bounds__(NW * 64, (hd_blocks(NB, NW, NSTG) * NW + 3) / 4) vo
     unsigned* const wave_mask = reinterpret_cast<unsigned*>(lds + OFF_MASK);
     unsigned short* const units_s = reinterpret_cast<unsigned short*>(lds + OFF_UNITS);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n0 = blockIdx.y * (NB * 32);
+    const int n0 = by * (NB * 32);
     const long long tile_id = xcd_tile(a);
     const int half = lane >> 5, l31 = lane & 31;
     const int nj = a.j_end - a.j_begin;
@@ -1116,6 +1121,7 @@ __global__ __launch_bounds__(NW * 64, (hd_blocks(NB, NW, NSTG) * NW + 3) / 4) vo
     }
     wait_vmcnt_le<0>();
     __syncthreads();                                 // the ring is dead: the epilogue tile reuses its LDS
+    model_epilogue(a, blockIdx.y, ma...);
     {
         const float sc = a.acc_scale_dev ? a.acc_scale * *a.acc_scale_dev : a.acc_scale;
 #pragma unroll
@@ -1148,8 +1154,9 @@ __global__ __launch_bounds__(NW * 64, (hd_blocks(NB, NW, NSTG) * NW + 3) / 4) vo
 // v_mfma_f32_32x32x16_f16 (k = the 16 offsets of the group, one MFMA triple per input channel).  The weights
 // (cv_sp_pack_weights_stem_h2_f32: BatchNorm scale and a power of two folded in, fp16 pairs in B-operand order,
 // 16 KB per input channel) sit in LDS for the whole workgroup.  Same products as the fp32 chain to 2^-22, fp32 accumulation.
-template <int CIN>
-__global__ __launch_bounds__(THREADS, (CIN <= 3 ? 3 : 1)) void conv_stem_mfma(ConvArgs a) {
+template <int CIN, class... MA>       // (MA: empty or one ModelArgs - blockIdx.y = model; the input rows are shared)
+__global__ __launch_bounds__(THREADS, (CIN <= 3 ? 3 : 1)) void conv_stem_mfma(ConvArgs a, MA... ma) {
+    model_enter_y(a, ma...);
     constexpr int G = 8;                              // groups of 16 kernel offsets (K <= 128)
     constexpr int W_BYTES = G * CIN * 2 * 1024;       // [group][channel][plane][col][half][8] fp16
     constexpr int EP_BYTES = 4 * 32 * EP_LD * 4;
@@ -1524,7 +1531,10 @@ __global__ __launch_bounds__(256) void col_sum_chunks(const float* __restrict__ 
 // One thread per 4 consecutive columns (float4 loads, cout % 4 == 0) and per quarter of the splits;
 // the four quarter-sums meet through LDS, so small outputs with many splits still have enough loads
 // in flight (a one-thread-per-element loop over 64 splits ran at 1.7 TB/s).
-__global__ __launch_bounds__(256) void conv_finish(ConvArgs a) {
+// (MA, here and in the two kernels below: empty, or one ModelArgs - blockIdx.y = model, the grid-stride loop over x unchanged)
+template <class... MA>
+__global__ __launch_bounds__(256) void conv_finish(ConvArgs a, MA... ma) {
+    model_enter_y(a, ma...);
     __shared__ float4 red[4][64];
     const int q = threadIdx.x >> 6, l = threadIdx.x & 63;
     const long long total4 = a.n_out * (long long)a.cout / 4;
@@ -1591,7 +1601,9 @@ __global__ __launch_bounds__(256) void conv_finish(ConvArgs a) {
 // itself - no LDS exchange, no barriers, every thread stores (ts1 96 -> 96 conv + finish: 125 -> 104 us).  Summation
 // order = conv_finish's: four running sums over the partials k % 4, then ((s0 + s1) + s2) + s3 - bit-identical results.
 constexpr int FINISH_SMALL_MAX = 16;
-__global__ __launch_bounds__(256) void conv_finish_small(ConvArgs a) {
+template <class... MA>
+__global__ __launch_bounds__(256) void conv_finish_small(ConvArgs a, MA... ma) {
+    model_enter_y(a, ma...);
     const long long total4 = a.n_out * (long long)a.cout / 4;
     const int cq = a.cout >> 2;
     for (long long e4 = blockIdx.x * 256ll + threadIdx.x; e4 < total4; e4 += (long long)gridDim.x * 256) {
@@ -1634,7 +1646,9 @@ __global__ __launch_bounds__(256) void conv_finish_small(ConvArgs a) {
 }
 
 // scalar variant for cout % 4 != 0
-__global__ __launch_bounds__(256) void conv_finish_scalar(ConvArgs a) {
+template <class... MA>
+__global__ __launch_bounds__(256) void conv_finish_scalar(ConvArgs a, MA... ma) {
+    model_enter_y(a, ma...);
     const long long total = a.n_out * (long long)a.cout;
     for (long long t = blockIdx.x * 256ll + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
         const long long row = t / a.cout;
@@ -1652,9 +1666,20 @@ __global__ __launch_bounds__(256) void conv_finish_scalar(ConvArgs a) {
 }  // namespace
 namespace cvsc {
 std::atomic<int> g_ablation{0};
-int launch_finish(const ConvArgs& a, hipStream_t st) {
+int launch_finish(const ConvArgs& a, hipStream_t st, const ModelArgs* ma, int models) {
     if (g_ablation.load(std::memory_order_relaxed) & 1) return CV_OK;      // cv_sp_set_ablation: timing only
     const long long total = a.n_out * (long long)a.cout;
+    if (ma) {       // the same kernel choice and x grid per model, the model on blockIdx.y
+        const unsigned my = (unsigned)models;
+        if (a.wide && a.splits <= FINISH_SMALL_MAX)
+            conv_finish_small<ModelArgs><<<dim3((unsigned)std::min<long long>((total / 4 + 255) / 256, 16384), my), 256, 0, st>>>(a, *ma);
+        else if (a.cout % 4 == 0)
+            conv_finish<ModelArgs><<<dim3((unsigned)std::min<long long>((total / 4 + 63) / 64, 8192), my), 256, 0, st>>>(a, *ma);
+        else
+            conv_finish_scalar<ModelArgs><<<dim3((unsigned)std::min<long long>((total + 255) / 256, 4096), my), 256, 0, st>>>(a, *ma);
+        CV_LAUNCH_CHECK();
+        return CV_OK;
+    }
     if (a.wide && a.splits <= FINISH_SMALL_MAX)
         conv_finish_small<<<(unsigned)std::min<long long>((total / 4 + 255) / 256, 16384), 256, 0, st>>>(a);
     else if (a.cout % 4 == 0)
@@ -2276,6 +2301,25 @@ __global__ __launch_bounds__(256) void head_separate(const float* __restrict__ f
     prob[i] = e1 / (e0 + e1);
 }
 
+// the same head over the model axis: blockIdx.y = model, outputs [K][n][3], [K][n][3], [K][n]
+struct HeadModels { const float* f[CV_MAX_CATEGORIES]; };
+__global__ __launch_bounds__(256) void head_separate_models(HeadModels hm, long long n, int ld, int log_scale,
+                                                            float* __restrict__ xyz, float* __restrict__ scale,
+                                                            float* __restrict__ prob) {
+    const long long i = blockIdx.x * 256ll + threadIdx.x;
+    if (i >= n) return;
+    const int m = blockIdx.y;
+    const float* row = hm.f[m] + i * ld;
+    xyz += (long long)m * n * 3, scale += (long long)m * n * 3, prob += (long long)m * n;
+    for (int d = 0; d < 3; ++d) {
+        xyz[i * 3 + d] = row[d];
+        scale[i * 3 + d] = log_scale ? expf(row[3 + d]) : row[3 + d];
+    }
+    const float mx = fmaxf(row[6], row[7]);
+    const float e0 = expf(row[6] - mx), e1 = expf(row[7] - mx);
+    prob[i] = e1 / (e0 + e1);
+}
+
 // run-time options (cv_sp_set_option): conv_hd switch (bit NB - 1) and its row threshold; defaults from the environment
 // defaults (profiles/r4/hd2_grid.txt, hd_shapes.txt): the 96-column fine-level launches (>= 16384 rows) on conv_hd, 8 waves x 2 ring
 // stages: 558 -> 573 scenes/s with eight scenes in flight (528 -> 575 under the one-call scene path); 32- and 64-column
@@ -2289,8 +2333,9 @@ std::atomic<long long> g_opt_hd_mask{getenv("CV_HD") ? atoll(getenv("CV_HD")) : 
 std::atomic<long long> g_opt_hd_min_rows{getenv("CV_HD_MIN_ROWS") ? atoll(getenv("CV_HD_MIN_ROWS")) : 16384};
 std::atomic<long long> g_opt_hd_shape{getenv("CV_HD_SHAPE") ? atoll(getenv("CV_HD_SHAPE")) : 2};      // 0: 8 waves x 3 stages, 1: 4 x 2, 2: 8 x 2
 
+// ma / models: the launch covers `models` models (cv_sp_conv_models_f32): grid.y = models x column blocks, the kernels' ModelArgs instantiations
 template <int NB>
-int launch_rows(const ConvArgs& a, bool vec, hipStream_t st) {
+int launch_rows(const ConvArgs& a, bool vec, hipStream_t st, ModelArgs* ma = nullptr, int models = 1) {
     dim3 grid((unsigned)((a.n_out + TM - 1) / TM), (unsigned)((a.cout + NB * 32 - 1) / (NB * 32)),
               (unsigned)a.splits);
     int per_wg = 0;                                  // most offsets one workgroup walks (the kernel's own formulas)
@@ -2311,6 +2356,13 @@ int launch_rows(const ConvArgs& a, bool vec, hipStream_t st) {
     static const bool xcd_on = getenv("CV_XCD_TILES") && atoi(getenv("CV_XCD_TILES")) != 0;      // experiment, off
     ConvArgs ax = a;
     dim3 gridx = grid;
+    if (ma) {
+        CV_REQUIRE(!xcd_on, CV_EINVAL, "the model axis does not run with the CV_XCD_TILES experiment");
+        CV_REQUIRE(a.in_hl && !a.tickets, CV_EINVAL,
+                   "the model axis runs fp16-pair programs on hl buffers only (no fp32 / bf16 convolution, no split_tickets)");
+        ma->ncb = (int)grid.y;
+    }
+    const dim3 grid_m(grid.x, grid.y * (unsigned)models, grid.z);
     if (xcd_on && grid.x >= 64) {                    // a few tiles per XCD at least; below that the input fits every L2
         ax.xcd_tiles = 1;
         gridx.x = (grid.x + 7) / 8 * 8;
@@ -2336,6 +2388,15 @@ int launch_rows(const ConvArgs& a, bool vec, hipStream_t st) {
                 ah.tickets = nullptr;
                 const int nw = hd_shape == 1 ? 4 : 8;
                 dim3 g((unsigned)((a.n_out + nw * 32 - 1) / (nw * 32)), grid.y, grid.z);
+                if (ma) {
+                    g.y = grid_m.y;
+                    if (hd_shape == 1) conv_hd<NB, 4, 2, ModelArgs><<<g, 256, 0, st>>>(ah, *ma);
+                    else if (hd_shape == 2) conv_hd<NB, 8, 2, ModelArgs><<<g, 512, 0, st>>>(ah, *ma);
+                    else conv_hd<NB, 8, 3, ModelArgs><<<g, 512, 0, st>>>(ah, *ma);
+                    CV_LAUNCH_CHECK();
+                    if (a.splits > 1) return launch_finish(a, st, ma, models);
+                    return CV_OK;
+                }
                 if (hd_shape == 1) conv_hd<NB, 4, 2><<<g, 256, 0, st>>>(ah);
                 else if (hd_shape == 2) conv_hd<NB, 8, 2><<<g, 512, 0, st>>>(ah);
                 else conv_hd<NB, 8, 3><<<g, 512, 0, st>>>(ah);
@@ -2346,6 +2407,12 @@ int launch_rows(const ConvArgs& a, bool vec, hipStream_t st) {
         }
         // split-K reduced by the last-arriving workgroup for callers that pass cv_conv_desc.split_tickets: bit-identical to the
         // finish launch (tests); the network executor does not hand tickets over (net_exec.cpp: measured slower)
+        if (ma) {
+            conv_hl<NB, ModelArgs><<<grid_m, THREADS, 0, st>>>(ax, *ma);
+            CV_LAUNCH_CHECK();
+            if (a.splits > 1) return launch_finish(a, st, ma, models);
+            return CV_OK;
+        }
         if (!(ax.splits > 1 && !ax.perm_per_split && !ax.xcd_tiles && (long long)gridx.x * gridx.y <= CV_SPLIT_TICKETS))
             ax.tickets = nullptr;
         conv_hl<NB><<<gridx, THREADS, 0, st>>>(ax);
@@ -2506,6 +2573,8 @@ int cv_sp_mask_perms_batch(const CvPermJob* jobs, int n_jobs, void* d_ws, size_t
     return CV_OK;
 }
 
+static int conv_dispatch(const cv_conv_desc* d, const CvConvModels* mm, void* stream);
+
 extern "C" {
 
 size_t cv_sp_conv_workspace_bytes(long long n_out, int cout, int K) {
@@ -2515,7 +2584,22 @@ size_t cv_sp_conv_workspace_bytes(long long n_out, int cout, int K) {
                                                                                             // 3-way split of conv_hl)
 }
 
-int cv_sp_conv_f32(const cv_conv_desc* d, void* stream) {
+int cv_sp_conv_f32(const cv_conv_desc* d, void* stream) { return conv_dispatch(d, nullptr, stream); }
+
+}  // extern "C"
+
+int cv_sp_conv_models_f32(const cv_conv_desc* d, const CvConvModels* mm, void* stream) {
+    CV_REQUIRE(d && mm && mm->d_params && mm->models >= 1 && mm->models <= CV_MAX_CATEGORIES, CV_EINVAL, "bad model-axis arguments");
+    CV_REQUIRE(!d->split_tickets, CV_EINVAL, "the model axis does not take split_tickets");
+    CV_REQUIRE(d->weight_pieces == 2 && !d->acc_in && !d->acc_scale_dev, CV_EINVAL,
+               "the model axis runs fp16-pair programs only (weight_pieces == 2; no bf16 triples, no fp32 convolution)");
+    CV_REQUIRE(((mm->in_stride | mm->in2_stride | mm->res_stride | mm->out_stride | mm->ws_stride) & 127) == 0, CV_EINVAL,
+               "model strides must keep rows 128-byte aligned");
+    return conv_dispatch(d, mm, stream);
+}
+
+// mm: the launches cover mm->models models (cv_sp_conv_models_f32); every choice below is made from ONE model's sizes
+static int conv_dispatch(const cv_conv_desc* d, const CvConvModels* mm, void* stream) {
     CV_REQUIRE(d, CV_EINVAL, "null descriptor");
     CV_REQUIRE(d->in && d->weight && d->out, CV_EINVAL, "null pointer argument");
     CV_REQUIRE(d->n_in > 0 && d->n_out > 0 && d->cin > 0 && d->cout > 0 && d->K > 0, CV_EINVAL, "bad conv sizes");
@@ -2559,6 +2643,16 @@ int cv_sp_conv_f32(const cv_conv_desc* d, void* stream) {
                "cv_sp_pack_weights_stem_h2_f32)");
 
     if (!d->in_hl) a.tickets = nullptr;       // the in-launch split-K reduction exists in conv_hl only
+    ModelArgs ma = {};
+    if (mm) {
+        ma.params = mm->d_params;
+        ma.in_stride = mm->in_stride, ma.in2_stride = mm->in2_stride, ma.res_stride = mm->res_stride, ma.out_stride = mm->out_stride;
+        ma.partial_stride = mm->ws_stride;
+        ma.out_ext = mm->out_ext;
+        for (int m = 0; m < mm->models; ++m) ma.ext_out[m] = mm->ext_out[m];
+    }
+    ModelArgs* const pma = mm ? &ma : nullptr;
+    const int models = mm ? mm->models : 1;
     CV_REQUIRE(!d->plan_ent && !d->plan_cnt && !d->weight_packed && (d->flavour == 0 || d->flavour == 1), CV_EINVAL,
                "flavours 3 / 4 (the experimental wave / tile kernels of rounds 1-3) are gone: flavour is 0 or 1, plan_ent / plan_cnt / "
                "weight_packed must be NULL");
@@ -2591,12 +2685,17 @@ int cv_sp_conv_f32(const cv_conv_desc* d, void* stream) {
             (d->j_end == 0 || d->j_end == d->K)) {
             // matrix-core stem (weights from cv_sp_pack_weights_stem_h2_f32, BatchNorm scale folded in)
             const unsigned gm = (unsigned)((d->n_out + TM - 1) / TM);
-            if (d->cin == 3) conv_stem_mfma<3><<<gm, THREADS, 0, st>>>(a);
+            if (mm) {
+                const dim3 g(gm, (unsigned)mm->models);
+                if (d->cin == 3) conv_stem_mfma<3, ModelArgs><<<g, THREADS, 0, st>>>(a, ma);
+                else conv_stem_mfma<6, ModelArgs><<<g, THREADS, 0, st>>>(a, ma);
+            } else if (d->cin == 3) conv_stem_mfma<3><<<gm, THREADS, 0, st>>>(a);
             else conv_stem_mfma<6><<<gm, THREADS, 0, st>>>(a);
             CV_LAUNCH_CHECK();
             return CV_OK;
         }
     }
+    CV_REQUIRE(!mm || d->in_hl, CV_EINVAL, "the model axis runs fp16-pair programs on hl buffers only (and their matrix-core stem)");
     a.acc_scale_dev = d->acc_scale_dev;
     if (d->perm_groups > 1) {
         // offsets split into perm_groups contiguous groups, each processed in its own row order, all in
@@ -2635,12 +2734,14 @@ int cv_sp_conv_f32(const cv_conv_desc* d, void* stream) {
         }
     }
     switch (nb_for(d->cout)) {
-        case 1: return launch_rows<1>(a, vec, st);
-        case 2: return launch_rows<2>(a, vec, st);
-        case 3: return launch_rows<3>(a, vec, st);
-        default: return launch_rows<4>(a, vec, st);
+        case 1: return launch_rows<1>(a, vec, st, pma, models);
+        case 2: return launch_rows<2>(a, vec, st, pma, models);
+        case 3: return launch_rows<3>(a, vec, st, pma, models);
+        default: return launch_rows<4>(a, vec, st, pma, models);
     }
 }
+
+extern "C" {
 
 // d_keys[n] = bit mask of valid neighbours among kernel offsets [j_begin, j_end) of each output row.
 // Sorting rows by this key groups rows that need the same offsets (cv_conv_desc.row_perm).
@@ -3140,6 +3241,21 @@ int cv_head_separate_f32(const float* d_feats, long long n, int ld, int log_scal
     CV_REQUIRE(d_feats && d_xyz && d_scale && d_prob && n > 0 && ld >= 8, CV_EINVAL, "bad head arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);
     head_separate<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(d_feats, n, ld, log_scale, d_xyz, d_scale, d_prob);
+    CV_LAUNCH_CHECK();
+    return CV_OK;
+}
+
+int cv_head_separate_models_f32(const float* const* d_feats, int K, long long n, int ld, int log_scale, float* d_xyz,
+                                float* d_scale, float* d_prob, void* stream) {
+    CV_REQUIRE(d_feats && d_xyz && d_scale && d_prob && n > 0 && ld >= 8, CV_EINVAL, "bad head arguments");
+    CV_REQUIRE(K >= 1 && K <= CV_MAX_CATEGORIES, CV_EINVAL, "number of models out of range (%d, 1..%d)", K, CV_MAX_CATEGORIES);
+    HeadModels hm = {};
+    for (int k = 0; k < K; ++k) {
+        CV_REQUIRE(d_feats[k], CV_EINVAL, "model %d: null network output", k);
+        hm.f[k] = d_feats[k];
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    head_separate_models<<<dim3((unsigned)((n + 255) / 256), (unsigned)K), 256, 0, st>>>(hm, n, ld, log_scale, d_xyz, d_scale, d_prob);
     CV_LAUNCH_CHECK();
     return CV_OK;
 }

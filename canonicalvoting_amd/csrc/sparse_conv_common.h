@@ -54,6 +54,65 @@ struct ConvArgs {
                                  // partial tile and conv_finish_small reads none for such (group, row) pairs (NULL: off)
 };
 
+// ---- model axis: K structurally identical programs as ONE launch sequence (cv_net_run_models_f32) ------------------------
+// A launch of a kernel's ModelArgs instantiation covers M models: the model m of a workgroup is a launch coordinate (blockIdx.y / ncb for
+// the convolutions, blockIdx.y for the stem, the finish kernels and the head) and model_sources() / model_sinks() below
+// swap model m's operands into the ConvArgs in front of the unchanged body.  What lives in the executor's arena / workspace is model 0's
+// pointer plus m x a byte stride (0: shared, e.g. the caller's input features); what has no constant stride - packed
+// weights, folded affine, acc_scale - comes from a device-resident row of cv_net_model_params, the caller's output tensors
+// from the kernel arguments.  Everything is uniform per workgroup.  A model's split count, mask groups, unit order and
+// summation order are those of its one-model launch: the axis only adds workgroups.
+struct ModelArgs {
+    const cv_net_model_params* params;      // [M] this op's row of the table, first model of the launch
+    long long in_stride, in2_stride, res_stride, out_stride, partial_stride;      // bytes between consecutive models
+    int ncb;                                // convolutions: column blocks of one model (gridDim.y = M * ncb)
+    int out_ext;                            // 1: the output is the caller's tensor of model m, ext_out[m]
+    float* ext_out[CV_MAX_CATEGORIES];
+};
+template <class T>
+__device__ __forceinline__ T* model_offset(T* p, long long bytes) {
+    return p ? reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + (uintptr_t)bytes) : p;
+}
+// what the unit loop of a convolution reads: the gathered sources and the packed weights
+__device__ __forceinline__ void model_sources(ConvArgs& a, const ModelArgs& ma, int m) {
+    const cv_net_model_params& p = ma.params[m];
+    a.in = model_offset(a.in, m * ma.in_stride);
+    a.in2 = model_offset(a.in2, m * ma.in2_stride);
+    a.wp6 = static_cast<const unsigned short*>(p.weight_x6);
+    a.wp6_2 = static_cast<const unsigned short*>(p.weight2_x6);
+}
+// what the epilogue reads and writes
+__device__ __forceinline__ void model_sinks(ConvArgs& a, const ModelArgs& ma, int m) {
+    const cv_net_model_params& p = ma.params[m];
+    a.res = model_offset(a.res, m * ma.res_stride);
+    a.out = ma.out_ext ? ma.ext_out[m] : model_offset(a.out, m * ma.out_stride);
+    a.partial = model_offset(a.partial, m * ma.partial_stride);
+    a.range_flag = a.range_flag ? a.range_flag + 16 * m : nullptr;        // one word per model, 16 ints apart
+    a.scale = p.scale;
+    a.shift = p.shift;
+    a.acc_scale = p.acc_scale;
+}
+// Entry of a kernel that takes the model axis as an optional trailing parameter (template <class... MA>, MA empty or one
+// ModelArgs).  Without it nothing happens and the column block is blockIdx.y: the one-model instantiation is the kernel it
+// was.  With it blockIdx.y = model * ncb + column block (model_enter) or the model itself (model_enter_y).
+// conv_hl / conv_hd swap the epilogue's operands in only when their unit loop is done (model_epilogue): the model's
+// pointers are computed values that would otherwise stay in scalar registers through the loop.
+__device__ __forceinline__ unsigned model_enter(ConvArgs&, unsigned by) { return by; }
+__device__ __forceinline__ unsigned model_enter(ConvArgs& a, unsigned by, const ModelArgs& ma) {
+    const unsigned m = by / (unsigned)ma.ncb;
+    model_sources(a, ma, (int)m);
+    return by - m * (unsigned)ma.ncb;
+}
+__device__ __forceinline__ void model_epilogue(ConvArgs&, unsigned) {}
+__device__ __forceinline__ void model_epilogue(ConvArgs& a, unsigned by_grid, const ModelArgs& ma) {
+    model_sinks(a, ma, (int)(by_grid / (unsigned)ma.ncb));
+}
+__device__ __forceinline__ void model_enter_y(ConvArgs&) {}
+__device__ __forceinline__ void model_enter_y(ConvArgs& a, const ModelArgs& ma) {
+    model_sources(a, ma, (int)blockIdx.y);
+    model_sinks(a, ma, (int)blockIdx.y);
+}
+
 // ---- hl format: activations stored as the fp16 pairs the matrix cores multiply --------------------------------------
 // A row of C channels (C % 32 == 0) keeps its 4*C bytes: 32-channel chunk q occupies bytes [128 q, 128 q + 128) =
 // 32 fp16 high pieces h = RNE16(x), then the 32 low pieces l = RNE16(x - h) (split2h below).  A convolution that reads
@@ -298,6 +357,7 @@ __device__ __forceinline__ void hd_read_frags(unsigned aa0, unsigned aa1, unsign
 }
 
 // ---- across the two translation units
-int launch_finish(const ConvArgs& a, hipStream_t st);                  // sparse_conv.hip: reduce the partial tiles + epilogue
+// sparse_conv.hip: reduce the partial tiles + epilogue (ma: over `models` models, blockIdx.y)
+int launch_finish(const ConvArgs& a, hipStream_t st, const ModelArgs* ma = nullptr, int models = 1);
 int nb_full(int cout);                                                 // sparse_conv.hip
 }  // namespace cvsc

@@ -215,18 +215,98 @@ def _call_growing(fn, name, d, r, dev, scratch_name, ws_hint):
 
 
 _sep_hosts = {}
+_model_tables = {}
+
+
+def model_params_table(mods, dev, pieces):
+    """Device table of cv_net_model_params [n_ops][K] for the model set ``mods`` (cv_net_run_models_f32: what differs between
+    the K programs without a constant stride - packed weights, folded affine, acc_scale).  Cached per model set next to
+    the programs it was filled from: a program that ``_program`` rebuilt (another parameter version) rebuilds the table.
+    Returns (programs, table tensor)."""
+    import numpy as np
+    progs = [m._program(dev, pieces) for m in mods]
+    key = (str(dev), pieces, tuple(id(m) for m in mods))
+    with _scene_lock:
+        hit = _model_tables.get(key)
+    if hit is not None and len(hit[0]) == len(progs) and all(a is b for a, b in zip(hit[0], progs)):
+        return progs, hit[1]
+    L = _lib.lib()
+    K, n_ops = len(progs), len(progs[0][0])
+    if any(len(p[0]) != n_ops for p in progs):
+        raise ValueError("model_params_table: the models' programs differ in length")
+    nbytes = L.cv_net_models_params_bytes(n_ops, K)
+    host = np.zeros(nbytes, np.uint8)
+    ops = (vp * K)(*[ctypes.cast(p[0], vp) for p in progs])
+    _lib.check(L.cv_net_models_params_fill(ops, n_ops, K, vp(host.ctypes.data), nbytes), "cv_net_models_params_fill")
+    table = torch.from_numpy(host).to(dev)
+    with _scene_lock:
+        _model_tables[key] = (progs, table)
+    return progs, table
+
+
+def forward_models(mods, x, models_per_pass=None, range_flags=None):
+    """The eval forward of K structurally identical models on ONE SparseTensor through cv_net_run_models_f32: passes of up
+    to ``models_per_pass`` models (None: all K), every launch covering the pass's models.  Returns the K outputs [N, C] -
+    bit for bit what ``m.program_forward(x)`` gives for each model.  ``range_flags``: optional zeroed int32 device tensor
+    [K, 16]; word [k, 0] is set when model k saw an input beyond the fp16 range (nothing is redone here)."""
+    L = _lib.lib()
+    dev = x.F.device
+    mods = list(mods)
+    K = len(mods)
+    G = K if not models_per_pass else min(int(models_per_pass), K)
+    pieces = 1 if ME.COMPUTE_DTYPE == "bf16" else mods[0].PIECES
+    progs, table = model_params_table(mods, dev, pieces)
+    m0 = mods[0]
+    plan = x.coordinate_manager.fused_fast(m0.conv0p1s1.kernel_size)
+    n = plan.counts
+    masked = [n[i] >= m0.masked_min_rows() for i in range(5)]
+    if any(m and plan.perm_ptrs[i] is None for i, m in enumerate(masked)):
+        raise ValueError("forward_models: the plan has no mask orders for a level that runs mask-sorted")
+    perm_ptrs = [p if masked[i] else None for i, p in enumerate(plan.perm_ptrs[:5])] + plan.perm_ptrs[5:]
+    map_ptrs = plan.map_ptrs
+    feats = x.F.contiguous()
+    ys = [torch.empty((n[0], m.final.out_channels), dtype=torch.float32, device=dev) for m in mods]
+    rows = (ctypes.c_int64 * 5)(*n)
+    c_bufs0 = progs[0][1]
+    arena = _lib.scratch(dev, "net_arena_models", L.cv_net_models_arena_bytes(c_bufs0, len(c_bufs0), rows, 5, G))
+    sorted_levels = (ctypes.c_int * 5)(*[p is not None for p in perm_ptrs[:5]])
+    ws_one = L.cv_sp_scene_conv_workspace_bytes(rows, sorted_levels, m0.MASK_GROUPS, max(max(m.PLANES) for m in mods))
+    ws = _lib.scratch(dev, "conv_ws_models", L.cv_net_models_workspace_bytes(ws_one, G))
+    ext_ld = (ctypes.c_int * 2)(feats.stride(0), ys[0].stride(0))
+    c_maps = (vp * len(map_ptrs))(*map_ptrs)
+    c_perms = (vp * len(perm_ptrs))(*perm_ptrs)
+    n_ops = len(progs[0][0])
+    entry = ctypes.sizeof(_lib.NetModelParams)
+    with torch.cuda.device(dev):
+        for k0 in range(0, K, G):
+            g = min(G, K - k0)
+            ops = (vp * g)(*[ctypes.cast(p[0], vp) for p in progs[k0:k0 + g]])
+            bufs = (vp * g)(*[ctypes.cast(p[1], vp) for p in progs[k0:k0 + g]])
+            ext = [(vp * 2)(feats.data_ptr(), y.data_ptr()) for y in ys[k0:k0 + g]]
+            c_ext = (vp * g)(*[ctypes.cast(e, vp) for e in ext])
+            flag = vp(range_flags.data_ptr() + 64 * k0) if range_flags is not None else None
+            _lib.check(L.cv_net_run_models_f32(ops, bufs, n_ops, len(c_bufs0), g, rows, 5, vp(arena.data_ptr()), arena.numel(),
+                                               c_ext, ext_ld, c_maps, len(map_ptrs), c_perms, len(perm_ptrs), vp(ws.data_ptr()),
+                                               ws.numel(), flag, vp(table.data_ptr() + entry * k0), K,
+                                               vp(torch.cuda.current_stream(dev).cuda_stream)), "cv_net_run_models_f32")
+    return ys
 
 
 def detect_scene_separate_c(models, hv, coords4, feats, res, predictions=None, policy=None, keep=None, events=None,
-                            log_scale=True, overlap_threshold=0.3, max_candidates=512, scan_points=None, **decode_kw):
+                            log_scale=True, overlap_threshold=0.3, max_candidates=512, scan_points=None,
+                            models_per_pass=None, **decode_kw):
     """detect_scene_separate through ONE C call (cv_detect_scene_separate_f32: the coordinate plan once, the K models'
     programs, K heads, ONE vote and ONE decode over the category axis - one host wait for the decode - and NMS per category;
     the GIL released for the whole call).  Returns what detect_scene_separate returns, [(category, box[8,3], score)], in the
     same order and the same bits.  ``predictions`` = (xyz [K,N,3], scale [K,N,3], prob [K,N]) fed to vote + decode instead of
     the networks'.  A scene with a model's input beyond the fp16 range, or a category whose walk fills ``max_candidates``,
     is redone by the call-by-call path.  ``keep`` receives the per-model outputs (``y``), the head outputs (``net_pred``),
-    the [K,...] grids, the per-category raw decode (``raw``), dims and corner.  ``events``: five recorded torch.cuda.Event
-    re-recorded at the stage boundaries.  ``policy``: ScenePolicy of this call."""
+    the [K,...] grids, the per-category raw decode (``raw``), dims and corner, and - also for a scene that is redone - the call's
+    ``range_flag`` bits and ``needed_ws_bytes``.  ``events``: five recorded torch.cuda.Event
+    re-recorded at the stage boundaries.  ``policy``: ScenePolicy of this call.  ``models_per_pass`` = G >= 1: the K networks
+    run as passes of up to G models over a model axis (cv_net_run_models_f32: every convolution launch covers G models) and
+    the K heads as one launch - the same bits with about K times fewer network launches, G arenas and convolution workspaces
+    of scratch; None or 0: one network after another."""
     import numpy as np
     decode_kw.setdefault("separate_variant", True)
     decode_kw.setdefault("err_thresh", float(np.float32(0.3)))
@@ -241,7 +321,13 @@ def detect_scene_separate_c(models, hv, coords4, feats, res, predictions=None, p
     if scan_points is None:
         scan_points = (coords4[:, 1:].to(dev) * res).float().contiguous()
     pieces = 1 if ME.COMPUTE_DTYPE == "bf16" else mods[0].PIECES
-    progs = [m._program(dev, pieces) for m in mods]
+    G = int(models_per_pass or 0)
+    if G < 0:
+        raise ValueError("detect_scene_separate_c: models_per_pass must be >= 0 (got %d)" % G)
+    if G > 0:
+        progs, table = model_params_table(mods, dev, pieces)
+    else:
+        progs, table = [m._program(dev, pieces) for m in mods], None
     coords4 = coords4.to(device=dev, dtype=torch.int32).contiguous()
     feats = feats.contiguous()
     ys = [torch.empty((n, m.final.out_channels), dtype=torch.float32, device=dev) for m in mods]
@@ -258,6 +344,8 @@ def detect_scene_separate_c(models, hv, coords4, feats, res, predictions=None, p
     d = _lib.SceneSeparateDesc()
     _fill_scene_desc(d, mods[0], hv, coords4, feats, scan_points, res, policy, pieces, max(max(m.PLANES) for m in mods), log_scale)
     d.num_models = K
+    if G > 0:
+        d.models_per_pass, d.d_model_params = G, vp(table.data_ptr())
     ops = (vp * K)(*[ctypes.cast(p[0], vp) for p in progs])
     n_ops = (ctypes.c_int * K)(*[len(p[0]) for p in progs])
     bufs = (vp * K)(*[ctypes.cast(p[1], vp) for p in progs])
@@ -279,6 +367,8 @@ def detect_scene_separate_c(models, hv, coords4, feats, res, predictions=None, p
     ws = _call_growing(L.cv_detect_scene_separate_f32, "cv_detect_scene_separate_f32", d, r, dev, "scene_call_separate",
                        host["ws_hint"])
     host["ws_hint"] = max(host["ws_hint"], int(r.needed_ws_bytes))
+    if keep is not None:
+        keep.update(range_flag=int(r.range_flag), needed_ws_bytes=int(r.needed_ws_bytes))
     if r.range_flag or any(r.truncated[k] for k in range(K)):
         # rare: a convolution input beyond the fp16 range, or more candidate cells than the result arrays hold
         kw = dict(decode_kw, max_candidates=M)

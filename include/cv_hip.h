@@ -38,8 +38,10 @@ extern "C" {
  *    cv_sp_copy_unless_flag, cv_sp_pack_weights_h2_batch_f32; the neighbour windows of round 5 (conv_win: exact, measured slower
  *    than the mask-sorted kernels at every level, LABNOTES round 5) are gone - cv_sp_build_windows, cv_conv_desc.win,
  *    cv_scene_maps.win, the win_levels arguments and cv_net_win_levels.
- * 4: cv_sp_scene_plan_layout, cv_sp_scene_plan_slots, cv_sp_scene_conv_workspace_bytes (additive: no struct or signature moved). */
-#define CV_ABI_VERSION 4
+ * 4: cv_sp_scene_plan_layout, cv_sp_scene_plan_slots, cv_sp_scene_conv_workspace_bytes (additive: no struct or signature moved).
+ * 5: the model axis - cv_net_run_models_f32 with its size / table helpers, cv_head_separate_models_f32,
+ *    cv_scene_separate_desc.models_per_pass / d_model_params (appended: a zero-initialised descriptor runs as before). */
+#define CV_ABI_VERSION 5
 int cv_abi_version(void);
 const char* cv_last_error(void);
 
@@ -486,6 +488,42 @@ int cv_net_run_f32(const cv_net_op* ops, int n_ops, const cv_net_buf* bufs, int 
                    const int32_t* const* maps, int n_maps, const int32_t* const* perms, int n_perms,
                    void* d_ws, size_t ws_bytes, int32_t* range_flag, void* stream);   /* range_flag: cv_conv_desc.range_flag of every fp16-pair op, or NULL */
 
+/* K structurally identical programs (the per-category models of separate mode: same ops, buffers, maps and orders; only
+ * the weight / scale / shift pointers, acc_scale and the output tensor differ) as ONE launch sequence: every op is issued
+ * once, the model is a launch coordinate of the convolution, finish and stem kernels.  Per model the split counts, mask
+ * groups, unit order and summation order are those of cv_net_run_f32: model m's output is bit for bit what cv_net_run_f32
+ * gives for program m.  fp16-pair programs on hl buffers only (weight_pieces == 2); anything else is CV_EINVAL.
+ *   d_params   device table of cv_net_model_params, what has no constant stride between models: op k's parameters of the K
+ *              models at d_params[k * params_ld + m] (params_ld >= K: a pass over models m0 ... of a larger set hands over
+ *              table + m0 and the set's size).  Built once per model set: cv_net_models_params_fill writes the host image
+ *              [n_ops][K] (cv_net_models_params_bytes), the caller copies it to the device.
+ *   d_arena    K arenas, cv_net_models_arena_bytes (= K x cv_net_arena_bytes); model m at m x cv_net_arena_bytes
+ *   d_ws       K convolution workspaces, cv_net_models_workspace_bytes of ONE model's size (what cv_net_run_f32 takes):
+ *              model m at m x that size rounded up to 256 bytes
+ *   ext_ptr    [K] pointer tables as cv_net_run_f32's (ext_ld is shared).  A buffer the program only reads (the input
+ *              features) must be the same tensor for every model; the one it writes is model m's own.
+ *   range_flag K words 16 ints apart (model m: range_flag + 16 m), or NULL
+ * The programs are compared on the host first: n_ops, n_bufs and every integer field of every op and buffer must agree and
+ * a pointer may be NULL in all models or in none, otherwise CV_EINVAL names the first differing op and model.
+ * 1 <= K <= CV_MAX_CATEGORIES.  Not available with models: cv_conv_desc.split_tickets, the CV_XCD_TILES experiment. */
+typedef struct cv_net_model_params {
+    const void* weight_x6;     /* cv_net_op.weight_x6 of the model */
+    const void* weight2_x6;
+    const float* scale;
+    const float* shift;
+    float acc_scale;
+    int reserved[3];
+} cv_net_model_params;
+size_t cv_net_models_params_bytes(int n_ops, int K);
+int cv_net_models_params_fill(const cv_net_op* const* ops, int n_ops, int K, void* h_params, size_t params_bytes);
+size_t cv_net_models_arena_bytes(const cv_net_buf* bufs, int n_bufs, const long long* level_rows, int n_levels, int K);
+size_t cv_net_models_workspace_bytes(size_t one_model_bytes, int K);
+int cv_net_run_models_f32(const cv_net_op* const* ops, const cv_net_buf* const* bufs, int n_ops, int n_bufs, int K,
+                          const long long* level_rows, int n_levels, void* d_arena, size_t arena_bytes,
+                          const void* const* const* ext_ptr, const int* ext_ld, const int32_t* const* maps, int n_maps,
+                          const int32_t* const* perms, int n_perms, void* d_ws, size_t ws_bytes, int32_t* range_flag,
+                          const void* d_params, int params_ld, void* stream);
+
 /* d_keys[n] (int64) = bit mask of the valid neighbours among offsets [j_begin, j_end) of every row of a
  * kernel map; argsort of it is a row_perm for cv_conv_desc.  Asynchronous. */
 int cv_sp_mask_keys(const int32_t* d_nbr, long long n, int K, int j_begin, int j_end, long long* d_keys,
@@ -584,6 +622,10 @@ int cv_head_joint_f32(const float* d_feats, long long n, int ld, int nclasses, i
 /* 8-channel head of a per-category model (eval_separate.py:170-181): xyz, exp(scale), softmax(obj)[1]. */
 int cv_head_separate_f32(const float* d_feats, long long n, int ld, int log_scale, float* d_xyz, float* d_scale,
                          float* d_prob, void* stream);
+/* The same head for K models in one launch (the model is blockIdx.y): d_feats[k] is model k's [n][ld] output (host array of
+ * K device pointers), the results are [K][n][3], [K][n][3], [K][n] - what K calls of cv_head_separate_f32 write. */
+int cv_head_separate_models_f32(const float* const* d_feats, int K, long long n, int ld, int log_scale, float* d_xyz,
+                                float* d_scale, float* d_prob, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * One call per scene: eval_joint.py:163-280 (network -> head split -> vote -> decode -> per-class NMS) behind ONE
@@ -659,7 +701,7 @@ int cv_detect_scene_f32(const cv_scene_desc* desc, cv_scene_result* result, void
 /* ------------------------------------------------------------------------ *
  * One call per SEPARATE-mode scene: eval_separate.py:162-264 (K per-category 8-channel models on one scan) behind one entry
  * point: the coordinate plan once, K network programs (cv_net_run_f32, one after another on the stream, sharing the plan and
- * one arena), K heads (cv_head_separate_f32), ONE vote over the category axis (cv_hv_forward_cat_f32), ONE decode over it
+ * one arena; or batched over a model axis, see models_per_pass), K heads (cv_head_separate_f32), ONE vote over the category axis (cv_hv_forward_cat_f32), ONE decode over it
  * (cv_decode_cat_f32: one host wait) and NMS per category on the host.  Category k is bit for bit the call-by-call path of
  * model k.  1 <= num_models <= CV_MAX_CATEGORIES; every field is validated before the first device call.
  * ------------------------------------------------------------------------ */
@@ -691,6 +733,12 @@ typedef struct cv_scene_separate_desc {
     int32_t* h_det_cat; int32_t* h_det_box;    /* [K * max_candidates]: detection j = box h_det_box[j] of category h_det_cat[j] */
     void* events[5];                           /* optional: scene start, behind the networks, the heads, the vote, the decode */
     int conv_split_target, vote_part_records;  /* launch sizing of this call (0 = thread / process-wide), as cv_scene_desc */
+    /* 0: the K programs one after another on one arena (cv_net_run_f32 K times, K head launches).  G >= 1: passes of up to G
+     * models through cv_net_run_models_f32 (the last pass may be shorter, G > K means K) and ONE head launch
+     * (cv_head_separate_models_f32): same bits, about K x fewer network launches.  G arenas and G convolution workspaces
+     * live at once - result.needed_ws_bytes says how much.  Needs d_model_params.  Negative: CV_EINVAL. */
+    int models_per_pass;
+    const void* d_model_params;                /* device table [n_ops][K] (cv_net_models_params_fill) of the K programs, or NULL */
 } cv_scene_separate_desc;
 typedef struct cv_scene_separate_result {
     int n_cand[CV_MAX_CATEGORIES], n_boxes[CV_MAX_CATEGORIES], truncated[CV_MAX_CATEGORIES];

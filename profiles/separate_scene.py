@@ -3,10 +3,13 @@
 against nine single calls (hv_cuda.forward + decode.decode_boxes per category, what detect_scene_separate does).
 
     python profiles/separate_scene.py [--sizes 80000 300000] [--repeats 3] [--scenes 20] [--out FILE]
+                                      [--models-per-pass 3 9] [--whole-only]
 
 and whole scenes (nine 8-channel networks on one coordinate plan, heads, vote, decode, NMS): the call-by-call path of
 detect_scene_separate against ONE pipeline.detect_scene_separate_c call (cv_detect_scene_separate_f32), both voting with
-the teacher below ("whole" in the output).  Launch counts per scene come from a run of its own under
+the teacher below ("whole" in the output), and against the same call with the nine networks batched over a model axis
+(--models-per-pass G ...: "whole_models_G", cv_net_run_models_f32 in passes of G models; with its scratch size,
+needed_ws_bytes).  --whole-only measures the one-call paths alone.  Launch counts per scene come from a run of its own under
 rocprofv3 --kernel-trace --stats (--scenes 2 --repeats 1) and counting the dispatches per kernel name.
 
 Predictions are a per-category teacher: category c's points keep the synthetic teacher's probability, every other point
@@ -74,6 +77,17 @@ def whole_one_call(models, hv, c4, feats, pts, X, S, P, ev):
     return dets
 
 
+def whole_models(G):
+    def run(models, hv, c4, feats, pts, X, S, P, ev, keep=None):
+        ev[0].record()
+        dets = pipeline.detect_scene_separate_c(models, hv, c4, feats, RES, predictions=(X, S, P), scan_points=pts,
+                                                models_per_pass=G, keep=keep, **SEPARATE)
+        ev[1].record()
+        ev[2].record()
+        return dets
+    return run
+
+
 def teacher(n):
     sc = scene_of(n)
     xyz, scale, prob, cls = synth_predictions(sc)
@@ -127,29 +141,49 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--scenes", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--models-per-pass", type=int, nargs="*", default=[], help="also time the one-call path with the networks batched")
+    ap.add_argument("--whole-only", action="store_true", help="only the whole-scene one-call paths")
     a = ap.parse_args()
     out = dict(categories=K, num_rots=R, res=RES, sizes={})
     for n in a.sizes:
         args = teacher(n)
-        a_raw, b_raw = single(*args, [torch.cuda.Event() for _ in range(3)]), batched(*args, [torch.cuda.Event() for _ in range(3)])
-        same = all(list(x["cand_idx"]) == list(y["cand_idx"]) and np.array_equal(x["boxes"], y["boxes"]) for x, y in zip(a_raw, b_raw))
-        rows = dict(single=[], batched=[])
-        for _ in range(a.repeats):
-            rows["single"].append(measure(single, args, a.scenes))
-            rows["batched"].append(measure(batched, args, a.scenes))
-        wargs = whole_inputs(n, args[0]) + args
-        da, db = whole_by_calls(*wargs, [torch.cuda.Event() for _ in range(3)]), whole_one_call(*wargs, [torch.cuda.Event() for _ in range(3)])
-        rows["whole_by_calls"], rows["whole_one_call"] = [], []
-        for _ in range(a.repeats):
-            rows["whole_by_calls"].append(measure(whole_by_calls, wargs, a.scenes))
-            rows["whole_one_call"].append(measure(whole_one_call, wargs, a.scenes))
-        summ = {k: {m: [round(r[m], 4) for r in v] for m in ("scenes_per_s", "vote_ms", "decode_ms")} for k, v in rows.items()}
-        for k in ("whole_by_calls", "whole_one_call"):
-            summ[k] = {"scenes_per_s": summ[k]["scenes_per_s"], "scene_ms": summ[k]["vote_ms"]}
-        summ["whole_same_detections"] = len(da) == len(db) and all(
+        events = lambda: [torch.cuda.Event() for _ in range(3)]
+        same_dets = lambda da, db: len(da) == len(db) and all(
             c0 == c1 and s0 == s1 and np.array_equal(b0, b1) for (c0, b0, s0), (c1, b1, s1) in zip(da, db))
-        summ["same_results"] = bool(same)
-        summ["candidates"] = [len(r["cand_idx"]) for r in b_raw]
+        rows = {}
+        if not a.whole_only:
+            a_raw, b_raw = single(*args, events()), batched(*args, events())
+            same = all(list(x["cand_idx"]) == list(y["cand_idx"]) and np.array_equal(x["boxes"], y["boxes"]) for x, y in zip(a_raw, b_raw))
+            rows.update(single=[], batched=[])
+            for _ in range(a.repeats):
+                rows["single"].append(measure(single, args, a.scenes))
+                rows["batched"].append(measure(batched, args, a.scenes))
+        wargs = whole_inputs(n, args[0]) + args
+        whole = {"whole_one_call": whole_one_call}
+        if not a.whole_only:
+            whole = {"whole_by_calls": whole_by_calls, "whole_one_call": whole_one_call}
+        whole.update({"whole_models_%d" % G: whole_models(G) for G in a.models_per_pass})
+        first, needed = {}, {}
+        for k, fn in whole.items():                  # warm-up (grows the scratch) and the results to compare
+            if k.startswith("whole_models_"):
+                keep = {}
+                first[k] = fn(*wargs, events(), keep=keep)
+                needed[k] = keep["needed_ws_bytes"]
+            else:
+                first[k] = fn(*wargs, events())
+            rows[k] = []
+        for _ in range(a.repeats):                   # the paths alternate inside a repeat
+            for k, fn in whole.items():
+                rows[k].append(measure(fn, wargs, a.scenes))
+        summ = {k: {m: [round(r[m], 4) for r in v] for m in ("scenes_per_s", "vote_ms", "decode_ms")} for k, v in rows.items()}
+        for k in whole:
+            summ[k] = {"scenes_per_s": summ[k]["scenes_per_s"], "scene_ms": summ[k]["vote_ms"]}
+            if k in needed:
+                summ[k]["needed_ws_bytes"] = needed[k]
+        summ["whole_same_detections"] = all(same_dets(first["whole_one_call"], d) for d in first.values())
+        if not a.whole_only:
+            summ["same_results"] = bool(same)
+            summ["candidates"] = [len(r["cand_idx"]) for r in b_raw]
         out["sizes"][str(n)] = summ
         print(json.dumps({str(n): summ}), flush=True)
     print(json.dumps(out))

@@ -34,7 +34,7 @@ def teacher_predictions(scene, categories, device):
     return t(np.stack([xyz] * len(categories))), t(np.stack([scale] * len(categories))), t(P)
 
 
-def evaluate(models, dataset, res=0.03, teacher=False, device="cuda"):
+def evaluate(models, dataset, res=0.03, teacher=False, device="cuda", models_per_pass=None):
     hv = HoughVoting(res)
     pred_map_cls, gt_map_cls = {}, {}
     loader = torch.utils.data.DataLoader(dataset, collate_fn=collate_fn, batch_size=1, shuffle=False)
@@ -44,7 +44,8 @@ def evaluate(models, dataset, res=0.03, teacher=False, device="cuda"):
         feats[:, -3:] = feats[:, -3:] * 2.0 - 1.0                             # eval_separate.py: colour columns only
         coords = coords.to(device)
         pred = teacher_predictions(dataset.scene(index), list(models), device) if teacher else None
-        pred_map_cls[id_scan] = pipeline.detect_scene_separate_c(models, hv, coords, feats, res, predictions=pred)
+        pred_map_cls[id_scan] = pipeline.detect_scene_separate_c(models, hv, coords, feats, res, predictions=pred,
+                                                                 models_per_pass=models_per_pass)
         gt_map_cls[id_scan] = [(c, calc_map.gt_box(*p)) for c, p in dataset.gt(index)]
     return {thr: calc_map.compute_map(pred_map_cls, gt_map_cls, thr) for thr in (0.25, 0.5)}
 
@@ -57,6 +58,9 @@ def main():
     ap.add_argument("--categories", type=int, nargs="+", default=list(range(9)))
     ap.add_argument("--teacher", action="store_true")
     ap.add_argument("--config", default=None, help="the reference's config.yaml: evaluate on real ScanNet/Scan2CAD files")
+    ap.add_argument("--models-per-pass", type=int, default=0,
+                    help="G >= 1: the networks run batched over a model axis, G per pass (same bits, fewer launches, G arenas of "
+                         "scratch); 0: one network after another")
     a = ap.parse_args()
     cfg = load_config(a.config, category="all") if a.config else None
     models = {}
@@ -66,9 +70,10 @@ def main():
             load_reference_checkpoint(m, os.path.join(a.weights_dir, "%s.pth" % c))
         models[c] = m.cuda().eval()
     if cfg:
-        res = evaluate(models, ScanNetXYZProbMultiDataset(cfg, training=False, augment=False), res=cfg.scannet_res)
+        res = evaluate(models, ScanNetXYZProbMultiDataset(cfg, training=False, augment=False), res=cfg.scannet_res,
+                       models_per_pass=a.models_per_pass)
     else:
-        res = evaluate(models, SyntheticScanDataset(a.scenes, a.points, seed0=100), teacher=a.teacher)
+        res = evaluate(models, SyntheticScanDataset(a.scenes, a.points, seed0=100), teacher=a.teacher, models_per_pass=a.models_per_pass)
     for thr, r in res.items():
         print("IoU %.2f: mAP %.4f  AR %.4f" % (thr, r["mAP"], r["AR"]))
 
