@@ -39,6 +39,7 @@ def _sources():
         "hv_decode.hip": STRICT + env("CV_DEC_DEFS"),    # greedy-walk experiments (-DDEC_BLOCKED=0)
         "sparse_coords.hip": [],
         "sparse_conv.hip": env("CV_SC_DEFS"),            # kernel experiments (-DCV_WP_NPRE=27)
+        "sparse_train.hip": [],                          # the training side: reads none of the CV_SC_DEFS switches
         "net_exec.cpp": [],
         "scene_exec.cpp": [],
     }

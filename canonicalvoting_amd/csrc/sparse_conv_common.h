@@ -1,6 +1,6 @@
-// Launch arguments, the hl format and the fused epilogue of the convolution kernels in sparse_conv.hip.  (Rounds 1-3 kept
-// parity-tested experiments - a wave-independent flavour, a pair-compacted tile flavour, an instrumented twin - in a
-// second translation unit over this header; they were removed in round 4, git history and LABNOTES.md hold them.)
+// What sparse_conv.hip (the forward kernels and everything else the eval path launches) and sparse_train.hip (the training
+// side) share: the launch arguments (ConvArgs, the model axis), the hl format, the fused epilogue, the bf16 / fp16 piece
+// splits, the LDS-DMA helpers of conv_hd and two host helpers.
 #pragma once
 #include "cv_common.h"
 
@@ -31,13 +31,9 @@ struct ConvArgs {
     int j_begin, j_end;    // kernel offsets handled by this launch
     const float* acc_in;   // optional [n_out][acc_ld] added to the accumulator before the epilogue
     int acc_ld;
-    const int* plan_ent;   // tile flavour: compacted (input row, tile row) lists per (tile, offset), see tile_plan
-    const int* plan_cnt;
-    const float4* wp;      // tile flavour: weights in MFMA operand order, see pack_weights
     int wide;              // epilogue operands are 16-byte aligned with leading dimensions % 4 == 0: float4 row stores
     const int* nbr_perm;   // mask-sorted groups: [splits][n_out][nbr_perm_w] kernel map rows in processing order
     int nbr_perm_w;
-    int reserved0;         // (was the switch of round 1's instrumented kernel)
     const unsigned short* wp6;   // weights split into bf16 pieces, see pack_weights_x6
     const float* in2;            // second source on the output rows (out += in2 @ W2), or NULL
     int in2_ld, cin2;
@@ -46,7 +42,6 @@ struct ConvArgs {
     float acc_scale;             // fp16 pairs: the packed weights carry a power-of-two factor; accumulators *= acc_scale
     int* range_flag;             // fp16 pairs: set to 1 when a staged input magnitude does not fit fp16
     int in_hl, out_hl, res_hl;   // 1: the operand is in the hl format (fp16 pairs in place, see below) instead of fp32
-    int xcd_tiles;               // conv_rows_wp / conv_hl: XCD-aware tile numbering (xcd_tile)
     int* tickets;                // conv_hl split-K: arrival counters per output tile (zero; the last arriver reduces, see there)
     const float* acc_scale_dev;  // optional device scalar multiplied into acc_scale (the input gradient's hl operand carries a
                                  // per-layer power of two chosen on the device)
@@ -165,6 +160,19 @@ __device__ __forceinline__ float4 partial_load4(const float4* p) {
     return make_float4(t[0], t[1], t[2], t[3]);
 }
 
+// the fused epilogue on one word (fp32 operands only: the host refuses the hl format without a.wide).  sc / sh: the column's
+// affine, loaded once by a caller that walks the rows of one column (its stores may alias them: the compiler hoists nothing)
+__device__ __forceinline__ void epilogue_apply1(const ConvArgs& a, long long row, int col, float v, float sc, float sh) {
+    if (a.acc_in) v += a.acc_in[row * a.acc_ld + col];
+    v = v * sc + sh;
+    if (a.res) v += a.res[row * a.res_ld + col];
+    if (a.relu) v = fmaxf(v, 0.f);
+    a.out[row * a.out_ld + col] = v;
+}
+__device__ __forceinline__ void epilogue_apply1(const ConvArgs& a, long long row, int col, float v) {
+    epilogue_apply1(a, row, col, v, a.scale ? a.scale[col] : 1.f, a.shift ? a.shift[col] : 0.f);
+}
+
 __device__ __forceinline__ void epilogue_store(const ConvArgs& a, const f32x16& acc, const int* rows,
                                                int col, int lane) {
     if (col >= a.cout) return;
@@ -182,13 +190,7 @@ __device__ __forceinline__ void epilogue_store(const ConvArgs& a, const f32x16& 
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int row = rows[(r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)];
-        if (row < 0) continue;
-        float v = acc[r];
-        if (a.acc_in) v += a.acc_in[(long long)row * a.acc_ld + col];
-        v = v * sc + sh;
-        if (a.res) v += a.res[(long long)row * a.res_ld + col];
-        if (a.relu) v = fmaxf(v, 0.f);
-        a.out[(long long)row * a.out_ld + col] = v;
+        if (row >= 0) epilogue_apply1(a, row, col, acc[r], sc, sh);
     }
 }
 
@@ -294,7 +296,6 @@ __device__ __forceinline__ void split2h(float x0, float x1, unsigned& h, unsigne
 
 __device__ __forceinline__ void hl_split2(float x0, float x1, unsigned& h, unsigned& l) { split2h(x0, x1, h, l); }
 
-
 // ---- shared by the LDS-DMA kernels (conv_hd in sparse_conv.hip) ------------------------------------------------------------
 template <int... I, class F>
 __device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
@@ -356,8 +357,7 @@ __device__ __forceinline__ void hd_read_frags(unsigned aa0, unsigned aa1, unsign
     }
 }
 
-// ---- across the two translation units
-// sparse_conv.hip: reduce the partial tiles + epilogue (ma: over `models` models, blockIdx.y)
-int launch_finish(const ConvArgs& a, hipStream_t st, const ModelArgs* ma = nullptr, int models = 1);
-int nb_full(int cout);                                                 // sparse_conv.hip
+// ---- host helpers of both translation units.  nb_full: 32-column blocks that cover cout in one workgroup (at most 4)
+inline int nb_full(int cout) { return cout <= 32 ? 1 : cout <= 64 ? 2 : cout <= 96 ? 3 : 4; }
+__host__ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 }  // namespace cvsc

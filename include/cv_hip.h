@@ -505,7 +505,7 @@ int cv_net_run_f32(const cv_net_op* ops, int n_ops, const cv_net_buf* bufs, int 
  *   range_flag K words 16 ints apart (model m: range_flag + 16 m), or NULL
  * The programs are compared on the host first: n_ops, n_bufs and every integer field of every op and buffer must agree and
  * a pointer may be NULL in all models or in none, otherwise CV_EINVAL names the first differing op and model.
- * 1 <= K <= CV_MAX_CATEGORIES.  Not available with models: cv_conv_desc.split_tickets, the CV_XCD_TILES experiment. */
+ * 1 <= K <= CV_MAX_CATEGORIES.  Not available with models: cv_conv_desc.split_tickets. */
 typedef struct cv_net_model_params {
     const void* weight_x6;     /* cv_net_op.weight_x6 of the model */
     const void* weight2_x6;

@@ -355,26 +355,33 @@ def test_perm_groups(groups):
                 perm_groups=groups, what="groups=%d n=%d" % (groups, n))
 
 
-def test_offset_halves_chained_through_acc_in():
-    """offsets [0, 13) into an fp32 buffer, [13, 27) on top of it through acc_in with the epilogue"""
+def acc_in_halves(pieces, flavour):
+    """offsets [0, 13) into an fp32 buffer, [13, 27) on top of it through acc_in with the epilogue, both checked; returns
+    the sentinel-padded buffer of the second launch"""
     n, cin, cout = 700, 64, 96
     nbr, ref_map, _, _ = maps(n, "mixed", 3)
     x, w, scale, shift, res = operands(n, n, cin, cout, 27)
+    path = path_of(cin, cout, pieces)
+    y1, m1, wa1 = oracle(n, "mixed", 3, cin, cout, False, 0, 13)
+    y2, m2, wa2 = oracle(n, "mixed", 3, cin, cout, False, 13, 27)
+    b1 = so.conv_bound(m1, wa1, path, so.conv_units(13, cin))
+    b2 = so.conv_bound(m2, wa2, path, so.conv_units(14, cin))
+    part = ME.conv_forward(cuda_t(x), cuda_t(w), nbr, n, flavour=flavour, j_begin=0, j_end=13, pieces=pieces,
+                           cache_weights=False)
+    check(part.cpu().numpy().astype(np.float64), y1, b1, "first half")
+    obuf = out_buffer(n, cout, False)
+    ME.conv_forward(cuda_t(x), cuda_t(w), nbr, n, flavour=flavour, j_begin=13, j_end=27, acc_in=part,
+                    scale=cuda_t(scale), shift=cuda_t(shift), residual=cuda_t(res), relu=True, pieces=pieces,
+                    out=obuf[:n, PAD:PAD + cout], cache_weights=False)
+    z, bz = so.epilogue64(y2, b2, acc_in=y1, b_acc=b1, scale=scale, shift=shift, res=res, relu=True)
+    check(read_out(obuf, n, cout, False), z, bz, "second half on acc_in, pieces=%d flavour=%d" % (pieces, flavour))
+    return obuf
+
+
+def test_offset_halves_chained_through_acc_in():
+    """offsets [0, 13) into an fp32 buffer, [13, 27) on top of it through acc_in with the epilogue"""
     for pieces, flavour in ((3, 1), (2, 0), (3, 0)):
-        path = path_of(cin, cout, pieces)
-        y1, m1, wa1 = oracle(n, "mixed", 3, cin, cout, False, 0, 13)
-        y2, m2, wa2 = oracle(n, "mixed", 3, cin, cout, False, 13, 27)
-        b1 = so.conv_bound(m1, wa1, path, so.conv_units(13, cin))
-        b2 = so.conv_bound(m2, wa2, path, so.conv_units(14, cin))
-        part = ME.conv_forward(cuda_t(x), cuda_t(w), nbr, n, flavour=flavour, j_begin=0, j_end=13, pieces=pieces,
-                               cache_weights=False)
-        check(part.cpu().numpy().astype(np.float64), y1, b1, "first half")
-        obuf = out_buffer(n, cout, False)
-        ME.conv_forward(cuda_t(x), cuda_t(w), nbr, n, flavour=flavour, j_begin=13, j_end=27, acc_in=part,
-                        scale=cuda_t(scale), shift=cuda_t(shift), residual=cuda_t(res), relu=True, pieces=pieces,
-                        out=obuf[:n, PAD:PAD + cout], cache_weights=False)
-        z, bz = so.epilogue64(y2, b2, acc_in=y1, b_acc=b1, scale=scale, shift=shift, res=res, relu=True)
-        check(read_out(obuf, n, cout, False), z, bz, "second half on acc_in, pieces=%d flavour=%d" % (pieces, flavour))
+        acc_in_halves(pieces, flavour)
 
 
 @pytest.mark.parametrize("n,cout", [(700, 64), (3000, 96), (257, 256)])
@@ -490,10 +497,9 @@ def test_hl_with_word_epilogue_is_refused(case, k):
     assert refused, "descriptor accepted"
 
 
-@pytest.mark.parametrize("k", [3, 1])
-def test_word_by_word_epilogue_fp32(k):
-    """fp32 operands that are not 16-byte aligned (scale, acc_in slices) and leading dimensions % 4 != 0 (residual,
-    output): the word-by-word epilogues (epilogue_store, conv_finish's scalar branch) with every operand"""
+def word_epilogue_fp32(k, pieces):
+    """one launch with fp32 operands that are not 16-byte aligned (scale, acc_in slices) and leading dimensions % 4 != 0
+    (residual, output), checked; returns the sentinel-padded buffer"""
     n, cin, cout = 300, 32, 64
     nbr, ref_map, _, _ = maps(n, "box", k)
     K = 1 if k == 1 else 27
@@ -507,16 +513,24 @@ def test_word_by_word_epilogue_fp32(k):
     rbuf = torch.zeros((n, cout + 1), device=DEV)
     rbuf[:, :cout] = cuda_t(res)
     obuf = torch.full((n + PAD_ROWS, cout + 2 * PAD + 1), SENT, device=DEV)
+    ME.conv_forward(cuda_t(x), cuda_t(w), nbr, n, scale=sc_buf[1:1 + cout], shift=cuda_t(shift),
+                    acc_in=acc_buf[:, 1:1 + cout], residual=rbuf[:, :cout], relu=True, pieces=pieces,
+                    out=obuf[:n, PAD:PAD + cout], cache_weights=False)
+    b = so.conv_bound(mag, wabs, path_of(cin, cout, pieces), so.conv_units(K, cin))
+    z, bz = so.epilogue64(y64, b, acc_in=acc.astype(np.float32).astype(np.float64), b_acc=0.0, scale=scale,
+                          shift=shift, res=res, relu=True)
+    full = obuf.cpu().numpy().astype(np.float64)
+    assert (full[:, :PAD] == SENT).all() and (full[:, PAD + cout:] == SENT).all() and (full[n:] == SENT).all()
+    check(full[:n, PAD:PAD + cout], z, bz, "word epilogue k=%d pieces=%d" % (k, pieces))
+    return obuf
+
+
+@pytest.mark.parametrize("k", [3, 1])
+def test_word_by_word_epilogue_fp32(k):
+    """fp32 operands that are not 16-byte aligned (scale, acc_in slices) and leading dimensions % 4 != 0 (residual,
+    output): the word-by-word epilogues (epilogue_store, conv_finish's scalar branch) with every operand"""
     for pieces in (3, 2):
-        ME.conv_forward(cuda_t(x), cuda_t(w), nbr, n, scale=sc_buf[1:1 + cout], shift=cuda_t(shift),
-                        acc_in=acc_buf[:, 1:1 + cout], residual=rbuf[:, :cout], relu=True, pieces=pieces,
-                        out=obuf[:n, PAD:PAD + cout], cache_weights=False)
-        b = so.conv_bound(mag, wabs, path_of(cin, cout, pieces), so.conv_units(K, cin))
-        z, bz = so.epilogue64(y64, b, acc_in=acc.astype(np.float32).astype(np.float64), b_acc=0.0, scale=scale,
-                              shift=shift, res=res, relu=True)
-        full = obuf.cpu().numpy().astype(np.float64)
-        assert (full[:, :PAD] == SENT).all() and (full[:, PAD + cout:] == SENT).all() and (full[n:] == SENT).all()
-        check(full[:n, PAD:PAD + cout], z, bz, "word epilogue k=%d pieces=%d" % (k, pieces))
+        word_epilogue_fp32(k, pieces)
 
 
 # ---- 3. backward ---------------------------------------------------------------------------------------------------------
