@@ -15,7 +15,7 @@ c_int_p = ctypes.POINTER(ctypes.c_int)
 c_i32_p = ctypes.POINTER(ctypes.c_int32)
 c_i64_p = ctypes.POINTER(ctypes.c_int64)
 vp = ctypes.c_void_p
-ABI_VERSION = 5          # CV_ABI_VERSION of include/cv_hip.h that these ctypes signatures were written against
+ABI_VERSION = 6          # CV_ABI_VERSION of include/cv_hip.h that these ctypes signatures were written against
 
 
 class CvError(RuntimeError):
@@ -146,6 +146,47 @@ class SceneResult(ctypes.Structure):
                 ("d_prob", vp), ("d_class", vp), ("host_us", ctypes.c_float * 4)]
 
 
+GATHER_MAX_JOBS = 8      # CV_GATHER_MAX_JOBS
+
+
+class GatherJob(ctypes.Structure):
+    """struct cv_gather_job (include/cv_hip.h)"""
+    _fields_ = [("d_src", vp), ("src_ld", ctypes.c_longlong), ("d_dst", vp), ("dst_ld", ctypes.c_longlong),
+                ("width", ctypes.c_int), ("recentre_from", ctypes.c_int)]
+
+
+class PointsFront(ctypes.Structure):
+    """struct cv_points_front (include/cv_hip.h)"""
+    _fields_ = [("d_raw_points", vp), ("m", ctypes.c_longlong), ("points_ld", ctypes.c_longlong), ("points_f64", ctypes.c_int),
+                ("quantization_size", ctypes.c_double), ("d_raw_feats", vp), ("raw_feats_ld", ctypes.c_longlong),
+                ("in_channels", ctypes.c_int), ("recentre_from", ctypes.c_int), ("d_raw_xyz", vp), ("d_raw_scale", vp),
+                ("d_raw_prob", vp), ("d_raw_class", vp), ("d_coords4", vp), ("d_index", vp), ("d_inverse", vp)]
+
+
+class PointsDesc(ctypes.Structure):
+    """struct cv_points_desc (include/cv_hip.h)"""
+    _fields_ = [("front", PointsFront), ("scene", SceneDesc)]
+
+
+class PointsSeparateDesc(ctypes.Structure):
+    """struct cv_points_separate_desc (include/cv_hip.h)"""
+    _fields_ = [("front", PointsFront), ("scene", SceneSeparateDesc)]
+
+
+class PointsResult(ctypes.Structure):
+    """struct cv_points_result (include/cv_hip.h)"""
+    _fields_ = [("scene", SceneResult), ("n", ctypes.c_longlong), ("rejected", ctypes.c_int), ("host_us_front", ctypes.c_float),
+                ("front_ws_bytes", ctypes.c_size_t), ("d_feats", vp), ("d_points", vp), ("d_xyz_in", vp), ("d_scale_in", vp),
+                ("d_prob_in", vp), ("d_class_in", vp)]
+
+
+class PointsSeparateResult(ctypes.Structure):
+    """struct cv_points_separate_result (include/cv_hip.h)"""
+    _fields_ = [("scene", SceneSeparateResult), ("n", ctypes.c_longlong), ("rejected", ctypes.c_int),
+                ("host_us_front", ctypes.c_float), ("front_ws_bytes", ctypes.c_size_t), ("d_feats", vp), ("d_points", vp),
+                ("d_xyz_in", vp), ("d_scale_in", vp), ("d_prob_in", vp)]
+
+
 # symbol -> (restype, argtypes); tests check every symbol of include/cv_hip.h is here and exported
 SIGNATURES = {
     "cv_abi_version": (ctypes.c_int, []),
@@ -186,6 +227,8 @@ SIGNATURES = {
                                           ctypes.c_int, vp, vp, vp, vp, c_i32_p, vp, ctypes.c_size_t, vp]),
     "cv_sp_quantize_f64": (ctypes.c_int, [vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_double, ctypes.c_int, c_i64_p,
                                           ctypes.c_int, vp, vp, vp, vp, c_i32_p, vp, ctypes.c_size_t, vp]),
+    "cv_sp_voxel_rows_f32": (ctypes.c_int, [vp, vp, ctypes.c_longlong, ctypes.c_float, vp, ctypes.POINTER(GatherJob), ctypes.c_int, vp]),
+    "cv_sizeof_gather_job": (ctypes.c_size_t, []),
     "cv_sp_morton_keys": (ctypes.c_int, [vp, ctypes.c_longlong, vp, vp]),
     "cv_sp_sort_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "cv_sp_sort_rows": (ctypes.c_int, [vp, ctypes.c_longlong, vp, vp, vp, vp, ctypes.c_size_t, vp]),
@@ -269,6 +312,12 @@ SIGNATURES = {
                                          vp, vp, vp, vp, vp]),
     "cv_head_separate_f32": (ctypes.c_int, [vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]),
     "cv_detect_scene_f32": (ctypes.c_int, [ctypes.POINTER(SceneDesc), ctypes.POINTER(SceneResult), vp]),
+    "cv_detect_points_f32": (ctypes.c_int, [ctypes.POINTER(PointsDesc), ctypes.POINTER(PointsResult), vp]),
+    "cv_detect_points_separate_f32": (ctypes.c_int, [ctypes.POINTER(PointsSeparateDesc), ctypes.POINTER(PointsSeparateResult), vp]),
+    "cv_sizeof_points_desc": (ctypes.c_size_t, []),
+    "cv_sizeof_points_separate_desc": (ctypes.c_size_t, []),
+    "cv_sizeof_points_result": (ctypes.c_size_t, []),
+    "cv_sizeof_points_separate_result": (ctypes.c_size_t, []),
     "cv_iou_obb": (ctypes.c_double, [c_float_p, c_float_p]),
     "cv_nms_obb": (ctypes.c_int, [c_float_p, c_float_p, ctypes.c_int, ctypes.c_double, c_i32_p]),
 }

@@ -405,3 +405,167 @@ int cv_detect_scene_separate_f32(const cv_scene_separate_desc* d, cv_scene_separ
 }
 
 }  // extern "C"
+
+// ---- a scene from a RAW cloud: voxelise -> gather -> the scene call above, as ONE call ------------------------------------
+// A front in front of cv_detect_scene_f32 / cv_detect_scene_separate_f32 (their bodies are untouched): its scratch is carved
+// from the head of the scene's workspace, the voxeliser's host wait gives the row count, one gather launch (one per eight jobs
+// in separate mode) makes the voxel-aligned features, world points and predictions, and the scene call runs on a private copy
+// of the descriptor that points at them, with the rest of the workspace.  A third host wait (the voxel count): the plan
+// kernels take the row count from the host, carrying it on the device through all of them is not done here.
+namespace {
+
+int check_points_front(const cv_points_front& f, bool joint) {
+    CV_REQUIRE(f.d_raw_points && f.d_raw_feats && f.d_coords4 && f.d_index, CV_EINVAL, "raw cloud: null pointer argument");
+    CV_REQUIRE(f.m > 0 && f.m <= (1ll << 29), CV_EINVAL, "raw cloud: bad point count %lld", f.m);
+    CV_REQUIRE(f.points_ld >= 3, CV_EINVAL, "raw cloud: bad row stride %lld", f.points_ld);
+    // (as float too: the scene's res and the fp32 voxeliser's divisor)
+    CV_REQUIRE(f.quantization_size > 0 && f.quantization_size <= 3.0e38 && (float)f.quantization_size > 0.0f, CV_EINVAL,
+               "raw cloud: quantization_size must be positive and finite (got %g)", f.quantization_size);
+    CV_REQUIRE(f.in_channels > 0 && f.in_channels <= f.raw_feats_ld, CV_EINVAL, "raw cloud: bad feature width %d (row stride %lld)",
+               f.in_channels, f.raw_feats_ld);
+    CV_REQUIRE(f.recentre_from <= f.in_channels, CV_EINVAL, "raw cloud: recentre_from %d beyond the feature width %d", f.recentre_from,
+               f.in_channels);
+    const int given = !!f.d_raw_xyz + !!f.d_raw_scale + !!f.d_raw_prob + (joint ? !!f.d_raw_class : 0);
+    CV_REQUIRE(given == 0 || given == (joint ? 4 : 3), CV_EINVAL, "raw cloud: predictions: all %d arrays or none", joint ? 4 : 3);
+    CV_REQUIRE(joint || !f.d_raw_class, CV_EINVAL, "raw cloud: separate mode takes no class array");
+    return CV_OK;
+}
+
+// K: prediction sets ([K][m][..] raw, [K][n][..] gathered); d_class_view: where joint mode's gathered class array is handed
+// over (NULL: separate mode, no class array)
+template <class PD, class PR, class Inner>
+int detect_points(const PD* pd, PR* r, int K, int32_t** d_class_view, Inner inner, void* stream) {
+    const bool joint = d_class_view != nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    const cv_points_front& f = pd->front;
+    auto sd = pd->scene;                            // the private copy the scene call runs on
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long long m = f.m;
+    const int C = f.in_channels;
+    const bool pred = f.d_raw_xyz != nullptr;
+    const float res = (float)f.quantization_size;
+
+    // ---- 1. the front's scratch, from the head of the scene's workspace
+    Carver cv(sd.d_ws, sd.ws_bytes);
+    const size_t q_ws_b = cv_sp_quantize_workspace_bytes(m);
+    char* q_ws = cv.take<char>(q_ws_b);
+    int32_t* d_counts = cv.take<int32_t>(2);
+    float* feats = cv.take<float>((size_t)m * C);
+    float* points = cv.take<float>((size_t)m * 3);
+    float* xyz = pred ? cv.take<float>((size_t)K * m * 3) : nullptr;
+    float* scale = pred ? cv.take<float>((size_t)K * m * 3) : nullptr;
+    float* prob = pred ? cv.take<float>((size_t)K * m) : nullptr;
+    int32_t* cls = pred && joint ? cv.take<int32_t>((size_t)m) : nullptr;
+    const size_t front = cv_align_up(cv.off, 256);
+    r->front_ws_bytes = front;
+    sd.events[0] = nullptr;                         // (recorded here, in front of the voxelisation)
+    const bool fits = front <= sd.ws_bytes && q_ws && d_counts && feats && points && (!pred || (xyz && scale && prob)) &&
+                      (!(pred && joint) || cls);
+    if (!fits) {
+        // the scene call's own size when every point is a voxel, asked with no room at all: it returns from its fixed-part check,
+        // in front of its first launch (the pointers are placeholders, never read)
+        sd.d_coords4 = f.d_coords4; sd.n = m;
+        sd.d_feats = static_cast<const float*>(sd.d_ws); sd.feats_ld = C;
+        sd.d_points = static_cast<const float*>(sd.d_ws); sd.res = res;
+        sd.ws_bytes = 0;
+        const int rc = inner(&sd, &r->scene, stream);
+        if (rc != CV_ENOMEM) return rc;
+        r->scene.needed_ws_bytes += front;
+        cv_set_error("scene workspace too small (needs at least %zu bytes)", r->scene.needed_ws_bytes);
+        return CV_ENOMEM;
+    }
+
+    // ---- 2. voxelise: the host waits for the voxel count and the rejected count
+    if (pd->scene.events[0]) CV_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(pd->scene.events[0]), st));
+    int32_t h_counts[2] = {0, 0};
+    int rc = f.points_f64
+                 ? cv_sp_quantize_f64(static_cast<const double*>(f.d_raw_points), m, f.points_ld, f.quantization_size, 0, nullptr, 0,
+                                      f.d_coords4, f.d_index, f.d_inverse, d_counts, h_counts, q_ws, q_ws_b, stream)
+                 : cv_sp_quantize_f32(static_cast<const float*>(f.d_raw_points), m, f.points_ld, res, 0, nullptr, 0, f.d_coords4,
+                                      f.d_index, f.d_inverse, d_counts, h_counts, q_ws, q_ws_b, stream);
+    if (rc != CV_OK) return rc;
+    const long long n = h_counts[0];
+    r->n = n;
+    r->rejected = h_counts[1];
+    CV_REQUIRE(h_counts[1] == 0, CV_EINVAL,
+               "%d points rejected (a non-finite component, or a voxel outside the supported window: spatial coordinates in "
+               "[-32704, 32703])", h_counts[1]);
+    CV_REQUIRE(n > 0 && n <= m, CV_EINVAL, "the voxeliser returned %lld voxels of %lld points", n, m);
+
+    // ---- 3. gather: features, world points and predictions of the voxels' first points
+    std::vector<cv_gather_job> jobs;
+    jobs.push_back({f.d_raw_feats, f.raw_feats_ld, feats, C, C, f.recentre_from});
+    for (int k = 0; pred && k < K; ++k) {
+        jobs.push_back({f.d_raw_xyz + (size_t)k * m * 3, 3, xyz + (size_t)k * n * 3, 3, 3, -1});
+        jobs.push_back({f.d_raw_scale + (size_t)k * m * 3, 3, scale + (size_t)k * n * 3, 3, 3, -1});
+        jobs.push_back({f.d_raw_prob + (size_t)k * m, 1, prob + (size_t)k * n, 1, 1, -1});
+    }
+    if (pred && joint) jobs.push_back({f.d_raw_class, 1, cls, 1, 1, -1});
+    for (size_t j0 = 0; j0 < jobs.size(); j0 += CV_GATHER_MAX_JOBS) {
+        rc = cv_sp_voxel_rows_f32(f.d_coords4, f.d_index, n, res, j0 == 0 ? points : nullptr, jobs.data() + j0,
+                                  (int)std::min<size_t>(CV_GATHER_MAX_JOBS, jobs.size() - j0), stream);
+        if (rc != CV_OK) return rc;
+    }
+    r->d_feats = feats; r->d_points = points; r->d_xyz_in = xyz; r->d_scale_in = scale; r->d_prob_in = prob;
+    if (joint) *d_class_view = cls;
+
+    // ---- 4. the scene call on the gathered arrays and the rest of the workspace
+    sd.d_coords4 = f.d_coords4; sd.n = n;
+    sd.d_feats = feats; sd.feats_ld = C;
+    sd.d_points = points; sd.res = res;
+    sd.d_xyz_in = xyz; sd.d_scale_in = scale; sd.d_prob_in = prob;
+    sd.d_ws = static_cast<char*>(sd.d_ws) + front;
+    sd.ws_bytes -= front;
+    r->host_us_front = std::chrono::duration<float, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    rc = inner(&sd, &r->scene, stream);
+    if (r->scene.needed_ws_bytes) r->scene.needed_ws_bytes += front;
+    if (rc == CV_ENOMEM) cv_set_error("scene workspace too small (needs %zu bytes)", r->scene.needed_ws_bytes);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cv_detect_points_f32(const cv_points_desc* d, cv_points_result* r, void* stream) {
+    CV_REQUIRE(d && r, CV_EINVAL, "null raw-cloud descriptor / result");
+    std::memset(r, 0, sizeof(*r));
+    int rc = check_points_front(d->front, true);
+    if (rc != CV_OK) return rc;
+    const cv_scene_desc& s = d->scene;
+    CV_REQUIRE(!s.d_coords4 && s.n == 0 && !s.d_feats && s.feats_ld == 0 && !s.d_points && !s.d_xyz_in && !s.d_scale_in && !s.d_prob_in &&
+                   !s.d_class_in, CV_EINVAL, "raw cloud: the scene's d_coords4 / n / d_feats / feats_ld / d_points / d_*_in must be NULL / 0");
+    CV_REQUIRE(s.ops && s.bufs && s.n_ops > 0 && s.n_bufs > 0 && s.d_out_feats && s.d_ws && s.h_pinned && s.max_candidates > 0, CV_EINVAL,
+               "bad scene descriptor");
+    // (the class array is joint mode's alone: the shared front hands its carve over through the result)
+    auto inner = [r](cv_scene_desc* sd, cv_scene_result* sr, void* st) {
+        sd->d_class_in = r->d_class_in;
+        return cv_detect_scene_f32(sd, sr, st);
+    };
+    return detect_points(d, r, 1, &r->d_class_in, inner, stream);
+}
+
+int cv_detect_points_separate_f32(const cv_points_separate_desc* d, cv_points_separate_result* r, void* stream) {
+    CV_REQUIRE(d && r, CV_EINVAL, "null raw-cloud descriptor / result");
+    std::memset(r, 0, sizeof(*r));
+    int rc = check_points_front(d->front, false);
+    if (rc != CV_OK) return rc;
+    const cv_scene_separate_desc& s = d->scene;
+    CV_REQUIRE(!s.d_coords4 && s.n == 0 && !s.d_feats && s.feats_ld == 0 && !s.d_points && !s.d_xyz_in && !s.d_scale_in && !s.d_prob_in,
+               CV_EINVAL, "raw cloud: the scene's d_coords4 / n / d_feats / feats_ld / d_points / d_*_in must be NULL / 0");
+    CV_REQUIRE(s.num_models >= 1 && s.num_models <= CV_MAX_CATEGORIES, CV_EINVAL, "num_models out of range (%d, 1..%d)", s.num_models,
+               CV_MAX_CATEGORIES);
+    CV_REQUIRE(s.ops && s.n_ops && s.bufs && s.n_bufs && s.d_out_feats && s.d_ws && s.h_pinned && s.max_candidates > 0, CV_EINVAL,
+               "bad scene descriptor");
+    auto inner = [](cv_scene_separate_desc* sd, cv_scene_separate_result* sr, void* st) {
+        return cv_detect_scene_separate_f32(sd, sr, st);
+    };
+    return detect_points(d, r, s.num_models, nullptr, inner, stream);
+}
+
+size_t cv_sizeof_points_desc(void) { return sizeof(cv_points_desc); }
+size_t cv_sizeof_points_separate_desc(void) { return sizeof(cv_points_separate_desc); }
+size_t cv_sizeof_points_result(void) { return sizeof(cv_points_result); }
+size_t cv_sizeof_points_separate_result(void) { return sizeof(cv_points_separate_result); }
+
+}  // extern "C"

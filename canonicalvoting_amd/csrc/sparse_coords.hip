@@ -962,6 +962,87 @@ int cv_sp_quantize_f64(const double* d_points, long long m, long long ld, double
 
 }  // extern "C"
 
+// ---- what a scene reads of a voxelised cloud (cv_sp_voxel_rows_f32) ---------------------------------------------------------
+// One launch behind the voxeliser: the world points of the voxels (float(coordinate) * res: the conversion and one fp32
+// multiply, nothing to contract) and up to CV_GATHER_MAX_JOBS row gathers by the first-point index.  The jobs travel in the
+// kernel arguments; every job (and the points) owns a range of workgroups that strides over its n * width words, so adjacent
+// lanes write adjacent destination words; rows are moved as 32-bit words (payloads stay the same bits).  `index` ascends: the
+// source rows are visited in nearly increasing order.
+namespace {
+
+struct RowJobsDev {
+    const int* coords4; const int* index; float* points;
+    long long n;
+    float res;
+    int n_jobs;
+    cv_gather_job j[CV_GATHER_MAX_JOBS];
+    int block_begin[CV_GATHER_MAX_JOBS + 2];        // job i: [i], [i + 1]); the points: [n_jobs], [n_jobs + 1])
+};
+
+__global__ __launch_bounds__(256) void voxel_rows(const RowJobsDev a) {
+    int ji = 0;
+    while (ji < a.n_jobs && (int)blockIdx.x >= a.block_begin[ji + 1]) ++ji;
+    const int nblk = a.block_begin[ji + 1] - a.block_begin[ji], blk = blockIdx.x - a.block_begin[ji];
+    const long long first = blk * 256ll + threadIdx.x, step = (long long)nblk * 256;
+    if (ji == a.n_jobs) {
+        for (long long e = first; e < a.n * 3; e += step) {
+            const long long i = e / 3;
+            a.points[e] = (float)a.coords4[4 * i + 1 + (int)(e - 3 * i)] * a.res;
+        }
+        return;
+    }
+    const cv_gather_job& jb = a.j[ji];
+    const unsigned* __restrict__ src = static_cast<const unsigned*>(jb.d_src);
+    unsigned* __restrict__ dst = static_cast<unsigned*>(jb.d_dst);
+    const int w = jb.width, rc = jb.recentre_from;
+    for (long long e = first; e < a.n * w; e += step) {
+        const long long i = e / w;
+        const int c = (int)(e - i * w);
+        unsigned v = src[(long long)a.index[i] * jb.src_ld + c];
+        if (rc >= 0 && c >= rc) v = __float_as_uint(__uint_as_float(v) * 2.0f - 1.0f);
+        dst[i * jb.dst_ld + c] = v;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int cv_sp_voxel_rows_f32(const int32_t* d_coords4, const int32_t* d_index, long long n, float res, float* d_points_out,
+                         const cv_gather_job* jobs, int n_jobs, void* stream) {
+    CV_REQUIRE(n > 0 && n <= (1ll << 29), CV_EINVAL, "bad row count %lld", n);
+    CV_REQUIRE(n_jobs >= 0 && n_jobs <= CV_GATHER_MAX_JOBS, CV_EINVAL, "bad gather job count %d (0..%d)", n_jobs, CV_GATHER_MAX_JOBS);
+    CV_REQUIRE((!d_points_out || d_coords4) && (n_jobs == 0 || (d_index && jobs)), CV_EINVAL, "null pointer argument");
+    CV_REQUIRE(!d_points_out || (res > 0.0f && res <= std::numeric_limits<float>::max()), CV_EINVAL,
+               "res must be positive and finite (got %g)", (double)res);
+    RowJobsDev a = {};
+    a.coords4 = d_coords4; a.index = d_index; a.points = d_points_out;
+    a.n = n; a.res = res; a.n_jobs = n_jobs;
+    int total = 0;
+    for (int i = 0; i < n_jobs; ++i) {
+        const cv_gather_job& j = jobs[i];
+        CV_REQUIRE(j.d_src && j.d_dst, CV_EINVAL, "gather job %d: null pointer argument", i);
+        CV_REQUIRE(j.width > 0 && j.width <= j.src_ld && j.width <= j.dst_ld, CV_EINVAL,
+                   "gather job %d: bad width %d (row strides %lld, %lld)", i, j.width, j.src_ld, j.dst_ld);
+        CV_REQUIRE(j.recentre_from <= j.width, CV_EINVAL, "gather job %d: recentre_from %d beyond the width %d", i,
+                   j.recentre_from, j.width);
+        a.j[i] = j;
+        a.block_begin[i] = total;
+        total += grid_for(n * j.width);
+    }
+    a.block_begin[n_jobs] = total;
+    if (d_points_out) total += grid_for(n * 3);
+    a.block_begin[n_jobs + 1] = total;
+    if (total == 0) return CV_OK;                   // no job and no points: nothing to launch
+    voxel_rows<<<total, 256, 0, static_cast<hipStream_t>(stream)>>>(a);
+    CV_LAUNCH_CHECK();
+    return CV_OK;
+}
+
+size_t cv_sizeof_gather_job(void) { return sizeof(cv_gather_job); }
+
+}  // extern "C"
+
 int cv_sp_kernel_maps_batch(const CvMapJob* jobs, int n_jobs, void* stream) {
     CV_REQUIRE(jobs && n_jobs > 0 && n_jobs <= CV_MAX_MAP_JOBS, CV_EINVAL, "bad kernel map batch");
     MapJobsDev d;

@@ -1,5 +1,6 @@
 """``ME.utils`` subset: batched_coordinates (train_joint.py:82), sparse_quantize
-(utils/dataloader.py:197, sunrgbd/brnetcanon.py:218; on the device: quantize_device / quantize_batch), kaiming_normal_
+(utils/dataloader.py:197, sunrgbd/brnetcanon.py:218; on the device: quantize_device / quantize_batch, and voxel_rows for
+what a scene gathers behind it), kaiming_normal_
 (utils/resnet.py:112)."""
 import math
 
@@ -100,6 +101,60 @@ def quantize_batch(clouds, quantization_size, return_inverse=False, offsets=None
         pts = torch.cat([c.to(dt) for c in clouds], 0)
     coords4, index, inverse = quantize_device(pts, quantization_size, offsets, return_inverse)
     return (coords4, index, inverse) if return_inverse else (coords4, index)
+
+
+def voxel_rows(coords4, index, res, *columns, recentre_from=None, out=None, points=True):
+    """What a scene reads of a voxelised cloud, in ONE launch on torch's current stream (cv_sp_voxel_rows_f32): the world
+    points ``float(coords4[:, 1:]) * float32(res)`` - the bits of ``(coords4[:, 1:] * res).float()`` - and
+    ``column[index]`` for up to eight raw-point-aligned ``columns`` ([M, w] or [M], float32 or int32, unit column stride;
+    the row stride may exceed w: a column block of a wider tensor).  Rows move as 32-bit words, payloads untouched.
+
+    recentre_from: None, one int for every column or a sequence with one entry (int or None) per column: columns >= it are
+    written as ``x * 2 - 1`` (float32).  out: optional destinations, one per column ([N, w] windows, row stride >= w; the
+    words beyond w are left alone).  points=False: no world points (coords4 and res are not read).
+    Returns (points [N, 3] float32 or None, list of the gathered columns)."""
+    import ctypes
+
+    from .. import _lib
+    L = _lib.lib()
+    vp = ctypes.c_void_p
+    n, dev = index.shape[0], index.device
+    assert index.dtype == torch.int32 and index.is_contiguous(), "index: a contiguous int32 device tensor"
+    if len(columns) > _lib.GATHER_MAX_JOBS:
+        raise ValueError("voxel_rows: at most %d columns per call (got %d)" % (_lib.GATHER_MAX_JOBS, len(columns)))
+    if recentre_from is None or isinstance(recentre_from, int):
+        recentre_from = [recentre_from] * len(columns)
+    pts = None
+    if points:
+        assert coords4.dtype == torch.int32 and coords4.is_contiguous() and coords4.shape == (n, 4), "coords4: contiguous int32 [N, 4]"
+        pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    jobs = (_lib.GatherJob * max(len(columns), 1))()
+    outs = []
+    for i, col in enumerate(columns):
+        if col.dtype not in (torch.float32, torch.int32):
+            raise TypeError("voxel_rows: columns are float32 or int32 (got %s)" % col.dtype)
+        c2 = col if col.dim() == 2 else col.unsqueeze(1)
+        w = c2.shape[1]
+        if c2.stride(1) != 1 or c2.stride(0) < w:
+            c2 = c2.contiguous()
+        if out is not None and out[i] is not None:
+            dst = out[i]
+            d2 = dst if dst.dim() == 2 else dst.unsqueeze(1)
+            assert d2.dtype == col.dtype and d2.shape == (n, w) and d2.stride(1) == 1 and d2.stride(0) >= w, "out: [N, w] windows"
+        else:
+            dst = torch.empty((n, w) if col.dim() == 2 else (n,), dtype=col.dtype, device=dev)
+            d2 = dst if dst.dim() == 2 else dst.unsqueeze(1)
+        rf = recentre_from[i]
+        if rf is not None and col.dtype != torch.float32:
+            raise TypeError("voxel_rows: only float32 columns are recentred")
+        jobs[i] = _lib.GatherJob(c2.data_ptr(), c2.stride(0), d2.data_ptr(), d2.stride(0), w, -1 if rf is None else int(rf))
+        outs.append(dst)
+    with torch.cuda.device(dev):
+        stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
+        _lib.check(L.cv_sp_voxel_rows_f32(vp(coords4.data_ptr()) if points else None, vp(index.data_ptr()), n,
+                                          float(res) if points else 0.0, vp(pts.data_ptr()) if points else None, jobs,
+                                          len(columns), stream), "cv_sp_voxel_rows_f32")
+    return pts, outs
 
 
 def sparse_quantize(coordinates, features=None, labels=None, quantization_size=None, return_index=False,

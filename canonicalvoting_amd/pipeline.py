@@ -186,8 +186,10 @@ def _set_events(d, events):
 
 def _fill_scene_desc(d, model, hv, coords4, feats, scan_points, res, policy, pieces, max_channels, log_scale):
     """the fields cv_scene_desc and cv_scene_separate_desc share (model: the one, or the first of the K, that the plan follows)"""
-    d.d_coords4, d.n, d.d_feats, d.feats_ld = vp(coords4.data_ptr()), coords4.shape[0], vp(feats.data_ptr()), feats.stride(0)
-    d.d_points, d.res, d.num_rots = vp(scan_points.data_ptr()), float(res), hv_cuda._scalar(hv.num_rots, "i")
+    if coords4 is not None:          # (None: a raw-cloud call, which makes the scene's arrays itself)
+        d.d_coords4, d.n, d.d_feats, d.feats_ld = vp(coords4.data_ptr()), coords4.shape[0], vp(feats.data_ptr()), feats.stride(0)
+        d.d_points = vp(scan_points.data_ptr())
+    d.res, d.num_rots = float(res), hv_cuda._scalar(hv.num_rots, "i")
     d.stem_k, d.mask_groups = model.conv0p1s1.kernel_size, ME.CoordinateManager.plan_mask_groups()
     d.masked_min_rows = policy.masked_min_rows if policy is not None else model.masked_min_rows()
     if policy is not None:
@@ -331,41 +333,18 @@ def detect_scene_separate_c(models, hv, coords4, feats, res, predictions=None, p
     coords4 = coords4.to(device=dev, dtype=torch.int32).contiguous()
     feats = feats.contiguous()
     ys = [torch.empty((n, m.final.out_channels), dtype=torch.float32, device=dev) for m in mods]
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
     M = int(max_candidates)
-    with _scene_lock:
-        host = _sep_hosts.get(key)
-        if host is None or host["M"] < M or host["K"] < K:
-            host = _sep_hosts[key] = dict(
-                M=M, K=K, ws_hint=0, pinned=torch.empty(64 + 64 * _lib.MAX_CATEGORIES, dtype=torch.uint8).pin_memory(),
-                cand=np.zeros((K, M), np.int64), verdict=np.zeros((K, M), np.int32), boxes=np.zeros((K, M, 8, 3), np.float32),
-                scores=np.zeros((K, M), np.float32), det_cat=np.zeros(K * M, np.int32), det_box=np.zeros(K * M, np.int32))
-    Mh = host["M"]
+    host = _sep_host(dev, K, M)
     d = _lib.SceneSeparateDesc()
     _fill_scene_desc(d, mods[0], hv, coords4, feats, scan_points, res, policy, pieces, max(max(m.PLANES) for m in mods), log_scale)
-    d.num_models = K
-    if G > 0:
-        d.models_per_pass, d.d_model_params = G, vp(table.data_ptr())
-    ops = (vp * K)(*[ctypes.cast(p[0], vp) for p in progs])
-    n_ops = (ctypes.c_int * K)(*[len(p[0]) for p in progs])
-    bufs = (vp * K)(*[ctypes.cast(p[1], vp) for p in progs])
-    n_bufs = (ctypes.c_int * K)(*[len(p[1]) for p in progs])
-    outs = (vp * K)(*[y.data_ptr() for y in ys])
-    d.ops, d.n_ops, d.bufs, d.n_bufs = ctypes.cast(ops, vp), ctypes.cast(n_ops, vp), ctypes.cast(bufs, vp), ctypes.cast(n_bufs, vp)
-    d.d_out_feats, d.out_ld, d.out_channels = ctypes.cast(outs, vp), ys[0].stride(0), ys[0].shape[1]
     if predictions is not None:
         px, ps, pp = [a.contiguous() for a in predictions]
         d.d_xyz_in, d.d_scale_in, d.d_prob_in = vp(px.data_ptr()), vp(ps.data_ptr()), vp(pp.data_ptr())
-    _fill_decode_params(d.decode, decode_kw, True)
-    d.max_candidates, d.nms_threshold = Mh, float(overlap_threshold)
-    _set_events(d, events)
-    d.h_pinned, d.pinned_bytes = vp(host["pinned"].data_ptr()), host["pinned"].numel()
-    d.h_cand_idx, d.h_verdict = vp(host["cand"].ctypes.data), vp(host["verdict"].ctypes.data)
-    d.h_boxes, d.h_scores = vp(host["boxes"].ctypes.data), vp(host["scores"].ctypes.data)
-    d.h_det_cat, d.h_det_box = vp(host["det_cat"].ctypes.data), vp(host["det_box"].ctypes.data)
+    alive = _fill_separate_desc(d, host, progs, table, G, ys, decode_kw, overlap_threshold, events)
     r = _lib.SceneSeparateResult()
     ws = _call_growing(L.cv_detect_scene_separate_f32, "cv_detect_scene_separate_f32", d, r, dev, "scene_call_separate",
                        host["ws_hint"])
+    del alive
     host["ws_hint"] = max(host["ws_hint"], int(r.needed_ws_bytes))
     if keep is not None:
         keep.update(range_flag=int(r.range_flag), needed_ws_bytes=int(r.needed_ws_bytes))
@@ -377,6 +356,50 @@ def detect_scene_separate_c(models, hv, coords4, feats, res, predictions=None, p
                                          overlap_threshold=overlap_threshold, **kw)
         return _separate_by_calls(hv, scan_points, predictions[0], predictions[1], predictions[2], res, categories,
                                   overlap_threshold, **kw)
+    return _separate_results(host, r, keep, categories, ys, n, dev, ws)
+
+
+def _sep_host(dev, K, M):
+    """host-side scratch of the separate scene calls on the calling thread's current stream: pinned landing words, result arrays"""
+    import numpy as np
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    with _scene_lock:
+        host = _sep_hosts.get(key)
+        if host is None or host["M"] < M or host["K"] < K:
+            host = _sep_hosts[key] = dict(
+                M=M, K=K, ws_hint=0, pinned=torch.empty(64 + 64 * _lib.MAX_CATEGORIES, dtype=torch.uint8).pin_memory(),
+                cand=np.zeros((K, M), np.int64), verdict=np.zeros((K, M), np.int32), boxes=np.zeros((K, M, 8, 3), np.float32),
+                scores=np.zeros((K, M), np.float32), det_cat=np.zeros(K * M, np.int32), det_box=np.zeros(K * M, np.int32))
+    return host
+
+
+def _fill_separate_desc(d, host, progs, table, G, ys, decode_kw, overlap_threshold, events):
+    """cv_scene_separate_desc beyond _fill_scene_desc: the K programs and outputs, decode parameters, the host's landing arrays.
+    Returns the pointer tables the descriptor refers to (keep them alive over the call)."""
+    K = len(progs)
+    d.num_models = K
+    if G > 0:
+        d.models_per_pass, d.d_model_params = G, vp(table.data_ptr())
+    ops = (vp * K)(*[ctypes.cast(p[0], vp) for p in progs])
+    n_ops = (ctypes.c_int * K)(*[len(p[0]) for p in progs])
+    bufs = (vp * K)(*[ctypes.cast(p[1], vp) for p in progs])
+    n_bufs = (ctypes.c_int * K)(*[len(p[1]) for p in progs])
+    outs = (vp * K)(*[y.data_ptr() for y in ys])
+    d.ops, d.n_ops, d.bufs, d.n_bufs = ctypes.cast(ops, vp), ctypes.cast(n_ops, vp), ctypes.cast(bufs, vp), ctypes.cast(n_bufs, vp)
+    d.d_out_feats, d.out_ld, d.out_channels = ctypes.cast(outs, vp), ys[0].stride(0), ys[0].shape[1]
+    _fill_decode_params(d.decode, decode_kw, True)
+    d.max_candidates, d.nms_threshold = host["M"], float(overlap_threshold)
+    _set_events(d, events)
+    d.h_pinned, d.pinned_bytes = vp(host["pinned"].data_ptr()), host["pinned"].numel()
+    d.h_cand_idx, d.h_verdict = vp(host["cand"].ctypes.data), vp(host["verdict"].ctypes.data)
+    d.h_boxes, d.h_scores = vp(host["boxes"].ctypes.data), vp(host["scores"].ctypes.data)
+    d.h_det_cat, d.h_det_box = vp(host["det_cat"].ctypes.data), vp(host["det_box"].ctypes.data)
+    return ops, n_ops, bufs, n_bufs, outs
+
+
+def _separate_results(host, r, keep, categories, ys, n, dev, ws):
+    """detections of a finished cv_scene_separate_result; ``keep`` (optional) receives the per-category raw decode and the device views"""
+    K = len(categories)
     dets = [(categories[int(c)], host["boxes"][int(c), int(b)].copy(), float(host["scores"][int(c), int(b)]))
             for c, b in zip(host["det_cat"][:r.n_det], host["det_box"][:r.n_det])]
     if keep is not None:
@@ -435,29 +458,15 @@ def detect_scene_c(model, hv, coords4, feats, res, nclasses=9, log_scale=True, s
     coords4 = coords4.to(device=dev, dtype=torch.int32).contiguous()
     feats = feats.contiguous()
     y = torch.empty((n, model.final.out_channels), dtype=torch.float32, device=dev)
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    with _scene_lock:
-        host = _scene_hosts.get(key)
-        if host is None or host.M < max_candidates:
-            host = _scene_hosts[key] = _SceneHost(max_candidates)
+    host = _scene_host(dev, max_candidates)
     d = _lib.SceneDesc()
     _fill_scene_desc(d, model, hv, coords4, feats, scan_points, res, policy, pieces, max(model.PLANES), log_scale)
-    d.ops, d.n_ops, d.bufs, d.n_bufs = ctypes.cast(c_ops, vp), len(c_ops), ctypes.cast(c_bufs, vp), len(c_bufs)
-    d.d_out_feats, d.out_ld, d.out_channels = vp(y.data_ptr()), y.stride(0), y.shape[1]
-    d.nclasses = nclasses
     if predictions is not None:
         px, ps, pp, pc = predictions
         pc = pc.to(torch.int32).contiguous()
         d.d_xyz_in, d.d_scale_in, d.d_prob_in, d.d_class_in = (vp(px.data_ptr()), vp(ps.data_ptr()), vp(pp.data_ptr()),
                                                                  vp(pc.data_ptr()))
-    _fill_decode_params(d.decode, decode_kw, False)
-    d.max_candidates, d.nms_threshold = host.M, 0.3
-    d.adaptive_split = 1 if adaptive_split else 0
-    _set_events(d, events)
-    d.h_pinned, d.pinned_bytes = vp(host.pinned.data_ptr()), host.pinned.numel()
-    d.h_cand_idx, d.h_verdict = vp(host.cand.ctypes.data), vp(host.verdict.ctypes.data)
-    d.h_boxes, d.h_scores, d.h_classes, d.h_pick = (vp(host.boxes.ctypes.data), vp(host.scores.ctypes.data),
-                                                    vp(host.classes.ctypes.data), vp(host.pick.ctypes.data))
+    _fill_joint_desc(d, host, c_ops, c_bufs, y, nclasses, decode_kw, adaptive_split, events)
     r = _lib.SceneResult()
     ws = _call_growing(L.cv_detect_scene_f32, "cv_detect_scene_f32", d, r, dev, "scene_call", host.ws_hint)
     host.ws_hint = max(host.ws_hint, int(r.needed_ws_bytes))
@@ -473,19 +482,49 @@ def detect_scene_c(model, hv, coords4, feats, res, nclasses=9, log_scale=True, s
             dets, raw = decode.detect(hv, coords4[:, 1:], pred[0], pred[1], pred[2], pred[3], res, nclasses,
                                       scan_points=scan_points, **decode_kw)
         return dets, raw, yy.F
+    dets, raw = _joint_results(host, r, keep, y, n, dev, ws)
+    return dets, raw, y
+
+
+def _scene_host(dev, max_candidates):
+    """the _SceneHost of the calling thread's current stream (one per (device, stream); regrown for more candidates)"""
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+    with _scene_lock:
+        host = _scene_hosts.get(key)
+        if host is None or host.M < max_candidates:
+            host = _scene_hosts[key] = _SceneHost(max_candidates)
+    return host
+
+
+def _fill_joint_desc(d, host, c_ops, c_bufs, y, nclasses, decode_kw, adaptive_split, events):
+    """cv_scene_desc beyond _fill_scene_desc: program, output, decode parameters, the host's landing arrays"""
+    d.ops, d.n_ops, d.bufs, d.n_bufs = ctypes.cast(c_ops, vp), len(c_ops), ctypes.cast(c_bufs, vp), len(c_bufs)
+    d.d_out_feats, d.out_ld, d.out_channels = vp(y.data_ptr()), y.stride(0), y.shape[1]
+    d.nclasses = nclasses
+    _fill_decode_params(d.decode, decode_kw, False)
+    d.max_candidates, d.nms_threshold = host.M, 0.3
+    d.adaptive_split = 1 if adaptive_split else 0
+    _set_events(d, events)
+    d.h_pinned, d.pinned_bytes = vp(host.pinned.data_ptr()), host.pinned.numel()
+    d.h_cand_idx, d.h_verdict = vp(host.cand.ctypes.data), vp(host.verdict.ctypes.data)
+    d.h_boxes, d.h_scores, d.h_classes, d.h_pick = (vp(host.boxes.ctypes.data), vp(host.scores.ctypes.data),
+                                                    vp(host.classes.ctypes.data), vp(host.pick.ctypes.data))
+
+
+def _joint_results(host, r, keep, y, n, dev, ws):
+    """(detections, raw decode dict) of a finished cv_scene_result; ``keep`` (optional) receives the device views"""
     k, m = r.n_boxes, r.n_cand
     raw = dict(boxes=host.boxes[:k].copy(), scores=host.scores[:k].copy(), classes=host.classes[:k].copy(),
                cand_idx=host.cand[:m].copy(), verdict=host.verdict[:m].copy(), truncated=False)
     dets = [(int(raw["classes"][i]), raw["boxes"][i], float(raw["scores"][i])) for i in host.pick[:r.n_det]]
     if keep is not None:
-        cells = r.dims[0] * r.dims[1] * r.dims[2]
         view = lambda ptr, shape, dt=torch.float32: _device_view(ptr, shape, dt, dev, ws)
         X, Y, Z = r.dims
         keep.update(y=y, dims=(X, Y, Z), corner=tuple(r.corner), level_rows=list(r.level_rows),
                     grids=(view(r.d_grid_obj, (X, Y, Z)), view(r.d_grid_rot, (X, Y, Z, 2)), view(r.d_grid_scale, (X, Y, Z, 3))),
                     net_pred=(view(r.d_xyz, (n, 3)), view(r.d_scale, (n, 3)), view(r.d_prob, (n,)),
                               view(r.d_class, (n,), torch.int32)), raw=raw)
-    return dets, raw, y
+    return dets, raw
 
 
 def detect_points(model, hv, points, feats, res, predictions=None, return_inverse=False, **kw):
@@ -494,7 +533,8 @@ def detect_points(model, hv, points, feats, res, predictions=None, return_invers
     ``predictions`` (xyz, scale, prob, class) are gathered by the first-point index, and the scene runs as detect_scene_c
     runs it - world points formed from the integer coordinates - so the results are bit for bit those of quantising on
     the host and calling detect_scene_c.  Returns detect_scene_c's (detections, raw, network output) plus ``index`` [N]
-    (and ``inverse`` [M] with return_inverse)."""
+    (and ``inverse`` [M] with return_inverse).  The call-by-call reference of detect_points_c, which does all of it in ONE
+    C call."""
     coords4, index, inverse = ME.utils.quantize_device(points, res, None, return_inverse)
     gi = index.long()
     dev = coords4.device
@@ -503,6 +543,162 @@ def detect_points(model, hv, points, feats, res, predictions=None, return_invers
         predictions = tuple(p.to(dev)[gi].contiguous() for p in predictions)
     out = detect_scene_c(model, hv, coords4, f, res, predictions=predictions, **kw)
     return out + ((index, inverse) if return_inverse else (index,))
+
+
+def _points_front(front, points, feats, in_channels, recentre_from, predictions, return_inverse, with_class):
+    """cv_points_front of a raw cloud; returns (coords4 [M, 4], index [M], inverse [M] or None, the tensors to keep alive)"""
+    dev = points.device
+    assert points.is_cuda and points.dim() == 2 and points.shape[1] == 3, "points: a [M, 3] device tensor"
+    if points.dtype not in (torch.float32, torch.float64):      # (as ME.utils.quantize_device: computed in fp64, as numpy promotes them)
+        points = points.to(torch.float64)
+    if points.stride(1) != 1 or points.stride(0) < 3:
+        points = points.contiguous()
+    m = points.shape[0]
+    if m == 0:
+        raise RuntimeError("sparse_quantize: empty point cloud")
+    feats = feats.to(device=dev, dtype=torch.float32)
+    if feats.stride(1) != 1 or feats.stride(0) < feats.shape[1]:
+        feats = feats.contiguous()
+    if feats.shape != (m, in_channels):
+        raise ValueError("raw cloud: feats must be [%d, %d] (got %s)" % (m, in_channels, tuple(feats.shape)))
+    coords4 = torch.empty((m, 4), dtype=torch.int32, device=dev)
+    index = torch.empty(m, dtype=torch.int32, device=dev)
+    inverse = torch.empty(m, dtype=torch.int32, device=dev) if return_inverse else None
+    front.d_raw_points, front.m, front.points_ld = vp(points.data_ptr()), m, points.stride(0)
+    front.points_f64 = 1 if points.dtype == torch.float64 else 0
+    front.d_raw_feats, front.raw_feats_ld, front.in_channels = vp(feats.data_ptr()), feats.stride(0), in_channels
+    front.recentre_from = -1 if recentre_from is None else int(recentre_from)
+    front.d_coords4, front.d_index = vp(coords4.data_ptr()), vp(index.data_ptr())
+    front.d_inverse = vp(inverse.data_ptr()) if return_inverse else None
+    alive = [points, feats]
+    if predictions is not None:
+        pred = [p.to(dev).contiguous() for p in predictions]
+        if with_class:
+            pred[3] = pred[3].to(torch.int32).contiguous()
+            front.d_raw_class = vp(pred[3].data_ptr())
+        front.d_raw_xyz, front.d_raw_scale, front.d_raw_prob = vp(pred[0].data_ptr()), vp(pred[1].data_ptr()), vp(pred[2].data_ptr())
+        alive += pred
+    return coords4, index, inverse, alive
+
+
+def _call_points(fn, name, d, r, dev, scratch_name, ws_hint):
+    """_call_growing for a raw-cloud descriptor (the scratch and its size live in the embedded scene descriptor / result); a
+    rejected cloud raises RuntimeError with the count, as ME.utils.quantize_device does"""
+    call = lambda _d, _r, stream: fn(ctypes.byref(d), ctypes.byref(r), stream)
+    try:
+        return _call_growing(call, name, d.scene, r.scene, dev, scratch_name, ws_hint)
+    except _lib.CvError:
+        if r.rejected:
+            raise RuntimeError("sparse_quantize: %d points rejected (a non-finite component, or a voxel outside the supported "
+                               "window: spatial coordinates in [-32704, 32703])" % r.rejected) from None
+        raise
+
+
+def detect_points_c(model, hv, points, feats, res, predictions=None, return_inverse=False, recentre_from=None, nclasses=9,
+                    log_scale=True, max_candidates=512, keep=None, events=None, adaptive_split=False, policy=None, **decode_kw):
+    """detect_points through ONE C call (cv_detect_points_f32: voxelise -> one gather launch for the features, world points
+    and predictions of the voxels' first points -> the scene of detect_scene_c), the GIL released for all of it: a host
+    that keeps several raw scenes in flight from several threads makes one foreign call per scene.  Same kernels in the same
+    order as detect_points: the same bits.  Three host waits inside the call: the voxel count, the level counts, the decode.
+
+    points [M, 3] device tensor (fp64 clouds are voxelised in fp64, other dtypes than fp32 converted to it; rows may be
+    strided), feats [M, C] and the optional ``predictions`` (xyz, scale, prob, class) aligned with the RAW points.
+    ``recentre_from`` = c: feature columns >= c are fed to the network as ``x * 2 - 1`` (eval_joint.py:167-168, in the
+    gather).  ``keep`` / ``events`` / ``policy`` / ``max_candidates`` as detect_scene_c; keep also receives ``scan_points``,
+    ``feats`` (the gathered ones) and the call's ``host_us`` / ``host_us_front``.  The network output buffer has M rows (the
+    voxel count N is not known before the call): the returned y is its first N.  A scene that needs what the call does not
+    do (range fallback, a decode walk beyond ``max_candidates``) is rerun through detect_scene_c from the voxel arrays the call
+    filled.  A cloud with rejected points raises RuntimeError with their count.
+    Returns (detections, raw, y [N, C'], index [N][, inverse [M]])."""
+    L = _lib.lib()
+    dev = points.device
+    pieces = 1 if ME.COMPUTE_DTYPE == "bf16" else model.PIECES
+    c_ops, c_bufs, _ = model._program(dev, pieces)
+    d, r = _lib.PointsDesc(), _lib.PointsResult()
+    coords4, index, inverse, alive = _points_front(d.front, points, feats, feats.shape[1], recentre_from, predictions,
+                                                   return_inverse, True)
+    d.front.quantization_size = float(res)
+    y = torch.empty((coords4.shape[0], model.final.out_channels), dtype=torch.float32, device=dev)
+    host = _scene_host(dev, max_candidates)
+    _fill_scene_desc(d.scene, model, hv, None, None, None, res, policy, pieces, max(model.PLANES), log_scale)
+    _fill_joint_desc(d.scene, host, c_ops, c_bufs, y, nclasses, decode_kw, adaptive_split, events)
+    ws = _call_points(L.cv_detect_points_f32, "cv_detect_points_f32", d, r, dev, "scene_call", host.ws_hint)
+    del alive
+    n = int(r.n)
+    host.ws_hint = max(host.ws_hint, int(r.scene.needed_ws_bytes))
+    host.last_host_us = tuple(r.scene.host_us)
+    coords4, index, y = coords4[:n], index[:n], y[:n]
+    tail = (index, inverse) if return_inverse else (index,)
+    view = lambda ptr, shape, dt=torch.float32: _device_view(ptr, shape, dt, dev, ws)
+    if r.scene.range_flag or r.scene.truncated:
+        pred = None
+        if predictions is not None:
+            pred = (view(r.d_xyz_in, (n, 3)), view(r.d_scale_in, (n, 3)), view(r.d_prob_in, (n,)), view(r.d_class_in, (n,), torch.int32))
+        return detect_scene_c(model, hv, coords4, view(r.d_feats, (n, d.front.in_channels)), res, nclasses=nclasses,
+                              log_scale=log_scale, predictions=pred, max_candidates=max_candidates, keep=keep, events=events,
+                              adaptive_split=adaptive_split, policy=policy, **decode_kw) + tail
+    if keep is not None:
+        keep.update(scan_points=view(r.d_points, (n, 3)), feats=view(r.d_feats, (n, d.front.in_channels)),
+                    host_us=tuple(r.scene.host_us), host_us_front=float(r.host_us_front), front_ws_bytes=int(r.front_ws_bytes))
+    dets, raw = _joint_results(host, r.scene, keep, y, n, dev, ws)
+    return (dets, raw, y) + tail
+
+
+def detect_points_separate_c(models, hv, points, feats, res, predictions=None, models_per_pass=None, return_inverse=False,
+                             recentre_from=None, policy=None, keep=None, events=None, log_scale=True, overlap_threshold=0.3,
+                             max_candidates=512, **decode_kw):
+    """detect_scene_separate_c from a RAW device cloud through ONE C call (cv_detect_points_separate_f32): voxelise, gather,
+    then the K models' scene.  ``predictions`` = (xyz [K, M, 3], scale [K, M, 3], prob [K, M]) aligned with the raw points; the
+    other arguments as detect_points_c / detect_scene_separate_c.  The same bits as ME.utils.quantize_device + torch gathers
+    + detect_scene_separate_c.  Returns (detections [(category, box[8,3], score)], index [N][, inverse [M]]); ``keep``
+    receives what detect_scene_separate_c's does (``y``: the K outputs' first N rows) plus ``coords4``."""
+    import numpy as np
+    decode_kw.setdefault("separate_variant", True)
+    decode_kw.setdefault("err_thresh", float(np.float32(0.3)))
+    L = _lib.lib()
+    dev = points.device
+    categories = list(models.keys())
+    mods = [models[c] for c in categories]
+    K = len(mods)
+    if not 1 <= K <= _lib.MAX_CATEGORIES:
+        raise ValueError("detect_points_separate_c: 1..%d models (got %d)" % (_lib.MAX_CATEGORIES, K))
+    pieces = 1 if ME.COMPUTE_DTYPE == "bf16" else mods[0].PIECES
+    G = int(models_per_pass or 0)
+    if G < 0:
+        raise ValueError("detect_points_separate_c: models_per_pass must be >= 0 (got %d)" % G)
+    if G > 0:
+        progs, table = model_params_table(mods, dev, pieces)
+    else:
+        progs, table = [m._program(dev, pieces) for m in mods], None
+    d, r = _lib.PointsSeparateDesc(), _lib.PointsSeparateResult()
+    coords4, index, inverse, alive = _points_front(d.front, points, feats, feats.shape[1], recentre_from, predictions,
+                                                   return_inverse, False)
+    d.front.quantization_size = float(res)
+    m = coords4.shape[0]
+    ys = [torch.empty((m, mod.final.out_channels), dtype=torch.float32, device=dev) for mod in mods]
+    M = int(max_candidates)
+    host = _sep_host(dev, K, M)
+    _fill_scene_desc(d.scene, mods[0], hv, None, None, None, res, policy, pieces, max(max(mod.PLANES) for mod in mods), log_scale)
+    alive.append(_fill_separate_desc(d.scene, host, progs, table, G, ys, decode_kw, overlap_threshold, events))
+    ws = _call_points(L.cv_detect_points_separate_f32, "cv_detect_points_separate_f32", d, r, dev, "scene_call_separate",
+                      host["ws_hint"])
+    del alive
+    n = int(r.n)
+    host["ws_hint"] = max(host["ws_hint"], int(r.scene.needed_ws_bytes))
+    coords4, index, ys = coords4[:n], index[:n], [y[:n] for y in ys]
+    tail = (index, inverse) if return_inverse else (index,)
+    if keep is not None:
+        keep.update(range_flag=int(r.scene.range_flag), needed_ws_bytes=int(r.scene.needed_ws_bytes), coords4=coords4)
+    if r.scene.range_flag or any(r.scene.truncated[k] for k in range(K)):
+        view = lambda ptr, shape: _device_view(ptr, shape, torch.float32, dev, ws)
+        pred = None
+        if predictions is not None:
+            pred = (view(r.d_xyz_in, (K, n, 3)), view(r.d_scale_in, (K, n, 3)), view(r.d_prob_in, (K, n)))
+        return (detect_scene_separate_c(models, hv, coords4, view(r.d_feats, (n, d.front.in_channels)), res, predictions=pred,
+                                        policy=policy, keep=keep, events=events, log_scale=log_scale,
+                                        overlap_threshold=overlap_threshold, max_candidates=M, models_per_pass=models_per_pass,
+                                        **decode_kw),) + tail
+    return (_separate_results(host, r.scene, keep, categories, ys, n, dev, ws),) + tail
 
 
 def last_scene_host_us(dev=None):

@@ -40,8 +40,10 @@ extern "C" {
  *    cv_scene_maps.win, the win_levels arguments and cv_net_win_levels.
  * 4: cv_sp_scene_plan_layout, cv_sp_scene_plan_slots, cv_sp_scene_conv_workspace_bytes (additive: no struct or signature moved).
  * 5: the model axis - cv_net_run_models_f32 with its size / table helpers, cv_head_separate_models_f32,
- *    cv_scene_separate_desc.models_per_pass / d_model_params (appended: a zero-initialised descriptor runs as before). */
-#define CV_ABI_VERSION 5
+ *    cv_scene_separate_desc.models_per_pass / d_model_params (appended: a zero-initialised descriptor runs as before).
+ * 6: raw clouds - cv_sp_voxel_rows_f32 (cv_gather_job), cv_detect_points_f32, cv_detect_points_separate_f32 with their
+ *    descriptors / results and the cv_sizeof_* helpers (additive: no struct or signature moved). */
+#define CV_ABI_VERSION 6
 int cv_abi_version(void);
 const char* cv_last_error(void);
 
@@ -228,6 +230,28 @@ int cv_sp_quantize_f32(const float* d_points, long long m, long long ld, float q
 int cv_sp_quantize_f64(const double* d_points, long long m, long long ld, double quantization_size, int floor_only,
                        const long long* h_offsets, int n_clouds, int32_t* d_coords4, int32_t* d_index, int32_t* d_inverse,
                        int32_t* d_counts, int32_t* h_counts, void* d_ws, size_t ws_bytes, void* stream);
+
+/* What a scene needs from the voxeliser's outputs, in ONE launch: the world points of the voxels and up to
+ * CV_GATHER_MAX_JOBS row gathers by the first-point index (features, raw-point-aligned predictions, labels).
+ *   d_coords4 [n][4], d_index [n]  as cv_sp_quantize_* wrote them (d_coords4 may be NULL without d_points_out, d_index without jobs)
+ *   d_points_out [n][3] or NULL    points[i][k] = float(coords4[i][1 + k]) * res: the int32 -> fp32 conversion and ONE fp32
+ *                                  multiply by `res` (what the scene calls read as cv_scene_desc.d_points)
+ *   jobs [n_jobs]                  host array, carried in the kernel arguments (no device table, no copy):
+ *                                  dst[i][0:width] = src[index[i]][0:width], rows of 4-byte words moved as words - fp32 payloads
+ *                                  (NaNs included) and int32 values come through bit for bit.  src_ld / dst_ld: row strides in
+ *                                  words (>= width; destination words beyond `width` are left alone).  recentre_from >= 0:
+ *                                  columns >= recentre_from are fp32 and written as x * 2 - 1 (the colour recentre of
+ *                                  eval_joint.py:167-168; x * 2 is exact: one rounding); -1: none.
+ * Every argument is validated before the first device call.  Asynchronous on `stream`. */
+#define CV_GATHER_MAX_JOBS 8
+typedef struct cv_gather_job {
+    const void* d_src; long long src_ld;
+    void* d_dst; long long dst_ld;
+    int width;
+    int recentre_from;
+} cv_gather_job;
+int cv_sp_voxel_rows_f32(const int32_t* d_coords4, const int32_t* d_index, long long n, float res, float* d_points_out,
+                         const cv_gather_job* jobs, int n_jobs, void* stream);
 
 /* Spatial row order of a coordinate set (what the fused network runs on; replaces the sort of Morton keys by the
  * caller): stable sort on (batch index, Z-order of the 2^shift cubes), rows of one cube in the caller's order.
@@ -754,6 +778,61 @@ typedef struct cv_scene_separate_result {
     float host_us[4];                          /* plan + wait, network enqueue, heads + vote enqueue, decode + wait + NMS */
 } cv_scene_separate_result;
 int cv_detect_scene_separate_f32(const cv_scene_separate_desc* desc, cv_scene_separate_result* result, void* stream);
+
+/* ------------------------------------------------------------------------ *
+ * A scene from a RAW point cloud in ONE call: voxelise (cv_sp_quantize_f32 / _f64), gather what the scene needs by the
+ * first-point index (ONE cv_sp_voxel_rows_f32 launch in joint mode; separate mode: one per 8 gather jobs, 1 + 3 K jobs), then
+ * cv_detect_scene_f32 / cv_detect_scene_separate_f32 on the gathered arrays - the same launches as the three pieces issued by
+ * the caller, so every output is the same bits.  The descriptor EMBEDS the scene descriptor unchanged behind a raw-cloud front.
+ * In `scene`, d_coords4, n, d_feats, feats_ld, d_points and the d_*_in predictions must be NULL / 0 (the call fills a private
+ * copy; scene.res is taken from quantization_size), everything else is as for the scene call, with two differences:
+ *   - d_out_feats has room for M rows (front.m): the voxel count is not known before the call; result.n rows are written;
+ *   - d_ws also holds the front's scratch, carved from its head (quantise workspace, two count words, [m][in_channels]
+ *     features, [m][3] points, the gathered predictions; 256-byte aligned carves); the rest is passed on to the scene call.
+ *     needed_ws_bytes is the sum of both parts, also after CV_ENOMEM from either; the voxelisation is bit-reproducible, so is
+ *     the repeat on a larger workspace.
+ * The host waits THREE times: for the voxel count (the row count n is a host argument of every plan kernel; carrying it on the
+ * device through them is not done here), the level counts and the decode results.  events[0] is recorded in front of the
+ * voxelisation, the other events and host_us are the scene call's.  Rejected points (cv_sp_quantize_*: a non-finite
+ * component, a voxel outside the key window): CV_EINVAL, result.rejected holds the count, nothing further is launched.
+ * Every field of the front is validated before the first device call.
+ * ------------------------------------------------------------------------ */
+typedef struct cv_points_front {
+    const void* d_raw_points; long long m, points_ld; int points_f64;   /* [m][points_ld] fp32, or fp64 when points_f64 != 0, as cv_sp_quantize_* */
+    double quantization_size;                                            /* voxel edge; also the scene's res (as float) */
+    const float* d_raw_feats; long long raw_feats_ld; int in_channels;   /* [m][raw_feats_ld], the first in_channels columns are the network's input */
+    int recentre_from;                                                   /* cv_gather_job.recentre_from of the features; -1: none */
+    /* optional raw-point-aligned predictions fed to vote + decode (NULL = the network's; all or none): [m][3], [m][3], [m], [m];
+     * separate mode: [K][m][3], [K][m][3], [K][m] and d_raw_class NULL */
+    const float* d_raw_xyz; const float* d_raw_scale; const float* d_raw_prob; const int32_t* d_raw_class;
+    /* the voxeliser's outputs, caller's buffers: [m][4], [m], [m] (d_inverse may be NULL); the first result.n rows of d_coords4 / d_index */
+    int32_t* d_coords4; int32_t* d_index; int32_t* d_inverse;
+} cv_points_front;
+typedef struct cv_points_desc { cv_points_front front; cv_scene_desc scene; } cv_points_desc;
+typedef struct cv_points_separate_desc { cv_points_front front; cv_scene_separate_desc scene; } cv_points_separate_desc;
+typedef struct cv_points_result {
+    cv_scene_result scene;             /* needed_ws_bytes: front + scene call */
+    long long n;                       /* voxels = rows of the scene */
+    int rejected;                      /* cv_sp_quantize_*'s count; != 0: CV_EINVAL */
+    float host_us_front;               /* host microseconds of carve + voxelisation (its wait included) + gather enqueue */
+    size_t front_ws_bytes;             /* the head of d_ws the front took */
+    /* device views into d_ws, valid until the next call on the same scratch: gathered features [n][in_channels], world points
+     * [n][3], predictions (NULL when none were given) */
+    float* d_feats; float* d_points; float* d_xyz_in; float* d_scale_in; float* d_prob_in; int32_t* d_class_in;
+} cv_points_result;
+typedef struct cv_points_separate_result {
+    cv_scene_separate_result scene;
+    long long n; int rejected; float host_us_front; size_t front_ws_bytes;
+    float* d_feats; float* d_points; float* d_xyz_in; float* d_scale_in; float* d_prob_in;      /* predictions [K][n][3], [K][n][3], [K][n] */
+} cv_points_separate_result;
+int cv_detect_points_f32(const cv_points_desc* desc, cv_points_result* result, void* stream);
+int cv_detect_points_separate_f32(const cv_points_separate_desc* desc, cv_points_separate_result* result, void* stream);
+/* sizeof of the structures above as the LIBRARY was compiled (a binding that mirrors them field by field compares) */
+size_t cv_sizeof_gather_job(void);
+size_t cv_sizeof_points_desc(void);
+size_t cv_sizeof_points_separate_desc(void);
+size_t cv_sizeof_points_result(void);
+size_t cv_sizeof_points_separate_result(void);
 
 #ifdef __cplusplus
 }

@@ -6,8 +6,8 @@ decode -> NMS per scene, then mAP @0.25 / @0.5.  argparse instead of hydra (abse
 
 --teacher feeds the vote/decode stage with predictions synthesised from the labels (there is no trained
 checkpoint offline); the network forward still runs.
---raw-points (synthetic scenes only): every scene is a RAW cloud of M surface samples (default 300000) that
-pipeline.detect_points voxelises on the device before the scene runs.
+--raw-points (synthetic scenes only): every scene is a RAW cloud of M surface samples (default 300000) that goes through
+pipeline.detect_points_c: voxelised on the device, gathered (with the colour recentre) and detected in one C call.
 """
 import argparse
 import os
@@ -48,20 +48,26 @@ def evaluate(model, dataset, res=0.03, teacher=False, nclasses=9, device="cuda")
     return {thr: calc_map.compute_map(pred_map_cls, gt_map_cls, thr) for thr in (0.25, 0.5)}
 
 
-def evaluate_raw(model, n_scenes, n_samples, seed0=100, res=0.03, teacher=False, nclasses=9, device="cuda"):
-    """the synthetic evaluation from raw clouds: voxelised on the device by pipeline.detect_points"""
+def evaluate_raw(model, n_scenes, n_samples, seed0=100, res=0.03, teacher=False, nclasses=9, device="cuda", detections=None,
+                 **scene_kw):
+    """the synthetic evaluation from raw clouds: one C call per scene (pipeline.detect_points_c voxelises, gathers - the
+    colour recentre of eval_joint.py:167-168 in the gather - and detects).  ``detections`` (a dict) receives every scene's
+    detection list; ``scene_kw`` goes to make_raw_scene / detect_points_c (room=..., thresh_high=...)."""
     hv = HoughVoting(res)
     pred_map_cls, gt_map_cls = {}, {}
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    raw_kw = {k: scene_kw.pop(k) for k in ("room", "n_boxes", "margin", "box_scale") if k in scene_kw}
     for index in range(n_scenes):
-        raw = make_raw_scene(seed0 + index, n_samples)
+        raw = make_raw_scene(seed0 + index, n_samples, **raw_kw)
         id_scan = "synth%04d" % (seed0 + index)
         pred = tuple(t(a) for a in synth_predictions(raw)) if teacher else None
-        dets = pipeline.detect_points(model, hv, t(raw.points), t(raw.feats) * 2.0 - 1.0, res, predictions=pred,
-                                      nclasses=nclasses)[0]
+        dets = pipeline.detect_points_c(model, hv, t(raw.points), t(raw.feats), res, predictions=pred, recentre_from=0,
+                                        nclasses=nclasses, **scene_kw)[0]
         pred_map_cls[id_scan] = dets
         lines = ["%f %f %f %f %f %f %f %d" % tuple(list(b[:7]) + [int(b[7])]) for b in raw.boxes]
         gt_map_cls[id_scan] = [(c, calc_map.gt_box(*p)) for c, p in parse_gt_lines(lines)]
+    if detections is not None:
+        detections.update(pred_map_cls)
     return {thr: calc_map.compute_map(pred_map_cls, gt_map_cls, thr) for thr in (0.25, 0.5)}
 
 
@@ -73,7 +79,7 @@ def main():
     ap.add_argument("--teacher", action="store_true")
     ap.add_argument("--config", default=None, help="the reference's config.yaml: evaluate on real ScanNet/Scan2CAD files")
     ap.add_argument("--raw-points", type=int, nargs="?", const=300000, default=0, metavar="M",
-                    help="synthetic scenes as raw clouds of M samples, voxelised on the device (pipeline.detect_points)")
+                    help="synthetic scenes as raw clouds of M samples: voxelise, gather and detect in one C call (pipeline.detect_points_c)")
     a = ap.parse_args()
     if a.raw_points and a.config:
         ap.error("--raw-points runs on the synthetic scenes only")

@@ -4,10 +4,13 @@ models on one scan -> ONE scene call (plan once, nine networks, nine heads, one 
 axis, NMS per category) per scene, then mAP @0.25 / @0.5.  argparse instead of hydra (absent here).
 
     python scripts/eval_separate.py [--scenes 4] [--points 80000] [--weights-dir DIR] [--teacher] [--config config.yaml]
+                                    [--raw-points [M]]
 
 --weights-dir holds one state dict per category, DIR/<category>.pth (reference checkpoints are loaded through
 minkunet.load_reference_checkpoint).  --teacher feeds the vote/decode stage with per-category predictions synthesised from
 the labels (there is no trained checkpoint offline); the networks still run.
+--raw-points (synthetic scenes only): every scene is a RAW cloud of M surface samples (default 300000) that goes through
+pipeline.detect_points_separate_c: voxelised on the device, gathered and detected in one C call.
 """
 import argparse
 import os
@@ -22,7 +25,8 @@ from canonicalvoting_amd.data import (ScanNetXYZProbMultiDataset, SyntheticScanD
                                      load_config)
 from canonicalvoting_amd.hough import HoughVoting  # noqa: E402
 from canonicalvoting_amd.minkunet import MinkUNet34C, load_reference_checkpoint  # noqa: E402
-from canonicalvoting_amd.synth import synth_predictions  # noqa: E402
+from canonicalvoting_amd.data import parse_gt_lines  # noqa: E402
+from canonicalvoting_amd.synth import make_raw_scene, synth_predictions  # noqa: E402
 
 
 def teacher_predictions(scene, categories, device):
@@ -50,7 +54,23 @@ def evaluate(models, dataset, res=0.03, teacher=False, device="cuda", models_per
     return {thr: calc_map.compute_map(pred_map_cls, gt_map_cls, thr) for thr in (0.25, 0.5)}
 
 
-def main():
+def evaluate_raw(models, n_scenes, n_samples, seed0=100, res=0.03, teacher=False, device="cuda", models_per_pass=None):
+    """the synthetic evaluation from raw clouds: one C call per scene (pipeline.detect_points_separate_c)"""
+    hv = HoughVoting(res)
+    pred_map_cls, gt_map_cls = {}, {}
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    for index in range(n_scenes):
+        raw = make_raw_scene(seed0 + index, n_samples)
+        id_scan = "synth%04d" % (seed0 + index)
+        pred = teacher_predictions(raw, list(models), device) if teacher else None
+        pred_map_cls[id_scan] = pipeline.detect_points_separate_c(models, hv, t(raw.points), t(raw.feats), res, predictions=pred,
+                                                                  recentre_from=0, models_per_pass=models_per_pass)[0]
+        lines = ["%f %f %f %f %f %f %f %d" % tuple(list(b[:7]) + [int(b[7])]) for b in raw.boxes]
+        gt_map_cls[id_scan] = [(c, calc_map.gt_box(*p)) for c, p in parse_gt_lines(lines)]
+    return {thr: calc_map.compute_map(pred_map_cls, gt_map_cls, thr) for thr in (0.25, 0.5)}
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", type=int, default=4)
     ap.add_argument("--points", type=int, default=80000)
@@ -61,7 +81,17 @@ def main():
     ap.add_argument("--models-per-pass", type=int, default=0,
                     help="G >= 1: the networks run batched over a model axis, G per pass (same bits, fewer launches, G arenas of "
                          "scratch); 0: one network after another")
+    ap.add_argument("--raw-points", type=int, nargs="?", const=300000, default=0, metavar="M",
+                    help="synthetic scenes as raw clouds of M samples: voxelise, gather and detect in one C call "
+                         "(pipeline.detect_points_separate_c)")
+    return ap
+
+
+def main():
+    ap = build_parser()
     a = ap.parse_args()
+    if a.raw_points and a.config:
+        ap.error("--raw-points runs on the synthetic scenes only")
     cfg = load_config(a.config, category="all") if a.config else None
     models = {}
     for c in a.categories:
@@ -72,6 +102,8 @@ def main():
     if cfg:
         res = evaluate(models, ScanNetXYZProbMultiDataset(cfg, training=False, augment=False), res=cfg.scannet_res,
                        models_per_pass=a.models_per_pass)
+    elif a.raw_points:
+        res = evaluate_raw(models, a.scenes, a.raw_points, seed0=100, teacher=a.teacher, models_per_pass=a.models_per_pass)
     else:
         res = evaluate(models, SyntheticScanDataset(a.scenes, a.points, seed0=100), teacher=a.teacher, models_per_pass=a.models_per_pass)
     for thr, r in res.items():
