@@ -35,7 +35,7 @@ def _sources():
     env = lambda k: os.environ.get(k, "").split()
     return {
         "cv_host.cpp": STRICT,
-        "hv_vote.hip": STRICT + env("CV_HV_DEFS"),       # tile-shape experiments (-DHV_TX=16 -DHV_TW=8)
+        "hv_vote.hip": STRICT + env("CV_HV_DEFS"),       # extra -D flags of an experiment (the file reads none today)
         "hv_decode.hip": STRICT + env("CV_DEC_DEFS"),    # greedy-walk experiments (-DDEC_BLOCKED=0)
         "sparse_coords.hip": [],
         "sparse_conv.hip": env("CV_SC_DEFS"),            # kernel experiments (-DCV_WP_NPRE=27)

@@ -16,14 +16,18 @@
 //            instead of N threads (79 blocks at N=80k cannot fill 256 CUs).
 //   tiles  : on-chip accumulation.  Every vote of a point has the same y, so points
 //            are counting-sorted by their vote's y cell (80k keys, not 9.6M).  One
-//            workgroup owns a 32x32 (x,z) tile of ONE y plane in LDS (6 channels,
-//            24 KB), pulls the points of y-bins {y-1, y}, culls them with a
-//            ring-vs-tile test into one survivor list of the workgroup (ballot +
-//            mbcnt, one LDS reservation per hand-out), computes the arcs with one
-//            survivor per lane, expands survivors x rotations densely over all lanes,
-//            wave-compacts the votes that land in the tile, and drains them with LDS
-//            fixed-point atomics.  The tile is then normalised and stored once: no
-//            memset, no global atomics, no second pass over the 63 MB grid.
+//            workgroup of eight waves owns a 16 x 32-cell (x,z) tile of ONE y plane:
+//            six channels of 64-bit fixed-point accumulators, one survivor list, the
+//            waves' vote queues and the rotation table - 68 KB of LDS, two workgroups
+//            per CU.  It works through the points of y-bins {y-1, y} (the records
+//            streamed, or this tile's work lists on large grids) in rounds of three
+//            phases over ONE survivor list of the workgroup: cull (ring-vs-tile test,
+//            ballot + mbcnt, one LDS reservation per hand-out), arcs (one survivor per
+//            lane, workgroup scan of the arc lengths), expand (survivors x rotations
+//            split evenly over all lanes, votes that land in the tile wave-compacted
+//            into a queue and drained 64 at a time with LDS integer atomics).  The
+//            tile is then normalised and stored once: no memset, no global atomics,
+//            no second pass over the 63 MB grid.
 #include "cv_common.h"
 
 #include <atomic>
@@ -31,6 +35,7 @@
 #include <cmath>
 #include <cstddef>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -201,7 +206,7 @@ __global__ __launch_bounds__(256) void hv_normalise(const float* __restrict__ g_
 // ---------------------------------------------------------------------------
 // tiles algorithm
 // ---------------------------------------------------------------------------
-// Tile = HV_TX x 32 cells of one y plane, HV_TW waves per workgroup.
+// Tile = TX x 32 cells of one y plane, TW waves per workgroup.
 // 16 x 32 cells / 8 waves (68 KB of LDS, two workgroups per CU): the fastest shape one scene in flight (0.36 ms) and with
 // scenes in flight (profiles/r3/vote_tile_sweep.txt).  Round 3 found it giving WRONG cells - a few dozen cells of one
 // (plane, tile), weight moved between neighbouring cells - in about a third of the launches that ran while fp16 / bf16
@@ -212,38 +217,23 @@ __global__ __launch_bounds__(256) void hv_normalise(const float* __restrict__ g_
 // co-resident loads and an instruction-class checker: profiles/vote_hammer_probe.py, op_check_probe.py,
 // microbench/lds_hammer.hip, r3/vote_concurrency_findings.txt).  The whole library is built without packed fp32
 // instructions now (csrc/build.py); with that every tile shape is exact under the same load (0 of 400 / 0 of 4800).
-#ifndef HV_TX
-#define HV_TX 16
-#endif
-#ifndef HV_TW
-#define HV_TW 8
-#endif
-#ifndef HV_PART_RECORDS
-#define HV_PART_RECORDS 4096
-#endif
-#ifndef HV_MAX_PARTS
-#define HV_MAX_PARTS 8
-#endif
-constexpr int TX = HV_TX, TZ = 32, TCELLS = TX * TZ;   // TZ = 32 is built into acc_idx
-constexpr int TW = HV_TW;    // waves per workgroup
+constexpr int TX = 16, TZ = 32, TCELLS = TX * TZ;   // tile cells in x / z: the fastest shape of the sweep above; TZ = 32 is built into acc_idx
+constexpr int TW = 8;        // waves per workgroup: same sweep (profiles/r3/vote_tile_sweep.txt), 68 KB of LDS = two workgroups per CU
 constexpr int LQ = TW * 64;  // surviving records per round of the workgroup: one per lane
-#ifndef HV_CULL_BATCH
-#define HV_CULL_BATCH 4
-#endif
-constexpr int CULL_BATCH = HV_CULL_BATCH;     // 64-record chunks a wave culls per hand-out
+constexpr int CULL_BATCH = 4;     // 64-record chunks a wave culls per hand-out: their loads in flight at once, cull 22 % -> 9 % of
+                                  // the wave time against one chunk per hand-out (profiles/r8/vote_dense.txt)
 static_assert(CULL_BATCH >= 1 && CULL_BATCH <= 8, "one carry bit and one record index per sub-chunk and lane");
 constexpr int VQ = 128;      // vote queue entries per wave
 constexpr int MAX_R_TILES = 256;
 static_assert(MAX_R_TILES <= TW * 64, "the rotation table is staged by one load per lane");
-#ifndef HV_LIST_PART_ENTRIES
-#define HV_LIST_PART_ENTRIES 384
-#endif
-#ifndef HV_LIST_CHUNK
-#define HV_LIST_CHUNK 16
-#endif
-constexpr int LIST_CHUNK = HV_LIST_CHUNK;                  // list entries a wave takes per hand-out
+constexpr int LIST_CHUNK = 16;    // list entries of a chunk, the unit the parts of a hot (tile, plane) interleave by: four chunks
+                                  // fill a wave's hand-out (the value of the round-3 work lists; never swept on its own)
 static_assert(64 % LIST_CHUNK == 0, "a wave takes 64 / LIST_CHUNK list chunks per hand-out, one entry per lane");
-constexpr int LIST_PART_ENTRIES = HV_LIST_PART_ENTRIES;    // work-list entries one part of a hot (tile, plane) takes
+// what a queued vote (TileShared::vq_rec: entry | rot << 9 | (lx + 1) << 17 | (lz + 1) << 23) and drain64 assume
+static_assert(LQ <= 512, "the list entry of a queued vote has 9 bits");
+static_assert(MAX_R_TILES <= 256, "the rotation of a queued vote has 8 bits");
+static_assert(TX + 1 < 64 && TZ + 1 < 64, "lx + 1 and lz + 1 of a queued vote have 6 bits each");
+static_assert(TZ == 32, "acc_idx splits a cell index by >> 5 and & 31");
 
 // y cell of every vote of a point (theta-independent: offset.y = -corr.y, :38-39).
 // Global atomics on a few hot addresses serialise at ~11 ns each on MI355X (measured: 80k
@@ -297,8 +287,8 @@ __global__ __launch_bounds__(PREP_THREADS) void hv_prep_count(
 // Hough peaks concentrate votes: the hottest (tile, plane) of an 80k scene receives ~27x the mean and
 // would take 0.3 ms on one CU.  Planes whose two y-bins hold many points are therefore split into
 // up to MAX_PARTS workgroups per tile (disjoint record chunks), merged by the last arriver.
-constexpr int PART_RECORDS = HV_PART_RECORDS;
-constexpr int MAX_PARTS = HV_MAX_PARTS;
+constexpr int PART_RECORDS = 4096;   // records per part, the floor of cv_hv_set_part_records: fastest with one scene in flight
+constexpr int MAX_PARTS = 8;         // against 2048 / 8192 records and 16 parts (profiles/r1/vote_tile_sweep.txt, r5/vote_parts.txt)
 
 // (round 3: the three scans used to be Hillis-Steele passes over 1024 LDS slots with two workgroup barriers per step -
 // sixty barriers for Y = 88 bins, 7.5 us; they are independent, so three waves run one wave-level scan each: 64 bins per step)
@@ -568,10 +558,8 @@ __global__ __launch_bounds__(1024) void hv_list_scan(const int* __restrict__ lis
 // ceil(weight / PART_VOTES) items for the others, weight = summed arc lengths of the rings that reach the tile in the
 // plane's two bins (hv_list_pass<false>); parts merge through `partials` slots handed out by the same scan.
 //   item = (plane, tile, part | parts << 8, first partial slot of the (plane, tile))
-#ifndef HV_PART_VOTES
-#define HV_PART_VOTES 32768
-#endif
-constexpr int PART_VOTES = HV_PART_VOTES;
+constexpr int PART_VOTES = 32768;    // arc steps per part: 64 per lane of the workgroup (set with the round-3 queue on the 300k-point
+                                     // scene, 2.01 -> 1.32 ms for the vote stage; never swept on its own)
 constexpr int QUEUE_MAX_PARTS = 32;
 
 __global__ __launch_bounds__(1024) void hv_build_queue(const int* __restrict__ tile_w, int Y, int ntiles, int max_items,
@@ -580,11 +568,10 @@ __global__ __launch_bounds__(1024) void hv_build_queue(const int* __restrict__ t
     tile_w = cat_ws(tile_w, ks_ws); list_ctl = cat_ws(list_ctl, ks_ws); items = cat_ws(items, ks_ws);
     __shared__ unsigned long long s[1024];
     __shared__ unsigned long long carry_s;
-    __shared__ int single_s;
     const int total = Y * ntiles;
     // pass 0 sizes the parts by weight; when the items or the partial slots would not fit, pass 1 gives every tile one part
     for (int pass = 0; pass < 2; ++pass) {
-        if (threadIdx.x == 0) { carry_s = 0ull; single_s = pass; }
+        if (threadIdx.x == 0) carry_s = 0ull;
         __syncthreads();
         for (int base = 0; base < total; base += 1024) {
             const int i = base + threadIdx.x;
@@ -642,40 +629,19 @@ __device__ __forceinline__ int lanes_below(uint64_t mask) {
 // rot / scale quotients lose digits; the reference's own fp32 atomics lose ~1e-7 relative per add everywhere).
 constexpr double FX_SCALE = 68719476736.0;            // 2^36
 constexpr double FX_MAGIC = 6755399441055744.0;       // 1.5 * 2^52: (x*2^36 + MAGIC) has round(x*2^36) in its low bits
-// round(v * 2^36) to nearest even without a floating-point instruction wider than the input (experiment HV_INT_FX:
-// are the f64 conversions what concurrent matrix kernels disturb?); exact for every finite v with |v| < 2^26
-__device__ __forceinline__ unsigned long long fx_from_float_int(float v) {
-    const unsigned b = __float_as_uint(v);
-    const int e = (int)((b >> 23) & 255u);
-    if (e == 0) return 0ull;                                  // zero / fp32 denormal: far below one quantum
-    unsigned long long m = (unsigned long long)((b & 0x7fffffu) | 0x800000u);
-    const int sh = e - 114;                                   // value = m * 2^(e - 150); times 2^36
-    unsigned long long q;
-    if (sh >= 0) q = sh < 40 ? (m << sh) : (m << 39);
-    else if (sh <= -26) q = 0ull;
-    else {
-        const int r = -sh;
-        const unsigned long long half = 1ull << (r - 1), rem = m & ((1ull << r) - 1ull);
-        q = m >> r;
-        if (rem > half || (rem == half && (q & 1ull))) ++q;
+// round(v * 2^36) as a two's-complement word
+template <bool SMALL>
+__device__ __forceinline__ unsigned long long fx_from_float(float v) {
+    if (SMALL) {                              // the magic-number conversion holds for |v * 2^36| < 2^51
+        const double d = __builtin_fma((double)v, FX_SCALE, FX_MAGIC);
+        return (unsigned long long)__double_as_longlong(d) - (unsigned long long)__double_as_longlong(FX_MAGIC);
     }
-    return (b >> 31) ? (0ull - q) : q;
+    // huge contributions (a diverged scale head): exact up to 6e7, clamped beyond
+    return (unsigned long long)__double2ll_rn((double)fminf(fmaxf(v, -6.0e7f), 6.0e7f) * FX_SCALE);
 }
 template <bool SMALL>
 __device__ __forceinline__ void lds_add(unsigned long long* p, float v) {
-    unsigned long long q;
-#ifdef HV_INT_FX
-    q = fx_from_float_int(SMALL ? v : fminf(fmaxf(v, -6.0e7f), 6.0e7f));
-    __hip_atomic_fetch_add(p, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    return;
-#endif
-    if (SMALL) {                              // the magic-number conversion holds for |v * 2^36| < 2^51
-        const double d = __builtin_fma((double)v, FX_SCALE, FX_MAGIC);
-        q = (unsigned long long)__double_as_longlong(d) - (unsigned long long)__double_as_longlong(FX_MAGIC);
-    } else {                                  // huge contributions (a diverged scale head): exact up to 6e7, clamped beyond
-        q = (unsigned long long)__double2ll_rn((double)fminf(fmaxf(v, -6.0e7f), 6.0e7f) * FX_SCALE);
-    }
-    __hip_atomic_fetch_add(p, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(p, fx_from_float<SMALL>(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 __device__ __forceinline__ double fx_value(unsigned long long q) { return (double)(long long)q * (1.0 / FX_SCALE); }
 // The objectness weight - the channel that is thresholded, arg-maxed and defines the touched-cell set - accumulated in
@@ -686,26 +652,9 @@ __device__ __forceinline__ double fx_value(unsigned long long q) { return (doubl
 // to zero (it adds one quantum, 1.5e-11), so a cell is non-zero exactly when the reference's fp32 sum is.
 template <bool SMALL>
 __device__ __forceinline__ void lds_add_obj(unsigned long long* p, float v) {
-    unsigned long long q;
-#ifdef HV_INT_FX
-    q = fx_from_float_int(SMALL ? v : fminf(fmaxf(v, -6.0e7f), 6.0e7f));
+    unsigned long long q = fx_from_float<SMALL>(v);
     if (q == 0ull && v != 0.f) q = v > 0.f ? 1ull : ~0ull;
     __hip_atomic_fetch_add(p, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    return;
-#endif
-    if (SMALL) {
-        const double d = __builtin_fma((double)v, FX_SCALE, FX_MAGIC);
-        q = (unsigned long long)__double_as_longlong(d) - (unsigned long long)__double_as_longlong(FX_MAGIC);
-    } else {
-        q = (unsigned long long)__double2ll_rn((double)fminf(fmaxf(v, -6.0e7f), 6.0e7f) * FX_SCALE);
-    }
-    if (q == 0ull && v != 0.f) q = v > 0.f ? 1ull : ~0ull;
-    __hip_atomic_fetch_add(p, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-// value of accumulator word i of the [6][TCELLS] tile (every channel in 2^-36 fixed point)
-__device__ __forceinline__ double acc_value(unsigned long long q, int i) {
-    (void)i;
-    return fx_value(q);
 }
 
 // LDS layout of the tile accumulators: word of (channel ch, cell (cx, cz)) = ch * ACC_CH + cx * ACC_PITCH + cz.
@@ -734,9 +683,6 @@ struct TileShared {
     int wtot[TW];              // summed arc lengths of each wave's 64 list entries (workgroup scan of phase B)
     int list_len;              // entries reserved in the list this round (may run past LQ: the surplus is carried over)
     int more;                  // a wave stopped for lack of room: another round follows
-#ifdef HV_LDS_PAD
-    char lds_pad[HV_LDS_PAD];  // experiment: LDS the workgroup does not use, to control what else fits on its CU
-#endif
 };
 
 template <bool SMALL>
@@ -791,9 +737,6 @@ __device__ __forceinline__ void drain64(TileShared& sh, int wave, int slot, bool
 }
 
 __device__ __forceinline__ void wave_sync_lds() {
-#ifdef HV_STRONG_WAVE_SYNC
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -862,15 +805,13 @@ __device__ __forceinline__ void edge_arc(float ux, float uz, float r, float a0, 
     }
 }
 
-// VARIANT (ablations for profiling only): 0 full, 1 no LDS atomics, 2 no dense phase, 3 no record streaming
-template <int VARIANT, bool QUEUE>
+template <bool QUEUE>
 __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
     int R, float res, F3 corner, I3 dims, const float2* __restrict__ tab,
     const int* __restrict__ ystart, const int4* __restrict__ items, const float* __restrict__ rec,
     int64_t rec_stride, int tiles_x, int tiles_z, unsigned long long* __restrict__ partials,
     int* __restrict__ arrivals, float* __restrict__ g_obj, float* __restrict__ g_rot,
-    float* __restrict__ g_scale, unsigned long long* __restrict__ prof,
-    const int* __restrict__ list_ctl, const int* __restrict__ list_start, const int* __restrict__ list_cnt,
+    float* __restrict__ g_scale, const int* __restrict__ list_ctl, const int* __restrict__ list_start, const int* __restrict__ list_cnt,
     const int2* __restrict__ entries, int list_mode /* 1: stream the bins, 2: work lists */,
     const int4* __restrict__ q_info, CatStride ks) {
     ystart = cat_ws(ystart, ks.ws); items = cat_ws(items, ks.ws); rec = cat_ws(rec, ks.ws);
@@ -880,17 +821,6 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
     g_obj = cat_el(g_obj, ks.cells); g_rot = cat_el(g_rot, 2 * ks.cells); g_scale = cat_el(g_scale, 3 * ks.cells);
     __shared__ TileShared sh;
     __shared__ int last_flag;
-    // VARIANT 4: shader-clock ticks per phase, summed over waves into prof[0..7], prof[8] = waves
-    unsigned long long pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long pt0 = VARIANT == 4 ? __builtin_amdgcn_s_memtime() : 0;
-#define HV_TICK(p)                                                        \
-    do {                                                                  \
-        if (VARIANT == 4) {                                               \
-            const unsigned long long t_ = __builtin_amdgcn_s_memtime();   \
-            pacc[p] += t_ - pt0;                                          \
-            pt0 = t_;                                                     \
-        }                                                                 \
-    } while (0)
     const int X = dims.x, Y = dims.y, Z = dims.z;
     const int ntiles = tiles_x * tiles_z;
     // QUEUE: one work item per workgroup (hv_build_queue; large grids) - ONE 16-byte load says which (plane, tile,
@@ -926,7 +856,7 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
     }
     // list_mode 2: work lists of this tile in the two y-bins (hv_list_pass; list_ctl[1] != 0: they overflowed, stream the
     // bins instead)
-    const bool use_list = QUEUE && VARIANT != 3 && list_mode == 2 && list_ctl[1] == 0;      // (the queue launch is the list launch)
+    const bool use_list = QUEUE && list_mode == 2 && list_ctl[1] == 0;      // (the queue launch is the list launch)
     int lbeg[2] = {0, 0}, llen[2] = {0, 0};
     if (use_list) {
 #pragma unroll
@@ -939,26 +869,13 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
         }
     }
 
-#ifdef HV_POISON      // debug: stale-LDS hunt (an uninitialised read shows up as a changed result)
-    {
-        unsigned* w = reinterpret_cast<unsigned*>(&sh);
-        const int lo[5] = {(int)(offsetof(TileShared, pq) / 4), (int)(offsetof(TileShared, arc_start) / 4),
-                           (int)(offsetof(TileShared, arc_cum) / 4), (int)(offsetof(TileShared, vq_rec) / 4),
-                           (int)(offsetof(TileShared, tab) / 4)};
-        const int hi[5] = {lo[1], lo[2], lo[3], lo[4], (int)(offsetof(TileShared, next_chunk) / 4)};
-        for (int k = 0; k < 5; ++k)
-            if ((HV_POISON >> k) & 1)
-                for (int i = lo[k] + threadIdx.x; i < hi[k]; i += TW * 64) w[i] = 0x7fc12345u + i * 2654435761u;
-        __syncthreads();
-    }
-#endif
     // first and last record (list entry) of the two bins and the rotation table: loads issued before the accumulators are
     // zeroed, so that their latency passes under the zeroing and not in front of phase A
     int bin_beg[2], bin_end[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const int s = y - 1 + k;
-        const bool valid = s >= 0 && s <= Y - 2 && VARIANT != 3;
+        const bool valid = s >= 0 && s <= Y - 2;
         bin_beg[k] = !valid ? 0 : (use_list ? lbeg[k] : ystart[s]);
         bin_end[k] = !valid ? 0 : (use_list ? lbeg[k] + llen[k] : ystart[s + 1]);
     }
@@ -968,7 +885,6 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
     if (threadIdx.x < 2) sh.next_chunk[threadIdx.x] = 0;
     if (threadIdx.x == 2) { sh.list_len = 0; sh.more = 0; }
     __syncthreads();
-    HV_TICK(0);
 
     // a vote at grid position g touches cells floor(g), floor(g)+1, so it reaches this
     // tile iff g in [x0-1, x0+TX) x [z0-1, z0+TZ); slack covers fp32 rounding of the test.
@@ -1069,8 +985,7 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
                     const float dzf = fmaxf(fabsf(uz[j] - zlo), fabsf(uz[j] - zhi));
                     const float dmin = sqrtf(dxn * dxn + dzn * dzn), dmax = sqrtf(dxf * dxf + dzf * dzf);
                     const float tol = slack + 1e-5f * (r[j] + fabsf(ux[j]) + fabsf(uz[j]));
-                    bool keep = idx[j] < end && (r[j] >= dmin - tol) && (r[j] <= dmax + tol);
-                    if (VARIANT == 2) keep = keep && (ux[j] == 1234.5f);
+                    const bool keep = idx[j] < end && (r[j] >= dmin - tol) && (r[j] <= dmax + tol);
                     mask |= (int)keep << j;
                 }
             }
@@ -1083,11 +998,9 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
             }
         }
         if (more && lane == 0) sh.more = 1;
-        HV_TICK(1);
         __syncthreads();
         const int n = min(sh.list_len, LQ);
         const bool again = sh.more != 0;      // (implies n > 0: room runs out only in a list that holds entries)
-        HV_TICK(3);
         if (n == 0) break;
 
         // ---- phase B: one survivor per lane
@@ -1147,9 +1060,7 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
             if (lane >= off) cum += t;
         }
         if (lane == 63) sh.wtot[wave] = cum;
-        HV_TICK(2);
         __syncthreads();
-        HV_TICK(3);
         if (threadIdx.x == 0) { sh.list_len = 0; sh.more = 0; }      // (every lane has read both; next written after the
                                                                      // barrier that ends the round)
         int items = 0;
@@ -1160,19 +1071,14 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
             items += t;
         }
         if (p < n) sh.arc_cum[p] = cum;
-        HV_TICK(2);
         __syncthreads();
-        HV_TICK(3);
 
         // ---- phase C: slice j walks items [j*S, (j+1)*S): at any step the lanes of a wave sit on different arcs
         // (different cells -> few same-address LDS atomic collisions), and a lane only advances along its arc, so the
         // (entry, step) pair is found by ONE binary search per round.
         const int S = (items + LQ - 1) / LQ;
-#ifdef HV_SLICE_INTERLEAVED
-        const int slice = lane * TW + wave;          // the waves' slices interleave: each wave samples the whole list
-#else
-        const int slice = wave * 64 + lane;          // a wave walks one contiguous run of the list
-#endif
+        const int slice = wave * 64 + lane;          // a wave walks one contiguous run of the list (interleaved slices: no
+                                                     // faster, profiles/r8/vote_dense.txt)
         int it0 = slice * S;
         const int it1 = min(it0 + S, items);
         int e = 0;
@@ -1196,7 +1102,6 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
             epx = sh.pq[0][e]; epz = sh.pq[1][e];
             ecx = sh.pq[2][e]; ecz = sh.pq[3][e];
         }
-        HV_TICK(2);
         for (int step = 0; step < S; ++step, ++it0) {
             bool isvote = false;
             uint32_t vrec = 0;
@@ -1235,29 +1140,21 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
             }
             vq_len += __popcll(mv);
             wave_sync_lds();
-            HV_TICK(4);
             if (vq_len >= 64) {
                 vq_len -= 64;
-                if (VARIANT != 1) drain64(sh, wave, vq_len + lane, true);
-                HV_TICK(5);
+                drain64(sh, wave, vq_len + lane, true);
             }
         }
         // queued votes index this round's list entries: flush before the list is overwritten
         if (vq_len > 0) {
-            if (VARIANT != 1) drain64(sh, wave, lane, lane < vq_len);
-            else if (lane < vq_len)
-                sh.acc[ACC_CH + lane] = (unsigned long long)(sh.vq_rx[wave][lane] + sh.vq_rz[wave][lane] + (float)sh.vq_rec[wave][lane]);
+            drain64(sh, wave, lane, lane < vq_len);
             vq_len = 0;
         }
         wave_sync_lds();
-        HV_TICK(6);
         if (!again) break;
         __syncthreads();
-        HV_TICK(3);
     }
-    HV_TICK(1);
     __syncthreads();
-    HV_TICK(3);
 
     if (nparts > 1) {
         // publish this part's tile as the raw 2^-36 fixed-point words, the last arriver adds the parts as integers: the
@@ -1290,20 +1187,16 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
     // fused normalise (hv_cuda_kernel.cu:112-117) + single store of the tile.  The weight the
     // reference divides by is the fp32 grid value, so round the double sum to float first.
     const int nx = min(TX, X - x0), nz = min(TZ, Z - z0);
-    if (VARIANT == 5) {                       // ablation: no normalise / store
-        if (threadIdx.x == 0) g_obj[((int64_t)x0 * Y + y) * Z + z0] = (float)acc_value(sh.acc[0], 0);
-        return;
-    }
     for (int i = threadIdx.x; i < TCELLS; i += TW * 64) {
         const int lx = i / TZ, lz = i % TZ;
         if (lx < nx && lz < nz)
-            g_obj[((int64_t)(x0 + lx) * Y + y) * Z + z0 + lz] = (float)acc_value(sh.acc[acc_idx(0, i)], 0);
+            g_obj[((int64_t)(x0 + lx) * Y + y) * Z + z0 + lz] = (float)fx_value(sh.acc[acc_idx(0, i)]);
     }
     for (int i = threadIdx.x; i < TCELLS * 2; i += TW * 64) {
         const int cell = i >> 1, j = i & 1;
         const int lx = cell / TZ, lz = cell % TZ;
         if (lx < nx && lz < nz) {
-            const double d = (double)(float)acc_value(sh.acc[acc_idx(0, cell)], 0) + 1e-7;
+            const double d = (double)(float)fx_value(sh.acc[acc_idx(0, cell)]) + 1e-7;
             g_rot[(((int64_t)(x0 + lx) * Y + y) * Z + z0 + lz) * 2 + j] =
                 (float)((double)(float)fx_value(sh.acc[acc_idx(1 + j, cell)]) / d);
         }
@@ -1312,17 +1205,11 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
         const int cell = i / 3, j = i - cell * 3;
         const int lx = cell / TZ, lz = cell % TZ;
         if (lx < nx && lz < nz) {
-            const double d = (double)(float)acc_value(sh.acc[acc_idx(0, cell)], 0) + 1e-7;
+            const double d = (double)(float)fx_value(sh.acc[acc_idx(0, cell)]) + 1e-7;
             g_scale[(((int64_t)(x0 + lx) * Y + y) * Z + z0 + lz) * 3 + j] =
                 (float)((double)(float)fx_value(sh.acc[acc_idx(3 + j, cell)]) / d);
         }
     }
-    HV_TICK(7);
-    if (VARIANT == 4 && lane == 0) {
-        for (int p2 = 0; p2 < 8; ++p2) atomicAdd(&prof[p2], pacc[p2]);
-        atomicAdd(&prof[8], 1ull);
-    }
-#undef HV_TICK
 }
 
 // ---------------------------------------------------------------------------
@@ -1463,14 +1350,9 @@ int check_common(const void* a, const void* b, const void* c, int64_t n, float r
 int64_t tiles_q_bound(int64_t n, int Y) { return (int64_t)Y + (2 * n + PART_RECORDS - 1) / PART_RECORDS; }
 // the launch shape: work lists + work queue where a plane has many tiles (measured, bench vote stage: 300k-point scene,
 // 200 tiles: 2.01 -> 1.32 ms; 80k scene, 66 tiles: 0.37 -> 0.40 ms - the weight pass and the queue build cost more than
-// the tile kernel gains there), the streaming launch below that.  CV_HV_LISTS=1 / 2 forces one of them.
-#ifndef HV_QUEUE_MIN_TILES
-#define HV_QUEUE_MIN_TILES 128      // 16-wide tiles: an 80k-point grid has 66 (streaming launch), a 300k-point grid 190 (work lists)
-#endif
-bool use_queue(int64_t ntiles) {
-    static const int lists_env = getenv("CV_HV_LISTS") ? atoi(getenv("CV_HV_LISTS")) : -1;
-    return lists_env >= 1 ? lists_env == 2 : ntiles >= HV_QUEUE_MIN_TILES;
-}
+// the tile kernel gains there; forced either way in flight: profiles/r3/vote_tile_sweep.txt, r5/knobs_in_flight.txt), the
+// streaming launch below that.  16-wide tiles: an 80k-point grid has 66 tiles, a 300k-point grid 190.
+constexpr int QUEUE_MIN_TILES = 128;
 // work queue: partial-tile slots for the (plane, tile) pairs with more than one part (sum of arc lengths <= about
 // 2 * n * num_rots counting both planes of a vote and the slack steps; twice that again as room) and items = one per
 // (plane, tile) + the extra parts; hv_build_queue falls back to one part per tile if either is exceeded
@@ -1480,8 +1362,74 @@ int64_t queue_max_items(int64_t n, int num_rots, int64_t Y, int64_t ntiles) { re
 // more than every (point, tile) pair; beyond it the tile kernel streams the bins as before
 int64_t list_capacity(int64_t n, int64_t ntiles) { return std::min<int64_t>(n * ntiles, 40 * n + 65536); }
 
-int pick_algo(int algo, int64_t n, int num_rots, const int* dims) {
-    if (algo >= 21 && algo <= 25) return 2;   // profiling ablations of the tiles kernel
+// The workspace of the tile algorithm, stated ONCE: the launch shape, the bounds derived from it and every array of one
+// category's carve, in carve order, each aligned to 256 bytes.  The size query, the category stride, the CV_ENOMEM check, the
+// zero fill and the launches all read this (base = nullptr: sizes only).  The workspace follows the launch shape actually
+// chosen: the streaming launch (80k-point scenes) takes none of the list / queue arrays (zero-length carves, nothing of it
+// reads them; they were > 60 MB of every stream's 100 MB vote scratch until round 4).
+struct TilesLayout {
+    bool queue;                    // work queue + work lists (large grids) or the streaming launch
+    int tiles_x, tiles_z, ntiles;
+    int64_t max_q;                 // streaming launch: (plane, part) slots
+    int64_t max_items, max_slots;  // work queue: items and partial-tile slots
+    int64_t list_cap, max_chunks;  // work lists: entries; chunks of LIST_CHUNK_RECORDS records of one bin
+    int* fy; float* rec;
+    int* list_ctl; int* list_cnt; int* tile_w; int* ycount; int* arrivals;      // zeroed by one fill: see zero_from
+    int* ystart; int* cursor; int* part_start; int4* q_info;
+    unsigned long long* partials;
+    int4* items; int* list_start; int* chunk_start; int* bin_of_chunk; int* chunk_off; int2* entries;
+    int* zero_from;                // list_ctl (queue; list_cnt is zeroed with the rest: the count pass adds to it) or ycount
+    size_t zero_bytes;             // ... up to the end of arrivals (the streaming launch only needs ycount and arrivals zeroed)
+    size_t bytes;                  // end of the last array, rounded up to 256: one category's workspace and the category stride
+};
+TilesLayout tiles_layout(int64_t n, int num_rots, const int* dims, void* base) {
+    TilesLayout L{};
+    const size_t Y = (size_t)dims[1];
+    L.tiles_x = (dims[0] + TX - 1) / TX;
+    L.tiles_z = (dims[2] + TZ - 1) / TZ;
+    const int64_t ntiles = (int64_t)L.tiles_x * L.tiles_z;
+    L.ntiles = (int)ntiles;
+    L.max_q = tiles_q_bound(n, (int)Y);
+    L.max_slots = queue_max_slots(n, num_rots);
+    L.max_items = queue_max_items(n, num_rots, (int64_t)Y, ntiles);
+    L.list_cap = list_capacity(n, ntiles);
+    L.max_chunks = (int64_t)Y + (n + LIST_CHUNK_RECORDS - 1) / LIST_CHUNK_RECORDS;
+    L.queue = ntiles >= QUEUE_MIN_TILES && ntiles <= LIST_MAX_TILES && L.list_cap < (1ll << 31) && L.max_items < (1ll << 31);
+    const size_t q = L.queue ? 1 : 0, planes = Y * (size_t)ntiles;
+    size_t off = 0;
+    auto take = [&](auto*& p, size_t count) {      // the array's first byte
+        off = cv_align_up(off, 256);
+        const size_t at = off;
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(reinterpret_cast<uintptr_t>(base) + at);
+        off += count * sizeof(*p);
+        return at;
+    };
+    take(L.fy, (size_t)n);
+    take(L.rec, (size_t)n * REC_F);
+    const size_t ctl_at = take(L.list_ctl, 64);
+    take(L.list_cnt, q * planes);
+    take(L.tile_w, q * planes);
+    const size_t ycount_at = take(L.ycount, Y);
+    take(L.arrivals, planes);
+    L.zero_from = L.queue ? L.list_ctl : L.ycount;
+    L.zero_bytes = off - (L.queue ? ctl_at : ycount_at);
+    take(L.ystart, Y + 1);
+    take(L.cursor, Y);
+    take(L.part_start, Y + 1);
+    take(L.q_info, (size_t)L.max_q);
+    take(L.partials, (size_t)(L.queue ? L.max_slots : L.max_q * ntiles) * 6 * TCELLS);
+    take(L.items, q * (size_t)L.max_items);
+    take(L.list_start, q * planes);
+    take(L.chunk_start, Y + 1);
+    take(L.bin_of_chunk, (size_t)L.max_chunks);
+    take(L.chunk_off, q * (size_t)L.max_chunks * (size_t)ntiles);
+    take(L.entries, q * (size_t)L.list_cap);
+    L.bytes = cv_align_up(off, 256);
+    return L;
+}
+
+bool algo_ok(int algo) { return algo >= 0 && algo <= 2; }      // include/cv_hip.h: 0 auto, 1 direct, 2 tiles
+int pick_algo(int algo, int64_t n, int num_rots) {
     if (algo == 1 || algo == 2) return algo;
     if (num_rots <= MAX_R_TILES && n < (1ll << 31)) return 2;
     return 1;
@@ -1495,21 +1443,11 @@ size_t cv_hv_minmax_workspace_bytes(void) { return 256 + sizeof(float) * 6 * (MM
 
 int cv_hv_minmax_f32(const float* d_points, int64_t n, float* h_min3, float* h_max3, void* d_ws,
                      size_t ws_bytes, void* stream) {
-    CV_REQUIRE(d_points && h_min3 && h_max3 && d_ws, CV_EINVAL, "null pointer argument");
-    CV_REQUIRE(n > 0, CV_EINVAL, "n must be positive (got %lld)", (long long)n);
-    CV_REQUIRE(ws_bytes >= cv_hv_minmax_workspace_bytes(), CV_ENOMEM, "workspace too small");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    CvCarver cv(d_ws);
-    float* part = cv.take<float>(6 * MM_BLOCKS);
-    float* out = cv.take<float>(6);
-    const int blocks = (int)std::min<int64_t>(MM_BLOCKS, (n + 255) / 256);
-    minmax_partial<<<blocks, 256, 0, st>>>(d_points, n, part);
-    CV_LAUNCH_CHECK();
-    minmax_final<<<1, 256, 0, st>>>(part, blocks, out);
-    CV_LAUNCH_CHECK();
+    CV_REQUIRE(h_min3 && h_max3, CV_EINVAL, "null pointer argument");
     float h[6];
-    CV_HIP_CHECK(hipMemcpyAsync(h, out, sizeof h, hipMemcpyDeviceToHost, st));
-    CV_HIP_CHECK(hipStreamSynchronize(st));
+    const int rc = cv_hv_minmax_async_ex(d_points, n, h, d_ws, ws_bytes, nullptr, nullptr, stream);
+    if (rc) return rc;
+    CV_HIP_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     for (int k = 0; k < 3; ++k) { h_min3[k] = h[k]; h_max3[k] = h[3 + k]; }
     return CV_OK;
 }
@@ -1556,30 +1494,10 @@ int cv_hv_grid_dims_f32(const float h_min3[3], const float h_max3[3], float res,
     return CV_OK;
 }
 
-// work queue + work lists (large grids) or the streaming launch: one decision for the workspace size and the launch
-static bool tiles_queue_mode(int64_t n, int num_rots, int64_t Y, int64_t ntiles, int algo) {
-    return use_queue(ntiles) && ntiles <= LIST_MAX_TILES && list_capacity(n, ntiles) < (1ll << 31) &&
-           queue_max_items(n, num_rots, Y, ntiles) < (1ll << 31) && algo != 23;
-}
-
-// The workspace follows the launch shape actually chosen: the streaming launch (80k-point scenes) carries neither the
-// work lists nor the queue items (they were > 60 MB of every stream's 100 MB vote scratch until round 4).
 size_t cv_hv_forward_workspace_bytes(int64_t n, int num_rots, const int dims[3], int algo) {
-    if (!dims || n <= 0) return 0;
-    if (pick_algo(algo, n, num_rots, dims) == 1) return 256;
-    const size_t Y = (size_t)dims[1];
-    const size_t ntiles = (size_t)((dims[0] + TX - 1) / TX) * (size_t)((dims[2] + TZ - 1) / TZ);
-    const bool queue = tiles_queue_mode(n, num_rots, (int64_t)Y, (int64_t)ntiles, algo);
-    const size_t max_chunks = Y + (size_t)((n + LIST_CHUNK_RECORDS - 1) / LIST_CHUNK_RECORDS);
-    const size_t slots = queue ? (size_t)queue_max_slots(n, num_rots) : (size_t)tiles_q_bound(n, (int)Y) * ntiles;
-    size_t b = 256 * 24 + sizeof(int) * ((size_t)n * (1 + REC_F) + Y * 8 + 16 + 64 + Y * ntiles + max_chunks +
-                                         4 * (size_t)tiles_q_bound(n, (int)Y)) +
-               sizeof(unsigned long long) * slots * 6 * TCELLS;
-    if (queue)
-        b += sizeof(int) * (3 * Y * ntiles + max_chunks * ntiles) +
-             sizeof(int4) * (size_t)queue_max_items(n, num_rots, (int64_t)Y, (int64_t)ntiles) +
-             sizeof(int2) * (size_t)list_capacity(n, (int64_t)ntiles);
-    return b;
+    if (!dims || n <= 0 || !algo_ok(algo)) return 0;
+    if (pick_algo(algo, n, num_rots) == 1) return 256;
+    return tiles_layout(n, num_rots, dims, nullptr).bytes;
 }
 
 // cv_hv_set_kernel_events: the calling thread's next cv_hv_forward_f32 calls record these events directly before and
@@ -1611,18 +1529,14 @@ int cv_hv_set_kernel_events(void* ev_start, void* ev_stop) {
     return CV_OK;
 }
 
-// byte distance of two categories' workspace carves (cv_hv_forward_cat_f32); the last category needs only the single carve
-static size_t cat_ws_stride(int64_t n, int num_rots, const int dims[3], int algo) {
-    return cv_align_up(cv_hv_forward_workspace_bytes(n, num_rots, dims, algo), 256);
-}
-
+// (a multiple of 256: it is also the byte distance of two categories' carves; the last category needs only the single carve)
 size_t cv_hv_forward_cat_workspace_bytes(int64_t n, int num_rots, const int dims[3], int algo, int num_cats) {
-    if (!dims || n <= 0 || num_cats < 1 || num_cats > CV_MAX_CATEGORIES) return 0;
-    return (size_t)(num_cats - 1) * cat_ws_stride(n, num_rots, dims, algo) + cv_hv_forward_workspace_bytes(n, num_rots, dims, algo);
+    if (num_cats < 1 || num_cats > CV_MAX_CATEGORIES) return 0;
+    return (size_t)num_cats * cv_hv_forward_workspace_bytes(n, num_rots, dims, algo);
 }
 
 // K categories over the same scan points and grid (K = 1: cv_hv_forward_f32).  Category k reads d_xyz / d_scale + 3 n k,
-// d_obj + n k and writes the grids + (1, 2, 3) * cells * k; its workspace carve starts cat_ws_stride() * k bytes into d_ws.
+// d_obj + n k and writes the grids + (1, 2, 3) * cells * k; its workspace carve starts TilesLayout::bytes * k bytes into d_ws.
 static int hv_forward_cats(const float* d_points, const float* d_xyz, const float* d_scale, const float* d_obj, int64_t n,
                            float res, int num_rots, const float h_corner3[3], const int dims[3], float* d_grid_obj,
                            float* d_grid_rot, float* d_grid_scale, void* d_ws, size_t ws_bytes, int algo, int K,
@@ -1634,7 +1548,7 @@ static int hv_forward_cats(const float* d_points, const float* d_xyz, const floa
     const F3 corner{h_corner3[0], h_corner3[1], h_corner3[2]};
     const I3 d3{dims[0], dims[1], dims[2]};
     const int64_t cells = (int64_t)dims[0] * dims[1] * dims[2];
-    const int a = pick_algo(algo, n, num_rots, dims);
+    const int a = pick_algo(algo, n, num_rots);
     if (a == 2) CV_REQUIRE(num_rots <= MAX_R_TILES, CV_EINVAL, "tiles algorithm needs num_rots <= %d", MAX_R_TILES);
     if (a == 1) {
         // (not the hot path: the categories one after another)
@@ -1655,110 +1569,53 @@ static int hv_forward_cats(const float* d_points, const float* d_xyz, const floa
         }
         return CV_OK;
     }
-    // (sized by the SAME algo value that decides the launch shape below: ablation algo 23 takes the streaming launch on
-    // grids where algo 2 would take the work queue, and the two carve different workspaces)
-    const int ws_algo = algo == 23 ? 23 : 2;
-    CV_REQUIRE(d_ws && ws_bytes >= cv_hv_forward_cat_workspace_bytes(n, num_rots, dims, ws_algo, K), CV_ENOMEM,
-               "workspace too small for the tiles algorithm");
-    const CatStride ks{K > 1 ? (int64_t)cat_ws_stride(n, num_rots, dims, ws_algo) : 0, n, cells};
     const int Y = dims[1];
-    CvCarver cv(d_ws);
-    int* fy = cv.take<int>(n);
-    float* rec = cv.take<float>((size_t)n * REC_F);
-    const int tiles_x = (dims[0] + TX - 1) / TX, tiles_z = (dims[2] + TZ - 1) / TZ;
-    const int ntiles = tiles_x * tiles_z;
-    const int64_t max_items = queue_max_items(n, num_rots, Y, ntiles), max_slots = queue_max_slots(n, num_rots);
-    const int64_t max_q = tiles_q_bound(n, Y);
-    const int64_t list_cap = list_capacity(n, ntiles);
-    const bool queue = tiles_queue_mode(n, num_rots, Y, ntiles, algo);
-    // the zero-initialised arrays sit next to each other: one fill launch.  The streaming launch takes none of the list /
-    // queue arrays (zero-length carves: nothing of it reads them)
-    int* list_ctl = cv.take<int>(64);
-    int* list_cnt = cv.take<int>(queue ? (size_t)Y * ntiles : 0);      // (zeroed with the rest: the count pass adds to them)
-    int* tile_w = cv.take<int>(queue ? (size_t)Y * ntiles : 0);
-    int* ycount = cv.take<int>(Y);
-    int* arrivals = cv.take<int>((size_t)Y * ntiles);
-    int* ystart = cv.take<int>(Y + 1);
-    int* cursor = cv.take<int>(Y);
-    int* part_start = cv.take<int>(Y + 1);
-    int4* q_info = cv.take<int4>((size_t)max_q);
-    unsigned long long* partials = cv.take<unsigned long long>((size_t)(queue ? max_slots : max_q * ntiles) * 6 * TCELLS);
-    int4* items = cv.take<int4>(queue ? (size_t)max_items : 0);
-    int* list_start = cv.take<int>(queue ? (size_t)Y * ntiles : 0);
-    const int64_t max_chunks = (int64_t)Y + (n + LIST_CHUNK_RECORDS - 1) / LIST_CHUNK_RECORDS;
-    int* chunk_start = cv.take<int>((size_t)Y + 1);
-    int* bin_of_chunk = cv.take<int>((size_t)max_chunks);
-    int* chunk_off = cv.take<int>(queue ? (size_t)max_chunks * ntiles : 0);
-    int2* entries = cv.take<int2>(queue ? (size_t)list_cap : 0);
+    const TilesLayout L = tiles_layout(n, num_rots, dims, d_ws);
+    CV_REQUIRE(d_ws && ws_bytes >= (size_t)K * L.bytes, CV_ENOMEM, "workspace too small for the tiles algorithm");
+    const CatStride ks{K > 1 ? (int64_t)L.bytes : 0, n, cells};
+    const int tiles_x = L.tiles_x, tiles_z = L.tiles_z, ntiles = L.ntiles;
+    const bool queue = L.queue;
     const int list_mode = queue ? 2 : 1;
-    // (the streaming launch only needs ycount and the arrival counters zeroed)
-    int* zero_from = queue ? list_ctl : ycount;
-    const size_t zero_bytes = (size_t)(reinterpret_cast<char*>(arrivals + (size_t)Y * ntiles) - reinterpret_cast<char*>(zero_from));
-    if (K == 1) CV_HIP_CHECK(hipMemsetAsync(zero_from, 0, zero_bytes, st));
+    if (K == 1) CV_HIP_CHECK(hipMemsetAsync(L.zero_from, 0, L.zero_bytes, st));
     else {
-        hv_zero_cat<<<dim3((unsigned)std::min<size_t>((zero_bytes / 4 + 255) / 256, 1024), K), 256, 0, st>>>(zero_from, zero_bytes / 4,
-                                                                                                        ks.ws);
+        hv_zero_cat<<<dim3((unsigned)std::min<size_t>((L.zero_bytes / 4 + 255) / 256, 1024), K), 256, 0, st>>>(L.zero_from,
+                                                                                                          L.zero_bytes / 4, ks.ws);
         CV_LAUNCH_CHECK();
     }
     const unsigned prep_wgs = (unsigned)((n + PREP_THREADS - 1) / PREP_THREADS);
-    hv_prep_count<<<dim3(prep_wgs, K), PREP_THREADS, 0, st>>>(d_points, d_xyz, d_scale, n, res, corner.y, Y, fy, ycount, ks);
+    hv_prep_count<<<dim3(prep_wgs, K), PREP_THREADS, 0, st>>>(d_points, d_xyz, d_scale, n, res, corner.y, Y, L.fy, L.ycount, ks);
     CV_LAUNCH_CHECK();
-    hv_prep_scan<<<dim3(1, K), 256, 0, st>>>(ycount, Y, ystart, cursor, part_start, q_info, (int)max_q, chunk_start, bin_of_chunk,
+    hv_prep_scan<<<dim3(1, K), 256, 0, st>>>(L.ycount, Y, L.ystart, L.cursor, L.part_start, L.q_info, (int)L.max_q, L.chunk_start,
+                                             L.bin_of_chunk,
                                              (int)(t_part_records > 0 ? t_part_records : g_part_records.load(std::memory_order_relaxed)),
                                              ks.ws);
     CV_LAUNCH_CHECK();
-    hv_prep_scatter<<<dim3(prep_wgs, K), PREP_THREADS, 0, st>>>(d_points, d_xyz, d_scale, d_obj, fy, n, Y, res, corner, cursor, rec,
-                                                                 n, ks);
+    hv_prep_scatter<<<dim3(prep_wgs, K), PREP_THREADS, 0, st>>>(d_points, d_xyz, d_scale, d_obj, L.fy, n, Y, res, corner, L.cursor,
+                                                                 L.rec, n, ks);
     CV_LAUNCH_CHECK();
     if (queue) {
-        hv_list_pass<false><<<dim3((unsigned)max_chunks, K), 1024, 0, st>>>(ystart, chunk_start, bin_of_chunk, Y, rec, n, num_rots,
-                                                                             tiles_x, tiles_z, list_ctl, list_cnt, list_start,
-                                                                             chunk_off, entries, tile_w, 1, ks.ws);
+        hv_list_pass<false><<<dim3((unsigned)L.max_chunks, K), 1024, 0, st>>>(L.ystart, L.chunk_start, L.bin_of_chunk, Y, L.rec, n,
+                                                                               num_rots, tiles_x, tiles_z, L.list_ctl, L.list_cnt,
+                                                                               L.list_start, L.chunk_off, L.entries, L.tile_w, 1, ks.ws);
         CV_LAUNCH_CHECK();
-        hv_build_queue<<<dim3(1, K), 1024, 0, st>>>(tile_w, Y, ntiles, (int)max_items, (int)max_slots, list_ctl, items, ks.ws);
+        hv_build_queue<<<dim3(1, K), 1024, 0, st>>>(L.tile_w, Y, ntiles, (int)L.max_items, (int)L.max_slots, L.list_ctl, L.items,
+                                                    ks.ws);
         CV_LAUNCH_CHECK();
-        hv_list_scan<<<dim3(1, K), 1024, 0, st>>>(list_cnt, Y, ntiles, list_cap, list_ctl, list_start, ks.ws);
+        hv_list_scan<<<dim3(1, K), 1024, 0, st>>>(L.list_cnt, Y, ntiles, L.list_cap, L.list_ctl, L.list_start, ks.ws);
         CV_LAUNCH_CHECK();
-        hv_list_pass<true><<<dim3((unsigned)max_chunks, K), 1024, 0, st>>>(ystart, chunk_start, bin_of_chunk, Y, rec, n, num_rots,
-                                                                            tiles_x, tiles_z, list_ctl, list_cnt, list_start,
-                                                                            chunk_off, entries, tile_w, 1, ks.ws);
+        hv_list_pass<true><<<dim3((unsigned)L.max_chunks, K), 1024, 0, st>>>(L.ystart, L.chunk_start, L.bin_of_chunk, Y, L.rec, n,
+                                                                              num_rots, tiles_x, tiles_z, L.list_ctl, L.list_cnt,
+                                                                              L.list_start, L.chunk_off, L.entries, L.tile_w, 1, ks.ws);
         CV_LAUNCH_CHECK();
     }
-    const int64_t wgs = queue ? max_items : max_q * ntiles;
+    const int64_t wgs = queue ? L.max_items : L.max_q * ntiles;
     CV_REQUIRE(wgs < (1ll << 31), CV_EINVAL, "grid too large");
-#define CV_TILES_ARGS num_rots, res, corner, d3, tab, ystart, items, rec, n, tiles_x, tiles_z, partials, arrivals, d_grid_obj, \
-                      d_grid_rot, d_grid_scale, prof, list_ctl, list_start, list_cnt, entries, list_mode, q_info, ks
-#define CV_TILES_LAUNCH(V)                                                                                   \
-    do {                                                                                                     \
-        if (t_ev_start) CV_HIP_CHECK(hipEventRecord(t_ev_start, st));                                         \
-        if (queue) hv_fwd_tiles<V, true><<<dim3((unsigned)wgs, K), TW * 64, 0, st>>>(CV_TILES_ARGS);          \
-        else hv_fwd_tiles<V, false><<<dim3((unsigned)wgs, K), TW * 64, 0, st>>>(CV_TILES_ARGS);               \
-        if (t_ev_stop) CV_HIP_CHECK(hipEventRecord(t_ev_stop, st));                                           \
-    } while (0)
-    unsigned long long* prof = nullptr;
-    if (algo == 24) {
-        static unsigned long long* d_prof = nullptr;
-        if (!d_prof) CV_HIP_CHECK(hipMalloc(&d_prof, 16 * sizeof(unsigned long long)));
-        CV_HIP_CHECK(hipMemsetAsync(d_prof, 0, 16 * sizeof(unsigned long long), st));
-        prof = d_prof;
-        CV_TILES_LAUNCH(4);
-        unsigned long long h[16];
-        CV_HIP_CHECK(hipMemcpyAsync(h, d_prof, sizeof h, hipMemcpyDeviceToHost, st));
-        CV_HIP_CHECK(hipStreamSynchronize(st));
-        static const char* names[8] = {"init", "cull", "arcs+scan+search", "barrier-wait", "walk", "drain",
-                                       "round-flush", "merge+store"};
-        double tot = 0;
-        for (int p2 = 0; p2 < 8; ++p2) tot += (double)h[p2];
-        fprintf(stderr, "hv_fwd_tiles waves %llu ticks/wave %.0f:", h[8], tot / (double)std::max(1ull, h[8]));
-        for (int p2 = 0; p2 < 8; ++p2) fprintf(stderr, " %s %.1f%%", names[p2], 100.0 * (double)h[p2] / tot);
-        fprintf(stderr, "\n");
-    } else
-    if (algo == 25) CV_TILES_LAUNCH(5);
-    else if (algo == 21) CV_TILES_LAUNCH(1);
-    else if (algo == 22) CV_TILES_LAUNCH(2);
-    else if (algo == 23) CV_TILES_LAUNCH(3);
-    else CV_TILES_LAUNCH(0);
-#undef CV_TILES_LAUNCH
+#define CV_TILES_ARGS num_rots, res, corner, d3, tab, L.ystart, L.items, L.rec, n, tiles_x, tiles_z, L.partials, L.arrivals, d_grid_obj, \
+                      d_grid_rot, d_grid_scale, L.list_ctl, L.list_start, L.list_cnt, L.entries, list_mode, L.q_info, ks
+    if (t_ev_start) CV_HIP_CHECK(hipEventRecord(t_ev_start, st));
+    if (queue) hv_fwd_tiles<true><<<dim3((unsigned)wgs, K), TW * 64, 0, st>>>(CV_TILES_ARGS);
+    else hv_fwd_tiles<false><<<dim3((unsigned)wgs, K), TW * 64, 0, st>>>(CV_TILES_ARGS);
+    if (t_ev_stop) CV_HIP_CHECK(hipEventRecord(t_ev_stop, st));
 #undef CV_TILES_ARGS
     CV_LAUNCH_CHECK();
     return CV_OK;
@@ -1769,6 +1626,7 @@ int cv_hv_forward_f32(const float* d_points, const float* d_xyz, const float* d_
                       const float h_corner3[3], const int dims[3], float* d_grid_obj,
                       float* d_grid_rot, float* d_grid_scale, void* d_ws, size_t ws_bytes, int algo,
                       void* stream) {
+    CV_REQUIRE(algo_ok(algo), CV_EINVAL, "algo out of range (%d: 0 auto, 1 direct, 2 tiles)", algo);
     int rc = check_common(d_points, d_xyz, d_scale, n, res, num_rots, h_corner3, dims);
     if (rc) return rc;
     CV_REQUIRE(d_obj && d_grid_obj && d_grid_rot && d_grid_scale, CV_EINVAL, "null pointer argument");
@@ -1781,6 +1639,7 @@ int cv_hv_forward_cat_f32(const float* d_points, const float* d_xyz, const float
                           float* d_grid_rot, float* d_grid_scale, void* d_ws, size_t ws_bytes, int algo, void* stream) {
     CV_REQUIRE(num_cats >= 1 && num_cats <= CV_MAX_CATEGORIES, CV_EINVAL, "num_cats out of range (%d, 1..%d)", num_cats,
                CV_MAX_CATEGORIES);
+    CV_REQUIRE(algo_ok(algo), CV_EINVAL, "algo out of range (%d: 0 auto, 1 direct, 2 tiles)", algo);
     int rc = check_common(d_points, d_xyz, d_scale, n, res, num_rots, h_corner3, dims);
     if (rc) return rc;
     CV_REQUIRE(d_obj && d_grid_obj && d_grid_rot && d_grid_scale, CV_EINVAL, "null pointer argument");

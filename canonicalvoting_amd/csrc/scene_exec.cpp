@@ -163,6 +163,7 @@ int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream
     const long long n = d->n;
     std::memset(r, 0, sizeof(*r));
     CV_REQUIRE(d->conv_split_target >= 0 && d->vote_part_records >= 0, CV_EINVAL, "negative launch sizing");
+    CV_REQUIRE(d->vote_algo >= 0 && d->vote_algo <= 2, CV_EINVAL, "vote_algo out of range (%d: 0 auto, 1 direct, 2 tiles)", d->vote_algo);
     SceneCount in_flight(d->adaptive_split != 0, d->conv_split_target, d->vote_part_records);
     r->scenes_in_flight = in_flight.before + 1;
     Carver cv(d->d_ws, d->ws_bytes);
@@ -280,6 +281,7 @@ int cv_detect_scene_separate_f32(const cv_scene_separate_desc* d, cv_scene_separ
                CV_EINVAL, "null result arrays");
     CV_REQUIRE(!!d->d_xyz_in == !!d->d_scale_in && !!d->d_xyz_in == !!d->d_prob_in, CV_EINVAL, "predictions: all three or none");
     CV_REQUIRE(d->conv_split_target >= 0 && d->vote_part_records >= 0, CV_EINVAL, "negative launch sizing");
+    CV_REQUIRE(d->vote_algo >= 0 && d->vote_algo <= 2, CV_EINVAL, "vote_algo out of range (%d: 0 auto, 1 direct, 2 tiles)", d->vote_algo);
     CV_REQUIRE(d->models_per_pass >= 0, CV_EINVAL, "negative models_per_pass (%d)", d->models_per_pass);
     const int G = std::min(d->models_per_pass, K);          // models per pass of the batched network (0: one after another)
     if (G > 0) {
@@ -537,6 +539,7 @@ int cv_detect_points_f32(const cv_points_desc* d, cv_points_result* r, void* str
                    !s.d_class_in, CV_EINVAL, "raw cloud: the scene's d_coords4 / n / d_feats / feats_ld / d_points / d_*_in must be NULL / 0");
     CV_REQUIRE(s.ops && s.bufs && s.n_ops > 0 && s.n_bufs > 0 && s.d_out_feats && s.d_ws && s.h_pinned && s.max_candidates > 0, CV_EINVAL,
                "bad scene descriptor");
+    CV_REQUIRE(s.vote_algo >= 0 && s.vote_algo <= 2, CV_EINVAL, "vote_algo out of range (%d: 0 auto, 1 direct, 2 tiles)", s.vote_algo);
     // (the class array is joint mode's alone: the shared front hands its carve over through the result)
     auto inner = [r](cv_scene_desc* sd, cv_scene_result* sr, void* st) {
         sd->d_class_in = r->d_class_in;
@@ -557,6 +560,7 @@ int cv_detect_points_separate_f32(const cv_points_separate_desc* d, cv_points_se
                CV_MAX_CATEGORIES);
     CV_REQUIRE(s.ops && s.n_ops && s.bufs && s.n_bufs && s.d_out_feats && s.d_ws && s.h_pinned && s.max_candidates > 0, CV_EINVAL,
                "bad scene descriptor");
+    CV_REQUIRE(s.vote_algo >= 0 && s.vote_algo <= 2, CV_EINVAL, "vote_algo out of range (%d: 0 auto, 1 direct, 2 tiles)", s.vote_algo);
     auto inner = [](cv_scene_separate_desc* sd, cv_scene_separate_result* sr, void* st) {
         return cv_detect_scene_separate_f32(sd, sr, st);
     };

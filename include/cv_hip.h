@@ -71,7 +71,9 @@ int cv_hv_minmax_async_f32(const float* d_points, int64_t n, float* h_minmax6, v
 int cv_hv_grid_dims_f32(const float h_min3[3], const float h_max3[3], float res, int dims_out[3]);
 
 /* algo: 0 = auto, 1 = direct global fp32 atomics (+memset +normalise pass),
- *       2 = LDS-tiled accumulation with fused normalise (no global atomics). */
+ *       2 = LDS-tiled accumulation with fused normalise (no global atomics).
+ * Any other value is refused: the forward calls and the scene descriptors (vote_algo) return CV_EINVAL before they touch
+ * the GPU, the two workspace queries return 0. */
 size_t cv_hv_forward_workspace_bytes(int64_t n, int num_rots, const int dims[3], int algo);
 
 /* Vote accumulation + per-cell normalisation (hv_cuda_kernel.cu:12-119).

@@ -1,7 +1,7 @@
 """scenes-in-flight finding of the vote tile kernel: the vote on captured network predictions, repeated on one stream while six
 other streams run a synthetic co-resident load (profiles/microbench/lds_hammer.hip) instead of the convolutions - which
-ingredient disturbs it?  Run with the tile kernel built in the shape that goes wrong next to the convolutions
-(CV_HV_DEFS="-DHV_TX=16 -DHV_TW=8")."""
+ingredient disturbs it?  The tile kernel's shape that went wrong next to the convolutions, 16 x 32 cells / 8 waves, is the
+one it is built in."""
 import ctypes, os, sys, threading
 import numpy as np, torch
 HERE = os.path.dirname(os.path.abspath(__file__))

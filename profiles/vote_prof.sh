@@ -1,5 +1,4 @@
 cd /tmp && export TMPDIR=/tmp
-python $GRAFT_REPO_ROOT/profiles/vote_time.py --ticks "$@" 2>&1 | grep "hv_fwd_tiles\|^vote"
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pv -- python $GRAFT_REPO_ROOT/profiles/vote_time.py "$@" 2>/dev/null | grep "^vote"
 f=$(find /tmp/pv -name "*kernel_stats.csv" | head -1)
 python - "$f" <<'PY'

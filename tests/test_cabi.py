@@ -341,3 +341,31 @@ def test_scene_call_refuses_bad_descriptors_before_touching_the_gpu(built_lib):
         assert r.host_us[0] == 0.0 and r.n_cand == 0
         setattr(d, field, 0)
     assert L.cv_sp_set_split_target_thread(0) == 0 and L.cv_hv_set_part_records_thread(0) == 0      # nothing left behind
+
+
+def test_vote_algo_outside_the_documented_values_is_refused_before_touching_the_gpu(built_lib):
+    """algo is 0 (auto), 1 (direct) or 2 (tiles), include/cv_hip.h: anything else - 3, the ablation numbers the tile kernel once
+    answered to (21), a negative value - is CV_EINVAL from both forward calls and from a scene descriptor, and 0 from both size
+    queries (host-side checks only: the fake pointers are never dereferenced)"""
+    L = _lib.lib()
+    fake = ctypes.c_void_p(4096)
+    corner = (ctypes.c_float * 3)(0, 0, 0)
+    dims = (ctypes.c_int * 3)(40, 20, 40)
+    d, r = _lib.SceneDesc(), _lib.SceneResult()
+    for f in ("d_coords4", "d_feats", "d_points", "ops", "bufs", "d_out_feats", "h_pinned", "d_ws", "h_boxes", "h_scores", "h_classes",
+              "h_cand_idx", "h_verdict", "h_pick"):
+        setattr(d, f, fake)
+    d.n, d.n_ops, d.n_bufs, d.out_ld, d.out_channels, d.pinned_bytes, d.max_candidates = 100, 1, 1, 64, 64, 256, 8
+    for algo in (3, 21, -1):
+        assert L.cv_hv_forward_f32(fake, fake, fake, fake, 100, 0.03, 120, corner, dims, fake, fake, fake, fake, 1 << 30, algo,
+                                   None) == -22 and b"algo out of range" in L.cv_last_error()
+        assert L.cv_hv_forward_cat_f32(fake, fake, fake, fake, 100, 0.03, 120, corner, dims, 2, fake, fake, fake, fake, 1 << 30,
+                                       algo, None) == -22 and b"algo out of range" in L.cv_last_error()
+        d.vote_algo = algo
+        assert L.cv_detect_scene_f32(ctypes.byref(d), ctypes.byref(r), None) == -22 and b"vote_algo out of range" in L.cv_last_error()
+        assert L.cv_hv_forward_workspace_bytes(100, 120, dims, algo) == 0
+        assert L.cv_hv_forward_cat_workspace_bytes(100, 120, dims, algo, 2) == 0
+    for algo in (0, 1, 2):
+        one = L.cv_hv_forward_workspace_bytes(100, 120, dims, algo)
+        assert one >= 256 and one % 256 == 0 and L.cv_hv_forward_cat_workspace_bytes(100, 120, dims, algo, 3) == 3 * one
+    assert L.cv_sp_set_split_target_thread(0) == 0 and L.cv_hv_set_part_records_thread(0) == 0      # nothing left behind

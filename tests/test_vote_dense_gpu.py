@@ -194,3 +194,46 @@ def test_parts_give_the_same_grids_at_every_part_size(cuda, built_lib):
     for other in grids[1:]:
         for a, b in zip(grids[0], other):
             assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("K", [1, 2])
+@pytest.mark.parametrize("name", ["parts", "lists"])
+def test_writes_nothing_beyond_the_workspace_size_it_reports(cuda, built_lib, name, K):
+    """cv_hv_forward_cat_f32 on a workspace of exactly cv_hv_forward_cat_workspace_bytes bytes: the 64 KB behind it (part of the
+    same allocation, so nothing can fault) keep their fill pattern, and the grids are the bits of the same call on a roomy
+    workspace.  `parts`: streaming launch with a plane split into parts; `lists`: work-queue launch; K = 2: a second category
+    (half the offsets) one category stride behind the first.  The workspace arrives filled with the pattern, not zeroed."""
+    import ctypes
+    (pts, xyz, scale, prob, res, R), _ = _case(name)
+    p, x, s, o = dev_inputs(cuda, pts, xyz, scale, prob)
+    x = torch.stack([x, x * 0.5][:K]).contiguous()
+    s = torch.stack([s, s][:K]).contiguous()
+    o = torch.stack([o, o][:K]).contiguous()
+    L = _lib.lib()
+    n = p.shape[0]
+    mn, _, dims = hv_cuda.grid_geometry(p, res)
+    cdims = (ctypes.c_int * 3)(*dims)
+    X, Y, Z = dims
+    size = L.cv_hv_forward_cat_workspace_bytes(n, R, cdims, 2, K)
+    assert size == K * L.cv_hv_forward_workspace_bytes(n, R, cdims, 2) > 0
+    TAIL, PATTERN = 65536, 0xA5
+
+    def vote(ws, ws_bytes):
+        grids = [torch.empty((K, X, Y, Z) + tail, dtype=torch.float32, device=cuda) for tail in ((), (2,), (3,))]
+        with torch.cuda.device(cuda):
+            _lib.check(L.cv_hv_forward_cat_f32(hv_cuda._ptr(p), hv_cuda._ptr(x), hv_cuda._ptr(s), hv_cuda._ptr(o), n,
+                                               ctypes.c_float(res), R, hv_cuda._f3(mn), cdims, K, hv_cuda._ptr(grids[0]),
+                                               hv_cuda._ptr(grids[1]), hv_cuda._ptr(grids[2]), hv_cuda._ptr(ws), ws_bytes, 2,
+                                               hv_cuda._stream(cuda)), "cv_hv_forward_cat_f32")
+        torch.cuda.synchronize()
+        return grids
+
+    tight = torch.full((size + TAIL,), PATTERN, dtype=torch.uint8, device=cuda)
+    got = vote(tight, size)
+    assert bool((tight[size:] == PATTERN).all()), "bytes behind the reported workspace size were written"
+    assert not bool((tight[:size] == PATTERN).all())
+    roomy = torch.zeros((2 * size + TAIL,), dtype=torch.uint8, device=cuda)
+    want = vote(roomy, roomy.numel())
+    assert float(want[0][K - 1].max()) > 0
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
