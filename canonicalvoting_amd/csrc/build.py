@@ -36,7 +36,7 @@ def _sources():
     return {
         "cv_host.cpp": STRICT,
         "hv_vote.hip": STRICT + env("CV_HV_DEFS"),       # extra -D flags of an experiment (the file reads none today)
-        "hv_decode.hip": STRICT + env("CV_DEC_DEFS"),    # greedy-walk experiments (-DDEC_BLOCKED=0)
+        "hv_decode.hip": STRICT + env("CV_DEC_DEFS"),    # extra -D flags of an experiment (the file reads none today)
         "sparse_coords.hip": [],
         "sparse_conv.hip": env("CV_SC_DEFS"),            # kernel experiments (-DCV_WP_NPRE=27)
         "sparse_train.hip": [],                          # the training side: reads none of the CV_SC_DEFS switches

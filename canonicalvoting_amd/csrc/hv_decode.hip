@@ -4,7 +4,7 @@
 // Replaces the inline host loop eval_joint.py:195-263 (one full-grid argmax and >= 6
 // device->host syncs per candidate) with three launches and ONE sync per scene:
 //
-//   dec_compact      cells with grid_obj >= thresh_high -> compact list (index, value, cell
+//   dec_compact      cells with grid_obj >= thresh_high -> compact list (value, cell
 //                    coordinates) PLUS the box geometry each cell would have as a candidate
 //                    (rotation from the rot grid :213-214, scale :216): the double-precision
 //                    atan2 / cos / sin of every listed cell are evaluated here, in parallel,
@@ -12,8 +12,9 @@
 //                    The loop stops when the maximum drops below thresh_high (:208-209)
 //                    and only ever writes zeros, so cells below the threshold can never
 //                    influence which candidates are examined.
-//   dec_greedy       one workgroup walks the list (kept in LDS): ONE pass and ONE barrier per
-//                    candidate - the pass applies the suppression of the current candidate (the
+//   dec_greedy_dispatch[_big]
+//                    one workgroup walks the list (walk_lds, walk_global or walk_sorted, by the
+//                    list length and the grid size): ONE pass and ONE barrier per candidate - the pass applies the suppression of the current candidate (the
 //                    +-elimination cube :211 and the cells inside the oriented box :225-229,:243)
 //                    to each entry and, for the survivors, accumulates the next argmax (ties ->
 //                    lowest flat index, like torch.argmax).  The candidate sequence does not
@@ -37,9 +38,6 @@
 
 namespace {
 
-#ifndef DEC_PROF
-#define DEC_PROF 0      // phase ticks of the greedy walk (thread 0, printed at the end)
-#endif
 constexpr int NCLS = 64;   // class histogram bins (class ids must be in [0, 64))
 
 struct Cand {
@@ -52,10 +50,12 @@ struct Cand {
 };
 
 struct Stats {
-    unsigned n_in, n_mask, pmax_bits, pad;
+    unsigned n_in, n_mask, pmax_bits;
     double err;
     unsigned hist[NCLS];
 };
+static_assert(offsetof(Stats, err) % 8 == 0, "64-bit atomic adds");
+static_assert(sizeof(Stats) % 4 == 0, "a candidate's statistics are zeroed word by word");
 
 struct Geo {
     int X, Y, Z;
@@ -65,26 +65,46 @@ struct Geo {
 
 // compact list, structure of arrays over list positions
 struct List {
-    int* idx;        // flat cell index
-    float* val;      // grid_obj value (zeroed when suppressed, global fallback only)
+    float* val;      // grid_obj value (zeroed when suppressed, global-array walk only)
     unsigned* xy;    // x | y << 16
     int* z;
     float* geo;      // [5][cap]: cos, sin, scale xyz of the box the cell would propose
     int64_t cap;
 };
 
-// Category axis (cv_decode_cat_f32): category k's workspace (list, counters, candidates, statistics) is a carve of the
-// single-category layout `ws` bytes behind category k - 1's, its grids `cells` cells and its predictions `n` points behind
-// (scan points and class input shared).  K = 1 (cv_decode_f32): k = 0, every offset is zero.
+// flat cell index of a list entry (the walks order ties by it, like torch.argmax)
+__device__ __forceinline__ int cell_id(const Geo& geo, unsigned xy, int z) {
+    return ((int)(xy & 0xffffu) * geo.Y + (int)(xy >> 16)) * geo.Z + z;
+}
+
+// the counters block of a workspace carve: zeroed at the start of every call
+constexpr int CTR_WORDS = 16;
+constexpr int CTR_LIST_N = 0;     // list length (dec_compact)
+constexpr int CTR_N_CAND = 4;     // candidate count, then the "truncated" flag (the walk)
+
+// one category's workspace (WsLayout::at)
+struct Ws {
+    List L;
+    unsigned* counters;
+    Cand* cands;
+    Stats* stats;
+    __host__ __device__ unsigned* list_n() const { return counters + CTR_LIST_N; }
+    __host__ __device__ int* n_cand() const { return reinterpret_cast<int*>(counters + CTR_N_CAND); }
+};
+
+// Category axis (cv_decode_cat_f32): category k's workspace is a carve of the single-category layout `ws` bytes behind
+// category k - 1's, its grids `cells` cells and its predictions `n` points behind (scan points and class input shared).
+// K = 1 (cv_decode_f32): k = 0, every offset is zero.
 struct CatStride { int64_t ws, n, cells; };
 template <class T>
-__device__ __forceinline__ T* cat_ws(T* p, int64_t bytes, int k) {
-    return (T*)((const char*)p + (int64_t)k * bytes);
+__device__ __forceinline__ void cat_shift(T*& p, int64_t bytes) {
+    p = (T*)((char*)p + bytes);
 }
-__device__ __forceinline__ List cat_list(List L, int64_t bytes, int k) {
-    L.idx = cat_ws(L.idx, bytes, k); L.val = cat_ws(L.val, bytes, k); L.xy = cat_ws(L.xy, bytes, k);
-    L.z = cat_ws(L.z, bytes, k); L.geo = cat_ws(L.geo, bytes, k);
-    return L;
+__device__ __forceinline__ Ws cat(Ws w, int64_t stride, int k) {
+    const int64_t o = (int64_t)k * stride;
+    cat_shift(w.L.val, o); cat_shift(w.L.xy, o); cat_shift(w.L.z, o); cat_shift(w.L.geo, o);
+    cat_shift(w.counters, o); cat_shift(w.cands, o); cat_shift(w.stats, o);
+    return w;
 }
 
 // workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding GLOBAL access
@@ -102,11 +122,12 @@ __device__ __forceinline__ int lanes_below(uint64_t mask) {
 __global__ __launch_bounds__(256) void dec_compact(const float* __restrict__ g_obj,
                                                    const float* __restrict__ g_rot,
                                                    const float* __restrict__ g_scale, Geo geo,
-                                                   int64_t G, float thresh, List L,
-                                                   unsigned* __restrict__ list_n, CatStride ks) {
+                                                   int64_t G, float thresh, Ws w, CatStride ks) {
     const int kc = blockIdx.y;
     g_obj = g_obj + kc * ks.cells; g_rot = g_rot + kc * 2 * ks.cells; g_scale = g_scale + kc * 3 * ks.cells;
-    L = cat_list(L, ks.ws, kc); list_n = cat_ws(list_n, ks.ws, kc);
+    w = cat(w, ks.ws, kc);
+    const List& L = w.L;
+    unsigned* list_n = w.list_n();
     for (int64_t base = blockIdx.x * 256ll; base < G; base += (int64_t)gridDim.x * 256) {
         const int64_t i = base + threadIdx.x;
         float v = 0.f;
@@ -122,7 +143,6 @@ __global__ __launch_bounds__(256) void dec_compact(const float* __restrict__ g_o
         if (hit) {
             const unsigned p = pos + lanes_below(m);
             const int id = (int)i;
-            L.idx[p] = id;
             L.val[p] = v;
             const int z = id % geo.Z, y = (id / geo.Z) % geo.Y, x = id / (geo.Z * geo.Y);
             L.xy[p] = (unsigned)x | ((unsigned)y << 16);
@@ -176,21 +196,19 @@ __device__ __forceinline__ void box_corners(float cs, float sn, const float* sc,
 struct Best {
     float v;
     int id, pos;
+    int q;      // the wave that published it
 };
 
-__device__ __forceinline__ void take_better(Best& b, float v, int id, int pos) {
-    if (v > b.v || (v == b.v && id < b.id)) { b.v = v; b.id = id; b.pos = pos; }
+__device__ __forceinline__ void take_better(Best& b, float v, int id, int pos, int q) {
+    if (v > b.v || (v == b.v && id < b.id)) { b.v = v; b.id = id; b.pos = pos; b.q = q; }
 }
 
-#ifndef DEC_SMALL_T
-#define DEC_SMALL_T 512     // 256: 0.180 ms, 512: 0.158 ms, 1024: 0.181 ms decode stage at 80k points (profiles/r4/dec_small_t.txt)
-#endif
-constexpr int GREEDY_T = DEC_SMALL_T;        // threads of the greedy workgroup: two waves per SIMD.  One wave per SIMD (256, rounds
-                                     // 2-3) runs the per-candidate part every wave repeats - reduction, candidate set-up -
-                                     // once per SIMD, but leaves the LDS round trips of a region's box tests (~1 000 per
-                                     // candidate at 80k points, 4 per thread) with nothing to hide behind
-constexpr int GREEDY_W = GREEDY_T / 64;
-constexpr int GREEDY_CAP = 4096;     // list entries held in LDS (32 bytes each)
+constexpr int GREEDY_T = 512;        // threads of the greedy workgroup: two waves per SIMD (256: 0.180 ms, 512: 0.158 ms, 1024: 0.181 ms
+                                     // decode stage at 80k points, profiles/r4/dec_small_t.txt).  One wave per SIMD runs the
+                                     // per-candidate part every wave repeats - reduction, candidate set-up - once per SIMD, but
+                                     // leaves the LDS round trips of a region's box tests (~1 000 per candidate at 80k points, 4 per
+                                     // thread) with nothing to hide behind
+constexpr int GREEDY_CAP = 4096;     // list entries held in LDS (28 bytes each)
 
 // cross-lane moves on the DPP path (one VALU instruction, no LDS round trip): quad swaps, then row rotations leave
 // every lane of a 16-lane row with the row's result; the four rows are combined through scalar registers
@@ -217,208 +235,230 @@ __device__ __forceinline__ int wave_min_i32(int x) {
                min(__builtin_amdgcn_readlane(x, 32), __builtin_amdgcn_readlane(x, 48)));
 }
 
-// MODE 1: the thread's entries in registers, the rare by-index reads from an LDS copy (lists <= 16 * T = 4096 at T = 256);
-// MODE 2: the same walk with the by-index reads from the global arrays (L2) - no 128 KB LDS copy, so 1024 threads take lists
-//         up to 16384 cells (300k-point scenes); MODE 0: everything from the global arrays (any length)
-template <int MODE, int T>
-__device__ __forceinline__ void dec_greedy(Geo geo, cv_decode_params prm, List L,
-                                           const unsigned* __restrict__ list_n, Cand* __restrict__ cands,
-                                           Stats* __restrict__ stats, int* __restrict__ n_cand_out) {
-    constexpr bool IN_REG = MODE != 0, IN_LDS = MODE == 1;
-    constexpr int GREEDY_E = (MODE == 1 ? GREEDY_CAP / T : 16);      // entries per thread of the register-resident walk
-    constexpr int CAP = IN_LDS ? GREEDY_E * T : 1;
-    constexpr int GREEDY_T = T, GREEDY_W = T / 64;
-    __shared__ unsigned l_xy[CAP];
-    __shared__ int l_z[CAP];
-    __shared__ float l_geo[5][CAP];
-    __shared__ float s_val[2][GREEDY_W];
-    __shared__ int s_idx[2][GREEDY_W], s_pos[2][GREEDY_W];
-    const int n = (int)*list_n;
-    float r_val[GREEDY_E];
-    unsigned r_xy[GREEDY_E], dead = 0;
-    int r_z[GREEDY_E], r_id[GREEDY_E];
-    if (IN_REG) {
-#pragma unroll
-        for (int j = 0; j < GREEDY_E; ++j) {
-            const int k = (int)threadIdx.x + j * GREEDY_T;
-            const bool ok = k < n;
-            r_val[j] = ok ? L.val[k] : 0.f;
-            r_xy[j] = ok ? L.xy[k] : 0u;
-            r_z[j] = ok ? L.z[k] : 0;
-            r_id[j] = ((int)(r_xy[j] & 0xffffu) * geo.Y + (int)(r_xy[j] >> 16)) * geo.Z + r_z[j];
-            dead |= ok ? 0u : (1u << j);
-            if (ok && IN_LDS) {
-                l_xy[k] = r_xy[j];
-                l_z[k] = r_z[j];
-                for (int q = 0; q < 5; ++q) l_geo[q][k] = L.geo[q * L.cap + k];
-            }
-        }
-        __syncthreads();
+// The argmax of a pass over the workgroup (largest value, lowest flat index on ties: eval_joint.py:205), from every thread's
+// own best: the wave's best through DPP, one LDS slot per wave, ONE barrier, then every thread reads the W slots.  The slots
+// are double-buffered by the parity of `it`: the one barrier also frees the other buffer.  `also` runs in the lane that
+// publishes its wave's best, before the barrier (the sorted walk sends the winner's cell along).
+template <int W, class Also>
+__device__ __forceinline__ Best best_of_workgroup(float (&s_val)[2][W], int (&s_idx)[2][W], int (&s_pos)[2][W], int it, float bv,
+                                                  int bid, int bpos, Also&& also) {
+    const int wave = threadIdx.x >> 6, par = it & 1;
+    const float wv = wave_max_f32(bv);
+    const int wid = wave_min_i32(bv == wv ? bid : 0x7fffffff);
+    if (bv == wv && bid == wid) {
+        s_val[par][wave] = bv; s_idx[par][wave] = bid; s_pos[par][wave] = bpos;
+        also(par, wave);
     }
-    const int wave = threadIdx.x >> 6;
-    const float inv_res = 1.0f / geo.res;
-    const int e = prm.elimination, hp = e + (prm.elim_hi_plus1 ? 1 : 0);
-    // the candidate whose suppression the next pass applies (none before the first pass)
-    bool have_cur = false;
-    int cx = 0, cy = 0, cz = 0, clo0 = 0, clo1 = 0, clo2 = 0, chi0 = 0, chi1 = 0, chi2 = 0;
-    // conservative region of that suppression (cube and box bounds together): one unsigned compare per axis
-    // dismisses the entries that are nowhere near it
-    int rlo0 = 0, rlo1 = 0, rlo2 = 0;
-    unsigned rsp0 = 0, rsp1 = 0, rsp2 = 0;
-    float ccs = 0.f, csn = 0.f, csc[3] = {1.f, 1.f, 1.f};
-    auto flat_id = [&](int pos) {        // global fallback only
-        const unsigned xy = L.xy[pos];
-        const int z = L.z[pos];
-        return ((int)(xy & 0xffffu) * geo.Y + (int)(xy >> 16)) * geo.Z + z;
-    };
-    int it = 0;
-    bool truncated = false;
-    for (;; ++it) {
-        // ---- one pass: suppression by the current candidate (:211, :225-229, :243), then the argmax of
-        //      what is left (largest value, lowest flat index on ties: eval_joint.py:205)
-        float bv = -1.f;
-        int bpos = -1, bid = 0x7fffffff;
-        if constexpr (IN_REG) {
-            // the thread's entries live in registers (r_*; loaded once): a pass is VALU work only.  The first version
-            // walked them in LDS - two dependent LDS round trips per entry with one wave per SIMD and nothing to
-            // overlap them with: 10k cycles per pass for 13 entries per thread.
-            if (have_cur) {
-                unsigned near = 0;        // alive entries inside the conservative region
+    lds_barrier();
+    Best w{s_val[par][0], s_idx[par][0], s_pos[par][0], 0};
 #pragma unroll
-                for (int j = 0; j < GREEDY_E; ++j) {
-                    const int x = (int)(r_xy[j] & 0xffffu), y = (int)(r_xy[j] >> 16), z = r_z[j];
-                    const bool in = (unsigned)(x - rlo0) <= rsp0 && (unsigned)(y - rlo1) <= rsp1 &&
-                                    (unsigned)(z - rlo2) <= rsp2;
-                    near |= in ? (1u << j) : 0u;
-                }
-                near &= ~dead;
-                while (near) {            // rare: a handful of entries per candidate, taken from LDS by index
-                    const int j = __ffs(near) - 1;
-                    near &= near - 1;
-                    const int k = (int)threadIdx.x + j * GREEDY_T;
-                    const unsigned xy = IN_LDS ? l_xy[k] : L.xy[k];
-                    const int z = IN_LDS ? l_z[k] : L.z[k];
-                    const int x = (int)(xy & 0xffffu), y = (int)(xy >> 16);
-                    bool kill = x >= cx - e && x < cx + hp && y >= cy - e && y < cy + hp && z >= cz - e && z < cz + hp;
-                    if (!kill && x >= clo0 && x <= chi0 && y >= clo1 && y <= chi1 && z >= clo2 && z <= chi2) {
-                        const float v0 = (float)(x - cx) * geo.res, v1 = (float)(y - cy) * geo.res,
-                                    v2 = (float)(z - cz) * geo.res;
-                        kill = inside_box(v0, v1, v2, ccs, csn, csc);
-                    }
-                    if (kill) dead |= 1u << j;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < GREEDY_E; ++j) {
-                const bool alive = !((dead >> j) & 1u);
-                const float v = r_val[j];
-                const int id = r_id[j];
-                if (alive && (v > bv || (v == bv && id < bid))) { bv = v; bid = id; bpos = (int)threadIdx.x + j * GREEDY_T; }
-            }
-        } else {
-            for (int k = threadIdx.x; k < n; k += GREEDY_T) {
-                const float v = L.val[k];
-                if (v == 0.f) continue;
-                if (have_cur) {
-                    const unsigned xy = L.xy[k];
-                    const int z = L.z[k];
-                    const int x = (int)(xy & 0xffffu), y = (int)(xy >> 16);
-                    if ((unsigned)(x - rlo0) <= rsp0 && (unsigned)(y - rlo1) <= rsp1 && (unsigned)(z - rlo2) <= rsp2) {
-                        bool kill = x >= cx - e && x < cx + hp && y >= cy - e && y < cy + hp && z >= cz - e && z < cz + hp;
-                        if (!kill && x >= clo0 && x <= chi0 && y >= clo1 && y <= chi1 && z >= clo2 && z <= chi2) {
-                            const float v0 = (float)(x - cx) * geo.res, v1 = (float)(y - cy) * geo.res,
-                                        v2 = (float)(z - cz) * geo.res;
-                            kill = inside_box(v0, v1, v2, ccs, csn, csc);
-                        }
-                        if (kill) {
-                            L.val[k] = 0.f;
-                            continue;
-                        }
-                    }
-                }
-                if (v > bv || (v == bv && flat_id(k) < flat_id(bpos))) { bv = v; bpos = k; }
-            }
-            bid = bpos >= 0 ? flat_id(bpos) : 0x7fffffff;
+    for (int q = 1; q < W; ++q) take_better(w, s_val[par][q], s_idx[par][q], s_pos[par][q], q);
+    return w;
+}
+template <int W>
+__device__ __forceinline__ Best best_of_workgroup(float (&s_val)[2][W], int (&s_idx)[2][W], int (&s_pos)[2][W], int it, float bv,
+                                                  int bid, int bpos) {
+    return best_of_workgroup(s_val, s_idx, s_pos, it, bv, bid, bpos, [](int, int) {});
+}
+
+// The suppression a candidate applies to the grid - the +-elimination cube (:211) and the cells inside its oriented box
+// (:225-229, :243) - as the walks test list entries against it.  Every thread holds the same values.
+struct Suppress {
+    int c[3] = {0, 0, 0}, clo[3] = {0, 0, 0}, chi[3] = {0, 0, 0};
+    // conservative region (cube and box bounds together): one unsigned compare per axis dismisses the entries that are
+    // nowhere near
+    int rlo[3] = {0, 0, 0};
+    unsigned rsp[3] = {0, 0, 0};
+    float cs = 0.f, sn = 0.f, sc[3] = {1.f, 1.f, 1.f};
+    int e, hp;
+    float res;
+
+    __device__ __forceinline__ Suppress(const Geo& geo, const cv_decode_params& prm)
+        : e(prm.elimination), hp(prm.elimination + (prm.elim_hi_plus1 ? 1 : 0)), res(geo.res) {}
+
+    __device__ __forceinline__ bool near(int x, int y, int z) const {
+        // (three compares and two ANDs, no branch: a short circuit here would put a walk's load of z behind the test of x)
+        return ((unsigned)(x - rlo[0]) <= rsp[0]) & ((unsigned)(y - rlo[1]) <= rsp[1]) & ((unsigned)(z - rlo[2]) <= rsp[2]);
+    }
+    __device__ __forceinline__ bool kills(int x, int y, int z) const {
+        bool kill = x >= c[0] - e && x < c[0] + hp && y >= c[1] - e && y < c[1] + hp && z >= c[2] - e && z < c[2] + hp;
+        if (!kill && x >= clo[0] && x <= chi[0] && y >= clo[1] && y <= chi[1] && z >= clo[2] && z <= chi[2]) {
+            const float v0 = (float)(x - c[0]) * res, v1 = (float)(y - c[1]) * res, v2 = (float)(z - c[2]) * res;
+            kill = inside_box(v0, v1, v2, cs, sn, sc);
         }
-        const float wv = wave_max_f32(bv);
-        const int wid = wave_min_i32(bv == wv ? bid : 0x7fffffff);
-        const int par = it & 1;           // double-buffered: the one barrier also frees the other buffer
-        if (bv == wv && bid == wid) { s_val[par][wave] = bv; s_idx[par][wave] = bid; s_pos[par][wave] = bpos; }
-        lds_barrier();
-        Best w{s_val[par][0], s_idx[par][0], s_pos[par][0]};
-#pragma unroll
-        for (int q = 1; q < GREEDY_W; ++q) take_better(w, s_val[par][q], s_idx[par][q], s_pos[par][q]);
-        if (!(w.v >= prm.thresh_high)) break;                                   // :208-209
-        if (it >= prm.max_iters) { truncated = true; break; }
-        // ---- the candidate (every thread forms the same values; thread 0 records them)
-        const int id = w.id;
-        {
-            const unsigned wxy = IN_LDS ? l_xy[w.pos] : L.xy[w.pos];
-            cx = (int)(wxy & 0xffffu); cy = (int)(wxy >> 16);
-            cz = IN_LDS ? l_z[w.pos] : L.z[w.pos];
-        }
-        ccs = IN_LDS ? l_geo[0][w.pos] : L.geo[0 * L.cap + w.pos];
-        csn = IN_LDS ? l_geo[1][w.pos] : L.geo[1 * L.cap + w.pos];
-        for (int k = 0; k < 3; ++k) csc[k] = IN_LDS ? l_geo[2 + k][w.pos] : L.geo[(2 + k) * L.cap + w.pos];
+        return kill;
+    }
+
+    // Candidate `it` is the cell (xy, z) with flat index id: its box from the five geometry words g[q * gs + pos] of its
+    // list position, the cells that box can reach, the candidate record (thread 0) and its zeroed statistics (the
+    // workspace is not cleared by a launch).  T: threads of the workgroup, all of which call this.
+    template <int T>
+    __device__ __forceinline__ void take(int it, int id, unsigned xy, int z, const float* g, int64_t gs, int pos,
+                                         const Geo& geo, float inv_res, Cand* __restrict__ cands, Stats* __restrict__ stats) {
+        c[0] = (int)(xy & 0xffffu); c[1] = (int)(xy >> 16); c[2] = z;
+        cs = g[0 * gs + pos];
+        sn = g[1 * gs + pos];
+        for (int k = 0; k < 3; ++k) sc[k] = g[(2 + k) * gs + pos];
         // extent of the eight corners (+-m00 +- m02, +-m11, +-m20 +- m22; :217-219): every sign combination occurs and
         // rounding is symmetric, so max = |.| + |.| and min = -max, bit for bit what the min / max over the corners give
         float hi[3];
         {
-            const float m00 = ccs * csc[0], m02 = (-csn) * csc[2], m11 = csc[1], m20 = csn * csc[0], m22 = ccs * csc[2];
+            const float m00 = cs * sc[0], m02 = (-sn) * sc[2], m11 = sc[1], m20 = sn * sc[0], m22 = cs * sc[2];
             hi[0] = fabsf(m00) + fabsf(m02);
             hi[1] = fabsf(m11);
             hi[2] = fabsf(m20) + fabsf(m22);
         }
-        const int cc[3] = {cx, cy, cz}, shape[3] = {geo.X, geo.Y, geo.Z};
-        int clo[3], chi[3];
+        const int shape[3] = {geo.X, geo.Y, geo.Z};
 #pragma unroll
         for (int k = 0; k < 3; ++k) {                                             // :220-223
             const int blo = (int)((-hi[k]) * inv_res), bhi = (int)(hi[k] * inv_res);
-            clo[k] = min(max(cc[k] + blo, 0), shape[k] - 1);
-            chi[k] = min(max(cc[k] + bhi, 0), shape[k] - 1);
+            clo[k] = min(max(c[k] + blo, 0), shape[k] - 1);
+            chi[k] = min(max(c[k] + bhi, 0), shape[k] - 1);
+            rlo[k] = min(c[k] - e, clo[k]);
+            rsp[k] = (unsigned)(max(c[k] + hp - 1, chi[k]) - rlo[k]);
         }
-        clo0 = clo[0]; clo1 = clo[1]; clo2 = clo[2]; chi0 = chi[0]; chi1 = chi[1]; chi2 = chi[2];
-        rlo0 = min(cx - e, clo0); rsp0 = (unsigned)(max(cx + hp - 1, chi0) - rlo0);
-        rlo1 = min(cy - e, clo1); rsp1 = (unsigned)(max(cy + hp - 1, chi1) - rlo1);
-        rlo2 = min(cz - e, clo2); rsp2 = (unsigned)(max(cz + hp - 1, chi2) - rlo2);
-        have_cur = true;
         if (threadIdx.x == 0) {
             Cand cd;
             cd.idx = id;
             for (int k = 0; k < 3; ++k) {
-                cd.c[k] = cc[k]; cd.clo[k] = clo[k]; cd.chi[k] = chi[k];
-                cd.cw[k] = geo.corner[k] + geo.res * (float)cc[k];                // :206
-                cd.sc[k] = csc[k];
+                cd.c[k] = c[k]; cd.clo[k] = clo[k]; cd.chi[k] = chi[k];
+                cd.cw[k] = geo.corner[k] + geo.res * (float)c[k];                 // :206
+                cd.sc[k] = sc[k];
             }
-            cd.cs = ccs; cd.sn = csn;
+            cd.cs = cs; cd.sn = sn;
             cands[it] = cd;
         }
-        // the statistics of this candidate start from zero (the workspace is not cleared by a launch)
-        for (int q = threadIdx.x; q < (int)(sizeof(Stats) / 4); q += GREEDY_T)
+        for (int q = threadIdx.x; q < (int)(sizeof(Stats) / 4); q += T)
             reinterpret_cast<unsigned*>(&stats[it])[q] = 0u;
     }
-    if (threadIdx.x == 0) { n_cand_out[0] = it; n_cand_out[1] = truncated ? 1 : 0; }
+};
+
+// ---- The three walks.  Each runs in ONE workgroup: a pass applies the suppression of the current candidate to the live
+// entries and takes the argmax of what is left; the loop ends when that drops below thresh_high (:208-209) or at max_iters.
+
+// Lists up to GREEDY_CAP entries: the thread's entries live in registers (loaded once: a pass is VALU work only), the rare
+// by-index reads go to an LDS copy.  (The first version walked the entries in LDS - two dependent LDS round trips per
+// entry with one wave per SIMD and nothing to overlap them with: 10k cycles per pass for 13 entries per thread.)
+__device__ __forceinline__ void walk_lds(const Geo& geo, const cv_decode_params& prm, const Ws& w, int n) {
+    constexpr int T = GREEDY_T, E = GREEDY_CAP / T;      // E entries per thread
+    __shared__ unsigned l_xy[GREEDY_CAP];
+    __shared__ int l_z[GREEDY_CAP];
+    __shared__ float l_geo[5][GREEDY_CAP];
+    __shared__ float s_val[2][T / 64];
+    __shared__ int s_idx[2][T / 64], s_pos[2][T / 64];
+    const List& L = w.L;
+    float r_val[E];
+    unsigned r_xy[E], dead = 0;
+    int r_z[E], r_id[E];
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+        const int k = (int)threadIdx.x + j * T;
+        const bool ok = k < n;
+        r_val[j] = ok ? L.val[k] : 0.f;
+        r_xy[j] = ok ? L.xy[k] : 0u;
+        r_z[j] = ok ? L.z[k] : 0;
+        r_id[j] = cell_id(geo, r_xy[j], r_z[j]);
+        dead |= ok ? 0u : (1u << j);
+        if (ok) {
+            l_xy[k] = r_xy[j];
+            l_z[k] = r_z[j];
+            for (int q = 0; q < 5; ++q) l_geo[q][k] = L.geo[q * L.cap + k];
+        }
+    }
+    __syncthreads();
+    const float inv_res = 1.0f / geo.res;
+    Suppress s(geo, prm);
+    bool have_cur = false;       // none before the first pass
+    int it = 0;
+    bool truncated = false;
+    for (;; ++it) {
+        if (have_cur) {
+            unsigned near = 0;        // alive entries inside the conservative region
+#pragma unroll
+            for (int j = 0; j < E; ++j)
+                near |= s.near((int)(r_xy[j] & 0xffffu), (int)(r_xy[j] >> 16), r_z[j]) ? (1u << j) : 0u;
+            near &= ~dead;
+            while (near) {            // rare: a handful of entries per candidate, taken from LDS by index
+                const int j = __ffs(near) - 1;
+                near &= near - 1;
+                const int k = (int)threadIdx.x + j * T;
+                const unsigned xy = l_xy[k];
+                if (s.kills((int)(xy & 0xffffu), (int)(xy >> 16), l_z[k])) dead |= 1u << j;
+            }
+        }
+        float bv = -1.f;
+        int bpos = -1, bid = 0x7fffffff;
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            const bool alive = !((dead >> j) & 1u);
+            const float v = r_val[j];
+            const int id = r_id[j];
+            if (alive && (v > bv || (v == bv && id < bid))) { bv = v; bid = id; bpos = (int)threadIdx.x + j * T; }
+        }
+        const Best b = best_of_workgroup(s_val, s_idx, s_pos, it, bv, bid, bpos);
+        if (!(b.v >= prm.thresh_high)) break;                                   // :208-209
+        if (it >= prm.max_iters) { truncated = true; break; }
+        s.take<T>(it, b.id, l_xy[b.pos], l_z[b.pos], &l_geo[0][0], GREEDY_CAP, b.pos, geo, inv_res, w.cands, w.stats);
+        have_cur = true;
+    }
+    if (threadIdx.x == 0) { w.n_cand()[0] = it; w.n_cand()[1] = truncated ? 1 : 0; }
 }
 
-// ---- the register-resident walk, second version (round 4).  The first one (dec_greedy<1 / 2>) tests every entry of every
-// thread against every candidate and re-scans them for the maximum: ~44 vector instructions per entry and pass, which is
-// what a 300k-point scene's walk spent its 1.6 ms on (21 000 listed cells x 180 candidates on ONE CU; the 16-entry
-// capacity was also 5 000 cells short, so that scene fell through to the walk over the global arrays).  Here
+// Lists of any length: everything from the global arrays (L2-resident); a suppressed entry's value is zeroed in the list.
+template <int T>
+__device__ __forceinline__ void walk_global(const Geo& geo, const cv_decode_params& prm, const Ws& w, int n) {
+    __shared__ float s_val[2][T / 64];
+    __shared__ int s_idx[2][T / 64], s_pos[2][T / 64];
+    const List& L = w.L;
+    const float inv_res = 1.0f / geo.res;
+    auto id_at = [&](int pos) { return cell_id(geo, L.xy[pos], L.z[pos]); };
+    Suppress s(geo, prm);
+    bool have_cur = false;
+    int it = 0;
+    bool truncated = false;
+    for (;; ++it) {
+        float bv = -1.f;
+        int bpos = -1;
+        for (int k = threadIdx.x; k < n; k += T) {
+            const float v = L.val[k];
+            if (v == 0.f) continue;
+            if (have_cur) {
+                const unsigned xy = L.xy[k];
+                const int z = L.z[k];
+                const int x = (int)(xy & 0xffffu), y = (int)(xy >> 16);
+                if (s.near(x, y, z)) {
+                    if (s.kills(x, y, z)) {
+                        L.val[k] = 0.f;
+                        continue;
+                    }
+                }
+            }
+            if (v > bv || (v == bv && id_at(k) < id_at(bpos))) { bv = v; bpos = k; }
+        }
+        const int bid = bpos >= 0 ? id_at(bpos) : 0x7fffffff;
+        const Best b = best_of_workgroup(s_val, s_idx, s_pos, it, bv, bid, bpos);
+        if (!(b.v >= prm.thresh_high)) break;                                   // :208-209
+        if (it >= prm.max_iters) { truncated = true; break; }
+        s.take<T>(it, b.id, L.xy[b.pos], L.z[b.pos], L.geo, L.cap, b.pos, geo, inv_res, w.cands, w.stats);
+        have_cur = true;
+    }
+    if (threadIdx.x == 0) { w.n_cand()[0] = it; w.n_cand()[1] = truncated ? 1 : 0; }
+}
+
+// The big grids' walk (round 4).  walk_lds tests every entry of every thread against every candidate and re-scans them for
+// the maximum: ~44 vector instructions per entry and pass, which is what a 300k-point scene's walk spent its 1.6 ms on
+// (21 000 listed cells x 180 candidates on ONE CU).  Here
 //   * a wave owns 64 * E CONSECUTIVE list entries (dec_compact appends in rounds of the grid-stride loop: a stretch of the
 //     list is a window of x slabs) and every thread keeps the bounding box of its own: a candidate's suppression region is
 //     tested against the box first, and a wave whose 64 boxes all miss skips its entries altogether;
 //   * the entries are sorted once (value descending, flat index ascending: the order the walk takes them in), so the
 //     thread's best live entry is the lowest clear bit of `dead`; value / cell / list position of that entry sit in
 //     registers and are re-picked (select chains over the E slots) only when it dies;
-//   * the winner's cell travels through LDS from its owner's registers - no LDS copy of the list (the 80k-point walk's 128 KB),
-//     no by-index global reads except the five geometry words.
-// Same candidates in the same order as the reference loop (eval_joint.py:204-263): the maximum with ties to the lowest flat
-// index, suppression by cube and box exactly as before.  Used for the big grids (dec_greedy_dispatch_big): a 300k-point
-// scene's decode 1.88 -> 1.28 ms.  What is left there (phase ticks, DEC_PROF): the waves that own the cells inside a
-// candidate's region run ~6 kill tests per lane (~100 instructions each with the select trees) in nearly every wave - the four
-// waves of a SIMD keep it busy for ~13 000 cycles per candidate - and the five geometry words cost 2 700 cycles (requesting them
-// before the barrier, by every wave's best lane, did not shorten that).
-// NOT used for the 80k-point lists (3 400 cells, 42 candidates): 0.21 ms against dec_greedy<1>'s 0.18.
+//   * the winner's cell travels through LDS from its owner's registers - no LDS copy of the list (walk_lds's 112 KB), no
+//     by-index global reads except the five geometry words.
+// Same candidates in the same order as the reference loop (eval_joint.py:204-263).  A 300k-point scene's decode 1.88 ->
+// 1.28 ms (LABNOTES, "Decode at 300k points", also for what is left there).  NOT used for the 80k-point lists (3 400 cells,
+// 42 candidates): 0.21 ms against walk_lds's 0.18.
 template <int N, class Tv>
 __device__ __forceinline__ Tv pick_slot(const Tv (&r)[N], int j) {
     // slot j of a register array (a dynamic index has to become selects): a binary tree over the bits of j - N - 1 selects
@@ -437,14 +477,14 @@ __device__ __forceinline__ Tv pick_slot(const Tv (&r)[N], int j) {
 }
 
 template <int T, int E, int G>
-__device__ __forceinline__ void dec_greedy_sorted(Geo geo, cv_decode_params prm, List L, int n, Cand* __restrict__ cands,
-                                                  Stats* __restrict__ stats, int* __restrict__ n_cand_out) {
+__device__ __forceinline__ void walk_sorted(const Geo& geo, const cv_decode_params& prm, const Ws& w, int n) {
     static_assert(E >= 2 && E <= 32 && T % 64 == 0 && G % 64 == 0 && T % G == 0, "entries per thread live in one 32-bit mask");
     constexpr int W = T / 64;
     constexpr unsigned ALL = E == 32 ? 0xffffffffu : ((1u << E) - 1u);
     __shared__ float s_val[2][W];
     __shared__ int s_idx[2][W], s_pos[2][W], s_z[2][W];
     __shared__ unsigned s_xy[2][W];
+    const List& L = w.L;
     // a group of G threads owns G * E consecutive list entries, dealt to its threads round-robin: the cells a candidate
     // suppresses sit next to each other in the list, and a thread that owned them all would walk them alone (E consecutive
     // entries per thread: 0.18 -> 0.30 ms at 80k points; G = 64 at 300k points: the wave that owns the ~500 suppressed cells
@@ -483,11 +523,7 @@ __device__ __forceinline__ void dec_greedy_sorted(Geo geo, cv_decode_params prm,
                 const unsigned x0 = r_xy[j], x1 = r_xy[j + 1];
                 const int z0 = r_zj[j], z1 = r_zj[j + 1];
                 bool sw = v1 > v0;
-                if (v1 == v0) {
-                    const int i0 = ((int)(x0 & 0xffffu) * geo.Y + (int)(x0 >> 16)) * geo.Z + (z0 & 0xffff);
-                    const int i1 = ((int)(x1 & 0xffffu) * geo.Y + (int)(x1 >> 16)) * geo.Z + (z1 & 0xffff);
-                    sw = i1 < i0;
-                }
+                if (v1 == v0) sw = cell_id(geo, x1, z1 & 0xffff) < cell_id(geo, x0, z0 & 0xffff);
                 r_val[j] = sw ? v1 : v0; r_val[j + 1] = sw ? v0 : v1;
                 r_xy[j] = sw ? x1 : x0;  r_xy[j + 1] = sw ? x0 : x1;
                 r_zj[j] = sw ? z1 : z0;  r_zj[j + 1] = sw ? z0 : z1;
@@ -495,58 +531,35 @@ __device__ __forceinline__ void dec_greedy_sorted(Geo geo, cv_decode_params prm,
         }
         dead = ALL & ~(cnt >= 32 ? 0xffffffffu : ((1u << cnt) - 1u));
     }
-    const int wave = threadIdx.x >> 6;
     const float inv_res = 1.0f / geo.res;
-    const int e = prm.elimination, hp = e + (prm.elim_hi_plus1 ? 1 : 0);
+    Suppress s(geo, prm);
     bool have_cur = false;
-    int cx = 0, cy = 0, cz = 0, clo0 = 0, clo1 = 0, clo2 = 0, chi0 = 0, chi1 = 0, chi2 = 0;
-    int rlo0 = 0, rlo1 = 0, rlo2 = 0, rhi0 = -1, rhi1 = -1, rhi2 = -1;     // conservative region of the current suppression
-    float ccs = 0.f, csn = 0.f, csc[3] = {1.f, 1.f, 1.f};
     // the thread's best live entry
     int cur_j = -1, cur_id = 0x7fffffff, cur_pos = -1, cur_z = 0;
     unsigned cur_xy = 0;
     float cur_val = -1.f;
     int it = 0;
     bool truncated = false;
-#if DEC_PROF
-    unsigned long long pt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_prev = __builtin_readcyclecounter();
-#define DEC_TICK(i) { const unsigned long long t_now = __builtin_readcyclecounter(); pt[i] += t_now - t_prev; t_prev = t_now; }
-    DEC_TICK(7)
-#else
-#define DEC_TICK(i)
-#endif
     for (;; ++it) {
-        // ---- suppression by the current candidate (:211, :225-229, :243): box against box first
-        const bool hit = have_cur && dead != ALL && bx1 >= rlo0 && bx0 <= rhi0 && by1 >= rlo1 && by0 <= rhi1 &&
-                         bz1 >= rlo2 && bz0 <= rhi2;
+        // ---- suppression by the current candidate: its region against the box of the thread's entries first
+        const bool hit = have_cur && dead != ALL && bx1 >= s.rlo[0] && bx0 <= s.rlo[0] + (int)s.rsp[0] && by1 >= s.rlo[1] &&
+                         by0 <= s.rlo[1] + (int)s.rsp[1] && bz1 >= s.rlo[2] && bz0 <= s.rlo[2] + (int)s.rsp[2];
         if (__any(hit)) {
             if (hit) {
                 unsigned near = 0;
 #pragma unroll
-                for (int j = 0; j < E; ++j) {
-                    const int x = (int)(r_xy[j] & 0xffffu), y = (int)(r_xy[j] >> 16), z = r_zj[j] & 0xffff;
-                    const bool in = (unsigned)(x - rlo0) <= (unsigned)(rhi0 - rlo0) && (unsigned)(y - rlo1) <= (unsigned)(rhi1 - rlo1) &&
-                                    (unsigned)(z - rlo2) <= (unsigned)(rhi2 - rlo2);
-                    near |= in ? (1u << j) : 0u;
-                }
+                for (int j = 0; j < E; ++j)
+                    near |= s.near((int)(r_xy[j] & 0xffffu), (int)(r_xy[j] >> 16), r_zj[j] & 0xffff) ? (1u << j) : 0u;
                 near &= ~dead;
                 while (near) {
                     const int j = __ffs(near) - 1;
                     near &= near - 1;
                     const unsigned xy = pick_slot<E>(r_xy, j);
                     const int z = pick_slot<E>(r_zj, j) & 0xffff;
-                    const int x = (int)(xy & 0xffffu), y = (int)(xy >> 16);
-                    bool kill = x >= cx - e && x < cx + hp && y >= cy - e && y < cy + hp && z >= cz - e && z < cz + hp;
-                    if (!kill && x >= clo0 && x <= chi0 && y >= clo1 && y <= chi1 && z >= clo2 && z <= chi2) {
-                        const float v0 = (float)(x - cx) * geo.res, v1 = (float)(y - cy) * geo.res,
-                                    v2 = (float)(z - cz) * geo.res;
-                        kill = inside_box(v0, v1, v2, ccs, csn, csc);
-                    }
-                    if (kill) dead |= 1u << j;
+                    if (s.kills((int)(xy & 0xffffu), (int)(xy >> 16), z)) dead |= 1u << j;
                 }
             }
         }
-        DEC_TICK(0)
         // ---- the thread's best live entry = the first live slot of the sorted order
         float bv = -1.f;
         int bid = 0x7fffffff, bpos = -1;
@@ -560,116 +573,39 @@ __device__ __forceinline__ void dec_greedy_sorted(Geo geo, cv_decode_params prm,
                     const int zj = pick_slot<E>(r_zj, cur_j);
                     cur_z = zj & 0xffff;
                     cur_pos = base + G * (zj >> 16);
-                    cur_id = ((int)(cur_xy & 0xffffu) * geo.Y + (int)(cur_xy >> 16)) * geo.Z + cur_z;
+                    cur_id = cell_id(geo, cur_xy, cur_z);
                 }
                 bv = cur_val; bid = cur_id; bpos = cur_pos;
             }
         }
-        DEC_TICK(1)
-        const float wv = wave_max_f32(bv);
-        const int wid = wave_min_i32(bv == wv ? bid : 0x7fffffff);
-        const int par = it & 1;           // double-buffered: the one barrier also frees the other buffer
-        if (bv == wv && bid == wid) {
-            s_val[par][wave] = bv; s_idx[par][wave] = bid; s_pos[par][wave] = bpos;
-            s_xy[par][wave] = cur_xy; s_z[par][wave] = cur_z;
-        }
-        DEC_TICK(2)
-        lds_barrier();
-        DEC_TICK(3)
-        Best w{s_val[par][0], s_idx[par][0], s_pos[par][0]};
-        int wq = 0;
-#pragma unroll
-        for (int q = 1; q < W; ++q) {
-            const float v = s_val[par][q];
-            const int id = s_idx[par][q];
-            if (v > w.v || (v == w.v && id < w.id)) { w.v = v; w.id = id; w.pos = s_pos[par][q]; wq = q; }
-        }
-        if (!(w.v >= prm.thresh_high)) break;                                   // :208-209
+        const Best b = best_of_workgroup(s_val, s_idx, s_pos, it, bv, bid, bpos,
+                                         [&](int par, int wave) { s_xy[par][wave] = cur_xy; s_z[par][wave] = cur_z; });
+        if (!(b.v >= prm.thresh_high)) break;                                   // :208-209
         if (it >= prm.max_iters) { truncated = true; break; }
-        // ---- the candidate (every thread forms the same values; thread 0 records them)
-        const int id = w.id;
-        {
-            const unsigned wxy = s_xy[par][wq];
-            cx = (int)(wxy & 0xffffu); cy = (int)(wxy >> 16);
-            cz = s_z[par][wq];
-        }
-        ccs = L.geo[0 * L.cap + w.pos];
-        csn = L.geo[1 * L.cap + w.pos];
-        for (int k = 0; k < 3; ++k) csc[k] = L.geo[(2 + k) * L.cap + w.pos];
-        DEC_TICK(4)
-        float hi[3];
-        {
-            const float m00 = ccs * csc[0], m02 = (-csn) * csc[2], m11 = csc[1], m20 = csn * csc[0], m22 = ccs * csc[2];
-            hi[0] = fabsf(m00) + fabsf(m02);
-            hi[1] = fabsf(m11);
-            hi[2] = fabsf(m20) + fabsf(m22);
-        }
-        const int cc[3] = {cx, cy, cz}, shape[3] = {geo.X, geo.Y, geo.Z};
-        int clo[3], chi[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {                                             // :220-223
-            const int blo = (int)((-hi[k]) * inv_res), bhi = (int)(hi[k] * inv_res);
-            clo[k] = min(max(cc[k] + blo, 0), shape[k] - 1);
-            chi[k] = min(max(cc[k] + bhi, 0), shape[k] - 1);
-        }
-        clo0 = clo[0]; clo1 = clo[1]; clo2 = clo[2]; chi0 = chi[0]; chi1 = chi[1]; chi2 = chi[2];
-        rlo0 = min(cx - e, clo0); rhi0 = max(cx + hp - 1, chi0);
-        rlo1 = min(cy - e, clo1); rhi1 = max(cy + hp - 1, chi1);
-        rlo2 = min(cz - e, clo2); rhi2 = max(cz + hp - 1, chi2);
+        s.take<T>(it, b.id, s_xy[it & 1][b.q], s_z[it & 1][b.q], L.geo, L.cap, b.pos, geo, inv_res, w.cands, w.stats);
         have_cur = true;
-        if (threadIdx.x == 0) {
-            Cand cd;
-            cd.idx = id;
-            for (int k = 0; k < 3; ++k) {
-                cd.c[k] = cc[k]; cd.clo[k] = clo[k]; cd.chi[k] = chi[k];
-                cd.cw[k] = geo.corner[k] + geo.res * (float)cc[k];                // :206
-                cd.sc[k] = csc[k];
-            }
-            cd.cs = ccs; cd.sn = csn;
-            cands[it] = cd;
-        }
-        // the statistics of this candidate start from zero (the workspace is not cleared by a launch)
-        for (int q = threadIdx.x; q < (int)(sizeof(Stats) / 4); q += T)
-            reinterpret_cast<unsigned*>(&stats[it])[q] = 0u;
-        DEC_TICK(5)
     }
-#if DEC_PROF
-    if ((threadIdx.x & 63) == 0)
-        printf("  wave %2d: suppress %llu best %llu reduce+write %llu barrier %llu final+geo %llu math+stores %llu\n", (int)(threadIdx.x >> 6),
-               pt[0], pt[1], pt[2], pt[3], pt[4], pt[5]);
-    if (threadIdx.x == 0)
-        printf("dec_greedy_sorted<%d,%d,%d> n=%d cand=%d ticks: setup %llu | suppress %llu best %llu reduce+write %llu barrier %llu final+geo %llu math+stores %llu\n",
-               T, E, G, n, it, pt[7], pt[0], pt[1], pt[2], pt[3], pt[4], pt[5]);
-#endif
-    if (threadIdx.x == 0) { n_cand_out[0] = it; n_cand_out[1] = truncated ? 1 : 0; }
+    if (threadIdx.x == 0) { w.n_cand()[0] = it; w.n_cand()[1] = truncated ? 1 : 0; }
 }
 
-// the list length is only known on the device: lists up to GREEDY_CAP entries are walked in registers + LDS, longer ones by
-// the same code over the global arrays (L2-resident)
-__global__ __launch_bounds__(GREEDY_T) void dec_greedy_dispatch(Geo geo, cv_decode_params prm, List L,
-                                                                const unsigned* __restrict__ list_n,
-                                                                Cand* __restrict__ cands, Stats* __restrict__ stats,
-                                                                int* __restrict__ n_cand_out, int64_t ks_ws) {
-    // one walker workgroup per category (blockIdx.y): the K walks run side by side
-    L = cat_list(L, ks_ws, blockIdx.y); list_n = cat_ws(list_n, ks_ws, blockIdx.y); cands = cat_ws(cands, ks_ws, blockIdx.y);
-    stats = cat_ws(stats, ks_ws, blockIdx.y); n_cand_out = cat_ws(n_cand_out, ks_ws, blockIdx.y);
-    if (*list_n <= (unsigned)GREEDY_CAP) dec_greedy<1, GREEDY_T>(geo, prm, L, list_n, cands, stats, n_cand_out);
-    else dec_greedy<0, GREEDY_T>(geo, prm, L, list_n, cands, stats, n_cand_out);
+// One walker workgroup per category (blockIdx.y): the K walks run side by side.  The list length is only known on the
+// device, so the kernel picks the walk: lists up to GREEDY_CAP entries in registers + LDS, longer ones over the global arrays
+__global__ __launch_bounds__(GREEDY_T) void dec_greedy_dispatch(Geo geo, cv_decode_params prm, Ws w, int64_t ks_ws) {
+    w = cat(w, ks_ws, blockIdx.y);
+    const unsigned n = *w.list_n();
+    if (n <= (unsigned)GREEDY_CAP) walk_lds(geo, prm, w, (int)n);
+    else walk_global<GREEDY_T>(geo, prm, w, (int)n);
 }
 // big grids (the host picks this launch from the cell count): 1024 threads, lists up to 24576 cells in registers (a
 // 300k-point scene lists ~21 000 cells) on the sorted walk
 constexpr int GREEDY_T_BIG = 1024;
 constexpr int GREEDY_E_BIG = 24;
 constexpr int GREEDY_G_BIG = 64;
-__global__ __launch_bounds__(GREEDY_T_BIG) void dec_greedy_dispatch_big(Geo geo, cv_decode_params prm, List L,
-                                                                        const unsigned* __restrict__ list_n,
-                                                                        Cand* __restrict__ cands, Stats* __restrict__ stats,
-                                                                        int* __restrict__ n_cand_out, int64_t ks_ws) {
-    L = cat_list(L, ks_ws, blockIdx.y); list_n = cat_ws(list_n, ks_ws, blockIdx.y); cands = cat_ws(cands, ks_ws, blockIdx.y);
-    stats = cat_ws(stats, ks_ws, blockIdx.y); n_cand_out = cat_ws(n_cand_out, ks_ws, blockIdx.y);
-    if (*list_n <= (unsigned)(GREEDY_E_BIG * GREEDY_T_BIG))
-        dec_greedy_sorted<GREEDY_T_BIG, GREEDY_E_BIG, GREEDY_G_BIG>(geo, prm, L, (int)*list_n, cands, stats, n_cand_out);
-    else dec_greedy<0, GREEDY_T_BIG>(geo, prm, L, list_n, cands, stats, n_cand_out);
+__global__ __launch_bounds__(GREEDY_T_BIG) void dec_greedy_dispatch_big(Geo geo, cv_decode_params prm, Ws w, int64_t ks_ws) {
+    w = cat(w, ks_ws, blockIdx.y);
+    const unsigned n = *w.list_n();
+    if (n <= (unsigned)(GREEDY_E_BIG * GREEDY_T_BIG)) walk_sorted<GREEDY_T_BIG, GREEDY_E_BIG, GREEDY_G_BIG>(geo, prm, w, (int)n);
+    else walk_global<GREEDY_T_BIG>(geo, prm, w, (int)n);
 }
 
 // packed host result: [0]=n_cand [1]=n_boxes [2]=truncated, then arrays sized by max_iters
@@ -746,12 +682,13 @@ __device__ void finalize_block(const Cand* __restrict__ cands, const Stats* __re
 
 __global__ __launch_bounds__(256) void dec_backproject(
     const float* __restrict__ pts, const float* __restrict__ xyz, const float* __restrict__ prob,
-    const int* __restrict__ cls, int64_t n, float prob_thresh, const Cand* __restrict__ cands,
-    const int* __restrict__ n_cand, Stats* __restrict__ stats, CatStride ks) {
+    const int* __restrict__ cls, int64_t n, float prob_thresh, Ws w, CatStride ks) {
     // category: blockIdx.z (blockIdx.y strides over the candidate groups)
     const int kc = blockIdx.z;
     xyz = xyz + kc * 3 * ks.n; prob = prob + kc * ks.n;
-    cands = cat_ws(cands, ks.ws, kc); n_cand = cat_ws(n_cand, ks.ws, kc); stats = cat_ws(stats, ks.ws, kc);
+    w = cat(w, ks.ws, kc);
+    const Cand* cands = w.cands;
+    Stats* stats = w.stats;
     const int64_t i = blockIdx.x * 256ll + threadIdx.x;
     const bool have = i < n;
     float p0 = 0, p1 = 0, p2 = 0, x0 = 0, x1 = 0, x2 = 0, pr = 0;
@@ -762,7 +699,7 @@ __global__ __launch_bounds__(256) void dec_backproject(
         pr = prob[i];
         cl = cls ? cls[i] : 0;          // (no class input: class 0, separate mode)
     }
-    const int nc = n_cand[0];
+    const int nc = w.n_cand()[0];
     // A workgroup takes its 256 points through GROUPS of CB candidates (blockIdx.y, strided): with all candidates
     // in one workgroup the launch had 1.2 waves per SIMD, each walking 42 dependent (LDS read -> three IEEE
     // divisions -> LDS atomics) rounds on its own - 46 us for 3.4 M in-box tests.  Candidates are staged through
@@ -824,24 +761,22 @@ __global__ __launch_bounds__(256) void dec_backproject(
 
 // one launch boundary (~2 us) instead of a release fence in each of the thousands of back-projection workgroups (an
 // agent-scope release writes the XCD's L2 back: the fused version ran 4x slower)
-__global__ __launch_bounds__(256) void dec_finalize(const Cand* __restrict__ cands, const Stats* __restrict__ stats,
-                                                    const int* __restrict__ n_cand, cv_decode_params prm,
-                                                    char* result, int M, int64_t ks_ws, int64_t result_stride) {
-    cands = cat_ws(cands, ks_ws, blockIdx.y); stats = cat_ws(stats, ks_ws, blockIdx.y); n_cand = cat_ws(n_cand, ks_ws, blockIdx.y);
+__global__ __launch_bounds__(256) void dec_finalize(Ws w, cv_decode_params prm, char* result, int M, int64_t ks_ws,
+                                                    int64_t result_stride) {
+    w = cat(w, ks_ws, blockIdx.y);
     result += (int64_t)blockIdx.y * result_stride;
     __shared__ int s_scan[256];
-    finalize_block(cands, stats, n_cand[0], n_cand[1], prm, result, M, s_scan);
+    finalize_block(w.cands, w.stats, w.n_cand()[0], w.n_cand()[1], prm, result, M, s_scan);
 }
 
 // optional: replay the zeroing on the real grid (the reference mutates grid_obj in place)
 __global__ __launch_bounds__(256) void dec_apply(float* __restrict__ g_obj, Geo geo,
-                                                 cv_decode_params prm, const Cand* __restrict__ cands,
-                                                 const int* __restrict__ n_cand, CatStride ks) {
+                                                 cv_decode_params prm, Ws w, CatStride ks) {
     g_obj = g_obj + (int64_t)blockIdx.y * ks.cells;
-    cands = cat_ws(cands, ks.ws, blockIdx.y); n_cand = cat_ws(n_cand, ks.ws, blockIdx.y);
+    w = cat(w, ks.ws, blockIdx.y);
     const int k = blockIdx.x;
-    if (k >= *n_cand) return;
-    const Cand& cd = cands[k];
+    if (k >= w.n_cand()[0]) return;
+    const Cand& cd = w.cands[k];
     const int e = prm.elimination, hp = e + (prm.elim_hi_plus1 ? 1 : 0);
     {
         const int x0 = max(cd.c[0] - e, 0), y0 = max(cd.c[1] - e, 0), z0 = max(cd.c[2] - e, 0);
@@ -865,27 +800,40 @@ __global__ __launch_bounds__(256) void dec_apply(float* __restrict__ g_obj, Geo 
     }
 }
 
-// the counters of K workspace carves zeroed in one launch (16 words each)
-__global__ __launch_bounds__(64) void dec_zero_counters(unsigned* __restrict__ counters, int64_t ks_ws) {
-    counters = cat_ws(counters, ks_ws, blockIdx.y);
-    if (threadIdx.x < 16) counters[threadIdx.x] = 0u;
+// the counters of K workspace carves zeroed in one launch
+__global__ __launch_bounds__(64) void dec_zero_counters(Ws w, int64_t ks_ws) {
+    w = cat(w, ks_ws, blockIdx.y);
+    if (threadIdx.x < CTR_WORDS) w.counters[threadIdx.x] = 0u;
 }
 
+// the single-category workspace: the list arrays (one slot per grid cell), the counters block, candidates, statistics
 struct WsLayout {
-    size_t off_list_idx, off_list_val, off_list_xy, off_list_z, off_list_geo, off_counters, off_cands, off_stats,
-        off_result, total;
-    WsLayout(int64_t G, int M) {
+    size_t off_val, off_xy, off_z, off_geo, off_counters, off_cands, off_stats, total;
+    int64_t cells;
+    WsLayout(int64_t G, int M) : cells(G) {
         size_t o = 0;
-        off_list_idx = o; o = cv_align_up(o + sizeof(int) * G, 256);
-        off_list_val = o; o = cv_align_up(o + sizeof(float) * G, 256);
-        off_list_xy = o; o = cv_align_up(o + sizeof(unsigned) * G, 256);
-        off_list_z = o; o = cv_align_up(o + sizeof(int) * G, 256);
-        off_list_geo = o; o = cv_align_up(o + sizeof(float) * 5 * G, 256);
-        off_counters = o; o = cv_align_up(o + 64, 256);
+        off_val = o; o = cv_align_up(o + sizeof(float) * G, 256);
+        off_xy = o; o = cv_align_up(o + sizeof(unsigned) * G, 256);
+        off_z = o; o = cv_align_up(o + sizeof(int) * G, 256);
+        off_geo = o; o = cv_align_up(o + sizeof(float) * 5 * G, 256);
+        off_counters = o; o = cv_align_up(o + sizeof(unsigned) * CTR_WORDS, 256);
         off_cands = o; o = cv_align_up(o + sizeof(Cand) * M, 256);
         off_stats = o; o = cv_align_up(o + sizeof(Stats) * M, 256);
-        off_result = o; o = cv_align_up(o + ResultLayout(M).total, 256);
+        // (a result block's worth of bytes that no kernel uses since the results go to pinned host memory: still reported)
+        o = cv_align_up(o + ResultLayout(M).total, 256);
         total = o;
+    }
+    Ws at(char* ws) const {
+        Ws w;
+        w.L.val = reinterpret_cast<float*>(ws + off_val);
+        w.L.xy = reinterpret_cast<unsigned*>(ws + off_xy);
+        w.L.z = reinterpret_cast<int*>(ws + off_z);
+        w.L.geo = reinterpret_cast<float*>(ws + off_geo);
+        w.L.cap = cells;
+        w.counters = reinterpret_cast<unsigned*>(ws + off_counters);
+        w.cands = reinterpret_cast<Cand*>(ws + off_cands);
+        w.stats = reinterpret_cast<Stats*>(ws + off_stats);
+        return w;
     }
 };
 
@@ -894,70 +842,53 @@ struct WsLayout {
 struct PinnedPool {
     std::mutex mu;
     std::vector<std::pair<char*, size_t>> free_list;
-    char* take(size_t bytes) {
+    // a buffer of at least `bytes` with its capacity; {nullptr, 0} when the allocation fails
+    std::pair<char*, size_t> take(size_t bytes) {
         {
             std::lock_guard<std::mutex> g(mu);
             for (size_t i = 0; i < free_list.size(); ++i)
                 if (free_list[i].second >= bytes) {
-                    char* p = free_list[i].first;
-                    cap_of_last = free_list[i].second;
+                    const std::pair<char*, size_t> b = free_list[i];
                     free_list.erase(free_list.begin() + i);
-                    return p;
+                    return b;
                 }
         }
         void* p = nullptr;
-        if (hipHostMalloc(&p, bytes, hipHostMallocMapped) != hipSuccess) return nullptr;
-        cap_of_last = bytes;
-        return static_cast<char*>(p);
+        if (hipHostMalloc(&p, bytes, hipHostMallocMapped) != hipSuccess) return {nullptr, 0};
+        return {static_cast<char*>(p), bytes};
     }
-    void give(char* p, size_t bytes) {
+    void give(std::pair<char*, size_t> b) {
         std::lock_guard<std::mutex> g(mu);
-        if (free_list.size() < 64) free_list.emplace_back(p, bytes);
-        else (void)hipHostFree(p);
+        if (free_list.size() < 64) free_list.push_back(b);
+        else (void)hipHostFree(b.first);
     }
-    static thread_local size_t cap_of_last;
 };
-thread_local size_t PinnedPool::cap_of_last = 0;
 PinnedPool g_pinned;
+
+// a pool buffer for the length of a call
+struct PinnedLease {
+    const std::pair<char*, size_t> buf;
+    explicit PinnedLease(size_t bytes) : buf(g_pinned.take(bytes)) {}
+    ~PinnedLease() { if (buf.first) g_pinned.give(buf); }
+    PinnedLease(const PinnedLease&) = delete;
+    PinnedLease& operator=(const PinnedLease&) = delete;
+};
 
 }  // namespace
 
-int cv_decode_f32_ev(float* d_grid_obj, const float* d_grid_rot, const float* d_grid_scale,
-                     const int dims[3], const float h_corner3[3], float res, const float* d_points,
-                     const float* d_xyz, const float* d_prob, const int32_t* d_class, int64_t n,
-                     const cv_decode_params* params, int mutate_grid, void* d_ws, size_t ws_bytes,
-                     int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes,
-                     float* h_boxes, float* h_scores, int32_t* h_classes, int* h_truncated, void* stream, void* ev_done);
-
-extern "C" {
-
-size_t cv_decode_workspace_bytes(const int dims[3], int64_t n, int max_iters) {
-    if (!dims || max_iters <= 0) return 0;
-    (void)n;
-    return WsLayout((int64_t)dims[0] * dims[1] * dims[2], max_iters).total;
-}
-
-int cv_decode_f32(float* d_grid_obj, const float* d_grid_rot, const float* d_grid_scale,
-                  const int dims[3], const float h_corner3[3], float res, const float* d_points,
-                  const float* d_xyz, const float* d_prob, const int32_t* d_class, int64_t n,
-                  const cv_decode_params* params, int mutate_grid, void* d_ws, size_t ws_bytes,
-                  int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes,
-                  float* h_boxes, float* h_scores, int32_t* h_classes, int* h_truncated, void* stream) {
-    return cv_decode_f32_ev(d_grid_obj, d_grid_rot, d_grid_scale, dims, h_corner3, res, d_points, d_xyz, d_prob, d_class, n, params,
-                            mutate_grid, d_ws, ws_bytes, h_n_cand, h_cand_idx, h_verdict, h_n_boxes, h_boxes, h_scores, h_classes,
-                            h_truncated, stream, nullptr);
-}
-
-}  // extern "C"
-
-// K categories (K = 1: cv_decode_f32).  Validation is the caller's; category k's host outputs at k, k * M, k * M * 24.
-static int decode_cats(float* d_grid_obj, const float* d_grid_rot, const float* d_grid_scale, const int dims[3],
-                       const float h_corner3[3], float res, const float* d_points, const float* d_xyz, const float* d_prob,
-                       const int32_t* d_class, int64_t n, int K, const cv_decode_params* params, int mutate_grid, void* d_ws,
-                       size_t ws_bytes, int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes, float* h_boxes,
-                       float* h_scores, int32_t* h_classes, int* h_truncated, hipStream_t st, void* ev_done) {
+// (C++ linkage, cv_common.h) K categories; category k's host outputs at k, k * M, k * M * 24
+int cv_decode_run(const DecodeCall& c, int K, bool need_class) {
+    CV_REQUIRE(K >= 1 && K <= CV_MAX_CATEGORIES, CV_EINVAL, "num_cats out of range (%d, 1..%d)", K, CV_MAX_CATEGORIES);
+    CV_REQUIRE(c.d_grid_obj && c.d_grid_rot && c.d_grid_scale && c.dims && c.h_corner3 && c.d_points && c.d_xyz && c.d_prob &&
+                   (c.d_class || !need_class) && c.params && c.d_ws && c.h_n_cand && c.h_cand_idx && c.h_verdict && c.h_n_boxes &&
+                   c.h_boxes && c.h_scores && c.h_classes,
+               CV_EINVAL, "null pointer argument");
+    const int* dims = c.dims;
+    const cv_decode_params* params = c.params;
+    const int64_t n = c.n;
+    hipStream_t st = static_cast<hipStream_t>(c.stream);
     CV_REQUIRE(n > 0, CV_EINVAL, "n must be positive");
-    CV_REQUIRE(res > 0.f, CV_EINVAL, "res must be positive");
+    CV_REQUIRE(c.res > 0.f, CV_EINVAL, "res must be positive");
     CV_REQUIRE(dims[0] > 0 && dims[1] > 0 && dims[2] > 0, CV_EINVAL, "bad grid dims");
     CV_REQUIRE(dims[0] < 65536 && dims[1] < 65536 && dims[2] < 65536, CV_EINVAL, "grid dims must be below 65536");
     const int64_t G = (int64_t)dims[0] * dims[1] * dims[2];
@@ -970,118 +901,82 @@ static int decode_cats(float* d_grid_obj, const float* d_grid_rot, const float* 
     CV_REQUIRE(params->thresh_high > 0.f, CV_EINVAL, "thresh_high must be positive");
     const WsLayout W(G, M);
     const size_t need = (size_t)K * W.total;
-    CV_REQUIRE(ws_bytes >= need, CV_ENOMEM, "workspace too small (%zu < %zu)", ws_bytes, need);
-    char* ws = static_cast<char*>(d_ws);
-    List L;
-    L.idx = reinterpret_cast<int*>(ws + W.off_list_idx);
-    L.val = reinterpret_cast<float*>(ws + W.off_list_val);
-    L.xy = reinterpret_cast<unsigned*>(ws + W.off_list_xy);
-    L.z = reinterpret_cast<int*>(ws + W.off_list_z);
-    L.geo = reinterpret_cast<float*>(ws + W.off_list_geo);
-    L.cap = G;
-    unsigned* list_n = reinterpret_cast<unsigned*>(ws + W.off_counters);
-    int* n_cand = reinterpret_cast<int*>(ws + W.off_counters + 16);
-    Cand* cands = reinterpret_cast<Cand*>(ws + W.off_cands);
-    Stats* stats = reinterpret_cast<Stats*>(ws + W.off_stats);
+    CV_REQUIRE(c.ws_bytes >= need, CV_ENOMEM, "workspace too small (%zu < %zu)", c.ws_bytes, need);
+    const Ws w = W.at(static_cast<char*>(c.d_ws));
     const ResultLayout RL(M);
-    char* host = g_pinned.take((size_t)K * RL.total);
+    const PinnedLease lease((size_t)K * RL.total);
+    char* host = lease.buf.first;
     CV_REQUIRE(host != nullptr, CV_ENOMEM, "pinned host buffer of %zu bytes", (size_t)K * RL.total);
-    const size_t host_cap = PinnedPool::cap_of_last;
-    struct Giveback {
-        char* p; size_t cap;
-        ~Giveback() { g_pinned.give(p, cap); }
-    } giveback{host, host_cap};
     const CatStride ks{K > 1 ? (int64_t)W.total : 0, n, G};
 
-    if (K == 1) CV_HIP_CHECK(hipMemsetAsync(ws + W.off_counters, 0, 64, st));
+    if (K == 1) CV_HIP_CHECK(hipMemsetAsync(w.counters, 0, sizeof(unsigned) * CTR_WORDS, st));
     else {
-        dec_zero_counters<<<dim3(1, K), 64, 0, st>>>(list_n, ks.ws);
+        dec_zero_counters<<<dim3(1, K), 64, 0, st>>>(w, ks.ws);
         CV_LAUNCH_CHECK();
     }
-    Geo geo{dims[0], dims[1], dims[2], {h_corner3[0], h_corner3[1], h_corner3[2]}, res};
+    Geo geo{dims[0], dims[1], dims[2], {c.h_corner3[0], c.h_corner3[1], c.h_corner3[2]}, c.res};
     const int cblocks = (int)std::min<int64_t>((G + 255) / 256, 2048);
-    dec_compact<<<dim3(cblocks, K), 256, 0, st>>>(d_grid_obj, d_grid_rot, d_grid_scale, geo, G, params->thresh_high, L,
-                                                  list_n, ks);
+    dec_compact<<<dim3(cblocks, K), 256, 0, st>>>(c.d_grid_obj, c.d_grid_rot, c.d_grid_scale, geo, G, params->thresh_high, w, ks);
     CV_LAUNCH_CHECK();
-    // the list length is only known on the device: the LDS-resident walker takes lists up to GREEDY_CAP, longer ones
-    // the same code over the global arrays - both are launched, the one that does not apply returns at once
-    // (grids beyond 4 M cells - 300k-point scenes - list more cells than the 256-thread walker keeps in registers)
+    // the walk is chosen by the kernel from the list length; the host only chooses the workgroup: grids beyond 4 M cells
+    // (300k-point scenes) list more cells than the 512-thread walker keeps in registers
     static const long long big_cells = getenv("CV_DEC_BIG_CELLS") ? atoll(getenv("CV_DEC_BIG_CELLS")) : (4ll << 20);
-    // (round 6, profiles/r6/decode_in_flight.txt: a walk with the whole list in registers and no 115 KB LDS copy - placeable next
-    // to any workgroup - and s_setprio 3 on the walk's waves were built and measured with seven scenes in flight: 0.213 against
-    // 0.198 ms in the timed region, 0.163 against 0.147 alone, no change of the scene rate; what round 5 read as "decode takes
-    // 4-14 x longer under load" was the host's wake-up behind the stream wait, inside the stage's event pair - the event now sits
-    // in front of the wait)
-    if (G > big_cells)
-        dec_greedy_dispatch_big<<<dim3(1, K), GREEDY_T_BIG, 0, st>>>(geo, *params, L, list_n, cands, stats, n_cand, ks.ws);
-    else dec_greedy_dispatch<<<dim3(1, K), GREEDY_T, 0, st>>>(geo, *params, L, list_n, cands, stats, n_cand, ks.ws);
+    if (G > big_cells) dec_greedy_dispatch_big<<<dim3(1, K), GREEDY_T_BIG, 0, st>>>(geo, *params, w, ks.ws);
+    else dec_greedy_dispatch<<<dim3(1, K), GREEDY_T, 0, st>>>(geo, *params, w, ks.ws);
     CV_LAUNCH_CHECK();
     // candidate groups of 8 over blockIdx.y (the count is only known on the device: groups beyond it return at once)
     const dim3 bgrid((unsigned)((n + 255) / 256), (unsigned)std::min((M + 7) / 8, 8), (unsigned)K);
-    dec_backproject<<<bgrid, 256, 0, st>>>(
-        d_points, d_xyz, d_prob, d_class, n, params->prob_thresh, cands, n_cand, stats, ks);
+    dec_backproject<<<bgrid, 256, 0, st>>>(c.d_points, c.d_xyz, c.d_prob, c.d_class, n, params->prob_thresh, w, ks);
     CV_LAUNCH_CHECK();
-    dec_finalize<<<dim3(1, K), 256, 0, st>>>(cands, stats, n_cand, *params, host, M, ks.ws, (int64_t)RL.total);
+    dec_finalize<<<dim3(1, K), 256, 0, st>>>(w, *params, host, M, ks.ws, (int64_t)RL.total);
     CV_LAUNCH_CHECK();
-    if (mutate_grid) {
-        dec_apply<<<dim3(M, K), 256, 0, st>>>(d_grid_obj, geo, *params, cands, n_cand, ks);
+    if (c.mutate_grid) {
+        dec_apply<<<dim3(M, K), 256, 0, st>>>(c.d_grid_obj, geo, *params, w, ks);
         CV_LAUNCH_CHECK();
     }
-    if (ev_done) CV_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(ev_done), st));
+    // (the event sits in front of the host's wait, so that the stage time it closes is a device time)
+    if (c.ev_done) CV_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(c.ev_done), st));
     CV_HIP_CHECK(hipStreamSynchronize(st));
     for (int k = 0; k < K; ++k) {
         const char* hk = host + (size_t)k * RL.total;
         const int* hdr = reinterpret_cast<const int*>(hk);
         const int nc = hdr[0], nb = hdr[1];
         CV_REQUIRE(nc >= 0 && nc <= M && nb >= 0 && nb <= nc, CV_ERANGE, "corrupt decode result");
-        h_n_cand[k] = nc;
-        h_n_boxes[k] = nb;
-        if (h_truncated) h_truncated[k] = hdr[2];
-        std::memcpy(h_cand_idx + (size_t)k * M, hk + RL.off_cand, sizeof(int64_t) * nc);
-        std::memcpy(h_verdict + (size_t)k * M, hk + RL.off_verdict, sizeof(int32_t) * nc);
-        std::memcpy(h_boxes + (size_t)k * M * 24, hk + RL.off_boxes, sizeof(float) * 24 * nb);
-        std::memcpy(h_scores + (size_t)k * M, hk + RL.off_scores, sizeof(float) * nb);
-        std::memcpy(h_classes + (size_t)k * M, hk + RL.off_classes, sizeof(int32_t) * nb);
+        c.h_n_cand[k] = nc;
+        c.h_n_boxes[k] = nb;
+        if (c.h_truncated) c.h_truncated[k] = hdr[2];
+        std::memcpy(c.h_cand_idx + (size_t)k * M, hk + RL.off_cand, sizeof(int64_t) * nc);
+        std::memcpy(c.h_verdict + (size_t)k * M, hk + RL.off_verdict, sizeof(int32_t) * nc);
+        std::memcpy(c.h_boxes + (size_t)k * M * 24, hk + RL.off_boxes, sizeof(float) * 24 * nb);
+        std::memcpy(c.h_scores + (size_t)k * M, hk + RL.off_scores, sizeof(float) * nb);
+        std::memcpy(c.h_classes + (size_t)k * M, hk + RL.off_classes, sizeof(int32_t) * nb);
     }
     return CV_OK;
 }
 
-int cv_decode_f32_ev(float* d_grid_obj, const float* d_grid_rot, const float* d_grid_scale,
-                     const int dims[3], const float h_corner3[3], float res, const float* d_points,
-                     const float* d_xyz, const float* d_prob, const int32_t* d_class, int64_t n,
-                     const cv_decode_params* params, int mutate_grid, void* d_ws, size_t ws_bytes,
-                     int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes,
-                     float* h_boxes, float* h_scores, int32_t* h_classes, int* h_truncated, void* stream, void* ev_done) {
-    CV_REQUIRE(d_grid_obj && d_grid_rot && d_grid_scale && dims && h_corner3 && d_points && d_xyz &&
-                   d_prob && d_class && params && d_ws && h_n_cand && h_cand_idx && h_verdict &&
-                   h_n_boxes && h_boxes && h_scores && h_classes,
-               CV_EINVAL, "null pointer argument");
-    return decode_cats(d_grid_obj, d_grid_rot, d_grid_scale, dims, h_corner3, res, d_points, d_xyz, d_prob, d_class, n, 1, params,
-                       mutate_grid, d_ws, ws_bytes, h_n_cand, h_cand_idx, h_verdict, h_n_boxes, h_boxes, h_scores, h_classes,
-                       h_truncated, static_cast<hipStream_t>(stream), ev_done);
-}
-
-// (C++ linkage, cv_common.h) the scene call's K-category decode with its "decode done" event
-int cv_decode_cat_f32_ev(float* d_grid_obj, const float* d_grid_rot, const float* d_grid_scale, const int dims[3],
-                         const float h_corner3[3], float res, const float* d_points, const float* d_xyz, const float* d_prob,
-                         const int32_t* d_class, int64_t n, int num_cats, const cv_decode_params* params, int mutate_grid,
-                         void* d_ws, size_t ws_bytes, int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes,
-                         float* h_boxes, float* h_scores, int32_t* h_classes, int* h_truncated, void* stream, void* ev_done) {
-    CV_REQUIRE(num_cats >= 1 && num_cats <= CV_MAX_CATEGORIES, CV_EINVAL, "num_cats out of range (%d, 1..%d)", num_cats,
-               CV_MAX_CATEGORIES);
-    CV_REQUIRE(d_grid_obj && d_grid_rot && d_grid_scale && dims && h_corner3 && d_points && d_xyz && d_prob && params && d_ws &&
-                   h_n_cand && h_cand_idx && h_verdict && h_n_boxes && h_boxes && h_scores && h_classes,
-               CV_EINVAL, "null pointer argument");
-    return decode_cats(d_grid_obj, d_grid_rot, d_grid_scale, dims, h_corner3, res, d_points, d_xyz, d_prob, d_class, n, num_cats,
-                       params, mutate_grid, d_ws, ws_bytes, h_n_cand, h_cand_idx, h_verdict, h_n_boxes, h_boxes, h_scores,
-                       h_classes, h_truncated, static_cast<hipStream_t>(stream), ev_done);
-}
-
 extern "C" {
+
+size_t cv_decode_workspace_bytes(const int dims[3], int64_t n, int max_iters) {
+    if (!dims || max_iters <= 0) return 0;
+    (void)n;
+    return WsLayout((int64_t)dims[0] * dims[1] * dims[2], max_iters).total;
+}
 
 size_t cv_decode_cat_workspace_bytes(const int dims[3], int64_t n, int max_iters, int num_cats) {
     if (num_cats < 1 || num_cats > CV_MAX_CATEGORIES) return 0;
     return (size_t)num_cats * cv_decode_workspace_bytes(dims, n, max_iters);
+}
+
+int cv_decode_f32(float* d_grid_obj, const float* d_grid_rot, const float* d_grid_scale,
+                  const int dims[3], const float h_corner3[3], float res, const float* d_points,
+                  const float* d_xyz, const float* d_prob, const int32_t* d_class, int64_t n,
+                  const cv_decode_params* params, int mutate_grid, void* d_ws, size_t ws_bytes,
+                  int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes,
+                  float* h_boxes, float* h_scores, int32_t* h_classes, int* h_truncated, void* stream) {
+    const DecodeCall c{d_grid_obj, d_grid_rot, d_grid_scale, dims, h_corner3, res, d_points, d_xyz, d_prob, d_class, n, params,
+                       mutate_grid, d_ws, ws_bytes, h_n_cand, h_cand_idx, h_verdict, h_n_boxes, h_boxes, h_scores, h_classes,
+                       h_truncated, stream, nullptr};
+    return cv_decode_run(c, 1, true);
 }
 
 int cv_decode_cat_f32(float* d_grid_obj, const float* d_grid_rot, const float* d_grid_scale, const int dims[3],
@@ -1089,9 +984,10 @@ int cv_decode_cat_f32(float* d_grid_obj, const float* d_grid_rot, const float* d
                       const int32_t* d_class, int64_t n, int num_cats, const cv_decode_params* params, int mutate_grid, void* d_ws,
                       size_t ws_bytes, int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes, float* h_boxes,
                       float* h_scores, int32_t* h_classes, int* h_truncated, void* stream) {
-    return cv_decode_cat_f32_ev(d_grid_obj, d_grid_rot, d_grid_scale, dims, h_corner3, res, d_points, d_xyz, d_prob, d_class, n,
-                                num_cats, params, mutate_grid, d_ws, ws_bytes, h_n_cand, h_cand_idx, h_verdict, h_n_boxes, h_boxes,
-                                h_scores, h_classes, h_truncated, stream, nullptr);
+    const DecodeCall c{d_grid_obj, d_grid_rot, d_grid_scale, dims, h_corner3, res, d_points, d_xyz, d_prob, d_class, n, params,
+                       mutate_grid, d_ws, ws_bytes, h_n_cand, h_cand_idx, h_verdict, h_n_boxes, h_boxes, h_scores, h_classes,
+                       h_truncated, stream, nullptr};
+    return cv_decode_run(c, num_cats, false);
 }
 
 }  // extern "C"

@@ -230,8 +230,9 @@ int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream
     prm.max_iters = d->max_candidates;
     int n_cand = 0, n_boxes = 0, truncated = 0;
     // (events[4] is recorded behind the decode's last launch, in front of its host wait: a device time)
-    rc = cv_decode_f32_ev(g_obj, g_rot, g_scale, f.dims, f.mn, d->res, d->d_points, v_xyz, v_prob, v_cls, n, &prm, 0, dec_ws, dec_ws_b, &n_cand,
-                          d->h_cand_idx, d->h_verdict, &n_boxes, d->h_boxes, d->h_scores, d->h_classes, &truncated, stream, d->events[4]);
+    const DecodeCall dc{g_obj, g_rot, g_scale, f.dims, f.mn, d->res, d->d_points, v_xyz, v_prob, v_cls, n, &prm, 0, dec_ws, dec_ws_b, &n_cand,
+                        d->h_cand_idx, d->h_verdict, &n_boxes, d->h_boxes, d->h_scores, d->h_classes, &truncated, stream, d->events[4]};
+    rc = cv_decode_run(dc, 1, true);
     if (rc != CV_OK) return rc;
     r->n_cand = n_cand;
     r->n_boxes = n_boxes;
@@ -383,9 +384,10 @@ int cv_detect_scene_separate_f32(const cv_scene_separate_desc* d, cv_scene_separ
     prm.max_iters = d->max_candidates;
     const int M = d->max_candidates;
     std::vector<int32_t> classes((size_t)K * M);
-    rc = cv_decode_cat_f32_ev(g_obj, g_rot, g_scale, f.dims, f.mn, d->res, d->d_points, v_xyz, v_prob, nullptr, n, K, &prm, 0, dec_ws,
-                              dec_ws_b, r->n_cand, d->h_cand_idx, d->h_verdict, r->n_boxes, d->h_boxes, d->h_scores, classes.data(),
-                              r->truncated, stream, d->events[4]);
+    const DecodeCall dc{g_obj, g_rot, g_scale, f.dims, f.mn, d->res, d->d_points, v_xyz, v_prob, nullptr, n, &prm, 0, dec_ws, dec_ws_b,
+                        r->n_cand, d->h_cand_idx, d->h_verdict, r->n_boxes, d->h_boxes, d->h_scores, classes.data(), r->truncated, stream,
+                        d->events[4]};
+    rc = cv_decode_run(dc, K, false);
     if (rc != CV_OK) return rc;
     // (the decode waited for the stream: the range flags of the K programs have landed)
     if (d->use_range_flag)

@@ -158,14 +158,74 @@ def test_hip_path_matches_reference_lines_executed_on_cpu(cuda, built_lib, name)
     assert np.array_equal(zeroed, z["zeroed"].astype(zeroed.dtype))
 
 
+def dense_case(seed, dims, res=0.05, n=2000):
+    """every cell listed (values 60..63 against thresh_high = 60: heavy ties), random yaw and box scale per cell, random
+    points / predictions / classes: lists far longer than any scene's, hundreds of candidates"""
+    rng = np.random.default_rng(seed)
+    g_obj = rng.integers(60, 64, dims).astype(np.float32)
+    yaw = rng.uniform(-np.pi, np.pi, dims)
+    g_rot = np.stack([np.cos(yaw), np.sin(yaw)], -1).astype(np.float32)
+    g_scale = rng.uniform(0.03, 0.12, dims + (3,)).astype(np.float32)
+    pts = (rng.uniform(0, 1, (n, 3)) * (np.array(dims) * res)).astype(np.float32)
+    xyz = rng.uniform(-1, 1, (n, 3)).astype(np.float32)
+    prob = rng.uniform(0, 1, n).astype(np.float32)
+    cls = rng.integers(0, 9, n).astype(np.int32)
+    assert int((g_obj >= 60).sum()) == dims[0] * dims[1] * dims[2]
+    return g_obj, g_rot, g_scale, pts, xyz, prob, cls
+
+
+def test_decode_global_walk_9k(cuda, built_lib):
+    """9216 listed cells: more than the 4096 the register + LDS walk holds, so the default dispatch takes the walk over the
+    global arrays (it zeroes suppressed values in the list).  With CV_DEC_BIG_CELLS=1 (the test below) the same list fills
+    the sorted walk at 9 entries per thread."""
+    g_obj, g_rot, g_scale, pts, xyz, prob, cls = dense_case(1, (24, 16, 24))
+    ref, _ = compare(cuda, g_obj, g_rot, g_scale, np.zeros(3, np.float32), 0.05, pts, xyz, prob, cls, max_candidates=1024)
+    assert len(ref["cand_idx"]) >= 200
+    assert {1, 2} <= set(ref["verdict"])
+
+
+def test_decode_global_walk_32k(cuda, built_lib):
+    """32000 listed cells: more than the 24576 the big grids' dispatch holds in registers - with CV_DEC_BIG_CELLS=1 its
+    1024-thread walk over the global arrays, in the default process one more case of the 512-thread one"""
+    g_obj, g_rot, g_scale, pts, xyz, prob, cls = dense_case(1, (40, 20, 40))
+    ref, _ = compare(cuda, g_obj, g_rot, g_scale, np.zeros(3, np.float32), 0.05, pts, xyz, prob, cls, max_candidates=4096)
+    assert len(ref["cand_idx"]) >= 600
+
+
+def test_decode_global_walk_two_categories(cuda, built_lib):
+    """two 9216-cell lists through decode_boxes_categories: the global-array walk zeroes list values through the category
+    stride of the workspace, and each category must still be its own oracle decode (scan points and classes are shared)"""
+    a, b = dense_case(1, (24, 16, 24)), dense_case(2, (24, 16, 24))
+    pts, cls = a[3], a[6]
+    corner = np.zeros(3, np.float32)
+    stack = lambda i: t(cuda, np.stack([a[i], b[i]]))
+    dg = stack(0)
+    got = decode.decode_boxes_categories(dg, stack(1), stack(2), t(cuda, pts), stack(4), stack(5), 0.05, class_pred=t(cuda, cls),
+                                         corner=corner, max_candidates=1024, mutate_grid=True)
+    assert len(got) == 2
+    for k, c in enumerate((a, b)):
+        ref = oracle.decode(c[0], c[1], c[2], corner, 0.05, pts, c[4], c[5], cls, oracle.DecodeParams.default(max_iters=1024))
+        assert len(ref["cand_idx"]) >= 200
+        assert list(got[k]["cand_idx"]) == list(ref["cand_idx"])
+        assert list(got[k]["verdict"]) == list(ref["verdict"])
+        assert list(got[k]["classes"]) == list(ref["classes"])
+        assert not got[k]["truncated"]
+        np.testing.assert_allclose(got[k]["boxes"], ref["boxes"].reshape(-1, 8, 3), rtol=0, atol=1e-6)
+        np.testing.assert_allclose(got[k]["scores"], ref["scores"], rtol=0, atol=0)
+        assert np.array_equal(dg[k].cpu().numpy(), ref["grid_obj_after"])
+    assert list(got[0]["cand_idx"]) != list(got[1]["cand_idx"])
+
+
 def test_sorted_walker_of_the_big_grids_on_the_small_cases(cuda, built_lib):
     """Grids beyond 4 M cells (300k-point scenes) take dec_greedy_dispatch_big: the sorted register-resident walk
-    (dec_greedy_sorted).  The oracle / planted-tie / iteration-cap / reference-line cases of this file are run through it
-    too: CV_DEC_BIG_CELLS=1 sends every grid that way (read once per process, hence a fresh interpreter).  The 300k-point
-    scene itself is compared with the oracle in test_production_size_gpu.py."""
+    (walk_sorted).  The oracle / planted-tie / iteration-cap / reference-line cases of this file are run through it
+    too: CV_DEC_BIG_CELLS=1 sends every grid that way (read once per process, hence a fresh interpreter); of the two dense
+    grids the 9 216-cell one fills that walk at 9 entries per thread and the 32 000-cell one takes its 1024-thread walk over
+    the global arrays.  The 300k-point scene itself is compared with the oracle in test_production_size_gpu.py."""
     env = dict(os.environ, CV_DEC_BIG_CELLS="1")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-m", "gpu", "-p", "no:cacheprovider",
-                        "-k", "oracle_grids or planted_ties or iteration_cap or reference_lines or end_to_end_80k"],
+                        "-k", "oracle_grids or planted_ties or iteration_cap or reference_lines or end_to_end_80k or global_walk_9k or "
+                              "global_walk_32k"],
                        env=env, capture_output=True, text=True, timeout=900,
                        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
