@@ -46,8 +46,8 @@ struct CvCarver {
     }
 };
 
-// ---- internal batch launches (one launch for the jobs of a whole scene instead of one per map; used by
-//      cv_sp_scene_maps; C++ linkage, not part of the C ABI) ----------------------------------------------------
+// ---- internal batch launches (one launch for the jobs of a whole scene instead of one per map; used by the coordinate
+//      plan, cv_sp_scene_plan_ex and cv_sp_scene_maps in net_exec.cpp; C++ linkage, not part of the C ABI) ---------------
 struct CvMapJob {            // kernel map: out set looked up in an input set's hash table
     const int32_t* out_coords; long long n_out;
     const unsigned long long* keys; const int32_t* vals; long long cap;
@@ -55,7 +55,7 @@ struct CvMapJob {            // kernel map: out set looked up in an input set's 
     int32_t* nbr;
     const int32_t* compose;  // optional: store compose[row] instead of row (a permutation folded into the map)
     const unsigned* bitmap;  // optional (ts == 1 maps of the set the bitmap was built from): occupancy bits in front of the
-    const int32_t* bbox;     // hash probes, see cv_sp_occupancy_bitmap; bbox = the 8 ints of cv_sp_sort_rows' bounds
+    const int32_t* bbox;     // hash probes, see CV_BITMAP_WORDS; bbox = the 8 ints of cv_sp_sort_rows' bounds
     int up;                  // 1: transposed k2s2 map instead - out_coords are the FINE rows (tensor stride ts), keys / vals the
                              // table of the next coarser level, nbr[n_out][8] = parent row in the octant column, -1 elsewhere
     int32_t* nbr3;           // optional (k == 5, ts == 1): the 3x3x3 map of the same set [n_out][27] (rows NOT composed) is built
@@ -66,30 +66,26 @@ struct CvMapJob {            // kernel map: out set looked up in an input set's 
 constexpr int CV_MAX_MAP_JOBS = 12;
 int cv_sp_kernel_maps_batch(const CvMapJob* jobs, int n_jobs, void* stream);
 // Occupancy bitmap of a coordinate set over its bounding box (d_bbox: mm[0..2] = min, mm[3..5] = -max per axis, mm[6] =
-// -max batch, as left by cv_sp_sort_rows at the start of its workspace): 87 % of a scene's kernel-map lookups are
-// misses, each ~2 random probes into a 2 MB table; a bit test against ~0.5 MB with neighbouring lookups in the same words
-// answers them.  d_bits: CV_BITMAP_WORDS words; when the box does not fit (or a batch index is negative) the kernels
-// that take the bitmap ignore it (they re-derive the same test from the bounds).  Two launches, asynchronous.
+// -max batch, as left by cv_sp_sort_rows at the start of its workspace; mm[7] = 1 while the bitmap may be trusted): 87 % of a
+// scene's kernel-map lookups are misses, each ~2 random probes into a 2 MB table; a bit test against ~0.5 MB with
+// neighbouring lookups in the same words answers them.  d_bits: CV_BITMAP_WORDS words, zeroed by the first launch of
+// cv_sp_build_levels_zero and filled by its insert pass (insert_all) on the way.  When the box does not fit (or a batch index
+// is negative: insert_all then clears mm[7]) the kernels that take the bitmap ignore it (they re-derive the same test from
+// the bounds).
 constexpr long long CV_BITMAP_WORDS = 1ll << 20;
-// pre_cleared: the words are zero and d_bbox[7] == 1 already (cv_sp_build_levels_zero did it): one launch
-int cv_sp_occupancy_bitmap(const int32_t* d_coords, long long n, const int32_t* d_bbox, unsigned* d_bits, void* stream,
-                           bool pre_cleared = false);
 
-// cv_sp_build_levels with an extra range of words zeroed by its first launch (saves the caller's fill launches)
+// cv_sp_build_levels with an extra range of words zeroed by its first launch (d_zero / n_zero, may be null / 0: saves the
+// caller's fill launches) and, with d_bbox / d_bits (both or neither; d_bits lies inside the zeroed range), the occupancy bitmap
 int cv_sp_build_levels_zero(int32_t* const* d_coords, unsigned long long* const* d_keys, int32_t* const* d_vals,
                             long long n, long long cap, int num_levels, int32_t* d_counts, int32_t* h_counts, void* d_ws,
-                            size_t ws_bytes, int32_t* d_zero, long long n_zero, int32_t* d_set_one, void* stream,
-                            uint32_t* d_bits = nullptr);       // d_bits: the occupancy bitmap (inside the zeroed range) is filled too
-
-struct CvUpJob { const int32_t* nbr_down; long long n_coarse; int32_t* up; };
-int cv_sp_up_maps_batch(const CvUpJob* jobs, int n_jobs, void* stream);      // the up arrays must be pre-filled with -1
+                            size_t ws_bytes, int32_t* d_zero, long long n_zero, int32_t* d_bbox, uint32_t* d_bits,
+                            void* stream);                                                  // sparse_coords.hip
 
 struct CvPermJob {
     const int32_t* nbr; long long n; int K, groups; int32_t* perm; int with_map;
     const int32_t* mask_words;   // optional (K <= 32): bit j of word [row] = nbr[row][j] >= 0, from the map builder (CvMapJob)
 };
 constexpr int CV_MAX_PERM_JOBS = 8;
-// d_ws: (sum of groups) * 1024 ints, zero-filled by the call (unless pre_zeroed)
 int cv_hv_minmax_async_ex(const float* d_points, int64_t n, float* h_minmax6, void* d_ws, size_t ws_bytes, int32_t* d_zero_word,
                           int32_t* d_fill7f, void* stream);                                // hv_vote.hip
 // One decode call (hv_decode.hip): what cv_decode_f32 / cv_decode_cat_f32 take, in their order, plus an optional event
@@ -108,15 +104,16 @@ struct DecodeCall {
 // need_class: d_class must not be NULL (the joint model's class vote; the separate models pass none: class 0)
 int cv_decode_run(const DecodeCall& c, int num_cats, bool need_class);
 int cv_sp_sort_rows_ex(const int32_t* d_coords, long long n, int32_t* d_sorted, int32_t* d_perm, int32_t* d_inv, void* d_ws,
-                       size_t ws_bytes, bool single_batch, void* stream, bool bounds_prefilled = false);   // sparse_coords.hip
+                       size_t ws_bytes, bool single_batch, void* stream, bool bounds_prefilled);           // sparse_coords.hip
 int cv_sp_scene_plan_ex(const int32_t* d_input, long long n, int32_t* d_perm, int32_t* d_inv, int32_t* const* d_coords,
                         unsigned long long* const* d_keys, int32_t* const* d_vals, long long cap, int32_t* d_counts,
                         int32_t* h_counts, int stem_k, int mask_groups, long long masked_min_rows,
                         int32_t* d_arena, size_t arena_words, cv_scene_maps* offsets, void* d_sort_ws, size_t sort_ws_bytes,
                         void* d_levels_ws, size_t levels_ws_bytes, bool single_batch, void* stream,
-                        bool bounds_prefilled = false);                                       // net_exec.cpp
+                        bool bounds_prefilled);                                               // net_exec.cpp
+// d_ws: (sum of groups) * 2048 ints, zero-filled by the call unless pre_zeroed
 int cv_sp_mask_perms_batch(const CvPermJob* jobs, int n_jobs, void* d_ws, size_t ws_bytes, void* stream,
-                           bool pre_zeroed = false);
+                           bool pre_zeroed);                                                // sparse_conv.hip
 
 // cv_sp_conv_f32 over the model axis (cv_net_run_models_f32): `d` describes model 0; the operands of model m are model 0's
 // plus m x the byte strides (0 = shared), its packed weights / affine / acc_scale row m of d_params, its workspace

@@ -5,7 +5,6 @@
 // C call per scene issues every launch: the Python layer's per-conv overhead (descriptor marshalling, tensor
 // allocation, ~35 us x 63) is what bounded the scene rate once several scenes were in flight.
 #include <algorithm>
-#include <cstdlib>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
@@ -37,8 +36,8 @@ extern "C" {
 
 // ---- every kernel map and processing order of the fused network in ONE call per scene ----------------------
 // (the Python coordinate manager issued ~25 calls for them: 0.65 ms of host time per scene on the critical path)
-static void scene_maps_layout(const long long* rows, long long n_orig, int stem_k, int mask_groups,
-                              long long masked_min_rows, cv_scene_maps* o, size_t* total) {
+static void scene_maps_layout(const long long* rows, int stem_k, int mask_groups, long long masked_min_rows, cv_scene_maps* o,
+                              size_t* total) {
     size_t off = 0;
     auto take = [&](size_t words) { const size_t at = off; off += cv_align_up(words, 64); return (long long)at; };
     const size_t K5 = (size_t)stem_k * stem_k * stem_k;
@@ -53,9 +52,8 @@ static void scene_maps_layout(const long long* rows, long long n_orig, int stem_
     // bin counts + running counts of the mask orders (cv_sp_mask_perms_batch: 2 x 1024 words per group): level 0, then <= 4
     // coarse levels and the 4 up-map orders
     o->scratch = take((size_t)(5 * std::max(mask_groups, 1) + 4) * 2048);
-    o->bitmap = take((size_t)CV_BITMAP_WORDS);          // occupancy bits of the level-0 set (cv_sp_scene_plan only)
+    o->bitmap = take((size_t)CV_BITMAP_WORDS);          // occupancy bits of the level-0 set (filled by cv_sp_scene_plan only)
     o->out = -1;                       // (the sort's inverse permutation is the final map)
-    (void)n_orig;
     for (int i = 0; i < 4; ++i) o->down[i] = take((size_t)rows[i + 1] * 8);
     for (int i = 1; i < 5; ++i) o->k3[i] = take((size_t)rows[i] * 28);
     for (int i = 0; i < 4; ++i) o->up[i] = take((size_t)rows[3 - i] * 8);            // up[i]: level 4-i -> 3-i
@@ -72,25 +70,18 @@ size_t cv_sp_scene_maps_words(const long long* level_rows, long long n_orig, int
                               long long masked_min_rows, cv_scene_maps* offsets) {
     if (!level_rows || !offsets || n_orig <= 0 || stem_k < 1) return 0;
     size_t total = 0;
-    scene_maps_layout(level_rows, n_orig, stem_k, mask_groups, masked_min_rows, offsets, &total);
+    scene_maps_layout(level_rows, stem_k, mask_groups, masked_min_rows, offsets, &total);
     return total;
 }
 
 // level-0 part (needs the caller's row count only): the stem map with the sort permutation folded in, the 3x3x3 map of
-// the finest level and its mask-sorted orders
+// the finest level and its mask-sorted orders.  d_bbox: the sort's bound words when cv_sp_scene_plan_ex calls - the
+// level build has filled the occupancy bitmap in front of the hash probes and zeroed the scratch; null from cv_sp_scene_maps
+// (no bitmap, the mask orders zero their scratch themselves)
 static int scene_maps_level0(int32_t* const* d_coords, const unsigned long long* const* d_keys, const int32_t* const* d_vals,
                              long long cap, long long n, const int32_t* d_perm, int stem_k, int mask_groups,
-                             const cv_scene_maps& o, int32_t* d_arena, const int32_t* d_bbox, void* stream,
-                             bool pre_cleared = false, bool bitmap_filled = false) {
-    const unsigned* bits = nullptr;
-    if (d_bbox) {       // occupancy bitmap in front of the hash probes (bounds from the sort; cv_sp_scene_plan)
-        bits = reinterpret_cast<const unsigned*>(d_arena + o.bitmap);
-        if (!bitmap_filled) {          // (cv_sp_scene_plan: the level build's insert pass set the bits already)
-            const int rc0 = cv_sp_occupancy_bitmap(d_coords[0], n, d_bbox, reinterpret_cast<unsigned*>(d_arena + o.bitmap), stream,
-                                                   pre_cleared);
-            if (rc0 != CV_OK) return rc0;
-        }
-    }
+                             const cv_scene_maps& o, int32_t* d_arena, const int32_t* d_bbox, void* stream) {
+    const unsigned* bits = d_bbox ? reinterpret_cast<const unsigned*>(d_arena + o.bitmap) : nullptr;
     CvMapJob mj[2];
     int32_t* mw = scene_mask_words(d_arena, o, 0, n);
     // stem: sorted rows <- rows of the ORIGINAL order = the sorted set's own map with the permutation folded in
@@ -107,17 +98,19 @@ static int scene_maps_level0(int32_t* const* d_coords, const unsigned long long*
     if (rc != CV_OK) return rc;
     if (o.mask_perm[0] >= 0) {
         CvPermJob pj = {d_arena + o.k3[0], n, 27, mask_groups, d_arena + o.mask_perm[0], 1, mw};
-        rc = cv_sp_mask_perms_batch(&pj, 1, d_arena + o.scratch, sizeof(int) * (size_t)mask_groups * 2048, stream, pre_cleared);
+        rc = cv_sp_mask_perms_batch(&pj, 1, d_arena + o.scratch, sizeof(int) * (size_t)mask_groups * 2048, stream,
+                                    /* pre_zeroed */ d_bbox != nullptr);
         if (rc != CV_OK) return rc;
     }
     return CV_OK;
 }
 
 // the coarse levels: ONE launch for the eight remaining kernel maps and the four transposed maps (by lookup of the
-// parent voxel: no pre-fill, no dependency on the strided maps), three launches for the remaining processing orders
+// parent voxel: no pre-fill, no dependency on the strided maps), three launches for the remaining processing orders.
+// from_plan: cv_sp_scene_plan_ex calls and the level build has zeroed the scratch of the orders
 static int scene_maps_coarse(int32_t* const* d_coords, const unsigned long long* const* d_keys, const int32_t* const* d_vals,
                              long long cap, const long long* level_rows, int mask_groups, const cv_scene_maps& o,
-                             int32_t* d_arena, void* stream, bool pre_zeroed = false) {
+                             int32_t* d_arena, void* stream, bool from_plan) {
     CvMapJob mj[CV_MAX_MAP_JOBS];
     int nm = 0;
     for (int i = 0; i < 4; ++i)
@@ -146,7 +139,7 @@ static int scene_maps_coarse(int32_t* const* d_coords, const unsigned long long*
         groups += 1;
     }
     return cv_sp_mask_perms_batch(pj, np, d_arena + o.scratch + (size_t)std::max(mask_groups, 1) * 2048,
-                                  sizeof(int) * (size_t)groups * 2048, stream, pre_zeroed);
+                                  sizeof(int) * (size_t)groups * 2048, stream, /* pre_zeroed */ from_plan);
 }
 
 int cv_sp_scene_maps(int32_t* const* d_coords, const unsigned long long* const* d_keys, const int32_t* const* d_vals,
@@ -156,11 +149,12 @@ int cv_sp_scene_maps(int32_t* const* d_coords, const unsigned long long* const* 
     CV_REQUIRE(n_orig == level_rows[0], CV_EINVAL, "the sorted set must hold the caller's %lld rows", n_orig);
     cv_scene_maps o;
     size_t total = 0;
-    scene_maps_layout(level_rows, n_orig, stem_k, mask_groups, masked_min_rows, &o, &total);
+    scene_maps_layout(level_rows, stem_k, mask_groups, masked_min_rows, &o, &total);
     CV_REQUIRE(arena_words >= total, CV_ENOMEM, "scene map arena too small");
-    int rc = scene_maps_level0(d_coords, d_keys, d_vals, cap, n_orig, d_perm, stem_k, mask_groups, o, d_arena, nullptr, stream);
+    int rc = scene_maps_level0(d_coords, d_keys, d_vals, cap, n_orig, d_perm, stem_k, mask_groups, o, d_arena,
+                               /* d_bbox: not from the plan */ nullptr, stream);
     if (rc != CV_OK) return rc;
-    return scene_maps_coarse(d_coords, d_keys, d_vals, cap, level_rows, mask_groups, o, d_arena, stream);
+    return scene_maps_coarse(d_coords, d_keys, d_vals, cap, level_rows, mask_groups, o, d_arena, stream, /* from_plan */ false);
 }
 
 // ---- the whole coordinate plan of a scene in ONE call: spatial row sort, the five coordinate levels with their hash
@@ -210,7 +204,7 @@ size_t cv_sp_scene_plan_words(long long n, int stem_k, int mask_groups, long lon
     const long long rows[5] = {n, n, n, n, n};          // a coarser level never has more rows than a finer one
     cv_scene_maps o;
     size_t total = 0;
-    scene_maps_layout(rows, n, stem_k, mask_groups, masked_min_rows, &o, &total);
+    scene_maps_layout(rows, stem_k, mask_groups, masked_min_rows, &o, &total);
     return total;
 }
 
@@ -261,7 +255,7 @@ int cv_sp_scene_plan(const int32_t* d_input, long long n, int32_t* d_perm, int32
                      size_t levels_ws_bytes, void* stream) {
     return cv_sp_scene_plan_ex(d_input, n, d_perm, d_inv, d_coords, d_keys, d_vals, cap, d_counts, h_counts, stem_k, mask_groups,
                                masked_min_rows, d_arena, arena_words, offsets, d_sort_ws, sort_ws_bytes, d_levels_ws,
-                               levels_ws_bytes, false, stream);
+                               levels_ws_bytes, /* single_batch */ false, stream, /* bounds_prefilled */ false);
 }
 
 }  // extern "C"
@@ -284,14 +278,13 @@ int cv_sp_scene_plan_ex(const int32_t* d_input, long long n, int32_t* d_perm, in
     long long rows[5] = {n, 1, 1, 1, 1};
     cv_scene_maps o;
     size_t total = 0;
-    scene_maps_layout(rows, n, stem_k, mask_groups, masked_min_rows, &o, &total);
-    static const bool bitmap_on = !(getenv("CV_MAP_BITMAP") && atoi(getenv("CV_MAP_BITMAP")) == 0);
-    const long long n_zero = o.bitmap + (bitmap_on ? CV_BITMAP_WORDS : 0) - o.scratch;
-    // (the sort leaves its bounds - min, -max per axis, -max batch - in the first 8 ints of its workspace; [7] = 1 marks
-    // the bitmap as trusted until bitmap_set finds a row outside them)
+    scene_maps_layout(rows, stem_k, mask_groups, masked_min_rows, &o, &total);
+    // (the sort leaves its bounds - min, -max per axis, -max batch - in the first 8 ints of its workspace; the level build
+    // sets [7] = 1, "the bitmap may be trusted", and takes it back when a row falls outside them)
+    int32_t* d_bbox = static_cast<int32_t*>(d_sort_ws);
     rc = cv_sp_build_levels_zero(d_coords, d_keys, d_vals, n, cap, 5, d_counts, nullptr, d_levels_ws, levels_ws_bytes,
-                                 d_arena + o.scratch, n_zero, bitmap_on ? static_cast<int32_t*>(d_sort_ws) + 7 : nullptr, stream,
-                                 bitmap_on ? reinterpret_cast<uint32_t*>(d_arena + o.bitmap) : nullptr);
+                                 d_arena + o.scratch, o.bitmap + CV_BITMAP_WORDS - o.scratch, d_bbox,
+                                 reinterpret_cast<uint32_t*>(d_arena + o.bitmap), stream);
     if (rc != CV_OK) return rc;
     PlanSideLease lease;
     rc = plan_side_acquire(&lease.ps);
@@ -301,18 +294,17 @@ int cv_sp_scene_plan_ex(const int32_t* d_input, long long n, int32_t* d_perm, in
     CV_HIP_CHECK(hipMemcpyAsync(ps.h_pinned, d_counts, sizeof(int32_t) * 8, hipMemcpyDeviceToHost, st));
     CV_HIP_CHECK(hipEventRecord(ps.ev, st));
     // level-0 maps: their arena offsets depend on n only
-    rc = scene_maps_level0(d_coords, d_keys, d_vals, cap, n, d_perm, stem_k, mask_groups, o, d_arena,
-                           bitmap_on ? static_cast<const int32_t*>(d_sort_ws) : nullptr, stream, true, bitmap_on);
+    rc = scene_maps_level0(d_coords, d_keys, d_vals, cap, n, d_perm, stem_k, mask_groups, o, d_arena, d_bbox, stream);
     if (rc != CV_OK) return rc;
     CV_HIP_CHECK(hipEventSynchronize(ps.ev));          // the counts have landed; the level-0 maps are still being built
     for (int i = 0; i < 8; ++i) h_counts[i] = ps.h_pinned[i];
     if (h_counts[5] != 0 || h_counts[6] != 0) return CV_OK;      // duplicates / out-of-window rows: the caller reports them
     for (int i = 0; i < 5; ++i) rows[i] = h_counts[i];
     CV_REQUIRE(rows[0] == n, CV_EINVAL, "level 0 lost rows (%lld of %lld)", rows[0], n);
-    scene_maps_layout(rows, n, stem_k, mask_groups, masked_min_rows, &o, &total);
+    scene_maps_layout(rows, stem_k, mask_groups, masked_min_rows, &o, &total);
     CV_REQUIRE(arena_words >= total, CV_ENOMEM, "scene map arena too small");
     *offsets = o;
-    return scene_maps_coarse(d_coords, d_keys, d_vals, cap, rows, mask_groups, o, d_arena, stream, true);
+    return scene_maps_coarse(d_coords, d_keys, d_vals, cap, rows, mask_groups, o, d_arena, stream, /* from_plan */ true);
 }
 
 extern "C" {

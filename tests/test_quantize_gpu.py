@@ -144,6 +144,23 @@ def test_inverse(cuda, built_lib, m, dtype):
     assert np.all(index[inverse] <= np.arange(m))
 
 
+def test_cloud_above_2_20_points(cuda, built_lib):
+    """m = 2^20 + 4097: the scan kernels take two points per thread (per = 2) in 515 blocks; below 2^20 + 1 points they
+    take one"""
+    m, q = (1 << 20) + 4097, 0.03
+    p = surface_cloud(25, m)
+    wc, wi = host(p, q)
+    check_against_host(p, q, cuda, tag="%d points" % m)
+    coords, index, inverse = me_utils.sparse_quantize(torch.from_numpy(p).to(cuda), quantization_size=q, return_index=True,
+                                                      return_inverse=True)
+    coords, index, inverse = coords.cpu().numpy(), index.cpu().numpy(), inverse.cpu().numpy()
+    assert np.array_equal(coords, wc) and np.array_equal(index, wi)
+    assert inverse.shape == (m,) and inverse.min() >= 0 and inverse.max() < index.size
+    assert np.array_equal(coords[inverse], np.floor(p / q).astype(np.int32))
+    assert np.array_equal(inverse[index], np.arange(index.size))
+    assert np.all(index[inverse] <= np.arange(m))
+
+
 def test_batch_of_three_clouds(cuda, built_lib):
     a = surface_cloud(21, 1000)
     b = a[:257].copy()                               # the same points in another cloud: separate voxels

@@ -45,6 +45,25 @@ def test_coordinate_sets_and_kernel_maps_exact(cuda, built_lib, seed, n, batch):
         assert np.array_equal(down[up[f, j], j], f)
 
 
+def test_coordinate_levels_of_a_set_above_2_20_rows(cuda, built_lib):
+    """more than 2^20 rows: the level build scans eight rows per thread (132 scan blocks here) instead of one.  Levels
+    only - no kernel maps at this size."""
+    box = np.stack(np.meshgrid(np.arange(128), np.arange(96), np.arange(88), indexing="ij"), -1).reshape(-1, 3)
+    n = box.shape[0]
+    assert n == 1081344 > 1 << 20
+    coords = np.concatenate([np.zeros((n, 1), np.int64), box + np.array([-11, 5, -3])], 1)
+    coords = coords[np.random.default_rng(0).permutation(n)]
+    cm = ME.CoordinateManager(torch.from_numpy(coords).to(cuda, torch.int32))
+    assert cm.num_rows(1) == n and np.array_equal(cm.coords[1].cpu().numpy(), coords)
+    want, sizes = coords, []
+    for ts in (2, 4, 8, 16):
+        want = so.downsample_coords(want, ts // 2)
+        sizes.append(len(want))
+        assert cm.num_rows(ts) == len(want), ts
+        assert np.array_equal(cm.coords[ts].cpu().numpy(), want), ts               # same order too
+    assert sizes == [143325, 18975, 2652, 441]
+
+
 @pytest.mark.parametrize("seed,n,batch", [(3, 1, 1), (0, 700, 1), (1, 3000, 3), (2, 80000, 1)])
 def test_spatial_row_sort_is_the_stable_sort_of_its_key(cuda, built_lib, seed, n, batch):
     """cv_sp_sort_rows (the row order the fused network runs on): key = batch | Z-order of the coarse cube,
