@@ -98,7 +98,7 @@ class SceneDesc(ctypes.Structure):
                 ("grid_capacity_floats", ctypes.c_size_t), ("h_pinned", vp), ("pinned_bytes", ctypes.c_size_t),
                 ("h_cand_idx", vp), ("h_verdict", vp), ("h_boxes", vp), ("h_scores", vp), ("h_classes", vp), ("h_pick", vp),
                 ("adaptive_split", ctypes.c_int), ("events", vp * 5),
-                ("conv_split_target", ctypes.c_int), ("vote_part_records", ctypes.c_int)]
+                ("conv_split_target", ctypes.c_int), ("vote_part_records", ctypes.c_int), ("peak_quotients", ctypes.c_int)]
 
 
 MAX_CATEGORIES = 16      # CV_MAX_CATEGORIES
@@ -202,6 +202,12 @@ SIGNATURES = {
     "cv_hv_forward_cat_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, c_int_p, ctypes.c_int, ctypes.c_int]),
     "cv_hv_forward_cat_f32": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_float, ctypes.c_int, c_float_p, c_int_p,
                                              ctypes.c_int, vp, vp, vp, vp, ctypes.c_size_t, ctypes.c_int, vp]),
+    "cv_hv_forward_peaks_f32": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_float, ctypes.c_int,
+                                               c_float_p, c_int_p, vp, vp, vp, vp, ctypes.c_size_t,
+                                               ctypes.c_int, ctypes.c_float, vp]),
+    "cv_hv_forward_peaks_cat_f32": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_float, ctypes.c_int, c_float_p, c_int_p,
+                                                   ctypes.c_int, vp, vp, vp, vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_float,
+                                                   vp]),
     "cv_hv_set_kernel_events": (ctypes.c_int, [vp, vp]),
     "cv_hv_backward_f32": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_float,
                                           ctypes.c_int, c_float_p, c_int_p, vp, vp, vp, vp]),

@@ -666,13 +666,28 @@ __device__ __forceinline__ void lds_add_obj(unsigned long long* p, float v) {
 // rotated order so that lanes voting into the SAME cell hit different words in different banks at any one instruction -
 // 0.62 ms (same-address lanes of one ds_add are evidently merged more cheaply than 24 rotated selects cost), rotating
 // the channel order only - 0.45 / 0.47 ms (no gain).
-constexpr int ACC_PITCH = TZ + 8, ACC_CH = TX * ACC_PITCH + 4, ACC_WORDS = 6 * ACC_CH;
+constexpr int ACC_PITCH = TZ + 8, ACC_CH = TX * ACC_PITCH + 4;
 __device__ __forceinline__ int acc_idx(int ch, int cell) { return ch * ACC_CH + (cell >> 5) * ACC_PITCH + (cell & 31); }
 
-struct TileShared {
-    unsigned long long acc[ACC_WORDS];   // channel 0: objectness weight, 1..5: rot.cos, rot.sin, scale.xyz - all
-                                         // in 2^-36 fixed point
-    float pq[9][LQ];           // px, pz, cx, cz, wy, obj, s0, s1, s2 of the round's surviving records (workgroup-wide list)
+// The channel set of a tile launch.  The rot / scale quotients are read in ONE place of the pipeline - the decode's compaction,
+// at cells with objectness >= thresh_high, 0.12 % of an 80k scene's grid - so a caller that only decodes runs two launches over
+// the same work items instead of VOTE_FULL:
+//   VOTE_FULL   all six channels, all three grids (cv_hv_forward_f32)
+//   VOTE_OBJ    the objectness channel alone; stores g_obj and, per (plane, tile), the bounding box of its cells >= thresh
+//   VOTE_PEAKS  the five numerators, only in the tiles that hold such a cell and only for corners inside that box; stores
+//               g_rot / g_scale at the cells >= thresh, dividing by the float VOTE_OBJ stored
+// Every sum is an integer, so the quotients of the second launch are the bits VOTE_FULL writes.
+constexpr int VOTE_FULL = 0, VOTE_OBJ = 1, VOTE_PEAKS = 2;
+constexpr int vote_channels(int mode) { return mode == VOTE_FULL ? 6 : (mode == VOTE_OBJ ? 1 : 5); }
+// cells >= thresh of one (plane, tile), tile-local and inclusive; x0 > x1: none
+struct HotBox { int x0, x1, z0, z1; };
+
+template <int MODE>
+struct TileSharedT {
+    static constexpr int ACC_WORDS = vote_channels(MODE) * ACC_CH;
+    unsigned long long acc[ACC_WORDS];   // VOTE_FULL: channel 0: objectness weight, 1..5: rot.cos, rot.sin, scale.xyz (VOTE_OBJ:
+                                         // channel 0 alone, VOTE_PEAKS: the five numerators as channels 0..4) - all in 2^-36 fixed point
+    float pq[MODE == VOTE_OBJ ? 6 : 9][LQ];   // px, pz, cx, cz, wy, obj, s0, s1, s2 of the round's surviving records (workgroup-wide list)
     int arc_start[LQ];         // phase A: record index | bin << 31; from phase B on: first rotation whose vote can reach the tile
     int arc_cum[LQ];           // (list mode, phase A: the entry's packed arc) inclusive prefix sum of the arc lengths
     uint32_t vq_rec[TW][VQ];   // entry | rot<<9 | (lx+1)<<17 | (lz+1)<<23
@@ -685,29 +700,36 @@ struct TileShared {
     int more;                  // a wave stopped for lack of room: another round follows
 };
 
-template <bool SMALL>
-__device__ __forceinline__ void drain_vote(TileShared& sh, int lx, int lz, float rx, float rz, float wy, float ob,
-                                           float s0, float s1, float s2, float2 cs) {
+template <bool SMALL, int MODE>
+__device__ __forceinline__ void drain_vote(TileSharedT<MODE>& sh, int lx, int lz, float rx, float rz, float wy, float ob,
+                                           float s0, float s1, float s2, float2 cs, HotBox box) {
     const float wx[2] = {1.f - rx, rx}, wz[2] = {1.f - rz, rz};
 #pragma unroll
     for (int bx = 0; bx < 2; ++bx)
 #pragma unroll
         for (int bz = 0; bz < 2; ++bz) {
             const int cxl = lx + bx, czl = lz + bz;
-            if (cxl < 0 || cxl >= TX || czl < 0 || czl >= TZ) continue;
+            if (MODE == VOTE_PEAKS) {
+                if (cxl < box.x0 || cxl > box.x1 || czl < box.z0 || czl > box.z1) continue;
+            } else {
+                if (cxl < 0 || cxl >= TX || czl < 0 || czl >= TZ) continue;
+            }
             // hv_cuda_kernel.cu:52-59 order: ((wx*wy)*wz)*objness
             const float w = wx[bx] * wy * wz[bz] * ob;
             unsigned long long* a = sh.acc + cxl * ACC_PITCH + czl;
-            lds_add_obj<SMALL>(a, w);
-            lds_add<SMALL>(a + ACC_CH, w * cs.x);
-            lds_add<SMALL>(a + 2 * ACC_CH, w * cs.y);
-            lds_add<SMALL>(a + 3 * ACC_CH, w * s0);
-            lds_add<SMALL>(a + 4 * ACC_CH, w * s1);
-            lds_add<SMALL>(a + 5 * ACC_CH, w * s2);
+            if (MODE != VOTE_PEAKS) lds_add_obj<SMALL>(a, w);
+            if (MODE == VOTE_OBJ) continue;
+            if (MODE == VOTE_FULL) a += ACC_CH;
+            lds_add<SMALL>(a, w * cs.x);
+            lds_add<SMALL>(a + ACC_CH, w * cs.y);
+            lds_add<SMALL>(a + 2 * ACC_CH, w * s0);
+            lds_add<SMALL>(a + 3 * ACC_CH, w * s1);
+            lds_add<SMALL>(a + 4 * ACC_CH, w * s2);
         }
 }
 
-__device__ __forceinline__ void drain64(TileShared& sh, int wave, int slot, bool active) {
+template <int MODE>
+__device__ __forceinline__ void drain64(TileSharedT<MODE>& sh, int wave, int slot, bool active, HotBox box) {
     float rx = 0.f, rz = 0.f, wy = 0.f, ob = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f;
     float2 cs = make_float2(0.f, 0.f);
     int lx = 0, lz = 0;
@@ -723,16 +745,20 @@ __device__ __forceinline__ void drain64(TileShared& sh, int wave, int slot, bool
         const int e = rec & 511, rot = (rec >> 9) & 255;
         lx = (int)((rec >> 17) & 63) - 1; lz = (int)((rec >> 23) & 63) - 1;
         wy = sh.pq[4][e]; ob = sh.pq[5][e];
-        s0 = sh.pq[6][e]; s1 = sh.pq[7][e]; s2 = sh.pq[8][e];
-        cs = sh.tab[rot];
+        if constexpr (MODE != VOTE_OBJ) {
+            s0 = sh.pq[6][e]; s1 = sh.pq[7][e]; s2 = sh.pq[8][e];
+            cs = sh.tab[rot];
+        }
     }
     // every contribution of a vote is bounded by |obj| * max(1, |scale|) (the trilinear weights are <= 1); the
-    // wave takes the fast fixed-point conversion unless one of its 64 votes could exceed its range
+    // wave takes the fast fixed-point conversion unless one of its 64 votes could exceed its range.  (VOTE_OBJ has s = 0: the
+    // objectness contribution is bounded by |obj| alone, and inside the fast conversion's range both conversions round v * 2^36
+    // to the nearest integer, ties to even - the same word whichever the wave takes.)
     const bool small = fabsf(ob) * fmaxf(1.f, fmaxf(fabsf(s0), fmaxf(fabsf(s1), fabsf(s2)))) < 16384.f;
     if (__all(small)) {
-        if (active) drain_vote<true>(sh, lx, lz, rx, rz, wy, ob, s0, s1, s2, cs);
+        if (active) drain_vote<true, MODE>(sh, lx, lz, rx, rz, wy, ob, s0, s1, s2, cs, box);
     } else {
-        if (active) drain_vote<false>(sh, lx, lz, rx, rz, wy, ob, s0, s1, s2, cs);
+        if (active) drain_vote<false, MODE>(sh, lx, lz, rx, rz, wy, ob, s0, s1, s2, cs, box);
     }
 }
 
@@ -805,41 +831,38 @@ __device__ __forceinline__ void edge_arc(float ux, float uz, float r, float a0, 
     }
 }
 
-template <bool QUEUE>
-__global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
-    int R, float res, F3 corner, I3 dims, const float2* __restrict__ tab,
-    const int* __restrict__ ystart, const int4* __restrict__ items, const float* __restrict__ rec,
+// One work item (plane y, tile, part of nparts) of a tile launch; the pointers are the category's own.  VOTE_FULL ignores the
+// last three arguments in front of `tab`:
+//   hot / thresh  VOTE_OBJ writes, VOTE_PEAKS reads: hot[plane * ntiles + tile] = the HotBox of the cells whose stored objectness is
+//                 >= thresh - the float and the comparison of the decode's compaction.  Every record is written by every VOTE_OBJ
+//                 launch (by the workgroup that stores the tile), so nothing of it survives a call.
+//   hot_items     VOTE_OBJ appends, VOTE_PEAKS walks: the work items (plane, tile, part | parts << 8, first partial slot) of the
+//                 (plane, tile) pairs whose box is not empty; its length is the word arrivals[Y * ntiles] (TilesLayout).
+template <bool QUEUE, int MODE>
+__device__ __forceinline__ void hv_tile_item(
+    int y, int tile, int part, int nparts, int slot0, int slot_stride,
+    int R, float res, F3 corner, I3 dims,
+    const int* __restrict__ ystart, const float* __restrict__ rec,
     int64_t rec_stride, int tiles_x, int tiles_z, unsigned long long* __restrict__ partials,
     int* __restrict__ arrivals, float* __restrict__ g_obj, float* __restrict__ g_rot,
     float* __restrict__ g_scale, const int* __restrict__ list_ctl, const int* __restrict__ list_start, const int* __restrict__ list_cnt,
     const int2* __restrict__ entries, int list_mode /* 1: stream the bins, 2: work lists */,
-    const int4* __restrict__ q_info, CatStride ks) {
-    ystart = cat_ws(ystart, ks.ws); items = cat_ws(items, ks.ws); rec = cat_ws(rec, ks.ws);
-    partials = cat_ws(partials, ks.ws); arrivals = cat_ws(arrivals, ks.ws); list_ctl = cat_ws(list_ctl, ks.ws);
-    list_start = cat_ws(list_start, ks.ws); list_cnt = cat_ws(list_cnt, ks.ws); entries = cat_ws(entries, ks.ws);
-    q_info = cat_ws(q_info, ks.ws);
-    g_obj = cat_el(g_obj, ks.cells); g_rot = cat_el(g_rot, 2 * ks.cells); g_scale = cat_el(g_scale, 3 * ks.cells);
-    __shared__ TileShared sh;
+    int4* __restrict__ hot, float thresh, int4* __restrict__ hot_items, const float2* __restrict__ tab) {
+    constexpr int NCH = vote_channels(MODE);
+    __shared__ TileSharedT<MODE> sh;
     __shared__ int last_flag;
+    __shared__ int hot_lds[MODE == VOTE_OBJ ? 4 : 1];      // VOTE_OBJ: x lo / hi, z lo / hi of the tile's cells >= thresh
     const int X = dims.x, Y = dims.y, Z = dims.z;
     const int ntiles = tiles_x * tiles_z;
-    // QUEUE: one work item per workgroup (hv_build_queue; large grids) - ONE 16-byte load says which (plane, tile,
-    // part) this is.  !QUEUE (small grids, the round-2 launch): (plane, part) x tile workgroups, parts by the records of
-    // the plane's bins (hv_prep_scan)
-    int y, tile, part, nparts, slot0, slot_stride;
-    if (QUEUE) {
-        if ((int)blockIdx.x >= list_ctl[2]) return;
-        const int4 item = items[blockIdx.x];
-        y = item.x; tile = item.y; part = item.z & 0xff; nparts = item.z >> 8; slot0 = item.w; slot_stride = 1;
-    } else {
-        tile = blockIdx.x % ntiles;
-        const int4 qi = q_info[blockIdx.x / ntiles];     // (plane, part) slot
-        if (qi.z < 0) return;
-        y = qi.x; part = qi.y; nparts = qi.z;
-        slot0 = qi.w * ntiles + tile; slot_stride = ntiles;
-    }
     const int x0 = (tile / tiles_z) * TX, z0 = (tile % tiles_z) * TZ;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // VOTE_PEAKS: the cells of this (plane, tile) that the decode can read; none (most tiles): nothing to do, for every part alike
+    HotBox box{0, TX - 1, 0, TZ - 1};
+    if (MODE == VOTE_PEAKS) {
+        const int4 h = hot[y * ntiles + tile];
+        box = HotBox{h.x, h.y, h.z, h.w};
+        if (box.x0 > box.x1) return;
+    }
     if (nparts == 0) {
         // nothing votes into this tile of this plane: zeros straight to the grids (no accumulators, no barriers)
         const int nx0 = min(TX, X - x0), nz0 = min(TZ, Z - z0);
@@ -847,10 +870,16 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
             const int lx = i / TZ, lz = i % TZ;
             if (lx < nx0 && lz < nz0) {
                 const int64_t cell = ((int64_t)(x0 + lx) * Y + y) * Z + z0 + lz;
-                g_obj[cell] = 0.f;
-                reinterpret_cast<float2*>(g_rot)[cell] = make_float2(0.f, 0.f);
-                g_scale[cell * 3 + 0] = 0.f; g_scale[cell * 3 + 1] = 0.f; g_scale[cell * 3 + 2] = 0.f;
+                if (MODE != VOTE_PEAKS) g_obj[cell] = 0.f;
+                if (MODE != VOTE_OBJ) {      // (VOTE_PEAKS gets here with thresh <= 0 only: every cell of the tile counts)
+                    reinterpret_cast<float2*>(g_rot)[cell] = make_float2(0.f, 0.f);
+                    g_scale[cell * 3 + 0] = 0.f; g_scale[cell * 3 + 1] = 0.f; g_scale[cell * 3 + 2] = 0.f;
+                }
             }
+        }
+        if (MODE == VOTE_OBJ && threadIdx.x == 0) {
+            hot[y * ntiles + tile] = 0.f >= thresh ? make_int4(0, nx0 - 1, 0, nz0 - 1) : make_int4(TX, -1, TZ, -1);
+            if (0.f >= thresh) hot_items[atomicAdd(&arrivals[Y * ntiles], 1)] = make_int4(y, tile, 0, slot0);
         }
         return;
     }
@@ -880,17 +909,22 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
         bin_end[k] = !valid ? 0 : (use_list ? lbeg[k] + llen[k] : ystart[s + 1]);
     }
     const float2 tab_mine = (int)threadIdx.x < R ? tab[threadIdx.x] : make_float2(0.f, 0.f);      // (R <= MAX_R_TILES <= TW * 64)
-    for (int i = threadIdx.x; i < ACC_WORDS; i += TW * 64) sh.acc[i] = 0ull;
+    for (int i = threadIdx.x; i < TileSharedT<MODE>::ACC_WORDS; i += TW * 64) sh.acc[i] = 0ull;
     if ((int)threadIdx.x < R) sh.tab[threadIdx.x] = tab_mine;
     if (threadIdx.x < 2) sh.next_chunk[threadIdx.x] = 0;
     if (threadIdx.x == 2) { sh.list_len = 0; sh.more = 0; }
+    if (MODE == VOTE_OBJ && threadIdx.x >= 4 && threadIdx.x < 8)      // (read behind the barriers of the tail)
+        hot_lds[threadIdx.x - 4] = (threadIdx.x & 1) ? -1 : (threadIdx.x == 4 ? TX : TZ);
     __syncthreads();
 
     // a vote at grid position g touches cells floor(g), floor(g)+1, so it reaches this
     // tile iff g in [x0-1, x0+TX) x [z0-1, z0+TZ); slack covers fp32 rounding of the test.
+    // (VOTE_PEAKS: the hot box in place of the tile - the cull, the arcs and the vote test below all take this rectangle)
     const float slack = 0.05f;
-    const float xlo = (float)(x0 - 1), xhi = (float)(x0 + TX), zlo = (float)(z0 - 1),
-                zhi = (float)(z0 + TZ);
+    const float xlo = MODE == VOTE_PEAKS ? (float)(x0 + box.x0 - 1) : (float)(x0 - 1),
+                xhi = MODE == VOTE_PEAKS ? (float)(x0 + box.x1 + 1) : (float)(x0 + TX),
+                zlo = MODE == VOTE_PEAKS ? (float)(z0 + box.z0 - 1) : (float)(z0 - 1),
+                zhi = MODE == VOTE_PEAKS ? (float)(z0 + box.z1 + 1) : (float)(z0 + TZ);
     int vq_len = 0;   // wave-uniform
 
     // Rounds of three phases over ONE survivor list of the workgroup (until round 8 every wave culled a 64-record chunk,
@@ -1047,9 +1081,11 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
             sh.pq[3][p] = rec[3 * rec_stride + idx];
             sh.pq[4][p] = (w < 0) ? (1.f - ry) : ry;       // bin y : bin y - 1
             sh.pq[5][p] = rec[5 * rec_stride + idx];
-            sh.pq[6][p] = rec[6 * rec_stride + idx];
-            sh.pq[7][p] = rec[7 * rec_stride + idx];
-            sh.pq[8][p] = rec[8 * rec_stride + idx];
+            if constexpr (MODE != VOTE_OBJ) {
+                sh.pq[6][p] = rec[6 * rec_stride + idx];
+                sh.pq[7][p] = rec[7 * rec_stride + idx];
+                sh.pq[8][p] = rec[8 * rec_stride + idx];
+            }
             sh.arc_start[p] = a_start;
         }
         // inclusive scan of the arc lengths in list order: per wave, then over the wave totals
@@ -1121,7 +1157,9 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
                 const float gz = grid_pos(epz, oz, corner.z, res);
                 if (gx >= 0 && gz >= 0 && gx < (float)(X - 1) && gz < (float)(Z - 1)) {
                     const int lx = (int)gx - x0, lz = (int)gz - z0;
-                    if (lx >= -1 && lx < TX && lz >= -1 && lz < TZ) {
+                    // (VOTE_PEAKS: one of the four corners in the hot box)
+                    if (MODE == VOTE_PEAKS ? (lx >= box.x0 - 1 && lx <= box.x1 && lz >= box.z0 - 1 && lz <= box.z1)
+                                           : (lx >= -1 && lx < TX && lz >= -1 && lz < TZ)) {
                         isvote = true;
                         rx = gx - floorf(gx);
                         rz = gz - floorf(gz);
@@ -1142,12 +1180,12 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
             wave_sync_lds();
             if (vq_len >= 64) {
                 vq_len -= 64;
-                drain64(sh, wave, vq_len + lane, true);
+                drain64<MODE>(sh, wave, vq_len + lane, true, box);
             }
         }
         // queued votes index this round's list entries: flush before the list is overwritten
         if (vq_len > 0) {
-            drain64(sh, wave, lane, lane < vq_len);
+            drain64<MODE>(sh, wave, lane, lane < vq_len, box);
             vq_len = 0;
         }
         wave_sync_lds();
@@ -1161,8 +1199,10 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
         // merged sums are the same bits whichever records landed in whichever part (until round 4 the parts went through
         // fp32, so the last bit of a hot cell depended on the atomic order of the scatter that fills the parts)
         // plain stores -> per-wave vmcnt(0) -> barrier -> one-lane agent release -> ticket.
+        // (a slot has room for six channels in every mode: VOTE_OBJ and VOTE_PEAKS use the first one / five of the same slots,
+        // one launch after the other)
         unsigned long long* mine = partials + ((int64_t)slot0 + (int64_t)part * slot_stride) * (6 * TCELLS);
-        for (int i = threadIdx.x; i < 6 * TCELLS; i += TW * 64) mine[i] = sh.acc[acc_idx(i / TCELLS, i % TCELLS)];
+        for (int i = threadIdx.x; i < NCH * TCELLS; i += TW * 64) mine[i] = sh.acc[acc_idx(i / TCELLS, i % TCELLS)];
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -1172,11 +1212,14 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
                                                    __HIP_MEMORY_SCOPE_AGENT);
             last_flag = old == nparts - 1;
             if (last_flag) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            // the VOTE_PEAKS launch behind this one counts its arrivals in the same word: back to zero once all have arrived
+            if (MODE == VOTE_OBJ && last_flag)
+                __hip_atomic_store(&arrivals[y * ntiles + tile], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         __syncthreads();
         if (!last_flag) return;
         const unsigned long long* base = partials + (int64_t)slot0 * (6 * TCELLS);
-        for (int i = threadIdx.x; i < 6 * TCELLS; i += TW * 64) {
+        for (int i = threadIdx.x; i < NCH * TCELLS; i += TW * 64) {
             unsigned long long sum = 0ull;
             for (int p2 = 0; p2 < nparts; ++p2) sum += base[(int64_t)p2 * slot_stride * (6 * TCELLS) + i];
             sh.acc[acc_idx(i / TCELLS, i % TCELLS)] = sum;
@@ -1187,29 +1230,115 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
     // fused normalise (hv_cuda_kernel.cu:112-117) + single store of the tile.  The weight the
     // reference divides by is the fp32 grid value, so round the double sum to float first.
     const int nx = min(TX, X - x0), nz = min(TZ, Z - z0);
-    for (int i = threadIdx.x; i < TCELLS; i += TW * 64) {
-        const int lx = i / TZ, lz = i % TZ;
-        if (lx < nx && lz < nz)
-            g_obj[((int64_t)(x0 + lx) * Y + y) * Z + z0 + lz] = (float)fx_value(sh.acc[acc_idx(0, i)]);
-    }
-    for (int i = threadIdx.x; i < TCELLS * 2; i += TW * 64) {
-        const int cell = i >> 1, j = i & 1;
-        const int lx = cell / TZ, lz = cell % TZ;
-        if (lx < nx && lz < nz) {
-            const double d = (double)(float)fx_value(sh.acc[acc_idx(0, cell)]) + 1e-7;
-            g_rot[(((int64_t)(x0 + lx) * Y + y) * Z + z0 + lz) * 2 + j] =
-                (float)((double)(float)fx_value(sh.acc[acc_idx(1 + j, cell)]) / d);
+    if constexpr (MODE == VOTE_OBJ) {
+        // the objectness grid, and the box of the cells the decode's compaction will take (the same float, the same comparison)
+        for (int i = threadIdx.x; i < TCELLS; i += TW * 64) {
+            const int lx = i / TZ, lz = i % TZ;
+            if (lx < nx && lz < nz) {
+                const float v = (float)fx_value(sh.acc[acc_idx(0, i)]);
+                g_obj[((int64_t)(x0 + lx) * Y + y) * Z + z0 + lz] = v;
+                if (v >= thresh) {
+                    atomicMin(&hot_lds[0], lx); atomicMax(&hot_lds[1], lx);
+                    atomicMin(&hot_lds[2], lz); atomicMax(&hot_lds[3], lz);
+                }
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            hot[y * ntiles + tile] = make_int4(hot_lds[0], hot_lds[1], hot_lds[2], hot_lds[3]);
+            if (hot_lds[0] <= hot_lds[1]) {      // every part of this (plane, tile) is an item of the VOTE_PEAKS launch
+                const int at = atomicAdd(&arrivals[Y * ntiles], nparts);
+                for (int p2 = 0; p2 < nparts; ++p2) hot_items[at + p2] = make_int4(y, tile, p2 | (nparts << 8), slot0);
+            }
+        }
+    } else if constexpr (MODE == VOTE_PEAKS) {
+        // quotients at the cells >= thresh, by the formula below with the float the VOTE_OBJ launch stored
+        for (int i = threadIdx.x; i < TCELLS; i += TW * 64) {
+            const int lx = i / TZ, lz = i % TZ;
+            if (lx < box.x0 || lx > box.x1 || lz < box.z0 || lz > box.z1) continue;       // (the box lies inside nx x nz)
+            const int64_t cell = ((int64_t)(x0 + lx) * Y + y) * Z + z0 + lz;
+            const float v = g_obj[cell];
+            if (!(v >= thresh)) continue;
+            const double d = (double)v + 1e-7;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) g_rot[cell * 2 + j] = (float)((double)(float)fx_value(sh.acc[acc_idx(j, i)]) / d);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) g_scale[cell * 3 + j] = (float)((double)(float)fx_value(sh.acc[acc_idx(2 + j, i)]) / d);
+        }
+    } else {
+        for (int i = threadIdx.x; i < TCELLS; i += TW * 64) {
+            const int lx = i / TZ, lz = i % TZ;
+            if (lx < nx && lz < nz)
+                g_obj[((int64_t)(x0 + lx) * Y + y) * Z + z0 + lz] = (float)fx_value(sh.acc[acc_idx(0, i)]);
+        }
+        for (int i = threadIdx.x; i < TCELLS * 2; i += TW * 64) {
+            const int cell = i >> 1, j = i & 1;
+            const int lx = cell / TZ, lz = cell % TZ;
+            if (lx < nx && lz < nz) {
+                const double d = (double)(float)fx_value(sh.acc[acc_idx(0, cell)]) + 1e-7;
+                g_rot[(((int64_t)(x0 + lx) * Y + y) * Z + z0 + lz) * 2 + j] =
+                    (float)((double)(float)fx_value(sh.acc[acc_idx(1 + j, cell)]) / d);
+            }
+        }
+        for (int i = threadIdx.x; i < TCELLS * 3; i += TW * 64) {
+            const int cell = i / 3, j = i - cell * 3;
+            const int lx = cell / TZ, lz = cell % TZ;
+            if (lx < nx && lz < nz) {
+                const double d = (double)(float)fx_value(sh.acc[acc_idx(0, cell)]) + 1e-7;
+                g_scale[(((int64_t)(x0 + lx) * Y + y) * Z + z0 + lz) * 3 + j] =
+                    (float)((double)(float)fx_value(sh.acc[acc_idx(3 + j, cell)]) / d);
+            }
         }
     }
-    for (int i = threadIdx.x; i < TCELLS * 3; i += TW * 64) {
-        const int cell = i / 3, j = i - cell * 3;
-        const int lx = cell / TZ, lz = cell % TZ;
-        if (lx < nx && lz < nz) {
-            const double d = (double)(float)fx_value(sh.acc[acc_idx(0, cell)]) + 1e-7;
-            g_scale[(((int64_t)(x0 + lx) * Y + y) * Z + z0 + lz) * 3 + j] =
-                (float)((double)(float)fx_value(sh.acc[acc_idx(3 + j, cell)]) / d);
+}
+
+// The launch: which item(s) a workgroup takes.  VOTE_FULL / VOTE_OBJ: one per workgroup.  QUEUE: hv_build_queue's items (large
+// grids) - ONE 16-byte load says which (plane, tile, part) this is.  !QUEUE (small grids, the round-2 launch): (plane, part) x tile
+// workgroups, parts by the records of the plane's bins (hv_prep_scan).  VOTE_PEAKS: PEAK_WGS workgroups stride over hot_items -
+// launched one workgroup per item of the full launch it spent its time on ~8 000 workgroups that found an empty record
+// (LABNOTES, vote peaks).
+template <bool QUEUE, int MODE>
+__global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
+    int R, float res, F3 corner, I3 dims, const float2* __restrict__ tab,
+    const int* __restrict__ ystart, const int4* __restrict__ items, const float* __restrict__ rec,
+    int64_t rec_stride, int tiles_x, int tiles_z, unsigned long long* __restrict__ partials,
+    int* __restrict__ arrivals, float* __restrict__ g_obj, float* __restrict__ g_rot,
+    float* __restrict__ g_scale, const int* __restrict__ list_ctl, const int* __restrict__ list_start, const int* __restrict__ list_cnt,
+    const int2* __restrict__ entries, int list_mode /* 1: stream the bins, 2: work lists */,
+    const int4* __restrict__ q_info, CatStride ks, int4* __restrict__ hot, float thresh, int4* __restrict__ hot_items) {
+    ystart = cat_ws(ystart, ks.ws); items = cat_ws(items, ks.ws); rec = cat_ws(rec, ks.ws);
+    partials = cat_ws(partials, ks.ws); arrivals = cat_ws(arrivals, ks.ws); list_ctl = cat_ws(list_ctl, ks.ws);
+    list_start = cat_ws(list_start, ks.ws); list_cnt = cat_ws(list_cnt, ks.ws); entries = cat_ws(entries, ks.ws);
+    q_info = cat_ws(q_info, ks.ws);
+    g_obj = cat_el(g_obj, ks.cells); g_rot = cat_el(g_rot, 2 * ks.cells); g_scale = cat_el(g_scale, 3 * ks.cells);
+    if (MODE != VOTE_FULL) { hot = cat_ws(hot, ks.ws); hot_items = cat_ws(hot_items, ks.ws); }
+    const int ntiles = tiles_x * tiles_z;
+#define CV_TILE_ITEM_ARGS R, res, corner, dims, ystart, rec, rec_stride, tiles_x, tiles_z, partials, arrivals, g_obj, g_rot, g_scale, \
+                          list_ctl, list_start, list_cnt, entries, list_mode, hot, thresh, hot_items
+    if (MODE == VOTE_PEAKS) {
+        const int count = arrivals[dims.y * ntiles];
+        if ((int)blockIdx.x >= count) return;
+        for (int i = blockIdx.x; i < count; i += gridDim.x) {
+            const int4 item = hot_items[i];
+            hv_tile_item<QUEUE, MODE>(item.x, item.y, item.z & 0xff, item.z >> 8, item.w, QUEUE ? 1 : ntiles, CV_TILE_ITEM_ARGS, tab);
+            __syncthreads();          // (the next item reuses the workgroup's LDS)
         }
+        return;
     }
+    int y, tile, part, nparts, slot0, slot_stride;
+    if (QUEUE) {
+        if ((int)blockIdx.x >= list_ctl[2]) return;
+        const int4 item = items[blockIdx.x];
+        y = item.x; tile = item.y; part = item.z & 0xff; nparts = item.z >> 8; slot0 = item.w; slot_stride = 1;
+    } else {
+        tile = blockIdx.x % ntiles;
+        const int4 qi = q_info[blockIdx.x / ntiles];     // (plane, part) slot
+        if (qi.z < 0) return;
+        y = qi.x; part = qi.y; nparts = qi.z;
+        slot0 = qi.w * ntiles + tile; slot_stride = ntiles;
+    }
+    hv_tile_item<QUEUE, MODE>(y, tile, part, nparts, slot0, slot_stride, CV_TILE_ITEM_ARGS, tab);
+#undef CV_TILE_ITEM_ARGS
 }
 
 // ---------------------------------------------------------------------------
@@ -1353,6 +1482,7 @@ int64_t tiles_q_bound(int64_t n, int Y) { return (int64_t)Y + (2 * n + PART_RECO
 // the tile kernel gains there; forced either way in flight: profiles/r3/vote_tile_sweep.txt, r5/knobs_in_flight.txt), the
 // streaming launch below that.  16-wide tiles: an 80k-point grid has 66 tiles, a 300k-point grid 190.
 constexpr int QUEUE_MIN_TILES = 128;
+constexpr int PEAK_WGS = 512;        // workgroups of the VOTE_PEAKS launch (two per CU); each strides over the listed items
 // work queue: partial-tile slots for the (plane, tile) pairs with more than one part (sum of arc lengths <= about
 // 2 * n * num_rots counting both planes of a vote and the slack steps; twice that again as room) and items = one per
 // (plane, tile) + the extra parts; hv_build_queue falls back to one part per tile if either is exceeded
@@ -1378,6 +1508,8 @@ struct TilesLayout {
     int* ystart; int* cursor; int* part_start; int4* q_info;
     unsigned long long* partials;
     int4* items; int* list_start; int* chunk_start; int* bin_of_chunk; int* chunk_off; int2* entries;
+    int4* hot_items;               // peak mode: the work items of the (plane, tile) pairs with a box, appended by VOTE_OBJ
+    int4* hot;                     // peak mode: the HotBox of every (plane, tile), written by VOTE_OBJ and read by VOTE_PEAKS
     int* zero_from;                // list_ctl (queue; list_cnt is zeroed with the rest: the count pass adds to it) or ycount
     size_t zero_bytes;             // ... up to the end of arrivals (the streaming launch only needs ycount and arrivals zeroed)
     size_t bytes;                  // end of the last array, rounded up to 256: one category's workspace and the category stride
@@ -1410,7 +1542,8 @@ TilesLayout tiles_layout(int64_t n, int num_rots, const int* dims, void* base) {
     take(L.list_cnt, q * planes);
     take(L.tile_w, q * planes);
     const size_t ycount_at = take(L.ycount, Y);
-    take(L.arrivals, planes);
+    // (+ 1: arrivals[planes] is the length of hot_items - VOTE_OBJ counts it up from the zero the per-call fill below leaves there)
+    take(L.arrivals, planes + 1);
     L.zero_from = L.queue ? L.list_ctl : L.ycount;
     L.zero_bytes = off - (L.queue ? ctl_at : ycount_at);
     take(L.ystart, Y + 1);
@@ -1424,6 +1557,8 @@ TilesLayout tiles_layout(int64_t n, int num_rots, const int* dims, void* base) {
     take(L.bin_of_chunk, (size_t)L.max_chunks);
     take(L.chunk_off, q * (size_t)L.max_chunks * (size_t)ntiles);
     take(L.entries, q * (size_t)L.list_cap);
+    take(L.hot, planes);
+    take(L.hot_items, (size_t)(L.queue ? L.max_items : L.max_q * ntiles));
     L.bytes = cv_align_up(off, 256);
     return L;
 }
@@ -1501,7 +1636,8 @@ size_t cv_hv_forward_workspace_bytes(int64_t n, int num_rots, const int dims[3],
 }
 
 // cv_hv_set_kernel_events: the calling thread's next cv_hv_forward_f32 calls record these events directly before and
-// after the accumulation kernel (hv_fwd_tiles), on the stream of the call
+// after the accumulation (hv_fwd_tiles; peak mode: in front of the first and behind the second of its two launches), on the
+// stream of the call
 static thread_local hipEvent_t t_ev_start = nullptr, t_ev_stop = nullptr;
 
 // records of a plane's two y-bins one workgroup of a hot (tile, plane) takes in the streaming launch: PART_RECORDS (the workspace
@@ -1537,10 +1673,12 @@ size_t cv_hv_forward_cat_workspace_bytes(int64_t n, int num_rots, const int dims
 
 // K categories over the same scan points and grid (K = 1: cv_hv_forward_f32).  Category k reads d_xyz / d_scale + 3 n k,
 // d_obj + n k and writes the grids + (1, 2, 3) * cells * k; its workspace carve starts TilesLayout::bytes * k bytes into d_ws.
+// peaks (tiles algorithm only; the direct one writes full grids either way): VOTE_OBJ then VOTE_PEAKS back to back instead of
+// VOTE_FULL - the same d_grid_obj, d_grid_rot / d_grid_scale written at the cells with d_grid_obj >= thresh only.
 static int hv_forward_cats(const float* d_points, const float* d_xyz, const float* d_scale, const float* d_obj, int64_t n,
                            float res, int num_rots, const float h_corner3[3], const int dims[3], float* d_grid_obj,
                            float* d_grid_rot, float* d_grid_scale, void* d_ws, size_t ws_bytes, int algo, int K,
-                           hipStream_t st) {
+                           hipStream_t st, bool peaks = false, float thresh = 0.f) {
     int rc = CV_OK;
     const float2* tab = nullptr;
     rc = get_rot_table(num_rots, &tab);
@@ -1611,11 +1749,23 @@ static int hv_forward_cats(const float* d_points, const float* d_xyz, const floa
     const int64_t wgs = queue ? L.max_items : L.max_q * ntiles;
     CV_REQUIRE(wgs < (1ll << 31), CV_EINVAL, "grid too large");
 #define CV_TILES_ARGS num_rots, res, corner, d3, tab, L.ystart, L.items, L.rec, n, tiles_x, tiles_z, L.partials, L.arrivals, d_grid_obj, \
-                      d_grid_rot, d_grid_scale, L.list_ctl, L.list_start, L.list_cnt, L.entries, list_mode, L.q_info, ks
+                      d_grid_rot, d_grid_scale, L.list_ctl, L.list_start, L.list_cnt, L.entries, list_mode, L.q_info, ks, L.hot, thresh, L.hot_items
+#define CV_TILES_LAUNCH(MODE, WGS)                                                                           \
+    do {                                                                                                      \
+        if (queue) hv_fwd_tiles<true, MODE><<<dim3((unsigned)(WGS), K), TW * 64, 0, st>>>(CV_TILES_ARGS);     \
+        else hv_fwd_tiles<false, MODE><<<dim3((unsigned)(WGS), K), TW * 64, 0, st>>>(CV_TILES_ARGS);          \
+    } while (0)
     if (t_ev_start) CV_HIP_CHECK(hipEventRecord(t_ev_start, st));
-    if (queue) hv_fwd_tiles<true><<<dim3((unsigned)wgs, K), TW * 64, 0, st>>>(CV_TILES_ARGS);
-    else hv_fwd_tiles<false><<<dim3((unsigned)wgs, K), TW * 64, 0, st>>>(CV_TILES_ARGS);
+    if (peaks) {
+        // (the hot boxes stay on the device; VOTE_OBJ leaves the arrival counters at zero for VOTE_PEAKS)
+        CV_TILES_LAUNCH(VOTE_OBJ, wgs);
+        CV_LAUNCH_CHECK();
+        CV_TILES_LAUNCH(VOTE_PEAKS, std::min<int64_t>(wgs, PEAK_WGS));
+    } else {
+        CV_TILES_LAUNCH(VOTE_FULL, wgs);
+    }
     if (t_ev_stop) CV_HIP_CHECK(hipEventRecord(t_ev_stop, st));
+#undef CV_TILES_LAUNCH
 #undef CV_TILES_ARGS
     CV_LAUNCH_CHECK();
     return CV_OK;
@@ -1645,6 +1795,34 @@ int cv_hv_forward_cat_f32(const float* d_points, const float* d_xyz, const float
     CV_REQUIRE(d_obj && d_grid_obj && d_grid_rot && d_grid_scale, CV_EINVAL, "null pointer argument");
     return hv_forward_cats(d_points, d_xyz, d_scale, d_obj, n, res, num_rots, h_corner3, dims, d_grid_obj, d_grid_rot, d_grid_scale,
                            d_ws, ws_bytes, algo, num_cats, static_cast<hipStream_t>(stream));
+}
+
+int cv_hv_forward_peaks_f32(const float* d_points, const float* d_xyz, const float* d_scale, const float* d_obj, int64_t n,
+                            float res, int num_rots, const float h_corner3[3], const int dims[3], float* d_grid_obj,
+                            float* d_grid_rot, float* d_grid_scale, void* d_ws, size_t ws_bytes, int algo, float thresh,
+                            void* stream) {
+    CV_REQUIRE(algo_ok(algo), CV_EINVAL, "algo out of range (%d: 0 auto, 1 direct, 2 tiles)", algo);
+    CV_REQUIRE(thresh == thresh, CV_EINVAL, "thresh is not a number");
+    int rc = check_common(d_points, d_xyz, d_scale, n, res, num_rots, h_corner3, dims);
+    if (rc) return rc;
+    CV_REQUIRE(d_obj && d_grid_obj && d_grid_rot && d_grid_scale, CV_EINVAL, "null pointer argument");
+    return hv_forward_cats(d_points, d_xyz, d_scale, d_obj, n, res, num_rots, h_corner3, dims, d_grid_obj, d_grid_rot, d_grid_scale,
+                           d_ws, ws_bytes, algo, 1, static_cast<hipStream_t>(stream), true, thresh);
+}
+
+int cv_hv_forward_peaks_cat_f32(const float* d_points, const float* d_xyz, const float* d_scale, const float* d_obj, int64_t n,
+                                float res, int num_rots, const float h_corner3[3], const int dims[3], int num_cats,
+                                float* d_grid_obj, float* d_grid_rot, float* d_grid_scale, void* d_ws, size_t ws_bytes, int algo,
+                                float thresh, void* stream) {
+    CV_REQUIRE(num_cats >= 1 && num_cats <= CV_MAX_CATEGORIES, CV_EINVAL, "num_cats out of range (%d, 1..%d)", num_cats,
+               CV_MAX_CATEGORIES);
+    CV_REQUIRE(algo_ok(algo), CV_EINVAL, "algo out of range (%d: 0 auto, 1 direct, 2 tiles)", algo);
+    CV_REQUIRE(thresh == thresh, CV_EINVAL, "thresh is not a number");
+    int rc = check_common(d_points, d_xyz, d_scale, n, res, num_rots, h_corner3, dims);
+    if (rc) return rc;
+    CV_REQUIRE(d_obj && d_grid_obj && d_grid_rot && d_grid_scale, CV_EINVAL, "null pointer argument");
+    return hv_forward_cats(d_points, d_xyz, d_scale, d_obj, n, res, num_rots, h_corner3, dims, d_grid_obj, d_grid_rot, d_grid_scale,
+                           d_ws, ws_bytes, algo, num_cats, static_cast<hipStream_t>(stream), true, thresh);
 }
 
 int cv_hv_backward_f32(const float* d_grad_obj, const float* d_points, const float* d_xyz,

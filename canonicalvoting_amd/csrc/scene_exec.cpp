@@ -221,8 +221,12 @@ int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream
     const float* v_scale = d->d_scale_in ? d->d_scale_in : scale;
     const float* v_prob = d->d_prob_in ? d->d_prob_in : prob;
     const int32_t* v_cls = d->d_class_in ? d->d_class_in : cls;
-    rc = cv_hv_forward_f32(d->d_points, v_xyz, v_scale, v_prob, n, d->res, d->num_rots, f.mn, f.dims, g_obj, g_rot, g_scale, vote_ws,
-                           std::max<size_t>(vote_ws_b, 256), d->vote_algo, stream);
+    // (peak_quotients: the decode below is the only reader of rot / scale, and it reads them where g_obj >= thresh_high)
+    rc = d->peak_quotients
+             ? cv_hv_forward_peaks_f32(d->d_points, v_xyz, v_scale, v_prob, n, d->res, d->num_rots, f.mn, f.dims, g_obj, g_rot, g_scale,
+                                       vote_ws, std::max<size_t>(vote_ws_b, 256), d->vote_algo, d->decode.thresh_high, stream)
+             : cv_hv_forward_f32(d->d_points, v_xyz, v_scale, v_prob, n, d->res, d->num_rots, f.mn, f.dims, g_obj, g_rot, g_scale, vote_ws,
+                                 std::max<size_t>(vote_ws_b, 256), d->vote_algo, stream);
     if (rc != CV_OK) return rc;
     CV_HIP_CHECK(clock.mark(3));
     clock.lap(2);

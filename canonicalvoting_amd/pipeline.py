@@ -467,6 +467,7 @@ def detect_scene_c(model, hv, coords4, feats, res, nclasses=9, log_scale=True, s
         d.d_xyz_in, d.d_scale_in, d.d_prob_in, d.d_class_in = (vp(px.data_ptr()), vp(ps.data_ptr()), vp(pp.data_ptr()),
                                                                  vp(pc.data_ptr()))
     _fill_joint_desc(d, host, c_ops, c_bufs, y, nclasses, decode_kw, adaptive_split, events)
+    d.peak_quotients = 1 if keep is None else 0      # nobody sees the grids without ``keep``: rot / scale only where the decode reads them
     r = _lib.SceneResult()
     ws = _call_growing(L.cv_detect_scene_f32, "cv_detect_scene_f32", d, r, dev, "scene_call", host.ws_hint)
     host.ws_hint = max(host.ws_hint, int(r.needed_ws_bytes))
@@ -622,6 +623,7 @@ def detect_points_c(model, hv, points, feats, res, predictions=None, return_inve
     host = _scene_host(dev, max_candidates)
     _fill_scene_desc(d.scene, model, hv, None, None, None, res, policy, pieces, max(model.PLANES), log_scale)
     _fill_joint_desc(d.scene, host, c_ops, c_bufs, y, nclasses, decode_kw, adaptive_split, events)
+    d.scene.peak_quotients = 1 if keep is None else 0      # (as detect_scene_c)
     ws = _call_points(L.cv_detect_points_f32, "cv_detect_points_f32", d, r, dev, "scene_call", host.ws_hint)
     del alive
     n = int(r.n)

@@ -42,7 +42,10 @@ extern "C" {
  * 5: the model axis - cv_net_run_models_f32 with its size / table helpers, cv_head_separate_models_f32,
  *    cv_scene_separate_desc.models_per_pass / d_model_params (appended: a zero-initialised descriptor runs as before).
  * 6: raw clouds - cv_sp_voxel_rows_f32 (cv_gather_job), cv_detect_points_f32, cv_detect_points_separate_f32 with their
- *    descriptors / results and the cv_sizeof_* helpers (additive: no struct or signature moved). */
+ *    descriptors / results and the cv_sizeof_* helpers (additive: no struct or signature moved).
+ *    Since then, still 6: cv_hv_forward_peaks_f32 / cv_hv_forward_peaks_cat_f32 and a trailing cv_scene_desc.peak_quotients
+ *    (appended: a zero-initialised descriptor runs as before; cv_scene_separate_desc has no such field, its scene call votes full
+ *    grids). */
 #define CV_ABI_VERSION 6
 int cv_abi_version(void);
 const char* cv_last_error(void);
@@ -99,6 +102,25 @@ int cv_hv_forward_cat_f32(const float* d_points, const float* d_xyz, const float
                           float res, int num_rots, const float h_corner3[3], const int dims[3], int num_cats, float* d_grid_obj,
                           float* d_grid_rot, float* d_grid_scale, void* d_ws, size_t ws_bytes, int algo, void* stream);
 
+/* The vote for a caller that only decodes.  The decode reads d_grid_rot / d_grid_scale in one place, the compaction of the
+ * cells with d_grid_obj >= thresh_high, so these variants accumulate the five quotient numerators only there: one launch of the
+ * tile kernel for the objectness channel alone (it also notes, per plane and tile, the box of its cells >= thresh), a second one
+ * over the tiles that hold such a cell.  Arguments as cv_hv_forward_f32 / cv_hv_forward_cat_f32 plus `thresh` (not NaN;
+ * -INFINITY makes every cell count).  d_grid_obj is written everywhere and is bit for bit what the full call writes;
+ * d_grid_rot / d_grid_scale HOLD VALUES ONLY WHERE d_grid_obj >= thresh - there the same bits as the full call's (every sum is
+ * an integer) - and are left untouched elsewhere.  The same workspace as the full call:
+ * cv_hv_forward_workspace_bytes covers the boxes (16 bytes per plane and tile) and the list of work items the second launch walks
+ * (16 bytes per workgroup of the full launch) for every caller, 0.2 MB at 80k points.  algo 1 (direct) has no such variant:
+ * it writes full grids.  Asynchronous on `stream`; no host wait, the boxes stay on the device. */
+int cv_hv_forward_peaks_f32(const float* d_points, const float* d_xyz, const float* d_scale, const float* d_obj, int64_t n,
+                            float res, int num_rots, const float h_corner3[3], const int dims[3], float* d_grid_obj,
+                            float* d_grid_rot, float* d_grid_scale, void* d_ws, size_t ws_bytes, int algo, float thresh,
+                            void* stream);
+int cv_hv_forward_peaks_cat_f32(const float* d_points, const float* d_xyz, const float* d_scale, const float* d_obj, int64_t n,
+                                float res, int num_rots, const float h_corner3[3], const int dims[3], int num_cats,
+                                float* d_grid_obj, float* d_grid_rot, float* d_grid_scale, void* d_ws, size_t ws_bytes, int algo,
+                                float thresh, void* stream);
+
 /* Launch sizing of the vote's streaming launch: records of a plane's two y-bins that one workgroup of a (tile, plane) takes; a
  * plane with more is split over up to 8 workgroups per tile whose partial tiles the last arriver adds (integer sums: the grids
  * are the same bits under every setting).  Default 4096 (or CV_HV_PART_RECORDS) - the fastest kernel for ONE scene in flight;
@@ -111,7 +133,8 @@ int cv_hv_set_part_records(int records);
  * cv_detect_scene_f32 sets it from cv_scene_desc.vote_part_records for the duration of the call. */
 int cv_hv_set_part_records_thread(int records);
 /* Measurement hook (no reference counterpart): the CALLING THREAD's following cv_hv_forward_f32 calls record the two
- * hipEvent_t handles directly before and after the accumulation kernel of the tile algorithm (hv_fwd_tiles), on the
+ * hipEvent_t handles directly before and after the accumulation kernel of the tile algorithm (hv_fwd_tiles; the peaks
+ * variants: before the first and after the second of their two launches - the whole accumulation), on the
  * stream of the call - bench.py times exactly the kernel its `roofline` prices, with other scenes in flight, instead
  * of the whole op.  NULL, NULL switches it off.  The events stay the caller's. */
 int cv_hv_set_kernel_events(void* ev_start, void* ev_stop);
@@ -707,6 +730,10 @@ typedef struct cv_scene_desc {
      * conv_split_target > 0 overrides adaptive_split. */
     int conv_split_target;        /* workgroups a split coarse-level convolution aims at (library default 768; 256 from four scenes in flight) */
     int vote_part_records;        /* records one workgroup of a hot (tile, plane) takes (library default 4096; 12288 from four in flight) */
+    /* 1: vote through cv_hv_forward_peaks_f32 with decode.thresh_high - for a caller that does not read the grids: detections and
+     * the raw decode are the same bits, result.d_grid_rot / d_grid_scale hold values only where d_grid_obj >= decode.thresh_high.
+     * 0 (a zero-initialised descriptor): full grids, as before. */
+    int peak_quotients;
 } cv_scene_desc;
 typedef struct cv_scene_result {
     int n_cand, n_boxes, n_det, truncated, range_flag, duplicates, out_of_window;
@@ -715,7 +742,8 @@ typedef struct cv_scene_result {
     float corner[3];
     long long level_rows[5];
     size_t needed_ws_bytes, needed_grid_floats;
-    /* device views into d_ws / d_grids, valid until the next call that uses the same scratch */
+    /* device views into d_ws / d_grids, valid until the next call that uses the same scratch (desc.peak_quotients: rot and scale
+     * hold values only at the cells with d_grid_obj >= decode.thresh_high) */
     float* d_grid_obj; float* d_grid_rot; float* d_grid_scale;
     float* d_xyz; float* d_scale; float* d_prob; int32_t* d_class;      /* the network's own head outputs */
     /* host time the call spent (microseconds): [0] coordinate plan incl. its wait for the level counts, [1] enqueueing the network
