@@ -2257,6 +2257,7 @@ int cv_sp_affine_f32(const float* d_x, long long n, int c, int x_ld, const float
                      void* stream) {
     CV_REQUIRE(d_x && d_y && n > 0 && c > 0 && x_ld >= c && y_ld >= c, CV_EINVAL, "bad affine arguments");
     CV_REQUIRE(!d_residual || res_ld >= c, CV_EINVAL, "bad residual stride");
+    CV_REQUIRE(d_scale || !d_shift, CV_EINVAL, "a shift without a scale is not applied by the kernels");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (c % 4 == 0 && x_ld % 4 == 0 && y_ld % 4 == 0 && (!d_residual || res_ld % 4 == 0) && aligned16(d_x) &&
         aligned16(d_y) && aligned16(d_residual) && aligned16(d_scale) && aligned16(d_shift))
@@ -2274,6 +2275,7 @@ int cv_sp_affine_hl_f32(const float* d_x, long long n, int c, int x_ld, const fl
                         uint32_t* d_relu_bits, int32_t* range_flag, void* stream) {
     CV_REQUIRE(d_x && d_y && d_y_hl && n > 0 && c > 0 && x_ld >= c && y_ld >= c && y_hl_ld >= c, CV_EINVAL, "bad affine arguments");
     CV_REQUIRE(!d_residual || res_ld >= c, CV_EINVAL, "bad residual stride");
+    CV_REQUIRE(d_scale || !d_shift, CV_EINVAL, "a shift without a scale is not applied by the kernels");
     CV_REQUIRE(c % 32 == 0 && y_hl_ld % 32 == 0 && (reinterpret_cast<uintptr_t>(d_y_hl) & 127) == 0, CV_EINVAL,
                "hl-format output: channels and leading dimension %% 32 == 0, 128-byte aligned rows");
     CV_REQUIRE(x_ld % 4 == 0 && y_ld % 4 == 0 && (!d_residual || res_ld % 4 == 0) && aligned16(d_x) && aligned16(d_y) &&

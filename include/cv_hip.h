@@ -647,7 +647,8 @@ int cv_sp_copy_unless_flag(const void* const* h_src, void* const* h_dst, const l
                            void* stream);
 
 /* y = relu?(x * scale + shift + residual): MinkowskiBatchNorm (eval) / MinkowskiReLU / the residual add of
- * BasicBlock on feature rows; scale, shift and residual may each be NULL. */
+ * BasicBlock on feature rows; scale, shift and residual may each be NULL, a shift only together with a scale
+ * (CV_EINVAL otherwise: the kernels apply the pair or neither). */
 int cv_sp_affine_f32(const float* d_x, long long n, int c, int x_ld, const float* d_scale,
                      const float* d_shift, const float* d_residual, int res_ld, int relu, float* d_y, int y_ld,
                      void* stream);

@@ -418,8 +418,9 @@ def conv_units(K, cin):
 
 
 def epilogue64(y, b, acc_in=None, b_acc=None, scale=None, shift=None, res=None, res_hl=False, relu=False,
-               hl_out=False):
-    """float64 epilogue z = relu((y + acc_in) * scale + shift + res) with its propagated bound (b: bound of y)"""
+               hl_out=False, roundings=3):
+    """float64 epilogue z = relu((y + acc_in) * scale + shift + res) with its propagated bound (b: bound of y);
+    roundings: the multiple of 2^-24 * (|y * scale| + |shift| + |res|) charged for the three fp32 operations"""
     y = np.asarray(y, np.float64)
     if acc_in is not None:
         y = y + acc_in
@@ -428,7 +429,7 @@ def epilogue64(y, b, acc_in=None, b_acc=None, scale=None, shift=None, res=None, 
     sh = np.zeros(y.shape[1]) if shift is None else np.asarray(shift, np.float64)
     r = np.zeros_like(y) if res is None else np.asarray(res, np.float64)
     z = y * sc + sh + r
-    bz = np.abs(sc) * b + 3 * U24 * (np.abs(y * sc) + np.abs(sh) + np.abs(r))
+    bz = np.abs(sc) * b + roundings * U24 * (np.abs(y * sc) + np.abs(sh) + np.abs(r))
     if res is not None and res_hl:
         bz = bz + U24 * np.abs(r) + 2.0 ** -25
     if relu:
@@ -467,3 +468,188 @@ def within(got, ref, bound):
     ratio = err / np.maximum(bound, 1e-300)
     i = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
     return bool((err <= bound).all()) and bool(np.isfinite(got).all()), i, float(ratio[i])
+
+
+# ---- float64 row kernels with per-element error bounds (tests/test_row_kernels_gpu.py) --------------------------------
+ROW_ERROR_MODEL = """Error model of the row kernels (affine, BatchNorm fold / statistics / backward, column sums, the hl
+format, the heads), per output element.  u = 2^-24 (U24).  Every function below takes the fp32 arrays the kernel receives,
+computes in float64 and returns (value, bound) pairs for within().  The constants are forward-error counts of the fp32
+operations in the kernel source with about 2x margin; tests/test_row_bound.py pins each of them on the CPU (a numpy fp32
+restatement of the kernel's operation order stays at a ratio <= 0.6 of the bound; named wrong results are >= 10 x outside).
+
+  affine       z = relu?(x * scale + shift + res): one product, two additions (or an fma and an addition):
+               4u (|x * scale| + |shift| + |res|) - epilogue64 with b = 0 and one more u of margin; the hl twin adds
+               u |z| + 2^-25 (ERROR_MODEL).  ReLU is 1-Lipschitz.
+  bn_fold      scale = gamma / sqrt(var + eps): addition, square root, division: 6u |scale|.
+               shift = beta - mean * scale (+ bias * scale):
+               2u (|beta| + 2 |mean * scale| + 2 |bias * scale|) + (|mean| + |bias|) * bound(scale)
+  bn_stats     sums of x and x^2 in double, one rounding to fp32 at the end:
+               mean        2u |mean| + 2^-50 * mean(|x|)
+               biased var  2u * var + 2^-48 * mean(x^2)       (E[x^2] - mu^2 is formed in double: the second term is the
+                           cancellation; a negative difference is clamped to 0)
+               running     r' = (1 - m) * r + m * s (s = mean, or the unbiased variance var * n / (n - 1); n = 1 keeps
+                           var): m * bound(s) + 2u of each fp32 result of the update, the two products and their sum:
+                           2u (|(1 - m) * r| + |m * s| + |r'|)   (1 - m is itself rounded: three roundings against 4u)
+               scale       gamma / sqrtf((float) var + eps): |scale| (4u + 0.5 (bound(var) + u (var + eps)) / (var + eps))
+               shift       beta - (float) mean * scale: u (|beta| + 2 |mean * scale|) + |mean| bound(scale) + |scale| bound(mean)
+  bn_backward  mean32 / var32 are exact inputs (arguments of the call).  g = dy * open, istd = 1 / sqrt(var32 + eps),
+               xh = (x - mean32) * istd.
+               dbeta  = sum g (double accumulator, one rounding):   2u |dbeta| + 2^-50 * sum |g|
+               dgamma = sum g * xh (fp32 products: subtraction, istd's three operations, two products; double
+                        accumulator):                               8u * sum |g * xh| + u |dgamma|
+               dx     = gamma * istd * (g - dbeta / n - xh * dgamma / n):
+                        |gamma * istd| * (16u (|g| + |dbeta| / n + |xh * dgamma| / n) + (bound(dbeta) + |xh| bound(dgamma)) / n)
+               dres   = g, exact
+  col_sum      fp32 throughout: a thread adds every 8th row of its chunk, 8 partial sums meet in LDS, `chunks` partial
+               sums per column are added (in chunk order, or by fp32 atomics in any order):
+               (ceil(n / 8 / chunks) + 8 + chunks + 2) * u * sum |x|
+  hl format    bit-exact model hl_bits(): h = RNE16(x), l = RNE16(x - float32(h)); per 32-channel chunk 64 bytes of h,
+               then 64 bytes of l (sparse_conv_common.h).  h + l is x to 2u |x| (the remainder x - h has up to 12
+               significant bits, l keeps 11) plus 2^-25 absolute where l is subnormal; the u |z| + 2^-25 that epilogue64 charges
+               an hl output is the typical case, and the affine's spare u covers the rest
+  heads        exact selection semantics in float64 (first index on ties, class `nclasses` -> head 0); exp / softmax
+               outputs are held to the tolerances the project holds expf to (tests/test_decode_gpu.py)
+"""
+
+
+def affine64(x, scale=None, shift=None, res=None, relu=False, hl_out=False):
+    """(z, bound) of cv_sp_affine_f32 / cv_sp_affine_hl_f32: relu?(x * scale + shift + res).  Without a scale the
+    kernel applies no shift either."""
+    assert scale is not None or shift is None
+    x = np.asarray(x, np.float64)
+    return epilogue64(x, np.zeros_like(x), scale=scale, shift=shift, res=res, relu=relu, hl_out=hl_out, roundings=4)
+
+
+def bn_fold64(gamma, beta, mean, var, bias=None, eps=1e-5):
+    """((scale, bound), (shift, bound)) of cv_sp_bn_fold_f32"""
+    gamma, beta, mean, var = (np.asarray(a, np.float64) for a in (gamma, beta, mean, var))
+    eps = float(np.float32(eps))
+    bias = np.zeros_like(mean) if bias is None else np.asarray(bias, np.float64)
+    scale = gamma / np.sqrt(var + eps)
+    b_scale = 6 * U24 * np.abs(scale)
+    shift = beta - mean * scale + bias * scale
+    b_shift = 2 * U24 * (np.abs(beta) + 2 * np.abs(mean * scale) + 2 * np.abs(bias * scale)) + \
+        (np.abs(mean) + np.abs(bias)) * b_scale
+    return (scale, b_scale), (shift, b_shift)
+
+
+def bn_stats64(x, n=None, gamma=None, beta=None, eps=1e-5, momentum=0.1, running_mean=None, running_var=None):
+    """cv_sp_bn_stats_f32 on the first n rows of x: dict of (value, bound) for "mean", "var" (biased), "scale", "shift"
+    and, with starting values, "running_mean" / "running_var" """
+    x = np.asarray(x, np.float64)
+    n = x.shape[0] if n is None else n
+    x = x[:n]
+    eps, m = float(np.float32(eps)), float(np.float32(momentum))
+    mean = x.mean(0)
+    var = ((x - mean) ** 2).mean(0)                  # the centred form: no cancellation of its own
+    b_mean = 2 * U24 * np.abs(mean) + 2.0 ** -50 * np.abs(x).mean(0)
+    b_var = 2 * U24 * var + 2.0 ** -48 * (x * x).mean(0)
+    out = {"mean": (mean, b_mean), "var": (var, b_var)}
+    if gamma is not None:
+        gamma, beta = np.asarray(gamma, np.float64), np.asarray(beta, np.float64)
+        scale = gamma / np.sqrt(var + eps)
+        b_scale = np.abs(scale) * (4 * U24 + 0.5 * (b_var + U24 * (var + eps)) / (var + eps))
+        shift = beta - mean * scale
+        b_shift = U24 * (np.abs(beta) + 2 * np.abs(mean * scale)) + np.abs(mean) * b_scale + np.abs(scale) * b_mean
+        out["scale"], out["shift"] = (scale, b_scale), (shift, b_shift)
+    if running_mean is not None:
+        f = n / (n - 1.0) if n > 1 else 1.0
+        for name, r0, s, bs in (("running_mean", running_mean, mean, b_mean), ("running_var", running_var, var * f, b_var * f)):
+            t1, t2 = (1.0 - m) * np.asarray(r0, np.float64), m * s
+            out[name] = (t1 + t2, m * bs + 2 * U24 * (np.abs(t1) + np.abs(t2) + np.abs(t1 + t2)))
+    return out
+
+
+def bn_backward64(x, dy, open_mask, mean32, var32, gamma, n=None, eps=1e-5):
+    """cv_sp_bn_backward_f32 given the fp32 mean / variance the call receives: dict of (value, bound) for "dbeta",
+    "dgamma", "dx", "dres".  open_mask: where the ReLU behind the normalisation was open (None: no ReLU)"""
+    x, dy = np.asarray(x, np.float64), np.asarray(dy, np.float64)
+    n = x.shape[0] if n is None else n
+    x, dy = x[:n], dy[:n]
+    eps = float(np.float32(eps))
+    mean, var, gamma = (np.asarray(a, np.float64) for a in (mean32, var32, gamma))
+    g = dy if open_mask is None else dy * np.asarray(open_mask[:n], np.float64)
+    istd = 1.0 / np.sqrt(var + eps)
+    xh = (x - mean) * istd
+    dbeta = g.sum(0)
+    b_dbeta = 2 * U24 * np.abs(dbeta) + 2.0 ** -50 * np.abs(g).sum(0)
+    dgamma = (g * xh).sum(0)
+    b_dgamma = 8 * U24 * np.abs(g * xh).sum(0) + U24 * np.abs(dgamma)
+    dx = gamma * istd * (g - dbeta / n - xh * dgamma / n)
+    b_dx = np.abs(gamma * istd) * (16 * U24 * (np.abs(g) + np.abs(dbeta) / n + np.abs(xh * dgamma) / n) +
+                                   (b_dbeta + np.abs(xh) * b_dgamma) / n)
+    return {"dbeta": (dbeta, b_dbeta), "dgamma": (dgamma, b_dgamma), "dx": (dx, b_dx), "dres": (g, np.zeros_like(g))}
+
+
+def col_sum64(x, chunks):
+    """(sums, bound) of cv_sp_col_sum_det_f32 / cv_sp_col_sum_f32 launched with `chunks` row chunks"""
+    x = np.asarray(x, np.float64)
+    n = x.shape[0]
+    steps = -(-n // (8 * chunks)) + 8 + chunks + 2
+    return x.sum(0), steps * U24 * np.abs(x).sum(0)
+
+
+def hl_bits(x):
+    """the hl format of fp32 rows x [n, c] (c % 32 == 0), bit for bit: uint32 words [n, c]"""
+    x = np.ascontiguousarray(x, np.float32)
+    n, c = x.shape
+    assert c % 32 == 0
+    with np.errstate(over="ignore"):
+        h = x.astype(np.float16)
+        l = (x - h.astype(np.float32)).astype(np.float16)
+    words = np.stack([h.reshape(n, c // 32, 32), l.reshape(n, c // 32, 32)], 2)        # [n, chunk, h | l, 32] fp16
+    return np.ascontiguousarray(words).view(np.uint32).reshape(n, c)
+
+
+def hl_decode(bits):
+    """float32(h) + float32(l) of hl words [n, c] (what cv_sp_from_hl_f32 returns)"""
+    n, c = bits.shape
+    p = np.ascontiguousarray(bits, np.uint32).view(np.float16).reshape(n, c // 32, 2, 32).astype(np.float32)
+    return (p[:, :, 0] + p[:, :, 1]).reshape(n, c)
+
+
+def head_joint64(out, nclasses=9, log_scale=True):
+    """cv_head_joint_f32 in float64 (eval_joint.py:173-190): xyz, scale, prob, class; arg-max takes the first index
+    on ties, class `nclasses` (background) selects head 0"""
+    out = np.asarray(out, np.float64)
+    n = out.shape[0]
+    logit = out[:, 6 * nclasses:7 * nclasses + 1]
+    am = logit.argmax(1)
+    h = np.where(am == nclasses, 0, am)
+    rows = np.arange(n)
+    xyz = out[:, :3 * nclasses].reshape(n, nclasses, 3)[rows, h]
+    scale = out[:, 3 * nclasses:6 * nclasses].reshape(n, nclasses, 3)[rows, h]
+    if log_scale:
+        scale = np.exp(scale)
+    cls = logit[:, :nclasses].argmax(1)
+    e = np.exp(logit - logit.max(1, keepdims=True))
+    prob = (e[:, :nclasses] / e.sum(1, keepdims=True)).max(1)
+    return xyz, scale, prob, cls
+
+
+def head_separate64(out, log_scale=True):
+    """cv_head_separate_f32 in float64 (eval_separate.py:170-181): xyz, scale, prob = softmax(out[6:8])[1]"""
+    out = np.asarray(out, np.float64)
+    scale = np.exp(out[:, 3:6]) if log_scale else out[:, 3:6]
+    mx = np.maximum(out[:, 6], out[:, 7])
+    e0, e1 = np.exp(out[:, 6] - mx), np.exp(out[:, 7] - mx)
+    return out[:, :3], scale, e1 / (e0 + e1)
+
+
+def row_case(n, c, seed=0):
+    """inputs of the row-kernel tests (fp32): x [n, c] with rows of 1e-3 and 30 times the unit scale and channel means
+    of up to 3 sigma, channel c // 2 with a variance below 1e-6 (c >= 2), channel c - 1 constant (c >= 3: its variance
+    is exactly 0 and eps decides); dy, res [n, c]; gamma, beta, bias, running_mean, running_var [c]"""
+    rng = np.random.default_rng(seed * 1000003 + n * 7 + c * 131)
+    x = rng.normal(0, 1, (n, c))
+    x[::7] *= 1e-3
+    x[::11] *= 30.0
+    x += rng.uniform(-3, 3, c)
+    if c >= 2:
+        x[:, c // 2] = 0.7 + 3e-4 * rng.normal(0, 1, n)
+    if c >= 3:
+        x[:, c - 1] = rng.uniform(0.5, 2.0)
+    f = lambda a: np.ascontiguousarray(a, np.float32)
+    return dict(x=f(x), dy=f(rng.normal(0, 1, (n, c))), res=f(rng.normal(0, 1, (n, c))),
+                gamma=f(rng.uniform(0.5, 1.5, c)), beta=f(rng.normal(0, 0.2, c)), bias=f(rng.normal(0, 0.5, c)),
+                running_mean=f(rng.normal(0, 0.5, c)), running_var=f(rng.uniform(0.5, 2.0, c)))

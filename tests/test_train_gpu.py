@@ -401,7 +401,8 @@ def test_a_forward_beyond_the_fp16_range_skips_its_update_on_the_device(cuda, bu
 
 def test_batchnorm_training_kernels_match_torch(cuda, built_lib):
     """MinkowskiBatchNorm in train mode (HIP statistics / apply / backward) vs torch.nn.BatchNorm1d on the CPU,
-    including the running-statistics update and a strided feature view."""
+    including the running-statistics update.  The module makes every operand contiguous first; leading dimensions wider
+    than the row are covered by tests/test_row_kernels_gpu.py."""
     rng = np.random.default_rng(0)
     for n, c in ((5000, 96), (333, 32), (20000, 256)):
         x = (rng.normal(0.3, 2.0, (n, c)) * rng.uniform(0.5, 2, c)).astype(np.float32)
