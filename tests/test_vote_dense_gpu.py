@@ -6,8 +6,9 @@ that preceded it: tests/golden/vote_parent_bits.json holds the sha256 of the byt
 kernel wrote them.  All six channels accumulate as 2^-36 fixed-point integers, whose sums do not depend on the order or the
 grouping of the votes, so the hashes are expected to be EQUAL.
 
-Not covered: the overflow of the work-list array (list mode falling back to streaming) - no scene of a few thousand points
-reaches the capacity of 40 entries per point, and no other test of the suite does either."""
+The overflow of the work-list array (list mode falling back to streaming) and the other launch shapes that no case here takes
+(more than 4096 planes, the tile-count bounds of the queue launch, more than 256 rotations) are in
+tests/test_vote_fallbacks_gpu.py."""
 import functools
 import hashlib
 import json
