@@ -19,6 +19,7 @@ import ctypes
 import math
 import os
 import threading
+import weakref
 
 import numpy as np
 import torch
@@ -159,16 +160,6 @@ class CoordinateManager:
         if self.num_levels < num_levels:
             self._build(num_levels, True)
 
-    def cross_map(self, out_coords, k, ts=1):
-        """kernel map of an arbitrary output set looked up in THIS manager's level-0 table"""
-        L = _lib.lib()
-        m = torch.empty((out_coords.shape[0], k ** 3), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(L.cv_sp_kernel_map(_ptr(out_coords), out_coords.shape[0], _ptr(self._keys[0]),
-                                          _ptr(self._vals[0]), self.cap, k, ts, _ptr(m), _stream(self.device)),
-                       "cv_sp_kernel_map")
-        return m
-
     def mask_perms(self, k, ts, groups=2):
         """int32 [groups, n]: for each contiguous group of the k^3 offsets, the row order sorted by the
         bit mask of valid neighbours within that group (stride-1 map at tensor stride ts, cached)."""
@@ -270,7 +261,6 @@ class CoordinateManager:
         plan.views = None
         cache[(stem_k, mmr)] = plan
         self._fused = plan
-        self._fused_k = stem_k
         return plan
 
     def fused_plan(self, stem_k=5):
@@ -444,110 +434,81 @@ def range_flag(dev):
     return f
 
 
+def _piece_path(cin, cout, flavour=0):
+    """the convolution runs on packed 16-bit weight pieces (conv_rows_wp / conv_hl / conv_hd), not on v_mfma_f32_32x32x2_f32"""
+    return CONV_X6 and flavour in (0, 1) and cin % 32 == 0 and cout % 4 == 0
+
+
 def conv_forward(x_feats, weight, nbr, n_out, scale=None, shift=None, residual=None, relu=False,
                  out=None, flavour=0, row_perm=None, j_begin=0, j_end=0, acc_in=None, perm_groups=0,
                  cache_weights=True, pieces=None, in_hl=False, out_hl=False, res_hl=False, stem_mfma=False,
-                 split_tickets=None, weight_t=False, acc_scale_dev=None):
+                 split_tickets=None, weight_t=False, acc_scale_dev=None, step=None):
     """Low-level call into cv_sp_conv_f32 (fused epilogue).  weight [K,Cin,Cout] or [Cin,Cout].
     in_hl / out_hl / res_hl: the operand is in the hl format (to_hl / from_hl; cv_conv_desc.in_hl), pieces=2 only.
-    pieces=2: fp16-pair products (weights packed per call; the caller reads range_flag(dev) after synchronising);
-    pieces=1: single bf16 products (the opt-in bf16 compute mode); None: 1 under COMPUTE_DTYPE == "bf16", else 3."""
+    pieces=2: fp16-pair products (the caller reads range_flag(dev) after synchronising);
+    pieces=1: single bf16 products (the opt-in bf16 compute mode); None: 1 under COMPUTE_DTYPE == "bf16", else 3.
+    weight_t: the TRANSPOSED convolution of `weight` ([K, Cout', Cin'] = a layer's forward kernel; the input gradient).
+    step: the training step whose weight scales and pre-packed weights apply (None: the calling thread's, if any)."""
     if pieces is None:
         pieces = 1 if COMPUTE_DTYPE == "bf16" else 3
     L = _lib.lib()
     dev = x_feats.device
+    # 1. the operands
     w = weight if weight.dim() == 3 else weight[None]
-    if weight_t:
-        # the TRANSPOSED convolution of `weight` ([K, Cout', Cin'] = a layer's forward kernel; the input gradient):
-        # packed straight from the forward layout where the 16-bit piece path runs, transposed by a copy otherwise
-        K, cout, cin = w.shape
-        x6_ok = CONV_X6 and flavour in (0, 1) and cin % 32 == 0 and cout % 4 == 0 and pieces in (1, 2, 3)
-        if not x6_ok:
-            w = w.permute(0, 2, 1)
-            weight_t = False
-    else:
-        K, cin, cout = w.shape
-    assert x_feats.shape[1] == cin and x_feats.stride(1) == 1
+    if weight_t and not _piece_path(w.shape[2], w.shape[1], flavour):
+        w, weight_t = w.permute(0, 2, 1), False       # (packed straight from the forward layout only where the pieces run)
     w = w.contiguous()
+    K, cin, cout = (w.shape[0], w.shape[2], w.shape[1]) if weight_t else w.shape
+    assert x_feats.shape[1] == cin and x_feats.stride(1) == 1
     if out is None:
         out = torch.empty((n_out, cout), dtype=torch.float32, device=dev)
+    # 2. generic (module-by-module / training) path: mask-sorted offset groups, orders cached on the map
     if (AUTO_MASK_GROUPS > 1 and row_perm is None and perm_groups == 0 and flavour == 0 and nbr is not None
             and K == 27 and n_out >= AUTO_MASK_MIN_ROWS and cin % 32 == 0 and j_begin == 0 and j_end == 0
             and acc_in is None):
-        # generic (module-by-module / training) path: mask-sorted offset groups, orders cached on the map
         row_perm = map_mask_perms(nbr, AUTO_MASK_GROUPS)
         perm_groups = row_perm.shape[0]
-    wp6 = None
-    acc_scale, flag = 0.0, None
-    if CONV_X6 and flavour in (0, 1) and cin % 32 == 0 and cout % 4 == 0:
-        if pieces == 2 and weight_t:
-            # the input gradient on fp16 pairs: W^T packed straight from the forward layout with the layer's scale of this step
-            pk = _bwd_ctx.get("packed")
-            pre = pk.get((w.data_ptr(), 1)) if pk else None
-            if pre is not None and pre[0].numel() == 2 * w.numel():
-                wp6, k = pre                              # packed at the start of the step (_prepack_pairs)
-                TRAIN_COUNTERS["prepacked"] += 1
-            else:
-                hints = _bwd_ctx.get("pair_scales")         # (the backward nodes run on the autograd engine's thread)
-                k = hints.get(weight.data_ptr()) if hints is not None else None
-                if k is None:
-                    k = h2_scale_log2((w, None))
-                wp6 = torch.empty(2 * w.numel(), dtype=torch.int16, device=dev)
-                with _on(dev):
-                    _lib.check(L.cv_sp_pack_weights_t_f32(_ptr(w), K, cout, cin, 2, int(k), _ptr(wp6), _stream(dev)),
-                               "cv_sp_pack_weights_t_f32")
-            acc_scale, flag = 2.0 ** -k, range_flag(dev)
-        elif pieces == 2:
-            key = id(weight)
-            ver = (weight.data_ptr(), weight._version, tuple(weight.shape))
-            hit = _packed_h2.get(key) if cache_weights else None
-            pk = _bwd_ctx.get("packed") if not cache_weights else None
-            pre = pk.get((w.data_ptr(), 0)) if pk else None
-            if pre is not None and pre[0].numel() == 2 * w.numel():
-                hit = (ver, pre[0], pre[1])               # packed at the start of the step (_prepack_pairs)
-                TRAIN_COUNTERS["prepacked"] += 1
-            elif hit is None or hit[0] != ver:
-                hints = getattr(_train_state, "pair_scales", None)
-                k = hints.get(weight.data_ptr()) if hints is not None else None
-                if k is None:
-                    k = h2_scale_log2((w, None))          # (one host wait: the training step hands the scales over instead)
-                hit = (ver, packed_weights_h2(w, None, k), k)
-                if cache_weights:
-                    if len(_packed_h2) > 512:
-                        _packed_h2.clear()
-                    _packed_h2[key] = hit
-            wp6, acc_scale, flag = hit[1], 2.0 ** -hit[2], range_flag(dev)
-        elif weight_t:
-            wp6 = torch.empty((3 if pieces == 3 else 1) * w.numel(), dtype=torch.int16, device=dev)
-            with _on(dev):
-                _lib.check(L.cv_sp_pack_weights_t_f32(_ptr(w), K, cout, cin, pieces, 0, _ptr(wp6), _stream(dev)),
-                           "cv_sp_pack_weights_t_f32")
-        elif pieces == 1:
-            wp6 = packed_weights_bf16(w)
-        else:
-            wp6 = packed_weights_x6(weight, w, cache_weights)
-    if stem_mfma and pieces == 2 and cin in (3, 6) and cout == 32 and K <= 128 and nbr is not None and flavour == 0:
-        # the matrix-core stem (conv_stem_mfma): BatchNorm scale folded into the fp16-pair weights
-        hints = getattr(_train_state, "pair_scales", None) if scale is None else None      # (a training step hands the scales over)
-        k = hints.get(weight.data_ptr()) if hints is not None else None
-        if k is None:
-            k = h2_scale_log2((w, scale))
-        wp6, acc_scale, flag, scale = packed_weights_stem_h2(w, scale, k), 2.0 ** -k, range_flag(dev), None
+    # 3. the weights as the kernel reads them
+    wp, _, weight_pieces, acc_scale, folded = resolve_weights(
+        weight, w, pieces, flavour=flavour, transposed=weight_t, stem=stem_mfma and nbr is not None and flavour == 0,
+        col_scale=scale, cache=cache_weights, step=step if step is not None else current_step())
+    if folded:
+        scale = None
+    # 4. the descriptor
     ws = None
     if perm_groups > 1:
         ws = _workspace(dev, 4 * perm_groups * n_out * cout + 256)
     elif flavour == 0 and n_out < 128 * 384:
         ws = _workspace(dev, int(L.cv_sp_conv_workspace_bytes(n_out, cout, K)))
-    p = lambda t: t.data_ptr() if t is not None else None
-    d = _lib.ConvDesc(p(x_feats), x_feats.shape[0], x_feats.stride(0), cin, p(w), K, cout, p(nbr), n_out,
-                      p(scale), p(shift), p(residual), residual.stride(0) if residual is not None else 0,
-                      1 if relu else 0, p(out), out.stride(0), flavour, p(ws),
-                      ws.numel() if ws is not None else 0, p(row_perm), j_begin, j_end, p(acc_in),
-                      acc_in.stride(0) if acc_in is not None else 0, perm_groups,
-                      None, None, None, p(wp6), None, 0, 0, None,
-                      1 if (perm_groups > 1 and getattr(row_perm, "_cv_has_map", False)) else 0,
-                      2 if flag is not None else (1 if (pieces == 1 and wp6 is not None) else 0), acc_scale, p(flag),
-                      1 if in_hl else 0, 1 if out_hl else 0, 1 if res_hl else 0, p(split_tickets), p(acc_scale_dev))
+    # (only what is set: ctypes zero-fills the rest, the three reserved fields among them, and every keyword costs host time)
+    d = _lib.ConvDesc(in_=x_feats.data_ptr(), n_in=x_feats.shape[0], in_ld=x_feats.stride(0), cin=cin, weight=w.data_ptr(),
+                      K=K, cout=cout, n_out=n_out, relu=bool(relu), out=out.data_ptr(), out_ld=out.stride(0), flavour=flavour,
+                      perm_groups=perm_groups, weight_pieces=weight_pieces, acc_scale=acc_scale, in_hl=bool(in_hl),
+                      out_hl=bool(out_hl), res_hl=bool(res_hl))
+    if nbr is not None:
+        d.nbr = nbr.data_ptr()
+    if scale is not None:
+        d.scale = scale.data_ptr()
+    if shift is not None:
+        d.shift = shift.data_ptr()
+    if residual is not None:
+        d.residual, d.res_ld = residual.data_ptr(), residual.stride(0)
+    if ws is not None:
+        d.ws, d.ws_bytes = ws.data_ptr(), ws.numel()
+    if row_perm is not None:
+        d.row_perm, d.perm_has_map = row_perm.data_ptr(), bool(perm_groups > 1 and getattr(row_perm, "_cv_has_map", False))
+    if j_begin or j_end:
+        d.j_begin, d.j_end = j_begin, j_end
+    if acc_in is not None:
+        d.acc_in, d.acc_ld = acc_in.data_ptr(), acc_in.stride(0)
+    if wp is not None:
+        d.weight_x6 = wp.data_ptr()
+    if weight_pieces == 2:
+        d.range_flag = range_flag(dev).data_ptr()
+    if split_tickets is not None:
+        d.split_tickets = split_tickets.data_ptr()
+    if acc_scale_dev is not None:
+        d.acc_scale_dev = acc_scale_dev.data_ptr()
     with _on(dev):
         _lib.check(L.cv_sp_conv_f32(ctypes.byref(d), _stream(dev)), "cv_sp_conv_f32")
     return out
@@ -579,7 +540,6 @@ def set_split_target(workgroups):
 
 def set_option(name, value):
     """cv_sp_set_option: kernel selection knobs of the convolutions ("hd_mask", "hd_min_rows"); returns the previous value"""
-    import ctypes
     prev = ctypes.c_longlong(0)
     _lib.check(_lib.lib().cv_sp_set_option(name.encode(), int(value), ctypes.byref(prev)), "cv_sp_set_option")
     return int(prev.value)
@@ -642,9 +602,6 @@ def _perms_with_map(nbr, groups):
     return m
 
 
-_packed = {}
-_packed_x6 = {}
-_packed_h2 = {}
 # 1 (default): vector-path convs run their fp32 products as six bf16 piece products on the bf16 matrix cores
 # (conv_rows_wp); 0: v_mfma_f32_32x32x2_f32
 CONV_X6 = os.environ.get("CV_CONV_X6", "1") != "0"
@@ -665,41 +622,36 @@ def set_compute_dtype(dtype):
     return prev
 
 
-def packed_weights_bf16(w3, col_scale=None):
-    """uncached: weights (times an optional per-output-column scale) rounded to bf16 in conv_rows_wp's layout"""
+def pack_weights(w3, pieces, col_scale=None, scale_log2=0, transposed=False, stem=False):
+    """uncached: w3 [K, Cin, Cout] (times an optional per-output-column scale - a folded BatchNorm - and 2^scale_log2) as the
+    int16 words one of the piece kernels reads: pieces = 3 bf16 triples (conv_rows_wp; cv_sp_pack_weights_x6_f32), 2 fp16
+    pairs (cv_sp_pack_weights_h2_f32), 1 one bf16 (cv_sp_pack_weights_bf16_f32).  transposed: the weights of the transposed
+    convolution, packed straight from the forward layout (cv_sp_pack_weights_t_f32; no column scale).  stem: [K, 3|6, 32] as
+    fp16 pairs in the B-operand order of conv_stem_mfma (cv_sp_pack_weights_stem_h2_f32)."""
     L = _lib.lib()
-    K, cin, cout = w3.shape
-    wp = torch.empty(w3.numel(), dtype=torch.int16, device=w3.device)
-    with _on(w3.device):
-        _lib.check(L.cv_sp_pack_weights_bf16_f32(_ptr(w3), K, cin, cout, _ptr(col_scale), _ptr(wp),
-                                                 _stream(w3.device)), "cv_sp_pack_weights_bf16_f32")
-    return wp
-
-
-def invalidate_weight_caches():
-    """Drop every cached re-packing of a weight tensor.  The caches are keyed by tensor version, and fused
-    optimizers (torch.optim.Adam(fused=True)) update parameters WITHOUT bumping it: modules call this when they
-    switch between train and eval mode, and the training path never caches."""
-    _packed.clear()
-    _packed_x6.clear()
-    _packed_h2.clear()
-
-
-def packed_weights_x6_scaled(w3, col_scale):
-    """uncached: weights times a per-output-column scale (a folded BatchNorm), split into bf16 pieces"""
-    L = _lib.lib()
-    K, cin, cout = w3.shape
-    wp = torch.empty(3 * w3.numel(), dtype=torch.int16, device=w3.device)
-    with _on(w3.device):
-        _lib.check(L.cv_sp_pack_weights_x6_f32(_ptr(w3), K, cin, cout, _ptr(col_scale), _ptr(wp), _stream(w3.device)),
-                   "cv_sp_pack_weights_x6_f32")
+    dev = w3.device
+    K, c1, c2 = w3.shape
+    assert not (transposed and col_scale is not None) and not (stem and (pieces != 2 or c2 != 32))
+    wp = torch.empty(8 * c1 * 1024 if stem else pieces * w3.numel(), dtype=torch.int16, device=dev)
+    args, k, st = (_ptr(w3), K, c1, c2), int(scale_log2), _stream(dev)
+    with _on(dev):
+        if stem:
+            _lib.check(L.cv_sp_pack_weights_stem_h2_f32(_ptr(w3), K, c1, _ptr(col_scale), k, _ptr(wp), st),
+                       "cv_sp_pack_weights_stem_h2_f32")
+        elif transposed:
+            _lib.check(L.cv_sp_pack_weights_t_f32(*args, pieces, k, _ptr(wp), st), "cv_sp_pack_weights_t_f32")
+        elif pieces == 2:
+            _lib.check(L.cv_sp_pack_weights_h2_f32(*args, _ptr(col_scale), k, _ptr(wp), st), "cv_sp_pack_weights_h2_f32")
+        elif pieces == 1:
+            _lib.check(L.cv_sp_pack_weights_bf16_f32(*args, _ptr(col_scale), _ptr(wp), st), "cv_sp_pack_weights_bf16_f32")
+        else:
+            _lib.check(L.cv_sp_pack_weights_x6_f32(*args, _ptr(col_scale), _ptr(wp), st), "cv_sp_pack_weights_x6_f32")
     return wp
 
 
 def h2_scale_log2(*scaled_weights):
     """power of two that brings the largest magnitude of the given (weight [K,Cin,Cout], column scale or None) sets
     to about 2^13 (cv_sp_pack_weights_h2_f32); one host sync, at pack time only"""
-    import math
     amax = 0.0
     for w3, col_scale in scaled_weights:
         a = w3.abs().amax(dim=(0, 1)) if col_scale is not None else w3.abs().max()
@@ -709,53 +661,71 @@ def h2_scale_log2(*scaled_weights):
     return max(-60, min(60, 13 - math.ceil(math.log2(amax))))
 
 
-def packed_weights_h2(w3, col_scale, scale_log2):
-    """uncached: weights (times an optional per-output-column scale and 2^scale_log2) split into two fp16 pieces"""
-    L = _lib.lib()
-    K, cin, cout = w3.shape
-    wp = torch.empty(2 * w3.numel(), dtype=torch.int16, device=w3.device)
-    with _on(w3.device):
-        _lib.check(L.cv_sp_pack_weights_h2_f32(_ptr(w3), K, cin, cout, _ptr(col_scale), int(scale_log2), _ptr(wp),
-                                               _stream(w3.device)), "cv_sp_pack_weights_h2_f32")
-    return wp
+# eval-time cache of packed weights, every format: id(weight) -> (weak reference, (data_ptr, _version, shape), {format: (words,
+# scale_log2)}).  A hit is the SAME live tensor object, unmodified: the weak reference drops the entry when the tensor dies,
+# so neither a recycled id nor a recycled allocation of the same shape can meet the packing of a dead tensor.
+_pack_cache = {}
 
 
-def packed_weights_stem_h2(w3, col_scale, scale_log2):
-    """uncached: stem weights [K, 3|6, 32] (times an optional column scale and 2^scale_log2) as fp16 pairs in the
-    B-operand order of conv_stem_mfma (cv_sp_pack_weights_stem_h2_f32)"""
-    L = _lib.lib()
-    K, cin, cout = w3.shape
-    assert cout == 32
-    wp = torch.empty(8 * cin * 1024, dtype=torch.int16, device=w3.device)
-    with _on(w3.device):
-        _lib.check(L.cv_sp_pack_weights_stem_h2_f32(_ptr(w3), K, cin, _ptr(col_scale), int(scale_log2), _ptr(wp),
-                                                    _stream(w3.device)), "cv_sp_pack_weights_stem_h2_f32")
-    return wp
+def invalidate_weight_caches():
+    """Drop every cached re-packing of a weight tensor.  The cache is keyed by tensor version, and fused optimizers
+    (torch.optim.Adam(fused=True)) update parameters WITHOUT bumping it: modules call this when they switch between train and
+    eval mode, and the training path never caches."""
+    _pack_cache.clear()
 
 
-def packed_weights_x6(weight, w3, cache=True):
-    """weights split into bf16 pieces for conv_rows_wp (cv_sp_pack_weights_x6_f32), cached per parameter tensor and
-    re-packed when it is modified in place or re-allocated."""
+def _cached_packings(weight):
+    """the {format: (words, scale_log2)} table of this tensor object as it is now"""
     key = id(weight)
     ver = (weight.data_ptr(), weight._version, tuple(weight.shape))
-    hit = _packed_x6.get(key)
-    if not cache:            # training: the weights change every step (see invalidate_weight_caches)
-        hit = None
-    if hit is None or hit[0] != ver or hit[2]() is not weight:
-        import weakref
-        L = _lib.lib()
-        K, cin, cout = w3.shape
-        wp = torch.empty(3 * w3.numel(), dtype=torch.int16, device=w3.device)
-        with _on(w3.device):
-            _lib.check(L.cv_sp_pack_weights_x6_f32(_ptr(w3), K, cin, cout, None, _ptr(wp), _stream(w3.device)),
-                       "cv_sp_pack_weights_x6_f32")
-        try:
-            ref = weakref.ref(weight, lambda _r, k=key: _packed_x6.pop(k, None))
-        except TypeError:
-            ref = lambda: weight
-        hit = _packed_x6[key] = (ver, wp, ref)
-    return hit[1]
+    hit = _pack_cache.get(key)
+    if hit is None or hit[1] != ver or hit[0]() is not weight:
+        hit = _pack_cache[key] = (weakref.ref(weight, lambda _r, k=key: _pack_cache.pop(k, None)), ver, {})
+    return hit[2]
 
+
+def resolve_weights(weight, w3, pieces, flavour=0, transposed=False, stem=False, col_scale=None, second=None, cache=False,
+                    step=None):
+    """How a convolution's weights reach the kernel - the one place that decides it, for conv_forward and the eval program:
+    (packed words, packed words of the second source, cv_conv_desc.weight_pieces, acc_scale, BatchNorm scale folded in).
+    weight: the caller's tensor (the cache and a step's scales go by it); w3: the same as contiguous [K, Cin, Cout]
+    (transposed: the forward kernel [K, Cout', Cin'] of the layer whose input gradient this is).
+    pieces: 1 / 2 / 3 as in pack_weights, where the shape allows the piece kernels (_piece_path) - else (None, None, 3, 1, False):
+    fp32 products on the unpacked weights.  stem: the caller allows conv_stem_mfma (fp16 pairs, [K <= 128, 3|6, 32]).
+    col_scale: the BatchNorm scale of the epilogue; folded into the packed weights (the caller then drops it) for the stem and
+    with a second source.  second = (w2 [1, Cin2, Cout], scale2): out += scale2 * (src2 @ w2), one accumulator - one common
+    power of two for the fp16 pairs.
+    fp16 pairs take their power of two (acc_scale = 2^-k) from, in this order: the step's pre-packed arena (not with cache),
+    the step's per-weight exponents (nothing folded in), one readback of the maximum (h2_scale_log2).
+    cache: keep / take the packing in the eval-time cache (never a folded or a transposed one)."""
+    K, cin, cout = (w3.shape[0], w3.shape[2], w3.shape[1]) if transposed else w3.shape
+    stem = stem and pieces == 2 and cin in (3, 6) and cout == 32 and K <= 128
+    if not stem and not _piece_path(cin, cout, flavour):
+        return None, None, 3, 1.0, False
+    folded = stem or second is not None
+    fold = col_scale if folded else None
+    k = None
+    if pieces == 2 and step is not None and fold is None and second is None:
+        pre = step.packed.get((w3.data_ptr(), int(transposed))) if (step.packed and not cache and not stem) else None
+        if pre is not None and pre[0].numel() == 2 * w3.numel():
+            TRAIN_COUNTERS["prepacked"] += 1              # packed at the start of the step (_ModuleState.prepack)
+            return pre[0], None, 2, 2.0 ** -pre[1], folded
+        k = step.scales.get(weight.data_ptr())
+    table = _cached_packings(weight) if (cache and fold is None and second is None and not transposed) else None
+    hit = table.get((pieces, stem)) if table is not None else None
+    wp2 = None
+    if hit is None:
+        sets = [(w3, fold)] + ([second] if second is not None else [])
+        if pieces != 2:
+            k = 0
+        elif k is None:
+            k = h2_scale_log2(*sets)                     # (one host wait: a training step hands the scales over instead)
+        hit = (pack_weights(w3, pieces, fold, k, transposed, stem), k)
+        if second is not None:
+            wp2 = pack_weights(second[0], pieces, second[1], k)
+        if table is not None:
+            table[(pieces, stem)] = hit
+    return hit[0], wp2, pieces, (2.0 ** -hit[1] if pieces == 2 else 1.0), folded
 
 
 def conv_forward_masked(x_feats, weight, nbr, perms, n_out, **epilogue):
@@ -868,71 +838,48 @@ def _gradient_untouched_until_end(kernel):
             and not torch.is_grad_enabled() and not torch.is_anomaly_enabled())
 
 
-TRAIN_FWD_PIECES = int(os.environ.get("CV_TRAIN_FWD_PIECES", "3"))      # 3 (default): bf16 triples; 2: fp16 pairs in the training forward (measured: no gain, profiles/r4/train_ab.txt)
 # 1 (default): the training forward's convolutions run on the eval path's hl-format kernels (conv_hl / conv_hd: fp16 pairs, operands
 # split once by the producing BatchNorm pass instead of once per gather) wherever the input has an hl twin; the range flag guards
-# it like TRAIN_FWD_PIECES = 2 (train.train_step redoes the step on the bf16 triples).  0: conv_rows_wp on the fp32 rows.
+# it (train.train_step redoes the step on the bf16 triples).  0: conv_rows_wp on the fp32 rows.
 TRAIN_FWD_HL = int(os.environ.get("CV_TRAIN_FWD_HL", "1"))
-_train_state = threading.local()
-
-
-def train_forward_hl():
-    return TRAIN_FWD_HL != 0 and COMPUTE_DTYPE != "bf16"
-
-
 # 1 (default): the input gradients run on the hl-format kernels too.  The BatchNorm backward writes dx a second time as fp16 pairs
 # times a per-layer power of two taken from the PREVIOUS step's largest |dx| of that layer (three words per layer that live on
-# the device: cv_sp_bn_backward_hl_f32) - inside train.train_step only (ME.pair_scale_hints rotates the maxima between steps);
+# the device: cv_sp_bn_backward_hl_f32) - inside train.train_step only (pair_scale_hints rotates the maxima between steps);
 # a layer's first step, and every backward outside a step, takes the bf16 triples.
 TRAIN_BWD_HL = int(os.environ.get("CV_TRAIN_BWD_HL", "1"))
-
-
 # 1 (default): train.train_step packs the fp16-pair weights of all convolutions (both directions) by one launch per step
 TRAIN_PREPACK = int(os.environ.get("CV_TRAIN_PREPACK", "1"))
 TRAIN_COUNTERS = {"hl_dgrad": 0, "prepacked": 0}           # (tests: how many input gradients took the hl path)
-# what the backward nodes of the step in progress share.  Process-wide, not thread-local: the autograd engine runs the nodes on
-# its own thread.  One training step at a time per process (the one-process-per-GPU layout of train_joint.py).
-_bwd_ctx = {"slots": None, "twins": {}, "pair_scales": None, "packed": None}
+# of the calling thread: .step, the training step in progress (pair_scale_hints); .triples, inside on_bf16_triples()
+_train_state = threading.local()
 
 
-def _prepack_pairs(module, ks, scales, dev):
-    """fp16-pair weights of every convolution of a training step - forward layout and, for the input gradients, transposed -
-    packed by ONE launch in front of the step's forward (cv_sp_pack_weights_h2_batch_f32) into an arena that lives with the
-    module: {(kernel.data_ptr(), transposed): (packed words, scale_log2)} for conv_forward.  Per layer and direction this
-    was a launch of its own (117 per MinkUNet34C step) with the stream idle in front of most of them."""
-    L = _lib.lib()
-    sig = tuple((k.data_ptr(), tuple(k.shape), k.is_contiguous()) for k in ks) + (bool(TRAIN_BWD_HL),)
-    st = module.__dict__.get("_prepack_state")
-    if st is None or st["sig"] != sig or st["arena"].device != dev:
-        meta, off = [], 0
-        for k in ks:
-            if not k.is_contiguous():
-                continue
-            K, cin, cout = (k.shape if k.dim() == 3 else (1,) + tuple(k.shape))
-            words = 2 * K * cin * cout
-            if cin % 32 == 0 and cout % 4 == 0:
-                meta.append((k.data_ptr(), 0, K, cin, cout, off, words))
-                off += (words + 63) // 64 * 64
-            if TRAIN_BWD_HL and cout % 32 == 0 and cin % 4 == 0:      # the transposed convolution: Cin' = cout, Cout' = cin
-                meta.append((k.data_ptr(), 1, K, cout, cin, off, words))
-                off += (words + 63) // 64 * 64
-        arena = torch.empty(max(off, 64), dtype=torch.int16, device=dev)
-        jobs = (_lib.PackJob * max(len(meta), 1))()
-        for j, (ptr, trans, K, cin, cout, o, words) in zip(jobs, meta):
-            j.w, j.wp, j.K, j.cin, j.cout, j.trans = ptr, arena.data_ptr() + 2 * o, K, cin, cout, trans
-        st = module.__dict__["_prepack_state"] = {
-            "sig": sig, "meta": meta, "arena": arena, "jobs": jobs,
-            "d_jobs": torch.empty(max(len(meta), 1) * ctypes.sizeof(_lib.PackJob), dtype=torch.uint8, device=dev)}
-    meta, arena, jobs = st["meta"], st["arena"], st["jobs"]
-    packed = {}
-    for j, (ptr, trans, K, cin, cout, o, words) in zip(jobs, meta):
-        j.scale_log2 = int(scales.get(ptr, 0))
-        packed[(ptr, trans)] = (arena[o:o + words], j.scale_log2)
-    if meta:
-        with _on(dev):
-            _lib.check(L.cv_sp_pack_weights_h2_batch_f32(jobs, len(meta), ctypes.c_void_p(st["d_jobs"].data_ptr()), _stream(dev)),
-                       "cv_sp_pack_weights_h2_batch_f32")
-    return packed
+def current_step():
+    """the training step the calling thread is in (a pair_scale_hints), or None"""
+    return getattr(_train_state, "step", None)
+
+
+class on_bf16_triples:
+    """`with on_bf16_triples():` the calling thread's training forwards stay off the fp16 pairs (train.train_step redoes a step
+    that left the fp16 range this way)"""
+
+    def __enter__(self):
+        self.outer = getattr(_train_state, "triples", False)
+        _train_state.triples = True
+        return self
+
+    def __exit__(self, *exc):
+        _train_state.triples = self.outer
+        return False
+
+
+def train_forward_hl():
+    return TRAIN_FWD_HL != 0 and COMPUTE_DTYPE != "bf16" and not getattr(_train_state, "triples", False)
+
+
+def train_uses_pairs():
+    """the training forward multiplies fp16 pairs somewhere (range flag to check, weight scales to hand over)"""
+    return train_forward_hl()
 
 
 class _GradSlots:
@@ -961,103 +908,149 @@ class _GradSlots:
         return self.buf[i], key in self.seen
 
 
-def train_uses_pairs():
-    """the training forward multiplies fp16 pairs somewhere (range flag to check, weight scales to hand over)"""
-    return COMPUTE_DTYPE != "bf16" and (TRAIN_FWD_PIECES == 2 or TRAIN_FWD_HL != 0)
+class _ModuleState:
+    """What a module tree keeps from one training step to the next, for the convolution kernels `ks` it had when this was
+    built (pair_scale_hints builds another when `sig` no longer matches): the weight maxima on their way to the host, the
+    arena of the pre-packed weights, the gradient slots."""
+
+    def __init__(self, sig, ks, dev):
+        self.sig, self.dev = sig, dev
+        self.host = torch.empty(len(ks), dtype=torch.float32).pin_memory()
+        self.request(ks)
+        self.slots = None
+        self.meta = None
+
+    @staticmethod
+    def signature(ks):
+        return tuple((k.data_ptr(), tuple(k.shape), k.is_contiguous()) for k in ks) + (str(ks[0].device), bool(TRAIN_BWD_HL))
+
+    def request(self, ks):
+        """the max-norms of the weights as they are now (ONE multi-tensor launch) travel to pinned memory"""
+        with torch.no_grad():
+            self.host.copy_(torch.stack(torch._foreach_norm([k.detach() for k in ks], float("inf"))), non_blocking=True)
+        self.event = torch.cuda.Event()
+        self.event.record(torch.cuda.current_stream(self.dev))
+
+    def scales(self, ks):
+        """{kernel.data_ptr(): scale_log2} from the maxima requested a step ago; requests the next step's"""
+        self.event.synchronize()                 # (already passed in the steady state: it was recorded a step ago)
+        amax = self.host.tolist()
+        self.request(ks)
+        return {k.data_ptr(): (max(-60, min(60, 13 - math.ceil(math.log2(a)))) if (math.isfinite(a) and a > 0) else 0)
+                for k, a in zip(ks, amax)}
+
+    def grad_slots(self):
+        if self.slots is None:
+            self.slots = _GradSlots(self.dev)
+        self.slots.rotate()
+        return self.slots
+
+    def prepack(self, ks, scales):
+        """fp16-pair weights of every convolution of a training step - forward layout and, for the input gradients, transposed
+        - packed by ONE launch in front of the step's forward (cv_sp_pack_weights_h2_batch_f32) into an arena that lives with
+        the module: {(kernel.data_ptr(), transposed): (packed words, scale_log2)} for resolve_weights.  Per layer and direction
+        this was a launch of its own (117 per MinkUNet34C step) with the stream idle in front of most of them."""
+        if self.meta is None:
+            meta, off = [], 0
+            for k in ks:
+                if not k.is_contiguous():
+                    continue
+                K, cin, cout = (k.shape if k.dim() == 3 else (1,) + tuple(k.shape))
+                words = 2 * K * cin * cout
+                if cin % 32 == 0 and cout % 4 == 0:
+                    meta.append((k.data_ptr(), 0, K, cin, cout, off, words))
+                    off += (words + 63) // 64 * 64
+                if TRAIN_BWD_HL and cout % 32 == 0 and cin % 4 == 0:      # the transposed convolution: Cin' = cout, Cout' = cin
+                    meta.append((k.data_ptr(), 1, K, cout, cin, off, words))
+                    off += (words + 63) // 64 * 64
+            self.arena = torch.empty(max(off, 64), dtype=torch.int16, device=self.dev)
+            self.jobs = (_lib.PackJob * max(len(meta), 1))()
+            for j, (ptr, trans, K, cin, cout, o, words) in zip(self.jobs, meta):
+                j.w, j.wp, j.K, j.cin, j.cout, j.trans = ptr, self.arena.data_ptr() + 2 * o, K, cin, cout, trans
+            self.d_jobs = torch.empty(max(len(meta), 1) * ctypes.sizeof(_lib.PackJob), dtype=torch.uint8, device=self.dev)
+            self.meta = meta
+        packed = {}
+        for j, (ptr, trans, K, cin, cout, o, words) in zip(self.jobs, self.meta):
+            j.scale_log2 = int(scales.get(ptr, 0))
+            packed[(ptr, trans)] = (self.arena[o:o + words], j.scale_log2)
+        if self.meta:
+            with _on(self.dev):
+                _lib.check(_lib.lib().cv_sp_pack_weights_h2_batch_f32(self.jobs, len(self.meta), _ptr(self.d_jobs),
+                                                                      _stream(self.dev)), "cv_sp_pack_weights_h2_batch_f32")
+        return packed
 
 
 class pair_scale_hints:
-    """power-of-two weight scales of the fp16-pair products for every convolution of `module`, valid inside the `with` block (a
-    training step: the weights do not move between its forward and its optimizer step).  Without it every fp16-pair convolution
-    whose packed weights are not cached reads its own maximum back (63 host waits per MinkUNet34C forward).
-    No host wait in the steady state: the max-norms (ONE multi-tensor launch) travel to pinned memory behind the step that
-    computed them and the NEXT step reads them - an optimizer step moves a weight maximum by a fraction of a percent and the scale
-    leaves a factor of 8 to the fp16 range.  The first step of a module (or a changed parameter list) waits once."""
+    """`with pair_scale_hints(module):` ONE TRAINING STEP of `module` on the calling thread (the weights do not move between its
+    forward and its optimizer step).  The object is what the step's autograd nodes share; _ConvFn and _BNTrainFn find it
+    through the calling thread in their forward and keep it on their ctx, for the backward on the autograd engine's thread:
+        scales      {kernel.data_ptr(): power of two of the fp16-pair products}.  Without it every fp16-pair convolution reads
+                    its own maximum back (63 host waits per MinkUNet34C forward).  No host wait in the steady state: the
+                    max-norms travel to pinned memory behind the step that computed them and the NEXT step reads them - an
+                    optimizer step moves a weight maximum by a fraction of a percent and the scale leaves a factor of 8 to
+                    the fp16 range.  The first step of a module (or a changed parameter list) waits once.
+        packed      the pre-packed weights of the step (TRAIN_PREPACK; _ModuleState.prepack), or None
+        slots       the gradient slots (TRAIN_BWD_HL; _GradSlots), or None
+        twins       {dx.data_ptr(): (hl twin, 1 / factor on the device, shape, dx)} from a BatchNorm backward to the input
+                    gradient of the convolution below it
+        used_pairs  a forward of the step multiplied fp16 pairs: there is a range flag to read
+    A node built outside a step has none: bf16 triples for its input gradient, its own scale readback for a pair forward.
+    When the block is left the step is closed: a backward that runs later finds it empty."""
 
     def __init__(self, module):
         self.module = module
+        self.scales, self.packed, self.slots, self.twins, self.used_pairs = {}, None, None, {}, False
 
     def __enter__(self):
-        self.outer = getattr(_train_state, "pair_scales", None)
+        self.outer = current_step()
         ks = [m.kernel for m in self.module.modules() if isinstance(m, MinkowskiConvolutionBase) and m.kernel.is_cuda]
-        scales = {}
-        if ks and train_uses_pairs():
-            ptrs = tuple(k.data_ptr() for k in ks)
-            dev = ks[0].device
-            st = self.module.__dict__.get("_pair_scale_state")
-            if st is None or st["ptrs"] != ptrs:
-                st = self.module.__dict__["_pair_scale_state"] = {
-                    "ptrs": ptrs, "host": torch.empty(len(ks), dtype=torch.float32).pin_memory(), "event": None}
-                self._request(st, ks, dev)
-            st["event"].synchronize()                # (already passed in the steady state: it was recorded a step ago)
-            amax = st["host"].tolist()
-            self._request(st, ks, dev)               # for the next step
-            for k, a in zip(ks, amax):
-                scales[k.data_ptr()] = (max(-60, min(60, 13 - math.ceil(math.log2(a)))) if (math.isfinite(a) and a > 0) else 0)
-        _train_state.pair_scales = scales
-        self.outer_slots = _bwd_ctx["slots"]
-        _bwd_ctx["slots"], _bwd_ctx["twins"] = None, {}
-        self.outer_packed = _bwd_ctx["packed"]
-        _bwd_ctx["packed"] = _prepack_pairs(self.module, ks, scales, ks[0].device) if (ks and train_forward_hl() and TRAIN_PREPACK) else None
-        if ks and train_forward_hl() and TRAIN_BWD_HL:
-            slots = self.module.__dict__.get("_grad_slots")
-            if slots is None or slots.buf.device != ks[0].device:
-                slots = self.module.__dict__["_grad_slots"] = _GradSlots(ks[0].device)
-            slots.rotate()
-            _bwd_ctx["slots"] = slots
-            _bwd_ctx["pair_scales"] = scales
+        if ks and train_forward_hl():
+            sig = _ModuleState.signature(ks)
+            st = self.module.__dict__.get("_cv_train_state")
+            if st is None or st.sig != sig:
+                st = self.module.__dict__["_cv_train_state"] = _ModuleState(sig, ks, ks[0].device)
+            self.scales = st.scales(ks)
+            if TRAIN_PREPACK:
+                self.packed = st.prepack(ks, self.scales)
+            if TRAIN_BWD_HL:
+                self.slots = st.grad_slots()
+        _train_state.step = self
         return self
 
-    @staticmethod
-    def _request(st, ks, dev):
-        with torch.no_grad():
-            amax = torch.stack(torch._foreach_norm([k.detach() for k in ks], float("inf")))
-            st["host"].copy_(amax, non_blocking=True)
-        st["event"] = torch.cuda.Event()
-        st["event"].record(torch.cuda.current_stream(dev))
-
     def __exit__(self, *exc):
-        _train_state.pair_scales = self.outer
-        _bwd_ctx["slots"], _bwd_ctx["twins"], _bwd_ctx["pair_scales"] = self.outer_slots, {}, None
-        _bwd_ctx["packed"] = self.outer_packed
+        _train_state.step = self.outer
+        self.scales, self.packed, self.slots, self.twins = {}, None, None, {}
         return False
 
+    def range_flag_device(self, dev):
+        """the range flag of this thread's stream as a float32 device scalar (1.0 = a training forward since the last reset left
+        the fp16 range), read in stream order behind the kernels that may raise it: hand it to a fused optimizer as `found_inf`
+        and the update is skipped on the device without a host wait (train.train_step).  None when no forward of the step used
+        the fp16 pairs."""
+        if not self.used_pairs:
+            return None
+        return range_flag(dev).to(dev, non_blocking=True).to(torch.float32).reshape(())
 
-def training_range_flag_device(dev):
-    """the range flag of this thread's stream as a float32 device scalar (1.0 = a training forward since the last reset left the
-    fp16 range), read in stream order behind the kernels that may raise it: hand it to a fused optimizer as `found_inf` and the
-    update is skipped on the device without a host wait (train.train_step).  None when no forward used the fp16 pairs."""
-    if not getattr(_train_state, "used_pairs", False):
-        return None
-    return range_flag(dev).to(dev, non_blocking=True).to(torch.float32).reshape(())
-
-
-def training_range_flag_peek(dev):
-    """the flag's current value without waiting for anything (kernels still in flight may raise it later)"""
-    return int(range_flag(dev)[0]) != 0
-
-
-def training_forward_left_fp16_range(dev, group=None):
-    """True when a convolution of this thread's training forwards since the last call staged an input beyond the fp16
-    range on the current stream (synchronises the stream; the flag is reset).  False without a wait when no forward used
-    the fp16 pairs.  group: a process group whose ranks step together (DDP) - the answer is then the MAXIMUM over the ranks
-    (what GradScaler does with found_inf): every rank redoes the step, or none does."""
-    used = getattr(_train_state, "used_pairs", False)
-    if not used and group is None:
-        return False
-    _train_state.used_pairs = False
-    torch.cuda.current_stream(dev).synchronize()
-    flag = range_flag(dev)
-    raised = int(flag[0]) != 0
-    if group is not None:
-        import torch.distributed as dist
-        t = torch.tensor([1.0 if raised else 0.0], device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
-        raised = float(t[0]) != 0.0
-    if not raised:
-        return False
-    flag.zero_()
-    return True
+    def left_fp16_range(self, dev, group=None):
+        """True when a convolution of this step's forward staged an input beyond the fp16 range on the current stream
+        (synchronises the stream; the flag is reset).  False without a wait when no forward used the fp16 pairs.  group: a
+        process group whose ranks step together (DDP) - the answer is then the MAXIMUM over the ranks (what GradScaler does
+        with found_inf): every rank redoes the step, or none does."""
+        if not self.used_pairs and group is None:
+            return False
+        self.used_pairs = False
+        torch.cuda.current_stream(dev).synchronize()
+        flag = range_flag(dev)
+        raised = int(flag[0]) != 0
+        if group is not None:
+            import torch.distributed as dist
+            t = torch.tensor([1.0 if raised else 0.0], device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+            raised = float(t[0]) != 0.0
+        if not raised:
+            return False
+        flag.zero_()
+        return True
 
 
 def copy_unless_flag(srcs, dsts, dev, flag=None):
@@ -1086,23 +1079,22 @@ class _ConvFn(torch.autograd.Function):
         ctx.has_nbr = nbr is not None
         ctx.has_bias = bias is not None
         shift = bias.reshape(-1).contiguous() if bias is not None else None
+        step = ctx.step = current_step()
         # fp32-level products of the training FORWARD: fp16 pairs (three piece products) while the activations are inside
         # the fp16 range - they sit behind BatchNorm - with the range flag as the guard (train.train_step reads it once per
-        # step and redoes the step on the bf16 triples); the input gradient keeps the triples (gradients have no bound)
+        # step and redoes the step on the bf16 triples)
         if feats_hl is not None and train_forward_hl() and feats.shape[1] % 32 == 0 and feats_hl.stride(0) % 32 == 0:
             # the eval path's kernels on the hl twin (the fp32 rows stay saved for the weight gradient)
-            _train_state.used_pairs = True
-            return conv_forward(feats_hl, kernel, nbr, n_out, shift=shift, cache_weights=False, pieces=2, in_hl=True)
+            if step is not None:
+                step.used_pairs = True
+            return conv_forward(feats_hl, kernel, nbr, n_out, shift=shift, cache_weights=False, pieces=2, in_hl=True, step=step)
         k3 = kernel if kernel.dim() == 3 else kernel[None]
         if (train_forward_hl() and nbr is not None and feats.shape[1] in (3, 6) and k3.shape[2] == 32 and k3.shape[0] <= 128):
             # the stem (conv0p1s1: 5x5x5, 3 or 6 -> 32 channels) on the matrix cores, like the eval program's (conv_stem_mfma)
-            _train_state.used_pairs = True
-            return conv_forward(feats, kernel, nbr, n_out, shift=shift, cache_weights=False, pieces=2, stem_mfma=True)
-        pieces = None
-        if TRAIN_FWD_PIECES == 2 and COMPUTE_DTYPE != "bf16" and feats.shape[1] % 32 == 0:
-            pieces = 2
-            _train_state.used_pairs = True
-        return conv_forward(feats, kernel, nbr, n_out, shift=shift, cache_weights=False, pieces=pieces)
+            if step is not None:
+                step.used_pairs = True
+            return conv_forward(feats, kernel, nbr, n_out, shift=shift, cache_weights=False, pieces=2, stem_mfma=True, step=step)
+        return conv_forward(feats, kernel, nbr, n_out, shift=shift, cache_weights=False, step=step)
 
     @staticmethod
     def backward(ctx, grad):
@@ -1136,18 +1128,18 @@ class _ConvFn(torch.autograd.Function):
                 _join_at_end_of_backward(cur, side)
                 if LATE_GRAD_LOG is not None:
                     LATE_GRAD_LOG.append((kernel, d_kernel.data_ptr()))
-        twins = _bwd_ctx["twins"]
-        twin = twins.pop(grad.data_ptr(), None) if twins else None          # (taken out whether or not it is used)
+        step = ctx.step
+        twin = step.twins.pop(grad.data_ptr(), None) if step is not None else None     # (taken out whether or not it is used)
         if ctx.needs_input_grad[0]:
             nbr_t = transposed_map(nbr, feats.shape[0]) if nbr is not None else None
             if (twin is not None and twin[2] == grad.shape and COMPUTE_DTYPE != "bf16" and k3.shape[2] % 32 == 0
                     and k3.shape[1] % 4 == 0):
                 # the eval path's kernels on the gradient's hl twin (written by the BatchNorm backward above this layer)
                 d_feats = conv_forward(twin[0], k3.detach(), nbr_t, feats.shape[0], cache_weights=False, weight_t=True,
-                                       pieces=2, in_hl=True, acc_scale_dev=twin[1])
+                                       pieces=2, in_hl=True, acc_scale_dev=twin[1], step=step)
                 TRAIN_COUNTERS["hl_dgrad"] += 1
             else:
-                d_feats = conv_forward(grad, k3.detach(), nbr_t, feats.shape[0], cache_weights=False, weight_t=True)
+                d_feats = conv_forward(grad, k3.detach(), nbr_t, feats.shape[0], cache_weights=False, weight_t=True, step=step)
         if side is not None:
             if not late:
                 cur.wait_stream(side)
@@ -1280,9 +1272,11 @@ class _BNTrainFn(torch.autograd.Function):
         ctx.eps = float(eps)
         ctx.has_res = residual is not None
         ctx.two = want_hl
+        ctx.step = current_step()
         ctx.set_materialize_grads(False)         # (no zero tensor for the twin's "gradient": it was a fill of N x C per layer)
         if want_hl:
-            _train_state.used_pairs = True
+            if ctx.step is not None:
+                ctx.step.used_pairs = True
             ctx.mark_non_differentiable(y_hl)
             return y, y_hl
         return y
@@ -1302,7 +1296,8 @@ class _BNTrainFn(torch.autograd.Function):
         ws = torch.empty(int(L.cv_sp_bn_workspace_bytes(c)), dtype=torch.uint8, device=dev)
         bits = y if ctx.bits else None
         y_rows = None if ctx.bits else y
-        slots = _bwd_ctx["slots"]
+        step = ctx.step
+        slots = step.slots if step is not None else None
         slot, usable, dx_hl = None, False, None
         if slots is not None and c % 32 == 0 and x.stride(0) % 32 == 0 and x.stride(0) == dx.stride(0):
             slot, usable = slots.take(gamma.data_ptr())
@@ -1327,7 +1322,7 @@ class _BNTrainFn(torch.autograd.Function):
             # (the entry holds dx itself: while it is in the table the allocator cannot hand dx's address to another gradient
             # tensor, so a twin whose consumer is not a _ConvFn - it then stays until the step's table is dropped - can never be
             # taken for a later tensor at the same address: ADVICE r5)
-            _bwd_ctx["twins"][dx.data_ptr()] = (dx_hl, slot[8192:8193].view(torch.float32), dx.shape, dx)
+            step.twins[dx.data_ptr()] = (dx_hl, slot[8192:8193].view(torch.float32), dx.shape, dx)
         return dx, dg[0], dg[1], None, None, None, None, dres, None, None
 
 

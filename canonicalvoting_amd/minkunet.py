@@ -11,11 +11,13 @@ Two forwards with identical results:
     its epilogue, skip connections are written straight into the concat buffers
     (no ``cat`` copy): 63 launches for the whole network.
 """
+import ctypes
 import os
 
 import torch
 import torch.nn as nn
 
+from . import _lib
 from . import me as ME
 from .me.modules.resnet_block import BasicBlock
 
@@ -169,10 +171,8 @@ class MinkUNetBase(ResNetBase):
             return v
         return self.MASKED_MIN_ROWS if self.MASKED_MIN_ROWS is not None else ME.CoordinateManager.MASKED_MIN_ROWS
     MASK_GROUPS = ME.CoordinateManager.MASK_GROUPS
-    # eval forward through the C executor (cv_net_run_f32, one call per scene: host time 1.46 -> 0.72 ms).  Off by
-    # default: the GPU, not the host, bounds the scene rate today, and the executor's per-scene arena (257 MB at
-    # 80k points, no aliasing across levels) costs more Infinity-Cache misses with several scenes in flight than
-    # the caching allocator's recycled temporaries (227 vs 244 scenes/s at 3 scenes in flight).
+    # eval forward through the C executor (cv_net_run_f32, one call per scene: host time 1.46 -> 0.72 ms).  On by
+    # default; CV_NET_PROGRAM=0 takes fused_forward, the same launches one Python call each.
     USE_PROGRAM = os.environ.get("CV_NET_PROGRAM", "1") != "0"
     # program mode: the 1x1 downsample conv of a block's first BasicBlock is folded into its conv2 (second source)
     FUSE_DOWNSAMPLE = os.environ.get("CV_FUSE_DOWNSAMPLE", "1") != "0"
@@ -252,7 +252,6 @@ class MinkUNetBase(ResNetBase):
     def _program(self, dev, pieces=3):
         """(ops, bufs, keep-alive) for cv_net_run_f32: the launch sequence of fused_forward with symbolic operands
         (arena buffer slots, map / order slots).  Built once per parameter version and piece format."""
-        from . import _lib
         # cheap staleness check (walking nn.Module.parameters() costs 0.3 ms per call): the flat tensor list is
         # kept with the program, in-place updates bump _version, re-allocation (.to(), load_state_dict with
         # assign) changes data_ptr of the first parameter or the tensor objects themselves
@@ -287,38 +286,16 @@ class MinkUNetBase(ResNetBase):
             """second = (src2, kernel2 [cin2, cout], scale2): out += scale2 * (src2 @ kernel2) on the output rows; the
             BatchNorm scales are then folded into both packed weight sets and only `shift` remains in the epilogue"""
             w = (kernel if kernel.dim() == 3 else kernel[None]).detach().contiguous()
-            in2 = (-1, 0)
-            cin2, w6_2 = 0, None
-            vec = ME.CONV_X6 and w.shape[1] % 32 == 0 and w.shape[2] % 4 == 0
-            op_pieces, acc_scale = 3, 1.0
+            in2, cin2 = (-1, 0), 0
             if second is not None:
-                src2, kernel2, scale2 = second
+                in2, kernel2, scale2 = second
                 w2 = (kernel2 if kernel2.dim() == 3 else kernel2[None]).detach().contiguous()
-                if pieces == 1:
-                    w6, w6_2 = ME.packed_weights_bf16(w, scale), ME.packed_weights_bf16(w2, scale2)
-                    op_pieces = 1
-                elif pieces == 2:
-                    k = ME.h2_scale_log2((w, scale), (w2, scale2))           # one accumulator: one common factor
-                    w6, w6_2 = ME.packed_weights_h2(w, scale, k), ME.packed_weights_h2(w2, scale2, k)
-                    op_pieces, acc_scale = 2, 2.0 ** -k
-                else:
-                    w6 = ME.packed_weights_x6_scaled(w, scale)
-                    w6_2 = ME.packed_weights_x6_scaled(w2, scale2)
-                in2, cin2, scale = src2, w2.shape[1], None
-            elif (pieces == 2 and hl and not vec and self.STEM_MFMA and w.shape[2] == 32 and w.shape[1] in (3, 6)
-                  and w.shape[0] <= 128):
-                # stem on the matrix cores: BatchNorm scale folded into the fp16-pair weights
-                k = ME.h2_scale_log2((w, scale))
-                w6 = ME.packed_weights_stem_h2(w, scale, k)
-                op_pieces, acc_scale, scale = 2, 2.0 ** -k, None
-            elif vec and pieces == 1:
-                w6, op_pieces = ME.packed_weights_bf16(w), 1
-            elif vec and pieces == 2:
-                k = ME.h2_scale_log2((w, None))
-                w6 = ME.packed_weights_h2(w, None, k)
-                op_pieces, acc_scale = 2, 2.0 ** -k
-            else:
-                w6 = ME.packed_weights_x6(kernel, w) if vec else None
+                cin2, second = w2.shape[1], (w2, scale2)
+            # (the stem on the matrix cores only between hl buffers; its BatchNorm scale is folded into the fp16-pair weights)
+            w6, w6_2, op_pieces, acc_scale, folded = ME.resolve_weights(kernel, w, pieces, stem=bool(hl) and self.STEM_MFMA,
+                                                                        col_scale=scale, second=second, cache=True)
+            if folded:
+                scale = None
             keep.extend([w, scale, shift, w6, w6_2])
             ops.append(dict(in_buf=src[0], in_col=src[1], cin=w.shape[1], out_buf=dst[0], out_col=dst[1],
                             cout=w.shape[2], res_buf=res[0] if res else -1, res_col=res[1] if res else 0,
@@ -413,8 +390,6 @@ class MinkUNetBase(ResNetBase):
 
     def program_forward(self, x, pieces=None, defer_check=None):
         """fused_forward through the C executor (cv_net_run_f32): identical launches, one call."""
-        import ctypes
-        from . import _lib
         L = _lib.lib()
         dev = x.F.device
         if pieces is None:

@@ -148,14 +148,28 @@ class _FlagRing:
         return found
 
 
+class _StepState:
+    """what train_step keeps with a model between its calls: the lagged range flags, the BatchNorm snapshot buffers, and
+    whether a flagged step has sent the model to the bf16 triples for good"""
+    ring, snapshot, pairs_off = None, None, False
+
+
+def _step_state(model):
+    st = model.__dict__.get("_cv_step_state")
+    if st is None:
+        st = model.__dict__["_cv_step_state"] = _StepState()
+    return st
+
+
 def _bn_state(model):
     """(the BatchNorm running statistics and counters of `model`, a snapshot buffer for each that lives with the model)"""
     bufs = [b for m in model.modules() for b in (getattr(m, "running_mean", None), getattr(m, "running_var", None),
                                                  getattr(m, "num_batches_tracked", None)) if b is not None]
-    saved = model.__dict__.get("_bn_snapshot")
+    st = _step_state(model)
+    saved = st.snapshot
     if saved is None or len(saved) != len(bufs) or any(a.shape != b.shape or a.device != b.device or a.dtype != b.dtype
                                                        for a, b in zip(saved, bufs)):
-        saved = model.__dict__["_bn_snapshot"] = [torch.empty_like(b) for b in bufs]
+        saved = st.snapshot = [torch.empty_like(b) for b in bufs]
     return bufs, saved
 
 
@@ -184,24 +198,20 @@ def train_step(model, optimizer, coords4, feats, xyz_labels, scale_labels, class
         return loss, parts
 
     def on_triples(fn):
-        prev, ME.TRAIN_FWD_PIECES = ME.TRAIN_FWD_PIECES, 3
-        prev_hl, ME.TRAIN_FWD_HL = ME.TRAIN_FWD_HL, 0
-        try:
+        with ME.on_bf16_triples():
             return fn()
-        finally:
-            ME.TRAIN_FWD_PIECES = prev
-            ME.TRAIN_FWD_HL = prev_hl
 
-    if not ME.train_uses_pairs() or model.__dict__.get("_pairs_off", False):
-        loss, parts = on_triples(fwd_bwd) if ME.train_uses_pairs() else fwd_bwd()
+    st = _step_state(model)
+    if not ME.train_uses_pairs() or st.pairs_off:
+        loss, parts = on_triples(fwd_bwd)
         optimizer.step()
         return loss.detach(), {k: v.detach() for k, v in parts.items()}
 
     bufs, saved = _bn_state(model)
     if _skips_on_device(optimizer):
-        ring = model.__dict__.get("_flag_ring")
-        if ring is None or ring.dev != dev:
-            ring = model.__dict__["_flag_ring"] = _FlagRing(dev)
+        if st.ring is None or st.ring.dev != dev:
+            st.ring = _FlagRing(dev)
+        ring = st.ring
         if ring.noticed():
             # the step FLAG_LAG calls ago left the fp16 range (on this rank or, under DDP, on any rank): its update and that
             # of every step queued since was skipped on the device, and the BatchNorm snapshot still holds the statistics and
@@ -211,14 +221,13 @@ def train_step(model, optimizer, coords4, feats, xyz_labels, scale_labels, class
                 torch._foreach_copy_(bufs, saved)
             ME.range_flag(dev).zero_()
             model.train_range_fallbacks = getattr(model, "train_range_fallbacks", 0) + 1
-            model.__dict__["_pairs_off"] = True
-            model.__dict__.pop("_flag_ring", None)
+            st.pairs_off, st.ring = True, None
             return train_step(model, optimizer, coords4, feats, xyz_labels, scale_labels, class_labels, **loss_kw)
         # BatchNorm statistics of before this step, kept ON THE DEVICE only while no step has raised the flag
         ME.copy_unless_flag(bufs, saved, dev, ME.range_flag(dev))
-        with ME.pair_scale_hints(model):
+        with ME.pair_scale_hints(model) as step:
             loss, parts = fwd_bwd()
-        found = ring.push(ME.training_range_flag_device(dev), group)
+        found = ring.push(step.range_flag_device(dev), group)
         if found is not None and group is not None:
             # the local flag follows the group's: every rank's later steps skip too, and every rank's snapshot guard closes
             ME.range_flag(dev).copy_(found.reshape(1).to(torch.int32), non_blocking=True)
@@ -234,9 +243,9 @@ def train_step(model, optimizer, coords4, feats, xyz_labels, scale_labels, class
     # (one multi-tensor copy into buffers that live with the model: 186 one-element clones per step were 186 launches)
     with torch.no_grad():
         torch._foreach_copy_(saved, bufs)
-    with ME.pair_scale_hints(model):
+    with ME.pair_scale_hints(model) as step:
         loss, parts = fwd_bwd()
-    if ME.training_forward_left_fp16_range(dev, group):
+    if step.left_fp16_range(dev, group):
         with torch.no_grad():
             torch._foreach_copy_(bufs, saved)
         loss, parts = on_triples(fwd_bwd)

@@ -13,7 +13,8 @@ opt = train.make_optimizer(model)
 for i in range(5):
     loss, _ = train.train_step(model, opt, *batch)
     torch.cuda.synchronize()
-    sl = model.__dict__.get("_grad_slots")
+    st = model.__dict__.get("_cv_train_state")
+    sl = st.slots if st is not None else None
     cur = sl.buf[:len(sl.index), 0:4096].view(torch.float32).max(1).values if sl is not None else None
     print("step %d loss %.4f flag %d fallbacks %d hl dgrads %d" % (i, float(loss), int(ME.range_flag(dev)[0]), getattr(model, "train_range_fallbacks", 0), ME.TRAIN_COUNTERS["hl_dgrad"]),
           "max|dx| per layer: min %.2e max %.2e" % (float(cur.min()), float(cur.max())) if cur is not None else "")

@@ -22,7 +22,6 @@ print("step %.2f ms" % ((time.perf_counter() - t0) * 100))
 # forward only / backward only host time
 x = None
 def fwd():
-    ME._train_state.used_pairs = False
     with ME.pair_scale_hints(model):
         out = model(ME.SparseTensor(batch[1], batch[0], device=dev))
         return train.joint_loss(out.F, batch[2], batch[3], batch[4])[0]
