@@ -22,6 +22,8 @@ import subprocess
 
 import numpy as np
 
+from .hv_numpy import VOTE_BWD_ERROR_MODEL, vote_bwd_bounds      # noqa: F401  (next to hv_backward below)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "_build", "libcv_oracle.so")
 _lib = None
@@ -191,8 +193,10 @@ def hv_forward_variant(points, xyz, scale, obj, res, num_rots, cs=None, fma_mode
     return g_obj, g_rot, g_scale
 
 
-def hv_backward(grad_grid, points, xyz, scale, obj, res, num_rots):
-    """Oracle of hv_cuda.backward (hv_cuda.cpp:47-71): -> d_xyz, d_scale, d_obj."""
+def hv_backward(grad_grid, points, xyz, scale, obj, res, num_rots, corner=None):
+    """Oracle of hv_cuda.backward (hv_cuda.cpp:47-71): -> d_xyz, d_scale, d_obj.  corner: the grid origin of a vote into
+    a box given by corners (default: the minimum of the points, hv_cuda_kernel.cu:274-276).  The float64 reference with
+    per-element bounds is hv_numpy.hv_backward64 / VOTE_BWD_ERROR_MODEL."""
     L = lib()
     ga, gp = _f(grad_grid)
     pts, pp = _f(points)
@@ -200,7 +204,10 @@ def hv_backward(grad_grid, points, xyz, scale, obj, res, num_rots):
     sa, sp = _f(scale)
     oa, op = _f(obj)
     n = pts.shape[0]
-    mn, mx, _ = grid_geometry(pts, res)
+    if corner is None:
+        mn, _, _ = grid_geometry(pts, res)
+    else:
+        mn = np.ascontiguousarray(corner, np.float32)
     dims = (ctypes.c_int * 3)(*ga.shape)
     d_xyz = np.zeros((n, 3), np.float32)
     d_scale = np.zeros((n, 3), np.float32)

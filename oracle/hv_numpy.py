@@ -112,3 +112,128 @@ def contribution_counts(points, xyz, scale, res, num_rots, corner=None, dims=Non
                 for bz in (0, 1):
                     counts += np.bincount(base + (bx * Y + by) * Z + bz, minlength=X * Y * Z)
     return counts.reshape(X, Y, Z).astype(np.int32)
+
+
+def vote_geometry(points, xyz, scale, res, num_rots, corner, dims):
+    """The in-bounds votes of hv_bwd / hv_fwd (hv_vote.hip) in fp32 with their operation order (the library is built with
+    -ffp-contract=off, so these are the kernel's bits): (pi, ri, fl[3] int64, w0[3] f32, w1[3] f32) - point and rotation of
+    every in-bounds vote, its floor cell and its two trilinear weights per axis, w0 = 1 - fr rounded to fp32."""
+    pts = np.asarray(points, f32)
+    xyz = np.asarray(xyz, f32)
+    scale = np.asarray(scale, f32)
+    res = f32(res)
+    corner = np.asarray(corner, f32)
+    X, Y, Z = dims
+    ct, st = rot_table(num_rots)
+    corr = (xyz * scale).astype(f32)
+    cx, cy, cz = corr[:, 0:1], corr[:, 1:2], corr[:, 2:3]
+    ox = ((-ct)[None] * cx).astype(f32) + (st[None] * cz).astype(f32)
+    oy = np.broadcast_to(-cy, ox.shape)
+    oz = ((-st)[None] * cx).astype(f32) - (ct[None] * cz).astype(f32)
+    g = [(((pts[:, k:k + 1] + o).astype(f32) - corner[k]).astype(f32) / res).astype(f32)
+         for k, o in enumerate((ox, oy, oz))]
+    ok = (g[0] >= 0) & (g[1] >= 0) & (g[2] >= 0) & (g[0] < f32(X - 1)) & (g[1] < f32(Y - 1)) & (g[2] < f32(Z - 1))
+    pi, ri = np.nonzero(ok)
+    gv = [a[pi, ri] for a in g]
+    fl = [np.trunc(a).astype(np.int64) for a in gv]
+    w1 = [(a - np.floor(a)).astype(f32) for a in gv]
+    w0 = [(f32(1) - a).astype(f32) for a in w1]
+    return pi, ri, fl, w0, w1
+
+
+# the eight cells of a vote in the order hv_bwd reads them (lll llh lhl lhh hll hlh hhl hhh): (bx, by, bz)
+CELLS = [(bx, by, bz) for bx in (0, 1) for by in (0, 1) for bz in (0, 1)]
+
+
+def gather_cells(grad, fl):
+    """float64 [8, votes]: grad at the eight cells of every vote, CELLS order"""
+    grad = np.asarray(grad, f32)
+    return np.stack([grad[fl[0] + bx, fl[1] + by, fl[2] + bz] for bx, by, bz in CELLS]).astype(np.float64)
+
+
+def backward_sums(cells, w0, w1, pi, ri, xyz, scale, obj, num_rots):
+    """The sums of hv_bwd over the given votes in float64, and the same sums with every product replaced by its absolute
+    value.  cells [8, votes] float64 (gather_cells), w0 / w1 the fp32 weights, pi / ri the point and rotation of each vote.
+    -> dict(d_xyz [n,3], d_scale [n,3], d_obj [n], m_xyz, m_scale, m_obj, votes [n])"""
+    f64 = np.float64
+    xyz = np.asarray(xyz, f32).astype(f64)
+    scale = np.asarray(scale, f32).astype(f64)
+    obj = np.asarray(obj, f32).astype(f64)
+    n = len(obj)
+    ct, st = (a.astype(f64)[ri] for a in rot_table(num_rots))
+    W = [[a.astype(f64) for a in w0], [a.astype(f64) for a in w1]]
+    dob = np.zeros(len(pi)); mob = np.zeros(len(pi))
+    d = [np.zeros(len(pi)) for _ in range(3)]
+    m = [np.zeros(len(pi)) for _ in range(3)]
+    for g, b in zip(cells, CELLS):
+        t = g * W[b[0]][0] * W[b[1]][1] * W[b[2]][2]
+        dob += t
+        mob += np.abs(t)
+        for k in range(3):                      # d/d(axis k): the other two weights, - for the low cell, + for the high
+            a, c = [j for j in range(3) if j != k]
+            t = g * W[b[a]][a] * W[b[c]][c]
+            d[k] += t if b[k] else -t
+            m[k] += np.abs(t)
+    ob = obj[pi]
+    d = [v * ob for v in d]
+    m = [v * np.abs(ob) for v in m]
+    dc = [-ct * d[0] - st * d[2], -d[1], st * d[0] - ct * d[2]]
+    mc = [np.abs(ct) * m[0] + np.abs(st) * m[2], m[1], np.abs(st) * m[0] + np.abs(ct) * m[2]]
+
+    def per_point(v):
+        return np.bincount(pi, weights=v, minlength=n)
+
+    out = dict(d_obj=per_point(dob), m_obj=per_point(mob), votes=np.bincount(pi, minlength=n).astype(np.int64))
+    for name, other in (("xyz", scale), ("scale", xyz)):
+        out["d_" + name] = np.stack([per_point(dc[k] * other[pi, k]) for k in range(3)], 1)
+        out["m_" + name] = np.stack([per_point(mc[k] * np.abs(other[pi, k])) for k in range(3)], 1)
+    return out
+
+
+def hv_backward64(grad, points, xyz, scale, obj, res, num_rots, corner):
+    """float64 reference of the vote's gradient (hv_bwd of hv_vote.hip, hv_cuda_kernel.cu:183-260).  The geometry - offsets,
+    grid_pos, the bounds test, trunc, fr and w0 = 1 - fr - is fp32 in hv_forward's operation order, which is the kernel's bit
+    for bit; everything after the weights is float64.  grad.shape gives the grid, corner its origin.
+    -> dict(d_xyz, d_scale, d_obj, m_xyz, m_scale, m_obj, votes): per point the sums, their magnitudes (every product
+    replaced by its absolute value) and the number of in-bounds rotations."""
+    grad = np.asarray(grad, f32)
+    pi, ri, fl, w0, w1 = vote_geometry(points, xyz, scale, res, num_rots, corner, grad.shape)
+    return backward_sums(gather_cells(grad, fl), w0, w1, pi, ri, xyz, scale, obj, num_rots)
+
+
+U24 = 2.0 ** -24
+VOTE_BWD_C0 = {"d_obj": 3, "d_xyz": 14, "d_scale": 14}
+VOTE_BWD_K = {"d_obj": 8, "d_xyz": 1, "d_scale": 1}
+VOTE_BWD_ERROR_MODEL = """Error model of hv_bwd (hv_vote.hip), per output element, against hv_backward64.  u = 2^-24.
+
+    bound = (c0 + k * votes) * u * magnitude + 2^-149
+
+votes is the number of in-bounds rotations of the point, magnitude the output's sum with every product replaced by its
+absolute value.  The weights are the kernel's own bits (vote_geometry), so the only error is the rounding of the fp32
+products and additions behind them.  An output is a sum of terms t; the kernel computes sum t * prod (1 + d_j), |d_j| <= u,
+one factor for each rounded operation a term passes through, so |error| <= ((1 + u)^p - 1) * sum |t| with p the longest
+such path - whatever the order of the additions, hence nothing here knows of the lane loop or the butterfly.
+
+  d_obj    term = grad * w * w * w: 3 products.  8 terms per vote, 8 * votes terms in all; summed in any order a term passes
+           through at most 8 * votes - 1 additions (one less than the number of terms).  p <= 3 + 8 * votes - 1.
+           c0 = 3, k = 8.
+  d_xyz    term = grad * w * w * obj * cos|sin * scale.  Longest path, through d_xyz[0] / [2]: 2 products, the 7 additions
+  d_scale  of the eight-term dx / dz, * obj, * cos|sin, the addition of the two halves of dcx / dcz, * scale (or * xyz): 13.
+           Then one such value per vote is summed: at most votes - 1 additions.  p <= 12 + votes; d_xyz[1] has three less.
+           c0 = 14, k = 1 (two roundings of margin over the count).
+
+(1 + u)^p - 1 <= p u / (1 - p u); the spare rounding of d_obj and the two of d_xyz cover the second-order part while
+p^2 u < 1, that is up to 511 in-bounds votes of a point for d_obj (R <= 511) and every R the op takes for the others.
+2^-149 is the one fp32 subnormal a flushed or underflowed term can cost; the C oracle (fp32, sequential) stays below 0.3 of
+the bound on the cases of tests/test_vote_bound.py."""
+
+
+def vote_bwd_bounds(ref):
+    """dict(d_xyz, d_scale, d_obj) of per-element bounds for a result of hv_backward64 (VOTE_BWD_ERROR_MODEL)"""
+    out = {}
+    for name in ("d_xyz", "d_scale", "d_obj"):
+        v = ref["votes"].astype(np.float64)
+        if name != "d_obj":
+            v = v[:, None]
+        out[name] = (VOTE_BWD_C0[name] + VOTE_BWD_K[name] * v) * U24 * ref["m_" + name[2:]] + 2.0 ** -149
+    return out

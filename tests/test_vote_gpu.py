@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import oracle
+from oracle import hv_numpy
 from canonicalvoting_amd import hv_cuda
 from canonicalvoting_amd.hough import HoughVoting
 from canonicalvoting_amd.synth import make_scene, synth_predictions
@@ -69,6 +70,18 @@ def assert_grids_close(hip, ref, tag="", inputs=None, counts=None):
     assert not g_rot[dead].any() and not g_scale[dead].any(), tag
 
 
+def assert_backward_within_bound(got, grad, pts, xyz, scale, prob, res, R, corner, tag):
+    """every element of (d_xyz, d_scale, d_obj) against the float64 oracle under VOTE_BWD_ERROR_MODEL (oracle/hv_numpy.py);
+    points without a vote in bounds have exact zeros"""
+    ref = hv_numpy.hv_backward64(grad, pts, xyz, scale, prob, res, R, corner)
+    bounds = hv_numpy.vote_bwd_bounds(ref)
+    for g, key in zip(got, ("d_xyz", "d_scale", "d_obj")):
+        g = g.detach().cpu().numpy() if torch.is_tensor(g) else np.asarray(g)
+        ratio = np.abs(g.astype(np.float64) - ref[key]) / bounds[key]
+        assert np.isfinite(g).all() and ratio.max() <= 1.0, "%s %s: %.3g x the bound" % (tag, key, float(ratio.max()))
+        assert not g[ref["votes"] == 0].any(), (tag, key)
+
+
 @pytest.mark.parametrize("algo", [1, 2])
 @pytest.mark.parametrize("seed,n,R", [(0, 600, 24), (1, 2048, 120), (2, 777, 60), (3, 64, 7)])
 def test_forward_matches_oracle_small(cuda, built_lib, algo, seed, n, R):
@@ -110,6 +123,7 @@ def test_forward_backward_match_golden(cuda, built_lib, name):
     for got, key in zip(d, ("d_xyz", "d_scale", "d_obj")):
         ref = z[key]
         np.testing.assert_allclose(got.cpu().numpy(), ref, rtol=RTOL, atol=RTOL * max(1.0, np.abs(ref).max()))
+    assert_backward_within_bound(d, z["grad"], pts, z["xyz"], z["scale"], z["prob"], res, R, oracle.grid_geometry(pts, res)[0], name)
 
 
 def test_backward_through_autograd(cuda, built_lib):
@@ -126,6 +140,8 @@ def test_backward_through_autograd(cuda, built_lib):
     r_xyz, r_scale, r_obj = oracle.hv_backward(grad, sc.points, xyz, scale, prob, sc.res, 36)
     for got, ref in ((x.grad, r_xyz), (s.grad, r_scale), (o.grad, r_obj)):
         np.testing.assert_allclose(got.cpu().numpy(), ref, rtol=RTOL, atol=RTOL * max(1.0, np.abs(ref).max()))
+    assert_backward_within_bound((x.grad, s.grad, o.grad), grad, sc.points, xyz, scale, prob, sc.res, 36,
+                                 oracle.grid_geometry(sc.points, sc.res)[0], "autograd")
     # grad_rot / grad_scale are ignored by the reference's backward
     x.grad = None
     g_obj, g_rot, g_scale = hv(p, x, s, o)
@@ -314,6 +330,20 @@ def test_compiled_extension_equals_the_ctypes_module_and_the_goldens(cuda, built
     corners = torch.from_numpy(np.stack([sc.points.min(0) - 0.2, sc.points.max(0) + 0.3]).astype(np.float32)).to(cuda)
     for a, b in zip(hv_cuda.forward(*args, hv.res, hv.num_rots, corners), ext.forward(*args, hv.res, hv.num_rots, corners)):
         assert torch.equal(a, b)
+    # backward with corners=: a box that cuts the cloud (the grid origin is corners[0], the grid grad_grid's); same bits from
+    # both modules, every element under the bound of tests/test_vote_backward_gpu.py
+    ext_lo, ext_hi = sc.points.min(0), sc.points.max(0)
+    span = ext_hi - ext_lo              # (the objects stand on the floor: the box keeps the lower half of the height)
+    cut = np.stack([ext_lo + np.array([0.3, 0.1, 0.3]) * span, ext_hi - np.array([0.25, 0.4, 0.25]) * span]).astype(np.float32)
+    cut_t = torch.from_numpy(cut).to(cuda)
+    g_cut = hv_cuda.forward(*args, hv.res, hv.num_rots, cut_t)[0]
+    gg_cut = torch.randn_like(g_cut)
+    d_ct, d_ext = hv_cuda.backward(gg_cut, *args, hv.res, hv.num_rots, corners=cut_t), ext.backward(gg_cut, *args, hv.res, hv.num_rots,
+                                                                                                   corners=cut_t)
+    for a, b in zip(d_ct, d_ext):
+        assert torch.equal(a, b)
+    assert_backward_within_bound(d_ext, gg_cut.cpu().numpy(), sc.points, xyz, scale, prob, sc.res, 120, cut[0], "ext, cut box")
+    assert 100 < int((d_ext[2] != 0).sum()) < len(sc.points) - 100
     with pytest.raises(RuntimeError, match="xyz_labels must be contiguous"):
         ext.forward(args[0], torch.rand(3, len(sc.points), device=cuda).t(), args[2], args[3], hv.res, hv.num_rots)
     with pytest.raises(RuntimeError, match="res must be a CUDA tensor"):
