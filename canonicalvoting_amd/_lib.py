@@ -155,6 +155,17 @@ class GatherJob(ctypes.Structure):
                 ("width", ctypes.c_int), ("recentre_from", ctypes.c_int)]
 
 
+class ScanRowsDesc(ctypes.Structure):
+    """struct cv_scan_rows_desc (include/cv_hip.h)"""
+    _fields_ = [("d_coords4", vp), ("d_index", vp), ("n", ctypes.c_longlong), ("m_points", ctypes.c_longlong),
+                ("d_points", vp), ("points_ld", ctypes.c_longlong), ("d_rgb", vp), ("d_owner", vp),
+                ("d_minv", vp), ("d_model_scale", vp), ("d_model_cls", vp), ("n_models", ctypes.c_int),
+                ("d_colour", vp), ("d_jitter", vp), ("n_clouds", ctypes.c_int),
+                ("use_xyz", ctypes.c_int), ("recentre", ctypes.c_int),
+                ("d_feats", vp), ("feats_ld", ctypes.c_longlong), ("d_xyz", vp), ("xyz_ld", ctypes.c_longlong),
+                ("d_scale", vp), ("scale_ld", ctypes.c_longlong), ("d_cls", vp), ("cls_ld", ctypes.c_longlong)]
+
+
 class PointsFront(ctypes.Structure):
     """struct cv_points_front (include/cv_hip.h)"""
     _fields_ = [("d_raw_points", vp), ("m", ctypes.c_longlong), ("points_ld", ctypes.c_longlong), ("points_f64", ctypes.c_int),
@@ -235,6 +246,8 @@ SIGNATURES = {
                                           ctypes.c_int, vp, vp, vp, vp, c_i32_p, vp, ctypes.c_size_t, vp]),
     "cv_sp_voxel_rows_f32": (ctypes.c_int, [vp, vp, ctypes.c_longlong, ctypes.c_float, vp, ctypes.POINTER(GatherJob), ctypes.c_int, vp]),
     "cv_sizeof_gather_job": (ctypes.c_size_t, []),
+    "cv_sp_scan_rows_f32": (ctypes.c_int, [ctypes.POINTER(ScanRowsDesc), vp]),
+    "cv_sizeof_scan_rows_desc": (ctypes.c_size_t, []),
     "cv_sp_morton_keys": (ctypes.c_int, [vp, ctypes.c_longlong, vp, vp]),
     "cv_sp_sort_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "cv_sp_sort_rows": (ctypes.c_int, [vp, ctypes.c_longlong, vp, vp, vp, vp, ctypes.c_size_t, vp]),

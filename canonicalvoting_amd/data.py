@@ -7,7 +7,11 @@ train_joint.py:78-90 (batch index in column 0 of the int coordinates).  ``gt_lin
 in the text format eval_joint.py:285-301 reads (``tx ty tz ry sx sy sz ... category``).
 There is no ScanNet/Scan2CAD data in this environment; ``ScanNetXYZProbMultiDataset`` below reads the real file
 formats and is checked against the reference's own class on a miniature dataset (tests/golden/scannet_mini).
+``raw_item`` / ``collate_raw`` / ``device_batch`` are the same training batch with everything behind the two host
+transforms computed on the device.
 """
+import typing
+
 import numpy as np
 import torch
 
@@ -266,6 +270,118 @@ class ScanNetXYZProbMultiDataset(torch.utils.data.Dataset):
                                         return_index=True)[1]
         coords = np.floor(points[keep] / self.cfg.scannet_res).astype(np.float32)
         return id_scan, coords, feats[keep], xyz[keep], scale[keep], cls[keep]
+
+    def raw_item(self, index):
+        """``__getitem__`` up to and including ``points.astype(np.float32)``, as a RawScan: the same file checks, the same
+        redraw and the same draws from numpy's global generator in the same order; everything behind that line - colours,
+        labels, voxelisation, gathers - is left to ``device_batch``, as operands rather than results."""
+        import os
+        ann = self.annotations[index]
+        id_scan = ann["id_scan"]
+        if not np.all(np.abs(np.asarray(ann["trs"]["scale"]) - 1.0) < 1e-7):
+            raise ValueError("%s: scan transform has a non-unit scale" % id_scan)
+        path = os.path.join(self.cfg.data.scannet, "scans", id_scan, id_scan + "_vh_clean_2.ply")
+        if not os.path.exists(path):
+            raise FileNotFoundError(path + " does not exist.")
+        v = read_ply_vertices(path)
+        rgb = np.stack([v["red"], v["green"], v["blue"]], -1).astype(np.uint8, copy=False)
+        to_world = trs_matrix(ann["trs"]["translation"], ann["trs"]["rotation"], ann["trs"]["scale"])
+        points = transform_points(np.stack([v["x"], v["y"], v["z"]], -1), to_world)
+        for model, seg in zip(ann["aligned_models"], self.segments[id_scan]):
+            model["segments"] = seg
+        models = self._select(ann["aligned_models"])
+        if not models:
+            return self.raw_item(np.random.randint(len(self)))
+        aug, colour = np.eye(4), None
+        if self.augment:
+            if self.cfg.augment_color:                                   # the operands of __getitem__'s three in-place lines
+                colour = (1 + 0.4 * np.random.random(3) - 0.2, 0.1 * np.random.random(3) - 0.05,
+                          0.05 * np.random.random(points.shape[0]) - 0.025)
+            angle = np.random.randint(4) * np.pi / 2.0 + (np.random.random() - 0.5) * 2.0 * np.pi / 9.0
+            c, s = np.cos(angle), np.sin(angle)
+            Ry = np.array([[c, 0, -s], [0, 1, 0], [s, 0, c]])
+            points = points @ Ry.T
+            aug[:3, :3] = Ry
+        points = points.astype(np.float32)
+        owner = np.full(points.shape[0], -1, np.int32)
+        minv, scale, cls = [], [], []
+        for m in models:
+            s32 = np.asarray(m["trs"]["scale"], np.float32)
+            if s32.min() < 1e-3:                                         # singular annotation: not in the table
+                continue
+            owner[m["segments"]] = len(cls)                              # in model order: the last model wins a shared vertex
+            minv.append(np.linalg.inv(aug @ bbox_matrix(m))[:3])
+            scale.append(s32 * np.asarray(m["bbox"], np.float32))
+            cls.append(self.class_index(m["catid_cad"]))
+        return RawScan(id_scan, points, rgb, owner, np.asarray(minv, np.float64).reshape(-1, 3, 4),
+                       np.asarray(scale, np.float32).reshape(-1, 3), np.asarray(cls, np.int32), colour)
+
+
+class RawScan(typing.NamedTuple):
+    """One scan as ``ScanNetXYZProbMultiDataset.raw_item`` leaves it: per vertex ``points`` f32 [M, 3] (world frame,
+    augmentation rotation applied), ``rgb`` uint8 [M, 3] and ``owner`` int32 [M] (row of the model table whose labels the
+    vertex gets, -1 = background); the model table ``minv`` f64 [m, 3, 4] (world -> unit cube, top three rows), ``scale``
+    f32 [m, 3], ``cls`` int32 [m] (m may be 0); ``colour`` None or (gain f64 [3], shift f64 [3], jitter f64 [M])."""
+    id_scan: str
+    points: np.ndarray
+    rgb: np.ndarray
+    owner: np.ndarray
+    minv: np.ndarray
+    scale: np.ndarray
+    cls: np.ndarray
+    colour: typing.Optional[tuple]
+
+
+class RawBatch(typing.NamedTuple):
+    """``collate_raw``'s result: the fields of the batch's RawScans one after the other as CPU tensors, ``owner`` counting
+    rows of the concatenated model table, ``offsets`` int64 [B] the first vertex of every cloud, ``colour`` f64 [B, 6]
+    (gain, shift) with ``jitter`` f64 [M], or both None."""
+    id_scans: tuple
+    points: torch.Tensor
+    rgb: torch.Tensor
+    owner: torch.Tensor
+    minv: torch.Tensor
+    scale: torch.Tensor
+    cls: torch.Tensor
+    colour: typing.Optional[torch.Tensor]
+    jitter: typing.Optional[torch.Tensor]
+    offsets: torch.Tensor
+
+
+def collate_raw(batch):
+    """RawScans -> RawBatch (the ``collate_fn`` of the device path; a tuple of tensors, so DataLoader workers and
+    ``pin_memory`` handle it).  A scan without colour operands in a batch that has some gets the identity (gain 1, shift 0,
+    jitter 0), which leaves its colours as they are."""
+    cat = lambda arrays: torch.from_numpy(np.ascontiguousarray(np.concatenate(arrays, 0)))
+    sizes = [s.points.shape[0] for s in batch]
+    first_model = np.cumsum([0] + [s.cls.shape[0] for s in batch[:-1]])
+    owner = [np.where(s.owner >= 0, s.owner + np.int32(f), np.int32(-1)).astype(np.int32) for s, f in zip(batch, first_model)]
+    colour = jitter = None
+    if any(s.colour is not None for s in batch):
+        colour = torch.from_numpy(np.stack([np.concatenate(s.colour[:2]) if s.colour is not None
+                                            else np.array([1.0, 1.0, 1.0, 0.0, 0.0, 0.0]) for s in batch]).astype(np.float64))
+        jitter = cat([np.asarray(s.colour[2], np.float64) if s.colour is not None else np.zeros(n, np.float64)
+                      for s, n in zip(batch, sizes)])
+    return RawBatch(tuple(s.id_scan for s in batch), cat([s.points for s in batch]), cat([s.rgb for s in batch]), cat(owner),
+                    cat([s.minv for s in batch]), cat([s.scale for s in batch]), cat([s.cls for s in batch]), colour, jitter,
+                    torch.from_numpy(np.cumsum([0] + sizes[:-1]).astype(np.int64)))
+
+
+def device_batch(raw_batch, device, res, use_xyz=False, recentre=True):
+    """A RawBatch -> ``(id_scans, coords4, feats, xyz, scale, cls)`` on ``device``: exactly what ``collate_fn([ds[i] ...])``
+    moved to the device gives (coords4 int32 [N, 4], feats f32 [N, 3|6], xyz / scale f32 [N, 3], cls int64 [N]), with the
+    training script's ``feats[:, -3:] * 2 - 1`` applied when ``recentre``.  On torch's current stream: non-blocking copies,
+    the voxelisation (ME.utils.quantize_batch, its one host wait for N) and one cv_sp_scan_rows_f32 launch."""
+    b = raw_batch
+    dev = torch.device(device)
+    up = lambda t: None if t is None else t.to(dev, non_blocking=True)
+    points, rgb, owner, minv, scale, cls, colour, jitter = (up(t) for t in (b.points, b.rgb, b.owner, b.minv, b.scale, b.cls,
+                                                                            b.colour, b.jitter))
+    with torch.cuda.device(dev):
+        coords4, index = me_utils.quantize_batch(points, res, offsets=b.offsets)
+        feats, xyz, scale_rows, cls_rows = me_utils.scan_rows(coords4, index, points, rgb, owner, minv, scale, cls, colour, jitter,
+                                                              use_xyz=use_xyz, recentre=recentre)
+    return b.id_scans, coords4, feats, xyz, scale_rows, cls_rows
 
 
 def _roty4(angle):

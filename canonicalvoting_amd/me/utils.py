@@ -1,6 +1,6 @@
 """``ME.utils`` subset: batched_coordinates (train_joint.py:82), sparse_quantize
-(utils/dataloader.py:197, sunrgbd/brnetcanon.py:218; on the device: quantize_device / quantize_batch, and voxel_rows for
-what a scene gathers behind it), kaiming_normal_
+(utils/dataloader.py:197, sunrgbd/brnetcanon.py:218; on the device: quantize_device / quantize_batch, voxel_rows for
+what a scene gathers behind it and scan_rows for what a training batch computes behind it), kaiming_normal_
 (utils/resnet.py:112)."""
 import math
 
@@ -155,6 +155,59 @@ def voxel_rows(coords4, index, res, *columns, recentre_from=None, out=None, poin
                                           float(res) if points else 0.0, vp(pts.data_ptr()) if points else None, jobs,
                                           len(columns), stream), "cv_sp_voxel_rows_f32")
     return pts, outs
+
+
+def scan_rows(coords4, index, points, rgb, owner, minv, scale, cls, colour=None, jitter=None, use_xyz=False, recentre=False,
+              out=None):
+    """The training batch of voxelised raw scans, in ONE launch on torch's current stream (cv_sp_scan_rows_f32): features and
+    labels of the kept rows from the raw per-vertex arrays, the bits ScanNetXYZProbMultiDataset.__getitem__ computes on the host.
+
+    coords4 [N, 4] / index [N] int32 as quantize_batch returns them; per raw vertex: points [M, 3] float32 (the row stride may
+    exceed 3), rgb [M, 3] uint8, owner [M] int32 (row of the model table, -1 = background); model table: minv [m, 3, 4]
+    float64, scale [m, 3] float32, cls [m] int32 (m may be 0); colour [B, 6] float64 (gain, shift per cloud) with jitter [M]
+    float64, both or neither.  use_xyz: the points in front of the colours; recentre: colours as c * 2 - 1.
+    out: optional (feats, xyz, scale, cls) destinations ([N, w] windows, row stride >= w; cls [N] int64, any stride).
+    Returns (feats [N, 3|6] float32, xyz [N, 3] float32, scale [N, 3] float32, cls [N] int64)."""
+    import ctypes
+
+    from .. import _lib
+    L = _lib.lib()
+    n, m, dev = index.shape[0], points.shape[0], index.device
+    assert index.dtype == torch.int32 and index.is_contiguous(), "index: a contiguous int32 device tensor"
+    assert coords4.dtype == torch.int32 and coords4.is_contiguous() and coords4.shape == (n, 4), "coords4: contiguous int32 [N, 4]"
+    assert points.dtype == torch.float32 and points.shape == (m, 3) and points.stride(1) == 1, "points: float32 [M, 3]"
+    assert rgb.dtype == torch.uint8 and rgb.shape == (m, 3) and rgb.is_contiguous(), "rgb: contiguous uint8 [M, 3]"
+    assert owner.dtype == torch.int32 and owner.shape == (m,) and owner.is_contiguous(), "owner: contiguous int32 [M]"
+    k = cls.shape[0]
+    assert minv.dtype == torch.float64 and minv.shape == (k, 3, 4) and minv.is_contiguous(), "minv: contiguous float64 [m, 3, 4]"
+    assert scale.dtype == torch.float32 and scale.shape == (k, 3) and scale.is_contiguous(), "scale: contiguous float32 [m, 3]"
+    assert cls.dtype == torch.int32 and cls.is_contiguous(), "cls: contiguous int32 [m]"
+    if (colour is None) != (jitter is None):
+        raise ValueError("scan_rows: the colour table and the jitter come together")
+    n_clouds = 1
+    if colour is not None:
+        n_clouds = colour.shape[0]
+        assert colour.dtype == torch.float64 and colour.shape == (n_clouds, 6) and colour.is_contiguous(), "colour: float64 [B, 6]"
+        assert jitter.dtype == torch.float64 and jitter.shape == (m,) and jitter.is_contiguous(), "jitter: contiguous float64 [M]"
+    fw = 6 if use_xyz else 3
+    widths, dtypes = (fw, 3, 3, 1), (torch.float32, torch.float32, torch.float32, torch.int64)
+    dst = list(out) if out is not None else [None] * 4
+    for i, (w, dt) in enumerate(zip(widths, dtypes)):
+        if dst[i] is None:
+            dst[i] = torch.empty((n, w) if i < 3 else (n,), dtype=dt, device=dev)
+        else:
+            d2 = dst[i] if i < 3 else dst[i].unsqueeze(1)
+            assert d2.dtype == dt and d2.shape == (n, w) and (d2.stride(1) == 1 or w == 1) and d2.stride(0) >= w, "out: [N, w] windows"
+    vp = ctypes.c_void_p
+    ptr = lambda t: vp(t.data_ptr()) if t is not None and t.numel() else None
+    d = _lib.ScanRowsDesc(ptr(coords4), ptr(index), n, m, ptr(points), points.stride(0), ptr(rgb), ptr(owner),
+                          ptr(minv), ptr(scale), ptr(cls), k, ptr(colour), ptr(jitter), n_clouds, int(bool(use_xyz)),
+                          int(bool(recentre)), ptr(dst[0]), dst[0].stride(0), ptr(dst[1]), dst[1].stride(0),
+                          ptr(dst[2]), dst[2].stride(0), ptr(dst[3]), dst[3].stride(0))
+    with torch.cuda.device(dev):
+        stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
+        _lib.check(L.cv_sp_scan_rows_f32(ctypes.byref(d), stream), "cv_sp_scan_rows_f32")
+    return tuple(dst)
 
 
 def sparse_quantize(coordinates, features=None, labels=None, quantization_size=None, return_index=False,

@@ -45,7 +45,9 @@ extern "C" {
  *    descriptors / results and the cv_sizeof_* helpers (additive: no struct or signature moved).
  *    Since then, still 6: cv_hv_forward_peaks_f32 / cv_hv_forward_peaks_cat_f32 and a trailing cv_scene_desc.peak_quotients
  *    (appended: a zero-initialised descriptor runs as before; cv_scene_separate_desc has no such field, its scene call votes full
- *    grids). */
+ *    grids).
+ *    Still 6: cv_sp_scan_rows_f32 (cv_scan_rows_desc) and cv_sizeof_scan_rows_desc, the training batch from raw scans
+ *    (additive: no struct or signature moved). */
 #define CV_ABI_VERSION 6
 int cv_abi_version(void);
 const char* cv_last_error(void);
@@ -277,6 +279,39 @@ typedef struct cv_gather_job {
 } cv_gather_job;
 int cv_sp_voxel_rows_f32(const int32_t* d_coords4, const int32_t* d_index, long long n, float res, float* d_points_out,
                          const cv_gather_job* jobs, int n_jobs, void* stream);
+
+/* A TRAINING batch from raw scans, in ONE launch behind the voxeliser: the network's input features and the three label arrays
+ * of the n kept rows, computed from the raw per-vertex arrays of the concatenated scans - what
+ * ScanNetXYZProbMultiDataset.__getitem__ (utils/dataloader.py:118-210) computes per vertex on the host and then gathers.
+ * For kept row i: v = d_index[i] (raw vertex), b = d_coords4[i][0] (cloud), o = d_owner[v] (row of the model table, -1 or
+ * outside [0, n_models): background).
+ *   feats  colour k: c = (float)((double)rgb[v][k] / 255.0); with a colour table, c = (float)((double)c * colour[b][k]),
+ *          c = (float)((double)c + colour[b][3 + k]), c = (float)((double)c + jitter[v]), then clamped to [0, 1] - every
+ *          step rounds to fp32, as numpy's in-place `float32 op= float64` does.  use_xyz != 0: the row's three d_points
+ *          words come first (width 6, else 3).  recentre != 0: the colour columns are written as c * 2.0f - 1.0f.
+ *   xyz    o >= 0: xyz[r] = (float)(((m[r][0] * x + m[r][1] * y) + m[r][2] * z) + m[r][3]) in fp64 with (x, y, z) =
+ *          d_points[v] and m = d_minv[o] - this order, no fused multiply-add; background: 0
+ *   scale  d_model_scale[o], background 0            cls   d_model_cls[o] widened to int64, background 9
+ * d_points [m_points][points_ld] fp32, d_rgb [m_points][3] uint8, d_owner [m_points] int32, d_minv [n_models][3][4] fp64,
+ * d_model_scale [n_models][3] fp32, d_model_cls [n_models] int32 (the three may be NULL when n_models == 0),
+ * d_colour [n_clouds][6] fp64 (gain, shift) with d_jitter [m_points] fp64 - both or neither.  Destinations are [n][width]
+ * windows with row strides in elements (>= width; what lies beyond the width is left alone).
+ * Every argument is validated before anything is launched.  No atomics, no host wait; asynchronous on `stream`. */
+typedef struct cv_scan_rows_desc {
+    const int32_t* d_coords4; const int32_t* d_index; long long n;       /* as cv_sp_quantize_* wrote them; n <= m_points */
+    long long m_points;
+    const float* d_points; long long points_ld;
+    const uint8_t* d_rgb;
+    const int32_t* d_owner;
+    const double* d_minv; const float* d_model_scale; const int32_t* d_model_cls; int n_models;
+    const double* d_colour; const double* d_jitter; int n_clouds;
+    int use_xyz, recentre;
+    float* d_feats; long long feats_ld;
+    float* d_xyz; long long xyz_ld;
+    float* d_scale; long long scale_ld;
+    long long* d_cls; long long cls_ld;
+} cv_scan_rows_desc;
+int cv_sp_scan_rows_f32(const cv_scan_rows_desc* desc, void* stream);
 
 /* Spatial row order of a coordinate set (what the fused network runs on; replaces the sort of Morton keys by the
  * caller): stable sort on (batch index, Z-order of the 2^shift cubes), rows of one cube in the caller's order.
@@ -860,6 +895,7 @@ int cv_detect_points_f32(const cv_points_desc* desc, cv_points_result* result, v
 int cv_detect_points_separate_f32(const cv_points_separate_desc* desc, cv_points_separate_result* result, void* stream);
 /* sizeof of the structures above as the LIBRARY was compiled (a binding that mirrors them field by field compares) */
 size_t cv_sizeof_gather_job(void);
+size_t cv_sizeof_scan_rows_desc(void);
 size_t cv_sizeof_points_desc(void);
 size_t cv_sizeof_points_separate_desc(void);
 size_t cv_sizeof_points_result(void);

@@ -4,6 +4,10 @@ batch of 3 scenes, masked MSE(xyz) + MSE(log scale) + CE(class); one process per
 through torch.distributed.run (the reference is single-GPU).
 
     python scripts/train_joint.py [--epochs 2] [--scenes 6] [--points 20000] [--batch 3]
+    python scripts/train_joint.py --config config.yaml [--device-loader]
+
+--device-loader (with --config): the workers stop at the raw scan (``raw_item``) and the batch - colours, labels,
+voxelisation, gathers - is built on the device (``data.device_batch``); the same batches bit for bit.
 """
 import argparse
 import os
@@ -16,8 +20,35 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from canonicalvoting_amd import dist as cvd  # noqa: E402
 from canonicalvoting_amd import train  # noqa: E402
 from canonicalvoting_amd.data import (ScanNetXYZProbMultiDataset, SyntheticScanDataset, collate_fn,  # noqa: E402
-                                     load_config)
+                                     collate_raw, device_batch, load_config)
 from canonicalvoting_amd.minkunet import MinkUNet34C  # noqa: E402
+
+
+class RawItems(torch.utils.data.Dataset):
+    """a ScanNetXYZProbMultiDataset whose items are its raw scans (``raw_item``), for the device loader"""
+
+    def __init__(self, ds):
+        self.ds = ds
+
+    def __len__(self):
+        return len(self.ds)
+
+    def __getitem__(self, index):
+        return self.ds.raw_item(index)
+
+
+def host_batches(loader, dev):
+    """train_joint.py:245-249: the collated host batch, copied to the device, colour columns recentred"""
+    for _, coords, feats, xyz, scale, cls in loader:
+        feats = feats.to(dev)
+        feats[:, -3:] = feats[:, -3:] * 2.0 - 1.0                         # train_joint.py:248-249: colour columns only
+        yield coords.to(dev), feats, xyz.to(dev), scale.to(dev), cls.to(dev)
+
+
+def device_batches(loader, dev, cfg):
+    """the same batches from raw scans (--device-loader)"""
+    for raw in loader:
+        yield device_batch(raw, dev, cfg.scannet_res, use_xyz=cfg.use_xyz, recentre=True)[1:]
 
 
 def main():
@@ -29,7 +60,11 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--save", default=None)
     ap.add_argument("--config", default=None, help="the reference's config.yaml: train on real ScanNet/Scan2CAD files")
+    ap.add_argument("--device-loader", action="store_true",
+                    help="with --config: build every batch on the device from raw scans (data.device_batch)")
     a = ap.parse_args()
+    if a.device_loader and not a.config:
+        ap.error("--device-loader needs --config (synthetic items are already voxel-level)")
     cfg = load_config(a.config, category="all") if a.config else None
     world, rank, local = cvd.world()
     torch.cuda.set_device(local)
@@ -53,8 +88,10 @@ def main():
         # train_joint.py:205-211; every rank reads its own slice of the scans (DistributedSampler)
         ds = ScanNetXYZProbMultiDataset(cfg, training=True, augment=cfg.augment)
         sampler = torch.utils.data.distributed.DistributedSampler(ds, world, rank, shuffle=True) if world > 1 else None
-        loader = torch.utils.data.DataLoader(ds, batch_size=cfg.batch_size, shuffle=sampler is None, sampler=sampler,
-                                             collate_fn=collate_fn, drop_last=True, num_workers=cfg.num_workers)
+        loader = torch.utils.data.DataLoader(RawItems(ds) if a.device_loader else ds, batch_size=cfg.batch_size,
+                                             shuffle=sampler is None, sampler=sampler,
+                                             collate_fn=collate_raw if a.device_loader else collate_fn, drop_last=True,
+                                             num_workers=cfg.num_workers, pin_memory=a.device_loader)
     else:
         ds = SyntheticScanDataset(a.scenes, a.points, seed0=1000 * rank)      # every rank owns its scenes
         loader = torch.utils.data.DataLoader(ds, batch_size=a.batch, shuffle=True, collate_fn=collate_fn, drop_last=True)
@@ -63,10 +100,8 @@ def main():
         train.set_bn_momentum(model, train.bn_momentum(epoch, bn_step, bn_rate))   # train_joint.py:224-225,239
         net.train()
         t0, tot, n = time.perf_counter(), 0.0, 0
-        for _, coords, feats, xyz, scale, cls in loader:
-            feats = feats.to(dev)
-            feats[:, -3:] = feats[:, -3:] * 2.0 - 1.0                         # train_joint.py:248-249: colour columns only
-            loss, _ = train.train_step(net, opt, coords.to(dev), feats, xyz.to(dev), scale.to(dev), cls.to(dev))
+        for batch in (device_batches(loader, dev, cfg) if a.device_loader else host_batches(loader, dev)):
+            loss, _ = train.train_step(net, opt, *batch)
             tot += float(loss)
             n += 1
         if rank == 0:
