@@ -166,6 +166,19 @@ class ScanRowsDesc(ctypes.Structure):
                 ("d_scale", vp), ("scale_ld", ctypes.c_longlong), ("d_cls", vp), ("cls_ld", ctypes.c_longlong)]
 
 
+class SymLossDesc(ctypes.Structure):
+    """struct cv_sym_loss_desc (include/cv_hip.h)"""
+    _fields_ = [("d_out", vp), ("n_rows", ctypes.c_longlong), ("ld", ctypes.c_longlong),
+                ("d_rows", vp), ("d_pseg", vp), ("n_points", ctypes.c_longlong),
+                ("d_seg_ptr", vp), ("d_pose_ptr", vp), ("d_tgt_ptr", vp), ("n_segments", ctypes.c_int), ("n_jobs", ctypes.c_int),
+                ("d_targets", vp), ("n_targets", ctypes.c_longlong),
+                ("d_urow", vp), ("d_uptr", vp), ("d_upoint", vp), ("n_urows", ctypes.c_int),
+                ("w", ctypes.c_float * 3), ("xyz_factor", ctypes.c_float),
+                ("d_loss", vp), ("d_pose_loss", vp), ("d_best", vp), ("d_seg_loss", vp),
+                ("d_grad_loss", vp), ("d_grad", vp), ("grad_ld", ctypes.c_longlong),
+                ("d_ws", vp), ("ws_bytes", ctypes.c_size_t)]
+
+
 class PointsFront(ctypes.Structure):
     """struct cv_points_front (include/cv_hip.h)"""
     _fields_ = [("d_raw_points", vp), ("m", ctypes.c_longlong), ("points_ld", ctypes.c_longlong), ("points_f64", ctypes.c_int),
@@ -248,6 +261,11 @@ SIGNATURES = {
     "cv_sizeof_gather_job": (ctypes.c_size_t, []),
     "cv_sp_scan_rows_f32": (ctypes.c_int, [ctypes.POINTER(ScanRowsDesc), vp]),
     "cv_sizeof_scan_rows_desc": (ctypes.c_size_t, []),
+    "cv_sym_loss_fwd_f32": (ctypes.c_int, [ctypes.POINTER(SymLossDesc), vp]),
+    "cv_sym_loss_bwd_f32": (ctypes.c_int, [ctypes.POINTER(SymLossDesc), vp]),
+    "cv_sym_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int]),
+    "cv_sym_loss_chunk_rows": (ctypes.c_int, []),
+    "cv_sizeof_sym_loss_desc": (ctypes.c_size_t, []),
     "cv_sp_morton_keys": (ctypes.c_int, [vp, ctypes.c_longlong, vp, vp]),
     "cv_sp_sort_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "cv_sp_sort_rows": (ctypes.c_int, [vp, ctypes.c_longlong, vp, vp, vp, vp, ctypes.c_size_t, vp]),

@@ -8,7 +8,8 @@ in the text format eval_joint.py:285-301 reads (``tx ty tz ry sx sy sz ... categ
 There is no ScanNet/Scan2CAD data in this environment; ``ScanNetXYZProbMultiDataset`` below reads the real file
 formats and is checked against the reference's own class on a miniature dataset (tests/golden/scannet_mini).
 ``raw_item`` / ``collate_raw`` / ``device_batch`` are the same training batch with everything behind the two host
-transforms computed on the device.
+transforms computed on the device.  ``collate_sym`` / ``SymBatch`` / ``sym_to_device`` are the
+per-category trainer's symmetry labels packed for the device loss, ``SyntheticSymDataset`` its synthetic items.
 """
 import typing
 
@@ -471,3 +472,125 @@ def collate_fn_separate(batch):
             torch.from_numpy(np.concatenate(scale_labels, 0)).float(),
             torch.from_numpy(np.concatenate(obj_labels, 0)).long(),
             torch.from_numpy(np.concatenate(class_labels, 0)).long())
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# The same labels in a form the device consumes: cv_sym_loss_fwd_f32 / cv_sym_loss_bwd_f32 through
+# me.utils.sym_loss, train.separate_loss_packed and train.train_step_separate.
+
+class SymBatch(typing.NamedTuple):
+    """``collate_sym``'s packed symmetry labels: CPU tensors and three host ints, so DataLoader workers and ``pin_memory``
+    carry it.  A segment is one aligned model of one scan, segments in batch order (scan, then model order):
+    ``rows`` int32 [P] output row of each labelled point, ``pseg`` int32 [P] its segment, ``seg_ptr`` int32 [S+1] (points of
+    segment s: rows[seg_ptr[s]:seg_ptr[s+1]]), ``pose_ptr`` int32 [S+1] prefix of the pose counts (J = pose_ptr[S] jobs),
+    ``tgt_ptr`` int32 [S+1] first row of segment s's block [n_pose][len][3] in ``targets`` float32 [T, 3] (the dataset's
+    fp32 bits, untouched); the inverse list of the backward: ``urow`` int32 [U] distinct rows ascending, ``uptr`` int32
+    [U+1], ``upoint`` int32 [P] the points of each row in ascending point index."""
+    rows: torch.Tensor
+    pseg: torch.Tensor
+    seg_ptr: torch.Tensor
+    pose_ptr: torch.Tensor
+    tgt_ptr: torch.Tensor
+    targets: torch.Tensor
+    urow: torch.Tensor
+    uptr: torch.Tensor
+    upoint: torch.Tensor
+    n_segments: int
+    n_jobs: int
+    max_row: int          # the largest entry of rows (-1 without segments): what the caller compares with the output's rows
+
+
+def pack_sym(xyz_labels, scan_sizes, reference_indexing=True):
+    """Per scan a list of ``[rows, [xyz under each pose]]`` (ScanNetXYZProbSymDataset's labels; numpy or torch) -> SymBatch.
+    ``scan_sizes``: rows of every scan.  reference_indexing: ``rows`` are the scan's own row numbers (what
+    train_separate.py:270 indexes the BATCH output with); False: offset by the rows of the scans in front.
+    A segment without a surviving row is DROPPED (the reference's mean over an empty tensor is NaN and poisons the batch);
+    a negative row raises."""
+    as_np = lambda a: a.numpy() if torch.is_tensor(a) else np.asarray(a)
+    first = np.cumsum([0] + [int(n) for n in scan_sizes[:-1]])
+    rows, targets, lens, poses = [], [], [], []
+    for j, per_scan in enumerate(xyz_labels):
+        for r, xyzs in per_scan:
+            r = as_np(r).astype(np.int64).reshape(-1)
+            if r.size == 0:
+                continue
+            if r.min() < 0:
+                raise ValueError("collate_sym: negative row %d in a segment of scan %d" % (int(r.min()), j))
+            if len(xyzs) == 0:
+                raise ValueError("collate_sym: a segment of scan %d has no pose" % j)
+            xs = [as_np(x) for x in xyzs]
+            if any(x.shape != (r.size, 3) for x in xs):
+                raise ValueError("collate_sym: targets of a segment of scan %d are not [%d, 3]" % (j, r.size))
+            rows.append(r if reference_indexing else r + first[j])
+            targets.extend(np.ascontiguousarray(x, np.float32) for x in xs)
+            lens.append(r.size)
+            poses.append(len(xs))
+    S = len(lens)
+    lens, poses = np.asarray(lens, np.int64), np.asarray(poses, np.int64)
+    rows = np.concatenate(rows) if S else np.zeros(0, np.int64)
+    prefix = lambda a: np.concatenate([[0], np.cumsum(a)])
+    seg_ptr, pose_ptr, tgt_ptr = prefix(lens), prefix(poses), prefix(lens * poses)
+    if max(int(tgt_ptr[-1]), int(rows.max()) if S else 0) >= 2 ** 31:
+        raise ValueError("collate_sym: the batch does not fit int32 pointers")
+    order = np.argsort(rows, kind="stable")                     # points by row; equal rows keep their ascending point index
+    urow, counts = np.unique(rows, return_counts=True)
+    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32))
+    return SymBatch(i32(rows), i32(np.repeat(np.arange(S), lens)), i32(seg_ptr), i32(pose_ptr), i32(tgt_ptr),
+                    torch.from_numpy(np.concatenate(targets, 0) if S else np.zeros((0, 3), np.float32)),
+                    i32(urow), i32(prefix(counts)), i32(order), S, int(pose_ptr[-1]), int(rows.max()) if S else -1)
+
+
+def unpack_sym(sym):
+    """the flat list of ``[rows int64, [targets per pose]]`` a SymBatch holds, in segment order (rows as packed)"""
+    out = []
+    for s in range(sym.n_segments):
+        a, b, t = int(sym.seg_ptr[s]), int(sym.seg_ptr[s + 1]), int(sym.tgt_ptr[s])
+        n_pose = int(sym.pose_ptr[s + 1] - sym.pose_ptr[s])
+        out.append([sym.rows[a:b].long(), [sym.targets[t + p * (b - a):t + (p + 1) * (b - a)] for p in range(n_pose)]])
+    return out
+
+
+def collate_sym(batch, reference_indexing=True):
+    """``collate_fn_separate`` with the per-model label lists packed for the device: ``(id_scans, coords4, feats, sym,
+    scale_labels, obj_labels, class_labels)`` with ``sym`` a SymBatch (``pack_sym``: a segment without a surviving row is
+    dropped, a negative row raises).  The scan sizes are known here, so reference_indexing=False needs no bincount later."""
+    id_scans, coords, feats, xyz_labels, scale_labels, obj_labels, class_labels = list(zip(*batch))
+    sym = pack_sym(xyz_labels, [len(c) for c in coords], reference_indexing)
+    return (id_scans, me_utils.batched_coordinates(coords), torch.from_numpy(np.concatenate(feats, 0)).float(), sym,
+            torch.from_numpy(np.concatenate(scale_labels, 0)).float(),
+            torch.from_numpy(np.concatenate(obj_labels, 0)).long(),
+            torch.from_numpy(np.concatenate(class_labels, 0)).long())
+
+
+def sym_to_device(sym, dev):
+    """the SymBatch with its tensors on ``dev`` (non-blocking copies: no host wait from pinned memory)"""
+    return sym._replace(**{k: v.to(dev, non_blocking=True) for k, v in sym._asdict().items() if torch.is_tensor(v)})
+
+
+class SyntheticSymDataset(torch.utils.data.Dataset):
+    """``ScanNetXYZProbSymDataset``-shaped items from ``make_scene`` scenes, for the profile and scripts/train_separate.py
+    without ScanNet files: one segment per distinct object (object rows grouped by their (scale_labels, class) rows), the
+    symmetry classes none / UP_2 / UP_4 / UP_INF cycling over the segments; the targets of a pose are
+    ``xyz0 @ Ry(a).T`` evaluated in fp64 and cast once."""
+
+    def __init__(self, n_scenes=6, n_points=20000, res=0.03, seed0=0, **scene_kw):
+        self.scenes = SyntheticScanDataset(n_scenes, n_points, res, seed0, **scene_kw)
+
+    def __len__(self):
+        return len(self.scenes)
+
+    def __getitem__(self, index):
+        id_scan, coords, feats, xyz, scale, cls = self.scenes[index]
+        obj_rows = np.nonzero(cls != 9)[0]
+        key = np.concatenate([scale[obj_rows], cls[obj_rows, None].astype(np.float32)], 1)
+        _, inverse = np.unique(key, axis=0, return_inverse=True)
+        inverse = np.asarray(inverse).reshape(-1)
+        syms = [None, "__SYM_ROTATE_UP_2", "__SYM_ROTATE_UP_4", "__SYM_ROTATE_UP_INF"]
+        xyz_labels = []
+        for k in range(int(inverse.max()) + 1 if obj_rows.size else 0):
+            rows = obj_rows[inverse == k]
+            x0 = xyz[rows].astype(np.float64)
+            angles = [0.0] + list(SYMMETRY_ANGLES.get(syms[k % 4], []))
+            xyz_labels.append([rows, [(x0 @ _roty4(a)[:3, :3].T).astype(np.float32) for a in angles]])
+        obj = (cls != 9).astype(np.int32)
+        return id_scan, coords, feats, xyz_labels, scale, obj, np.where(cls == 9, 0, cls).astype(np.int32)

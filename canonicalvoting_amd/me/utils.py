@@ -1,7 +1,8 @@
 """``ME.utils`` subset: batched_coordinates (train_joint.py:82), sparse_quantize
 (utils/dataloader.py:197, sunrgbd/brnetcanon.py:218; on the device: quantize_device / quantize_batch, voxel_rows for
 what a scene gathers behind it and scan_rows for what a training batch computes behind it), kaiming_normal_
-(utils/resnet.py:112)."""
+(utils/resnet.py:112); sym_loss, the per-category trainer's coordinate loss over packed symmetry labels
+(train_separate.py:265-280)."""
 import math
 
 import numpy as np
@@ -208,6 +209,92 @@ def scan_rows(coords4, index, points, rgb, owner, minv, scale, cls, colour=None,
         stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
         _lib.check(L.cv_sp_scan_rows_f32(ctypes.byref(d), stream), "cv_sp_scan_rows_f32")
     return tuple(dst)
+
+
+def _sym_desc(out_feats, sym, weights, xyz_factor):
+    """cv_sym_loss_desc of predictions ``out_feats`` [N, C >= 3] and a device SymBatch, outputs and workspace still unset"""
+    import ctypes
+
+    from .. import _lib
+    dev = out_feats.device
+    assert out_feats.is_cuda and out_feats.dtype == torch.float32 and out_feats.dim() == 2 and out_feats.stride(1) == 1 \
+        and out_feats.stride(0) >= 3 and out_feats.shape[1] >= 3, "out_feats: float32 [N, C >= 3] device rows"
+    ints = (sym.rows, sym.pseg, sym.seg_ptr, sym.pose_ptr, sym.tgt_ptr, sym.urow, sym.uptr, sym.upoint)
+    assert all(t.device == dev and t.dtype == torch.int32 and t.is_contiguous() for t in ints), "sym: int32 tensors on the output's device"
+    assert sym.targets.device == dev and sym.targets.dtype == torch.float32 and sym.targets.is_contiguous(), "sym.targets: float32 [T, 3]"
+    S, P = sym.n_segments, sym.rows.shape[0]
+    assert sym.seg_ptr.shape[0] == S + 1 and sym.pose_ptr.shape[0] == S + 1 and sym.tgt_ptr.shape[0] == S + 1 \
+        and sym.pseg.shape[0] == P and sym.upoint.shape[0] == P and sym.uptr.shape[0] == sym.urow.shape[0] + 1, "sym: inconsistent sizes"
+    if sym.max_row >= out_feats.shape[0]:
+        raise ValueError("sym_loss: label row %d outside the %d output rows" % (sym.max_row, out_feats.shape[0]))
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+    d = _lib.SymLossDesc()
+    d.d_out, d.n_rows, d.ld = ptr(out_feats), out_feats.shape[0], out_feats.stride(0)
+    d.d_rows, d.d_pseg, d.n_points = ptr(sym.rows), ptr(sym.pseg), P
+    d.d_seg_ptr, d.d_pose_ptr, d.d_tgt_ptr, d.n_segments, d.n_jobs = ptr(sym.seg_ptr), ptr(sym.pose_ptr), ptr(sym.tgt_ptr), S, sym.n_jobs
+    d.d_targets, d.n_targets = ptr(sym.targets), sym.targets.shape[0]
+    d.d_urow, d.d_uptr, d.d_upoint, d.n_urows = ptr(sym.urow), ptr(sym.uptr), ptr(sym.upoint), sym.urow.shape[0]
+    d.w = (ctypes.c_float * 3)(*[float(v) for v in weights])
+    d.xyz_factor = float(xyz_factor)
+    return d
+
+
+class _SymLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out_feats, sym, weights, xyz_factor):
+        import ctypes
+
+        from .. import _lib
+        L = _lib.lib()
+        vp = ctypes.c_void_p
+        dev = out_feats.device
+        out_feats = out_feats if out_feats.stride(1) == 1 else out_feats.contiguous()
+        d = _sym_desc(out_feats, sym, weights, xyz_factor)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        pose_loss = torch.empty(max(sym.n_jobs, 1), dtype=torch.float32, device=dev)
+        best = torch.empty(max(sym.n_segments, 1), dtype=torch.int32, device=dev)
+        seg_loss = torch.empty(max(sym.n_segments, 1), dtype=torch.float32, device=dev)
+        ws = _lib.scratch(dev, "sym_loss", int(L.cv_sym_loss_workspace_bytes(d.n_targets, d.n_jobs)))
+        d.d_loss, d.d_pose_loss, d.d_best, d.d_seg_loss = (vp(t.data_ptr()) for t in (loss, pose_loss, best, seg_loss))
+        d.d_ws, d.ws_bytes = vp(ws.data_ptr()), ws.numel()
+        with torch.cuda.device(dev):
+            stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
+            _lib.check(L.cv_sym_loss_fwd_f32(ctypes.byref(d), stream), "cv_sym_loss_fwd_f32")
+        ctx.save_for_backward(out_feats, best)
+        ctx.sym, ctx.weights, ctx.xyz_factor = sym, weights, xyz_factor
+        ctx.mark_non_differentiable(pose_loss, best)
+        return loss.reshape(()), pose_loss[:sym.n_jobs], best[:sym.n_segments]
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_pose, _grad_best):
+        import ctypes
+
+        from .. import _lib
+        vp = ctypes.c_void_p
+        out_feats, best = ctx.saved_tensors
+        dev = out_feats.device
+        grad = torch.zeros(out_feats.shape, dtype=torch.float32, device=dev)
+        gl = grad_loss.to(torch.float32).reshape(1).contiguous()
+        d = _sym_desc(out_feats, ctx.sym, ctx.weights, ctx.xyz_factor)
+        d.d_best, d.d_grad_loss, d.d_grad, d.grad_ld = vp(best.data_ptr()), vp(gl.data_ptr()), vp(grad.data_ptr()), grad.stride(0)
+        with torch.cuda.device(dev):
+            stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
+            _lib.check(_lib.lib().cv_sym_loss_bwd_f32(ctypes.byref(d), stream), "cv_sym_loss_bwd_f32")
+        return grad, None, None, None
+
+
+def sym_loss(out_feats, sym, weights=(1.0, 1.0, 1.0), xyz_factor=1.0, return_poses=False):
+    """The per-category model's coordinate loss over packed symmetry labels (cv_sym_loss_fwd_f32 / cv_sym_loss_bwd_f32, two
+    launches forward and one backward on torch's current stream, no host wait): per segment the weighted mean square distance
+    of columns 0..2 of ``out_feats`` [N, C] to the targets of every symmetry-equivalent pose, the minimum over the poses (the
+    lowest pose on ties, NaN as torch.min), the mean over the segments times ``xyz_factor`` - a scalar.  ``sym``: a
+    data.SymBatch whose tensors are on the output's device (data.sym_to_device); its ``max_row`` is checked against N here,
+    on the host, before anything is launched.  The backward gives an [N, C] gradient that is zero outside columns 0..2 of
+    labelled rows, through the winning pose only: torch's full-reduction ``min()`` splits the gradient evenly over exact ties,
+    which distinct poses do not produce (tests/test_sym_loss.py requires a decidable minimum of every case it runs).
+    Bit-reproducible: no atomics, every sum in an order the labels fix.  return_poses: also (pose losses [J], best pose [S])."""
+    loss, pose_loss, best = _SymLossFn.apply(out_feats, sym, tuple(float(v) for v in weights), float(xyz_factor))
+    return (loss, pose_loss, best) if return_poses else loss
 
 
 def sparse_quantize(coordinates, features=None, labels=None, quantization_size=None, return_index=False,

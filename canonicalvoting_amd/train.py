@@ -4,7 +4,9 @@
                         (train_joint.py:253-283; defaults from config/config.yaml)
     separate_loss       the per-category model's loss with the minimum over symmetry-equivalent poses
                         (train_separate.py:247-287)
+    separate_loss_packed the same over data.collate_sym's packed labels: the pose loss on the device, no host wait
     train_step          zero_grad -> forward -> loss -> backward -> optimizer.step (:246-288)
+    train_step_separate the same for the per-category model (train_separate.py:236-292); both run through _run_step
     adjust_learning_rate step LR decay (:128-138, config.yaml:32-36)
     make_ddp            scene-parallel data parallelism: torch DDP (bucketed gradient all-reduce over
                         RCCL, overlapped with backward) around the model (the reference
@@ -12,7 +14,7 @@
 
 The sparse convolutions run forward / input-gradient / weight-gradient on the HIP kernels
 (canonicalvoting_amd.me._ConvFn), batch-statistics BatchNorm with the residual add and ReLU folded in on
-bn_col_reduce4 / bn_backward_apply4 (me._BNTrainFn); the losses are torch ops.
+bn_col_reduce4 / bn_backward_apply4 (me._BNTrainFn); the losses are torch ops, except the packed pose loss (sym_loss.hip).
 The reference's stale-loss bug (`losses` persists across iterations) is not
 reproduced: a batch without object points contributes only the classification loss.
 """
@@ -86,6 +88,32 @@ def separate_loss(out_feats, xyz_labels, scale_labels, obj_labels, coords4=None,
             pred = out_xyz[rows]
             per_model.append(torch.stack([torch.mean((pred - x.to(out_feats.device)) ** 2 * w) for x in xyzs]).min())
     losses["loss_xyz"] = torch.mean(torch.stack(per_model)) * xyz_factor
+    return sum(losses.values()), losses
+
+
+def separate_loss_packed(out_feats, sym, scale_labels, obj_labels, log_scale=True, xyz_factor=1.0, scale_factor=1.0,
+                         xyz_component_weights=(1.0, 1.0, 1.0)):
+    """separate_loss - the same three terms under the same keys - over packed symmetry labels, without a host wait.
+    ``sym``: a data.SymBatch on the output's device (data.collate_sym + data.sym_to_device; which indexing its rows follow
+    was decided in the collate).  Its largest row is compared with the output's rows here, from the host int, before anything
+    is launched.  loss_xyz: ME.utils.sym_loss (HIP: minimum over the symmetry-equivalent poses per model, mean over the
+    models; two launches forward, one backward).  loss_obj: the same cross entropy.  loss_scale: in joint_loss's form - the
+    object count stays on the device as the denominator and background rows are selected away in front of the arithmetic,
+    so a non-finite background prediction reaches neither the loss nor a gradient, and a batch without an object row gives
+    a zero term where separate_loss's mean over nothing gives NaN."""
+    if sym.max_row >= out_feats.shape[0]:
+        raise ValueError("separate_loss_packed: label row %d outside the %d output rows" % (sym.max_row, out_feats.shape[0]))
+    obj = obj_labels.long()
+    m = (obj == 1)[:, None]
+    w = torch.as_tensor(xyz_component_weights, dtype=out_feats.dtype, device=out_feats.device)
+    losses = {"loss_obj": F.cross_entropy(out_feats[:, 6:8], obj)}
+    denom = (m.sum() * 3).clamp(min=1).to(out_feats.dtype)
+    zero = torch.zeros((), dtype=out_feats.dtype, device=out_feats.device)
+    safe_scale = torch.where(m, scale_labels, torch.ones_like(scale_labels))
+    tgt = torch.where(m, torch.log(safe_scale) if log_scale else safe_scale, zero)
+    out_scale = torch.where(m, out_feats[:, 3:6], zero)
+    losses["loss_scale"] = torch.sum((out_scale - tgt) ** 2 * w) / denom * scale_factor
+    losses["loss_xyz"] = ME.utils.sym_loss(out_feats, sym, xyz_component_weights, xyz_factor)
     return sum(losses.values()), losses
 
 
@@ -173,27 +201,16 @@ def _bn_state(model):
     return bufs, saved
 
 
-def train_step(model, optimizer, coords4, feats, xyz_labels, scale_labels, class_labels, **loss_kw):
-    """one iteration of train_joint.py:246-288; feats already recentred (:248-249).
-
-    The forward multiplies fp16 pairs on the eval path's kernels (ME.TRAIN_FWD_HL); an activation beyond the fp16 range - never
-    behind a healthy BatchNorm - raises the range flag.  With a fused Adam the flag rides to the optimizer as `found_inf`: the
-    update of such a step is skipped ON THE DEVICE (no host wait in the step).  The host reads the flag of the step FLAG_LAG
-    calls ago (pinned memory + an event that has long passed): it then restores the BatchNorm running statistics and counters
-    from a snapshot that a device-side guard has kept at the state before the FIRST flagged step (cv_sp_copy_unless_flag: the
-    flagged batches are dropped as a whole - no update, no statistics, exactly as if they had not been drawn), counts the
-    fallback (model.train_range_fallbacks) and runs this and the following steps on the bf16 triples.  Other optimizers: the host
-    waits for the flag and redoes the step on the triples before the optimizer sees a gradient.
-    Under DDP the flag is all-reduced (MAX) over the ranks of the model's process group before anybody acts on it, and the
-    lagged read looks at the same step on every rank: all ranks skip, restore, redo and switch to the triples together."""
-    dev = feats.device
+def _run_step(model, optimizer, dev, forward_loss):
+    """The core of train_step and train_step_separate: zero_grad -> ``forward_loss()`` (a closure: forward and loss, returns
+    ``(loss, parts)``) -> backward -> optimizer.step, inside the one training-step state a model keeps (_StepState): the
+    pair-scale hints and the batched weight pack, the range-flag ring with `found_inf`, the BatchNorm snapshot guard, the
+    bf16-triples fallback and the agreement of the flag over DDP ranks - as train_step's docstring describes them."""
     group = _step_group(model)
 
     def fwd_bwd():
         optimizer.zero_grad(set_to_none=True)
-        x = ME.SparseTensor(feats, coords4, device=dev)
-        out = model(x)
-        loss, parts = joint_loss(out.F, xyz_labels, scale_labels, class_labels, **loss_kw)
+        loss, parts = forward_loss()
         loss.backward()
         return loss, parts
 
@@ -222,7 +239,7 @@ def train_step(model, optimizer, coords4, feats, xyz_labels, scale_labels, class
             ME.range_flag(dev).zero_()
             model.train_range_fallbacks = getattr(model, "train_range_fallbacks", 0) + 1
             st.pairs_off, st.ring = True, None
-            return train_step(model, optimizer, coords4, feats, xyz_labels, scale_labels, class_labels, **loss_kw)
+            return _run_step(model, optimizer, dev, forward_loss)
         # BatchNorm statistics of before this step, kept ON THE DEVICE only while no step has raised the flag
         ME.copy_unless_flag(bufs, saved, dev, ME.range_flag(dev))
         with ME.pair_scale_hints(model) as step:
@@ -254,14 +271,60 @@ def train_step(model, optimizer, coords4, feats, xyz_labels, scale_labels, class
     return loss.detach(), {k: v.detach() for k, v in parts.items()}
 
 
+def train_step(model, optimizer, coords4, feats, xyz_labels, scale_labels, class_labels, **loss_kw):
+    """one iteration of train_joint.py:246-288; feats already recentred (:248-249).
+
+    The forward multiplies fp16 pairs on the eval path's kernels (ME.TRAIN_FWD_HL); an activation beyond the fp16 range - never
+    behind a healthy BatchNorm - raises the range flag.  With a fused Adam the flag rides to the optimizer as `found_inf`: the
+    update of such a step is skipped ON THE DEVICE (no host wait in the step).  The host reads the flag of the step FLAG_LAG
+    calls ago (pinned memory + an event that has long passed): it then restores the BatchNorm running statistics and counters
+    from a snapshot that a device-side guard has kept at the state before the FIRST flagged step (cv_sp_copy_unless_flag: the
+    flagged batches are dropped as a whole - no update, no statistics, exactly as if they had not been drawn), counts the
+    fallback (model.train_range_fallbacks) and runs this and the following steps on the bf16 triples.  Other optimizers: the host
+    waits for the flag and redoes the step on the triples before the optimizer sees a gradient.
+    Under DDP the flag is all-reduced (MAX) over the ranks of the model's process group before anybody acts on it, and the
+    lagged read looks at the same step on every rank: all ranks skip, restore, redo and switch to the triples together."""
+    dev = feats.device
+
+    def forward_loss():
+        out = model(ME.SparseTensor(feats, coords4, device=dev))
+        return joint_loss(out.F, xyz_labels, scale_labels, class_labels, **loss_kw)
+
+    return _run_step(model, optimizer, dev, forward_loss)
+
+
+def _is_sym_batch(labels):
+    return isinstance(labels, tuple) and hasattr(labels, "seg_ptr") and hasattr(labels, "n_segments")
+
+
 def train_step_separate(model, optimizer, coords4, feats, xyz_labels, scale_labels, obj_labels, **loss_kw):
     """one iteration of train_separate.py:236-292 (8-channel per-category model); feats already recentred (:241-242).
-    Returns None for a batch without object points, which the reference skips (:238-240)."""
+    Returns None for a batch without object points, which the reference skips (:238-240).
+
+    ``xyz_labels`` a data.SymBatch (data.collate_sym): the step of train_step - one _StepState per model with the pair-scale
+    hints, the batched weight pack, the range flag as `found_inf`, the BatchNorm snapshot guard, the bf16-triples fallback and
+    the DDP flag agreement (_run_step) - around separate_loss_packed, with no host wait: the skip is ``n_segments == 0``, a
+    host int.  The labels may still be on the host (copied non-blocking here) or already on the device (data.sym_to_device).
+    ``xyz_labels`` the nested lists of data.collate_fn_separate: the plain forward -> separate_loss -> backward -> step."""
+    dev = feats.device
+    if _is_sym_batch(xyz_labels):
+        sym = xyz_labels
+        if sym.n_segments == 0:
+            return None
+        if sym.rows.device != dev:
+            from .data import sym_to_device
+            sym = sym_to_device(sym, dev)
+        scale_dev, obj_dev = scale_labels.to(dev, non_blocking=True), obj_labels.to(dev, non_blocking=True)
+
+        def forward_loss():
+            out = model(ME.SparseTensor(feats, coords4, device=dev))
+            return separate_loss_packed(out.F, sym, scale_dev, obj_dev, **loss_kw)
+
+        return _run_step(model, optimizer, dev, forward_loss)
     if not bool((obj_labels == 1).any()):
         return None
     optimizer.zero_grad(set_to_none=True)
     out = model(ME.SparseTensor(feats, coords4, device=feats.device))
-    dev = feats.device
     loss, parts = separate_loss(out.F, xyz_labels, scale_labels.to(dev), obj_labels.to(dev), coords4=coords4, **loss_kw)
     loss.backward()
     optimizer.step()

@@ -47,6 +47,9 @@ extern "C" {
  *    (appended: a zero-initialised descriptor runs as before; cv_scene_separate_desc has no such field, its scene call votes full
  *    grids).
  *    Still 6: cv_sp_scan_rows_f32 (cv_scan_rows_desc) and cv_sizeof_scan_rows_desc, the training batch from raw scans
+ *    (additive: no struct or signature moved).
+ *    Still 6: cv_sym_loss_fwd_f32 / cv_sym_loss_bwd_f32 (cv_sym_loss_desc) with cv_sym_loss_workspace_bytes,
+ *    cv_sym_loss_chunk_rows and cv_sizeof_sym_loss_desc, the separate-model coordinate loss over packed symmetry labels
  *    (additive: no struct or signature moved). */
 #define CV_ABI_VERSION 6
 int cv_abi_version(void);
@@ -312,6 +315,50 @@ typedef struct cv_scan_rows_desc {
     long long* d_cls; long long cls_ld;
 } cv_scan_rows_desc;
 int cv_sp_scan_rows_f32(const cv_scan_rows_desc* desc, void* stream);
+
+/* The coordinate loss of the per-category model (train_separate.py:265-280) over PACKED symmetry labels, and its gradient.
+ * A segment is one aligned model of one scan: len_s labelled points, each an output row, and n_pose_s symmetry-equivalent
+ * poses with one fp32 target per point and pose.  With w = the component weights,
+ *   pose_loss[j]  = sum over the segment's points i and c in 0..2 of w[c] * (out[rows[i]][c] - target[pose][i][c])^2 / (3 len_s)
+ *   seg_loss[s]   = min over the segment's poses (on the fp32 pose losses; the LOWEST pose on ties; a NaN pose loss wins, as
+ *                   torch.min returns NaN), best[s] = that pose
+ *   loss[0]       = xyz_factor * (sum_s seg_loss[s]) / n_segments
+ *   grad[row][c] += grad_loss[0] * xyz_factor * 2 * w[c] * (out[row][c] - target[best[s]][i][c]) / (3 len_s n_segments)
+ *                   over the labelled points i of the row (a row may belong to several segments)
+ * Segments are concatenated: points of segment s are d_rows[d_seg_ptr[s] .. d_seg_ptr[s + 1]), its poses the jobs
+ * d_pose_ptr[s] .. d_pose_ptr[s + 1), its targets the block [n_pose_s][len_s][3] that starts at row d_tgt_ptr[s] of
+ * d_targets [n_targets][3]; d_pseg[i] = segment of point i.  For the backward, the inverse list: d_urow [n_urows] = the
+ * distinct rows ascending, d_upoint[d_uptr[u] .. d_uptr[u + 1]) = the points of row d_urow[u], ascending.
+ * Terms and sums are fp64 (fp32 inputs, so every difference is exact), rounded to fp32 once per output.  No atomics: the order
+ * of every sum depends on the labels and on cv_sym_loss_chunk_rows() alone, so loss, pose losses, best and gradient are the
+ * same bytes on every run and stream.  The gradient goes to the winning pose only: torch's full-reduction min() splits it
+ * evenly over exact ties, which distinct poses do not produce.
+ * PRECONDITIONS the host cannot see through device pointers: the pointer arrays are prefix sums as described (first entry 0,
+ * last entries n_points, n_jobs, n_targets), every segment has at least one point and one pose, and every row lies in
+ * [0, n_rows) - the caller checks its largest row on the host before it launches (a row outside reads as NaN and gets no
+ * gradient, but nothing else is promised for it).
+ * forward:  launches the partial pass and the select pass; writes d_loss [1], d_pose_loss [n_jobs], d_best [n_segments],
+ *           d_seg_loss [n_segments]; d_ws: cv_sym_loss_workspace_bytes(n_targets, n_jobs), else CV_ENOMEM (the message names
+ *           the size).  n_segments == 0: d_loss[0] = 0 and nothing else is launched.
+ * backward: one launch; reads d_best of the forward and d_grad_loss on the device (no host wait) and writes columns 0..2 of
+ *           the rows d_urow of d_grad [n_rows][grad_ld], which the caller has zeroed.  n_segments == 0: nothing.
+ * Arguments are validated before anything is launched (CV_EINVAL: null pointer, row stride below 3, negative count).
+ * Asynchronous on `stream`. */
+typedef struct cv_sym_loss_desc {
+    const float* d_out; long long n_rows; long long ld;                   /* predictions: columns 0..2 of [n_rows][ld] */
+    const int32_t* d_rows; const int32_t* d_pseg; long long n_points;
+    const int32_t* d_seg_ptr; const int32_t* d_pose_ptr; const int32_t* d_tgt_ptr; int n_segments; int n_jobs;
+    const float* d_targets; long long n_targets;
+    const int32_t* d_urow; const int32_t* d_uptr; const int32_t* d_upoint; int n_urows;
+    float w[3]; float xyz_factor;
+    float* d_loss; float* d_pose_loss; int32_t* d_best; float* d_seg_loss;  /* forward: written; backward: d_best read */
+    const float* d_grad_loss; float* d_grad; long long grad_ld;           /* backward only */
+    void* d_ws; size_t ws_bytes;                                          /* forward only */
+} cv_sym_loss_desc;
+int cv_sym_loss_fwd_f32(const cv_sym_loss_desc* desc, void* stream);
+int cv_sym_loss_bwd_f32(const cv_sym_loss_desc* desc, void* stream);
+size_t cv_sym_loss_workspace_bytes(long long n_targets, int n_jobs);
+int cv_sym_loss_chunk_rows(void);           /* rows per workgroup of the partial pass: the chunking the sums are ordered by */
 
 /* Spatial row order of a coordinate set (what the fused network runs on; replaces the sort of Morton keys by the
  * caller): stable sort on (batch index, Z-order of the 2^shift cubes), rows of one cube in the caller's order.
@@ -896,6 +943,7 @@ int cv_detect_points_separate_f32(const cv_points_separate_desc* desc, cv_points
 /* sizeof of the structures above as the LIBRARY was compiled (a binding that mirrors them field by field compares) */
 size_t cv_sizeof_gather_job(void);
 size_t cv_sizeof_scan_rows_desc(void);
+size_t cv_sizeof_sym_loss_desc(void);
 size_t cv_sizeof_points_desc(void);
 size_t cv_sizeof_points_separate_desc(void);
 size_t cv_sizeof_points_result(void);
