@@ -179,6 +179,26 @@ class SymLossDesc(ctypes.Structure):
                 ("d_ws", vp), ("ws_bytes", ctypes.c_size_t)]
 
 
+class SymRowsDesc(ctypes.Structure):
+    """struct cv_sym_rows_desc (include/cv_hip.h)"""
+    _fields_ = [("d_coords4", vp), ("d_index", vp), ("d_inverse", vp), ("d_quant_counts", vp), ("m_points", ctypes.c_longlong),
+                ("d_points", vp), ("points_ld", ctypes.c_longlong), ("d_rgb", vp), ("d_owner", vp),
+                ("d_model_scale", vp), ("d_model_cls", vp), ("n_models", ctypes.c_int),
+                ("d_colour", vp), ("d_jitter", vp), ("d_offsets", vp), ("n_clouds", ctypes.c_int),
+                ("d_seg_vertex", vp), ("n_cand", ctypes.c_longlong),
+                ("d_seg_vptr", vp), ("d_seg_pose_ptr", vp), ("n_seg_in", ctypes.c_int),
+                ("d_minv", vp), ("n_jobs_in", ctypes.c_longlong), ("n_targets_in", ctypes.c_longlong),
+                ("reference_indexing", ctypes.c_int), ("use_xyz", ctypes.c_int), ("recentre", ctypes.c_int),
+                ("d_rows", vp), ("d_pseg", vp), ("d_seg_ptr", vp), ("d_pose_ptr", vp), ("d_tgt_ptr", vp), ("d_targets", vp),
+                ("d_urow", vp), ("d_uptr", vp), ("d_upoint", vp),
+                ("d_feats", vp), ("feats_ld", ctypes.c_longlong), ("d_scale", vp), ("scale_ld", ctypes.c_longlong),
+                ("d_obj", vp), ("d_cls", vp), ("d_counts", vp), ("h_counts", vp),
+                ("d_ws", vp), ("ws_bytes", ctypes.c_size_t)]
+
+
+SYM_ROWS_COUNTS = ("P", "S", "J", "T", "U", "max_row", "N", "rejected")     # the eight ints of cv_sym_rows_desc.d_counts
+
+
 class PointsFront(ctypes.Structure):
     """struct cv_points_front (include/cv_hip.h)"""
     _fields_ = [("d_raw_points", vp), ("m", ctypes.c_longlong), ("points_ld", ctypes.c_longlong), ("points_f64", ctypes.c_int),
@@ -266,6 +286,11 @@ SIGNATURES = {
     "cv_sym_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int]),
     "cv_sym_loss_chunk_rows": (ctypes.c_int, []),
     "cv_sizeof_sym_loss_desc": (ctypes.c_size_t, []),
+    "cv_sp_sym_rows_f32": (ctypes.c_int, [ctypes.POINTER(SymRowsDesc), vp]),
+    "cv_sp_sym_rows_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.c_int]),
+    "cv_sp_sym_rows_block": (ctypes.c_int, []),
+    "cv_sp_sym_rows_scan_span": (ctypes.c_longlong, []),
+    "cv_sizeof_sym_rows_desc": (ctypes.c_size_t, []),
     "cv_sp_morton_keys": (ctypes.c_int, [vp, ctypes.c_longlong, vp, vp]),
     "cv_sp_sort_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
     "cv_sp_sort_rows": (ctypes.c_int, [vp, ctypes.c_longlong, vp, vp, vp, vp, ctypes.c_size_t, vp]),

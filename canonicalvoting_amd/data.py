@@ -10,6 +10,8 @@ formats and is checked against the reference's own class on a miniature dataset 
 ``raw_item`` / ``collate_raw`` / ``device_batch`` are the same training batch with everything behind the two host
 transforms computed on the device.  ``collate_sym`` / ``SymBatch`` / ``sym_to_device`` are the
 per-category trainer's symmetry labels packed for the device loss, ``SyntheticSymDataset`` its synthetic items.
+``ScanNetXYZProbSymDataset.raw_item`` / ``collate_raw_sym`` / ``device_batch_sym`` build that trainer's batch on the device
+from raw scans.
 """
 import typing
 
@@ -461,6 +463,172 @@ class ScanNetXYZProbSymDataset(ScanNetXYZProbMultiDataset):
             xyz_labels.append([rows, xyzs])
         feats = np.concatenate([points, rgb], -1) if self.cfg.use_xyz else rgb
         return id_scan, coords, feats, xyz_labels, scale, obj, cls
+
+    def raw_item(self, index):
+        """``__getitem__`` up to and including ``points.astype(np.float32)``, as a RawSymScan: the same file checks, the same
+        redraw and the same draws from numpy's global generator in the same order (gain 3, shift 3, jitter M, randint(4),
+        random()); voxelisation, the survivor filter, the targets under every pose and the packing are left to
+        ``device_batch_sym``, as operands rather than results."""
+        import os
+        ann = self.annotations[index]
+        id_scan = ann["id_scan"]
+        if not np.all(np.abs(np.asarray(ann["trs"]["scale"]) - 1.0) < 1e-7):
+            raise ValueError("%s: scan transform has a non-unit scale" % id_scan)
+        path = os.path.join(self.cfg.data.scannet, "scans", id_scan, id_scan + "_vh_clean_2.ply")
+        if not os.path.exists(path):
+            raise FileNotFoundError(path + " does not exist.")
+        v = read_ply_vertices(path)
+        rgb = np.stack([v["red"], v["green"], v["blue"]], -1).astype(np.uint8, copy=False)
+        to_world = trs_matrix(ann["trs"]["translation"], ann["trs"]["rotation"], ann["trs"]["scale"])
+        points = transform_points(np.stack([v["x"], v["y"], v["z"]], -1), to_world)
+        for model, seg in zip(ann["aligned_models"], self.segments[id_scan]):
+            model["segments"] = seg
+        models = self._select(ann["aligned_models"])
+        if not models:
+            return self.raw_item(np.random.randint(len(self)))
+        aug, colour = np.eye(4), None
+        if self.augment:
+            if self.cfg.augment_color:                                   # the operands of __getitem__'s three in-place lines
+                colour = (1 + 0.4 * np.random.random(3) - 0.2, 0.1 * np.random.random(3) - 0.05,
+                          0.05 * np.random.random(points.shape[0]) - 0.025)
+            angle = np.random.randint(4) * np.pi / 2.0 + (np.random.random() - 0.5) * 2.0 * np.pi / 9.0
+            c, s = np.cos(angle), np.sin(angle)
+            Ry = np.array([[c, 0, -s], [0, 1, 0], [s, 0, c]])
+            points = points @ Ry.T
+            aug[:3, :3] = Ry
+        points = points.astype(np.float32)
+        n_vertex = points.shape[0]
+        owner = np.full(n_vertex, -1, np.int32)
+        minv, scale, cls, segs, vptr, pose_ptr = [], [], [], [], [0], [0]
+        for m in models:
+            s32 = np.asarray(m["trs"]["scale"], np.float32)
+            if s32.min() < 1e-3:                                         # singular annotation: not in the table
+                continue
+            seg = np.asarray(m["segments"], np.int64).reshape(-1)
+            if seg.size and (seg.min() < 0 or seg.max() >= n_vertex):
+                raise IndexError("%s: segment vertex %d outside the scan's %d vertices"
+                                 % (id_scan, int(seg.min() if seg.min() < 0 else seg.max()), n_vertex))
+            owner[seg] = len(cls)                                        # in model order: the last model wins a shared vertex
+            M = bbox_matrix(m)
+            poses = [M] + [M @ _roty4(a) for a in SYMMETRY_ANGLES.get(m["sym"], [])]
+            minv.extend(np.linalg.inv(aug @ P)[:3] for P in poses)
+            scale.append(s32 * np.asarray(m["bbox"], np.float32))
+            cls.append(self.class_index(m["catid_cad"]))
+            segs.append(seg.astype(np.int32))                            # as it lies: unsorted lists and duplicates are kept
+            vptr.append(vptr[-1] + seg.size)
+            pose_ptr.append(pose_ptr[-1] + len(poses))
+        return RawSymScan(id_scan, points, rgb, owner, np.asarray(scale, np.float32).reshape(-1, 3), np.asarray(cls, np.int32),
+                          np.concatenate(segs) if segs else np.zeros(0, np.int32), np.asarray(vptr, np.int32),
+                          np.asarray(pose_ptr, np.int32), np.asarray(minv, np.float64).reshape(-1, 3, 4), colour)
+
+
+class RawSymScan(typing.NamedTuple):
+    """One scan as ``ScanNetXYZProbSymDataset.raw_item`` leaves it: per vertex ``points`` f32 [M, 3], ``rgb`` uint8 [M, 3] and
+    ``owner`` int32 [M] (row of the model table, -1 = background; the last model wins a shared vertex); the table of the
+    non-singular models ``scale`` f32 [m, 3], ``cls`` int32 [m]; their segment vertex lists one after the other
+    ``seg_vertex`` int32 [Q] (list k = seg_vertex[seg_vptr[k]:seg_vptr[k + 1]], as they lie) with ``seg_vptr`` / ``pose_ptr``
+    int32 [m + 1]; ``minv`` f64 [J, 3, 4] = the top three rows of inv(aug @ P) of every (model, pose), model k's poses the
+    rows pose_ptr[k]:pose_ptr[k + 1] in ``__getitem__``'s pose order; ``colour`` None or (gain f64 [3], shift f64 [3],
+    jitter f64 [M]) for the 0..255 colours."""
+    id_scan: str
+    points: np.ndarray
+    rgb: np.ndarray
+    owner: np.ndarray
+    scale: np.ndarray
+    cls: np.ndarray
+    seg_vertex: np.ndarray
+    seg_vptr: np.ndarray
+    pose_ptr: np.ndarray
+    minv: np.ndarray
+    colour: typing.Optional[tuple]
+
+
+class RawSymBatch(typing.NamedTuple):
+    """``collate_raw_sym``'s result: the fields of the batch's RawSymScans one after the other as CPU tensors - ``owner``
+    counts rows of the concatenated model table, ``seg_vertex`` vertices of the concatenated clouds, ``seg_vptr`` /
+    ``pose_ptr`` int32 [S0 + 1] are prefix sums over the batch's S0 segments, ``seg_cloud`` int32 [S0] the cloud of every
+    segment, ``offsets`` int64 [B] the first vertex of every cloud, ``colour`` f64 [B, 6] (gain, shift) with ``jitter`` f64 [M] or
+    both None - and the upper bounds known on the host: ``n_cand`` = Q, ``n_jobs`` = J0, ``n_targets`` = T0 = the sum over the
+    segments of list length * poses."""
+    id_scans: tuple
+    points: torch.Tensor
+    rgb: torch.Tensor
+    owner: torch.Tensor
+    scale: torch.Tensor
+    cls: torch.Tensor
+    seg_vertex: torch.Tensor
+    seg_vptr: torch.Tensor
+    pose_ptr: torch.Tensor
+    minv: torch.Tensor
+    seg_cloud: torch.Tensor
+    colour: typing.Optional[torch.Tensor]
+    jitter: typing.Optional[torch.Tensor]
+    offsets: torch.Tensor
+    n_cand: int
+    n_jobs: int
+    n_targets: int
+
+
+def collate_raw_sym(batch):
+    """RawSymScans -> RawSymBatch (the ``collate_fn`` of the per-category trainer's device path; a tuple of tensors and host
+    ints, so DataLoader workers and ``pin_memory`` handle it).  Raises when M or T0 does not fit int32, and when only some
+    scans of the batch carry colour operands (the 0..255 clip has no identity operands)."""
+    cat = lambda arrays: torch.from_numpy(np.ascontiguousarray(np.concatenate(arrays, 0)))
+    sizes = [s.points.shape[0] for s in batch]
+    first_vertex = np.cumsum([0] + sizes[:-1]).astype(np.int64)
+    first_model = np.cumsum([0] + [s.cls.shape[0] for s in batch[:-1]])
+    lens = np.concatenate([np.diff(s.seg_vptr.astype(np.int64)) for s in batch])
+    poses = np.concatenate([np.diff(s.pose_ptr.astype(np.int64)) for s in batch])
+    n_targets = int((lens * poses).sum())
+    if sum(sizes) >= 2 ** 31 or n_targets >= 2 ** 31:
+        raise ValueError("collate_raw_sym: the batch does not fit int32 pointers (%d vertices, %d target rows)"
+                         % (sum(sizes), n_targets))
+    owner = [np.where(s.owner >= 0, s.owner + np.int32(f), np.int32(-1)).astype(np.int32) for s, f in zip(batch, first_model)]
+    with_colour = [s.colour is not None for s in batch]
+    if any(with_colour) != all(with_colour):
+        raise ValueError("collate_raw_sym: colour operands come for every scan of a batch or for none")
+    colour = jitter = None
+    if all(with_colour):
+        colour = torch.from_numpy(np.stack([np.concatenate(s.colour[:2]) for s in batch]).astype(np.float64))
+        jitter = cat([np.asarray(s.colour[2], np.float64) for s in batch])
+    prefix = lambda a: torch.from_numpy(np.concatenate([[0], np.cumsum(a)]).astype(np.int32))
+    return RawSymBatch(tuple(s.id_scan for s in batch), cat([s.points for s in batch]), cat([s.rgb for s in batch]), cat(owner),
+                       cat([s.scale for s in batch]), cat([s.cls for s in batch]),
+                       cat([(s.seg_vertex.astype(np.int64) + f).astype(np.int32) for s, f in zip(batch, first_vertex)]),
+                       prefix(lens), prefix(poses), cat([s.minv for s in batch]),
+                       torch.from_numpy(np.repeat(np.arange(len(batch)), [s.cls.shape[0] for s in batch]).astype(np.int32)),
+                       colour, jitter, torch.from_numpy(first_vertex), int(lens.sum()), int(poses.sum()), n_targets)
+
+
+def device_batch_sym(raw_batch, device, res, use_xyz=False, recentre=True, reference_indexing=True):
+    """A RawSymBatch -> ``(id_scans, coords4, feats, sym, scale, obj, cls)`` on ``device``: exactly what
+    ``collate_sym([ds[i] ...], reference_indexing)`` moved to the device (``sym_to_device``) gives, with the training script's
+    ``feats[:, -3:] * 2 - 1`` applied when ``recentre``.  On torch's current stream: non-blocking copies, the voxelisation
+    without its host wait (ME.utils.quantize_nowait), cv_sp_sym_rows_f32 on buffers of the host's upper bounds, then ONE host
+    wait that reads N, the rejected count, P, S, J, T, U and max_row from pinned memory; the outputs are slices of those
+    buffers.  Rejected points raise as ME.utils.quantize_device does."""
+    from . import _lib
+    b = raw_batch
+    dev = torch.device(device)
+    up = lambda t: None if t is None else t.to(dev, non_blocking=True)
+    points, rgb, owner, scale, cls, seg_vertex, seg_vptr, pose_ptr, minv, colour, jitter, offsets = (
+        up(t) for t in (b.points, b.rgb, b.owner, b.scale, b.cls, b.seg_vertex, b.seg_vptr, b.pose_ptr, b.minv, b.colour, b.jitter,
+                        b.offsets))
+    h_counts = torch.empty(8, dtype=torch.int32, pin_memory=True)
+    with torch.cuda.device(dev):
+        coords4, index, inverse, quant_counts = me_utils.quantize_nowait(points, res, b.offsets)
+        o = me_utils.sym_rows(coords4, index, inverse, quant_counts, points, rgb, owner, scale, cls, colour, jitter, offsets,
+                              seg_vertex, seg_vptr, pose_ptr, minv, b.n_targets, reference_indexing=reference_indexing,
+                              use_xyz=use_xyz, recentre=recentre, h_counts=h_counts)
+        torch.cuda.current_stream(dev).synchronize()                     # the batch's one host wait
+    c = dict(zip(_lib.SYM_ROWS_COUNTS, h_counts.tolist()))
+    if c["rejected"] != 0:
+        raise RuntimeError("sparse_quantize: %d points rejected (a non-finite component, or a voxel outside the supported "
+                           "window: spatial coordinates in [-32704, 32703])" % c["rejected"])
+    n, P, S, U = c["N"], c["P"], c["S"], c["U"]
+    sym = SymBatch(o["rows"][:P], o["pseg"][:P], o["seg_ptr"][:S + 1], o["pose_ptr"][:S + 1], o["tgt_ptr"][:S + 1],
+                   o["targets"][:c["T"]], o["urow"][:U], o["uptr"][:U + 1], o["upoint"][:P], S, c["J"], c["max_row"])
+    return b.id_scans, coords4[:n], o["feats"][:n], sym, o["scale"][:n], o["obj"][:n], o["cls"][:n]
 
 
 def collate_fn_separate(batch):

@@ -1,6 +1,7 @@
 """``ME.utils`` subset: batched_coordinates (train_joint.py:82), sparse_quantize
 (utils/dataloader.py:197, sunrgbd/brnetcanon.py:218; on the device: quantize_device / quantize_batch, voxel_rows for
-what a scene gathers behind it and scan_rows for what a training batch computes behind it), kaiming_normal_
+what a scene gathers behind it, scan_rows for what a training batch computes behind it, and quantize_nowait + sym_rows for
+the per-category trainer's batch with one host wait behind both), kaiming_normal_
 (utils/resnet.py:112); sym_loss, the per-category trainer's coordinate loss over packed symmetry labels
 (train_separate.py:265-280)."""
 import math
@@ -82,6 +83,37 @@ def quantize_device(points, quantization_size=None, offsets=None, return_inverse
         raise RuntimeError("sparse_quantize: %d points rejected (a non-finite component, or a voxel outside the supported "
                            "window: spatial coordinates in [-32704, 32703])" % rejected)
     return coords4[:n], index[:n], inverse
+
+
+def quantize_nowait(points, quantization_size, offsets):
+    """quantize_device's sibling WITHOUT the host wait (cv_sp_quantize_f32 with h_counts == NULL): float32 ``points`` [M, 3]
+    of the clouds whose first rows are ``offsets``, on torch's current stream.  Returns the full-size buffers
+    (coords4 [M, 4], index [M], inverse [M], counts [2] = (N, rejected points)), all int32 on the device: only the first N rows
+    of coords4 / index are written, and nothing has been checked - the caller reads ``counts`` behind its own wait and treats
+    rejected points as quantize_device does."""
+    import ctypes
+
+    from .. import _lib
+    L = _lib.lib()
+    assert points.is_cuda and points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 3 \
+        and points.stride(1) == 1 and points.stride(0) >= 3, "points: a float32 [M, 3] device tensor"
+    dev, m = points.device, points.shape[0]
+    if m == 0:
+        raise RuntimeError("sparse_quantize: empty point cloud")
+    offsets = [int(o) for o in (offsets.tolist() if hasattr(offsets, "tolist") else offsets)]
+    h_off = (ctypes.c_int64 * len(offsets))(*offsets)
+    coords4 = torch.empty((m, 4), dtype=torch.int32, device=dev)
+    index = torch.empty(m, dtype=torch.int32, device=dev)
+    inverse = torch.empty(m, dtype=torch.int32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    ws = _lib.scratch(dev, "quantize", int(L.cv_sp_quantize_workspace_bytes(m)))
+    vp = ctypes.c_void_p
+    with torch.cuda.device(dev):
+        stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
+        _lib.check(L.cv_sp_quantize_f32(vp(points.data_ptr()), m, points.stride(0), float(np.float32(quantization_size)), 0, h_off,
+                                        len(offsets), vp(coords4.data_ptr()), vp(index.data_ptr()), vp(inverse.data_ptr()),
+                                        vp(counts.data_ptr()), None, vp(ws.data_ptr()), ws.numel(), stream), "cv_sp_quantize_f32")
+    return coords4, index, inverse, counts
 
 
 def quantize_batch(clouds, quantization_size, return_inverse=False, offsets=None):
@@ -209,6 +241,65 @@ def scan_rows(coords4, index, points, rgb, owner, minv, scale, cls, colour=None,
         stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
         _lib.check(L.cv_sp_scan_rows_f32(ctypes.byref(d), stream), "cv_sp_scan_rows_f32")
     return tuple(dst)
+
+
+def sym_rows(coords4, index, inverse, quant_counts, points, rgb, owner, scale, cls, colour, jitter, offsets, seg_vertex, seg_vptr,
+             pose_ptr, minv, n_targets, reference_indexing=True, use_xyz=False, recentre=False, h_counts=None):
+    """The per-category trainer's batch behind quantize_nowait, on torch's current stream and without a host wait
+    (cv_sp_sym_rows_f32): packed symmetry labels and the row arrays into buffers of the host's upper bounds.
+
+    coords4 / index / inverse / quant_counts as quantize_nowait returns them; per raw vertex points [M, 3] float32 (row stride
+    >= 3), rgb [M, 3] uint8, owner [M] int32; model table scale [m, 3] float32, cls [m] int32; colour [B, 6] float64 with
+    jitter [M] float64, both or neither; offsets [B] int64 (device); the segments' vertex lists seg_vertex [Q] int32 with
+    seg_vptr / pose_ptr [S0 + 1] int32 and minv [J0, 3, 4] float64; n_targets: the bound T0 = sum of list length * poses.
+    h_counts: a pinned int32 [8] tensor that receives the counts by a copy on the stream, or None.
+    Returns a dict of the upper-bound buffers: rows, pseg, urow, upoint [Q], uptr [Q + 1], seg_ptr, pose_ptr, tgt_ptr
+    [S0 + 1], targets [T0, 3], feats [M, 3|6], scale [M, 3], obj, cls [M] int64, counts int32 [8] (_lib.SYM_ROWS_COUNTS)."""
+    import ctypes
+
+    from .. import _lib
+    L = _lib.lib()
+    dev, m, q, s0, j0 = index.device, points.shape[0], seg_vertex.shape[0], seg_vptr.shape[0] - 1, minv.shape[0]
+    i32c = lambda t, shape: t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev
+    assert i32c(coords4, (m, 4)) and i32c(index, (m,)) and i32c(inverse, (m,)) and i32c(quant_counts, (2,)), \
+        "coords4 / index / inverse / counts: quantize_nowait's full-size int32 buffers"
+    assert points.dtype == torch.float32 and points.shape == (m, 3) and points.stride(1) == 1, "points: float32 [M, 3]"
+    assert rgb.dtype == torch.uint8 and rgb.shape == (m, 3) and rgb.is_contiguous(), "rgb: contiguous uint8 [M, 3]"
+    assert i32c(owner, (m,)), "owner: contiguous int32 [M]"
+    k = cls.shape[0]
+    assert scale.dtype == torch.float32 and scale.shape == (k, 3) and scale.is_contiguous() and i32c(cls, (k,)), "model table"
+    if (colour is None) != (jitter is None):
+        raise ValueError("sym_rows: the colour table and the jitter come together")
+    n_clouds = offsets.shape[0]
+    assert offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.device == dev, "offsets: int64 [B] on the device"
+    if colour is not None:
+        assert colour.dtype == torch.float64 and colour.shape == (n_clouds, 6) and colour.is_contiguous(), "colour: float64 [B, 6]"
+        assert jitter.dtype == torch.float64 and jitter.shape == (m,) and jitter.is_contiguous(), "jitter: contiguous float64 [M]"
+    assert i32c(seg_vertex, (q,)) and i32c(seg_vptr, (s0 + 1,)) and i32c(pose_ptr, (s0 + 1,)), "segment lists: int32"
+    assert minv.dtype == torch.float64 and minv.shape == (j0, 3, 4) and minv.is_contiguous(), "minv: contiguous float64 [J0, 3, 4]"
+    if h_counts is not None:
+        assert h_counts.dtype == torch.int32 and h_counts.numel() == 8 and h_counts.is_pinned(), "h_counts: pinned int32 [8]"
+    t0 = int(n_targets)
+    new = lambda shape, dt=torch.int32: torch.empty(shape, dtype=dt, device=dev)
+    o = dict(rows=new(q), pseg=new(q), seg_ptr=new(s0 + 1), pose_ptr=new(s0 + 1), tgt_ptr=new(s0 + 1),
+             targets=new((t0, 3), torch.float32), urow=new(q), uptr=new(q + 1), upoint=new(q),
+             feats=new((m, 6 if use_xyz else 3), torch.float32), scale=new((m, 3), torch.float32), obj=new(m, torch.int64),
+             cls=new(m, torch.int64), counts=new(8))
+    ws = _lib.scratch(dev, "sym_rows", int(L.cv_sp_sym_rows_workspace_bytes(m, q, s0, n_clouds)))
+    vp = ctypes.c_void_p
+    ptr = lambda t: vp(t.data_ptr()) if t is not None and t.numel() else None
+    d = _lib.SymRowsDesc(ptr(coords4), ptr(index), ptr(inverse), ptr(quant_counts), m, ptr(points), points.stride(0), ptr(rgb),
+                         ptr(owner), ptr(scale), ptr(cls), k, ptr(colour), ptr(jitter), ptr(offsets), n_clouds,
+                         ptr(seg_vertex), q, ptr(seg_vptr), ptr(pose_ptr), s0, ptr(minv), j0, t0,
+                         int(bool(reference_indexing)), int(bool(use_xyz)), int(bool(recentre)),
+                         ptr(o["rows"]), ptr(o["pseg"]), ptr(o["seg_ptr"]), ptr(o["pose_ptr"]), ptr(o["tgt_ptr"]), ptr(o["targets"]),
+                         ptr(o["urow"]), ptr(o["uptr"]), ptr(o["upoint"]), ptr(o["feats"]), o["feats"].stride(0),
+                         ptr(o["scale"]), 3, ptr(o["obj"]), ptr(o["cls"]), ptr(o["counts"]), ptr(h_counts),
+                         vp(ws.data_ptr()), ws.numel())
+    with torch.cuda.device(dev):
+        stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
+        _lib.check(L.cv_sp_sym_rows_f32(ctypes.byref(d), stream), "cv_sp_sym_rows_f32")
+    return o
 
 
 def _sym_desc(out_feats, sym, weights, xyz_factor):

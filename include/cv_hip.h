@@ -50,7 +50,10 @@ extern "C" {
  *    (additive: no struct or signature moved).
  *    Still 6: cv_sym_loss_fwd_f32 / cv_sym_loss_bwd_f32 (cv_sym_loss_desc) with cv_sym_loss_workspace_bytes,
  *    cv_sym_loss_chunk_rows and cv_sizeof_sym_loss_desc, the separate-model coordinate loss over packed symmetry labels
- *    (additive: no struct or signature moved). */
+ *    (additive: no struct or signature moved).
+ *    Still 6: cv_sp_sym_rows_f32 (cv_sym_rows_desc) with cv_sp_sym_rows_workspace_bytes, cv_sp_sym_rows_block,
+ *    cv_sp_sym_rows_scan_span and cv_sizeof_sym_rows_desc, the separate-model training batch (packed symmetry labels and row
+ *    arrays) from raw scans (additive: no struct or signature moved). */
 #define CV_ABI_VERSION 6
 int cv_abi_version(void);
 const char* cv_last_error(void);
@@ -359,6 +362,73 @@ int cv_sym_loss_fwd_f32(const cv_sym_loss_desc* desc, void* stream);
 int cv_sym_loss_bwd_f32(const cv_sym_loss_desc* desc, void* stream);
 size_t cv_sym_loss_workspace_bytes(long long n_targets, int n_jobs);
 int cv_sym_loss_chunk_rows(void);           /* rows per workgroup of the partial pass: the chunking the sums are ordered by */
+
+/* The per-category trainer's batch from raw scans, behind the voxeliser and with NO host wait in front: the packed symmetry
+ * labels cv_sym_loss_* consume (data.SymBatch) and the per-row arrays, from raw per-vertex arrays plus per-model vertex
+ * lists - what ScanNetXYZProbSymDataset.__getitem__ (utils/dataloader.py:339-476) and data.pack_sym compute on the host.
+ * The voxeliser ran with d_inverse and h_counts == NULL; N is read on the device from d_quant_counts[0].
+ * Candidates: d_seg_vertex [n_cand] = the vertex lists of the batch's n_seg_in segments (one aligned model of one scan, batch
+ * order) one after the other, list s = [d_seg_vptr[s], d_seg_vptr[s + 1]); its poses are the jobs [d_seg_pose_ptr[s],
+ * d_seg_pose_ptr[s + 1]) of d_minv [n_jobs_in][3][4] fp64.  Both pointer arrays are prefix sums (first entry 0, last entries
+ * n_cand and n_jobs_in) - a precondition, like the vertices lying in [0, m_points) (a vertex outside is dropped).
+ *   1 survivors  candidate q with v = seg_vertex[q] survives iff r = inverse[v] >= 0 and index[r] == v (v is the first point
+ *                of its voxel).  Kept candidates are compacted by an ordered scan: segment order, list order, duplicates kept.
+ *   2 segments   len_s = kept candidates of segment s; segments with len_s == 0 are dropped, the others renumbered in order.
+ *                seg_ptr / pose_ptr / tgt_ptr [S + 1] = prefix sums over the kept segments of len, n_pose and len * n_pose;
+ *                pseg[p] = new segment of kept point p; rows[p] = r, minus the first row of the point's cloud when
+ *                reference_indexing != 0 (rows of a cloud are contiguous: the first row of cloud b is the lower bound of
+ *                d_offsets[b] in the ascending d_index).
+ *   3 targets    kept segment s, pose j, point i, (x, y, z) = d_points[v], m = d_minv[job]:
+ *                targets[tgt_ptr[s] + j * len_s + i][r] = (float)(((m[r][0] * x + m[r][1] * y) + m[r][2] * z) + m[r][3])
+ *                in fp64, this order, no fused multiply-add.
+ *   4 inverse    urow [U] = the distinct rows ascending, uptr [U + 1] their prefix, upoint [P] the points of each row in
+ *                ascending point index (np.argsort(rows, kind="stable") / np.unique(rows, return_counts=True)).  Rows are
+ *                counted with integer atomics, a row's points are placed by an atomic slot and then SORTED by one lane per
+ *                row (insertion sort: quadratic in the multiplicity of a row, meant for the handful of overlapping models
+ *                and scans that share a row).
+ *   5 rows       for the N kept rows, v = index[i], b = coords4[i][0], o = owner[v] (outside [0, n_models): background):
+ *                colour k without d_colour: c = (float)((double)rgb[v][k] / 255.0); with d_colour [n_clouds][6] (gain, shift)
+ *                and d_jitter [m_points]: t = (double)rgb[v][k]; t = t * gain[b][k]; t = t + shift[b][k]; t = t + jitter[v];
+ *                t = min(max(t, 0), 1); c = (float)(t / 255.0) - fp64 throughout, one rounding.  recentre != 0: c * 2.0f -
+ *                1.0f.  use_xyz != 0: the row's three d_points words first (width 6, else 3).  scale = d_model_scale[o] or 0,
+ *                obj = (o >= 0) and cls = d_model_cls[o] or 0, both int64.
+ *   6 counts     d_counts int32[8] = P, S, J, T, U, max_row (urow[U - 1], -1 when U == 0), N, rejected points - and the same
+ *                eight ints to h_counts (PINNED host memory, or NULL) by a copy on the stream; valid once the stream's work
+ *                up to this call has completed.  Without a kept segment S = P = J = T = U = 0 and max_row = -1; the row
+ *                arrays are still written.
+ * Output buffers hold the host's upper bounds: rows / pseg / urow / upoint [n_cand], uptr [n_cand + 1], seg_ptr / pose_ptr /
+ * tgt_ptr [n_seg_in + 1], targets [n_targets_in][3] with n_targets_in >= sum of list length * n_pose, the row arrays
+ * [m_points] rows (strides in elements).  Only the counted prefixes are written.  Arrays of a zero bound may be NULL.
+ * d_ws: cv_sp_sym_rows_workspace_bytes(m_points, n_cand, n_seg_in, n_clouds), else CV_ENOMEM.
+ * Every sum is an ordered scan or an integer count: the outputs are the same bytes on every run and stream.
+ * Every argument is validated before anything is launched.  No host wait; asynchronous on `stream`. */
+typedef struct cv_sym_rows_desc {
+    const int32_t* d_coords4; const int32_t* d_index; const int32_t* d_inverse;   /* as cv_sp_quantize_* wrote them, [m_points] rows */
+    const int32_t* d_quant_counts;                                                  /* its d_counts: [0] = N, [1] = rejected */
+    long long m_points;
+    const float* d_points; long long points_ld;
+    const uint8_t* d_rgb;
+    const int32_t* d_owner;
+    const float* d_model_scale; const int32_t* d_model_cls; int n_models;
+    const double* d_colour; const double* d_jitter;
+    const long long* d_offsets; int n_clouds;                                       /* device: first vertex of every cloud */
+    const int32_t* d_seg_vertex; long long n_cand;
+    const int32_t* d_seg_vptr; const int32_t* d_seg_pose_ptr; int n_seg_in;
+    const double* d_minv; long long n_jobs_in;
+    long long n_targets_in;
+    int reference_indexing, use_xyz, recentre;
+    int32_t* d_rows; int32_t* d_pseg; int32_t* d_seg_ptr; int32_t* d_pose_ptr; int32_t* d_tgt_ptr; float* d_targets;
+    int32_t* d_urow; int32_t* d_uptr; int32_t* d_upoint;
+    float* d_feats; long long feats_ld;
+    float* d_scale; long long scale_ld;
+    long long* d_obj; long long* d_cls;
+    int32_t* d_counts; int32_t* h_counts;
+    void* d_ws; size_t ws_bytes;
+} cv_sym_rows_desc;
+int cv_sp_sym_rows_f32(const cv_sym_rows_desc* desc, void* stream);
+size_t cv_sp_sym_rows_workspace_bytes(long long m_points, long long n_cand, int n_seg_in, int n_clouds);
+int cv_sp_sym_rows_block(void);             /* candidates per workgroup of the candidate passes (first level of their scan) */
+long long cv_sp_sym_rows_scan_span(void);   /* candidates one trip of the second scan level covers: beyond it, a second trip */
 
 /* Spatial row order of a coordinate set (what the fused network runs on; replaces the sort of Morton keys by the
  * caller): stable sort on (batch index, Z-order of the 2^shift cubes), rows of one cube in the caller's order.
@@ -944,6 +1014,7 @@ int cv_detect_points_separate_f32(const cv_points_separate_desc* desc, cv_points
 size_t cv_sizeof_gather_job(void);
 size_t cv_sizeof_scan_rows_desc(void);
 size_t cv_sizeof_sym_loss_desc(void);
+size_t cv_sizeof_sym_rows_desc(void);
 size_t cv_sizeof_points_desc(void);
 size_t cv_sizeof_points_separate_desc(void);
 size_t cv_sizeof_points_result(void);

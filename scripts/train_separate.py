@@ -6,6 +6,11 @@ one process per GPU with DDP when launched through torch.distributed.run (the re
 
     python scripts/train_separate.py [--epochs 2] [--scenes 6] [--points 20000] [--batch 3]        # synthetic scenes
     python scripts/train_separate.py --config config.yaml --category 03001627                       # ScanNet / Scan2CAD files
+    python scripts/train_separate.py --config config.yaml --category 03001627 --device-loader       # batches built on the device
+
+--device-loader: the DataLoader workers stop at the raw scan (ScanNetXYZProbSymDataset.raw_item / collate_raw_sym) and
+data.device_batch_sym voxelises, filters the models' points, evaluates the targets of every pose and packs the labels on the
+device - the same bits as the default path, one host wait per batch.
 
 The reference's validation every 10 epochs is not repeated here: scripts/eval_separate.py evaluates the saved models.
 """
@@ -20,7 +25,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from canonicalvoting_amd import dist as cvd  # noqa: E402
 from canonicalvoting_amd import train  # noqa: E402
-from canonicalvoting_amd.data import ScanNetXYZProbSymDataset, SyntheticSymDataset, collate_sym, load_config, sym_to_device  # noqa: E402
+from canonicalvoting_amd.data import (ScanNetXYZProbSymDataset, SyntheticSymDataset, collate_raw_sym, collate_sym,  # noqa: E402
+                                      device_batch_sym, load_config, sym_to_device)
 from canonicalvoting_amd.minkunet import MinkUNet34C  # noqa: E402
 
 
@@ -31,6 +37,27 @@ def device_batches(loader, dev):
         feats[:, -3:] = feats[:, -3:] * 2.0 - 1.0                         # train_separate.py:242-243: colour columns only
         yield (coords.to(dev, non_blocking=True), feats, sym_to_device(sym, dev), scale.to(dev, non_blocking=True),
                obj.to(dev, non_blocking=True))
+
+
+class RawSymItems(torch.utils.data.Dataset):
+    """the dataset's raw scans: what the workers of --device-loader produce"""
+
+    def __init__(self, ds):
+        self.ds = ds
+
+    def __len__(self):
+        return len(self.ds)
+
+    def __getitem__(self, index):
+        return self.ds.raw_item(index)
+
+
+def device_loader_batches(loader, dev, cfg, reference_indexing):
+    """--device-loader: RawSymBatches -> the tuples of device_batches, built on the device (colour columns recentred there)"""
+    for raw in loader:
+        _, coords, feats, sym, scale, obj, _ = device_batch_sym(raw, dev, cfg.scannet_res, use_xyz=bool(cfg.use_xyz), recentre=True,
+                                                                reference_indexing=reference_indexing)
+        yield coords, feats, sym, scale, obj
 
 
 def main():
@@ -45,7 +72,12 @@ def main():
     ap.add_argument("--repaired-indexing", action="store_true",
                     help="offset the label rows of scan j by the rows of the scans in front (the reference indexes the batch "
                          "output with each scan's own row numbers, train_separate.py:270)")
+    ap.add_argument("--device-loader", action="store_true",
+                    help="with --config: workers read raw scans, the batch is built on the device (data.device_batch_sym)")
     a = ap.parse_args()
+    if a.device_loader and not a.config:
+        ap.error("--device-loader needs --config: the synthetic scenes (SyntheticSymDataset) are generated as finished items "
+                 "and have no raw-scan form")
     if a.category and not a.config:
         ap.error("--category needs --config (synthetic scenes have no categories)")
     cfg = None
@@ -75,8 +107,10 @@ def main():
     if cfg:
         ds = ScanNetXYZProbSymDataset(cfg, training=True, augment=cfg.augment)
         sampler = torch.utils.data.distributed.DistributedSampler(ds, world, rank, shuffle=True) if world > 1 else None
-        loader = torch.utils.data.DataLoader(ds, batch_size=cfg.batch_size, shuffle=sampler is None, sampler=sampler,
-                                             collate_fn=collate, drop_last=True, num_workers=cfg.num_workers, pin_memory=True)
+        loader = torch.utils.data.DataLoader(RawSymItems(ds) if a.device_loader else ds, batch_size=cfg.batch_size,
+                                             shuffle=sampler is None, sampler=sampler,
+                                             collate_fn=collate_raw_sym if a.device_loader else collate, drop_last=True,
+                                             num_workers=cfg.num_workers, pin_memory=True)
     else:
         ds = SyntheticSymDataset(a.scenes, a.points, seed0=1000 * rank)       # every rank owns its scenes
         loader = torch.utils.data.DataLoader(ds, batch_size=a.batch, shuffle=True, collate_fn=collate, drop_last=True)
@@ -85,7 +119,8 @@ def main():
         train.set_bn_momentum(model, train.bn_momentum(epoch, bn_step, bn_rate))   # train_separate.py:216-217,230
         net.train()
         t0, losses = time.perf_counter(), []
-        for batch in device_batches(loader, dev):
+        batches = device_loader_batches(loader, dev, cfg, not a.repaired_indexing) if a.device_loader else device_batches(loader, dev)
+        for batch in batches:
             res = train.train_step_separate(net, opt, *batch, **loss_kw)
             if res is not None:                                             # train_separate.py:238-240: no object, no step
                 losses.append(res[0])
