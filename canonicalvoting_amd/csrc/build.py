@@ -38,8 +38,7 @@ def _sources():
         "hv_vote.hip": STRICT + env("CV_HV_DEFS"),       # extra -D flags of an experiment (the file reads none today)
         "hv_decode.hip": STRICT + env("CV_DEC_DEFS"),    # extra -D flags of an experiment (the file reads none today)
         "sparse_coords.hip": [],
-        "scan_rows.hip": STRICT,                         # training batch from raw scans: the host's fp64 label bits
-        "sym_rows.hip": STRICT,                          # separate-model batch from raw scans: the host's fp64 target bits
+        "train_rows.hip": STRICT,                        # training batches from raw scans: the host's fp64 label and target bits
         "sym_loss.hip": STRICT,                          # separate-model pose loss: fp64 sums in the order written
         "sparse_conv.hip": env("CV_SC_DEFS"),            # kernel experiments (-DCV_WP_NPRE=27)
         "sparse_train.hip": [],                          # the training side: reads none of the CV_SC_DEFS switches

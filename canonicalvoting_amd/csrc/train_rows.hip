@@ -1,5 +1,16 @@
-// Separate-model training batch from raw scans (cv_sp_sym_rows_f32): packed symmetry labels (data.SymBatch, what cv_sym_loss_*
-// consume) and the per-row arrays, from the voxeliser's outputs, the raw per-vertex arrays and the per-model vertex lists - what
+// Training batches from raw scans, behind the voxeliser: the row arrays of both trainers, and the packed symmetry labels.
+//
+// cv_sp_scan_rows_f32 (joint trainer): the features and the three label arrays of the kept rows of a voxelised batch, computed
+// per row from the raw per-vertex arrays - what ScanNetXYZProbMultiDataset.__getitem__ (utils/dataloader.py:118-210) computes
+// for EVERY vertex on the host and then gathers by the first-point index.  ONE launch, scan_rows.
+//
+// Row-array kernels (scan_rows, sym_row_arrays) are laid out like voxel_rows (sparse_coords.hip, section 7): every output owns
+// a range of workgroups that strides over its n * width elements, so adjacent lanes write adjacent destination words.  The
+// model table ([n_models] x (12 fp64 + 3 fp32 + 1 int32)) and the colour table ([n_clouds][6] fp64) are a few hundred bytes and
+// stay in cache; the per-vertex reads follow `index`, which ascends.  About 100 B per row: the launch is bound by its latency.
+//
+// cv_sp_sym_rows_f32 (separate-model trainer): packed symmetry labels (data.SymBatch, what cv_sym_loss_* consume) and the
+// per-row arrays, from the voxeliser's outputs, the raw per-vertex arrays and the per-model vertex lists - what
 // ScanNetXYZProbSymDataset.__getitem__ (utils/dataloader.py:339-476) and data.pack_sym compute on the host.  No count is
 // known to the host: every launch is sized by the host's upper bounds and reads N, P, S, T, U from device words.
 //
@@ -13,20 +24,166 @@
 //   row_sums / row_top / row_emit   two-level scan over the row counters: urow, uptr, U, max_row; counter := first slot.
 //   upoint_fill    point p takes a slot of its row (atomic: any order), upoint_sort: one lane per row sorts its slots ascending
 //                  (insertion sort, quadratic in the row's multiplicity - see cv_hip.h) - the result is the stable order.
-//   sym_row_arrays feats / scale / obj / cls of the N kept rows, laid out like scan_rows: every output owns a range of
-//                  workgroups that strides over its elements.
+//   sym_row_arrays feats / scale / obj / cls of the N kept rows.
 //
-// Built with -ffp-contract=off (csrc/build.py STRICT): targets and colours are the fp64 expressions of cv_hip.h as written.
+// Built with -ffp-contract=off (csrc/build.py STRICT): labels, targets and colours are the expressions of cv_hip.h as written.
 #include "cv_common.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int BLOCK = 256;                          // candidates (and row counters) per workgroup: first scan level
+constexpr int BLOCK = 256;                          // threads per workgroup; candidates (and row counters) per first scan level
 constexpr int SCAN_WIDTH = 1024;                    // block sums per trip of the one-workgroup second level
-constexpr int MAX_BLOCKS = 512;                     // per output of the strided kernels
+constexpr int MAX_BLOCKS = 512;                     // per output of the strided kernels: 131072 threads, then the loops stride
 enum { C_P = 0, C_S, C_J, C_T, C_U, C_MAXROW, C_N, C_REJECTED };
+
+// ---- what the two row-array kernels share ------------------------------------------------------------------------------
+
+// four outputs in one launch: output s owns the workgroups [block_begin[s], block_begin[s + 1])
+struct RowPartition {
+    int block_begin[5];
+};
+
+RowPartition partition_rows(const long long (&elems)[4], int min_blocks) {
+    RowPartition p;
+    int total = 0;
+    for (int s = 0; s < 4; ++s) {
+        p.block_begin[s] = total;
+        total += (int)std::max<long long>(min_blocks, std::min<long long>((elems[s] + BLOCK - 1) / BLOCK, MAX_BLOCKS));
+    }
+    p.block_begin[4] = total;
+    return p;
+}
+
+// this thread's output, its first element there and its step
+__device__ __forceinline__ int row_output(const RowPartition& p, long long* first, long long* step) {
+    int s = 0;
+    while (s < 3 && (int)blockIdx.x >= p.block_begin[s + 1]) ++s;
+    const int nb = p.block_begin[s + 1] - p.block_begin[s], blk = blockIdx.x - p.block_begin[s];
+    *first = (long long)blk * BLOCK + threadIdx.x;
+    *step = (long long)nb * BLOCK;
+    return s;
+}
+
+// the model of a raw vertex: a row of the model table, or -1 (background; also what an owner outside the table reads as)
+template <class Desc>
+__device__ __forceinline__ int model_of(const Desc& d, int v) {
+    const int o = d.d_owner[v];
+    return (unsigned)o < (unsigned)d.n_models ? o : -1;
+}
+
+// row m[0..3] of a world -> unit cube matrix applied to the point p, in fp64: this order, no fused multiply-add
+__device__ __forceinline__ float label_transform(const double* m, const float* p) {
+    const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
+    return (float)(((m[0] * x + m[1] * y) + m[2] * z) + m[3]);
+}
+
+// The two trainers' colours: raw = rgb[v][k], g = the cloud's (gain, shift) row of the colour table or NULL, jitter = jitter[v].
+// Joint: c = (float)((double)rgb[v][k] / 255.0); with a colour table, c = (float)((double)c * colour[b][k]),
+// c = (float)((double)c + colour[b][3 + k]), c = (float)((double)c + jitter[v]), then clamped to [0, 1] - every step rounds to
+// fp32, as numpy's in-place `float32 op= float64` does.
+__device__ __forceinline__ float colour_joint(unsigned char raw, const double* g, int k, double jitter) {
+    float x = (float)((double)raw / 255.0);
+    if (g) {
+        x = (float)((double)x * g[k]);
+        x = (float)((double)x + g[3 + k]);
+        x = (float)((double)x + jitter);
+        x = fminf(fmaxf(x, 0.0f), 1.0f);
+    }
+    return x;
+}
+
+// Separate: without a table c = (float)((double)rgb[v][k] / 255.0); with one, t = (double)rgb[v][k]; t = t * gain[b][k];
+// t = t + shift[b][k]; t = t + jitter[v]; t = min(max(t, 0), 1); c = (float)(t / 255.0) - fp64 throughout, one rounding.
+__device__ __forceinline__ float colour_separate(unsigned char raw, const double* g, int k, double jitter) {
+    double t = (double)raw;
+    if (g) {
+        t = t * g[k];
+        t = t + g[3 + k];
+        t = t + jitter;
+        t = fmin(fmax(t, 0.0), 1.0);
+    }
+    return (float)(t / 255.0);
+}
+
+// feats of the n kept rows: fw = 3 colour columns, or 6 with the row's point in front; recentre: colours as c * 2.0f - 1.0f
+template <float (*COLOUR)(unsigned char, const double*, int, double), class Desc>
+__device__ __forceinline__ void feature_rows(const Desc& d, long long n, int fw, long long first, long long step) {
+    const int c0 = fw - 3;                          // colour columns: [c0, fw)
+    for (long long e = first; e < n * fw; e += step) {
+        const long long i = e / fw;
+        const int c = (int)(e - i * fw);
+        const long long v = d.d_index[i];
+        float x;
+        if (c < c0) {
+            x = d.d_points[v * d.points_ld + c];
+        } else {
+            const double* g = nullptr;
+            double jitter = 0.0;
+            if (d.d_colour) {
+                const int b = d.d_coords4[4 * i];
+                g = d.d_colour + 6ll * ((unsigned)b < (unsigned)d.n_clouds ? b : 0);
+                jitter = d.d_jitter[v];
+            }
+            x = COLOUR(d.d_rgb[v * 3 + (c - c0)], g, c - c0, jitter);
+            if (d.recentre) x = x * 2.0f - 1.0f;
+        }
+        d.d_feats[i * d.feats_ld + c] = x;
+    }
+}
+
+// scale of the n kept rows: the model's, background 0
+template <class Desc>
+__device__ __forceinline__ void scale_rows(const Desc& d, long long n, long long first, long long step) {
+    for (long long e = first; e < n * 3; e += step) {
+        const long long i = e / 3;
+        const int r = (int)(e - i * 3);
+        const int o = model_of(d, d.d_index[i]);
+        d.d_scale[i * d.scale_ld + r] = o >= 0 ? d.d_model_scale[3ll * o + r] : 0.0f;
+    }
+}
+
+// class of the n kept rows, widened to int64: the model's, or `background`
+template <class Desc>
+__device__ __forceinline__ void class_rows(const Desc& d, long long n, long long background, long long ld, long long first,
+                                           long long step) {
+    for (long long i = first; i < n; i += step) {
+        const int o = model_of(d, d.d_index[i]);
+        d.d_cls[i * ld] = o >= 0 ? (long long)d.d_model_cls[o] : background;
+    }
+}
+
+// ---- cv_sp_scan_rows_f32 -----------------------------------------------------------------------------------------------
+
+struct ScanRowsDev {
+    cv_scan_rows_desc d;
+    int fw;                                         // feature width: 3, or 6 with use_xyz
+    RowPartition part;                              // feats, xyz, scale, cls
+};
+
+__global__ __launch_bounds__(BLOCK) void scan_rows(const ScanRowsDev a) {
+    const cv_scan_rows_desc& d = a.d;
+    long long first, step;
+    const int s = row_output(a.part, &first, &step);
+    if (s == 0) {
+        feature_rows<colour_joint>(d, d.n, a.fw, first, step);
+    } else if (s == 1) {
+        for (long long e = first; e < d.n * 3; e += step) {
+            const long long i = e / 3;
+            const int r = (int)(e - i * 3);
+            const long long v = d.d_index[i];
+            const int o = model_of(d, (int)v);
+            d.d_xyz[i * d.xyz_ld + r] = o >= 0 ? label_transform(d.d_minv + 12ll * o + 4 * r, d.d_points + v * d.points_ld) : 0.0f;
+        }
+    } else if (s == 2) {
+        scale_rows(d, d.n, first, step);
+    } else {
+        class_rows(d, d.n, 9, d.cls_ld, first, step);                    // background 9: utils/dataloader.py:166
+    }
+}
+
+// ---- cv_sp_sym_rows_f32 ------------------------------------------------------------------------------------------------
 
 struct SymWs {
     int* flag;        // [Q]
@@ -45,7 +202,7 @@ struct SymDev {
     cv_sym_rows_desc d;
     SymWs w;
     int fw;
-    int block_begin[5];                             // feats, scale, obj, cls
+    RowPartition part;                              // feats, scale, obj, cls
 };
 
 long long nblk(long long n) { return (n + BLOCK - 1) / BLOCK; }
@@ -218,10 +375,7 @@ __global__ __launch_bounds__(BLOCK) void sym_targets(const SymDev a) {
         const int k = t - d.d_tgt_ptr[lo], j = k / len, i = k - j * len;
         long long job = (long long)w.job0[lo] + j;
         job = job < 0 ? 0 : (job >= d.n_jobs_in ? d.n_jobs_in - 1 : job);
-        const double* m = d.d_minv + 12 * job + 4 * r;
-        const float* pt = d.d_points + (long long)w.kept_v[p0 + i] * d.points_ld;
-        const double x = (double)pt[0], y = (double)pt[1], z = (double)pt[2];
-        d.d_targets[e] = (float)(((m[0] * x + m[1] * y) + m[2] * z) + m[3]);
+        d.d_targets[e] = label_transform(d.d_minv + 12 * job + 4 * r, d.d_points + (long long)w.kept_v[p0 + i] * d.points_ld);
     }
 }
 
@@ -290,57 +444,19 @@ __global__ __launch_bounds__(BLOCK) void upoint_sort(const SymDev a) {
     }
 }
 
-__device__ __forceinline__ int model_of(const cv_sym_rows_desc& d, int v) {
-    const int o = d.d_owner[v];
-    return (unsigned)o < (unsigned)d.n_models ? o : -1;
-}
-
 __global__ __launch_bounds__(BLOCK) void sym_row_arrays(const SymDev a) {
     const cv_sym_rows_desc& d = a.d;
     const long long n = rows_n(d);
-    int s = 0;
-    while (s < 3 && (int)blockIdx.x >= a.block_begin[s + 1]) ++s;
-    const int nb = a.block_begin[s + 1] - a.block_begin[s], blk = blockIdx.x - a.block_begin[s];
-    const long long first = (long long)blk * BLOCK + threadIdx.x, step = (long long)nb * BLOCK;
+    long long first, step;
+    const int s = row_output(a.part, &first, &step);
     if (s == 0) {
-        const int fw = a.fw, c0 = fw - 3;
-        for (long long e = first; e < n * fw; e += step) {
-            const long long i = e / fw;
-            const int c = (int)(e - i * fw);
-            const long long v = d.d_index[i];
-            float x;
-            if (c < c0) {
-                x = d.d_points[v * d.points_ld + c];
-            } else {
-                const int k = c - c0;
-                double t = (double)d.d_rgb[v * 3 + k];
-                if (d.d_colour) {
-                    const int b = d.d_coords4[4 * i];
-                    const double* g = d.d_colour + 6ll * ((unsigned)b < (unsigned)d.n_clouds ? b : 0);
-                    t = t * g[k];
-                    t = t + g[3 + k];
-                    t = t + d.d_jitter[v];
-                    t = fmin(fmax(t, 0.0), 1.0);
-                }
-                x = (float)(t / 255.0);
-                if (d.recentre) x = x * 2.0f - 1.0f;
-            }
-            d.d_feats[i * d.feats_ld + c] = x;
-        }
+        feature_rows<colour_separate>(d, n, a.fw, first, step);
     } else if (s == 1) {
-        for (long long e = first; e < n * 3; e += step) {
-            const long long i = e / 3;
-            const int r = (int)(e - i * 3);
-            const int o = model_of(d, d.d_index[i]);
-            d.d_scale[i * d.scale_ld + r] = o >= 0 ? d.d_model_scale[3ll * o + r] : 0.0f;
-        }
+        scale_rows(d, n, first, step);
     } else if (s == 2) {
         for (long long i = first; i < n; i += step) d.d_obj[i] = model_of(d, d.d_index[i]) >= 0;
     } else {
-        for (long long i = first; i < n; i += step) {
-            const int o = model_of(d, d.d_index[i]);
-            d.d_cls[i] = o >= 0 ? (long long)d.d_model_cls[o] : 0;
-        }
+        class_rows(d, n, 0, 1, first, step);                             // background (and 'others') 0
     }
 }
 
@@ -366,6 +482,36 @@ int strided_blocks(long long elems) { return (int)std::max<long long>(1, std::mi
 }  // namespace
 
 extern "C" {
+
+int cv_sp_scan_rows_f32(const cv_scan_rows_desc* desc, void* stream) {
+    CV_REQUIRE(desc, CV_EINVAL, "null scan-rows descriptor");
+    const cv_scan_rows_desc& d = *desc;
+    CV_REQUIRE(d.n > 0 && d.n <= (1ll << 29), CV_EINVAL, "bad row count %lld", d.n);
+    CV_REQUIRE(d.m_points > 0 && d.m_points <= (1ll << 29), CV_EINVAL, "bad point count %lld", d.m_points);
+    CV_REQUIRE(d.n <= d.m_points, CV_EINVAL, "more kept rows (%lld) than points (%lld)", d.n, d.m_points);
+    CV_REQUIRE(d.n_models >= 0, CV_EINVAL, "bad model count %d", d.n_models);
+    CV_REQUIRE(d.n_clouds >= 1, CV_EINVAL, "bad cloud count %d", d.n_clouds);
+    CV_REQUIRE(d.d_coords4 && d.d_index && d.d_points && d.d_rgb && d.d_owner && d.d_feats && d.d_xyz && d.d_scale && d.d_cls,
+               CV_EINVAL, "null pointer argument");
+    CV_REQUIRE(d.n_models == 0 || (d.d_minv && d.d_model_scale && d.d_model_cls), CV_EINVAL,
+               "null pointer argument (model table of %d rows)", d.n_models);
+    CV_REQUIRE(!d.d_jitter || d.d_colour, CV_EINVAL, "jitter without a colour table");
+    CV_REQUIRE(!d.d_colour || d.d_jitter, CV_EINVAL, "colour table without jitter");
+    const int fw = d.use_xyz ? 6 : 3;
+    CV_REQUIRE(d.points_ld >= 3, CV_EINVAL, "row stride %lld of the points below 3", d.points_ld);
+    CV_REQUIRE(d.feats_ld >= fw && d.xyz_ld >= 3 && d.scale_ld >= 3 && d.cls_ld >= 1, CV_EINVAL,
+               "destination row stride below its width (feats %lld < %d, xyz %lld, scale %lld < 3, or cls %lld < 1)",
+               d.feats_ld, fw, d.xyz_ld, d.scale_ld, d.cls_ld);
+    ScanRowsDev a = {};
+    a.d = d;
+    a.fw = fw;
+    a.part = partition_rows({d.n * fw, d.n * 3, d.n * 3, d.n}, 0);
+    scan_rows<<<a.part.block_begin[4], BLOCK, 0, static_cast<hipStream_t>(stream)>>>(a);
+    CV_LAUNCH_CHECK();
+    return CV_OK;
+}
+
+size_t cv_sizeof_scan_rows_desc(void) { return sizeof(cv_scan_rows_desc); }
 
 size_t cv_sp_sym_rows_workspace_bytes(long long m_points, long long n_cand, int n_seg_in, int n_clouds) {
     if (m_points <= 0 || n_cand < 0 || n_seg_in < 0 || n_clouds < 1) return 0;
@@ -440,14 +586,8 @@ int cv_sp_sym_rows_f32(const cv_sym_rows_desc* desc, void* stream) {
         upoint_sort<<<strided_blocks(std::min(d.n_cand, d.m_points)), BLOCK, 0, st>>>(a);
         CV_LAUNCH_CHECK();
     }
-    const long long elems[4] = {d.m_points * fw, d.m_points * 3, d.m_points, d.m_points};
-    int total = 0;
-    for (int s = 0; s < 4; ++s) {
-        a.block_begin[s] = total;
-        total += strided_blocks(elems[s]);
-    }
-    a.block_begin[4] = total;
-    sym_row_arrays<<<total, BLOCK, 0, st>>>(a);
+    a.part = partition_rows({d.m_points * fw, d.m_points * 3, d.m_points, d.m_points}, 1);
+    sym_row_arrays<<<a.part.block_begin[4], BLOCK, 0, st>>>(a);
     CV_LAUNCH_CHECK();
     if (d.h_counts) CV_HIP_CHECK(hipMemcpyAsync(d.h_counts, d.d_counts, sizeof(int32_t) * 8, hipMemcpyDeviceToHost, st));
     return CV_OK;

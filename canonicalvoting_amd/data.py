@@ -11,7 +11,7 @@ formats and is checked against the reference's own class on a miniature dataset 
 transforms computed on the device.  ``collate_sym`` / ``SymBatch`` / ``sym_to_device`` are the
 per-category trainer's symmetry labels packed for the device loss, ``SyntheticSymDataset`` its synthetic items.
 ``ScanNetXYZProbSymDataset.raw_item`` / ``collate_raw_sym`` / ``device_batch_sym`` build that trainer's batch on the device
-from raw scans.
+from raw scans.  ``RawItems`` is the dataset view both device paths hand to their DataLoader workers.
 """
 import typing
 
@@ -184,6 +184,23 @@ def transform_points(pc, M):
     return (M @ np.concatenate([pc, np.ones((pc.shape[0], 1))], -1).T).T[:, :3]
 
 
+def _draw_augmentation(n_vertex, augment, augment_color):
+    """The augmentation draws from numpy's global generator, in the reference's order: gain 3, shift 3, jitter ``n_vertex``
+    (these three only with ``augment_color``), randint(4), random(); without ``augment`` nothing is drawn.  Returns ``(colour
+    operands (gain f64 [3], shift f64 [3], jitter f64 [n_vertex]) or None, Ry f64 [3, 3] about the up axis or None, aug f64
+    [4, 4])``."""
+    colour, Ry, aug = None, None, np.eye(4)
+    if augment:
+        if augment_color:
+            colour = (1 + 0.4 * np.random.random(3) - 0.2, 0.1 * np.random.random(3) - 0.05,
+                      0.05 * np.random.random(n_vertex) - 0.025)
+        angle = np.random.randint(4) * np.pi / 2.0 + (np.random.random() - 0.5) * 2.0 * np.pi / 9.0
+        c, s = np.cos(angle), np.sin(angle)
+        Ry = np.array([[c, 0, -s], [0, 1, 0], [s, 0, c]])
+        aug[:3, :3] = Ry
+    return colour, Ry, aug
+
+
 class ScanNetXYZProbMultiDataset(torch.utils.data.Dataset):
     """utils/dataloader.py:89-210.  ``cfg`` needs ``data.scan2cad`` (full_annotations.json), ``data.scannet`` (root with
     scans/<id>/<id>_vh_clean_2.ply), ``data.{train,val}_split`` (text, one scan id per line),
@@ -225,37 +242,77 @@ class ScanNetXYZProbMultiDataset(torch.utils.data.Dataset):
         with open(os.path.join(self.cfg.data.gt_path, self.annotations[index]["id_scan"] + ".txt")) as f:
             return parse_gt_lines(f.read().splitlines())
 
-    def __getitem__(self, index):
+    def _read_scan(self, index):
+        """What every item method starts with (utils/dataloader.py:118-150): ``(id_scan, rgb uint8 [M, 3], points f64 [M, 3]
+        in the world frame, the selected models with their ``segments`` attached)``.  A scan without a selected model draws
+        ``np.random.randint(len(self))`` - nothing else has been drawn by then - and the checks run again on that scan."""
         import os
-        ann = self.annotations[index]
-        id_scan = ann["id_scan"]
-        if not np.all(np.abs(np.asarray(ann["trs"]["scale"]) - 1.0) < 1e-7):
-            raise ValueError("%s: scan transform has a non-unit scale" % id_scan)
-        path = os.path.join(self.cfg.data.scannet, "scans", id_scan, id_scan + "_vh_clean_2.ply")
-        if not os.path.exists(path):
-            raise FileNotFoundError(path + " does not exist.")
-        v = read_ply_vertices(path)
-        rgb = (np.stack([v["red"], v["green"], v["blue"]], -1) / 255.0).astype(np.float32)
-        to_world = trs_matrix(ann["trs"]["translation"], ann["trs"]["rotation"], ann["trs"]["scale"])
-        points = transform_points(np.stack([v["x"], v["y"], v["z"]], -1), to_world)
-        for model, seg in zip(ann["aligned_models"], self.segments[id_scan]):
-            model["segments"] = seg
-        models = self._select(ann["aligned_models"])
-        if not models:
-            return self[np.random.randint(len(self))]
-        aug = np.eye(4)
-        if self.augment:
-            if self.cfg.augment_color:                                   # :156-160, float32 in place
-                rgb *= (1 + 0.4 * np.random.random(3) - 0.2)
-                rgb += (0.1 * np.random.random(3) - 0.05)
-                rgb += (0.05 * np.random.random(points.shape[0]) - 0.025)[:, None]
-                rgb = np.clip(rgb, 0, 1)
-            angle = np.random.randint(4) * np.pi / 2.0 + (np.random.random() - 0.5) * 2.0 * np.pi / 9.0
-            c, s = np.cos(angle), np.sin(angle)
-            Ry = np.array([[c, 0, -s], [0, 1, 0], [s, 0, c]])
-            points = points @ Ry.T
-            aug[:3, :3] = Ry
-        points = points.astype(np.float32)
+        while True:
+            ann = self.annotations[index]
+            id_scan = ann["id_scan"]
+            if not np.all(np.abs(np.asarray(ann["trs"]["scale"]) - 1.0) < 1e-7):
+                raise ValueError("%s: scan transform has a non-unit scale" % id_scan)
+            path = os.path.join(self.cfg.data.scannet, "scans", id_scan, id_scan + "_vh_clean_2.ply")
+            if not os.path.exists(path):
+                raise FileNotFoundError(path + " does not exist.")
+            v = read_ply_vertices(path)
+            rgb = np.stack([v["red"], v["green"], v["blue"]], -1).astype(np.uint8, copy=False)
+            to_world = trs_matrix(ann["trs"]["translation"], ann["trs"]["rotation"], ann["trs"]["scale"])
+            points = transform_points(np.stack([v["x"], v["y"], v["z"]], -1), to_world)
+            for model, seg in zip(ann["aligned_models"], self.segments[id_scan]):
+                model["segments"] = seg
+            models = self._select(ann["aligned_models"])
+            if models:
+                return id_scan, rgb, points, models
+            index = np.random.randint(len(self))
+
+    def _augmented_scan(self, index):
+        """``_read_scan``, then ``_draw_augmentation`` and what every item method does with it: ``(id_scan, rgb uint8 [M, 3],
+        points f32 [M, 3] rotated, models, colour operands or None, aug f64 [4, 4])`` - the scan up to and including the
+        reference's ``points.astype(np.float32)``.  Each trainer applies the colour operands in its own arithmetic."""
+        id_scan, rgb, points, models = self._read_scan(index)
+        colour, Ry, aug = _draw_augmentation(points.shape[0], self.augment, self.cfg.augment_color)
+        if Ry is not None:
+            points = points @ Ry.T               # (rebinding releases the fp64 world points before the cast allocates)
+        return id_scan, rgb, points.astype(np.float32), models, colour, aug
+
+    def _model_table(self, id_scan, models, aug, n_vertex, sym_poses=False):
+        """The table of the non-singular models, in model order: ``(owner int32 [M], minv f64 [J, 3, 4], scale f32 [m, 3],
+        cls int32 [m], segs, seg_vptr, pose_ptr)``.  ``owner`` is assigned in model order, so the last model wins a shared
+        vertex.  ``minv`` holds the top three rows of inv(aug @ P): one pose per model, or with ``sym_poses`` every
+        symmetry-equivalent pose (rows pose_ptr[k]:pose_ptr[k + 1]) - then ``segs`` are the models' vertex lists as int32,
+        as they lie, and a vertex outside the scan raises IndexError; without, numpy's own indexing holds."""
+        owner = np.full(n_vertex, -1, np.int32)
+        minv, scale, cls, segs, vptr, pose_ptr = [], [], [], [], [0], [0]
+        for m in models:
+            s32 = np.asarray(m["trs"]["scale"], np.float32)
+            if s32.min() < 1e-3:                                         # singular annotation (:171-172): not in the table
+                continue
+            seg, poses = m["segments"], [bbox_matrix(m)]
+            if sym_poses:
+                seg = np.asarray(seg, np.int64).reshape(-1)
+                if seg.size and (seg.min() < 0 or seg.max() >= n_vertex):
+                    raise IndexError("%s: segment vertex %d outside the scan's %d vertices"
+                                     % (id_scan, int(seg.min() if seg.min() < 0 else seg.max()), n_vertex))
+                poses += [poses[0] @ _roty4(a) for a in SYMMETRY_ANGLES.get(m["sym"], [])]
+                segs.append(seg.astype(np.int32))                        # unsorted lists and duplicates are kept
+                vptr.append(vptr[-1] + seg.size)
+            owner[seg] = len(cls)
+            minv.extend(np.linalg.inv(aug @ P)[:3] for P in poses)
+            scale.append(s32 * np.asarray(m["bbox"], np.float32))        # half extents in metres
+            cls.append(self.class_index(m["catid_cad"]))
+            pose_ptr.append(pose_ptr[-1] + len(poses))
+        return (owner, np.asarray(minv, np.float64).reshape(-1, 3, 4), np.asarray(scale, np.float32).reshape(-1, 3),
+                np.asarray(cls, np.int32), segs, np.asarray(vptr, np.int32), np.asarray(pose_ptr, np.int32))
+
+    def __getitem__(self, index):
+        id_scan, rgb, points, models, colour, aug = self._augmented_scan(index)
+        rgb = (rgb / 255.0).astype(np.float32)
+        if colour is not None:                                           # :156-160, float32 in place
+            rgb *= colour[0]
+            rgb += colour[1]
+            rgb += colour[2][:, None]
+            rgb = np.clip(rgb, 0, 1)
         n = points.shape[0]
         xyz = np.zeros((n, 3), np.float32)
         scale = np.zeros((n, 3), np.float32)
@@ -278,46 +335,9 @@ class ScanNetXYZProbMultiDataset(torch.utils.data.Dataset):
         """``__getitem__`` up to and including ``points.astype(np.float32)``, as a RawScan: the same file checks, the same
         redraw and the same draws from numpy's global generator in the same order; everything behind that line - colours,
         labels, voxelisation, gathers - is left to ``device_batch``, as operands rather than results."""
-        import os
-        ann = self.annotations[index]
-        id_scan = ann["id_scan"]
-        if not np.all(np.abs(np.asarray(ann["trs"]["scale"]) - 1.0) < 1e-7):
-            raise ValueError("%s: scan transform has a non-unit scale" % id_scan)
-        path = os.path.join(self.cfg.data.scannet, "scans", id_scan, id_scan + "_vh_clean_2.ply")
-        if not os.path.exists(path):
-            raise FileNotFoundError(path + " does not exist.")
-        v = read_ply_vertices(path)
-        rgb = np.stack([v["red"], v["green"], v["blue"]], -1).astype(np.uint8, copy=False)
-        to_world = trs_matrix(ann["trs"]["translation"], ann["trs"]["rotation"], ann["trs"]["scale"])
-        points = transform_points(np.stack([v["x"], v["y"], v["z"]], -1), to_world)
-        for model, seg in zip(ann["aligned_models"], self.segments[id_scan]):
-            model["segments"] = seg
-        models = self._select(ann["aligned_models"])
-        if not models:
-            return self.raw_item(np.random.randint(len(self)))
-        aug, colour = np.eye(4), None
-        if self.augment:
-            if self.cfg.augment_color:                                   # the operands of __getitem__'s three in-place lines
-                colour = (1 + 0.4 * np.random.random(3) - 0.2, 0.1 * np.random.random(3) - 0.05,
-                          0.05 * np.random.random(points.shape[0]) - 0.025)
-            angle = np.random.randint(4) * np.pi / 2.0 + (np.random.random() - 0.5) * 2.0 * np.pi / 9.0
-            c, s = np.cos(angle), np.sin(angle)
-            Ry = np.array([[c, 0, -s], [0, 1, 0], [s, 0, c]])
-            points = points @ Ry.T
-            aug[:3, :3] = Ry
-        points = points.astype(np.float32)
-        owner = np.full(points.shape[0], -1, np.int32)
-        minv, scale, cls = [], [], []
-        for m in models:
-            s32 = np.asarray(m["trs"]["scale"], np.float32)
-            if s32.min() < 1e-3:                                         # singular annotation: not in the table
-                continue
-            owner[m["segments"]] = len(cls)                              # in model order: the last model wins a shared vertex
-            minv.append(np.linalg.inv(aug @ bbox_matrix(m))[:3])
-            scale.append(s32 * np.asarray(m["bbox"], np.float32))
-            cls.append(self.class_index(m["catid_cad"]))
-        return RawScan(id_scan, points, rgb, owner, np.asarray(minv, np.float64).reshape(-1, 3, 4),
-                       np.asarray(scale, np.float32).reshape(-1, 3), np.asarray(cls, np.int32), colour)
+        id_scan, rgb, points, models, colour, aug = self._augmented_scan(index)
+        owner, minv, scale, cls = self._model_table(id_scan, models, aug, points.shape[0])[:4]
+        return RawScan(id_scan, points, rgb, owner, minv, scale, cls, colour)
 
 
 class RawScan(typing.NamedTuple):
@@ -355,7 +375,17 @@ def collate_raw(batch):
     """RawScans -> RawBatch (the ``collate_fn`` of the device path; a tuple of tensors, so DataLoader workers and
     ``pin_memory`` handle it).  A scan without colour operands in a batch that has some gets the identity (gain 1, shift 0,
     jitter 0), which leaves its colours as they are."""
-    cat = lambda arrays: torch.from_numpy(np.ascontiguousarray(np.concatenate(arrays, 0)))
+    return RawBatch(minv=_cat([s.minv for s in batch]), **_collate_common(batch))
+
+
+def _cat(arrays):
+    return torch.from_numpy(np.ascontiguousarray(np.concatenate(arrays, 0)))
+
+
+def _collate_common(batch):
+    """the fields RawBatch and RawSymBatch share, by name: the scans' points, rgb, scale and cls one after the other, ``owner``
+    shifted to rows of the concatenated model table, ``offsets``, and the colour operands - ``colour`` f64 [B, 6] with
+    ``jitter`` f64 [M], a scan without operands getting the identity, or both None when no scan has any"""
     sizes = [s.points.shape[0] for s in batch]
     first_model = np.cumsum([0] + [s.cls.shape[0] for s in batch[:-1]])
     owner = [np.where(s.owner >= 0, s.owner + np.int32(f), np.int32(-1)).astype(np.int32) for s, f in zip(batch, first_model)]
@@ -363,11 +393,32 @@ def collate_raw(batch):
     if any(s.colour is not None for s in batch):
         colour = torch.from_numpy(np.stack([np.concatenate(s.colour[:2]) if s.colour is not None
                                             else np.array([1.0, 1.0, 1.0, 0.0, 0.0, 0.0]) for s in batch]).astype(np.float64))
-        jitter = cat([np.asarray(s.colour[2], np.float64) if s.colour is not None else np.zeros(n, np.float64)
-                      for s, n in zip(batch, sizes)])
-    return RawBatch(tuple(s.id_scan for s in batch), cat([s.points for s in batch]), cat([s.rgb for s in batch]), cat(owner),
-                    cat([s.minv for s in batch]), cat([s.scale for s in batch]), cat([s.cls for s in batch]), colour, jitter,
-                    torch.from_numpy(np.cumsum([0] + sizes[:-1]).astype(np.int64)))
+        jitter = _cat([np.asarray(s.colour[2], np.float64) if s.colour is not None else np.zeros(n, np.float64)
+                       for s, n in zip(batch, sizes)])
+    return dict(id_scans=tuple(s.id_scan for s in batch), points=_cat([s.points for s in batch]), rgb=_cat([s.rgb for s in batch]),
+                owner=_cat(owner), scale=_cat([s.scale for s in batch]), cls=_cat([s.cls for s in batch]), colour=colour,
+                jitter=jitter, offsets=torch.from_numpy(np.cumsum([0] + sizes[:-1]).astype(np.int64)))
+
+
+def _upload(batch, dev, host=()):
+    """a NamedTuple batch with its tensors on ``dev`` (non-blocking copies in field order: no host wait from pinned memory);
+    the fields named in ``host``, host ints and None stay as they are"""
+    return batch._replace(**{k: v.to(dev, non_blocking=True) for k, v in batch._asdict().items()
+                             if torch.is_tensor(v) and k not in host})
+
+
+class RawItems(torch.utils.data.Dataset):
+    """a ScanNetXYZProbMultiDataset or ScanNetXYZProbSymDataset whose items are its raw scans (``raw_item``): what the
+    DataLoader workers of the device path produce, for ``collate_raw`` / ``collate_raw_sym``"""
+
+    def __init__(self, ds):
+        self.ds = ds
+
+    def __len__(self):
+        return len(self.ds)
+
+    def __getitem__(self, index):
+        return self.ds.raw_item(index)
 
 
 def device_batch(raw_batch, device, res, use_xyz=False, recentre=True):
@@ -375,15 +426,12 @@ def device_batch(raw_batch, device, res, use_xyz=False, recentre=True):
     moved to the device gives (coords4 int32 [N, 4], feats f32 [N, 3|6], xyz / scale f32 [N, 3], cls int64 [N]), with the
     training script's ``feats[:, -3:] * 2 - 1`` applied when ``recentre``.  On torch's current stream: non-blocking copies,
     the voxelisation (ME.utils.quantize_batch, its one host wait for N) and one cv_sp_scan_rows_f32 launch."""
-    b = raw_batch
     dev = torch.device(device)
-    up = lambda t: None if t is None else t.to(dev, non_blocking=True)
-    points, rgb, owner, minv, scale, cls, colour, jitter = (up(t) for t in (b.points, b.rgb, b.owner, b.minv, b.scale, b.cls,
-                                                                            b.colour, b.jitter))
+    b = _upload(raw_batch, dev, host=("offsets",))
     with torch.cuda.device(dev):
-        coords4, index = me_utils.quantize_batch(points, res, offsets=b.offsets)
-        feats, xyz, scale_rows, cls_rows = me_utils.scan_rows(coords4, index, points, rgb, owner, minv, scale, cls, colour, jitter,
-                                                              use_xyz=use_xyz, recentre=recentre)
+        coords4, index = me_utils.quantize_batch(b.points, res, offsets=b.offsets)
+        feats, xyz, scale_rows, cls_rows = me_utils.scan_rows(coords4, index, b.points, b.rgb, b.owner, b.minv, b.scale, b.cls,
+                                                              b.colour, b.jitter, use_xyz=use_xyz, recentre=recentre)
     return b.id_scans, coords4, feats, xyz, scale_rows, cls_rows
 
 
@@ -404,42 +452,19 @@ class ScanNetXYZProbSymDataset(ScanNetXYZProbMultiDataset):
     scale_labels, obj_labels (0/1), class_labels (0 = background or 'others'))."""
 
     def __getitem__(self, index):
-        import os
-        ann = self.annotations[index]
-        id_scan = ann["id_scan"]
-        if not np.all(np.abs(np.asarray(ann["trs"]["scale"]) - 1.0) < 1e-7):
-            raise ValueError("%s: scan transform has a non-unit scale" % id_scan)
-        path = os.path.join(self.cfg.data.scannet, "scans", id_scan, id_scan + "_vh_clean_2.ply")
-        if not os.path.exists(path):
-            raise FileNotFoundError(path + " does not exist.")
-        v = read_ply_vertices(path)
-        rgb = np.stack([v["red"], v["green"], v["blue"]], -1)               # stays uint8 until after quantisation (:383)
-        to_world = trs_matrix(ann["trs"]["translation"], ann["trs"]["rotation"], ann["trs"]["scale"])
-        points = transform_points(np.stack([v["x"], v["y"], v["z"]], -1), to_world)
-        for model, seg in zip(ann["aligned_models"], self.segments[id_scan]):
-            model["segments"] = seg
-        models = self._select(ann["aligned_models"])
-        if not models:
-            return self[np.random.randint(len(self))]
-        aug = np.eye(4)
-        if self.augment:
-            if self.cfg.augment_color:                                   # :400-404 (on the raw 0..255 colours)
-                rgb = rgb.astype(np.float64)
-                rgb *= (1 + 0.4 * np.random.random(3) - 0.2)
-                rgb += (0.1 * np.random.random(3) - 0.05)
-                rgb += (0.05 * np.random.random(points.shape[0]) - 0.025)[:, None]
-                rgb = np.clip(rgb, 0, 1)
-            angle = np.random.randint(4) * np.pi / 2.0 + (np.random.random() - 0.5) * 2.0 * np.pi / 9.0
-            c, s = np.cos(angle), np.sin(angle)
-            Ry = np.array([[c, 0, -s], [0, 1, 0], [s, 0, c]])
-            points = points @ Ry.T
-            aug[:3, :3] = Ry
-        points = points.astype(np.float32)
+        id_scan, rgb, points, models, colour, aug = self._augmented_scan(index)   # rgb stays uint8 until after quantisation (:383)
+        if colour is not None:                                           # :400-404 (on the raw 0..255 colours)
+            rgb = rgb.astype(np.float64)
+            rgb *= colour[0]
+            rgb += colour[1]
+            rgb += colour[2][:, None]
+            rgb = np.clip(rgb, 0, 1)
+        n_vertex = points.shape[0]
         keep = me_utils.sparse_quantize(np.ascontiguousarray(points), quantization_size=self.cfg.scannet_res,
                                         return_index=True)[1]
         points = points[keep]
         rgb = (rgb[keep] / 255.0).astype(np.float32)
-        new_row = np.full(v.shape[0], -1, np.int64)
+        new_row = np.full(n_vertex, -1, np.int64)
         new_row[keep] = np.arange(len(keep))
         coords = np.floor(points / self.cfg.scannet_res).astype(np.float32)
         n = points.shape[0]
@@ -466,60 +491,12 @@ class ScanNetXYZProbSymDataset(ScanNetXYZProbMultiDataset):
 
     def raw_item(self, index):
         """``__getitem__`` up to and including ``points.astype(np.float32)``, as a RawSymScan: the same file checks, the same
-        redraw and the same draws from numpy's global generator in the same order (gain 3, shift 3, jitter M, randint(4),
-        random()); voxelisation, the survivor filter, the targets under every pose and the packing are left to
-        ``device_batch_sym``, as operands rather than results."""
-        import os
-        ann = self.annotations[index]
-        id_scan = ann["id_scan"]
-        if not np.all(np.abs(np.asarray(ann["trs"]["scale"]) - 1.0) < 1e-7):
-            raise ValueError("%s: scan transform has a non-unit scale" % id_scan)
-        path = os.path.join(self.cfg.data.scannet, "scans", id_scan, id_scan + "_vh_clean_2.ply")
-        if not os.path.exists(path):
-            raise FileNotFoundError(path + " does not exist.")
-        v = read_ply_vertices(path)
-        rgb = np.stack([v["red"], v["green"], v["blue"]], -1).astype(np.uint8, copy=False)
-        to_world = trs_matrix(ann["trs"]["translation"], ann["trs"]["rotation"], ann["trs"]["scale"])
-        points = transform_points(np.stack([v["x"], v["y"], v["z"]], -1), to_world)
-        for model, seg in zip(ann["aligned_models"], self.segments[id_scan]):
-            model["segments"] = seg
-        models = self._select(ann["aligned_models"])
-        if not models:
-            return self.raw_item(np.random.randint(len(self)))
-        aug, colour = np.eye(4), None
-        if self.augment:
-            if self.cfg.augment_color:                                   # the operands of __getitem__'s three in-place lines
-                colour = (1 + 0.4 * np.random.random(3) - 0.2, 0.1 * np.random.random(3) - 0.05,
-                          0.05 * np.random.random(points.shape[0]) - 0.025)
-            angle = np.random.randint(4) * np.pi / 2.0 + (np.random.random() - 0.5) * 2.0 * np.pi / 9.0
-            c, s = np.cos(angle), np.sin(angle)
-            Ry = np.array([[c, 0, -s], [0, 1, 0], [s, 0, c]])
-            points = points @ Ry.T
-            aug[:3, :3] = Ry
-        points = points.astype(np.float32)
-        n_vertex = points.shape[0]
-        owner = np.full(n_vertex, -1, np.int32)
-        minv, scale, cls, segs, vptr, pose_ptr = [], [], [], [], [0], [0]
-        for m in models:
-            s32 = np.asarray(m["trs"]["scale"], np.float32)
-            if s32.min() < 1e-3:                                         # singular annotation: not in the table
-                continue
-            seg = np.asarray(m["segments"], np.int64).reshape(-1)
-            if seg.size and (seg.min() < 0 or seg.max() >= n_vertex):
-                raise IndexError("%s: segment vertex %d outside the scan's %d vertices"
-                                 % (id_scan, int(seg.min() if seg.min() < 0 else seg.max()), n_vertex))
-            owner[seg] = len(cls)                                        # in model order: the last model wins a shared vertex
-            M = bbox_matrix(m)
-            poses = [M] + [M @ _roty4(a) for a in SYMMETRY_ANGLES.get(m["sym"], [])]
-            minv.extend(np.linalg.inv(aug @ P)[:3] for P in poses)
-            scale.append(s32 * np.asarray(m["bbox"], np.float32))
-            cls.append(self.class_index(m["catid_cad"]))
-            segs.append(seg.astype(np.int32))                            # as it lies: unsorted lists and duplicates are kept
-            vptr.append(vptr[-1] + seg.size)
-            pose_ptr.append(pose_ptr[-1] + len(poses))
-        return RawSymScan(id_scan, points, rgb, owner, np.asarray(scale, np.float32).reshape(-1, 3), np.asarray(cls, np.int32),
-                          np.concatenate(segs) if segs else np.zeros(0, np.int32), np.asarray(vptr, np.int32),
-                          np.asarray(pose_ptr, np.int32), np.asarray(minv, np.float64).reshape(-1, 3, 4), colour)
+        redraw and the same draws from numpy's global generator in the same order; voxelisation, the survivor filter, the
+        targets under every pose and the packing are left to ``device_batch_sym``, as operands rather than results."""
+        id_scan, rgb, points, models, colour, aug = self._augmented_scan(index)
+        owner, minv, scale, cls, segs, vptr, pose_ptr = self._model_table(id_scan, models, aug, points.shape[0], sym_poses=True)
+        return RawSymScan(id_scan, points, rgb, owner, scale, cls, np.concatenate(segs) if segs else np.zeros(0, np.int32), vptr,
+                          pose_ptr, minv, colour)
 
 
 class RawSymScan(typing.NamedTuple):
@@ -573,31 +550,23 @@ def collate_raw_sym(batch):
     """RawSymScans -> RawSymBatch (the ``collate_fn`` of the per-category trainer's device path; a tuple of tensors and host
     ints, so DataLoader workers and ``pin_memory`` handle it).  Raises when M or T0 does not fit int32, and when only some
     scans of the batch carry colour operands (the 0..255 clip has no identity operands)."""
-    cat = lambda arrays: torch.from_numpy(np.ascontiguousarray(np.concatenate(arrays, 0)))
-    sizes = [s.points.shape[0] for s in batch]
-    first_vertex = np.cumsum([0] + sizes[:-1]).astype(np.int64)
-    first_model = np.cumsum([0] + [s.cls.shape[0] for s in batch[:-1]])
+    n_vertex = sum(s.points.shape[0] for s in batch)
     lens = np.concatenate([np.diff(s.seg_vptr.astype(np.int64)) for s in batch])
     poses = np.concatenate([np.diff(s.pose_ptr.astype(np.int64)) for s in batch])
     n_targets = int((lens * poses).sum())
-    if sum(sizes) >= 2 ** 31 or n_targets >= 2 ** 31:
+    if n_vertex >= 2 ** 31 or n_targets >= 2 ** 31:
         raise ValueError("collate_raw_sym: the batch does not fit int32 pointers (%d vertices, %d target rows)"
-                         % (sum(sizes), n_targets))
-    owner = [np.where(s.owner >= 0, s.owner + np.int32(f), np.int32(-1)).astype(np.int32) for s, f in zip(batch, first_model)]
+                         % (n_vertex, n_targets))
     with_colour = [s.colour is not None for s in batch]
     if any(with_colour) != all(with_colour):
         raise ValueError("collate_raw_sym: colour operands come for every scan of a batch or for none")
-    colour = jitter = None
-    if all(with_colour):
-        colour = torch.from_numpy(np.stack([np.concatenate(s.colour[:2]) for s in batch]).astype(np.float64))
-        jitter = cat([np.asarray(s.colour[2], np.float64) for s in batch])
+    common = _collate_common(batch)
     prefix = lambda a: torch.from_numpy(np.concatenate([[0], np.cumsum(a)]).astype(np.int32))
-    return RawSymBatch(tuple(s.id_scan for s in batch), cat([s.points for s in batch]), cat([s.rgb for s in batch]), cat(owner),
-                       cat([s.scale for s in batch]), cat([s.cls for s in batch]),
-                       cat([(s.seg_vertex.astype(np.int64) + f).astype(np.int32) for s, f in zip(batch, first_vertex)]),
-                       prefix(lens), prefix(poses), cat([s.minv for s in batch]),
-                       torch.from_numpy(np.repeat(np.arange(len(batch)), [s.cls.shape[0] for s in batch]).astype(np.int32)),
-                       colour, jitter, torch.from_numpy(first_vertex), int(lens.sum()), int(poses.sum()), n_targets)
+    return RawSymBatch(seg_vertex=_cat([(s.seg_vertex.astype(np.int64) + f).astype(np.int32)
+                                        for s, f in zip(batch, common["offsets"].numpy())]),
+                       seg_vptr=prefix(lens), pose_ptr=prefix(poses), minv=_cat([s.minv for s in batch]),
+                       seg_cloud=torch.from_numpy(np.repeat(np.arange(len(batch)), [s.cls.shape[0] for s in batch]).astype(np.int32)),
+                       n_cand=int(lens.sum()), n_jobs=int(poses.sum()), n_targets=n_targets, **common)
 
 
 def device_batch_sym(raw_batch, device, res, use_xyz=False, recentre=True, reference_indexing=True):
@@ -608,23 +577,18 @@ def device_batch_sym(raw_batch, device, res, use_xyz=False, recentre=True, refer
     wait that reads N, the rejected count, P, S, J, T, U and max_row from pinned memory; the outputs are slices of those
     buffers.  Rejected points raise as ME.utils.quantize_device does."""
     from . import _lib
-    b = raw_batch
     dev = torch.device(device)
-    up = lambda t: None if t is None else t.to(dev, non_blocking=True)
-    points, rgb, owner, scale, cls, seg_vertex, seg_vptr, pose_ptr, minv, colour, jitter, offsets = (
-        up(t) for t in (b.points, b.rgb, b.owner, b.scale, b.cls, b.seg_vertex, b.seg_vptr, b.pose_ptr, b.minv, b.colour, b.jitter,
-                        b.offsets))
+    b = _upload(raw_batch, dev, host=("seg_cloud",))
     h_counts = torch.empty(8, dtype=torch.int32, pin_memory=True)
     with torch.cuda.device(dev):
-        coords4, index, inverse, quant_counts = me_utils.quantize_nowait(points, res, b.offsets)
-        o = me_utils.sym_rows(coords4, index, inverse, quant_counts, points, rgb, owner, scale, cls, colour, jitter, offsets,
-                              seg_vertex, seg_vptr, pose_ptr, minv, b.n_targets, reference_indexing=reference_indexing,
-                              use_xyz=use_xyz, recentre=recentre, h_counts=h_counts)
+        coords4, index, inverse, quant_counts = me_utils.quantize_nowait(b.points, res, raw_batch.offsets)
+        o = me_utils.sym_rows(coords4, index, inverse, quant_counts, b.points, b.rgb, b.owner, b.scale, b.cls, b.colour, b.jitter,
+                              b.offsets, b.seg_vertex, b.seg_vptr, b.pose_ptr, b.minv, b.n_targets,
+                              reference_indexing=reference_indexing, use_xyz=use_xyz, recentre=recentre, h_counts=h_counts)
         torch.cuda.current_stream(dev).synchronize()                     # the batch's one host wait
     c = dict(zip(_lib.SYM_ROWS_COUNTS, h_counts.tolist()))
     if c["rejected"] != 0:
-        raise RuntimeError("sparse_quantize: %d points rejected (a non-finite component, or a voxel outside the supported "
-                           "window: spatial coordinates in [-32704, 32703])" % c["rejected"])
+        me_utils.raise_rejected(c["rejected"])
     n, P, S, U = c["N"], c["P"], c["S"], c["U"]
     sym = SymBatch(o["rows"][:P], o["pseg"][:P], o["seg_ptr"][:S + 1], o["pose_ptr"][:S + 1], o["tgt_ptr"][:S + 1],
                    o["targets"][:c["T"]], o["urow"][:U], o["uptr"][:U + 1], o["upoint"][:P], S, c["J"], c["max_row"])
@@ -732,7 +696,7 @@ def collate_sym(batch, reference_indexing=True):
 
 def sym_to_device(sym, dev):
     """the SymBatch with its tensors on ``dev`` (non-blocking copies: no host wait from pinned memory)"""
-    return sym._replace(**{k: v.to(dev, non_blocking=True) for k, v in sym._asdict().items() if torch.is_tensor(v)})
+    return _upload(sym, dev)
 
 
 class SyntheticSymDataset(torch.utils.data.Dataset):

@@ -46,15 +46,43 @@ def quantize_device(points, quantization_size=None, offsets=None, return_inverse
     cloud).  Voxel = floor(p / quantization_size) in the input's precision, floor(p) when quantization_size is None.
     Returns (coords4 [N, 4] int32 = (batch, x, y, z), index [N] int32 = first point of every voxel, ascending,
     inverse [M] int32 or None).  Raises RuntimeError when points are non-finite or outside the coordinate window."""
-    import ctypes
-
-    from .. import _lib
-    L = _lib.lib()
     assert points.is_cuda and points.dim() == 2 and points.shape[1] == 3, "points: a [M, 3] device tensor"
     if points.dtype not in (torch.float32, torch.float64):
         points = points.to(torch.float64)
     if points.stride(1) != 1 or points.stride(0) < 3:
         points = points.contiguous()
+    coords4, index, inverse, _, (n, rejected) = _quantize_call(points, quantization_size, offsets, return_inverse, True)
+    if rejected != 0:
+        raise_rejected(rejected)
+    return coords4[:n], index[:n], inverse
+
+
+def quantize_nowait(points, quantization_size, offsets):
+    """quantize_device's sibling WITHOUT the host wait (cv_sp_quantize_f32 with h_counts == NULL): float32 ``points`` [M, 3]
+    of the clouds whose first rows are ``offsets``, on torch's current stream.  Returns the full-size buffers
+    (coords4 [M, 4], index [M], inverse [M], counts [2] = (N, rejected points)), all int32 on the device: only the first N rows
+    of coords4 / index are written, and nothing has been checked - the caller reads ``counts`` behind its own wait and treats
+    rejected points as quantize_device does."""
+    assert points.is_cuda and points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 3 \
+        and points.stride(1) == 1 and points.stride(0) >= 3, "points: a float32 [M, 3] device tensor"
+    return _quantize_call(points, quantization_size, offsets, True, False)[:4]
+
+
+def raise_rejected(count):
+    """the error of a voxelisation that rejected ``count`` points, worded the same wherever the count is read"""
+    raise RuntimeError("sparse_quantize: %d points rejected (a non-finite component, or a voxel outside the supported "
+                       "window: spatial coordinates in [-32704, 32703])" % count) from None
+
+
+def _quantize_call(points, quantization_size, offsets, return_inverse, host_counts):
+    """The one call into cv_sp_quantize_f32 / _f64, on torch's current stream: ``points`` [M, 3] fp32 or fp64 device rows
+    (unit column stride), ``offsets`` None or the first rows of the clouds.  Returns the full-size int32 device buffers
+    (coords4 [M, 4], index [M], inverse [M] or None, counts [2] = (N, rejected points)) and, with ``host_counts``, the two
+    counts as host ints - the call then waits for them; without, h_counts is NULL, nothing waits and the fifth entry is None."""
+    import ctypes
+
+    from .. import _lib
+    L = _lib.lib()
     dev, m = points.device, points.shape[0]
     if m == 0:
         raise RuntimeError("sparse_quantize: empty point cloud")
@@ -67,7 +95,7 @@ def quantize_device(points, quantization_size=None, offsets=None, return_inverse
     index = torch.empty(m, dtype=torch.int32, device=dev)
     inverse = torch.empty(m, dtype=torch.int32, device=dev) if return_inverse else None
     counts_d = torch.empty(2, dtype=torch.int32, device=dev)
-    counts_h = (ctypes.c_int32 * 2)()
+    counts_h = (ctypes.c_int32 * 2)() if host_counts else None
     ws = _lib.scratch(dev, "quantize", int(L.cv_sp_quantize_workspace_bytes(m)))
     vp = ctypes.c_void_p
     fn = L.cv_sp_quantize_f64 if f64 else L.cv_sp_quantize_f32
@@ -78,42 +106,7 @@ def quantize_device(points, quantization_size=None, offsets=None, return_inverse
                       vp(coords4.data_ptr()), vp(index.data_ptr()), vp(inverse.data_ptr()) if return_inverse else None,
                       vp(counts_d.data_ptr()), counts_h, vp(ws.data_ptr()), ws.numel(), stream),
                    "cv_sp_quantize_f64" if f64 else "cv_sp_quantize_f32")
-    n, rejected = int(counts_h[0]), int(counts_h[1])
-    if rejected != 0:
-        raise RuntimeError("sparse_quantize: %d points rejected (a non-finite component, or a voxel outside the supported "
-                           "window: spatial coordinates in [-32704, 32703])" % rejected)
-    return coords4[:n], index[:n], inverse
-
-
-def quantize_nowait(points, quantization_size, offsets):
-    """quantize_device's sibling WITHOUT the host wait (cv_sp_quantize_f32 with h_counts == NULL): float32 ``points`` [M, 3]
-    of the clouds whose first rows are ``offsets``, on torch's current stream.  Returns the full-size buffers
-    (coords4 [M, 4], index [M], inverse [M], counts [2] = (N, rejected points)), all int32 on the device: only the first N rows
-    of coords4 / index are written, and nothing has been checked - the caller reads ``counts`` behind its own wait and treats
-    rejected points as quantize_device does."""
-    import ctypes
-
-    from .. import _lib
-    L = _lib.lib()
-    assert points.is_cuda and points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 3 \
-        and points.stride(1) == 1 and points.stride(0) >= 3, "points: a float32 [M, 3] device tensor"
-    dev, m = points.device, points.shape[0]
-    if m == 0:
-        raise RuntimeError("sparse_quantize: empty point cloud")
-    offsets = [int(o) for o in (offsets.tolist() if hasattr(offsets, "tolist") else offsets)]
-    h_off = (ctypes.c_int64 * len(offsets))(*offsets)
-    coords4 = torch.empty((m, 4), dtype=torch.int32, device=dev)
-    index = torch.empty(m, dtype=torch.int32, device=dev)
-    inverse = torch.empty(m, dtype=torch.int32, device=dev)
-    counts = torch.empty(2, dtype=torch.int32, device=dev)
-    ws = _lib.scratch(dev, "quantize", int(L.cv_sp_quantize_workspace_bytes(m)))
-    vp = ctypes.c_void_p
-    with torch.cuda.device(dev):
-        stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
-        _lib.check(L.cv_sp_quantize_f32(vp(points.data_ptr()), m, points.stride(0), float(np.float32(quantization_size)), 0, h_off,
-                                        len(offsets), vp(coords4.data_ptr()), vp(index.data_ptr()), vp(inverse.data_ptr()),
-                                        vp(counts.data_ptr()), None, vp(ws.data_ptr()), ws.numel(), stream), "cv_sp_quantize_f32")
-    return coords4, index, inverse, counts
+    return coords4, index, inverse, counts_d, (tuple(int(c) for c in counts_h) if host_counts else None)
 
 
 def quantize_batch(clouds, quantization_size, return_inverse=False, offsets=None):
@@ -190,6 +183,23 @@ def voxel_rows(coords4, index, res, *columns, recentre_from=None, out=None, poin
     return pts, outs
 
 
+def _check_vertex_arrays(who, points, rgb, owner, scale, cls, colour, jitter, n_clouds):
+    """what scan_rows and sym_rows both require of the per-vertex arrays, the model table and the colour operands; returns the
+    number of models"""
+    m, k = points.shape[0], cls.shape[0]
+    assert points.dtype == torch.float32 and points.shape == (m, 3) and points.stride(1) == 1, "points: float32 [M, 3]"
+    assert rgb.dtype == torch.uint8 and rgb.shape == (m, 3) and rgb.is_contiguous(), "rgb: contiguous uint8 [M, 3]"
+    assert owner.dtype == torch.int32 and owner.shape == (m,) and owner.is_contiguous(), "owner: contiguous int32 [M]"
+    assert scale.dtype == torch.float32 and scale.shape == (k, 3) and scale.is_contiguous(), "scale: contiguous float32 [m, 3]"
+    assert cls.dtype == torch.int32 and cls.shape == (k,) and cls.is_contiguous(), "cls: contiguous int32 [m]"
+    if (colour is None) != (jitter is None):
+        raise ValueError("%s: the colour table and the jitter come together" % who)
+    if colour is not None:
+        assert colour.dtype == torch.float64 and colour.shape == (n_clouds, 6) and colour.is_contiguous(), "colour: float64 [B, 6]"
+        assert jitter.dtype == torch.float64 and jitter.shape == (m,) and jitter.is_contiguous(), "jitter: contiguous float64 [M]"
+    return k
+
+
 def scan_rows(coords4, index, points, rgb, owner, minv, scale, cls, colour=None, jitter=None, use_xyz=False, recentre=False,
               out=None):
     """The training batch of voxelised raw scans, in ONE launch on torch's current stream (cv_sp_scan_rows_f32): features and
@@ -208,20 +218,9 @@ def scan_rows(coords4, index, points, rgb, owner, minv, scale, cls, colour=None,
     n, m, dev = index.shape[0], points.shape[0], index.device
     assert index.dtype == torch.int32 and index.is_contiguous(), "index: a contiguous int32 device tensor"
     assert coords4.dtype == torch.int32 and coords4.is_contiguous() and coords4.shape == (n, 4), "coords4: contiguous int32 [N, 4]"
-    assert points.dtype == torch.float32 and points.shape == (m, 3) and points.stride(1) == 1, "points: float32 [M, 3]"
-    assert rgb.dtype == torch.uint8 and rgb.shape == (m, 3) and rgb.is_contiguous(), "rgb: contiguous uint8 [M, 3]"
-    assert owner.dtype == torch.int32 and owner.shape == (m,) and owner.is_contiguous(), "owner: contiguous int32 [M]"
-    k = cls.shape[0]
+    n_clouds = 1 if colour is None else colour.shape[0]
+    k = _check_vertex_arrays("scan_rows", points, rgb, owner, scale, cls, colour, jitter, n_clouds)
     assert minv.dtype == torch.float64 and minv.shape == (k, 3, 4) and minv.is_contiguous(), "minv: contiguous float64 [m, 3, 4]"
-    assert scale.dtype == torch.float32 and scale.shape == (k, 3) and scale.is_contiguous(), "scale: contiguous float32 [m, 3]"
-    assert cls.dtype == torch.int32 and cls.is_contiguous(), "cls: contiguous int32 [m]"
-    if (colour is None) != (jitter is None):
-        raise ValueError("scan_rows: the colour table and the jitter come together")
-    n_clouds = 1
-    if colour is not None:
-        n_clouds = colour.shape[0]
-        assert colour.dtype == torch.float64 and colour.shape == (n_clouds, 6) and colour.is_contiguous(), "colour: float64 [B, 6]"
-        assert jitter.dtype == torch.float64 and jitter.shape == (m,) and jitter.is_contiguous(), "jitter: contiguous float64 [M]"
     fw = 6 if use_xyz else 3
     widths, dtypes = (fw, 3, 3, 1), (torch.float32, torch.float32, torch.float32, torch.int64)
     dst = list(out) if out is not None else [None] * 4
@@ -263,18 +262,10 @@ def sym_rows(coords4, index, inverse, quant_counts, points, rgb, owner, scale, c
     i32c = lambda t, shape: t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev
     assert i32c(coords4, (m, 4)) and i32c(index, (m,)) and i32c(inverse, (m,)) and i32c(quant_counts, (2,)), \
         "coords4 / index / inverse / counts: quantize_nowait's full-size int32 buffers"
-    assert points.dtype == torch.float32 and points.shape == (m, 3) and points.stride(1) == 1, "points: float32 [M, 3]"
-    assert rgb.dtype == torch.uint8 and rgb.shape == (m, 3) and rgb.is_contiguous(), "rgb: contiguous uint8 [M, 3]"
-    assert i32c(owner, (m,)), "owner: contiguous int32 [M]"
-    k = cls.shape[0]
-    assert scale.dtype == torch.float32 and scale.shape == (k, 3) and scale.is_contiguous() and i32c(cls, (k,)), "model table"
-    if (colour is None) != (jitter is None):
-        raise ValueError("sym_rows: the colour table and the jitter come together")
     n_clouds = offsets.shape[0]
+    k = _check_vertex_arrays("sym_rows", points, rgb, owner, scale, cls, colour, jitter, n_clouds)
+    assert owner.device == dev and cls.device == dev, "owner / cls: on the device of index"
     assert offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.device == dev, "offsets: int64 [B] on the device"
-    if colour is not None:
-        assert colour.dtype == torch.float64 and colour.shape == (n_clouds, 6) and colour.is_contiguous(), "colour: float64 [B, 6]"
-        assert jitter.dtype == torch.float64 and jitter.shape == (m,) and jitter.is_contiguous(), "jitter: contiguous float64 [M]"
     assert i32c(seg_vertex, (q,)) and i32c(seg_vptr, (s0 + 1,)) and i32c(pose_ptr, (s0 + 1,)), "segment lists: int32"
     assert minv.dtype == torch.float64 and minv.shape == (j0, 3, 4) and minv.is_contiguous(), "minv: contiguous float64 [J0, 3, 4]"
     if h_counts is not None:

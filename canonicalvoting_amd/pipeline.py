@@ -590,8 +590,7 @@ def _call_points(fn, name, d, r, dev, scratch_name, ws_hint):
         return _call_growing(call, name, d.scene, r.scene, dev, scratch_name, ws_hint)
     except _lib.CvError:
         if r.rejected:
-            raise RuntimeError("sparse_quantize: %d points rejected (a non-finite component, or a voxel outside the supported "
-                               "window: spatial coordinates in [-32704, 32703])" % r.rejected) from None
+            ME.utils.raise_rejected(r.rejected)
         raise
 
 

@@ -38,7 +38,7 @@ import train_loader as joint  # noqa: E402
 
 RES, BATCH, MODELS = joint.RES, joint.BATCH, 15
 SYMS = ["__SYM_NONE", "__SYM_ROTATE_UP_2", "__SYM_ROTATE_UP_4", "__SYM_ROTATE_UP_INF"]
-# per batch: the voxeliser's clear / insert / flag / emit / inverse, then cv_sp_sym_rows_f32's ten kernels (csrc/sym_rows.hip)
+# per batch: the voxeliser's clear / insert / flag / emit / inverse, then cv_sp_sym_rows_f32's ten kernels (csrc/train_rows.hip)
 LAUNCHES = (5, 10)
 
 

@@ -19,22 +19,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from canonicalvoting_amd import dist as cvd  # noqa: E402
 from canonicalvoting_amd import train  # noqa: E402
-from canonicalvoting_amd.data import (ScanNetXYZProbMultiDataset, SyntheticScanDataset, collate_fn,  # noqa: E402
+from canonicalvoting_amd.data import (RawItems, ScanNetXYZProbMultiDataset, SyntheticScanDataset, collate_fn,  # noqa: E402
                                      collate_raw, device_batch, load_config)
 from canonicalvoting_amd.minkunet import MinkUNet34C  # noqa: E402
-
-
-class RawItems(torch.utils.data.Dataset):
-    """a ScanNetXYZProbMultiDataset whose items are its raw scans (``raw_item``), for the device loader"""
-
-    def __init__(self, ds):
-        self.ds = ds
-
-    def __len__(self):
-        return len(self.ds)
-
-    def __getitem__(self, index):
-        return self.ds.raw_item(index)
 
 
 def host_batches(loader, dev):

@@ -25,8 +25,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from canonicalvoting_amd import dist as cvd  # noqa: E402
 from canonicalvoting_amd import train  # noqa: E402
-from canonicalvoting_amd.data import (ScanNetXYZProbSymDataset, SyntheticSymDataset, collate_raw_sym, collate_sym,  # noqa: E402
-                                      device_batch_sym, load_config, sym_to_device)
+from canonicalvoting_amd.data import (RawItems, ScanNetXYZProbSymDataset, SyntheticSymDataset, collate_raw_sym,  # noqa: E402
+                                      collate_sym, device_batch_sym, load_config, sym_to_device)
 from canonicalvoting_amd.minkunet import MinkUNet34C  # noqa: E402
 
 
@@ -37,19 +37,6 @@ def device_batches(loader, dev):
         feats[:, -3:] = feats[:, -3:] * 2.0 - 1.0                         # train_separate.py:242-243: colour columns only
         yield (coords.to(dev, non_blocking=True), feats, sym_to_device(sym, dev), scale.to(dev, non_blocking=True),
                obj.to(dev, non_blocking=True))
-
-
-class RawSymItems(torch.utils.data.Dataset):
-    """the dataset's raw scans: what the workers of --device-loader produce"""
-
-    def __init__(self, ds):
-        self.ds = ds
-
-    def __len__(self):
-        return len(self.ds)
-
-    def __getitem__(self, index):
-        return self.ds.raw_item(index)
 
 
 def device_loader_batches(loader, dev, cfg, reference_indexing):
@@ -107,7 +94,7 @@ def main():
     if cfg:
         ds = ScanNetXYZProbSymDataset(cfg, training=True, augment=cfg.augment)
         sampler = torch.utils.data.distributed.DistributedSampler(ds, world, rank, shuffle=True) if world > 1 else None
-        loader = torch.utils.data.DataLoader(RawSymItems(ds) if a.device_loader else ds, batch_size=cfg.batch_size,
+        loader = torch.utils.data.DataLoader(RawItems(ds) if a.device_loader else ds, batch_size=cfg.batch_size,
                                              shuffle=sampler is None, sampler=sampler,
                                              collate_fn=collate_raw_sym if a.device_loader else collate, drop_last=True,
                                              num_workers=cfg.num_workers, pin_memory=True)

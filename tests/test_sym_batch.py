@@ -447,6 +447,29 @@ def test_collate_raw_sym_layout_and_its_int32_bound():
         data.collate_raw_sym([raw, aug])
 
 
+WORKER_SEED = 93
+
+
+def _seed_worker(_worker_id):
+    np.random.seed(WORKER_SEED)
+
+
+def test_collate_raw_sym_through_dataloader_workers(tmp_path):
+    """data.RawItems under DataLoader workers with collate_raw_sym: the one batch of a two-scan dataset (260 and 195 vertices,
+    colour and rotation drawn), made by the worker that starts from WORKER_SEED, is the batch collated in-process from that seed"""
+    specs = [_scan_with_q(91, 120, n_vox=220, copies=40), _scan_with_q(92, 90, n_vox=160, copies=35)]
+    ds = data.ScanNetXYZProbSymDataset(mini_cfg(root=write_dataset(tmp_path, specs), augment_color=True), training=False, augment=True)
+    np.random.seed(WORKER_SEED)
+    want = data.collate_raw_sym([ds.raw_item(0), ds.raw_item(1)])
+    loader = torch.utils.data.DataLoader(data.RawItems(ds), batch_size=2, shuffle=False, collate_fn=data.collate_raw_sym,
+                                         num_workers=2, worker_init_fn=_seed_worker, pin_memory=torch.cuda.is_available())
+    (got,) = list(loader)
+    assert isinstance(got, data.RawSymBatch) and want.colour is not None and want.points.shape[0] == 260 + 195
+    for name, w in want._asdict().items():
+        g = getattr(got, name)
+        assert same_bits(g.numpy(), w.numpy()) if torch.is_tensor(w) else (type(g) is type(w) and g == w), name
+
+
 # ---- named wrong results the comparison must reject -------------------------------------------------------------------
 
 @pytest.mark.parametrize("wrong,name", [("occupied", "shapes"), ("unstable", "shapes"), ("keep_empty", "dropped_first_between_last")])

@@ -376,21 +376,10 @@ def test_collate_raw_without_colour_and_with_colour_in_part_of_the_batch():
     assert np.array_equal(restate(same, RES)[1], restate(raws["plain0"], RES)[1])
 
 
-class _RawView(torch.utils.data.Dataset):
-    def __init__(self, ds):
-        self.ds = ds
-
-    def __len__(self):
-        return len(self.ds)
-
-    def __getitem__(self, i):
-        return self.ds.raw_item(i)
-
-
 def test_collate_raw_through_dataloader_workers():
     ds = data.ScanNetXYZProbMultiDataset(mini_cfg(), training=False, augment=False)
     want = data.collate_raw([ds.raw_item(0), ds.raw_item(1)])
-    loader = torch.utils.data.DataLoader(_RawView(ds), batch_size=2, shuffle=False, collate_fn=data.collate_raw, num_workers=2,
+    loader = torch.utils.data.DataLoader(data.RawItems(ds), batch_size=2, shuffle=False, collate_fn=data.collate_raw, num_workers=2,
                                          pin_memory=torch.cuda.is_available())
     (got,) = list(loader)
     assert isinstance(got, data.RawBatch) and got.id_scans == want.id_scans and got.colour is None and got.jitter is None

@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 RES = cases.RES
 GOLD = cases.GOLD
-# cv_sp_scan_rows_f32 gives every output at most 512 workgroups of 256 threads (SCAN_ROWS_MAX_BLOCKS, csrc/scan_rows.hip):
+# cv_sp_scan_rows_f32 gives every output at most 512 workgroups of 256 threads (MAX_BLOCKS, csrc/train_rows.hip):
 # from 131 073 elements on a loop takes a second trip.  The shortest loop (cls) has N elements.
 ONE_TRIP = 512 * 256
 
