@@ -411,6 +411,23 @@ def lib():
     return _lib
 
 
+def ptr(t):
+    """the device (or pinned) address of tensor ``t`` as a C pointer argument; None gives NULL"""
+    return vp(t.data_ptr() if t is not None else 0)
+
+
+def stream_handle(dev):
+    """raw handle (an int) of torch's current stream on ``dev``: what scratch and the scene hosts are keyed by
+    (torch.cuda.current_stream would build a Stream object per call, about 4 us each)"""
+    import torch
+    return torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device())
+
+
+def stream(dev):
+    """torch's current stream on ``dev`` as a C stream argument"""
+    return vp(stream_handle(dev))
+
+
 _scratch_lock = threading.Lock()
 _scratch_bufs = {}
 
@@ -424,8 +441,7 @@ def scratch(dev, name, nbytes):
     of one stream only and the next call on that stream is ordered behind them, so one buffer per (device, stream,
     name) is safe; results handed to the caller are never scratch."""
     import torch
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(),
-           torch.cuda.current_stream(dev).cuda_stream, name)
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), stream_handle(dev), name)
     nbytes = max(int(nbytes), 256)
     with _scratch_lock:
         buf = _scratch_bufs.get(key)

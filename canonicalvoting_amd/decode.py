@@ -1,7 +1,9 @@
 """Detection decode: the reference's inline loop as one function.
 
 ``decode_boxes`` is eval_joint.py:195-263 (greedy peak picking, grid suppression,
-back-projection check, class vote); ``nms`` / ``get_iou_obb`` are eval_joint.py:75-89 and
+back-projection check, class vote) and ``decode_boxes_categories`` the same over K separate-mode
+categories with one host sync: two thin wrappers, each through its own C entry point, around one
+walk (``_walk``); ``nms`` / ``get_iou_obb`` are eval_joint.py:75-89 and
 utils/calc_map.py:6-21; ``detect`` chains vote -> decode -> per-class NMS the way
 eval_joint.py:193-280 does.  Module-level constants keep the reference's names and values
 (eval_joint.py:18-21).
@@ -12,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib, hv_cuda
+from ._lib import ptr, stream
 
 thresh_high = 60
 thresh_low = 10
@@ -19,15 +22,79 @@ valid_ratio = 0.2
 elimination = 2
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+def _walk(K, grid_obj, grid_rot, grid_scale, scan_points, xyz_pred, prob_pred, class_pred, res, corner, params, mutate_grid,
+          allow_truncation):
+    """The decode behind decode_boxes (K None: cv_decode_f32) and decode_boxes_categories (cv_decode_cat_f32 over K
+    categories): operand checks, grid origin, the walk - redone with eight times the room while it stops early with a cell
+    >= thresh_high still live - and the results, one dict per category.  ``params``: cv_decode_params, max_iters = the first
+    capacity."""
+    who = "decode_boxes" if K is None else "decode_boxes_categories"
+    L = _lib.lib()
+    dev = grid_obj.device
+    for t, name in ((grid_obj, "grid_obj"), (grid_rot, "grid_rot"), (grid_scale, "grid_scale"),
+                    (scan_points, "scan_points"), (xyz_pred, "xyz_pred"), (prob_pred, "prob_pred")):
+        if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32:
+            raise RuntimeError("%s must be a contiguous float32 CUDA tensor" % name)
+    n = scan_points.shape[0]
+    if K is not None and (grid_obj.dim() != 4 or tuple(xyz_pred.shape) != (K, n, 3) or tuple(prob_pred.shape) != (K, n)):
+        raise RuntimeError("expected grid_obj [K,X,Y,Z], xyz_pred [K,N,3] and prob_pred [K,N]")
+    # (class_pred None - class 0 everywhere - is the category call's alone)
+    cls = None if (class_pred is None and K is not None) else class_pred.to(torch.int32).contiguous()
+    if corner is None:
+        corner = hv_cuda.recent_corner(grid_obj)            # set by hv_cuda.forward / forward_categories (same points)
+    if corner is None:
+        corner, _, _ = hv_cuda.grid_geometry(scan_points, float(res))
+    dims = (ctypes.c_int * 3)(*(grid_obj.shape if K is None else grid_obj.shape[1:]))
+    rows = 1 if K is None else K
+    if K is None:
+        fn, name, cat, ws_bytes = L.cv_decode_f32, "cv_decode_f32", (), lambda M: L.cv_decode_workspace_bytes(dims, n, M)
+    else:
+        fn, name, cat, ws_bytes = L.cv_decode_cat_f32, "cv_decode_cat_f32", (K,), lambda M: L.cv_decode_cat_workspace_bytes(dims, n, M, K)
+    M = params.max_iters
+    while True:
+        params.max_iters = M
+        ws = _lib.scratch(dev, "decode", ws_bytes(M))
+        n_cand, n_boxes, truncated = np.zeros(rows, np.int32), np.zeros(rows, np.int32), np.zeros(rows, np.int32)
+        cand = np.zeros((rows, M), np.int64)
+        verdict = np.zeros((rows, M), np.int32)
+        boxes = np.zeros((rows, M, 8, 3), np.float32)
+        scores = np.zeros((rows, M), np.float32)
+        classes = np.zeros((rows, M), np.int32)
+        with torch.cuda.device(dev):
+            rc = fn(ptr(grid_obj), ptr(grid_rot), ptr(grid_scale), dims,
+                    (ctypes.c_float * 3)(*[float(v) for v in corner]), ctypes.c_float(float(res)),
+                    ptr(scan_points), ptr(xyz_pred), ptr(prob_pred), ptr(cls), n, *cat, ctypes.byref(params),
+                    1 if mutate_grid else 0, ptr(ws), ws.numel(), n_cand.ctypes.data_as(_lib.c_int_p),
+                    cand.ctypes.data_as(_lib.c_i64_p), verdict.ctypes.data_as(_lib.c_i32_p),
+                    n_boxes.ctypes.data_as(_lib.c_int_p), boxes.ctypes.data_as(_lib.c_float_p),
+                    scores.ctypes.data_as(_lib.c_float_p), classes.ctypes.data_as(_lib.c_i32_p),
+                    truncated.ctypes.data_as(_lib.c_int_p), stream(dev))
+        _lib.check(rc, name)
+        if not truncated.any() or allow_truncation:
+            break
+        # the reference's `while True` (eval_joint.py:204-209) runs until the grid maximum drops below thresh_high:
+        # a capped walk that stopped early is redone with more room, never returned as if it were complete
+        if M >= 65536 or mutate_grid:
+            raise RuntimeError("%s: more than %d candidate cells >= thresh_high (max_candidates)" % (who, M))
+        M = min(M * 8, 65536)
+    out = []
+    for k in range(rows):
+        b, m = int(n_boxes[k]), int(n_cand[k])
+        out.append(dict(boxes=boxes[k, :b].copy(), scores=scores[k, :b].copy(), classes=classes[k, :b].copy(),
+                        cand_idx=cand[k, :m].copy(), verdict=verdict[k, :m].copy(), truncated=bool(truncated[k])))
+    return out
+
+
+def _params(thresh_high, thresh_low, valid_ratio, elimination, prob_thresh, separate_variant, max_candidates, err_thresh):
+    return _lib.DecodeParams(float(thresh_high), float(thresh_low), float(valid_ratio), int(elimination), float(prob_thresh),
+                             0 if separate_variant else 1, int(max_candidates), float(err_thresh))
 
 
 def decode_boxes(grid_obj, grid_rot, grid_scale, scan_points, xyz_pred, prob_pred, class_pred, res,
                  corner=None, thresh_high=thresh_high, thresh_low=thresh_low,
                  valid_ratio=valid_ratio, elimination=elimination, prob_thresh=0.3, err_thresh=0.3,
                  separate_variant=False, max_candidates=512, mutate_grid=False, allow_truncation=False):
-    """Greedy decode on the device, one host sync.
+    """Greedy decode on the device, one host sync (cv_decode_f32).
 
     scan_points [N,3] f32 world points (``curr_points * res``, eval_joint.py:200), ``corner``
     defaults to their minimum (``corners[0]``, :201).  Returns a dict with ``boxes`` [K,8,3],
@@ -38,53 +105,9 @@ def decode_boxes(grid_obj, grid_rot, grid_scale, scan_points, xyz_pred, prob_pre
     (:204-209) runs until the grid maximum drops below ``thresh_high``, so a walk that fills its capacity with a cell
     >= thresh_high still live is redone with eight times the room (up to 65536, then RuntimeError).
     ``allow_truncation=True`` returns the capped walk instead, marked ``truncated=True`` in the dict."""
-    L = _lib.lib()
-    dev = grid_obj.device
-    for t, name in ((grid_obj, "grid_obj"), (grid_rot, "grid_rot"), (grid_scale, "grid_scale"),
-                    (scan_points, "scan_points"), (xyz_pred, "xyz_pred"), (prob_pred, "prob_pred")):
-        if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32:
-            raise RuntimeError("%s must be a contiguous float32 CUDA tensor" % name)
-    cls = class_pred.to(torch.int32).contiguous()
-    n = scan_points.shape[0]
-    if corner is None:
-        corner = hv_cuda.recent_corner(grid_obj)            # set by hv_cuda.forward (same points)
-    if corner is None:
-        corner, _, _ = hv_cuda.grid_geometry(scan_points, float(res))
-    dims = (ctypes.c_int * 3)(*grid_obj.shape)
-    p = _lib.DecodeParams(float(thresh_high), float(thresh_low), float(valid_ratio),
-                          int(elimination), float(prob_thresh), 0 if separate_variant else 1,
-                          int(max_candidates), float(err_thresh))
-    M = int(max_candidates)
-    while True:
-        p.max_iters = M
-        ws = _lib.scratch(dev, "decode", L.cv_decode_workspace_bytes(dims, n, M))
-        n_cand, n_boxes, truncated = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-        cand = np.zeros(M, np.int64)
-        verdict = np.zeros(M, np.int32)
-        boxes = np.zeros((M, 8, 3), np.float32)
-        scores = np.zeros(M, np.float32)
-        classes = np.zeros(M, np.int32)
-        with torch.cuda.device(dev):
-            rc = L.cv_decode_f32(
-                _ptr(grid_obj), _ptr(grid_rot), _ptr(grid_scale), dims,
-                (ctypes.c_float * 3)(*[float(v) for v in corner]), ctypes.c_float(float(res)),
-                _ptr(scan_points), _ptr(xyz_pred), _ptr(prob_pred), _ptr(cls), n, ctypes.byref(p),
-                1 if mutate_grid else 0, _ptr(ws), ws.numel(), ctypes.byref(n_cand),
-                cand.ctypes.data_as(_lib.c_i64_p), verdict.ctypes.data_as(_lib.c_i32_p),
-                ctypes.byref(n_boxes), boxes.ctypes.data_as(_lib.c_float_p),
-                scores.ctypes.data_as(_lib.c_float_p), classes.ctypes.data_as(_lib.c_i32_p),
-                ctypes.byref(truncated), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _lib.check(rc, "cv_decode_f32")
-        if not truncated.value or allow_truncation:
-            break
-        # the reference's `while True` (eval_joint.py:204-209) runs until the grid maximum drops below thresh_high:
-        # a capped walk that stopped early is redone with more room, never returned as if it were complete
-        if M >= 65536 or mutate_grid:
-            raise RuntimeError("decode_boxes: more than %d candidate cells >= thresh_high (max_candidates)" % M)
-        M = min(M * 8, 65536)
-    k, m = n_boxes.value, n_cand.value
-    return dict(boxes=boxes[:k].copy(), scores=scores[:k].copy(), classes=classes[:k].copy(),
-                cand_idx=cand[:m].copy(), verdict=verdict[:m].copy(), truncated=bool(truncated.value))
+    p = _params(thresh_high, thresh_low, valid_ratio, elimination, prob_thresh, separate_variant, max_candidates, err_thresh)
+    return _walk(None, grid_obj, grid_rot, grid_scale, scan_points, xyz_pred, prob_pred, class_pred, res, corner, p,
+                 mutate_grid, allow_truncation)[0]
 
 
 def decode_boxes_categories(grid_obj, grid_rot, grid_scale, scan_points, xyz_pred, prob_pred, res, class_pred=None,
@@ -96,56 +119,9 @@ def decode_boxes_categories(grid_obj, grid_rot, grid_scale, scan_points, xyz_pre
     shared by the categories, None = class 0 everywhere (separate mode, eval_separate.py:195-264).  Returns a list of K
     dicts, entry k exactly what decode_boxes returns for category k alone (same keys, same truncation rule: a walk that
     fills ``max_candidates`` with a live cell >= thresh_high is redone with eight times the room)."""
-    L = _lib.lib()
-    dev = grid_obj.device
-    for t, name in ((grid_obj, "grid_obj"), (grid_rot, "grid_rot"), (grid_scale, "grid_scale"),
-                    (scan_points, "scan_points"), (xyz_pred, "xyz_pred"), (prob_pred, "prob_pred")):
-        if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32:
-            raise RuntimeError("%s must be a contiguous float32 CUDA tensor" % name)
-    K, n = grid_obj.shape[0], scan_points.shape[0]
-    if grid_obj.dim() != 4 or tuple(xyz_pred.shape) != (K, n, 3) or tuple(prob_pred.shape) != (K, n):
-        raise RuntimeError("expected grid_obj [K,X,Y,Z], xyz_pred [K,N,3] and prob_pred [K,N]")
-    cls = None if class_pred is None else class_pred.to(torch.int32).contiguous()
-    if corner is None:
-        corner = hv_cuda.recent_corner(grid_obj)            # set by hv_cuda.forward_categories (same points)
-    if corner is None:
-        corner, _, _ = hv_cuda.grid_geometry(scan_points, float(res))
-    dims = (ctypes.c_int * 3)(*grid_obj.shape[1:])
-    p = _lib.DecodeParams(float(thresh_high), float(thresh_low), float(valid_ratio),
-                          int(elimination), float(prob_thresh), 0 if separate_variant else 1,
-                          int(max_candidates), float(err_thresh))
-    M = int(max_candidates)
-    while True:
-        p.max_iters = M
-        ws = _lib.scratch(dev, "decode", L.cv_decode_cat_workspace_bytes(dims, n, M, K))
-        n_cand, n_boxes, truncated = np.zeros(K, np.int32), np.zeros(K, np.int32), np.zeros(K, np.int32)
-        cand = np.zeros((K, M), np.int64)
-        verdict = np.zeros((K, M), np.int32)
-        boxes = np.zeros((K, M, 8, 3), np.float32)
-        scores = np.zeros((K, M), np.float32)
-        classes = np.zeros((K, M), np.int32)
-        with torch.cuda.device(dev):
-            rc = L.cv_decode_cat_f32(
-                _ptr(grid_obj), _ptr(grid_rot), _ptr(grid_scale), dims,
-                (ctypes.c_float * 3)(*[float(v) for v in corner]), ctypes.c_float(float(res)),
-                _ptr(scan_points), _ptr(xyz_pred), _ptr(prob_pred), None if cls is None else _ptr(cls), n, K,
-                ctypes.byref(p), 1 if mutate_grid else 0, _ptr(ws), ws.numel(), n_cand.ctypes.data_as(_lib.c_int_p),
-                cand.ctypes.data_as(_lib.c_i64_p), verdict.ctypes.data_as(_lib.c_i32_p),
-                n_boxes.ctypes.data_as(_lib.c_int_p), boxes.ctypes.data_as(_lib.c_float_p),
-                scores.ctypes.data_as(_lib.c_float_p), classes.ctypes.data_as(_lib.c_i32_p),
-                truncated.ctypes.data_as(_lib.c_int_p), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        _lib.check(rc, "cv_decode_cat_f32")
-        if not truncated.any() or allow_truncation:
-            break
-        if M >= 65536 or mutate_grid:
-            raise RuntimeError("decode_boxes_categories: more than %d candidate cells >= thresh_high (max_candidates)" % M)
-        M = min(M * 8, 65536)
-    out = []
-    for k in range(K):
-        b, m = int(n_boxes[k]), int(n_cand[k])
-        out.append(dict(boxes=boxes[k, :b].copy(), scores=scores[k, :b].copy(), classes=classes[k, :b].copy(),
-                        cand_idx=cand[k, :m].copy(), verdict=verdict[k, :m].copy(), truncated=bool(truncated[k])))
-    return out
+    p = _params(thresh_high, thresh_low, valid_ratio, elimination, prob_thresh, separate_variant, max_candidates, err_thresh)
+    return _walk(grid_obj.shape[0], grid_obj, grid_rot, grid_scale, scan_points, xyz_pred, prob_pred, class_pred, res, corner,
+                 p, mutate_grid, allow_truncation)
 
 
 def get_iou_obb(bbox1, bbox2):

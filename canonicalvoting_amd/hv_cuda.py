@@ -67,12 +67,7 @@ def _scalar(t, kind):
     return hit[1]
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+_ptr, _stream = _lib.ptr, _lib.stream
 
 
 def _f3(vals):
@@ -114,7 +109,7 @@ def prefetch_geometry(points):
     ws = _lib.scratch(dev, "hv_minmax", L.cv_hv_minmax_workspace_bytes())
     host = _pinned6()
     with torch.cuda.device(dev):
-        _lib.check(L.cv_hv_minmax_async_f32(_ptr(points), points.shape[0], ctypes.c_void_p(host.data_ptr()),
+        _lib.check(L.cv_hv_minmax_async_f32(_ptr(points), points.shape[0], _ptr(host),
                                             _ptr(ws), ws.numel(), _stream(dev)), "cv_hv_minmax_async_f32")
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(dev))
@@ -153,77 +148,89 @@ def _take_prefetched(points):
     return h[:3], h[3:]
 
 
+def _grid_dims(mn, mx, res):
+    dims = (ctypes.c_int * 3)()
+    _lib.check(_lib.lib().cv_hv_grid_dims_f32(mn, mx, ctypes.c_float(res), dims), "cv_hv_grid_dims_f32")
+    return [int(d) for d in dims]
+
+
 def grid_geometry(points, res):
     """(corner[3], max[3], dims[3]) as hv_cuda_kernel.cu:129-134 computes them (one host sync, or none when
     prefetch_geometry(points) ran earlier)."""
-    L = _lib.lib()
     pre = _take_prefetched(points)
     if pre is not None:
         mn, mx = _f3(pre[0]), _f3(pre[1])
-        dims = (ctypes.c_int * 3)()
-        _lib.check(L.cv_hv_grid_dims_f32(mn, mx, ctypes.c_float(res), dims), "cv_hv_grid_dims_f32")
-        return list(mn), list(mx), [int(d) for d in dims]
-    ws = _lib.scratch(points.device, "hv_minmax", L.cv_hv_minmax_workspace_bytes())
-    mn = (ctypes.c_float * 3)()
-    mx = (ctypes.c_float * 3)()
-    with torch.cuda.device(points.device):
-        _lib.check(L.cv_hv_minmax_f32(_ptr(points), points.shape[0], mn, mx, _ptr(ws), ws.numel(),
-                                      _stream(points.device)), "cv_hv_minmax_f32")
-    dims = (ctypes.c_int * 3)()
-    _lib.check(L.cv_hv_grid_dims_f32(mn, mx, ctypes.c_float(res), dims), "cv_hv_grid_dims_f32")
-    return list(mn), list(mx), [int(d) for d in dims]
+    else:
+        L = _lib.lib()
+        ws = _lib.scratch(points.device, "hv_minmax", L.cv_hv_minmax_workspace_bytes())
+        mn = (ctypes.c_float * 3)()
+        mx = (ctypes.c_float * 3)()
+        with torch.cuda.device(points.device):
+            _lib.check(L.cv_hv_minmax_f32(_ptr(points), points.shape[0], mn, mx, _ptr(ws), ws.numel(),
+                                          _stream(points.device)), "cv_hv_minmax_f32")
+    return list(mn), list(mx), _grid_dims(mn, mx, res)
 
 
-def _checked_inputs(points, xyz_labels, scale_labels, obj_labels, res, num_rots):
-    _check_input(points, "points")
-    _check_input(xyz_labels, "xyz_labels")
-    _check_input(scale_labels, "scale_labels")
-    _check_input(obj_labels, "obj_labels")
-    _check_input(res, "res")
-    _check_input(num_rots, "num_rots")
-    for t, name in ((points, "points"), (xyz_labels, "xyz_labels"), (scale_labels, "scale_labels"),
-                    (obj_labels, "obj_labels")):
+def _checked_inputs(points, xyz_labels, scale_labels, obj_labels, res, num_rots, categories=False):
+    """The input checks of forward / backward and, with ``categories``, of forward_categories (labels with a leading K axis;
+    ``res`` / ``num_rots`` may then be numbers).  Returns (N, res, num_rots, K or None), the two scalars as host values."""
+    named = ((points, "points"), (xyz_labels, "xyz_labels"), (scale_labels, "scale_labels"), (obj_labels, "obj_labels"))
+    for t, name in named + (() if categories else ((res, "res"), (num_rots, "num_rots"))):
+        _check_input(t, name)
+    for t, name in named:
         if t.dtype != torch.float32:
             raise RuntimeError("%s must be float32 (got %s)" % (name, t.dtype))
-    n = points.shape[0]
-    if points.dim() != 2 or points.shape[1] != 3 or xyz_labels.shape != (n, 3) \
-            or scale_labels.shape != (n, 3) or obj_labels.shape != (n,):
-        raise RuntimeError("expected points/xyz_labels/scale_labels [N,3] and obj_labels [N]")
+    n, K = points.shape[0], None
+    if categories:
+        if xyz_labels.dim() != 3:
+            raise RuntimeError("expected xyz_labels / scale_labels [K,N,3] and obj_labels [K,N]")
+        K = xyz_labels.shape[0]
+    lead = () if K is None else (K,)
+    if points.dim() != 2 or points.shape[1] != 3 or xyz_labels.shape != lead + (n, 3) \
+            or scale_labels.shape != lead + (n, 3) or obj_labels.shape != lead + (n,):
+        raise RuntimeError("expected points [N,3], xyz_labels / scale_labels [K,N,3] and obj_labels [K,N]" if categories else
+                           "expected points/xyz_labels/scale_labels [N,3] and obj_labels [N]")
     if n == 0:
         # the reference fails inside torch::min on an empty tensor (hv_cuda_kernel.cu:129)
         raise RuntimeError("hv_cuda: cannot vote with zero points")
-    return n, _scalar(res, "f"), _scalar(num_rots, "i")
+    return (n, _scalar(res, "f") if torch.is_tensor(res) else float(res),
+            _scalar(num_rots, "i") if torch.is_tensor(num_rots) else int(num_rots), K)
+
+
+def _vote(points, xyz_labels, scale_labels, obj_labels, res_v, nrot, mn, dims, K=None):
+    """The vote onto the grid (origin ``mn``, ``dims``): cv_hv_forward_f32, or with K cv_hv_forward_cat_f32 over the labels'
+    category axis (grids [K,X,Y,Z,...]); the grid origin is remembered on grid_obj for the decode that follows."""
+    L = _lib.lib()
+    n, dev = points.shape[0], points.device
+    shape = (() if K is None else (K,)) + tuple(dims)
+    grid_obj = torch.empty(shape, dtype=torch.float32, device=dev)
+    grid_rot = torch.empty(shape + (2,), dtype=torch.float32, device=dev)
+    grid_scale = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
+    cdims = (ctypes.c_int * 3)(*dims)
+    if K is None:
+        fn, name, cat, wsb = L.cv_hv_forward_f32, "cv_hv_forward_f32", (), L.cv_hv_forward_workspace_bytes(n, nrot, cdims, _algo)
+    else:
+        fn, name, cat = L.cv_hv_forward_cat_f32, "cv_hv_forward_cat_f32", (K,)
+        wsb = L.cv_hv_forward_cat_workspace_bytes(n, nrot, cdims, _algo, K)
+    ws = _lib.scratch(dev, "hv_forward", wsb)
+    with torch.cuda.device(dev):
+        _lib.check(fn(_ptr(points), _ptr(xyz_labels), _ptr(scale_labels), _ptr(obj_labels), n, ctypes.c_float(res_v), nrot,
+                      _f3(mn), cdims, *cat, _ptr(grid_obj), _ptr(grid_rot), _ptr(grid_scale), _ptr(ws), ws.numel(), _algo,
+                      _stream(dev)), name)
+    # remember the grid origin of this grid so the decode that follows does not reduce the points again
+    _remember_corner(grid_obj, mn)
+    return [grid_obj, grid_rot, grid_scale]
 
 
 def forward(points, xyz_labels, scale_labels, obj_labels, res, num_rots, corners=None):
-    n, res_v, nrot = _checked_inputs(points, xyz_labels, scale_labels, obj_labels, res, num_rots)
-    L = _lib.lib()
-    dev = points.device
+    n, res_v, nrot, _ = _checked_inputs(points, xyz_labels, scale_labels, obj_labels, res, num_rots)
     if corners is None:
         mn, _, dims = grid_geometry(points, res_v)
     else:
         c = corners.detach().to("cpu", torch.float32)
         mn = [float(v) for v in c[0]]
-        d = (ctypes.c_int * 3)()
-        _lib.check(L.cv_hv_grid_dims_f32(_f3(mn), _f3(c[1]), ctypes.c_float(res_v), d),
-                   "cv_hv_grid_dims_f32")
-        dims = [int(v) for v in d]
-    X, Y, Z = dims
-    grid_obj = torch.empty((X, Y, Z), dtype=torch.float32, device=dev)
-    grid_rot = torch.empty((X, Y, Z, 2), dtype=torch.float32, device=dev)
-    grid_scale = torch.empty((X, Y, Z, 3), dtype=torch.float32, device=dev)
-    cdims = (ctypes.c_int * 3)(*dims)
-    wsb = L.cv_hv_forward_workspace_bytes(n, nrot, cdims, _algo)
-    ws = _lib.scratch(dev, "hv_forward", wsb)
-    with torch.cuda.device(dev):
-        _lib.check(L.cv_hv_forward_f32(_ptr(points), _ptr(xyz_labels), _ptr(scale_labels),
-                                       _ptr(obj_labels), n, ctypes.c_float(res_v), nrot, _f3(mn),
-                                       cdims, _ptr(grid_obj), _ptr(grid_rot), _ptr(grid_scale),
-                                       _ptr(ws), ws.numel(), _algo, _stream(dev)),
-                   "cv_hv_forward_f32")
-    # remember the grid origin of this grid so the decode that follows does not reduce the points again
-    _remember_corner(grid_obj, mn)
-    return [grid_obj, grid_rot, grid_scale]
+        dims = _grid_dims(_f3(mn), _f3(c[1]), res_v)
+    return _vote(points, xyz_labels, scale_labels, obj_labels, res_v, nrot, mn, dims)
 
 
 def forward_categories(points, xyz_labels, scale_labels, obj_labels, res, num_rots):
@@ -231,45 +238,16 @@ def forward_categories(points, xyz_labels, scale_labels, obj_labels, res, num_ro
     eval_separate.py:166-186): xyz_labels / scale_labels [K,N,3], obj_labels [K,N] -> [grid_obj[K,X,Y,Z],
     grid_rot[K,X,Y,Z,2], grid_scale[K,X,Y,Z,3]].  Category k is bit for bit forward(points, xyz_labels[k], ...).
     ``res`` / ``num_rots`` are 0-dim tensors (as forward takes them) or numbers."""
-    for t, name in ((points, "points"), (xyz_labels, "xyz_labels"), (scale_labels, "scale_labels"), (obj_labels, "obj_labels")):
-        _check_input(t, name)
-        if t.dtype != torch.float32:
-            raise RuntimeError("%s must be float32 (got %s)" % (name, t.dtype))
-    n = points.shape[0]
-    if xyz_labels.dim() != 3:
-        raise RuntimeError("expected xyz_labels / scale_labels [K,N,3] and obj_labels [K,N]")
-    K = xyz_labels.shape[0]
-    if points.dim() != 2 or points.shape[1] != 3 or xyz_labels.shape != (K, n, 3) or scale_labels.shape != (K, n, 3) \
-            or obj_labels.shape != (K, n):
-        raise RuntimeError("expected points [N,3], xyz_labels / scale_labels [K,N,3] and obj_labels [K,N]")
-    if n == 0:
-        raise RuntimeError("hv_cuda: cannot vote with zero points")
-    res_v = _scalar(res, "f") if torch.is_tensor(res) else float(res)
-    nrot = _scalar(num_rots, "i") if torch.is_tensor(num_rots) else int(num_rots)
-    L = _lib.lib()
-    dev = points.device
+    n, res_v, nrot, K = _checked_inputs(points, xyz_labels, scale_labels, obj_labels, res, num_rots, categories=True)
     mn, _, dims = grid_geometry(points, res_v)
-    X, Y, Z = dims
-    grid_obj = torch.empty((K, X, Y, Z), dtype=torch.float32, device=dev)
-    grid_rot = torch.empty((K, X, Y, Z, 2), dtype=torch.float32, device=dev)
-    grid_scale = torch.empty((K, X, Y, Z, 3), dtype=torch.float32, device=dev)
-    cdims = (ctypes.c_int * 3)(*dims)
-    wsb = L.cv_hv_forward_cat_workspace_bytes(n, nrot, cdims, _algo, K)
-    ws = _lib.scratch(dev, "hv_forward", wsb)
-    with torch.cuda.device(dev):
-        _lib.check(L.cv_hv_forward_cat_f32(_ptr(points), _ptr(xyz_labels), _ptr(scale_labels), _ptr(obj_labels), n,
-                                           ctypes.c_float(res_v), nrot, _f3(mn), cdims, K, _ptr(grid_obj), _ptr(grid_rot),
-                                           _ptr(grid_scale), _ptr(ws), ws.numel(), _algo, _stream(dev)),
-                   "cv_hv_forward_cat_f32")
-    _remember_corner(grid_obj, mn)
-    return [grid_obj, grid_rot, grid_scale]
+    return _vote(points, xyz_labels, scale_labels, obj_labels, res_v, nrot, mn, dims, K)
 
 
 def backward(grad_grid, points, xyz_labels, scale_labels, obj_labels, res, num_rots, corners=None):
     """``corners`` (optional, not in the reference's 7-positional signature): the [2,3] box the forward was
     given; the grid origin is then corners[0] as in forward() instead of the minimum of the points."""
     _check_input(grad_grid, "grad_grid")
-    n, res_v, nrot = _checked_inputs(points, xyz_labels, scale_labels, obj_labels, res, num_rots)
+    n, res_v, nrot, _ = _checked_inputs(points, xyz_labels, scale_labels, obj_labels, res, num_rots)
     if grad_grid.dtype != torch.float32 or grad_grid.dim() != 3:
         raise RuntimeError("grad_grid must be a float32 [X,Y,Z] tensor")
     L = _lib.lib()

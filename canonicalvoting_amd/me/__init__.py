@@ -26,18 +26,10 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
+from .._lib import ptr as _ptr, stream as _stream, vp
 from . import utils  # noqa: F401
 
 __version__ = "0.5.3-cvhip"
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-
-
-def _stream(dev):
-    # (the raw handle: torch.cuda.current_stream builds a Stream object per call - 4 us x ~10 per layer of a training step)
-    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device()))
 
 
 class _NoSwitch:
@@ -237,7 +229,6 @@ class CoordinateManager:
         o_lws = (sws_b + 63) & ~63
         wbuf = _lib.scratch(dev, "scene_plan", o_lws + lws_b)      # sort + level workspaces: dead when the call returns
         ib, kb, wb = ibuf.data_ptr(), kbuf.data_ptr(), wbuf.data_ptr()
-        vp = ctypes.c_void_p
         c_coords = (vp * NL)(*[ib + 4 * o for o in lay.coords])
         c_keys = (vp * NL)(*[kb + 8 * lay.cap * i for i in range(NL)])
         c_vals = (vp * NL)(*[ib + 4 * o for o in lay.vals])
@@ -1059,7 +1050,6 @@ def copy_unless_flag(srcs, dsts, dev, flag=None):
     n = len(srcs)
     if n == 0:
         return
-    vp = ctypes.c_void_p
     a_src = (vp * n)(*[t.data_ptr() for t in srcs])
     a_dst = (vp * n)(*[t.data_ptr() for t in dsts])
     a_len = (ctypes.c_longlong * n)(*[t.numel() * t.element_size() for t in srcs])

@@ -4,10 +4,19 @@ what a scene gathers behind it, scan_rows for what a training batch computes beh
 the per-category trainer's batch with one host wait behind both), kaiming_normal_
 (utils/resnet.py:112); sym_loss, the per-category trainer's coordinate loss over packed symmetry labels
 (train_separate.py:265-280)."""
+import ctypes
 import math
 
 import numpy as np
 import torch
+
+from .. import _lib
+from .._lib import ptr as _ptr, stream as _stream
+
+
+def _ptr_if_any(t):
+    """_ptr(t), NULL also for a tensor without elements (torch gives those an address of its own)"""
+    return _ptr(t) if t is not None and t.numel() else None
 
 
 def batched_coordinates(coords, dtype=torch.int32, device=None):
@@ -79,9 +88,6 @@ def _quantize_call(points, quantization_size, offsets, return_inverse, host_coun
     (unit column stride), ``offsets`` None or the first rows of the clouds.  Returns the full-size int32 device buffers
     (coords4 [M, 4], index [M], inverse [M] or None, counts [2] = (N, rejected points)) and, with ``host_counts``, the two
     counts as host ints - the call then waits for them; without, h_counts is NULL, nothing waits and the fifth entry is None."""
-    import ctypes
-
-    from .. import _lib
     L = _lib.lib()
     dev, m = points.device, points.shape[0]
     if m == 0:
@@ -97,14 +103,12 @@ def _quantize_call(points, quantization_size, offsets, return_inverse, host_coun
     counts_d = torch.empty(2, dtype=torch.int32, device=dev)
     counts_h = (ctypes.c_int32 * 2)() if host_counts else None
     ws = _lib.scratch(dev, "quantize", int(L.cv_sp_quantize_workspace_bytes(m)))
-    vp = ctypes.c_void_p
     fn = L.cv_sp_quantize_f64 if f64 else L.cv_sp_quantize_f32
     q = 0.0 if quantization_size is None else float(np.float64(quantization_size) if f64 else np.float32(quantization_size))
     with torch.cuda.device(dev):
-        stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
-        _lib.check(fn(vp(points.data_ptr()), m, points.stride(0), q, 1 if quantization_size is None else 0, h_off, n_clouds,
-                      vp(coords4.data_ptr()), vp(index.data_ptr()), vp(inverse.data_ptr()) if return_inverse else None,
-                      vp(counts_d.data_ptr()), counts_h, vp(ws.data_ptr()), ws.numel(), stream),
+        _lib.check(fn(_ptr(points), m, points.stride(0), q, 1 if quantization_size is None else 0, h_off, n_clouds,
+                      _ptr(coords4), _ptr(index), _ptr(inverse) if return_inverse else None,
+                      _ptr(counts_d), counts_h, _ptr(ws), ws.numel(), _stream(dev)),
                    "cv_sp_quantize_f64" if f64 else "cv_sp_quantize_f32")
     return coords4, index, inverse, counts_d, (tuple(int(c) for c in counts_h) if host_counts else None)
 
@@ -139,11 +143,7 @@ def voxel_rows(coords4, index, res, *columns, recentre_from=None, out=None, poin
     written as ``x * 2 - 1`` (float32).  out: optional destinations, one per column ([N, w] windows, row stride >= w; the
     words beyond w are left alone).  points=False: no world points (coords4 and res are not read).
     Returns (points [N, 3] float32 or None, list of the gathered columns)."""
-    import ctypes
-
-    from .. import _lib
     L = _lib.lib()
-    vp = ctypes.c_void_p
     n, dev = index.shape[0], index.device
     assert index.dtype == torch.int32 and index.is_contiguous(), "index: a contiguous int32 device tensor"
     if len(columns) > _lib.GATHER_MAX_JOBS:
@@ -176,10 +176,9 @@ def voxel_rows(coords4, index, res, *columns, recentre_from=None, out=None, poin
         jobs[i] = _lib.GatherJob(c2.data_ptr(), c2.stride(0), d2.data_ptr(), d2.stride(0), w, -1 if rf is None else int(rf))
         outs.append(dst)
     with torch.cuda.device(dev):
-        stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
-        _lib.check(L.cv_sp_voxel_rows_f32(vp(coords4.data_ptr()) if points else None, vp(index.data_ptr()), n,
-                                          float(res) if points else 0.0, vp(pts.data_ptr()) if points else None, jobs,
-                                          len(columns), stream), "cv_sp_voxel_rows_f32")
+        _lib.check(L.cv_sp_voxel_rows_f32(_ptr(coords4) if points else None, _ptr(index), n,
+                                          float(res) if points else 0.0, _ptr(pts) if points else None, jobs,
+                                          len(columns), _stream(dev)), "cv_sp_voxel_rows_f32")
     return pts, outs
 
 
@@ -211,9 +210,6 @@ def scan_rows(coords4, index, points, rgb, owner, minv, scale, cls, colour=None,
     float64, both or neither.  use_xyz: the points in front of the colours; recentre: colours as c * 2 - 1.
     out: optional (feats, xyz, scale, cls) destinations ([N, w] windows, row stride >= w; cls [N] int64, any stride).
     Returns (feats [N, 3|6] float32, xyz [N, 3] float32, scale [N, 3] float32, cls [N] int64)."""
-    import ctypes
-
-    from .. import _lib
     L = _lib.lib()
     n, m, dev = index.shape[0], points.shape[0], index.device
     assert index.dtype == torch.int32 and index.is_contiguous(), "index: a contiguous int32 device tensor"
@@ -230,15 +226,13 @@ def scan_rows(coords4, index, points, rgb, owner, minv, scale, cls, colour=None,
         else:
             d2 = dst[i] if i < 3 else dst[i].unsqueeze(1)
             assert d2.dtype == dt and d2.shape == (n, w) and (d2.stride(1) == 1 or w == 1) and d2.stride(0) >= w, "out: [N, w] windows"
-    vp = ctypes.c_void_p
-    ptr = lambda t: vp(t.data_ptr()) if t is not None and t.numel() else None
+    ptr = _ptr_if_any
     d = _lib.ScanRowsDesc(ptr(coords4), ptr(index), n, m, ptr(points), points.stride(0), ptr(rgb), ptr(owner),
                           ptr(minv), ptr(scale), ptr(cls), k, ptr(colour), ptr(jitter), n_clouds, int(bool(use_xyz)),
                           int(bool(recentre)), ptr(dst[0]), dst[0].stride(0), ptr(dst[1]), dst[1].stride(0),
                           ptr(dst[2]), dst[2].stride(0), ptr(dst[3]), dst[3].stride(0))
     with torch.cuda.device(dev):
-        stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
-        _lib.check(L.cv_sp_scan_rows_f32(ctypes.byref(d), stream), "cv_sp_scan_rows_f32")
+        _lib.check(L.cv_sp_scan_rows_f32(ctypes.byref(d), _stream(dev)), "cv_sp_scan_rows_f32")
     return tuple(dst)
 
 
@@ -254,9 +248,6 @@ def sym_rows(coords4, index, inverse, quant_counts, points, rgb, owner, scale, c
     h_counts: a pinned int32 [8] tensor that receives the counts by a copy on the stream, or None.
     Returns a dict of the upper-bound buffers: rows, pseg, urow, upoint [Q], uptr [Q + 1], seg_ptr, pose_ptr, tgt_ptr
     [S0 + 1], targets [T0, 3], feats [M, 3|6], scale [M, 3], obj, cls [M] int64, counts int32 [8] (_lib.SYM_ROWS_COUNTS)."""
-    import ctypes
-
-    from .. import _lib
     L = _lib.lib()
     dev, m, q, s0, j0 = index.device, points.shape[0], seg_vertex.shape[0], seg_vptr.shape[0] - 1, minv.shape[0]
     i32c = lambda t, shape: t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev
@@ -277,8 +268,7 @@ def sym_rows(coords4, index, inverse, quant_counts, points, rgb, owner, scale, c
              feats=new((m, 6 if use_xyz else 3), torch.float32), scale=new((m, 3), torch.float32), obj=new(m, torch.int64),
              cls=new(m, torch.int64), counts=new(8))
     ws = _lib.scratch(dev, "sym_rows", int(L.cv_sp_sym_rows_workspace_bytes(m, q, s0, n_clouds)))
-    vp = ctypes.c_void_p
-    ptr = lambda t: vp(t.data_ptr()) if t is not None and t.numel() else None
+    ptr = _ptr_if_any
     d = _lib.SymRowsDesc(ptr(coords4), ptr(index), ptr(inverse), ptr(quant_counts), m, ptr(points), points.stride(0), ptr(rgb),
                          ptr(owner), ptr(scale), ptr(cls), k, ptr(colour), ptr(jitter), ptr(offsets), n_clouds,
                          ptr(seg_vertex), q, ptr(seg_vptr), ptr(pose_ptr), s0, ptr(minv), j0, t0,
@@ -286,18 +276,14 @@ def sym_rows(coords4, index, inverse, quant_counts, points, rgb, owner, scale, c
                          ptr(o["rows"]), ptr(o["pseg"]), ptr(o["seg_ptr"]), ptr(o["pose_ptr"]), ptr(o["tgt_ptr"]), ptr(o["targets"]),
                          ptr(o["urow"]), ptr(o["uptr"]), ptr(o["upoint"]), ptr(o["feats"]), o["feats"].stride(0),
                          ptr(o["scale"]), 3, ptr(o["obj"]), ptr(o["cls"]), ptr(o["counts"]), ptr(h_counts),
-                         vp(ws.data_ptr()), ws.numel())
+                         _ptr(ws), ws.numel())
     with torch.cuda.device(dev):
-        stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
-        _lib.check(L.cv_sp_sym_rows_f32(ctypes.byref(d), stream), "cv_sp_sym_rows_f32")
+        _lib.check(L.cv_sp_sym_rows_f32(ctypes.byref(d), _stream(dev)), "cv_sp_sym_rows_f32")
     return o
 
 
 def _sym_desc(out_feats, sym, weights, xyz_factor):
     """cv_sym_loss_desc of predictions ``out_feats`` [N, C >= 3] and a device SymBatch, outputs and workspace still unset"""
-    import ctypes
-
-    from .. import _lib
     dev = out_feats.device
     assert out_feats.is_cuda and out_feats.dtype == torch.float32 and out_feats.dim() == 2 and out_feats.stride(1) == 1 \
         and out_feats.stride(0) >= 3 and out_feats.shape[1] >= 3, "out_feats: float32 [N, C >= 3] device rows"
@@ -309,7 +295,7 @@ def _sym_desc(out_feats, sym, weights, xyz_factor):
         and sym.pseg.shape[0] == P and sym.upoint.shape[0] == P and sym.uptr.shape[0] == sym.urow.shape[0] + 1, "sym: inconsistent sizes"
     if sym.max_row >= out_feats.shape[0]:
         raise ValueError("sym_loss: label row %d outside the %d output rows" % (sym.max_row, out_feats.shape[0]))
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+    ptr = _ptr_if_any
     d = _lib.SymLossDesc()
     d.d_out, d.n_rows, d.ld = ptr(out_feats), out_feats.shape[0], out_feats.stride(0)
     d.d_rows, d.d_pseg, d.n_points = ptr(sym.rows), ptr(sym.pseg), P
@@ -324,11 +310,7 @@ def _sym_desc(out_feats, sym, weights, xyz_factor):
 class _SymLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, out_feats, sym, weights, xyz_factor):
-        import ctypes
-
-        from .. import _lib
         L = _lib.lib()
-        vp = ctypes.c_void_p
         dev = out_feats.device
         out_feats = out_feats if out_feats.stride(1) == 1 else out_feats.contiguous()
         d = _sym_desc(out_feats, sym, weights, xyz_factor)
@@ -337,11 +319,10 @@ class _SymLossFn(torch.autograd.Function):
         best = torch.empty(max(sym.n_segments, 1), dtype=torch.int32, device=dev)
         seg_loss = torch.empty(max(sym.n_segments, 1), dtype=torch.float32, device=dev)
         ws = _lib.scratch(dev, "sym_loss", int(L.cv_sym_loss_workspace_bytes(d.n_targets, d.n_jobs)))
-        d.d_loss, d.d_pose_loss, d.d_best, d.d_seg_loss = (vp(t.data_ptr()) for t in (loss, pose_loss, best, seg_loss))
-        d.d_ws, d.ws_bytes = vp(ws.data_ptr()), ws.numel()
+        d.d_loss, d.d_pose_loss, d.d_best, d.d_seg_loss = (_ptr(t) for t in (loss, pose_loss, best, seg_loss))
+        d.d_ws, d.ws_bytes = _ptr(ws), ws.numel()
         with torch.cuda.device(dev):
-            stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
-            _lib.check(L.cv_sym_loss_fwd_f32(ctypes.byref(d), stream), "cv_sym_loss_fwd_f32")
+            _lib.check(L.cv_sym_loss_fwd_f32(ctypes.byref(d), _stream(dev)), "cv_sym_loss_fwd_f32")
         ctx.save_for_backward(out_feats, best)
         ctx.sym, ctx.weights, ctx.xyz_factor = sym, weights, xyz_factor
         ctx.mark_non_differentiable(pose_loss, best)
@@ -349,19 +330,14 @@ class _SymLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss, _grad_pose, _grad_best):
-        import ctypes
-
-        from .. import _lib
-        vp = ctypes.c_void_p
         out_feats, best = ctx.saved_tensors
         dev = out_feats.device
         grad = torch.zeros(out_feats.shape, dtype=torch.float32, device=dev)
         gl = grad_loss.to(torch.float32).reshape(1).contiguous()
         d = _sym_desc(out_feats, ctx.sym, ctx.weights, ctx.xyz_factor)
-        d.d_best, d.d_grad_loss, d.d_grad, d.grad_ld = vp(best.data_ptr()), vp(gl.data_ptr()), vp(grad.data_ptr()), grad.stride(0)
+        d.d_best, d.d_grad_loss, d.d_grad, d.grad_ld = _ptr(best), _ptr(gl), _ptr(grad), grad.stride(0)
         with torch.cuda.device(dev):
-            stream = vp(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
-            _lib.check(_lib.lib().cv_sym_loss_bwd_f32(ctypes.byref(d), stream), "cv_sym_loss_bwd_f32")
+            _lib.check(_lib.lib().cv_sym_loss_bwd_f32(ctypes.byref(d), _stream(dev)), "cv_sym_loss_bwd_f32")
         return grad, None, None, None
 
 

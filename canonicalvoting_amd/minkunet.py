@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import me as ME
+from ._lib import ptr, stream, vp
 from .me.modules.resnet_block import BasicBlock
 
 
@@ -388,42 +389,54 @@ class MinkUNetBase(ResNetBase):
         self.range_fallbacks = getattr(self, "range_fallbacks", 0) + 1
         return self.program_forward(x, pieces=3)
 
+    def eval_pieces(self):
+        """the piece format of the eval forward: bf16 singles under ME.COMPUTE_DTYPE == "bf16", else this model's PIECES"""
+        return 1 if ME.COMPUTE_DTYPE == "bf16" else self.PIECES
+
+    def launch_args(self, plan, level_orders=None, max_planes=None):
+        """What cv_net_run_f32 and cv_net_run_models_f32 take of (model, plan): (rows, convolution workspace bytes, map
+        pointer table, order pointer table), a level's mask order only where it has at least masked_min_rows() rows.
+        ``level_orders``: five order pointers that replace the plan's; ``max_planes``: the widest layer of a model set.
+        Returns None where a level that runs mask-sorted has no order."""
+        masked = [c >= self.masked_min_rows() for c in plan.counts[:5]]
+        orders = plan.perm_ptrs[:5] if level_orders is None else level_orders
+        if any(m and o is None for m, o in zip(masked, orders)):
+            return None
+        perm_ptrs = [o if m else None for m, o in zip(masked, orders)] + plan.perm_ptrs[5:]
+        rows = (ctypes.c_int64 * 5)(*plan.counts)
+        sorted_levels = (ctypes.c_int * 5)(*[p is not None for p in perm_ptrs[:5]])
+        ws_bytes = _lib.lib().cv_sp_scene_conv_workspace_bytes(rows, sorted_levels, self.MASK_GROUPS,
+                                                               max_planes or max(self.PLANES))
+        return rows, ws_bytes, (vp * len(plan.map_ptrs))(*plan.map_ptrs), (vp * len(perm_ptrs))(*perm_ptrs)
+
     def program_forward(self, x, pieces=None, defer_check=None):
         """fused_forward through the C executor (cv_net_run_f32): identical launches, one call."""
         L = _lib.lib()
         dev = x.F.device
         if pieces is None:
-            pieces = 1 if ME.COMPUTE_DTYPE == "bf16" else self.PIECES
+            pieces = self.eval_pieces()
         c_ops, c_bufs, _ = self._program(dev, pieces)
         plan = x.coordinate_manager.fused_fast(self.conv0p1s1.kernel_size)
         flag = ME.range_flag(dev) if pieces == 2 else None
         n = plan.counts
-        masked = [n[i] >= self.masked_min_rows() for i in range(5)]
-        if any(m and plan.perm_ptrs[i] is None for i, m in enumerate(masked)):
+        args = self.launch_args(plan)
+        if args is None:
             # mask groups too wide for the plan's counting sort: orders from the generic path
             cm = x.coordinate_manager.fused_plan(self.conv0p1s1.kernel_size)[0]
-            wide = [cm.mask_perms(3, 1 << i, self.MASK_GROUPS) if masked[i] else None for i in range(5)]
-            perm_ptrs = [w.data_ptr() if w is not None else None for w in wide] + plan.perm_ptrs[5:]
-        else:
-            perm_ptrs = [p if masked[i] else None for i, p in enumerate(plan.perm_ptrs[:5])] + plan.perm_ptrs[5:]
-        map_ptrs = plan.map_ptrs
+            wide = [cm.mask_perms(3, 1 << i, self.MASK_GROUPS) if n[i] >= self.masked_min_rows() else None for i in range(5)]
+            args = self.launch_args(plan, [w.data_ptr() if w is not None else None for w in wide])
+        rows, ws_bytes, c_maps, c_perms = args
         feats = x.F.contiguous()
         y = torch.empty((n[0], self.final.out_channels), dtype=torch.float32, device=dev)
-        rows = (ctypes.c_int64 * 5)(*n)
         # activations of the executor: scratch of this stream (dead when `y` is written; sizes differ from scene to scene)
         arena = _lib.scratch(dev, "net_arena", L.cv_net_arena_bytes(c_bufs, len(c_bufs), rows, 5))
-        sorted_levels = (ctypes.c_int * 5)(*[p is not None for p in perm_ptrs[:5]])
-        ws = ME._workspace(dev, L.cv_sp_scene_conv_workspace_bytes(rows, sorted_levels, self.MASK_GROUPS, max(self.PLANES)))
-        vp = ctypes.c_void_p
+        ws = ME._workspace(dev, ws_bytes)
         ext_ptr = (vp * 2)(feats.data_ptr(), y.data_ptr())
         ext_ld = (ctypes.c_int * 2)(feats.stride(0), y.stride(0))
-        c_maps = (vp * len(map_ptrs))(*map_ptrs)
-        c_perms = (vp * len(perm_ptrs))(*perm_ptrs)
         with torch.cuda.device(dev):
-            _lib.check(L.cv_net_run_f32(c_ops, len(c_ops), c_bufs, len(c_bufs), rows, 5, vp(arena.data_ptr()),
-                                        arena.numel(), ext_ptr, ext_ld, c_maps, len(map_ptrs), c_perms, len(perm_ptrs),
-                                        vp(ws.data_ptr()), ws.numel(), vp(flag.data_ptr()) if flag is not None else None,
-                                        vp(torch.cuda.current_stream(dev).cuda_stream)), "cv_net_run_f32")
+            _lib.check(L.cv_net_run_f32(c_ops, len(c_ops), c_bufs, len(c_bufs), rows, 5, ptr(arena), arena.numel(), ext_ptr,
+                                        ext_ld, c_maps, len(c_maps), c_perms, len(c_perms), ptr(ws), ws.numel(),
+                                        ptr(flag), stream(dev)), "cv_net_run_f32")
         out = x._like(y, 1)
         if flag is not None and not (self.defer_range_check if defer_check is None else defer_check):
             torch.cuda.current_stream(dev).synchronize()

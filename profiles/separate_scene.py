@@ -63,7 +63,7 @@ def whole_by_calls(models, hv, c4, feats, pts, X, S, P, ev):
         x = ME.SparseTensor(feats, c4, device=feats.device)
         for model in models.values():
             pipeline.head_separate(model(x).F)
-    dets = pipeline._separate_by_calls(hv, pts, X, S, P, RES, list(models), **SEPARATE)
+    dets = pipeline._separate_by_calls(hv, pts, zip(X, S, P), RES, list(models), **SEPARATE)
     ev[1].record()
     ev[2].record()
     return dets
