@@ -33,19 +33,27 @@ def _sources():
     """source -> extra flags, with the experiment switches of the environment as they are NOW (read per call, and part of
     the recorded command line: an object built with other -D flags is stale)"""
     env = lambda k: os.environ.get(k, "").split()
+    # kernel experiments (-DCV_WP_NPRE=27): sparse_conv_common.h reads the switch, so every file that includes it takes the flags
+    sc = env("CV_SC_DEFS")
     return {
+        # the sparse convolution, one kernel family per file; the slowest to compile first (build() starts its jobs in this order)
+        "conv_rows_wp.hip": sc,                          # product kernels: conv_rows_wp (24 instantiations: the longest job)
+        "conv_hd.hip": sc,                               #   conv_hd
+        "conv_hl.hip": sc,                               #   conv_hl
+        "conv_rows.hip": sc,                             #   conv_rows
+        "sparse_conv.hip": sc,                           # the dispatcher, the stem and the finish kernels
+        "sparse_train.hip": sc,                          # weight gradient, transposed map
+        "conv_prep.hip": sc,                             # weight packers, mask orders
+        "row_ops.hip": sc,                               # row kernels and heads, eval and training
         "cv_host.cpp": STRICT,
         "hv_vote.hip": STRICT + env("CV_HV_DEFS"),       # extra -D flags of an experiment (the file reads none today)
         "hv_decode.hip": STRICT + env("CV_DEC_DEFS"),    # extra -D flags of an experiment (the file reads none today)
         "sparse_coords.hip": [],
         "train_rows.hip": STRICT,                        # training batches from raw scans: the host's fp64 label and target bits
         "sym_loss.hip": STRICT,                          # separate-model pose loss: fp64 sums in the order written
-        "sparse_conv.hip": env("CV_SC_DEFS"),            # kernel experiments (-DCV_WP_NPRE=27)
-        "sparse_train.hip": [],                          # the training side: reads none of the CV_SC_DEFS switches
         "net_exec.cpp": [],
         "scene_exec.cpp": [],
     }
-
 
 
 def _stale(target, deps, cmd=None):
@@ -70,20 +78,27 @@ def _cmd_text(cmd):
     return "\n".join(c.replace(ROOT, "$ROOT") for c in cmd) + "\n"
 
 
-def build(force=False, verbose=False):
-    os.makedirs(OBJ_DIR, exist_ok=True)
+def _obj(src):
+    return os.path.join(OBJ_DIR, src + ".o")
+
+
+def _jobs(force=False):
+    """(source, object, command) of every source that has to be compiled now, in the order of _sources()"""
     headers = [os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".h")]
-    headers.append(os.path.join(ROOT, "include", "cv_hip.h"))
-    headers.append(os.path.abspath(__file__))
+    headers += [os.path.join(ROOT, "include", "cv_hip.h"), os.path.abspath(__file__)]
     jobs = []
-    objs = []
     for src, extra in _sources().items():
-        s = os.path.join(HERE, src)
-        o = os.path.join(OBJ_DIR, src + ".o")
-        objs.append(o)
+        s, o = os.path.join(HERE, src), _obj(src)
         cmd = [HIPCC] + COMMON + extra + (["-x", "hip"] if src.endswith(".cpp") else []) + ["-c", s, "-o", o]
         if force or _stale(o, [s] + headers, cmd):
-            jobs.append(cmd)
+            jobs.append((src, o, cmd))
+    return jobs
+
+
+def build(force=False, verbose=False):
+    os.makedirs(OBJ_DIR, exist_ok=True)
+    objs = [_obj(src) for src in _sources()]
+    jobs = [cmd for _, _, cmd in _jobs(force)]
 
     def run(cmd):
         if verbose:
@@ -111,15 +126,7 @@ def build(force=False, verbose=False):
 
 def plan(force=False):
     """the sources build() would compile now (tests: a changed CV_*_DEFS must show up here)"""
-    headers = [os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(".h")]
-    headers += [os.path.join(ROOT, "include", "cv_hip.h"), os.path.abspath(__file__)]
-    todo = []
-    for src, extra in _sources().items():
-        s, o = os.path.join(HERE, src), os.path.join(OBJ_DIR, src + ".o")
-        cmd = [HIPCC] + COMMON + extra + (["-x", "hip"] if src.endswith(".cpp") else []) + ["-c", s, "-o", o]
-        if force or _stale(o, [s] + headers, cmd):
-            todo.append(src)
-    return todo
+    return [src for src, _, _ in _jobs(force)]
 
 
 def ext_path():

@@ -113,7 +113,7 @@ int cv_sp_scene_plan_ex(const int32_t* d_input, long long n, int32_t* d_perm, in
                         bool bounds_prefilled);                                               // net_exec.cpp
 // d_ws: (sum of groups) * 2048 ints, zero-filled by the call unless pre_zeroed
 int cv_sp_mask_perms_batch(const CvPermJob* jobs, int n_jobs, void* d_ws, size_t ws_bytes, void* stream,
-                           bool pre_zeroed);                                                // sparse_conv.hip
+                           bool pre_zeroed);                                                // conv_prep.hip
 
 // cv_sp_conv_f32 over the model axis (cv_net_run_models_f32): `d` describes model 0; the operands of model m are model 0's
 // plus m x the byte strides (0 = shared), its packed weights / affine / acc_scale row m of d_params, its workspace

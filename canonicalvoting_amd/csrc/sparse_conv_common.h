@@ -1,6 +1,8 @@
-// What sparse_conv.hip (the forward kernels and everything else the eval path launches) and sparse_train.hip (the training
-// side) share: the launch arguments (ConvArgs, the model axis), the hl format, the fused epilogue, the bf16 / fp16 piece
-// splits, the LDS-DMA helpers of conv_hd and two host helpers.
+// What the sparse-convolution translation units share - sparse_conv.hip (the dispatcher, the stem and the finish kernels), one
+// file per product-kernel family (conv_rows.hip, conv_rows_wp.hip, conv_hl.hip, conv_hd.hip), conv_prep.hip (weight packers, mask orders),
+// row_ops.hip (row kernels, heads) and sparse_train.hip (weight gradient): the launch arguments (ConvArgs, the model axis),
+// the limits the dispatcher checks and the kernels are built for, the families' launchers, the hl format, the fused
+// epilogue, the bf16 / fp16 piece splits, the in-order sum, the LDS-DMA helpers of conv_hd and two host helpers.
 #pragma once
 #include "cv_common.h"
 
@@ -15,6 +17,15 @@ constexpr int KC = 32;            // K chunk (channels per staging step)
 constexpr int TM = 128;           // rows per workgroup
 constexpr int A_LD = TM + 2;      // A staged k-major: A_s[k][row]; +2 makes the 4-row-strided staging stores 2-way (free) instead of 4-way conflicted
 constexpr int THREADS = 256;
+
+// map rows a workgroup of conv_rows_wp / conv_hl / conv_hd keeps in LDS = most kernel offsets it may walk (the dispatcher splits a
+// launch further, or takes the second instance of conv_rows_wp, or the fp32 kernel conv_rows)
+#ifndef CV_WP_NPRE
+#define CV_WP_NPRE 10
+#endif
+constexpr int WP_NPRE = CV_WP_NPRE;          // the traffic cap of pick_splits leaves 9 offsets per workgroup on the training ts8 level
+constexpr int WP_NPRE_BIG = 28;              // the second instance: a whole 3x3x3 kernel in one workgroup (flavour 1, wide mask groups)
+constexpr int HL_MAX_UNITS = 512;      // live units of one workgroup: <= 10 offsets x Cin / 32 chunks + the second source's (host-checked)
 
 struct ConvArgs {
     const float* in; long long n_in; int in_ld; int cin;
@@ -108,6 +119,38 @@ __device__ __forceinline__ void model_enter_y(ConvArgs& a, const ModelArgs& ma) 
     model_sinks(a, ma, (int)blockIdx.y);
 }
 
+// One launch statement per kernel for the plain and the model-axis form: f() launches the kernel as it always was, f(*ma) its
+// ModelArgs instantiation (f is a generic lambda over `auto... m` that names kernel<..., decltype(m)...>).
+template <class F>
+void with_models(const ModelArgs* ma, F&& f) {
+    if (ma) f(*ma);
+    else f();
+}
+// A launcher's step from the run-time block count nb (1 ... MAX) to an instantiation: f(std::integral_constant<int, nb>)
+template <int MAX, class F>
+void with_nb(int nb, F&& f) {
+    if constexpr (MAX > 1) {
+        if (nb < MAX) return with_nb<MAX - 1>(nb, f);
+    }
+    f(std::integral_constant<int, MAX>{});
+}
+
+// Tile of a workgroup.  Mask-sorted orders end with the rows that need the most offsets: those tiles start FIRST so that
+// the light tiles fill the tail of the launch (longest-processing-time-first).
+__device__ __forceinline__ long long tile_of(const ConvArgs& a) {
+    return a.row_perm ? (long long)gridDim.x - 1 - blockIdx.x : blockIdx.x;
+}
+
+// ---- the product-kernel families, one translation unit each.  A launcher names the instantiation its arguments describe and
+// launches it on `grid`: which kernel runs, how it is sized and every check are the dispatcher's (launch_rows, sparse_conv.hip).
+// nb: 32-column blocks per workgroup (1-4; conv_hd 1-3).  ma: NULL, or the launch covers the models of grid.y (the ModelArgs instantiation).
+void launch_conv_rows(const ConvArgs& a, int nb, bool vec, dim3 grid, hipStream_t st);                     // conv_rows.hip
+void launch_conv_rows_wp(const ConvArgs& a, int nb, int pieces, bool npre_big, dim3 grid, hipStream_t st); // conv_rows_wp.hip: pieces 1 / 2 / 3,
+                                                                                                           // WP_NPRE or WP_NPRE_BIG map rows
+void launch_conv_hl(const ConvArgs& a, int nb, const ModelArgs* ma, dim3 grid, hipStream_t st);            // conv_hl.hip
+void launch_conv_hd(const ConvArgs& a, int nb, int hd_shape, const ModelArgs* ma, dim3 grid, hipStream_t st);   // conv_hd.hip: hd_shape as the
+                                                                                                           // option (0: 8 waves x 3 stages, 1: 4 x 2, 2: 8 x 2)
+
 // ---- hl format: activations stored as the fp16 pairs the matrix cores multiply --------------------------------------
 // A row of C channels (C % 32 == 0) keeps its 4*C bytes: 32-channel chunk q occupies bytes [128 q, 128 q + 128) =
 // 32 fp16 high pieces h = RNE16(x), then the 32 low pieces l = RNE16(x - h) (split2h below).  A convolution that reads
@@ -173,7 +216,8 @@ __device__ __forceinline__ void epilogue_apply1(const ConvArgs& a, long long row
     epilogue_apply1(a, row, col, v, a.scale ? a.scale[col] : 1.f, a.shift ? a.shift[col] : 0.f);
 }
 
-__device__ __forceinline__ void epilogue_store(const ConvArgs& a, const f32x16& acc, const int* rows,
+// (`used`: see epilogue_store_wide)
+__device__ __forceinline__ __attribute__((used)) void epilogue_store(const ConvArgs& a, const f32x16& acc, const int* rows,
                                                int col, int lane) {
     if (col >= a.cout) return;
     if (a.splits > 1) {
@@ -222,8 +266,14 @@ __device__ __forceinline__ void epilogue_apply4(const ConvArgs& a, long long row
 // 8 lanes write 128 contiguous bytes of one output row (4 dwordx4 stores per lane instead of 16 dword stores).
 // Measured with the instrumented twin (profiles/conv_phases.py): the dword epilogue was 63 % of the wave time
 // of the split ts16 convs and 20 % of the mask-sorted ts1 convs - it is store-ISSUE bound, not bandwidth bound.
+// `used`: hipcc optimises an inline function as a function of its own BEFORE it inlines it, with what it knows of the callers of the
+// translation unit - the range of `lane`, `acc` promoted to a value, a `colbase` that is 0 in every call - and the inlined code then
+// depends on which kernels share the file (conv_hl alone: 6 instructions more per kernel than in one file with conv_rows, whose
+// call tells it nothing).  A function with a use besides its calls is left as written until it is inlined: every kernel gets
+// the same epilogue whatever else its file holds (profiles/tu_split/tu_split_isa.txt).  The price is one uncalled copy per object.
+// The same holds for epilogue_store above (conv_rows_wp calls both).
 constexpr int EP_LD = 36;
-__device__ __forceinline__ void epilogue_store_wide(const ConvArgs& a, const f32x16& acc, const int* rows, int colbase,
+__device__ __forceinline__ __attribute__((used)) void epilogue_store_wide(const ConvArgs& a, const f32x16& acc, const int* rows, int colbase,
                                                     int lane, float (*T)[EP_LD]) {
     const int h = lane >> 5, c = lane & 31;
 #pragma unroll
@@ -296,7 +346,22 @@ __device__ __forceinline__ void split2h(float x0, float x1, unsigned& h, unsigne
 
 __device__ __forceinline__ void hl_split2(float x0, float x1, unsigned& h, unsigned& l) { split2h(x0, x1, h, l); }
 
-// ---- shared by the LDS-DMA kernels (conv_hd in sparse_conv.hip) ------------------------------------------------------------
+// p[0] + p[stride] + ... + p[(n - 1) * stride] in a fixed order (wgrad_reduce, col_sum_chunks): four interleaved running sums
+// (terms k % 4), combined as (s0 + s1) + (s2 + s3) - four independent load chains in flight, a result that depends on nothing else
+__device__ __forceinline__ float sum_in_order4(const float* __restrict__ p, int n, long long stride) {
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int k = 0;
+    for (; k + 3 < n; k += 4) {
+        s0 += p[k * stride];
+        s1 += p[(k + 1) * stride];
+        s2 += p[(k + 2) * stride];
+        s3 += p[(k + 3) * stride];
+    }
+    for (; k < n; ++k) s0 += p[k * stride];
+    return (s0 + s1) + (s2 + s3);
+}
+
+// ---- shared by the LDS-DMA kernels (conv_hd.hip) ---------------------------------------------------------------------------
 template <int... I, class F>
 __device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
     (f(std::integral_constant<int, I>{}), ...);

@@ -599,7 +599,7 @@ CONV_X6 = os.environ.get("CV_CONV_X6", "1") != "0"
 
 
 # Product precision of the vector-path convolutions (forward, input gradient, weight gradient):
-#   "fp32" (default): fp32-level products (bf16 triples / fp16 pairs, see sparse_conv.hip) - the parity path;
+#   "fp32" (default): fp32-level products (bf16 triples / fp16 pairs, see conv_rows_wp.hip) - the parity path;
 #   "bf16": operands rounded to bf16, one bf16 x bf16 product, fp32 accumulation and fp32 storage - the opt-in
 #           compute mode BASELINE configs 3-4 name for training (bench.py --dtype bf16); NOT within the 1e-4 bar.
 COMPUTE_DTYPE = "bf16" if os.environ.get("CV_COMPUTE_DTYPE", "fp32") == "bf16" else "fp32"
@@ -1296,18 +1296,14 @@ class _BNTrainFn(torch.autograd.Function):
                 # second step on: the factor comes from the maximum the step before left in the slot)
                 dx_hl = torch.empty_like(dx)
         with _on(dev):
-            if dx_hl is not None or bits is not None:
-                _lib.check(L.cv_sp_bn_backward_hl_f32(_ptr(x), _ptr(dy), _ptr(y_rows), n, c, x.stride(0), _ptr(stats[0]),
-                                                      _ptr(stats[1]), ctx.eps, _ptr(gamma), _ptr(dg[0]), _ptr(dg[1]),
-                                                      _ptr(dx), _ptr(dres) if y is not None else None, _ptr(ws), ws.numel(),
-                                                      _ptr(dx_hl), _ptr(slot) if dx_hl is not None else None,
-                                                      range_flag(dev).data_ptr(), _ptr(bits), _stream(dev)),
-                           "cv_sp_bn_backward_hl_f32")
-            else:
-                _lib.check(L.cv_sp_bn_backward_f32(_ptr(x), _ptr(dy), _ptr(y), n, c, x.stride(0), _ptr(stats[0]),
-                                                   _ptr(stats[1]), ctx.eps, _ptr(gamma), _ptr(dg[0]), _ptr(dg[1]),
-                                                   _ptr(dx), _ptr(dres) if y is not None else None, _ptr(ws), ws.numel(),
-                                                   _stream(dev)), "cv_sp_bn_backward_f32")
+            # (without a twin and without ReLU bits the trailing arguments are NULL: cv_sp_bn_backward_f32)
+            _lib.check(L.cv_sp_bn_backward_hl_f32(_ptr(x), _ptr(dy), _ptr(y_rows), n, c, x.stride(0), _ptr(stats[0]),
+                                                  _ptr(stats[1]), ctx.eps, _ptr(gamma), _ptr(dg[0]), _ptr(dg[1]),
+                                                  _ptr(dx), _ptr(dres) if y is not None else None, _ptr(ws), ws.numel(),
+                                                  _ptr(dx_hl), _ptr(slot) if dx_hl is not None else None,
+                                                  range_flag(dev).data_ptr() if dx_hl is not None or bits is not None else None,
+                                                  _ptr(bits),
+                                                  _stream(dev)), "cv_sp_bn_backward_hl_f32")
         if dx_hl is not None and usable:
             # (the entry holds dx itself: while it is in the table the allocator cannot hand dx's address to another gradient
             # tensor, so a twin whose consumer is not a _ConvFn - it then stays until the step's table is dropped - can never be

@@ -339,7 +339,7 @@ bound (tests/test_conv_bound.py shows both at Cin 32).
 
 Per path (u_prod, STEPS_PER_UNIT), from the kernel comments:
   "f32"   v_mfma_f32_32x32x2_f32, exact fp32 products (conv_rows, the wgrad pieces = 0 mode): u_prod = 0, 16 steps
-  "x6"    bf16 triples x = h + m + l (24 significant bits), six of the nine piece products (sparse_conv.hip, the
+  "x6"    bf16 triples x = h + m + l (24 significant bits), six of the nine piece products (conv_rows_wp.hip, the
           bf16x6 comment): the representation is exact and the three dropped products are <= 2^-24 relative each,
           u_prod = 2^-22; six 32x32x16 instructions per 16 channels: 12 steps
   "h2"    fp16 pairs x = h + l, h = RNE16(x), l = RNE16(x - h) (sparse_conv_common.h): each operand to 2^-24

@@ -310,16 +310,27 @@ def test_a_changed_define_makes_the_object_stale(built_lib, monkeypatch):
     for k in ("CV_HV_DEFS", "CV_DEC_DEFS", "CV_SC_DEFS"):
         monkeypatch.delenv(k, raising=False)
     assert b.plan() == []
+    # (CV_SC_DEFS: every file that includes sparse_conv_common.h, where CV_WP_NPRE is read)
+    sc = ["conv_rows_wp.hip", "conv_hd.hip", "conv_hl.hip", "conv_rows.hip", "sparse_conv.hip", "sparse_train.hip", "conv_prep.hip",
+          "row_ops.hip"]
     monkeypatch.setenv("CV_SC_DEFS", "-DX=1")
-    assert b.plan() == ["sparse_conv.hip"]
+    assert b.plan() == sc
     monkeypatch.setenv("CV_HV_DEFS", "-DHV_TX=16 -DHV_TW=8")
-    assert b.plan() == ["hv_vote.hip", "sparse_conv.hip"]
+    assert b.plan() == sc + ["hv_vote.hip"]
     monkeypatch.delenv("CV_SC_DEFS")
     monkeypatch.delenv("CV_HV_DEFS")
     assert b.plan() == []
     obj = os.path.join(b.OBJ_DIR, "cv_host.cpp.o")
     assert open(obj + ".cmd").read().split("\n")[0] == b.HIPCC and not b._stale(obj, [])
     assert b._stale(obj, [], ["another", "command"])
+
+
+def test_every_source_file_is_in_the_build():
+    """csrc/build.py lists its sources by name: a new translation unit that is not a key of _sources() fails here, not as an
+    undefined symbol when the library is loaded (hv_cuda_ext.cpp is the extension module, build_ext's own source)"""
+    from canonicalvoting_amd.csrc import build as b
+    on_disk = {f for f in os.listdir(b.HERE) if f.endswith((".hip", ".cpp"))} - {"hv_cuda_ext.cpp"}
+    assert on_disk == set(b._sources())
 
 
 def test_scene_call_refuses_bad_descriptors_before_touching_the_gpu(built_lib):

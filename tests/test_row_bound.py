@@ -138,7 +138,7 @@ def col_sum32(x, drop_chunk=None):
 
 
 def head_joint32(f, ncls, log_scale, background_rule=True, prob_over_all=False):
-    """head_joint of sparse_conv.hip in float32"""
+    """head_joint of row_ops.hip in float32"""
     n = f.shape[0]
     logit = f[:, 6 * ncls:7 * ncls + 1]
     am = logit.argmax(1)

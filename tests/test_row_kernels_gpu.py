@@ -4,7 +4,7 @@ tests/test_row_bound.py).  Every output lives in a sentinel-filled allocation (P
 [c, ld) of every row, PAD_ROWS rows below); misaligned and odd-ld operands are slices of larger allocations; workspaces are
 NaN-filled before every call.
 
-kernel -> test (every dispatch branch of the entry points):
+kernel (all of them in csrc/row_ops.hip) -> test (every dispatch branch of the entry points):
   affine_rows4            test_affine_sizes (c % 4 == 0), test_affine_switches, test_affine_in_place,
                           test_affine_grid_caps[rows4] (second grid-stride trip past 16384 blocks)
   affine_rows             test_affine_sizes (c = 3, 30), test_affine_scalar_reasons (c % 4, x_ld, y_ld, res_ld, base,
@@ -13,7 +13,8 @@ kernel -> test (every dispatch branch of the entry points):
   to_hl / from_hl         test_hl_format, test_hl_format_grid_cap (past 8192 blocks), test_hl_format_refusals
   bn_fold                 test_bn_fold
   col_sum                 test_col_sums (cv_sp_col_sum_f32), chunks 1, 2 and the 256 cap
-  col_sum_partial/_chunks test_col_sums (cv_sp_col_sum_det_f32)
+  col_sum_partial/_chunks test_col_sums (cv_sp_col_sum_det_f32); both block sums are one body, col_block_sum, and the chunk
+                          sum is sum_in_order4 of sparse_conv_common.h (shared with wgrad_reduce, sparse_train.hip)
   bn_col_reduce4<0>       test_bn_stats (c = 4 ... 1024: rl = 256 ... 1, idle threads at c = 96 and 384; n around the
                           four-rows-in-flight loop and the chunk thresholds), test_bn_stats_chunk_cap
   bn_col_reduce<0>        test_bn_stats_scalar (c % 4, c > 1024, odd ld, misaligned base)
@@ -25,7 +26,7 @@ kernel -> test (every dispatch branch of the entry points):
   bn_backward_apply4 twin test_backward_twin (slot maxima, scale exponent and its escapes, inverse word, range flag; grids
                           below and past the 4096-block cap), test_backward_refusals
   head_joint              test_head_joint
-  head_separate(_models)  test_head_separate
+  head_separate(_models)  test_head_separate (one row body, head_separate_row, under both)
 """
 import ctypes
 import functools
@@ -361,7 +362,7 @@ def col_data():
 
 @pytest.mark.parametrize("n", [1, 7, 8, 9, 1024, 1025, 262144, 262145])
 def test_col_sums(n):
-    """both entry points, ld > c; the chunk count restated from sparse_train.hip (1, 2 and the 256 cap)"""
+    """both entry points, ld > c; the chunk count restated from row_ops.hip (1, 2 and the 256 cap)"""
     x, buf = col_data()
     L = _lib.lib()
     chunks = col_chunks(n)
