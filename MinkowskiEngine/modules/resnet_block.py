@@ -1,1 +1,1 @@
-from canonicalvoting_amd.me.modules.resnet_block import BasicBlock  # noqa: F401
+from canonicalvoting_amd.me.modules.resnet_block import BasicBlock, Bottleneck  # noqa: F401

@@ -199,6 +199,15 @@ class SymRowsDesc(ctypes.Structure):
 SYM_ROWS_COUNTS = ("P", "S", "J", "T", "U", "max_row", "N", "rejected")     # the eight ints of cv_sym_rows_desc.d_counts
 
 
+class PropSelectDesc(ctypes.Structure):
+    """struct cv_prop_select_desc (include/cv_hip.h)"""
+    _fields_ = [("d_grid_scale", vp), ("d_yidx", vp), ("d_cdf", vp), ("dims", ctypes.c_int * 3), ("res", ctypes.c_float),
+                ("corner", ctypes.c_float * 3), ("d_seeds", vp), ("n_seeds", ctypes.c_int), ("radius", ctypes.c_float),
+                ("d_draws", vp), ("d_uniform", vp), ("rounds", ctypes.c_int), ("per_round", ctypes.c_int),
+                ("num_proposal", ctypes.c_int), ("start", ctypes.c_int), ("d_cand", vp), ("d_scale", vp),
+                ("d_info", vp), ("h_info", vp), ("d_ws", vp), ("ws_bytes", ctypes.c_size_t)]
+
+
 class PointsFront(ctypes.Structure):
     """struct cv_points_front (include/cv_hip.h)"""
     _fields_ = [("d_raw_points", vp), ("m", ctypes.c_longlong), ("points_ld", ctypes.c_longlong), ("points_f64", ctypes.c_int),
@@ -257,6 +266,11 @@ SIGNATURES = {
                                           ctypes.c_int, c_float_p, c_int_p, vp, vp, vp, vp]),
     "cv_hv_count_votes_f32": (ctypes.c_int, [vp, vp, vp, ctypes.c_int64, ctypes.c_float, ctypes.c_int,
                                              c_float_p, c_int_p, c_i64_p, vp, ctypes.c_size_t, vp]),
+    "cv_prop_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "cv_prop_columns_f32": (ctypes.c_int, [vp, c_int_p, ctypes.c_double, vp, vp, vp, vp, vp]),
+    "cv_prop_select_f32": (ctypes.c_int, [ctypes.POINTER(PropSelectDesc), vp]),
+    "cv_prop_cloud_ranges_i32": (ctypes.c_int, [vp, ctypes.c_longlong, ctypes.c_int, vp, vp, vp]),
+    "cv_sizeof_prop_select_desc": (ctypes.c_size_t, []),
     "cv_decode_workspace_bytes": (ctypes.c_size_t, [c_int_p, ctypes.c_int64, ctypes.c_int]),
     "cv_decode_f32": (ctypes.c_int, [vp, vp, vp, c_int_p, c_float_p, ctypes.c_float, vp, vp, vp, vp,
                                      ctypes.c_int64, ctypes.POINTER(DecodeParams), ctypes.c_int, vp,

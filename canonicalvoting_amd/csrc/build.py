@@ -48,6 +48,7 @@ def _sources():
         "cv_host.cpp": STRICT,
         "hv_vote.hip": STRICT + env("CV_HV_DEFS"),       # extra -D flags of an experiment (the file reads none today)
         "hv_decode.hip": STRICT + env("CV_DEC_DEFS"),    # extra -D flags of an experiment (the file reads none today)
+        "hv_proposals.hip": STRICT,                      # SUN RGB-D proposal sampler: the oracle's fp32 expressions as written
         "sparse_coords.hip": [],
         "train_rows.hip": STRICT,                        # training batches from raw scans: the host's fp64 label and target bits
         "sym_loss.hip": STRICT,                          # separate-model pose loss: fp64 sums in the order written

@@ -67,6 +67,12 @@ def _scalar(t, kind):
     return hit[1]
 
 
+def prime_scalar(t, value):
+    """Record ``value`` as the host value of the 0-dim device tensor ``t`` that was just created from it, so that the first
+    vote through ``t`` does not read it back (``_scalar`` still re-reads after any in-place change of ``t``)."""
+    t._cv_host_value = (t._version, value)
+
+
 _ptr, _stream = _lib.ptr, _lib.stream
 
 

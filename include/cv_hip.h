@@ -1010,7 +1010,60 @@ typedef struct cv_points_separate_result {
 } cv_points_separate_result;
 int cv_detect_points_f32(const cv_points_desc* desc, cv_points_result* result, void* stream);
 int cv_detect_points_separate_f32(const cv_points_separate_desc* desc, cv_points_separate_result* result, void* stream);
+/* ------------------------------------------------------------------------ *
+ * SUN RGB-D proposal sampler on the device (sunrgbd/brnetcanon.py:123-159 behind the 7-argument vote; hv_proposals.hip,
+ * DESIGN.md 4.2b).  Both entry points validate every field on the host before their first device call (CV_EINVAL with
+ * cv_last_error) and neither waits for the stream.  Built without FMA contraction: every expression is evaluated as written.
+ *
+ * cv_prop_columns_f32: d_grid_obj [X][Y][Z] (dims = X, Y, Z) -> per (x, z) column c = x * Z + z
+ *   m = maximum over y, d_yidx[c] = the FIRST y that attains it; NaN counts as the maximum and the first NaN wins
+ *   (torch.max / torch.argmax, numpy); d_dist[c] = (m + 1e-7f) ^ pow: sqrtf for pow == 0.5, else pow in fp64 rounded once.
+ *   A second launch of ONE workgroup: d_flags[1] = a non-finite dist was seen, d_flags[0] = uniform taken = that or the sum of
+ *   dist (fp64, fixed order) below 1e-7f - every dist is then 1.0f (:128-129); d_cdf[c] = inclusive prefix sum of dist in
+ *   fp64, non-decreasing, in an order that depends on X * Z alone: the same bytes on every run and stream.
+ *   dims > 0, X * Z <= 2^30, X * Y * Z < 2^31.
+ *
+ * cv_prop_select_f32: the while loop of :135-159 as ONE workgroup, over a budget of `rounds` rounds of `per_round` draws.
+ *   Exactly one of d_draws / d_uniform:
+ *     d_draws   int64 [rounds][per_round] flat indices into [X][Z] (an index outside the map is clamped into it);
+ *     d_uniform f32 [rounds][per_round] in [0, 1): t = u * d_cdf[last] in fp64, the cell is the first one whose cdf exceeds
+ *               t (bisection), the last cell when none does.
+ *   Per draw s: ix = s / Z, iz = s % Z, iy = d_yidx[s]; world = (float(i) * res) + corner (two fp32 roundings per component);
+ *   scale row = d_grid_scale[ix][iy][iz][:]; d2 = ((dx * dx + dy * dy) + dz * dz) in fp32 against every seed (a NaN wins the
+ *   minimum, as in torch.min); near = sqrtf(min d2) < radius.
+ *   Per round, in draw order: no draw near -> all per_round draws are kept, else the near ones; kept rows are appended at
+ *   start + rows kept so far, rows beyond num_proposal are dropped, and the walk stops as soon as num_proposal rows exist
+ *   (later rounds are not evaluated).  Only rows start .. filled - 1 of d_cand / d_scale [num_proposal][3] are written.
+ *   d_info = {filled, rounds_used of this call}; with h_info (page-locked) a copy of it is enqueued on the stream.
+ *   start > 0 continues a sample that a previous call left short.  d_ws: cv_prop_workspace_bytes of per_round.
+ *
+ * cv_prop_cloud_ranges_i32: per cloud b of a batched coordinate set d_coords4 [n][4] (batch, x, y, z; batch non-decreasing,
+ *   as cv_sp_quantize_* writes it) ONE launch, workgroup b: d_out[b] = {first row, end row, min x, y, z, max x, y, z}
+ *   (a cloud without rows: first = end, min = INT32_MAX, max = INT32_MIN); with h_out a copy is enqueued on the stream.
+ * ------------------------------------------------------------------------ */
+typedef struct cv_prop_select_desc {
+    const float* d_grid_scale;                 /* [X][Y][Z][3] */
+    const int32_t* d_yidx;                     /* [X * Z] (cv_prop_columns_f32); a value outside [0, Y) is clamped */
+    const double* d_cdf;                       /* [X * Z]; read in uniform mode only (may be NULL with d_draws) */
+    int dims[3];                               /* X, Y, Z */
+    float res; float corner[3];                /* cell edge, grid origin (corners[0]) */
+    const float* d_seeds; int n_seeds;         /* vote points [n_seeds][3], n_seeds >= 1 */
+    float radius;                              /* 0.3f */
+    const int64_t* d_draws; const float* d_uniform;       /* exactly one */
+    int rounds, per_round;                     /* >= 1 */
+    int num_proposal, start;                   /* P >= 1, 0 <= start <= P */
+    float* d_cand; float* d_scale;             /* [P][3] */
+    int32_t* d_info; int32_t* h_info;          /* {filled, rounds_used}; h_info may be NULL */
+    void* d_ws; size_t ws_bytes;
+} cv_prop_select_desc;
+size_t cv_prop_workspace_bytes(int per_round);
+int cv_prop_columns_f32(const float* d_grid_obj, const int* dims, double pow, float* d_dist, int32_t* d_yidx, double* d_cdf,
+                        int32_t* d_flags, void* stream);
+int cv_prop_select_f32(const cv_prop_select_desc* desc, void* stream);
+int cv_prop_cloud_ranges_i32(const int32_t* d_coords4, long long n, int n_clouds, int32_t* d_out, int32_t* h_out, void* stream);
+
 /* sizeof of the structures above as the LIBRARY was compiled (a binding that mirrors them field by field compares) */
+size_t cv_sizeof_prop_select_desc(void);
 size_t cv_sizeof_gather_job(void);
 size_t cv_sizeof_scan_rows_desc(void);
 size_t cv_sizeof_sym_loss_desc(void);
