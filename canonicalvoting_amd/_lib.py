@@ -179,6 +179,25 @@ class SymLossDesc(ctypes.Structure):
                 ("d_ws", vp), ("ws_bytes", ctypes.c_size_t)]
 
 
+class RowLossDesc(ctypes.Structure):
+    """struct cv_row_loss_desc (include/cv_hip.h)"""
+    _fields_ = [("d_out", vp), ("n_rows", ctypes.c_longlong), ("ld", ctypes.c_longlong),
+                ("d_labels", vp), ("d_xyz_labels", vp), ("d_scale_labels", vp),
+                ("heads", ctypes.c_int), ("n_logits", ctypes.c_int), ("xyz_col", ctypes.c_int), ("scale_col", ctypes.c_int),
+                ("logit_col", ctypes.c_int), ("obj_lo", ctypes.c_longlong), ("obj_hi", ctypes.c_longlong),
+                ("with_xyz", ctypes.c_int), ("log_scale", ctypes.c_int), ("gather", ctypes.c_int), ("empty", ctypes.c_int),
+                ("w", ctypes.c_float * 3), ("xyz_factor", ctypes.c_float), ("scale_factor", ctypes.c_float),
+                ("d_losses", vp), ("d_info", vp),
+                ("d_grad_loss", vp), ("d_grad", vp), ("grad_ld", ctypes.c_longlong), ("n_cols", ctypes.c_int),
+                ("d_ws", vp), ("ws_bytes", ctypes.c_size_t)]
+
+
+ROW_LOSS_GATHER = {"label": 0, "argmax": 1}         # CV_ROW_LOSS_GATHER_*
+ROW_LOSS_EMPTY = {"zero": 0, "nan": 1}              # CV_ROW_LOSS_EMPTY_*
+# layout -> (heads, n_logits, xyz_col, scale_col, logit_col, obj_lo, obj_hi, with_xyz); 'joint' for nclasses = 9
+ROW_LOSS_LAYOUTS = {"joint": (9, 10, 0, 27, 54, 0, 8, 1), "separate": (1, 2, 0, 3, 6, 1, 1, 0)}
+
+
 class SymRowsDesc(ctypes.Structure):
     """struct cv_sym_rows_desc (include/cv_hip.h)"""
     _fields_ = [("d_coords4", vp), ("d_index", vp), ("d_inverse", vp), ("d_quant_counts", vp), ("m_points", ctypes.c_longlong),
@@ -300,6 +319,11 @@ SIGNATURES = {
     "cv_sym_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int]),
     "cv_sym_loss_chunk_rows": (ctypes.c_int, []),
     "cv_sizeof_sym_loss_desc": (ctypes.c_size_t, []),
+    "cv_row_loss_fwd_f32": (ctypes.c_int, [ctypes.POINTER(RowLossDesc), vp]),
+    "cv_row_loss_bwd_f32": (ctypes.c_int, [ctypes.POINTER(RowLossDesc), vp]),
+    "cv_row_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "cv_row_loss_chunk_rows": (ctypes.c_int, []),
+    "cv_sizeof_row_loss_desc": (ctypes.c_size_t, []),
     "cv_sp_sym_rows_f32": (ctypes.c_int, [ctypes.POINTER(SymRowsDesc), vp]),
     "cv_sp_sym_rows_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.c_int]),
     "cv_sp_sym_rows_block": (ctypes.c_int, []),

@@ -52,6 +52,7 @@ def _sources():
         "sparse_coords.hip": [],
         "train_rows.hip": STRICT,                        # training batches from raw scans: the host's fp64 label and target bits
         "sym_loss.hip": STRICT,                          # separate-model pose loss: fp64 sums in the order written
+        "row_loss.hip": STRICT,                          # per-row losses of both trainers: fp64 terms and sums as written
         "net_exec.cpp": [],
         "scene_exec.cpp": [],
     }

@@ -3,7 +3,8 @@
 what a scene gathers behind it, scan_rows for what a training batch computes behind it, and quantize_nowait + sym_rows for
 the per-category trainer's batch with one host wait behind both), kaiming_normal_
 (utils/resnet.py:112); sym_loss, the per-category trainer's coordinate loss over packed symmetry labels
-(train_separate.py:265-280)."""
+(train_separate.py:265-280); row_loss, the per-row losses of both trainers and the joint trainer's validation form
+(train_joint.py:253-283, :311-340)."""
 import ctypes
 import math
 
@@ -353,6 +354,95 @@ def sym_loss(out_feats, sym, weights=(1.0, 1.0, 1.0), xyz_factor=1.0, return_pos
     Bit-reproducible: no atomics, every sum in an order the labels fix.  return_poses: also (pose losses [J], best pose [S])."""
     loss, pose_loss, best = _SymLossFn.apply(out_feats, sym, tuple(float(v) for v in weights), float(xyz_factor))
     return (loss, pose_loss, best) if return_poses else loss
+
+
+def row_loss_layout(layout, nclasses=9):
+    """(heads, n_logits, xyz_col, scale_col, logit_col, obj_lo, obj_hi, with_xyz) of cv_row_loss_desc: 'joint' = the
+    [N, 7 nclasses + 1] output (objects 0 .. nclasses - 1), 'separate' = the per-category [N, 8] output (object = label 1; its
+    coordinate term stays with sym_loss)"""
+    if layout == "joint":
+        return (nclasses, nclasses + 1, 0, 3 * nclasses, 6 * nclasses, 0, nclasses - 1, 1)
+    if layout == "separate":
+        return _lib.ROW_LOSS_LAYOUTS["separate"]
+    raise ValueError("row_loss: layout %r is neither 'joint' nor 'separate'" % (layout,))
+
+
+def _row_loss_desc(out_feats, labels, xyz_labels, scale_labels, cfg):
+    """cv_row_loss_desc of the network output and its per-row labels, outputs and workspace still unset"""
+    layout, gather, empty, log_scale, weights, xyz_factor, scale_factor = cfg
+    dev, n = out_feats.device, out_feats.shape[0]
+    assert out_feats.is_cuda and out_feats.dtype == torch.float32 and out_feats.dim() == 2 and out_feats.stride(1) == 1, \
+        "out_feats: float32 [N, C] device rows"
+    assert labels.device == dev and labels.dtype == torch.int64 and labels.shape == (n,) and labels.is_contiguous(), \
+        "labels: int64 [N] on the output's device"
+    for name, t in (("xyz_labels", xyz_labels), ("scale_labels", scale_labels)):
+        assert t is None or (t.device == dev and t.dtype == torch.float32 and t.shape == (n, 3) and t.is_contiguous()), \
+            "%s: float32 [N, 3] on the output's device" % name
+    d = _lib.RowLossDesc()
+    d.d_out, d.n_rows, d.ld = _ptr_if_any(out_feats), n, out_feats.stride(0) if n > 1 else out_feats.shape[1]
+    d.d_labels, d.d_xyz_labels, d.d_scale_labels = _ptr_if_any(labels), _ptr_if_any(xyz_labels), _ptr_if_any(scale_labels)
+    d.heads, d.n_logits, d.xyz_col, d.scale_col, d.logit_col, d.obj_lo, d.obj_hi, d.with_xyz = layout
+    d.log_scale, d.gather, d.empty = int(bool(log_scale)), _lib.ROW_LOSS_GATHER[gather], _lib.ROW_LOSS_EMPTY[empty]
+    d.w = (ctypes.c_float * 3)(*weights)
+    d.xyz_factor, d.scale_factor = xyz_factor, scale_factor
+    return d
+
+
+class _RowLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out_feats, labels, xyz_labels, scale_labels, cfg):
+        L = _lib.lib()
+        dev = out_feats.device
+        out_feats = out_feats if out_feats.stride(1) == 1 else out_feats.contiguous()
+        d = _row_loss_desc(out_feats, labels, xyz_labels, scale_labels, cfg)
+        losses = torch.empty(4, dtype=torch.float32, device=dev)
+        info = torch.empty(2, dtype=torch.int32, device=dev)
+        ws = _lib.scratch(dev, "row_loss", int(L.cv_row_loss_workspace_bytes(d.n_rows)))
+        d.d_losses, d.d_info, d.d_ws, d.ws_bytes = _ptr(losses), _ptr(info), _ptr(ws), ws.numel()
+        with torch.cuda.device(dev):
+            _lib.check(L.cv_row_loss_fwd_f32(ctypes.byref(d), _stream(dev)), "cv_row_loss_fwd_f32")
+        ctx.save_for_backward(out_feats, labels, xyz_labels, scale_labels, info)
+        ctx.cfg = cfg
+        parts = losses[:3].clone()                 # (the parts are reported, the gradient flows through the total)
+        ctx.mark_non_differentiable(parts, info)
+        return losses[3], parts, info
+
+    @staticmethod
+    def backward(ctx, grad_total, _grad_parts, _grad_info):
+        out_feats, labels, xyz_labels, scale_labels, info = ctx.saved_tensors
+        dev = out_feats.device
+        grad = torch.empty(out_feats.shape, dtype=torch.float32, device=dev)        # every element is written by the launch
+        gl = grad_total.to(torch.float32).reshape(1).contiguous()
+        d = _row_loss_desc(out_feats, labels, xyz_labels, scale_labels, ctx.cfg)
+        d.d_info, d.d_grad_loss, d.d_grad = _ptr(info), _ptr(gl), _ptr_if_any(grad)
+        d.grad_ld, d.n_cols = grad.stride(0) if grad.shape[0] > 1 else grad.shape[1], grad.shape[1]
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().cv_row_loss_bwd_f32(ctypes.byref(d), _stream(dev)), "cv_row_loss_bwd_f32")
+        return grad, None, None, None, None
+
+
+def row_loss(out_feats, labels, xyz_labels, scale_labels, *, layout="joint", gather="label", empty="zero", nclasses=9,
+             log_scale=True, weights=(1.0, 1.0, 1.0), xyz_factor=1.0, scale_factor=1.0, return_info=False):
+    """The per-row losses of a trainer on the device (cv_row_loss_fwd_f32 / cv_row_loss_bwd_f32: two launches forward, one
+    backward, on torch's current stream, no host wait): the masked squared errors of the chosen head's coordinate and scale
+    columns and the cross entropy of the logits, as include/cv_hip.h defines them.  ``out_feats`` [N, C] float32,
+    ``labels`` [N] (any integer dtype), ``xyz_labels`` / ``scale_labels`` [N, 3]; layout 'joint' ([N, 7 nclasses + 1]) or
+    'separate' ([N, 8]; no coordinate term, ``xyz_labels`` may be None).  gather 'label' (training) or 'argmax' (the
+    validation form, no gradient); empty 'zero' (no object row: zero terms) or 'nan' (the reference's mean over nothing).
+    Returns the device scalars (loss_xyz, loss_scale, loss_class, total); the gradient flows through ``total`` (the three
+    parts are reported values).  return_info: also the int32 pair (object rows, labels above the last logit)."""
+    if gather not in _lib.ROW_LOSS_GATHER or empty not in _lib.ROW_LOSS_EMPTY:
+        raise ValueError("row_loss: gather %r / empty %r" % (gather, empty))
+    lay = row_loss_layout(layout, nclasses)
+    if gather == "argmax" and out_feats.requires_grad and torch.is_grad_enabled():
+        out_feats = out_feats.detach()
+    dev = out_feats.device
+    prep = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()
+    cfg = (lay, gather, empty, bool(log_scale), tuple(float(v) for v in weights), float(xyz_factor), float(scale_factor))
+    total, parts, info = _RowLossFn.apply(out_feats, labels.to(device=dev, dtype=torch.int64).contiguous(),
+                                          prep(xyz_labels) if lay[7] else None, prep(scale_labels), cfg)
+    res = (parts[0], parts[1], parts[2], total)
+    return res + (info,) if return_info else res
 
 
 def sparse_quantize(coordinates, features=None, labels=None, quantization_size=None, return_index=False,

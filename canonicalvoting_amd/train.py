@@ -14,7 +14,15 @@
 
 The sparse convolutions run forward / input-gradient / weight-gradient on the HIP kernels
 (canonicalvoting_amd.me._ConvFn), batch-statistics BatchNorm with the residual add and ReLU folded in on
-bn_col_reduce4 / bn_backward_apply4 (me._BNTrainFn); the losses are torch ops, except the packed pose loss (sym_loss.hip).
+bn_col_reduce4 / bn_backward_apply4 (me._BNTrainFn).  The losses are torch ops by default; the packed pose loss always runs on
+sym_loss.hip, and with ``device_loss=True`` (train_step, train_step_separate; ``device_rows=True`` of separate_loss_packed) the
+per-row terms - head gather, masked squared errors, cross entropy and their backward - run on row_loss.hip instead
+(joint_loss_device: two launches forward, one backward, no host wait).
+
+    joint_loss_device   joint_loss on the row-loss kernels, the same arguments and keys
+    joint_loss_val      the validation form (train_joint.py:311-340): head by the predicted class, NaN without object rows
+    validate_joint      the trainer's validation pass (train_joint.py:293-430): losses, detections and mAP per scan list
+
 The reference's stale-loss bug (`losses` persists across iterations) is not
 reproduced: a batch without object points contributes only the classification loss.
 """
@@ -60,6 +68,29 @@ def joint_loss(out_feats, xyz_labels, scale_labels, class_labels, nclasses=9, lo
     return sum(losses.values()), losses
 
 
+def joint_loss_device(out_feats, xyz_labels, scale_labels, class_labels, nclasses=9, log_scale=True,
+                      xyz_factor=1.0, scale_factor=1.0, xyz_component_weights=(1.0, 1.0, 1.0)):
+    """joint_loss on the device (ME.utils.row_loss, cv_row_loss_fwd_f32 / cv_row_loss_bwd_f32): the same arguments, the same
+    ``(total, {"loss_scale", "loss_xyz", "loss_class"})``; fp64 terms and sums rounded once, the same bytes on every run, no
+    host wait.  The gradient flows through ``total``; the three parts are reported values without one."""
+    loss_xyz, loss_scale, loss_class, total = ME.utils.row_loss(
+        out_feats, class_labels, xyz_labels, scale_labels, layout="joint", gather="label", empty="zero", nclasses=nclasses,
+        log_scale=log_scale, weights=xyz_component_weights, xyz_factor=xyz_factor, scale_factor=scale_factor)
+    return total, {"loss_scale": loss_scale, "loss_xyz": loss_xyz, "loss_class": loss_class}
+
+
+def joint_loss_val(out_feats, xyz_labels, scale_labels, class_labels, nclasses=9, log_scale=True,
+                   xyz_factor=1.0, scale_factor=1.0, xyz_component_weights=(1.0, 1.0, 1.0)):
+    """The validation losses of train_joint.py:311-340 on the device, without a gradient: the head is chosen by the PREDICTED
+    class (argmax of the logits, class ``nclasses`` -> head 0, :315-316), not by the label, and a scan without an object row
+    gives NaN for loss_xyz and loss_scale - the reference's mean over nothing (:331-332).  Same return form as joint_loss."""
+    with torch.no_grad():
+        loss_xyz, loss_scale, loss_class, total = ME.utils.row_loss(
+            out_feats, class_labels, xyz_labels, scale_labels, layout="joint", gather="argmax", empty="nan", nclasses=nclasses,
+            log_scale=log_scale, weights=xyz_component_weights, xyz_factor=xyz_factor, scale_factor=scale_factor)
+    return total, {"loss_scale": loss_scale, "loss_xyz": loss_xyz, "loss_class": loss_class}
+
+
 def separate_loss(out_feats, xyz_labels, scale_labels, obj_labels, coords4=None, log_scale=True, xyz_factor=1.0,
                   scale_factor=1.0, xyz_component_weights=(1.0, 1.0, 1.0), reference_indexing=True):
     """Loss of the per-category model (train_separate.py:247-287): out_feats [N, 8] = xyz, (log) scale, 2 objectness
@@ -92,7 +123,7 @@ def separate_loss(out_feats, xyz_labels, scale_labels, obj_labels, coords4=None,
 
 
 def separate_loss_packed(out_feats, sym, scale_labels, obj_labels, log_scale=True, xyz_factor=1.0, scale_factor=1.0,
-                         xyz_component_weights=(1.0, 1.0, 1.0)):
+                         xyz_component_weights=(1.0, 1.0, 1.0), device_rows=False):
     """separate_loss - the same three terms under the same keys - over packed symmetry labels, without a host wait.
     ``sym``: a data.SymBatch on the output's device (data.collate_sym + data.sym_to_device; which indexing its rows follow
     was decided in the collate).  Its largest row is compared with the output's rows here, from the host int, before anything
@@ -100,9 +131,18 @@ def separate_loss_packed(out_feats, sym, scale_labels, obj_labels, log_scale=Tru
     models; two launches forward, one backward).  loss_obj: the same cross entropy.  loss_scale: in joint_loss's form - the
     object count stays on the device as the denominator and background rows are selected away in front of the arithmetic,
     so a non-finite background prediction reaches neither the loss nor a gradient, and a batch without an object row gives
-    a zero term where separate_loss's mean over nothing gives NaN."""
+    a zero term where separate_loss's mean over nothing gives NaN.
+    ``device_rows``: loss_scale and loss_obj come from ME.utils.row_loss(layout='separate') (row_loss.hip) instead of torch
+    ops, loss_xyz still from sym_loss; the two gradients stay two autograd outputs that torch adds.  The gradient of the row
+    terms then flows through the total only (the two parts are reported values)."""
     if sym.max_row >= out_feats.shape[0]:
         raise ValueError("separate_loss_packed: label row %d outside the %d output rows" % (sym.max_row, out_feats.shape[0]))
+    if device_rows:
+        _, loss_scale, loss_obj, rows_total = ME.utils.row_loss(
+            out_feats, obj_labels, None, scale_labels, layout="separate", gather="label", empty="zero", log_scale=log_scale,
+            weights=xyz_component_weights, scale_factor=scale_factor)
+        loss_xyz = ME.utils.sym_loss(out_feats, sym, xyz_component_weights, xyz_factor)
+        return rows_total + loss_xyz, {"loss_obj": loss_obj, "loss_scale": loss_scale, "loss_xyz": loss_xyz}
     obj = obj_labels.long()
     m = (obj == 1)[:, None]
     w = torch.as_tensor(xyz_component_weights, dtype=out_feats.dtype, device=out_feats.device)
@@ -271,8 +311,9 @@ def _run_step(model, optimizer, dev, forward_loss):
     return loss.detach(), {k: v.detach() for k, v in parts.items()}
 
 
-def train_step(model, optimizer, coords4, feats, xyz_labels, scale_labels, class_labels, **loss_kw):
-    """one iteration of train_joint.py:246-288; feats already recentred (:248-249).
+def train_step(model, optimizer, coords4, feats, xyz_labels, scale_labels, class_labels, device_loss=False, **loss_kw):
+    """one iteration of train_joint.py:246-288; feats already recentred (:248-249).  ``device_loss``: joint_loss_device (the
+    row-loss kernels) instead of joint_loss (torch ops).
 
     The forward multiplies fp16 pairs on the eval path's kernels (ME.TRAIN_FWD_HL); an activation beyond the fp16 range - never
     behind a healthy BatchNorm - raises the range flag.  With a fused Adam the flag rides to the optimizer as `found_inf`: the
@@ -288,7 +329,7 @@ def train_step(model, optimizer, coords4, feats, xyz_labels, scale_labels, class
 
     def forward_loss():
         out = model(ME.SparseTensor(feats, coords4, device=dev))
-        return joint_loss(out.F, xyz_labels, scale_labels, class_labels, **loss_kw)
+        return (joint_loss_device if device_loss else joint_loss)(out.F, xyz_labels, scale_labels, class_labels, **loss_kw)
 
     return _run_step(model, optimizer, dev, forward_loss)
 
@@ -297,7 +338,7 @@ def _is_sym_batch(labels):
     return isinstance(labels, tuple) and hasattr(labels, "seg_ptr") and hasattr(labels, "n_segments")
 
 
-def train_step_separate(model, optimizer, coords4, feats, xyz_labels, scale_labels, obj_labels, **loss_kw):
+def train_step_separate(model, optimizer, coords4, feats, xyz_labels, scale_labels, obj_labels, device_loss=False, **loss_kw):
     """one iteration of train_separate.py:236-292 (8-channel per-category model); feats already recentred (:241-242).
     Returns None for a batch without object points, which the reference skips (:238-240).
 
@@ -305,6 +346,7 @@ def train_step_separate(model, optimizer, coords4, feats, xyz_labels, scale_labe
     hints, the batched weight pack, the range flag as `found_inf`, the BatchNorm snapshot guard, the bf16-triples fallback and
     the DDP flag agreement (_run_step) - around separate_loss_packed, with no host wait: the skip is ``n_segments == 0``, a
     host int.  The labels may still be on the host (copied non-blocking here) or already on the device (data.sym_to_device).
+    ``device_loss`` (packed labels only): separate_loss_packed(device_rows=True).
     ``xyz_labels`` the nested lists of data.collate_fn_separate: the plain forward -> separate_loss -> backward -> step."""
     dev = feats.device
     if _is_sym_batch(xyz_labels):
@@ -318,9 +360,11 @@ def train_step_separate(model, optimizer, coords4, feats, xyz_labels, scale_labe
 
         def forward_loss():
             out = model(ME.SparseTensor(feats, coords4, device=dev))
-            return separate_loss_packed(out.F, sym, scale_dev, obj_dev, **loss_kw)
+            return separate_loss_packed(out.F, sym, scale_dev, obj_dev, device_rows=device_loss, **loss_kw)
 
         return _run_step(model, optimizer, dev, forward_loss)
+    if device_loss:
+        raise ValueError("train_step_separate: device_loss needs packed labels (data.collate_sym)")
     if not bool((obj_labels == 1).any()):
         return None
     optimizer.zero_grad(set_to_none=True)
@@ -329,6 +373,56 @@ def train_step_separate(model, optimizer, coords4, feats, xyz_labels, scale_labe
     loss.backward()
     optimizer.step()
     return loss.detach(), {k: v.detach() for k, v in parts.items()}
+
+
+def validate_joint(model, hv, batches, res, gt_boxes=None, nclasses=9, log_scale=True, xyz_factor=1.0, scale_factor=1.0,
+                   xyz_component_weights=(1.0, 1.0, 1.0), **decode_kw):
+    """The validation pass of train_joint.py:293-430.  ``batches`` yields one scan at a time (batch size 1):
+    ``(id_scan, coords4, feats, xyz_labels, scale_labels, class_labels)`` on the model's device, feats already recentred
+    (:305-306).  Per scan ONE eval-mode forward under no_grad (pipeline.detect_scene's, its fp16-range check included),
+    joint_loss_val on that output (:311-340), then pipeline.head_joint and vote, decode and per-class NMS on the same output
+    (decode.detect, :342-439); the detections go into ``pred_map_cls[id_scan]``.
+    Returns a dict: ``losses`` = the mean of loss / loss_xyz / loss_scale / loss_class over the scans (the per-scan values
+    stay on the device and are read once at the end; a scan without an object row makes the two means NaN, as the
+    reference's values are), ``pred_map_cls``, ``n_scans`` and - with ``gt_boxes`` {id_scan: lines ``tx ty tz ry sx sy sz ...
+    category`` as in cfg.data.gt_path} - ``map`` = {0.25: ..., 0.5: ...} from calc_map.compute_map.
+    The model is put back into the mode it was in; eval-mode BatchNorm leaves the running statistics untouched."""
+    from . import calc_map, decode, hv_cuda, pipeline
+    from .data import parse_gt_lines
+    was_training = model.training
+    model.eval()
+    kw = dict(nclasses=nclasses, log_scale=log_scale, xyz_factor=xyz_factor, scale_factor=scale_factor,
+              xyz_component_weights=xyz_component_weights)
+    pred_map_cls, per_scan = {}, []
+    try:
+        with torch.no_grad():
+            for id_scan, coords4, feats, xyz_labels, scale_labels, class_labels in batches:
+                dev = feats.device
+                scan_points = (coords4[:, 1:].to(dev) * res).float().contiguous()
+                hv_cuda.prefetch_geometry(scan_points)
+                x = ME.SparseTensor(feats, coords4, device=dev)
+                deferred = hasattr(model, "check_range")
+                y = model(x, defer_check=True) if deferred else model(x)
+                for attempt in range(2):
+                    total, parts = joint_loss_val(y.F, xyz_labels.to(dev), scale_labels.to(dev), class_labels.to(dev), **kw)
+                    xyz, scale, prob, cls = pipeline.head_joint(y.F, nclasses, log_scale)
+                    dets, _ = decode.detect(hv, coords4[:, 1:], xyz, scale, prob, cls, res, nclasses, scan_points=scan_points,
+                                            **decode_kw)
+                    y2 = model.check_range(x, y) if (deferred and attempt == 0) else y
+                    if y2 is y:
+                        break
+                    y = y2
+                pred_map_cls[id_scan] = dets
+                per_scan.append(torch.stack([total, parts["loss_xyz"], parts["loss_scale"], parts["loss_class"]]))
+    finally:
+        model.train(was_training)
+    out = {"pred_map_cls": pred_map_cls, "n_scans": len(per_scan)}
+    mean = torch.stack(per_scan).mean(0).tolist() if per_scan else [float("nan")] * 4       # the one host read
+    out["losses"] = dict(zip(("loss", "loss_xyz", "loss_scale", "loss_class"), mean))
+    if gt_boxes is not None:
+        gt_map_cls = {i: [(c, calc_map.gt_box(*p)) for c, p in parse_gt_lines(gt_boxes[i])] for i in pred_map_cls}
+        out["map"] = {thr: calc_map.compute_map(pred_map_cls, gt_map_cls, thr) for thr in (0.25, 0.5)}
+    return out
 
 
 def adjust_learning_rate(optimizer, epoch, base_lr=1e-3, decay_steps=(80, 120, 160), decay_rates=(0.1, 0.1, 0.1)):

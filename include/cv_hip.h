@@ -53,7 +53,10 @@ extern "C" {
  *    (additive: no struct or signature moved).
  *    Still 6: cv_sp_sym_rows_f32 (cv_sym_rows_desc) with cv_sp_sym_rows_workspace_bytes, cv_sp_sym_rows_block,
  *    cv_sp_sym_rows_scan_span and cv_sizeof_sym_rows_desc, the separate-model training batch (packed symmetry labels and row
- *    arrays) from raw scans (additive: no struct or signature moved). */
+ *    arrays) from raw scans (additive: no struct or signature moved).
+ *    Still 6: cv_row_loss_fwd_f32 / cv_row_loss_bwd_f32 (cv_row_loss_desc) with cv_row_loss_workspace_bytes,
+ *    cv_row_loss_chunk_rows and cv_sizeof_row_loss_desc, the per-row training losses of both models (masked squared errors of
+ *    the chosen head and the cross entropy) and the validation form of the joint one (additive: no struct or signature moved). */
 #define CV_ABI_VERSION 6
 int cv_abi_version(void);
 const char* cv_last_error(void);
@@ -362,6 +365,60 @@ int cv_sym_loss_fwd_f32(const cv_sym_loss_desc* desc, void* stream);
 int cv_sym_loss_bwd_f32(const cv_sym_loss_desc* desc, void* stream);
 size_t cv_sym_loss_workspace_bytes(long long n_targets, int n_jobs);
 int cv_sym_loss_chunk_rows(void);           /* rows per workgroup of the partial pass: the chunking the sums are ordered by */
+
+/* The per-row losses of both trainers over the network output d_out [n_rows][ld] fp32 (train_joint.py:253-283 and :311-340,
+ * train_separate.py:247-262): the masked squared errors of the chosen head's coordinate and scale columns and the cross
+ * entropy of the logit columns.  Per row i with label y = d_labels[i] (int64):
+ *   obj     = obj_lo <= y <= obj_hi
+ *   head h  = gather LABEL: y on object rows, else 0;  gather ARGMAX: the first maximum of the n_logits logits (fp32 `>`, as
+ *             cv_head_joint_f32 compares), the LAST logit mapping to 0 (train_joint.py:315-316);  heads == 1: always 0
+ *   e_xyz   = sum_c w[c] * (out[xyz_col + 3 h + c] - xyz_labels[i][c])^2            object rows, with_xyz only
+ *   e_scale = sum_c w[c] * (out[scale_col + 3 h + c] - t[c])^2, t = log(scale_labels[i]) with log_scale      object rows
+ *   ce      = lse - logit[target], target = y, a NEGATIVE label counting as n_logits - 1; the maximum is subtracted before exp
+ * Background rows: predictions and targets are selected away in front of the arithmetic - a NaN or Inf there reaches neither
+ * a loss nor a gradient.  A label above n_logits - 1 cannot be seen from the host: it makes loss_class (and that row's logit
+ * gradients) NaN and is counted in d_info[1]; nothing aborts.
+ *   cnt        = object rows -> d_info[0]
+ *   denom      = empty ZERO: max(3 cnt, 1) (a batch without object rows gives zero terms: the training form);
+ *                empty NAN: 3 cnt (no object row gives NaN, the reference's mean over nothing: the validation form)
+ *   d_losses   = {loss_xyz = xyz_factor * sum e_xyz / denom, loss_scale = scale_factor * sum e_scale / denom,
+ *                 loss_class = sum ce / n_rows, total = (loss_scale + loss_xyz) + loss_class in fp32}
+ * Terms and sums are fp64 from the fp32 inputs, each output is rounded to fp32 once.  No atomics: a workgroup sums
+ * cv_row_loss_chunk_rows() rows in a fixed order and writes four fp64 partials (and its count of labels above n_logits - 1)
+ * to the workspace, ONE workgroup adds the partials (each lane a contiguous stretch in order, then a fixed tree over the
+ * lanes; any number of partials).  The order depends on n_rows, the column layout and the chunk alone: the same bytes on
+ * every run and stream.
+ * forward:  two launches; writes d_losses [4] and d_info [2]; d_ws: cv_row_loss_workspace_bytes(n_rows), else CV_ENOMEM (the
+ *           message names the size).  n_rows == 0: d_losses = 0 (NaN with empty NAN), d_info = 0, nothing else is launched.
+ * backward: gather LABEL only (ARGMAX: CV_EINVAL).  One launch; reads d_grad_loss[0] and d_info[0] (the forward's cnt; lse is
+ *           recomputed) on the device and writes EVERY element of columns [0, n_cols) of d_grad [n_rows][grad_ld] exactly
+ *           once - the caller zeroes nothing: the chosen head's columns of object rows get
+ *           g * factor * 2 * w[c] * (p - t) / denom, the logit columns g * (softmax_k - [k == target]) / n_rows, every other
+ *           column an exact 0.  Columns from n_cols on are not touched.
+ * Every field is validated before the first device call (CV_EINVAL: null pointer, ld or n_cols below the last used column,
+ * overlapping column ranges, negative count, n_rows of 2^31 or more, heads < 1, n_logits < 2 or > 16, obj_lo < 0 or
+ * obj_hi >= heads with heads > 1, ARGMAX with n_logits - 1 > heads > 1, more than 8192 words for 16 staged rows).
+ * Asynchronous on `stream`. */
+#define CV_ROW_LOSS_GATHER_LABEL 0
+#define CV_ROW_LOSS_GATHER_ARGMAX 1
+#define CV_ROW_LOSS_EMPTY_ZERO 0
+#define CV_ROW_LOSS_EMPTY_NAN 1
+typedef struct cv_row_loss_desc {
+    const float* d_out; long long n_rows; long long ld;
+    const int64_t* d_labels;                                      /* [n_rows] */
+    const float* d_xyz_labels; const float* d_scale_labels;       /* [n_rows][3] each; d_xyz_labels may be NULL without with_xyz */
+    int heads; int n_logits; int xyz_col; int scale_col; int logit_col;
+    long long obj_lo; long long obj_hi;                           /* inclusive */
+    int with_xyz; int log_scale; int gather; int empty;
+    float w[3]; float xyz_factor; float scale_factor;
+    float* d_losses; int32_t* d_info;                             /* forward: written [4], [2]; backward: d_info[0] read */
+    const float* d_grad_loss; float* d_grad; long long grad_ld; int n_cols;      /* backward only */
+    void* d_ws; size_t ws_bytes;                                  /* forward only */
+} cv_row_loss_desc;
+int cv_row_loss_fwd_f32(const cv_row_loss_desc* desc, void* stream);
+int cv_row_loss_bwd_f32(const cv_row_loss_desc* desc, void* stream);
+size_t cv_row_loss_workspace_bytes(long long n_rows);
+int cv_row_loss_chunk_rows(void);           /* rows per workgroup of the partial pass: the chunking the sums are ordered by */
 
 /* The per-category trainer's batch from raw scans, behind the voxeliser and with NO host wait in front: the packed symmetry
  * labels cv_sym_loss_* consume (data.SymBatch) and the per-row arrays, from raw per-vertex arrays plus per-model vertex
@@ -1067,6 +1124,7 @@ size_t cv_sizeof_prop_select_desc(void);
 size_t cv_sizeof_gather_job(void);
 size_t cv_sizeof_scan_rows_desc(void);
 size_t cv_sizeof_sym_loss_desc(void);
+size_t cv_sizeof_row_loss_desc(void);
 size_t cv_sizeof_sym_rows_desc(void);
 size_t cv_sizeof_points_desc(void);
 size_t cv_sizeof_points_separate_desc(void);

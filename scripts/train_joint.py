@@ -5,9 +5,14 @@ through torch.distributed.run (the reference is single-GPU).
 
     python scripts/train_joint.py [--epochs 2] [--scenes 6] [--points 20000] [--batch 3]
     python scripts/train_joint.py --config config.yaml [--device-loader]
+    python scripts/train_joint.py --device-loss --val-every 10
 
 --device-loader (with --config): the workers stop at the raw scan (``raw_item``) and the batch - colours, labels,
 voxelisation, gathers - is built on the device (``data.device_batch``); the same batches bit for bit.
+--device-loss: the loss and its backward on the row-loss kernels (``train.joint_loss_device``).
+--val-every K: every K epochs, next to the checkpoint and on rank 0, the reference's validation pass
+(train_joint.py:293-430, ``train.validate_joint``): validation losses, detections and mAP at 0.25 / 0.5 over the validation
+scans (the config's validation split; without --config, ``--val-scenes`` further synthetic scenes).  0 = off.
 """
 import argparse
 import os
@@ -32,6 +37,26 @@ def host_batches(loader, dev):
         yield coords.to(dev), feats, xyz.to(dev), scale.to(dev), cls.to(dev)
 
 
+def validation_scans(val_ds, dev):
+    """train_joint.py:301-306: one scan per batch, in the form train.validate_joint reads"""
+    loader = torch.utils.data.DataLoader(val_ds, collate_fn=collate_fn, batch_size=1, shuffle=False)
+    for ids, coords, feats, xyz, scale, cls in loader:
+        feats = feats.to(dev)
+        feats[:, -3:] = feats[:, -3:] * 2.0 - 1.0
+        yield ids[0], coords.to(dev), feats, xyz.to(dev), scale.to(dev), cls.to(dev)
+
+
+def validation_gt_lines(val_ds, cfg):
+    """{id_scan: ground-truth lines}: the files under cfg.data.gt_path, or the synthetic scenes' own boxes"""
+    if cfg is None:
+        return {val_ds[i][0]: val_ds.gt_lines(i) for i in range(len(val_ds))}
+    gt = {}
+    for ann in val_ds.annotations:
+        with open(os.path.join(cfg.data.gt_path, ann["id_scan"] + ".txt")) as f:
+            gt[ann["id_scan"]] = f.read().splitlines()
+    return gt
+
+
 def device_batches(loader, dev, cfg):
     """the same batches from raw scans (--device-loader)"""
     for raw in loader:
@@ -49,6 +74,11 @@ def main():
     ap.add_argument("--config", default=None, help="the reference's config.yaml: train on real ScanNet/Scan2CAD files")
     ap.add_argument("--device-loader", action="store_true",
                     help="with --config: build every batch on the device from raw scans (data.device_batch)")
+    ap.add_argument("--device-loss", action="store_true",
+                    help="loss and its backward on the row-loss kernels (train.joint_loss_device) instead of torch ops")
+    ap.add_argument("--val-every", type=int, default=0,
+                    help="run the validation pass (train.validate_joint: losses, mAP@0.25/0.5) every K epochs on rank 0; 0 = off")
+    ap.add_argument("--val-scenes", type=int, default=2, help="without --config: synthetic validation scenes")
     a = ap.parse_args()
     if a.device_loader and not a.config:
         ap.error("--device-loader needs --config (synthetic items are already voxel-level)")
@@ -82,13 +112,21 @@ def main():
     else:
         ds = SyntheticScanDataset(a.scenes, a.points, seed0=1000 * rank)      # every rank owns its scenes
         loader = torch.utils.data.DataLoader(ds, batch_size=a.batch, shuffle=True, collate_fn=collate_fn, drop_last=True)
+    val_ds, hv = None, None
+    if a.val_every > 0 and rank == 0:
+        from canonicalvoting_amd.hough import HoughVoting
+        res = float(cfg.scannet_res) if cfg else ds.res
+        hv = HoughVoting(res)
+        val_ds = (ScanNetXYZProbMultiDataset(cfg, training=False, augment=False) if cfg
+                  else SyntheticScanDataset(a.val_scenes, a.points, seed0=500000))
+        val_gt = validation_gt_lines(val_ds, cfg)
     for epoch in range(first_epoch, last_epoch + 1):
         train.adjust_learning_rate(opt, epoch, base_lr, steps, rates)
         train.set_bn_momentum(model, train.bn_momentum(epoch, bn_step, bn_rate))   # train_joint.py:224-225,239
         net.train()
         t0, tot, n = time.perf_counter(), 0.0, 0
         for batch in (device_batches(loader, dev, cfg) if a.device_loader else host_batches(loader, dev)):
-            loss, _ = train.train_step(net, opt, *batch)
+            loss, _ = train.train_step(net, opt, *batch, device_loss=a.device_loss)
             tot += float(loss)
             n += 1
         if rank == 0:
@@ -97,6 +135,12 @@ def main():
             # train_joint.py:290-291: one file per saved epoch, 'epoch{N}.pth' (here under the --save prefix)
             stem, ext = os.path.splitext(a.save)
             torch.save(model.state_dict(), "%s_epoch%d%s" % (stem, epoch, ext or ".pth"))
+        if val_ds is not None and (epoch % a.val_every == 0 or epoch == last_epoch):
+            # train_joint.py:293-430; the other ranks go on to their next epoch and meet this one at its first all-reduce
+            v = train.validate_joint(model, hv, validation_scans(val_ds, dev), res, gt_boxes=val_gt)      # the training loss's settings
+            print("epoch %d  validation over %d scans  %s%s" % (
+                epoch, v["n_scans"], "  ".join("%s %.4f" % kv for kv in v["losses"].items()),
+                "".join("  mAP@%.2f %.4f" % (t, m["mAP"]) for t, m in v.get("map", {}).items())), flush=True)
     cvd.finalize()
 
 

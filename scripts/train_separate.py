@@ -48,7 +48,9 @@ def device_loader_batches(loader, dev, cfg, reference_indexing):
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    ap = argparse.ArgumentParser(epilog="There is no validation pass in this trainer (scripts/train_joint.py has --val-every): "
+                                        "the reference's validation every 10 epochs stays with scripts/eval_separate.py, which "
+                                        "evaluates the saved models.")
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--scenes", type=int, default=6)
     ap.add_argument("--points", type=int, default=20000)
@@ -61,6 +63,8 @@ def main():
                          "output with each scan's own row numbers, train_separate.py:270)")
     ap.add_argument("--device-loader", action="store_true",
                     help="with --config: workers read raw scans, the batch is built on the device (data.device_batch_sym)")
+    ap.add_argument("--device-loss", action="store_true",
+                    help="scale term and cross entropy on the row-loss kernels (train_step_separate(device_loss=True)) instead of torch ops")
     a = ap.parse_args()
     if a.device_loader and not a.config:
         ap.error("--device-loader needs --config: the synthetic scenes (SyntheticSymDataset) are generated as finished items "
@@ -108,7 +112,7 @@ def main():
         t0, losses = time.perf_counter(), []
         batches = device_loader_batches(loader, dev, cfg, not a.repaired_indexing) if a.device_loader else device_batches(loader, dev)
         for batch in batches:
-            res = train.train_step_separate(net, opt, *batch, **loss_kw)
+            res = train.train_step_separate(net, opt, *batch, device_loss=a.device_loss, **loss_kw)
             if res is not None:                                             # train_separate.py:238-240: no object, no step
                 losses.append(res[0])
         if rank == 0:
