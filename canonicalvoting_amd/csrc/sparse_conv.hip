@@ -317,6 +317,10 @@ int launch_rows(ConvArgs a, const int NB, bool vec, hipStream_t st, ModelArgs* m
         launch_conv_rows_wp(a, NB, a.pieces, true, grid, st);
     } else {
         CV_REQUIRE(a.pieces != 1 || !(vec && a.wp6), CV_EINVAL, "the bf16 compute mode takes at most %d kernel offsets per workgroup", WP_NPRE_BIG);
+        // conv_rows knows one source: a launch that reached it with in2 set would return CV_OK without in2 @ W2
+        CV_REQUIRE(!a.in2, CV_EINVAL,
+                   "a second source takes at most %d kernel offsets per workgroup (%d here: flavour 0 with a workspace splits the "
+                   "launch, or pass fewer offsets per call)", WP_NPRE_BIG, per_wg);
         launch_conv_rows(a, NB, vec, grid, st);
     }
     CV_LAUNCH_CHECK();

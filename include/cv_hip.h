@@ -544,7 +544,10 @@ typedef struct cv_conv_desc {
                                product (fp32-level accuracy, 0.375x the matrix time of v_mfma_f32_32x32x2_f32) */
     const float* in2;       /* optional second source on the OUTPUT rows (bf16x6 path only): the accumulator also gets */
     int in2_ld, cin2;       /* in2[u][0:cin2] @ W2 - BasicBlock's 1x1 downsample branch folded into conv2             */
-    const void* weight2_x6; /* cv_sp_pack_weights_x6_f32 of W2 [1][cin2][cout]                                         */
+    const void* weight2_x6; /* cv_sp_pack_weights_x6_f32 of W2 [1][cin2][cout] (the packer of weight_pieces, as weight_x6).
+                               At most 28 kernel offsets per workgroup: a launch that does not split below that (flavour 1,
+                               or flavour 0 without ws, with more than 28 offsets in [j_begin, j_end)) is CV_EINVAL - the
+                               kernel that takes such launches has no second source                                  */
     int perm_has_map;       /* with perm_groups > 1: row_perm is followed by the kernel map rows in processing order
                                (cv_sp_mask_perms with_map = 1), which turns the random map reads into coalesced ones */
     int weight_pieces;      /* 1: one bf16 plane (cv_sp_pack_weights_bf16_f32): operands rounded to bf16, one product -

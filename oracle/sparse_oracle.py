@@ -355,6 +355,11 @@ roundings of at most 2^-24 * (|y * scale| + |shift| + |residual|) each (and an h
 2^-25 absolute).  ReLU is 1-Lipschitz, so |got - relu(z64)| <= bound(z) holds for every element, also where z64 lies
 within the bound of zero (there it only says that |got| is within the bound).
 
+A second source (cv_conv_desc.in2: out += in2 @ W2 on the output rows, conv64_two) adds Cin2 / 32 units to the same
+accumulator and its terms to mag and wabs; nothing else changes.  BatchNorm scales folded into the packed weights are
+restated exactly (folded_weights): the packers form w * (col_scale * 2^k) with one fp32 rounding, so the reference uses
+the rounded product as ITS weight and the fold adds no term to the bound.
+
 The weight gradient dW[j, ci, co] = sum_u x[nbr[u, j], ci] * dy[u, co] follows the same model with the rows as the
 reduction axis: units of 16 rows (the k of one 32x32x16 instruction; 8 instructions of k = 2 for "f32"), plus the row
 splits of the plan (at most WGRAD_SPLIT_CAP = 1024) and the reduce launch.
@@ -415,6 +420,30 @@ def conv_bound(mag, wabs, path, units, hl_out=False, y=None):
 
 def conv_units(K, cin):
     return K * ((cin + 31) // 32)
+
+
+def folded_weights(w, col_scale=None, bf16=False):
+    """the weights a packer splits, exactly: w * (col_scale * 2^k) is ONE fp32 rounding (the power of two is exact and
+    leaves the accumulator again through acc_scale = 2^-k), so w_eff = float32(w * col_scale), widened; bf16: the
+    pieces = 1 packer then rounds that to bf16"""
+    w = np.asarray(w, np.float32)
+    if col_scale is not None:
+        w = (w * np.asarray(col_scale, np.float32)).astype(np.float32)
+    return (bf16_round(w) if bf16 else w).astype(np.float64)
+
+
+def conv64_two(x, w, nbr, x2, w2, j_begin=0, j_end=None):
+    """the two-source convolution (cv_conv_desc.in2): y64 = conv64(x, w, nbr, j_begin, j_end) + x2 @ w2 on the output
+    rows; x2 [N_out, Cin2], w2 [Cin2, Cout] or [1, Cin2, Cout].  mag and wabs are the sums of both sources' terms."""
+    y, mag, wabs = conv64(x, w, nbr, j_begin, j_end)
+    x2 = np.asarray(x2, np.float64)
+    w2 = np.asarray(w2, np.float64).reshape(x2.shape[1], -1)
+    return y + x2 @ w2, mag + np.abs(x2) @ np.abs(w2), wabs + np.abs(w2).sum(0)[None]
+
+
+def conv_units_two(nj, cin, cin2):
+    """units of a two-source launch: nj offsets x ceil(Cin / 32) chunks, then the Cin2 / 32 chunks of the second source"""
+    return conv_units(nj, cin) + cin2 // 32
 
 
 def epilogue64(y, b, acc_in=None, b_acc=None, scale=None, shift=None, res=None, res_hl=False, relu=False,

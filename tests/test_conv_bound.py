@@ -111,6 +111,68 @@ def test_wgrad_oracle_and_bound():
     assert so.within(dw, dw, b)[0] and not so.within(bad, dw, b)[0]
 
 
+# ---- the two-source bound separates the defects the second-source and network-program tests exist for ----------------
+def _worst(bad, case):
+    return float((np.abs(bad - case["y"]) / case["bound"]).max())
+
+
+def test_two_source_reference_adds_both_sources():
+    from tests import conv_two_source as ts
+    c = ts.two_source(129, "mixed", 3, 32, 64, 32, 3)
+    x, w, scale = ts.operands(129, 129, 32, 32, 27)[:3]
+    x2, w2, scale2 = ts.second_operands(129, 64, 32)
+    y1, m1, a1 = so.conv64(x, so.folded_weights(w, scale), c["ref"])
+    w2e = so.folded_weights(w2, scale2)[0]
+    assert np.array_equal(c["y"], y1 + x2.astype(np.float64) @ w2e)
+    assert np.array_equal(c["mag"], m1 + np.abs(x2).astype(np.float64) @ np.abs(w2e))
+    assert np.array_equal(c["wabs"], a1 + np.abs(w2e).sum(0)[None])
+    assert so.conv_units_two(27, 32, 64) == 29 and so.conv_units_two(10, 40, 128) == 24
+    # the fold is one fp32 rounding of the product; the bf16 packer rounds that once more
+    assert np.array_equal(so.folded_weights(w, scale), (w * scale).astype(np.float32).astype(np.float64))
+    assert np.array_equal(so.folded_weights(w, scale, bf16=True), so.bf16_round((w * scale).astype(np.float32)))
+
+
+@pytest.mark.parametrize("pieces", [3, 2, 1])
+def test_two_source_bound_rejects_a_lost_or_misplaced_second_source(pieces):
+    """(i) the second source absent, (ii) its last chunk dropped, (iii) x2 read at the tile position for one mask group:
+    each more than twice the bound on some element of every shape tests/test_conv_second_source_gpu.py runs"""
+    from tests import conv_two_source as ts
+    seen = set()
+    for n, kind, k, cin, cin2, cout, jr, groups in ts.section1_shapes():
+        jb, je = jr if jr else (0, None)
+        c = ts.two_source(n, kind, k, cin, cin2, cout, pieces, jb, je)
+        assert so.within(c["y"], c["y"], c["bound"])[0]
+        for name, bad in ts.defects(c, groups):
+            if name.startswith("tile") and n == 1:
+                continue
+            r = _worst(bad, c)
+            assert r > 2, "%s at %s: only %.3g x the bound" % (name, (n, kind, k, cin, cin2, cout, jr, groups), r)
+            seen.add(name)
+    assert len(seen) == 3
+
+
+@pytest.mark.parametrize("cout", [64, 256])
+def test_two_source_bound_rejects_the_neighbour_models_parameters(cout):
+    """(iv) model m's two-source conv with model m - 1's shift, and separately with its w2, on the parameters of
+    tests/test_net_program_gpu.py (stand-in activations of the same scale)"""
+    from tests import conv_two_source as ts
+    ref = ts.ref_map(300, "mixed", 3)[0]
+    x = ts.operands(300, 300, 64, cout, 27)[0]
+    x2 = ts.second_operands(300, 64, cout)[0]
+    for m in range(1, 16):
+        p, q = (ts.model_params(mm, "shortcut/conv2", 27, 64, cout, 64) for mm in (m, m - 1))
+        we, w2e = so.folded_weights(p["w"], p["scale"]), so.folded_weights(p["w2"], p["scale2"])
+        y, mag, wabs = so.conv64_two(x, we, ref, x2, w2e)
+        b = so.conv_bound(mag, wabs, "h2", so.conv_units_two(27, 64, 64))
+        z, bz = so.epilogue64(y, b, shift=p["shift"], relu=True, hl_out=True)
+        z_shift = so.epilogue64(y, b, shift=q["shift"], relu=True)[0]
+        y_w2 = so.conv64_two(x, we, ref, x2, so.folded_weights(q["w2"], q["scale2"]))[0]
+        z_w2 = so.epilogue64(y_w2, b, shift=p["shift"], relu=True)[0]
+        for name, bad in (("shift", z_shift), ("w2", z_w2)):
+            r = float((np.abs(bad - z) / bz).max())
+            assert r > 2, "model %d with model %d's %s: only %.3g x the bound" % (m, m - 1, name, r)
+
+
 WS_CODE = ("import sys; sys.path.insert(0, sys.argv[1]); from canonicalvoting_amd import _lib; "
            "print(int(_lib.lib().cv_sp_wgrad_workspace_bytes(20000, 64, 64, 27)), "
            "int(_lib.lib().cv_sp_wgrad_workspace_bytes(20000, 32, 32, 8)))")

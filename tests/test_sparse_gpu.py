@@ -777,7 +777,7 @@ def test_reference_checkpoint_in_z_fastest_offset_order_loads_and_matches_oracle
 def test_conv_hd_is_bit_identical_to_conv_hl(cuda, built_lib, cin, cout, n, masked):
     """conv_hd (LDS-DMA operand rings, 256-row workgroups, cv_sp_set_option "hd_mask") keeps conv_hl's units and MFMA
     sequence per accumulator: the same bits for mask-grouped and split launches, with a residual / ReLU / hl epilogue and a
-    ragged last tile (n is no multiple of 256); the second source rides through the network-level comparison."""
+    ragged last tile (n is no multiple of 256); the second source has its own per-element tests (tests/test_conv_second_source_gpu.py)."""
     coords, _ = scene_coords(3, n, small=n < 10000)
     N = len(coords)
     rng = np.random.default_rng(cin + 3 * cout)
