@@ -22,6 +22,10 @@ per-row terms - head gather, masked squared errors, cross entropy and their back
     joint_loss_device   joint_loss on the row-loss kernels, the same arguments and keys
     joint_loss_val      the validation form (train_joint.py:311-340): head by the predicted class, NaN without object rows
     validate_joint      the trainer's validation pass (train_joint.py:293-430): losses, detections and mAP per scan list
+    validate_separate   the per-category trainer's (train_separate.py:301-458): separate_loss_packed, head_separate, vote,
+                        the separate-variant decode and NMS of the one category, AP and recall
+    finish_pending      act on a range flag the lagged read has not reached yet (restore BatchNorm statistics, go to the
+                        triples) in front of a validation pass or a checkpoint
 
 The reference's stale-loss bug (`losses` persists across iterations) is not
 reproduced: a batch without object points contributes only the classification loss.
@@ -194,6 +198,17 @@ class _FlagRing:
             slot["event"].synchronize()
         return float(slot["host"][0]) != 0.0
 
+    def pending(self):
+        """whether ANY stored flag is raised, the youngest included: waits for the event of every valid slot (finish_pending)"""
+        raised = False
+        for slot in self.slots:
+            if slot is None or not slot["valid"]:
+                continue
+            if slot["event"] is not None:
+                slot["event"].synchronize()
+            raised = raised or float(slot["host"][0]) != 0.0
+        return raised
+
     def push(self, found, group=None):
         """found: float scalar tensor on the step's device (None: the step used no fp16 pairs); returns the group's value"""
         i = self.k % self.lag
@@ -241,6 +256,41 @@ def _bn_state(model):
     return bufs, saved
 
 
+def _drop_flagged_steps(model, st, dev, bufs, saved):
+    """What follows a noticed range flag: the flagged steps' updates were skipped on the device and the BatchNorm snapshot still
+    holds the statistics and counters of before the first of them - wait for the stream, put them back, clear the flag, count
+    the fallback and send the model to the bf16 triples for good (no ring from here on)."""
+    torch.cuda.current_stream(dev).synchronize()
+    with torch.no_grad():
+        torch._foreach_copy_(bufs, saved)
+    ME.range_flag(dev).zero_()
+    model.train_range_fallbacks = getattr(model, "train_range_fallbacks", 0) + 1
+    st.pairs_off, st.ring = True, None
+
+
+def finish_pending(model):
+    """Act NOW on a range flag that train_step / train_step_separate would only notice FLAG_LAG calls later - in front of
+    anything that reads the model between two steps: a validation pass, a checkpoint.  ``model``: the object that was handed to
+    the step (under DDP the wrapper: the step state lives on it).
+    No ring (the model never stepped, the optimizer cannot skip on the device, or the model is on the bf16 triples already):
+    returns False and launches nothing.  Otherwise waits for the event of every stored flag and reads them all; all zero:
+    returns False and nothing changes.  Any non-zero: what the step's own lagged read does - stream synchronised, BatchNorm
+    running statistics and counters restored from the snapshot of before the first flagged step, ME.range_flag zeroed,
+    ``model.train_range_fallbacks`` counted, the model on the triples from here on - and returns True.  It runs no step: the
+    flagged batches stay dropped, as train_step documents.
+    Under DDP the stored flags are the all-reduced ones (push reduces before it stores), so every rank reads the same values
+    and no collective is needed here - but EVERY rank must call this at the same point between the same two steps, or the
+    ranks leave the fp16 pairs at different steps."""
+    st = model.__dict__.get("_cv_step_state")
+    ring = st.ring if st is not None else None
+    if ring is None:
+        return False
+    if not ring.pending():
+        return False
+    _drop_flagged_steps(model, st, ring.dev, *_bn_state(model))
+    return True
+
+
 def _run_step(model, optimizer, dev, forward_loss):
     """The core of train_step and train_step_separate: zero_grad -> ``forward_loss()`` (a closure: forward and loss, returns
     ``(loss, parts)``) -> backward -> optimizer.step, inside the one training-step state a model keeps (_StepState): the
@@ -273,12 +323,7 @@ def _run_step(model, optimizer, dev, forward_loss):
             # the step FLAG_LAG calls ago left the fp16 range (on this rank or, under DDP, on any rank): its update and that
             # of every step queued since was skipped on the device, and the BatchNorm snapshot still holds the statistics and
             # counters of before it
-            torch.cuda.current_stream(dev).synchronize()
-            with torch.no_grad():
-                torch._foreach_copy_(bufs, saved)
-            ME.range_flag(dev).zero_()
-            model.train_range_fallbacks = getattr(model, "train_range_fallbacks", 0) + 1
-            st.pairs_off, st.ring = True, None
+            _drop_flagged_steps(model, st, dev, bufs, saved)
             return _run_step(model, optimizer, dev, forward_loss)
         # BatchNorm statistics of before this step, kept ON THE DEVICE only while no step has raised the flag
         ME.copy_unless_flag(bufs, saved, dev, ME.range_flag(dev))
@@ -387,8 +432,7 @@ def validate_joint(model, hv, batches, res, gt_boxes=None, nclasses=9, log_scale
     reference's values are), ``pred_map_cls``, ``n_scans`` and - with ``gt_boxes`` {id_scan: lines ``tx ty tz ry sx sy sz ...
     category`` as in cfg.data.gt_path} - ``map`` = {0.25: ..., 0.5: ...} from calc_map.compute_map.
     The model is put back into the mode it was in; eval-mode BatchNorm leaves the running statistics untouched."""
-    from . import calc_map, decode, hv_cuda, pipeline
-    from .data import parse_gt_lines
+    from . import decode, hv_cuda, pipeline
     was_training = model.training
     model.eval()
     kw = dict(nclasses=nclasses, log_scale=log_scale, xyz_factor=xyz_factor, scale_factor=scale_factor,
@@ -416,13 +460,76 @@ def validate_joint(model, hv, batches, res, gt_boxes=None, nclasses=9, log_scale
                 per_scan.append(torch.stack([total, parts["loss_xyz"], parts["loss_scale"], parts["loss_class"]]))
     finally:
         model.train(was_training)
+    return _validation_result(per_scan, ("loss", "loss_xyz", "loss_scale", "loss_class"), pred_map_cls, gt_boxes)
+
+
+def _validation_result(per_scan, keys, pred_map_cls, gt_boxes):
+    """what validate_joint and validate_separate return: the means of the per-scan loss rows (the pass's one host read), the
+    detections, the scan count and - with ground truth - the mAP dicts over the scans that ran"""
+    from . import calc_map
+    from .data import parse_gt_lines
     out = {"pred_map_cls": pred_map_cls, "n_scans": len(per_scan)}
-    mean = torch.stack(per_scan).mean(0).tolist() if per_scan else [float("nan")] * 4       # the one host read
-    out["losses"] = dict(zip(("loss", "loss_xyz", "loss_scale", "loss_class"), mean))
+    mean = torch.stack(per_scan).mean(0).tolist() if per_scan else [float("nan")] * len(keys)
+    out["losses"] = dict(zip(keys, mean))
     if gt_boxes is not None:
         gt_map_cls = {i: [(c, calc_map.gt_box(*p)) for c, p in parse_gt_lines(gt_boxes[i])] for i in pred_map_cls}
         out["map"] = {thr: calc_map.compute_map(pred_map_cls, gt_map_cls, thr) for thr in (0.25, 0.5)}
     return out
+
+
+def validate_separate(model, hv, batches, res, category=0, gt_boxes=None, log_scale=True, xyz_factor=1.0, scale_factor=1.0,
+                      xyz_component_weights=(1.0, 1.0, 1.0), device_loss=False, overlap_threshold=0.3, **decode_kw):
+    """The validation pass of train_separate.py:301-458, validate_joint's twin for the 8-channel model of ONE category.
+    ``batches`` yields one scan at a time: ``(id_scan, coords4, feats, sym, scale_labels, obj_labels)``, feats already
+    recentred (:316-317), ``sym`` the data.SymBatch of that one scan on the host or on the device.  A scan without a segment
+    (``sym.n_segments == 0``, a host int) is skipped as the reference skips it (:310-312): not counted, no entry in
+    ``pred_map_cls``, its ground truth unused.  Per scan ONE eval-mode forward under no_grad (its fp16-range check deferred
+    behind the decode, as validate_joint's), separate_loss_packed on that output (:322-357; ``device_loss``: its
+    ``device_rows``), then pipeline.head_separate and vote, decode and NMS of the one category on the same output - the decode
+    of eval_separate.py (its elimination slice and float32 error threshold), which train_separate.py:386,420 shares; the
+    detections go into ``pred_map_cls[id_scan]`` as ``(category, box[8,3], score)``.
+    Returns validate_joint's dict: ``losses`` = the mean of loss / loss_obj / loss_scale / loss_xyz over the scans that ran
+    (read once at the end; NaN without a scan), ``pred_map_cls``, ``n_scans`` and - with ``gt_boxes`` {id_scan: lines} -
+    ``map`` = {0.25: ..., 0.5: ...} from calc_map.compute_map over the scans that ran, ground-truth classes from
+    data.parse_gt_lines (the reference logs the 0.5 entry's '<category> Average Precision' and '<category> Recall', :455-458).
+    The model is put back into the mode it was in; eval-mode BatchNorm leaves the running statistics untouched.  In the middle
+    of a training run call finish_pending first: a range flag nobody has read yet means non-finite statistics."""
+    from . import hv_cuda, pipeline
+    from .data import sym_to_device
+    was_training = model.training
+    model.eval()
+    kw = dict(log_scale=log_scale, xyz_factor=xyz_factor, scale_factor=scale_factor, xyz_component_weights=xyz_component_weights,
+              device_rows=device_loss)
+    pipeline._separate_defaults(decode_kw)
+    pred_map_cls, per_scan = {}, []
+    try:
+        with torch.no_grad():
+            for id_scan, coords4, feats, sym, scale_labels, obj_labels in batches:
+                if sym.n_segments == 0:
+                    continue
+                dev = feats.device
+                if sym.rows.device != dev:
+                    sym = sym_to_device(sym, dev)
+                scale_dev, obj_dev = scale_labels.to(dev, non_blocking=True), obj_labels.to(dev, non_blocking=True)
+                scan_points = (coords4[:, 1:].to(dev) * res).float().contiguous()
+                hv_cuda.prefetch_geometry(scan_points)
+                x = ME.SparseTensor(feats, coords4, device=dev)
+                deferred = hasattr(model, "check_range")
+                y = model(x, defer_check=True) if deferred else model(x)
+                for attempt in range(2):
+                    total, parts = separate_loss_packed(y.F, sym, scale_dev, obj_dev, **kw)
+                    dets = pipeline._separate_by_calls(hv, scan_points, [pipeline.head_separate(y.F, log_scale)], res, [category],
+                                                       overlap_threshold, **decode_kw)
+                    # the decode has waited for the stream: the fp16-range flag of the network's convolutions is final now
+                    y2 = model.check_range(x, y) if (deferred and attempt == 0) else y
+                    if y2 is y:
+                        break
+                    y = y2
+                pred_map_cls[id_scan] = dets
+                per_scan.append(torch.stack([total, parts["loss_obj"], parts["loss_scale"], parts["loss_xyz"]]))
+    finally:
+        model.train(was_training)
+    return _validation_result(per_scan, ("loss", "loss_obj", "loss_scale", "loss_xyz"), pred_map_cls, gt_boxes)
 
 
 def adjust_learning_rate(optimizer, epoch, base_lr=1e-3, decay_steps=(80, 120, 160), decay_rates=(0.1, 0.1, 0.1)):

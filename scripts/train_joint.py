@@ -129,6 +129,8 @@ def main():
             loss, _ = train.train_step(net, opt, *batch, device_loss=a.device_loss)
             tot += float(loss)
             n += 1
+        # every rank, in front of the checkpoint and the validation: act on a range flag of the epoch's last steps now
+        train.finish_pending(net)
         if rank == 0:
             print("epoch %d  loss %.4f  %.1f s" % (epoch, tot / max(n, 1), time.perf_counter() - t0), flush=True)
         if a.save and rank == 0 and (epoch % 10 == 0 or epoch == last_epoch):

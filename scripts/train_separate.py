@@ -12,7 +12,12 @@ one process per GPU with DDP when launched through torch.distributed.run (the re
 data.device_batch_sym voxelises, filters the models' points, evaluates the targets of every pose and packs the labels on the
 device - the same bits as the default path, one host wait per batch.
 
-The reference's validation every 10 epochs is not repeated here: scripts/eval_separate.py evaluates the saved models.
+--val-every K: every K epochs and on the last one, next to the checkpoint and on rank 0, the reference's validation pass
+(train_separate.py:301-458, ``train.validate_separate``): the three validation losses, detections of the category and its AP
+and recall at 0.25 / 0.5 over the validation scans (the config's validation split with the ground truth under
+``cfg.data.gt_path``; without --config, ``--val-scenes`` further synthetic scenes whose boxes all count as class 0).  0 = off.
+Every rank calls ``train.finish_pending`` at the end of every epoch, in front of the checkpoint and the validation: a
+fp16-range flag of the epoch's last steps is acted on before anything reads the BatchNorm statistics.
 """
 import argparse
 import functools
@@ -25,8 +30,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from canonicalvoting_amd import dist as cvd  # noqa: E402
 from canonicalvoting_amd import train  # noqa: E402
-from canonicalvoting_amd.data import (RawItems, ScanNetXYZProbSymDataset, SyntheticSymDataset, collate_raw_sym,  # noqa: E402
-                                      collate_sym, device_batch_sym, load_config, sym_to_device)
+from canonicalvoting_amd.data import (TOP8_CLASSES, RawItems, ScanNetXYZProbSymDataset, SyntheticSymDataset,  # noqa: E402
+                                      collate_raw_sym, collate_sym, device_batch_sym, load_config, sym_to_device)
 from canonicalvoting_amd.minkunet import MinkUNet34C  # noqa: E402
 
 
@@ -47,10 +52,54 @@ def device_loader_batches(loader, dev, cfg, reference_indexing):
         yield coords, feats, sym, scale, obj
 
 
+def validation_scans(val_ds, dev, cfg, device_loader):
+    """train_separate.py:309-317: one scan per batch, in the form train.validate_separate reads; with --device-loader the scan
+    is built on the device from its raw form, the same bits (one scan: both row indexings are the same rows)"""
+    if device_loader:
+        loader = torch.utils.data.DataLoader(RawItems(val_ds), collate_fn=collate_raw_sym, batch_size=1, shuffle=False)
+        for raw in loader:
+            ids, coords, feats, sym, scale, obj, _ = device_batch_sym(raw, dev, cfg.scannet_res, use_xyz=bool(cfg.use_xyz),
+                                                                      recentre=True)
+            yield ids[0], coords, feats, sym, scale, obj
+        return
+    loader = torch.utils.data.DataLoader(val_ds, collate_fn=collate_sym, batch_size=1, shuffle=False)
+    for ids, coords, feats, sym, scale, obj, _ in loader:
+        feats = feats.to(dev)
+        feats[:, -3:] = feats[:, -3:] * 2.0 - 1.0
+        yield ids[0], coords.to(dev), feats, sym, scale, obj
+
+
+def synthetic_gt_lines(val_ds):
+    """{id_scan: ground-truth lines} of a SyntheticSymDataset: the scenes' own boxes, every one as class 0 - synthetic scenes
+    have no categories, and the one model under training predicts category 0"""
+    gt = {}
+    for i in range(len(val_ds)):
+        lines = val_ds.scenes.gt_lines(i)
+        gt[val_ds.scenes[i][0]] = [" ".join(line.split(" ")[:-1] + ["0"]) for line in lines]
+    return gt
+
+
+def config_gt_lines(val_ds, cfg):
+    """{id_scan: ground-truth lines} from the files under cfg.data.gt_path (train_separate.py:436)"""
+    gt = {}
+    for ann in val_ds.annotations:
+        with open(os.path.join(cfg.data.gt_path, ann["id_scan"] + ".txt")) as f:
+            gt[ann["id_scan"]] = f.read().splitlines()
+    return gt
+
+
+def validation_line(epoch, v, category):
+    """the one line of a validation: scan count, the four mean losses, AP and recall of the category at 0.25 and 0.5"""
+    # (calc_map.compute_map has no entry for a class with neither a detection nor a ground-truth box)
+    return "epoch %d  validation over %d scans  %s%s" % (
+        epoch, v["n_scans"], "  ".join("%s %.4f" % kv for kv in v["losses"].items()),
+        "".join("  AP@%.2f %.4f  recall@%.2f %.4f" % (t, m.get("%d Average Precision" % category, 0.0), t,
+                                                      m.get("%d Recall" % category, 0.0))
+                for t, m in v.get("map", {}).items()))
+
+
 def main():
-    ap = argparse.ArgumentParser(epilog="There is no validation pass in this trainer (scripts/train_joint.py has --val-every): "
-                                        "the reference's validation every 10 epochs stays with scripts/eval_separate.py, which "
-                                        "evaluates the saved models.")
+    ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--scenes", type=int, default=6)
     ap.add_argument("--points", type=int, default=20000)
@@ -65,7 +114,15 @@ def main():
                     help="with --config: workers read raw scans, the batch is built on the device (data.device_batch_sym)")
     ap.add_argument("--device-loss", action="store_true",
                     help="scale term and cross entropy on the row-loss kernels (train_step_separate(device_loss=True)) instead of torch ops")
+    ap.add_argument("--val-every", type=int, default=0,
+                    help="run the validation pass (train.validate_separate: losses, AP and recall of the category at 0.25 / 0.5) "
+                         "every K epochs and on the last one, on rank 0; 0 = off")
+    ap.add_argument("--val-scenes", type=int, default=2, help="without --config: synthetic validation scenes")
     a = ap.parse_args()
+    if a.val_every < 0:
+        ap.error("--val-every counts epochs: 0 (off) or more")
+    if a.val_every > 0 and not a.config and a.val_scenes < 1:
+        ap.error("--val-every without --config validates on synthetic scenes: --val-scenes must be 1 or more")
     if a.device_loader and not a.config:
         ap.error("--device-loader needs --config: the synthetic scenes (SyntheticSymDataset) are generated as finished items "
                  "and have no raw-scan form")
@@ -105,6 +162,17 @@ def main():
     else:
         ds = SyntheticSymDataset(a.scenes, a.points, seed0=1000 * rank)       # every rank owns its scenes
         loader = torch.utils.data.DataLoader(ds, batch_size=a.batch, shuffle=True, collate_fn=collate, drop_last=True)
+    val_ds, hv = None, None
+    if a.val_every > 0 and rank == 0:
+        from canonicalvoting_amd.hough import HoughVoting
+        val_res = float(cfg.scannet_res) if cfg else ds.scenes.res
+        hv = HoughVoting(val_res)
+        if cfg:
+            val_ds = ScanNetXYZProbSymDataset(cfg, training=False, augment=False)
+            val_gt, category = config_gt_lines(val_ds, cfg), TOP8_CLASSES.get(str(cfg.category), 0)
+        else:
+            val_ds = SyntheticSymDataset(a.val_scenes, a.points, seed0=500000)
+            val_gt, category = synthetic_gt_lines(val_ds), 0
     for epoch in range(first_epoch, last_epoch + 1):
         train.adjust_learning_rate(opt, epoch, base_lr, steps, rates)
         train.set_bn_momentum(model, train.bn_momentum(epoch, bn_step, bn_rate))   # train_separate.py:216-217,230
@@ -115,6 +183,9 @@ def main():
             res = train.train_step_separate(net, opt, *batch, device_loss=a.device_loss, **loss_kw)
             if res is not None:                                             # train_separate.py:238-240: no object, no step
                 losses.append(res[0])
+        # every rank, in front of everything that reads the model between two steps: a range flag of the epoch's last steps
+        # would otherwise be noticed only in the next epoch, behind a checkpoint and a validation over non-finite statistics
+        train.finish_pending(net)
         if rank == 0:
             mean = float(torch.stack(losses).mean()) if losses else float("nan")          # one host wait per epoch
             print("epoch %d  loss %.4f  %d steps  %.1f s" % (epoch, mean, len(losses), time.perf_counter() - t0), flush=True)
@@ -122,6 +193,11 @@ def main():
             # train_separate.py:298-299: one file per saved epoch, 'epoch{N}.pth' (here under the --save prefix)
             stem, ext = os.path.splitext(a.save)
             torch.save(model.state_dict(), "%s_epoch%d%s" % (stem, epoch, ext or ".pth"))
+        if val_ds is not None and (epoch % a.val_every == 0 or epoch == last_epoch):
+            # train_separate.py:301-458; the other ranks go on to their next epoch and meet this one at its first all-reduce
+            v = train.validate_separate(model, hv, validation_scans(val_ds, dev, cfg, a.device_loader), val_res, category=category,
+                                        gt_boxes=val_gt, device_loss=a.device_loss, **loss_kw)
+            print(validation_line(epoch, v, category), flush=True)
     cvd.finalize()
 
 
