@@ -111,6 +111,18 @@ int cv_sp_scene_plan_ex(const int32_t* d_input, long long n, int32_t* d_perm, in
                         int32_t* d_arena, size_t arena_words, cv_scene_maps* offsets, void* d_sort_ws, size_t sort_ws_bytes,
                         void* d_levels_ws, size_t levels_ws_bytes, bool single_batch, void* stream,
                         bool bounds_prefilled);                                               // net_exec.cpp
+// cv_net_run_f32 / cv_net_run_models_f32 for a caller that KNOWS where its maps come from (the scene calls).  plan_maps: the maps
+// are the scene plan's, so a validity word per row lies behind every 3x3x3 map with mask orders; the mask-sorted convolutions
+// get it as cv_conv_desc.valid_words (the C ABI entry points pass false: their caller's maps may be any)
+int cv_net_run_ex(const cv_net_op* ops, int n_ops, const cv_net_buf* bufs, int n_bufs, const long long* level_rows,
+                  int n_levels, void* d_arena, size_t arena_bytes, const void* const* ext_ptr, const int* ext_ld,
+                  const int32_t* const* maps, int n_maps, const int32_t* const* perms, int n_perms,
+                  void* d_ws, size_t ws_bytes, int32_t* range_flag, bool plan_maps, void* stream);           // net_exec.cpp
+int cv_net_run_models_ex(const cv_net_op* const* ops, const cv_net_buf* const* bufs, int n_ops, int n_bufs, int K,
+                         const long long* level_rows, int n_levels, void* d_arena, size_t arena_bytes,
+                         const void* const* const* ext_ptr, const int* ext_ld, const int32_t* const* maps, int n_maps,
+                         const int32_t* const* perms, int n_perms, void* d_ws, size_t ws_bytes, int32_t* range_flag,
+                         const void* d_params, int params_ld, bool plan_maps, void* stream);                  // net_exec.cpp
 // d_ws: (sum of groups) * 2048 ints, zero-filled by the call unless pre_zeroed
 int cv_sp_mask_perms_batch(const CvPermJob* jobs, int n_jobs, void* d_ws, size_t ws_bytes, void* stream,
                            bool pre_zeroed);                                                // conv_prep.hip

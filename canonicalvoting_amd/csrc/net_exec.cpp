@@ -28,7 +28,7 @@ struct NetModels {
 int net_run(const cv_net_op* ops, int n_ops, const cv_net_buf* bufs, int n_bufs, const long long* level_rows, int n_levels,
             void* d_arena, size_t arena_bytes, const void* const* ext_ptr, const int* ext_ld, const int32_t* const* maps,
             int n_maps, const int32_t* const* perms, int n_perms, void* d_ws, size_t ws_bytes, int32_t* range_flag,
-            const NetModels* nm, void* stream);
+            const NetModels* nm, bool plan_maps, void* stream);
 
 }  // namespace
 
@@ -323,9 +323,23 @@ int cv_net_run_f32(const cv_net_op* ops, int n_ops, const cv_net_buf* bufs, int 
                    int n_levels, void* d_arena, size_t arena_bytes, const void* const* ext_ptr, const int* ext_ld,
                    const int32_t* const* maps, int n_maps, const int32_t* const* perms, int n_perms,
                    void* d_ws, size_t ws_bytes, int32_t* range_flag, void* stream) {
-    return net_run(ops, n_ops, bufs, n_bufs, level_rows, n_levels, d_arena, arena_bytes, ext_ptr, ext_ld, maps, n_maps, perms,
-                   n_perms, d_ws, ws_bytes, range_flag, nullptr, stream);
+    return cv_net_run_ex(ops, n_ops, bufs, n_bufs, level_rows, n_levels, d_arena, arena_bytes, ext_ptr, ext_ld, maps, n_maps, perms,
+                         n_perms, d_ws, ws_bytes, range_flag, /* plan_maps */ false, stream);
 }
+
+}  // extern "C"
+
+// (C++ linkage, cv_common.h) plan_maps: the maps are the scene plan's (cv_sp_scene_plan_slots) - a validity word per row lies
+// behind every 3x3x3 map that has mask orders, and the mask-sorted convolutions hand it on (cv_conv_desc.valid_words)
+int cv_net_run_ex(const cv_net_op* ops, int n_ops, const cv_net_buf* bufs, int n_bufs, const long long* level_rows,
+                  int n_levels, void* d_arena, size_t arena_bytes, const void* const* ext_ptr, const int* ext_ld,
+                  const int32_t* const* maps, int n_maps, const int32_t* const* perms, int n_perms,
+                  void* d_ws, size_t ws_bytes, int32_t* range_flag, bool plan_maps, void* stream) {
+    return net_run(ops, n_ops, bufs, n_bufs, level_rows, n_levels, d_arena, arena_bytes, ext_ptr, ext_ld, maps, n_maps, perms,
+                   n_perms, d_ws, ws_bytes, range_flag, nullptr, plan_maps, stream);
+}
+
+extern "C" {
 
 // ---- K structurally identical programs as one launch sequence -------------------------------------------------------
 size_t cv_net_models_params_bytes(int n_ops, int K) {
@@ -363,6 +377,18 @@ int cv_net_run_models_f32(const cv_net_op* const* ops, const cv_net_buf* const* 
                           const void* const* const* ext_ptr, const int* ext_ld, const int32_t* const* maps, int n_maps,
                           const int32_t* const* perms, int n_perms, void* d_ws, size_t ws_bytes, int32_t* range_flag,
                           const void* d_params, int params_ld, void* stream) {
+    return cv_net_run_models_ex(ops, bufs, n_ops, n_bufs, K, level_rows, n_levels, d_arena, arena_bytes, ext_ptr, ext_ld, maps, n_maps,
+                                perms, n_perms, d_ws, ws_bytes, range_flag, d_params, params_ld, /* plan_maps */ false, stream);
+}
+
+}  // extern "C"
+
+// (C++ linkage, cv_common.h; plan_maps as cv_net_run_ex)
+int cv_net_run_models_ex(const cv_net_op* const* ops, const cv_net_buf* const* bufs, int n_ops, int n_bufs, int K,
+                         const long long* level_rows, int n_levels, void* d_arena, size_t arena_bytes,
+                         const void* const* const* ext_ptr, const int* ext_ld, const int32_t* const* maps, int n_maps,
+                         const int32_t* const* perms, int n_perms, void* d_ws, size_t ws_bytes, int32_t* range_flag,
+                         const void* d_params, int params_ld, bool plan_maps, void* stream) {
     CV_REQUIRE(K >= 1 && K <= CV_MAX_CATEGORIES, CV_EINVAL, "number of models out of range (%d, 1..%d)", K, CV_MAX_CATEGORIES);
     CV_REQUIRE(ops && bufs && level_rows && d_arena && ext_ptr && n_ops > 0 && n_bufs > 0 && n_levels > 0, CV_EINVAL,
                "bad network program arguments");
@@ -403,17 +429,15 @@ int cv_net_run_models_f32(const cv_net_op* const* ops, const cv_net_buf* const* 
     const size_t ws_one = K > 1 ? ws_stride : ws_bytes;
     NetModels nm = {K, ext_ptr, arena_one, ws_stride, static_cast<const cv_net_model_params*>(d_params), params_ld};
     return net_run(ops[0], n_ops, bufs[0], n_bufs, level_rows, n_levels, d_arena, arena_one, ext_ptr[0], ext_ld, maps, n_maps,
-                   perms, n_perms, d_ws, ws_one, range_flag, &nm, stream);
+                   perms, n_perms, d_ws, ws_one, range_flag, &nm, plan_maps, stream);
 }
-
-}  // extern "C"
 
 namespace {
 
 int net_run(const cv_net_op* ops, int n_ops, const cv_net_buf* bufs, int n_bufs, const long long* level_rows, int n_levels,
             void* d_arena, size_t arena_bytes, const void* const* ext_ptr, const int* ext_ld, const int32_t* const* maps,
             int n_maps, const int32_t* const* perms, int n_perms, void* d_ws, size_t ws_bytes, int32_t* range_flag,
-            const NetModels* nm, void* stream) {
+            const NetModels* nm, bool plan_maps, void* stream) {
     CV_REQUIRE(ops && bufs && level_rows && d_arena && n_ops > 0 && n_bufs > 0 && n_levels > 0, CV_EINVAL,
                "bad network program arguments");
     CV_REQUIRE(arena_bytes >= cv_net_arena_bytes(bufs, n_bufs, level_rows, n_levels), CV_ENOMEM, "arena too small");
@@ -490,6 +514,8 @@ int net_run(const cv_net_op* ops, int n_ops, const cv_net_buf* bufs, int n_bufs,
             d.row_perm = perm;
             d.perm_groups = o.perm_groups;
             d.perm_has_map = o.perm_groups > 1;      /* scene maps build the orders with their map rows */
+            // (the plan's validity words: level_rows-many behind the [rows][27] map, scene_maps_layout)
+            if (plan_maps && d.perm_has_map && o.K == 27 && d.nbr) d.valid_words = d.nbr + out.rows * 27;
         }
         int rc;
         if (nm) {

@@ -205,8 +205,8 @@ int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream
     // ---- network forward
     const void* ext_ptr[2] = {d->d_feats, d->d_out_feats};
     const int ext_ld[2] = {d->feats_ld, d->out_ld};
-    rc = cv_net_run_f32(d->ops, d->n_ops, d->bufs, d->n_bufs, f.rows, 5, arena, arena_b, ext_ptr, ext_ld, f.maps, CV_NET_MAP_SLOTS,
-                        f.perms, CV_NET_PERM_SLOTS, conv_ws, f.conv_ws_b, d->use_range_flag ? d_flag : nullptr, stream);
+    rc = cv_net_run_ex(d->ops, d->n_ops, d->bufs, d->n_bufs, f.rows, 5, arena, arena_b, ext_ptr, ext_ld, f.maps, CV_NET_MAP_SLOTS,
+                       f.perms, CV_NET_PERM_SLOTS, conv_ws, f.conv_ws_b, d->use_range_flag ? d_flag : nullptr, /* plan_maps */ true, stream);
     if (rc != CV_OK) return rc;
     clock.lap(1);
     CV_HIP_CHECK(clock.mark(1));
@@ -346,18 +346,18 @@ int cv_detect_scene_separate_f32(const cv_scene_separate_desc* d, cv_scene_separ
             ext_tab[m] = ext_ptr[m];
         }
         const int ext_ld[2] = {d->feats_ld, d->out_ld};
-        rc = cv_net_run_models_f32(d->ops + m0, d->bufs + m0, d->n_ops[0], d->n_bufs[0], g, f.rows, 5, arena, arena_all, ext_tab, ext_ld,
-                                   f.maps, CV_NET_MAP_SLOTS, f.perms, CV_NET_PERM_SLOTS, conv_ws, conv_ws_all,
-                                   d->use_range_flag ? d_flags + 16 * m0 : nullptr,
-                                   static_cast<const cv_net_model_params*>(d->d_model_params) + m0, K, stream);
+        rc = cv_net_run_models_ex(d->ops + m0, d->bufs + m0, d->n_ops[0], d->n_bufs[0], g, f.rows, 5, arena, arena_all, ext_tab, ext_ld,
+                                  f.maps, CV_NET_MAP_SLOTS, f.perms, CV_NET_PERM_SLOTS, conv_ws, conv_ws_all,
+                                  d->use_range_flag ? d_flags + 16 * m0 : nullptr,
+                                  static_cast<const cv_net_model_params*>(d->d_model_params) + m0, K, /* plan_maps */ true, stream);
         if (rc != CV_OK) return rc;
     }
     for (int k = 0; G == 0 && k < K; ++k) {
         const void* ext_ptr[2] = {d->d_feats, d->d_out_feats[k]};
         const int ext_ld[2] = {d->feats_ld, d->out_ld};
-        rc = cv_net_run_f32(d->ops[k], d->n_ops[k], d->bufs[k], d->n_bufs[k], f.rows, 5, arena, arena_b, ext_ptr, ext_ld, f.maps,
-                            CV_NET_MAP_SLOTS, f.perms, CV_NET_PERM_SLOTS, conv_ws, f.conv_ws_b,
-                            d->use_range_flag ? d_flags + 16 * k : nullptr, stream);
+        rc = cv_net_run_ex(d->ops[k], d->n_ops[k], d->bufs[k], d->n_bufs[k], f.rows, 5, arena, arena_b, ext_ptr, ext_ld, f.maps,
+                           CV_NET_MAP_SLOTS, f.perms, CV_NET_PERM_SLOTS, conv_ws, f.conv_ws_b,
+                           d->use_range_flag ? d_flags + 16 * k : nullptr, /* plan_maps */ true, stream);
         if (rc != CV_OK) return rc;
     }
     clock.lap(1);

@@ -185,32 +185,48 @@ __global__ __launch_bounds__(256) void conv_finish(ConvArgs a, MA... ma) {
 // up to FINISH_SMALL_MAX partial tiles (the mask groups, the split-K of the middle levels) with 16-byte aligned
 // operands: a thread owns a float4 of the output, has all its partial loads in flight at once and runs the epilogue
 // itself - no LDS exchange, no barriers, every thread stores (ts1 96 -> 96 conv + finish: 125 -> 104 us).  Summation
-// order = conv_finish's: four running sums over the partials k % 4, then ((s0 + s1) + s2) + s3 - bit-identical results.
+// order = conv_finish's: four running sums (from +0) over the partials k % 4, then ((s0 + s1) + s2) + s3 - bit-identical results.
+//   - instances per class of the split count (SMAX = 4, 8, 16 slots: three mask groups do not carry sixteen predicated
+//     slots - 23 / 40 / 72 VGPRs, it was one instance of 80);
+//   - IDX: item, row and column arithmetic in 32 bits where n_out * cout fits (the host decides), else in 64;
+//   - no grid cap and no stride loop: the grid covers the items.
+// Which partials exist comes as ONE word per row, loaded in front of the partials: w & gm.m[k] != 0 = partial k of the row was
+// written.  Without validity data (a.gvalid NULL) the word is all ones and m[k] is all ones for k < splits, 0 behind; with it
+// (zskip) the word is the row's validity word and m[k] the bits of mask group k's offsets.  A partial that was not written
+// is not loaded (zskip saves the read as well as the write) and adds +0 in its place - the adds of zero stay, they decide the
+// sign of a zero sum.
+// Measured and dropped (LABNOTES "Zero tiles", profiles/zero_tiles/rates_variants.txt; parent 655-672 scenes/s seven in flight):
+// a thread that owns 8 columns (two float4 per partial, 16-byte hl stores) 651-661, several items per thread with every load of
+// all of them issued first 633-657 (8 columns) / 667-679 (4 columns x 2) against 676-682 for this form - a lane that owns 32 bytes
+// of a row halves what one load instruction of the wave covers contiguously, and fatter threads only cost registers (118 / 220
+// VGPRs) on a chip that other scenes' waves already fill.
 constexpr int FINISH_SMALL_MAX = 16;
-template <class... MA>
-__global__ __launch_bounds__(256) void conv_finish_small(ConvArgs a, MA... ma) {
+template <int SMAX> struct FinishMasks { unsigned m[SMAX]; };
+
+template <int SMAX, class IDX, class... MA>
+__global__ __launch_bounds__(256) void conv_finish_small(ConvArgs a, FinishMasks<SMAX> gm, MA... ma) {
     model_enter_y(a, ma...);
-    const long long total4 = a.n_out * (long long)a.cout / 4;
-    const int cq = a.cout >> 2;
-    for (long long e4 = blockIdx.x * 256ll + threadIdx.x; e4 < total4; e4 += (long long)gridDim.x * 256) {
-        const float4* p = reinterpret_cast<const float4*>(a.partial) + e4;
-        const long long row = e4 / cq;
-        float4 pv[FINISH_SMALL_MAX];
+    const IDX cq = (IDX)(a.cout >> 2);
+    const IDX total4 = (IDX)a.n_out * cq;
+    const IDX e4 = (IDX)blockIdx.x * (IDX)256 + (IDX)threadIdx.x;
+    if (e4 >= total4) return;
+    const IDX row = e4 / cq;
+    const int col = (int)(e4 - row * cq) * 4;
+    const unsigned w = a.gvalid ? (unsigned)a.gvalid[row] : ~0u;
+    const float4* p = reinterpret_cast<const float4*>(a.partial) + e4;
+    float4 pv[SMAX];
 #pragma unroll
-        for (int k = 0; k < FINISH_SMALL_MAX; ++k)          // (a.gvalid: partial tiles of rows without a neighbour in group k were never written)
-            pv[k] = (k < a.splits && (!a.gvalid || a.gvalid[(long long)k * a.n_out + row]))
-                        ? partial_load4(p + (long long)k * total4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const int col = (int)(e4 - row * cq) * 4;
-        float4 sq[4];
+    for (int k = 0; k < SMAX; ++k)
+        pv[k] = (w & gm.m[k]) ? partial_load4(p + (long long)k * (long long)total4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 sq[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) sq[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int q = 0; q < 4; ++q) sq[q] = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-        for (int k = 0; k < FINISH_SMALL_MAX; ++k)
-            if (k < a.splits) { sq[k & 3].x += pv[k].x; sq[k & 3].y += pv[k].y; sq[k & 3].z += pv[k].z; sq[k & 3].w += pv[k].w; }
-        const float4 x = make_float4(sq[0].x + sq[1].x + sq[2].x + sq[3].x, sq[0].y + sq[1].y + sq[2].y + sq[3].y,
-                                     sq[0].z + sq[1].z + sq[2].z + sq[3].z, sq[0].w + sq[1].w + sq[2].w + sq[3].w);
-        epilogue_apply4(a, row, col, x);
-    }
+    for (int k = 0; k < SMAX; ++k)
+        if (k < a.splits) { sq[k & 3].x += pv[k].x; sq[k & 3].y += pv[k].y; sq[k & 3].z += pv[k].z; sq[k & 3].w += pv[k].w; }
+    const float4 x = make_float4(sq[0].x + sq[1].x + sq[2].x + sq[3].x, sq[0].y + sq[1].y + sq[2].y + sq[3].y,
+                                 sq[0].z + sq[1].z + sq[2].z + sq[3].z, sq[0].w + sq[1].w + sq[2].w + sq[3].w);
+    epilogue_apply4(a, (long long)row, col, x);
 }
 
 // scalar variant for cout % 4 != 0
@@ -227,6 +243,22 @@ __global__ __launch_bounds__(256) void conv_finish_scalar(ConvArgs a, MA... ma) 
     }
 }
 
+// conv_finish_small's instance for (split-count class, index width), its masks and its grid
+template <int SMAX, class IDX>
+void launch_finish_small(const ConvArgs& a, hipStream_t st, const ModelArgs* ma, int models) {
+    FinishMasks<SMAX> gm;
+    for (int k = 0; k < SMAX; ++k) {
+        gm.m[k] = k < a.splits ? ~0u : 0u;
+        if (a.gvalid && k < a.splits) {      // (K <= 32, the dispatcher's condition) group k's offsets, as the kernels and the orders split them
+            const int jb = a.K * k / a.splits, je = a.K * (k + 1) / a.splits;
+            gm.m[k] = (unsigned)(((1ull << je) - 1) & ~((1ull << jb) - 1));
+        }
+    }
+    const long long items = a.n_out * (long long)a.cout / 4;
+    const dim3 grid((unsigned)((items + 255) / 256), (unsigned)models);
+    with_models(ma, [&](auto... m) { conv_finish_small<SMAX, IDX, decltype(m)...><<<grid, 256, 0, st>>>(a, gm, m...); });
+}
+
 std::atomic<int> g_ablation{0};
 // reduce the partial tiles + epilogue (ma: over `models` models, blockIdx.y; the same kernel choice and x grid per model)
 int launch_finish(const ConvArgs& a, hipStream_t st, const ModelArgs* ma, int models) {
@@ -235,9 +267,15 @@ int launch_finish(const ConvArgs& a, hipStream_t st, const ModelArgs* ma, int mo
     const auto grid = [&](long long items, int per_block, long long cap) {      // items: float4s or words of the output
         return dim3((unsigned)std::min<long long>((items + per_block - 1) / per_block, cap), (unsigned)models);
     };
-    if (a.wide && a.splits <= FINISH_SMALL_MAX)
-        with_models(ma, [&](auto... m) { conv_finish_small<decltype(m)...><<<grid(total / 4, 256, 16384), 256, 0, st>>>(a, m...); });
-    else if (a.cout % 4 == 0)
+    if (a.wide && a.splits <= FINISH_SMALL_MAX) {
+        const auto with_idx = [&](auto smax) {
+            if (total < (1ll << 31)) launch_finish_small<smax.value, unsigned>(a, st, ma, models);
+            else launch_finish_small<smax.value, long long>(a, st, ma, models);
+        };
+        if (a.splits <= 4) with_idx(std::integral_constant<int, 4>{});
+        else if (a.splits <= 8) with_idx(std::integral_constant<int, 8>{});
+        else with_idx(std::integral_constant<int, FINISH_SMALL_MAX>{});
+    } else if (a.cout % 4 == 0)
         with_models(ma, [&](auto... m) { conv_finish<decltype(m)...><<<grid(total / 4, 64, 8192), 256, 0, st>>>(a, m...); });
     else
         with_models(ma, [&](auto... m) { conv_finish_scalar<decltype(m)...><<<grid(total, 256, 4096), 256, 0, st>>>(a, m...); });
@@ -249,11 +287,17 @@ int launch_finish(const ConvArgs& a, hipStream_t st, const ModelArgs* ma, int mo
 // defaults (profiles/r4/hd2_grid.txt, hd_shapes.txt): the 96-column fine-level launches (>= 16384 rows) on conv_hd, 8 waves x 2 ring
 // stages: 558 -> 573 scenes/s with eight scenes in flight (528 -> 575 under the one-call scene path); 32- and 64-column
 // launches and the coarse levels stay on conv_hl (conv_hd measured slower there)
-// zskip (round 5, OFF: measured slower, profiles/r5/zskip_ab.txt - 570 against 577 scenes/s seven in flight, 332 against 337 one
-// at a time): 27 % of a scan's rows have no neighbour in the first / last mask group; with the switch on their tiles write no
-// partial tile and the finish launch reads none for such (group, row) pairs - the three validity bytes a finish thread then
-// loads cost more than the zeros it no longer streams
-std::atomic<long long> g_opt_zskip{getenv("CV_ZSKIP") ? atoll(getenv("CV_ZSKIP")) : 0};
+// zskip (ON): 12-18 % of the (mask group, 128-row tile) pairs of a mask-sorted level hold no row with a neighbour in the group
+// (profiles/zero_tiles/dead_pairs.txt); those tiles write no partial tile and the finish launch loads none for such
+// (group, row) pairs.  Round 5 read three validity bytes per finish thread, each load in front of its partial's: 570 against
+// 577 scenes/s, off.  Since the rebuilt conv_finish_small the validity is ONE word per row (cv_conv_desc.valid_words: the scene
+// plan's word behind every 3x3x3 map), loaded in front of all partials: 84 MB less written and 39 MB less fetched per scene,
+// 679-682 against 665-675 scenes/s with the switch off and 664-666 for the parent, five alternated rounds (LABNOTES "Zero
+// tiles", profiles/zero_tiles/).  The words are the caller's: the library cannot check them against nbr, wrong words give wrong
+// sums.  The C ABI executor entry points (cv_net_run_f32, cv_net_run_models_f32) hand none over - the switch acts in the scene
+// calls and on cv_sp_conv_f32 descriptors that carry the words.
+std::atomic<long long> g_opt_zskip{getenv("CV_ZSKIP") ? atoll(getenv("CV_ZSKIP")) : 1};
+std::atomic<long long> g_zskip_launches{0};      // "zskip_launches": convolutions dispatched with validity words so far (tests: did the switch engage?)
 std::atomic<long long> g_opt_hd_mask{getenv("CV_HD") ? atoll(getenv("CV_HD")) : 4};
 std::atomic<long long> g_opt_hd_min_rows{getenv("CV_HD_MIN_ROWS") ? atoll(getenv("CV_HD_MIN_ROWS")) : 16384};
 std::atomic<long long> g_opt_hd_shape{getenv("CV_HD_SHAPE") ? atoll(getenv("CV_HD_SHAPE")) : 2};      // 0: 8 waves x 3 stages, 1: 4 x 2, 2: 8 x 2
@@ -386,13 +430,14 @@ int pick_splits(long long n_out, int cout, int K, int cin, bool vec) {
 
 static std::atomic<long long>* option_named(const char* name) {
     return !strcmp(name, "hd_mask") ? &g_opt_hd_mask : !strcmp(name, "hd_min_rows") ? &g_opt_hd_min_rows :
-           !strcmp(name, "hd_shape") ? &g_opt_hd_shape : !strcmp(name, "zskip") ? &g_opt_zskip : nullptr;
+           !strcmp(name, "hd_shape") ? &g_opt_hd_shape : !strcmp(name, "zskip") ? &g_opt_zskip :
+           !strcmp(name, "zskip_launches") ? &g_zskip_launches : nullptr;
 }
 
 int cv_sp_set_option(const char* name, long long value, long long* previous) {
     CV_REQUIRE(name, CV_EINVAL, "null option name");
     std::atomic<long long>* o = option_named(name);
-    CV_REQUIRE(o, CV_EINVAL, "unknown option '%s' (hd_mask, hd_min_rows, hd_shape, zskip)", name);
+    CV_REQUIRE(o, CV_EINVAL, "unknown option '%s' (hd_mask, hd_min_rows, hd_shape, zskip, zskip_launches)", name);
     const long long before = o->exchange(value, std::memory_order_relaxed);
     if (previous) *previous = before;
     return CV_OK;
@@ -565,10 +610,13 @@ static int conv_dispatch(const cv_conv_desc* d, const CvConvModels* mm, void* st
             a.nbr_perm = d->row_perm + (long long)d->perm_groups * d->n_out;
             a.nbr_perm_w = (d->K + d->perm_groups - 1) / d->perm_groups;
             // zskip: tiles whose rows have no neighbour in their group write no partial tile and the finish launch does not read
-            // one (the validity bytes sit behind the map rows).  Not with a second source (its chunks are dealt to the groups:
-            // every row gets a sum from them) and only where conv_finish_small finishes.
-            if (g_opt_zskip.load(std::memory_order_relaxed) && !d->in2 && a.wide && d->perm_groups <= FINISH_SMALL_MAX && d->in_hl)
-                a.gvalid = reinterpret_cast<const unsigned char*>(a.nbr_perm + (long long)d->perm_groups * d->n_out * a.nbr_perm_w);
+            // one (validity: the caller's word per row, cv_conv_desc.valid_words).  Not with a second source (its chunks are
+            // dealt to the groups: every row gets a sum from them) and only where conv_finish_small finishes.
+            if (g_opt_zskip.load(std::memory_order_relaxed) && d->valid_words && d->K <= 32 && !d->in2 && a.wide &&
+                d->perm_groups <= FINISH_SMALL_MAX && d->in_hl) {
+                a.gvalid = d->valid_words;
+                g_zskip_launches.fetch_add(1, std::memory_order_relaxed);
+            }
         }
     } else if (d->flavour == 0) {
         int sp = pick_splits(d->n_out, d->cout, je - jb, d->cin, vec);

@@ -56,8 +56,9 @@ struct ConvArgs {
     int* tickets;                // conv_hl split-K: arrival counters per output tile (zero; the last arriver reduces, see there)
     const float* acc_scale_dev;  // optional device scalar multiplied into acc_scale (the input gradient's hl operand carries a
                                  // per-layer power of two chosen on the device)
-    const unsigned char* gvalid; // mask groups: [splits][n_out] 1 = the row has a neighbour in the group; tiles without any write no
-                                 // partial tile and conv_finish_small reads none for such (group, row) pairs (NULL: off)
+    const int* gvalid;           // mask groups: [n_out] the row's validity word, bit j = entry j of its kernel map >= 0 (K <= 32; group g
+                                 // of the row is live when bits [K g / splits, K (g + 1) / splits) are not all zero).  Tiles without a
+                                 // live row write no partial tile and conv_finish_small reads none for dead (group, row) pairs (NULL: off)
 };
 
 // ---- model axis: K structurally identical programs as ONE launch sequence (cv_net_run_models_f32) ------------------------

@@ -280,6 +280,8 @@ class CoordinateManager:
                 cm_s._maps[("upperm", 16 >> i)] = arena[off.up_perm[i]:off.up_perm[i] + c[3 - i]]
             for i in range(5):
                 cm_s._maps[("k", 3, 1 << i, 1)] = view(off.k3[i], c[i], 27)
+                if i == 0 or off.mask_perm[i] >= 0:     # the map builder's validity words lie behind these maps (map_valid_words)
+                    cm_s._maps[("k", 3, 1 << i, 1)]._cv_valid_words = arena[off.k3[i] + 27 * c[i]:off.k3[i] + 28 * c[i]]
                 if off.mask_perm[i] >= 0:
                     mp = view(off.mask_perm[i], G, c[i])
                     mp._cv_has_map = True              # the map rows in processing order follow in the arena
@@ -488,6 +490,8 @@ def conv_forward(x_feats, weight, nbr, n_out, scale=None, shift=None, residual=N
         d.ws, d.ws_bytes = ws.data_ptr(), ws.numel()
     if row_perm is not None:
         d.row_perm, d.perm_has_map = row_perm.data_ptr(), bool(perm_groups > 1 and getattr(row_perm, "_cv_has_map", False))
+        if d.perm_has_map and nbr is not None and K <= 32 and option("zskip"):
+            d.valid_words = map_valid_words(nbr).data_ptr()
     if j_begin or j_end:
         d.j_begin, d.j_end = j_begin, j_end
     if acc_in is not None:
@@ -572,6 +576,16 @@ def map_mask_perms(nbr, groups):
         return hit          # built with the scene's coordinate plan (its own group count): no second sort of the same map
     if hit is None or hit.shape[0] != groups:
         hit = nbr._cv_mask_perms = _perms_with_map(nbr, groups)
+    return hit
+
+
+def map_valid_words(nbr):
+    """int32 [n]: bit j of word i = nbr[i, j] >= 0 (K <= 32) - cv_conv_desc.valid_words, cached on the map.  A map of the
+    scene plan carries the words its builder left behind it; for any other map they are made here, once."""
+    hit = getattr(nbr, "_cv_valid_words", None)
+    if hit is None:
+        bits = torch.ones(nbr.shape[1], dtype=torch.int64, device=nbr.device) << torch.arange(nbr.shape[1], device=nbr.device)
+        hit = nbr._cv_valid_words = ((nbr >= 0) * bits).sum(1).to(torch.int32)
     return hit
 
 

@@ -56,7 +56,8 @@ extern "C" {
  *    arrays) from raw scans (additive: no struct or signature moved).
  *    Still 6: cv_row_loss_fwd_f32 / cv_row_loss_bwd_f32 (cv_row_loss_desc) with cv_row_loss_workspace_bytes,
  *    cv_row_loss_chunk_rows and cv_sizeof_row_loss_desc, the per-row training losses of both models (masked squared errors of
- *    the chosen head and the cross entropy) and the validation form of the joint one (additive: no struct or signature moved). */
+ *    the chosen head and the cross entropy) and the validation form of the joint one (additive: no struct or signature moved).
+ *    Still 6: a trailing cv_conv_desc.valid_words (appended: a zero-initialised descriptor runs as before). */
 #define CV_ABI_VERSION 6
 int cv_abi_version(void);
 const char* cv_last_error(void);
@@ -573,6 +574,9 @@ typedef struct cv_conv_desc {
     const float* acc_scale_dev; /* optional, hl-format input only: a device scalar multiplied into acc_scale when the kernel
                                runs (the training backward scales a layer's gradient rows by a power of two chosen on the
                                device, cv_sp_bn_backward_hl_f32, and hands the inverse over here: no host wait). */
+    const int32_t* valid_words; /* optional, with perm_has_map and K <= 32: [n_out] validity word of every row of nbr, bit j =
+                               nbr[row][j] >= 0 (the scene plan leaves one behind each 3x3x3 map).  Read only under option
+                               "zskip": (group, row) pairs without a neighbour then cost no partial tile.  NULL: as before. */
 } cv_conv_desc;
 #define CV_SPLIT_TICKETS 4096
 
@@ -648,8 +652,11 @@ int cv_sp_set_ablation(int bits);
  * bit-identical under every setting).  "hd_mask": bit NB - 1 sends the hl-format convolutions whose workgroups are
  * NB x 32 columns wide to conv_hd (LDS-DMA operand rings, 256-row workgroups) instead of conv_hl when the launch has at
  * least "hd_min_rows" output rows; "hd_shape": 0 = 8 waves x 3 ring stages (one workgroup per CU), 1 = 4 waves x 2 stages
- * (two per CU), 2 = 8 waves x 2 stages.  *previous (may be NULL) receives the old value.  Environment defaults: CV_HD,
- * CV_HD_MIN_ROWS, CV_HD_SHAPE. */
+ * (two per CU), 2 = 8 waves x 2 stages.  "zskip" (CV_ZSKIP, default 0): mask-sorted hl convolutions whose descriptor carries
+ * cv_conv_desc.valid_words write and read no partial tile for (group, row) pairs without a neighbour; the scene calls pass
+ * their plan's words, cv_net_run_f32 / cv_net_run_models_f32 pass none (the knob does nothing there).  "zskip_launches": not
+ * a knob but a counter - convolutions dispatched with validity words so far; set it to reset it.
+ * *previous (may be NULL) receives the old value.  Environment defaults: CV_HD, CV_HD_MIN_ROWS, CV_HD_SHAPE, CV_ZSKIP. */
 int cv_sp_set_option(const char* name, long long value, long long* previous);
 /* Reads a knob of cv_sp_set_option without touching it (other threads may be launching). */
 int cv_sp_get_option(const char* name, long long* value);
