@@ -1,7 +1,7 @@
 """Hand-made cases for the device proposal sampler (cv_prop_columns_f32 / cv_prop_select_f32), numpy only and without a vote:
 grids, scale grids, seeds and draws from seeded generators, plus a numpy restatement of the contract of include/cv_hip.h in
 the kernel's own precision.  Shared by tests/test_proposals_device.py (CPU: the restatement against the oracle, the case
-conditions) and tests/test_proposals_device_gpu.py (the kernels against the oracle)."""
+conditions), tests/test_proposals_device_gpu.py (the kernels against the oracle) and tests/test_proposals_edges_gpu.py."""
 import math
 
 import numpy as np
@@ -9,7 +9,17 @@ import numpy as np
 F32 = np.float32
 RADIUS = 0.3
 SHAPES = [(1, 1, 1), (3, 2, 5), (16, 7, 16), (17, 3, 15), (1, 4, 257), (32, 5, 33)]
+# seed counts either side of the constants the select kernel has, or had: 256 was its lane count when the seeds were staged
+# one per lane (SEED_COUNTS, the random and scripted cases), and today it stages SEED_TILE = 1024 seeds (3072 words) per LDS
+# tile with 1024 lanes, so the staging loop takes its second trip at 342 seeds and its third at 683, and a second tile
+# starts at seed 1024 (TILE_SEEDS, the seed-tile cases)
 SEED_COUNTS = [1, 255, 256, 257]
+# V -> positions of the near seeds in the seed list, on both sides of 341 | 342, 682 | 683, 1023 | 1024 and 2047 | 2048
+TILE_SEEDS = {342: (0, 340, 341), 683: (341, 342, 682), 1023: (0, 682, 1022), 1024: (682, 683, 1023), 1025: (683, 1023, 1024),
+              2049: (1024, 1025, 2047, 2048), 3000: (2047, 2048, 2999)}
+# the named wrong results that read only a part of the seed list: the first trip of the staging loop, the first tile, two tiles
+SEED_CUTS = {"first_trip_only": 341, "first_tile_only": 1024, "second_tile_short": 2048}
+PRODUCTION_SEED = 5                                           # (case_margin of the draws it gives: 3e-4)
 BUDGETS = [(1, 1), (3, 2), (192, 128), (1536, 1024)]          # (per_round S, num_proposal P), S = int(1.5 P)
 
 
@@ -95,8 +105,10 @@ def nearest_f64(world, seeds):
 def select_contract(yidx, grid_scale, corner, res, seeds, draws, P, start=0, rows=None, wrong=None):
     """cv_prop_select_f32 in draws mode: (cand [P,3], scale [P,3], filled, rounds_used); rows beyond ``filled`` keep what
     ``rows`` = (cand, scale) held (NaN without).  wrong: one of the named wrong results ("fused_world", "keep_nothing",
-    "no_truncation", "last_argmax" is a wrong yidx and lives in the caller)."""
+    "no_truncation", the seed-list cuts of SEED_CUTS; "last_argmax" is a wrong yidx and lives in the caller)."""
     X, Y, Z = grid_scale.shape[:3]
+    if wrong in SEED_CUTS:                                     # a WRONG result: only the front of the seed list is read
+        seeds = seeds[:SEED_CUTS[wrong]]
     cand = np.full((P, 3), np.nan, F32) if rows is None else rows[0].copy()
     scale = np.full((P, 3), np.nan, F32) if rows is None else rows[1].copy()
     got_c, got_s = [cand[:start]], [scale[:start]]
@@ -145,24 +157,25 @@ def _random_case(rng, name, shape, V, S, P, rounds, res, pow=0.5, grid=None):
     return Case(name, grid, gs, corner, res, seeds, draws[:used + 1], P, pow)
 
 
-def _layout(rng, shape, V, res=1.0):
+def _layout(rng, shape, V, res=1.0, near_at=None):
     """a grid whose columns with flat index below n / 2 are near (a seed sits on their cell) and the others at least `res`
-    = 1 m away from every seed; seeds beyond the near columns are 100 m away"""
+    = 1 m away from every seed; seeds beyond the near columns are 100 m away.  near_at: the positions in the seed list of
+    the near seeds (the seed at near_at[j] sits on column j, every other seed is 100 m away); the front of the list without"""
     X, Y, Z = shape
     n = X * Z
     grid = distinct_grid(rng, shape)
     gs = rng.uniform(0.1, 2.0, shape + (3,)).astype(F32)
     corner = np.array([0.5, -1.0, 2.0], F32)
     yidx = grid.argmax(1).reshape(-1)
-    near_cells = np.arange(min(n // 2, V))
+    near_cells = np.arange(min(n // 2, V) if near_at is None else len(near_at))
     seeds = np.full((V, 3), 100.0, F32)
-    seeds[:len(near_cells)] = world_of(near_cells, yidx, Z, res, corner)
+    seeds[np.arange(len(near_cells)) if near_at is None else np.asarray(near_at)] = world_of(near_cells, yidx, Z, res, corner)
     return grid, gs, corner, seeds, len(near_cells), n
 
 
-def _scripted(rng, name, shape, V, S, P, near_counts, res=1.0):
+def _scripted(rng, name, shape, V, S, P, near_counts, res=1.0, near_at=None):
     """draws with exactly near_counts[r] near draws in round r, at random places of the round"""
-    grid, gs, corner, seeds, n_near, n = _layout(rng, shape, V, res)
+    grid, gs, corner, seeds, n_near, n = _layout(rng, shape, V, res, near_at)
     draws = np.empty((len(near_counts), S), np.int64)
     for r, k in enumerate(near_counts):
         row = rng.integers(n_near, n, S)                       # far columns
@@ -195,6 +208,15 @@ def select_cases():
         if name in ("ties", "all_equal", "nan_cell", "inf_cell", "zeros_pow2", "zeros_pow0.5"):
             shape = grid.shape
             out.append(_random_case(rng, "grid_" + name, shape, 255, 192, 128, 64, res=0.23, pow=pow, grid=grid))
+    # (generators of their own from here on: the cases above keep their bytes)
+    # seed tiles: a few near seeds at the list positions of TILE_SEEDS, three rounds of 60 near draws each (P inside round 3)
+    rng = np.random.default_rng(12)
+    for V, near_at in TILE_SEEDS.items():
+        out.append(_scripted(rng, "tile_V%d" % V, (32, 5, 33), V, 192, 128, [60, 60, 60], near_at=near_at))
+    # rounds longer than the workgroup over two tiles and a seed: a lane without a draw in the last chunk still stages seeds
+    out.append(_scripted(rng, "tile_chunks_V2049", (32, 5, 33), 2049, 1536, 1024, [500, 300, 400], near_at=TILE_SEEDS[2049]))
+    # the reference's own sizes (BRNet: 1024 vote points per sample, num_proposal = 512) on a 5 m x 2 m x 5 m map
+    out.append(_random_case(np.random.default_rng(PRODUCTION_SEED), "production", (100, 40, 101), 1024, 768, 512, 64, res=0.05))
     return out
 
 

@@ -1,6 +1,6 @@
 """The device proposal sampler without a GPU: the C ABI surface and its host-side validation, the SUN RGB-D caller's
 imports, and the contract itself - a numpy restatement of cv_prop_select_f32 in the kernel's precision against the fp64
-oracle on every hand-made case, the case conditions that make that comparison decidable, and five named wrong results."""
+oracle on every hand-made case, the case conditions that make that comparison decidable, and eight named wrong results."""
 import ctypes
 import math
 import os
@@ -181,6 +181,56 @@ def test_named_wrong_results_are_outside_the_contract():
     u = np.float32(0.99999994)
     assert cell_in_bracket(pc.cell_of_uniform(u, cdf), u, dist)
     assert not cell_in_bracket(pc.cell_of_uniform(u, cdf, wrong="off_by_one"), u, dist)
+    # 6. - 8. a seed list read in part: the first trip of the staging loop (341 seeds), the first tile (1024), two tiles
+    # (2048).  Every seed-tile case rejects each one that is shorter than its list.
+    applied = {w: 0 for w in pc.SEED_CUTS}
+    for case in TILE_CASES:
+        _, yidx, _, _, _ = pc.columns_contract(case.grid, case.pow)
+        a = (case.grid_scale, case.corner, case.res, case.seeds, case.draws, case.P)
+        ref_c, ref_s, _, _ = _oracle(case)
+        assert pc.select_contract(yidx, *a)[0].tobytes() == ref_c.tobytes()
+        for w, cut in pc.SEED_CUTS.items():
+            if len(case.seeds) > cut:
+                wrong_c, wrong_s, _, _ = pc.select_contract(yidx, *a, wrong=w)
+                assert wrong_c.tobytes() != ref_c.tobytes() and wrong_s.tobytes() != ref_s.tobytes(), (case, w)
+                applied[w] += 1
+    assert applied == {"first_trip_only": 8, "first_tile_only": 4, "second_tile_short": 3}
+
+
+TILE_CASES = [c for c in SELECT_CASES if c.name.startswith("tile_")]
+
+
+def test_seed_tile_cases_are_what_their_table_says():
+    """every V of the table and the long-round case; the near seeds at the listed positions and nowhere else; all three
+    rounds evaluated, so the tile loop is walked with a full budget; the nearest-seed margin of the layout is the radius"""
+    assert [len(c.seeds) for c in TILE_CASES] == list(pc.TILE_SEEDS) + [2049]
+    assert [(c.S, c.P) for c in TILE_CASES] == [(192, 128)] * 7 + [(1536, 1024)]
+    for case in TILE_CASES:
+        near_at = pc.TILE_SEEDS[len(case.seeds)]
+        assert np.flatnonzero((case.seeds != 100.0).any(1)).tolist() == list(near_at)
+        assert case.grid.shape == (32, 5, 33) and case.res == 1.0 and _oracle(case)[3] == 3 == len(case.draws)
+        assert abs(pc.case_margin(case) - 0.3) < 1e-6
+
+
+@pytest.mark.parametrize("at", [1024, 3])
+def test_nan_seed_in_the_contract_keeps_every_draw(at):
+    """a NaN wins the minimum: no draw is near, every round keeps all its draws; +Inf neither wins nor poisons it"""
+    case = _case("tile_V1025")
+    _, yidx, _, _, _ = pc.columns_contract(case.grid, case.pow)
+    Z = case.grid.shape[2]
+    seeds = case.seeds.copy()
+    seeds[at] = np.nan
+    with np.errstate(invalid="ignore"):
+        assert np.isnan(pc.nearest_f32(pc.world_of(case.draws[0], yidx, Z, case.res, case.corner), seeds)).all()
+        cand, _, filled, used = pc.select_contract(yidx, case.grid_scale, case.corner, case.res, seeds, case.draws, 300)
+    assert (filled, used) == (300, 2)
+    assert cand.tobytes() == pc.world_of(case.draws.reshape(-1)[:300], yidx, Z, case.res, case.corner).tobytes()
+    seeds[at] = np.inf
+    a = (yidx, case.grid_scale, case.corner, case.res)
+    with_inf = pc.select_contract(*a, seeds, case.draws, case.P)
+    without = pc.select_contract(*a, np.delete(case.seeds, at, 0), case.draws, case.P)
+    assert with_inf[0].tobytes() == without[0].tobytes() and with_inf[1].tobytes() == without[1].tobytes()
+    assert with_inf[2:] == without[2:] and with_inf[3] == 3
 
 
 def cell_in_bracket(c, u, dist):
