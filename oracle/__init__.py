@@ -7,7 +7,8 @@ path fails loudly when its HIP library is missing instead of falling back here.
 Contents (each file cites the reference lines it restates):
   hv_oracle.c      vote forward / average / backward   (hv_cuda_kernel.cu)
   decode_oracle.c  greedy decode + OBB IoU + NMS        (eval_joint.py, calc_map.py)
-  hv_numpy.py      independent numpy restatement of the vote (cross-check)
+  hv_numpy.py      independent numpy restatement of the vote (cross-check); the exact integer restatement of the tile
+                   algorithm (hv_forward_fixed) and the float64 references with their error models
   sparse_oracle.py MinkUNet34C on dense torch convs      (utils/minkunet.py, resnet.py)
 
 PARITY STATUS (per stage): head split, decode loop, joint loss and the
@@ -23,6 +24,7 @@ import subprocess
 import numpy as np
 
 from .hv_numpy import VOTE_BWD_ERROR_MODEL, vote_bwd_bounds      # noqa: F401  (next to hv_backward below)
+from .hv_numpy import VOTE_FWD_ERROR_MODEL, hv_forward_fixed, vote_fwd_bounds      # noqa: F401  (next to hv_forward below)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "_build", "libcv_oracle.so")

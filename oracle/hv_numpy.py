@@ -9,6 +9,10 @@ kernel can be measured.
 
 Follows houghvoting/src/hv_cuda_kernel.cu:25-96 (vote), :106-118 (average),
 :129-134 (grid dims).
+
+Below the restatement: the float64 reference and error model of the vote's gradient (hv_backward64, VOTE_BWD_ERROR_MODEL), the
+exact restatement of the tile algorithm's 2^-36 fixed-point sums (hv_forward_fixed: the bits hv_fwd_tiles must write) and the
+float64 reference and error model of the direct forward kernel (hv_forward64, VOTE_FWD_ERROR_MODEL).
 """
 import numpy as np
 
@@ -28,90 +32,6 @@ def rot_table(num_rots):
     rot_interval = f32(f32(2) * f32(3.141592654)) / f32(num_rots)   # :35
     theta = (np.arange(num_rots).astype(f32) * rot_interval).astype(f32)  # :37
     return np.cos(theta.astype(np.float64)).astype(f32), np.sin(theta.astype(np.float64)).astype(f32)
-
-
-def hv_forward(points, xyz, scale, obj, res, num_rots, acc_dtype=np.float64):
-    pts = np.asarray(points, f32)
-    xyz = np.asarray(xyz, f32)
-    scale = np.asarray(scale, f32)
-    obj = np.asarray(obj, f32)
-    res = f32(res)
-    corner, _, dims = grid_dims(pts, res)
-    X, Y, Z = dims
-    ct, st = rot_table(num_rots)
-    corr = (xyz * scale).astype(f32)                                   # :29-33
-    cx, cy, cz = corr[:, 0:1], corr[:, 1:2], corr[:, 2:3]
-    ox = ((-ct)[None] * cx).astype(f32) + (st[None] * cz).astype(f32)  # :38
-    oy = np.broadcast_to(-cy, ox.shape)
-    oz = ((-st)[None] * cx).astype(f32) - (ct[None] * cz).astype(f32)  # :39
-    g = [(((pts[:, k:k + 1] + o).astype(f32) - corner[k]).astype(f32) / res).astype(f32)
-         for k, o in enumerate((ox, oy, oz))]                          # :40
-    ok = (g[0] >= 0) & (g[1] >= 0) & (g[2] >= 0) & (g[0] < f32(X - 1)) & (g[1] < f32(Y - 1)) \
-        & (g[2] < f32(Z - 1))                                          # :41-44
-    pi, ri = np.nonzero(ok)
-    gx, gy, gz = (a[pi, ri] for a in g)
-    fl = [np.trunc(a).astype(np.int64) for a in (gx, gy, gz)]          # :45
-    fr = [(a - np.floor(a)).astype(f32) for a in (gx, gy, gz)]         # :47
-    w0 = [(f32(1) - a).astype(f32) for a in fr]                        # :49
-    w1 = fr                                                            # :50
-    o = obj[pi]
-    g_obj = np.zeros(X * Y * Z, acc_dtype)
-    g_rot = np.zeros((X * Y * Z, 2), acc_dtype)
-    g_scale = np.zeros((X * Y * Z, 3), acc_dtype)
-    for bx in (0, 1):
-        for by in (0, 1):
-            for bz in (0, 1):
-                wx = (w1 if bx else w0)[0]
-                wy = (w1 if by else w0)[1]
-                wz = (w1 if bz else w0)[2]
-                w = (((wx * wy).astype(f32) * wz).astype(f32) * o).astype(f32)   # :52-59
-                cell = ((fl[0] + bx) * Y + (fl[1] + by)) * Z + (fl[2] + bz)
-                np.add.at(g_obj, cell, w.astype(acc_dtype))
-                np.add.at(g_rot[:, 0], cell, (w * ct[ri]).astype(f32).astype(acc_dtype))
-                np.add.at(g_rot[:, 1], cell, (w * st[ri]).astype(f32).astype(acc_dtype))
-                for j in range(3):
-                    np.add.at(g_scale[:, j], cell, (w * scale[pi, j]).astype(f32).astype(acc_dtype))
-    # :112-117  x /= w + 1e-7 (double), stored as float.  The grid weight the
-    # reference divides by is the fp32-accumulated one; mirror that rounding.
-    w32 = g_obj.astype(f32)
-    d = w32.astype(np.float64) + 1e-7
-    g_rot = (g_rot.astype(f32).astype(np.float64) / d[:, None]).astype(f32)
-    g_scale = (g_scale.astype(f32).astype(np.float64) / d[:, None]).astype(f32)
-    return (w32.reshape(X, Y, Z), g_rot.reshape(X, Y, Z, 2), g_scale.reshape(X, Y, Z, 3),
-            int(ok.sum()))
-
-
-def contribution_counts(points, xyz, scale, res, num_rots, corner=None, dims=None, chunk=20000):
-    """int32 [X,Y,Z]: how many (vote, corner) contributions each cell receives (hv_cuda_kernel.cu:41-96: eight per
-    in-bounds vote).  Tests use it to state the accumulated-rounding bound of a cell's sums; same fp32 geometry as
-    hv_forward above, chunked over points so that a 300k-point scene stays within a few hundred MB."""
-    pts = np.asarray(points, f32)
-    xyz = np.asarray(xyz, f32)
-    scale = np.asarray(scale, f32)
-    res = f32(res)
-    if corner is None:
-        corner, _, dims = grid_dims(pts, res)
-    corner = np.asarray(corner, f32)
-    X, Y, Z = dims
-    ct, st = rot_table(num_rots)
-    counts = np.zeros(X * Y * Z, np.int64)
-    for a in range(0, len(pts), chunk):
-        p = pts[a:a + chunk]
-        corr = (xyz[a:a + chunk] * scale[a:a + chunk]).astype(f32)
-        cx, cy, cz = corr[:, 0:1], corr[:, 1:2], corr[:, 2:3]
-        ox = ((-ct)[None] * cx).astype(f32) + (st[None] * cz).astype(f32)
-        oy = np.broadcast_to(-cy, ox.shape)
-        oz = ((-st)[None] * cx).astype(f32) - (ct[None] * cz).astype(f32)
-        g = [(((p[:, k:k + 1] + o).astype(f32) - corner[k]).astype(f32) / res).astype(f32)
-             for k, o in enumerate((ox, oy, oz))]
-        ok = (g[0] >= 0) & (g[1] >= 0) & (g[2] >= 0) & (g[0] < f32(X - 1)) & (g[1] < f32(Y - 1)) & (g[2] < f32(Z - 1))
-        fl = [np.trunc(v[ok]).astype(np.int64) for v in g]
-        base = (fl[0] * Y + fl[1]) * Z + fl[2]
-        for bx in (0, 1):
-            for by in (0, 1):
-                for bz in (0, 1):
-                    counts += np.bincount(base + (bx * Y + by) * Z + bz, minlength=X * Y * Z)
-    return counts.reshape(X, Y, Z).astype(np.int32)
 
 
 def vote_geometry(points, xyz, scale, res, num_rots, corner, dims):
@@ -139,6 +59,61 @@ def vote_geometry(points, xyz, scale, res, num_rots, corner, dims):
     w1 = [(a - np.floor(a)).astype(f32) for a in gv]
     w0 = [(f32(1) - a).astype(f32) for a in w1]
     return pi, ri, fl, w0, w1
+
+
+def hv_forward(points, xyz, scale, obj, res, num_rots, acc_dtype=np.float64):
+    pts = np.asarray(points, f32)
+    scale = np.asarray(scale, f32)
+    obj = np.asarray(obj, f32)
+    corner, _, dims = grid_dims(pts, f32(res))
+    X, Y, Z = dims
+    ct, st = rot_table(num_rots)
+    pi, ri, fl, w0, w1 = vote_geometry(pts, xyz, scale, res, num_rots, corner, dims)   # :29-50
+    o = obj[pi]
+    g_obj = np.zeros(X * Y * Z, acc_dtype)
+    g_rot = np.zeros((X * Y * Z, 2), acc_dtype)
+    g_scale = np.zeros((X * Y * Z, 3), acc_dtype)
+    for bx in (0, 1):
+        for by in (0, 1):
+            for bz in (0, 1):
+                wx = (w1 if bx else w0)[0]
+                wy = (w1 if by else w0)[1]
+                wz = (w1 if bz else w0)[2]
+                w = (((wx * wy).astype(f32) * wz).astype(f32) * o).astype(f32)   # :52-59
+                cell = ((fl[0] + bx) * Y + (fl[1] + by)) * Z + (fl[2] + bz)
+                np.add.at(g_obj, cell, w.astype(acc_dtype))
+                np.add.at(g_rot[:, 0], cell, (w * ct[ri]).astype(f32).astype(acc_dtype))
+                np.add.at(g_rot[:, 1], cell, (w * st[ri]).astype(f32).astype(acc_dtype))
+                for j in range(3):
+                    np.add.at(g_scale[:, j], cell, (w * scale[pi, j]).astype(f32).astype(acc_dtype))
+    # :112-117  x /= w + 1e-7 (double), stored as float.  The grid weight the
+    # reference divides by is the fp32-accumulated one; mirror that rounding.
+    w32 = g_obj.astype(f32)
+    d = w32.astype(np.float64) + 1e-7
+    g_rot = (g_rot.astype(f32).astype(np.float64) / d[:, None]).astype(f32)
+    g_scale = (g_scale.astype(f32).astype(np.float64) / d[:, None]).astype(f32)
+    return (w32.reshape(X, Y, Z), g_rot.reshape(X, Y, Z, 2), g_scale.reshape(X, Y, Z, 3), len(pi))
+
+
+def contribution_counts(points, xyz, scale, res, num_rots, corner=None, dims=None, chunk=20000):
+    """int32 [X,Y,Z]: how many (vote, corner) contributions each cell receives (hv_cuda_kernel.cu:41-96: eight per
+    in-bounds vote).  Tests use it to state the accumulated-rounding bound of a cell's sums; the geometry is vote_geometry's,
+    chunked over points so that a 300k-point scene stays within a few hundred MB."""
+    pts = np.asarray(points, f32)
+    xyz = np.asarray(xyz, f32)
+    scale = np.asarray(scale, f32)
+    if corner is None:
+        corner, _, dims = grid_dims(pts, f32(res))
+    X, Y, Z = dims
+    counts = np.zeros(X * Y * Z, np.int64)
+    for a in range(0, len(pts), chunk):
+        _, _, fl, _, _ = vote_geometry(pts[a:a + chunk], xyz[a:a + chunk], scale[a:a + chunk], res, num_rots, corner, dims)
+        base = (fl[0] * Y + fl[1]) * Z + fl[2]
+        for bx in (0, 1):
+            for by in (0, 1):
+                for bz in (0, 1):
+                    counts += np.bincount(base + (bx * Y + by) * Z + bz, minlength=X * Y * Z)
+    return counts.reshape(X, Y, Z).astype(np.int32)
 
 
 # the eight cells of a vote in the order hv_bwd reads them (lll llh lhl lhh hll hlh hhl hhh): (bx, by, bz)
@@ -237,3 +212,179 @@ def vote_bwd_bounds(ref):
             v = v[:, None]
         out[name] = (VOTE_BWD_C0[name] + VOTE_BWD_K[name] * v) * U24 * ref["m_" + name[2:]] + 2.0 ** -149
     return out
+
+
+# ---------------------------------------------------------------------------
+# forward vote: the exact restatement of the tile algorithm, and the direct kernel's float64 reference and error model
+# ---------------------------------------------------------------------------
+FX_SCALE = 2.0 ** 36           # hv_vote.hip: every fp32 contribution is rounded once to a multiple of 2^-36
+FX_CLAMP = f32(6.0e7)          # fx_from_float: contributions beyond it are clamped
+
+
+def fx_quantum(v, truncate=False):
+    """int64 round(clip(v, -6e7, 6e7) * 2^36), ties to even: the word fx_from_float (hv_vote.hip) adds for the fp32
+    contribution v.  v * 2^36 is exact in float64, so both of the kernel's conversions - the magic-number fma inside
+    |v| < 2^15 and __double2ll_rn of the clamped value - give this word.  truncate: towards zero instead (a named wrong
+    result of tests/test_vote_fixed.py, not the kernel)."""
+    d = np.clip(np.asarray(v, f32), -FX_CLAMP, FX_CLAMP).astype(np.float64) * FX_SCALE
+    return (np.trunc(d) if truncate else np.rint(d)).astype(np.int64)
+
+
+def vote_contributions(points, xyz, scale, obj, res, num_rots, corner, dims, chunk=2000):
+    """Generator over chunks of points: (cell int64 [m], t f32 [6, m], point int64 [m]) - every (in-bounds vote, corner)
+    contribution: its flat cell, the six fp32 terms in channel order (objectness weight, w cos, w sin, w s0, w s1, w s2) and the
+    point it comes from.  w = ((wx wy) wz) obj and t = w c are single fp32 operations in the order of hv_fwd_direct and
+    drain_vote (hv_vote.hip) on vote_geometry's bits, so the terms are the kernels' bits."""
+    pts = np.asarray(points, f32)
+    xyz = np.asarray(xyz, f32)
+    scale = np.asarray(scale, f32)
+    obj = np.asarray(obj, f32)
+    X, Y, Z = dims
+    ct, st = rot_table(num_rots)
+    for a in range(0, len(pts), chunk):
+        pi, ri, fl, w0, w1 = vote_geometry(pts[a:a + chunk], xyz[a:a + chunk], scale[a:a + chunk], res, num_rots, corner, dims)
+        pi = pi + a
+        o = obj[pi]
+        chan = (ct[ri], st[ri], scale[pi, 0], scale[pi, 1], scale[pi, 2])
+        base = (fl[0] * Y + fl[1]) * Z + fl[2]
+        cells, terms = [], []
+        for bx, by, bz in CELLS:
+            w = ((((w1 if bx else w0)[0] * (w1 if by else w0)[1]).astype(f32) * (w1 if bz else w0)[2]).astype(f32) * o).astype(f32)
+            cells.append(base + (bx * Y + by) * Z + bz)
+            terms.append(np.stack([w] + [(w * c).astype(f32) for c in chan]))
+        yield np.concatenate(cells), np.concatenate(terms, 1), np.tile(pi, 8)
+
+
+def obj_quantum(w, truncate=False, nonzero_rule=True):
+    """the objectness channel's word (lds_add_obj): fx_quantum, but a non-zero weight never rounds to zero - it adds one
+    quantum of its sign"""
+    q = fx_quantum(w, truncate)
+    if nonzero_rule:
+        q = np.where((q == 0) & (w != 0), np.sign(w).astype(np.int64), q)
+    return q
+
+
+def reduce_by_cell(cell, values):
+    """(sorted unique cells, int64 sums [C, cells]) of values [C, m] - sort and np.add.reduceat, one channel at a time;
+    int64 addition wraps as the kernel's does"""
+    if len(cell) == 0:
+        return cell.astype(np.int64), np.zeros((len(values), 0), np.int64)
+    order = np.argsort(cell, kind="stable")
+    sc = cell[order]
+    starts = np.concatenate([[0], np.flatnonzero(sc[1:] != sc[:-1]) + 1])
+    return sc[starts], np.stack([np.add.reduceat(v[order], starts) for v in values])
+
+
+def fixed_sums(points, xyz, scale, obj, res, num_rots, corner, dims, truncate=False, nonzero_rule=True, chunk=2000):
+    """(cells int64 [c] sorted, sums int64 [6, c], counts int64 [c]): the tile algorithm's six integer sums at every cell that
+    receives a contribution, and how many it receives.  Memory goes with a chunk's contributions, not with the grid."""
+    ucells, usums = [], []
+    for cell, t, _ in vote_contributions(points, xyz, scale, obj, res, num_rots, corner, dims, chunk):
+        q = [obj_quantum(t[0], truncate, nonzero_rule)] + [fx_quantum(v, truncate) for v in t[1:]]
+        c, s = reduce_by_cell(cell, q + [np.ones(len(cell), np.int64)])
+        ucells.append(c)
+        usums.append(s)
+    if not ucells:
+        return np.zeros(0, np.int64), np.zeros((6, 0), np.int64), np.zeros(0, np.int64)
+    c, s = reduce_by_cell(np.concatenate(ucells), list(np.concatenate(usums, 1)))
+    return c, s[:6], s[6]
+
+
+def fixed_store(sums, double_divisor=False):
+    """(obj32 [c], quot f32 [5, c]) the tile kernel stores for the integer sums [6, c]: obj32 = float(sum0 2^-36), each quotient
+    float(double(float(sum_k 2^-36)) / (double(obj32) + 1e-7)).  double_divisor: divide by the unrounded double sum instead
+    (a named wrong result, not the kernel)."""
+    val = sums.astype(np.float64) * (1.0 / FX_SCALE)
+    obj32 = val[0].astype(f32)
+    d = (val[0] if double_divisor else obj32.astype(np.float64)) + 1e-7
+    with np.errstate(divide="ignore", invalid="ignore"):
+        quot = (val[1:].astype(f32).astype(np.float64) / d).astype(f32)
+    return obj32, quot
+
+
+def dense_grids(cells, obj32, quot, dims):
+    """the three dense float32 grids of sparse results, zeros elsewhere"""
+    X, Y, Z = dims
+    g_obj = np.zeros(X * Y * Z, f32)
+    g_rot = np.zeros((X * Y * Z, 2), f32)
+    g_scale = np.zeros((X * Y * Z, 3), f32)
+    g_obj[cells] = obj32
+    g_rot[cells] = quot[:2].T
+    g_scale[cells] = quot[2:].T
+    return g_obj.reshape(X, Y, Z), g_rot.reshape(X, Y, Z, 2), g_scale.reshape(X, Y, Z, 3)
+
+
+def hv_forward_fixed(points, xyz, scale, obj, res, num_rots, corner=None, dims=None, thresh=None):
+    """The bits hv_fwd_tiles (hv_vote.hip) must write, whatever its launch shape: (grid_obj, grid_rot, grid_scale) float32.
+
+    Per in-bounds vote and corner the six fp32 terms of vote_contributions; each is rounded once to an int64 multiple of 2^-36
+    (fx_quantum; objectness: obj_quantum), the words are summed per cell and channel as integers - exact and independent of
+    the order, so no cull, work list, part or round of the kernel may show in them - and stored by fixed_store.  Cells
+    without a contribution are zeros.  corner / dims: the grid of a vote into a box (default: the points' bounding box).
+    thresh (cv_hv_forward_peaks_f32): a fourth value, the mask grid_obj >= thresh; the quotients are defined only there."""
+    pts = np.asarray(points, f32)
+    if corner is None:
+        corner, _, dims = grid_dims(pts, f32(res))
+    cells, sums, _ = fixed_sums(pts, xyz, scale, obj, res, num_rots, corner, dims)
+    grids = dense_grids(cells, *fixed_store(sums), dims)
+    if thresh is None:
+        return grids
+    return grids + (grids[0] >= f32(thresh),)
+
+
+def hv_forward64(points, xyz, scale, obj, res, num_rots, corner=None, dims=None):
+    """float64 reference of the forward vote's sums before the division: dict(sum [X,Y,Z,6], mag [X,Y,Z,6], count [X,Y,Z]) -
+    per cell and channel (objectness, cos, sin, s0, s1, s2) the float64 sum of the fp32 terms of vote_contributions (the
+    kernels' bits), the sum of their absolute values, and the number of contributions n_c (contribution_counts)."""
+    pts = np.asarray(points, f32)
+    if corner is None:
+        corner, _, dims = grid_dims(pts, f32(res))
+    X, Y, Z = dims
+    n = X * Y * Z
+    total = np.zeros((6, n))
+    mag = np.zeros((6, n))
+    count = np.zeros(n, np.int64)
+    for cell, t, _ in vote_contributions(pts, xyz, scale, obj, res, num_rots, corner, dims):
+        count += np.bincount(cell, minlength=n)
+        for k in range(6):
+            v = t[k].astype(np.float64)
+            total[k] += np.bincount(cell, weights=v, minlength=n)
+            mag[k] += np.bincount(cell, weights=np.abs(v), minlength=n)
+    return dict(sum=total.T.reshape(X, Y, Z, 6).copy(), mag=mag.T.reshape(X, Y, Z, 6).copy(), count=count.reshape(X, Y, Z))
+
+
+VOTE_FWD_ERROR_MODEL = """Error model of the direct forward vote (hv_fwd_direct + hv_normalise, hv_vote.hip), per output element,
+against hv_forward64.  u = 2^-24, gamma(n) = n u / (1 - n u).
+
+The terms are the kernel's own bits (vote_contributions), so the only errors are those of the fp32 atomic additions, in whatever
+order they arrive, and of the division.
+
+  a sum of n_c terms t (grid_obj, and the numerators N of the quotients):
+      b = gamma(n_c) * sum |t| + n_c * 2^-126
+    Summed in any order a term passes through at most n_c - 1 additions, each (1 + d), |d| <= u: the error is at most
+    ((1 + u)^(n_c - 1) - 1) sum |t| <= gamma(n_c - 1) sum |t|; gamma(n_c) leaves one rounding spare.  The second part covers an
+    atomic unit that flushes a subnormal operand or result to zero: at most the smallest normal number per addition.
+
+  a quotient q = N / D, D = sum_obj + 1e-7 (hv_normalise: float(double(N32) / (double(D32) + 1e-7))):
+      b_q = (b_N + |q| b_D) / (D - b_D) + 2 u |q| + 2^-149
+    |N32 / D32' - N / D| <= (|N32 - N| + |q| |D32' - D|) / D32' and D32' >= D - b_D, valid where D - b_D > 0 (the tests assert
+    it at every touched cell; it holds wherever objectness >= 0).  The division is double, its result rounded once to fp32:
+    u |q'| <= 2 u |q| while the first part is below |q|, and one subnormal.
+
+  cells without a contribution: exact zeros in all three grids (0 / 1e-7)."""
+
+
+def vote_fwd_bounds(ref):
+    """dict(obj, rot, scale: the float64 values the direct kernel approximates; b_obj, b_rot, b_scale: their per-element bounds
+    (VOTE_FWD_ERROR_MODEL); margin [X,Y,Z]: D - b_D, which must be > 0 wherever count > 0) for a result of hv_forward64"""
+    n = ref["count"].astype(np.float64)[..., None]
+    b = n * U24 / (1.0 - n * U24) * ref["mag"] + n * 2.0 ** -126
+    D = ref["sum"][..., 0:1] + 1e-7
+    bD = b[..., 0:1]
+    margin = D - bD
+    q = ref["sum"][..., 1:] / D
+    with np.errstate(divide="ignore", invalid="ignore"):
+        bq = (b[..., 1:] + np.abs(q) * bD) / margin + 2 * U24 * np.abs(q) + 2.0 ** -149
+    bq = np.where(margin > 0, bq, np.nan)
+    return dict(obj=ref["sum"][..., 0], rot=q[..., :2], scale=q[..., 2:], b_obj=b[..., 0], b_rot=bq[..., :2],
+                b_scale=bq[..., 2:], margin=margin[..., 0])
