@@ -299,6 +299,10 @@ SIGNATURES = {
     "cv_decode_cat_f32": (ctypes.c_int, [vp, vp, vp, c_int_p, c_float_p, ctypes.c_float, vp, vp, vp, vp, ctypes.c_int64,
                                          ctypes.c_int, ctypes.POINTER(DecodeParams), ctypes.c_int, vp, ctypes.c_size_t, c_int_p,
                                          c_i64_p, c_i32_p, c_int_p, c_float_p, c_float_p, c_i32_p, c_int_p, vp]),
+    "cv_decode_instances_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "cv_decode_instances_f32": (ctypes.c_int, [vp, vp, c_int_p, c_float_p, ctypes.c_float, vp, vp, ctypes.c_int64, ctypes.c_int,
+                                               c_i64_p, c_i32_p, c_int_p, ctypes.c_int, ctypes.c_float, ctypes.c_int, vp, vp, vp,
+                                               vp, ctypes.c_size_t, vp]),
     "cv_detect_scene_separate_f32": (ctypes.c_int, [ctypes.POINTER(SceneSeparateDesc), ctypes.POINTER(SceneSeparateResult), vp]),
     "cv_sp_table_capacity": (ctypes.c_longlong, [ctypes.c_longlong]),
     "cv_sp_levels_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),

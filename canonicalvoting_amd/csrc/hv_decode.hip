@@ -954,7 +954,185 @@ int cv_decode_run(const DecodeCall& c, int K, bool need_class) {
     return CV_OK;
 }
 
+// ---- dec_instances: which scan points each final detection owns (cv_decode_instances_f32).  The decode's dec_backproject
+// forms the same membership (eval_joint.py:231-245: bbox_mask_world and mask) for every candidate before NMS and reduces it
+// to five statistics; here the caller names the boxes it wants - grid cells the decode examined, in priority order - and gets
+// the per-point answer.  Two launches, no host wait:
+//
+//   inst_boxes    one thread per (category, box): the geometry the decode gave the box's cell as a candidate (rotation and
+//                 scale as dec_compact, centre as the walk's candidate step), as a 12-word record in the workspace; the box's
+//                 two count words are zeroed.  The host lists travel as kernel arguments (INST_CHUNK entries per launch): they
+//                 are consumed when the launch is enqueued, so the caller may reuse them at once and nothing is pinned.
+//   inst_assign   one thread per scan point, category on blockIdx.y: the records of INST_GROUP boxes at a time through LDS,
+//                 walked in list order; the first box that has the point as a member owns it.
+namespace {
+
+constexpr int INST_GROUP = 64;      // boxes staged in LDS at a time (3 KB of records)
+constexpr int INST_REC = 12;        // words of a box record: centre xyz, cos | sin, scale xyz | label, three unused
+constexpr int INST_CHUNK = 256;     // (category, box) entries of one inst_boxes launch: 3 KB of the 4 KB kernel arguments
+
+struct InstChunk {
+    int cell[INST_CHUNK];           // flat grid cell
+    int label[INST_CHUNK];
+    int slot[INST_CHUNK];           // k * max_boxes + j: record and count position
+};
+struct InstCats {
+    int n_boxes[CV_MAX_CATEGORIES];
+};
+
+__global__ __launch_bounds__(INST_CHUNK) void inst_boxes(const float* __restrict__ g_rot, const float* __restrict__ g_scale,
+                                                         Geo geo, int64_t cells, int max_boxes, InstChunk ch, int count,
+                                                         unsigned* __restrict__ recs, int32_t* __restrict__ count_in,
+                                                         int32_t* __restrict__ count_owned) {
+    const int t = threadIdx.x;
+    if (t >= count) return;
+    const int id = ch.cell[t], slot = ch.slot[t];
+    const int64_t at = (int64_t)(slot / max_boxes) * cells + id;
+    const float r0 = g_rot[at * 2], r1 = g_rot[at * 2 + 1];
+    const float rot = (float)atan2((double)r1, (double)r0);                                // :214
+    const float cs = (float)cos((double)rot), sn = (float)sin((double)rot);
+    const int c[3] = {id / (geo.Z * geo.Y), (id / geo.Z) % geo.Y, id % geo.Z};
+    float* r = reinterpret_cast<float*>(recs + (int64_t)slot * INST_REC);
+    for (int d = 0; d < 3; ++d) r[d] = geo.corner[d] + geo.res * (float)c[d];               // :206
+    r[3] = cs;
+    r[4] = sn;
+    for (int d = 0; d < 3; ++d) r[5 + d] = g_scale[at * 3 + d];                             // :216
+    recs[(int64_t)slot * INST_REC + 8] = (unsigned)ch.label[t];
+    for (int d = 9; d < INST_REC; ++d) recs[(int64_t)slot * INST_REC + d] = 0u;
+    if (count_in) count_in[slot] = 0;
+    if (count_owned) count_owned[slot] = 0;
+}
+
+__global__ __launch_bounds__(256) void inst_assign(const float* __restrict__ pts, const float* __restrict__ prob, int64_t n,
+                                                   const unsigned* __restrict__ recs, InstCats cats, int max_boxes,
+                                                   float prob_thresh, int confident_only, int32_t* __restrict__ owner,
+                                                   int32_t* __restrict__ count_in, int32_t* __restrict__ count_owned) {
+    const int kc = blockIdx.y;
+    const int nbox = cats.n_boxes[kc];
+    recs += (int64_t)kc * max_boxes * INST_REC;
+    const int64_t i = blockIdx.x * 256ll + threadIdx.x;
+    const bool have = i < n;
+    float p0 = 0, p1 = 0, p2 = 0;
+    bool ok = have;                    // the point can be a member at all
+    if (have) {
+        p0 = pts[i * 3]; p1 = pts[i * 3 + 1]; p2 = pts[i * 3 + 2];
+        if (confident_only) ok = prob[kc * n + i] > prob_thresh;                            // :245 (a NaN prob is not confident)
+    }
+    const bool counting = count_in != nullptr || count_owned != nullptr;
+    __shared__ float4 l_rec[INST_GROUP * INST_REC / 4];
+    // per-workgroup counts, flushed once per group: integer sums, the same for every arrival order
+    __shared__ int l_in[INST_GROUP], l_owned[INST_GROUP];
+    int own = -1;
+    bool owned = false;
+    for (int j0 = 0; j0 < nbox; j0 += INST_GROUP) {
+        const int g = min(INST_GROUP, nbox - j0);
+        // (the barrier frees the previous group's LDS; without counts a workgroup whose points all have their owner is done)
+        if (counting) __syncthreads();
+        else if (!__syncthreads_or(ok && !owned)) break;
+        for (int e = threadIdx.x; e < g * INST_REC; e += 256)
+            reinterpret_cast<unsigned*>(l_rec)[e] = recs[(int64_t)j0 * INST_REC + e];
+        if (threadIdx.x < INST_GROUP) { l_in[threadIdx.x] = 0; l_owned[threadIdx.x] = 0; }
+        __syncthreads();
+        if (ok && (counting || !owned))
+            for (int jj = 0; jj < g; ++jj) {
+                const float4 a = l_rec[jj * 3], b = l_rec[jj * 3 + 1];
+                const float sc[3] = {b.y, b.z, b.w};
+                if (!inside_box(p0 - a.x, p1 - a.y, p2 - a.z, a.w, b.x, sc)) continue;       // :231-234
+                if (count_in) atomicAdd(&l_in[jj], 1);
+                if (!owned) {
+                    owned = true;
+                    own = __float_as_int(l_rec[jj * 3 + 2].x);
+                    if (count_owned) atomicAdd(&l_owned[jj], 1);
+                }
+                if (!counting) break;
+            }
+        if (counting) {
+            __syncthreads();
+            if (threadIdx.x < g) {
+                const int64_t slot = (int64_t)kc * max_boxes + j0 + threadIdx.x;
+                if (count_in && l_in[threadIdx.x]) atomicAdd(&count_in[slot], l_in[threadIdx.x]);
+                if (count_owned && l_owned[threadIdx.x]) atomicAdd(&count_owned[slot], l_owned[threadIdx.x]);
+            }
+        }
+    }
+    if (have) owner[kc * n + i] = own;
+}
+
+size_t inst_ws_bytes(int K, int max_boxes) {
+    return cv_align_up((size_t)K * max_boxes * INST_REC * sizeof(unsigned), 256);
+}
+
+}  // namespace
+
 extern "C" {
+
+size_t cv_decode_instances_workspace_bytes(int num_cats, int max_boxes) {
+    if (num_cats < 1 || num_cats > CV_MAX_CATEGORIES || max_boxes < 0 || (int64_t)num_cats * max_boxes >= (1ll << 31)) return 0;
+    return inst_ws_bytes(num_cats, max_boxes);
+}
+
+int cv_decode_instances_f32(const float* d_grid_rot, const float* d_grid_scale, const int dims[3], const float h_corner3[3],
+                            float res, const float* d_points, const float* d_prob, int64_t n, int num_cats,
+                            const int64_t* h_cells, const int32_t* h_label_of, const int* h_n_boxes, int max_boxes,
+                            float prob_thresh, int confident_only, int32_t* d_owner, int32_t* d_count_in,
+                            int32_t* d_count_owned, void* d_ws, size_t ws_bytes, void* stream) {
+    const int K = num_cats;
+    CV_REQUIRE(K >= 1 && K <= CV_MAX_CATEGORIES, CV_EINVAL, "num_cats out of range (%d, 1..%d)", K, CV_MAX_CATEGORIES);
+    CV_REQUIRE(d_grid_rot && d_grid_scale && dims && h_corner3 && d_points && d_owner && h_n_boxes, CV_EINVAL,
+               "null pointer argument");
+    CV_REQUIRE(d_prob || !confident_only, CV_EINVAL, "confident_only needs d_prob");
+    CV_REQUIRE(n >= 0 && n <= (int64_t)0x7fffffff * 256, CV_EINVAL, "n out of range (%lld)", (long long)n);
+    CV_REQUIRE(dims[0] > 0 && dims[1] > 0 && dims[2] > 0, CV_EINVAL, "bad grid dims");
+    const int64_t G = (int64_t)dims[0] * dims[1] * dims[2];
+    CV_REQUIRE(G < (1ll << 31), CV_EINVAL, "grid too large");
+    CV_REQUIRE(max_boxes >= 0 && (int64_t)K * max_boxes < (1ll << 31), CV_EINVAL, "max_boxes out of range (%d)", max_boxes);
+    int64_t total = 0;
+    for (int k = 0; k < K; ++k) {
+        CV_REQUIRE(h_n_boxes[k] >= 0 && h_n_boxes[k] <= max_boxes, CV_EINVAL, "n_boxes[%d] out of range (%d, 0..%d)", k,
+                   h_n_boxes[k], max_boxes);
+        total += h_n_boxes[k];
+    }
+    CV_REQUIRE(total == 0 || (h_cells && h_label_of), CV_EINVAL, "null pointer argument");
+    for (int k = 0; k < K; ++k)
+        for (int j = 0; j < h_n_boxes[k]; ++j) {
+            const int64_t cell = h_cells[(size_t)k * max_boxes + j];
+            CV_REQUIRE(cell >= 0 && cell < G, CV_EINVAL, "cell %lld of category %d, box %d outside the grid (%lld cells)",
+                       (long long)cell, k, j, (long long)G);
+        }
+    const size_t need = inst_ws_bytes(K, max_boxes);
+    CV_REQUIRE(ws_bytes >= need && (d_ws || total == 0), CV_EINVAL, "workspace too small (%zu < %zu)", d_ws ? ws_bytes : (size_t)0,
+               need);
+    if (n == 0) return CV_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned* recs = static_cast<unsigned*>(d_ws);
+    const Geo geo{dims[0], dims[1], dims[2], {h_corner3[0], h_corner3[1], h_corner3[2]}, res};
+    InstChunk ch;
+    InstCats cats;
+    int fill = 0;
+    for (int k = 0; k < CV_MAX_CATEGORIES; ++k) cats.n_boxes[k] = k < K ? h_n_boxes[k] : 0;
+    for (int k = 0; k < K; ++k)
+        for (int j = 0; j < h_n_boxes[k]; ++j) {
+            const size_t slot = (size_t)k * max_boxes + j;
+            ch.cell[fill] = (int)h_cells[slot];
+            ch.label[fill] = h_label_of[slot];
+            ch.slot[fill] = (int)slot;
+            if (++fill == INST_CHUNK) {
+                inst_boxes<<<1, INST_CHUNK, 0, st>>>(d_grid_rot, d_grid_scale, geo, G, max_boxes, ch, fill, recs, d_count_in,
+                                                     d_count_owned);
+                CV_LAUNCH_CHECK();
+                fill = 0;
+            }
+        }
+    if (fill) {
+        inst_boxes<<<1, INST_CHUNK, 0, st>>>(d_grid_rot, d_grid_scale, geo, G, max_boxes, ch, fill, recs, d_count_in, d_count_owned);
+        CV_LAUNCH_CHECK();
+    }
+    inst_assign<<<dim3((unsigned)((n + 255) / 256), (unsigned)K), 256, 0, st>>>(d_points, d_prob, n, recs, cats, max_boxes,
+                                                                                prob_thresh, confident_only, d_owner, d_count_in,
+                                                                                d_count_owned);
+    CV_LAUNCH_CHECK();
+    return CV_OK;
+}
 
 size_t cv_decode_workspace_bytes(const int dims[3], int64_t n, int max_iters) {
     if (!dims || max_iters <= 0) return 0;

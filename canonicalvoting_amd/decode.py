@@ -124,6 +124,70 @@ def decode_boxes_categories(grid_obj, grid_rot, grid_scale, scan_points, xyz_pre
                  p, mutate_grid, allow_truncation)
 
 
+SUPPORT = {"confident": 1, "inside": 0}      # instance_labels' ``support`` -> cv_decode_instances_f32's confident_only
+
+
+def instance_labels(grid_rot, grid_scale, corner, res, scan_points, prob, cells, label_of=None, support="confident",
+                    prob_thresh=0.3, counts=False):
+    """Which scan points each of a list of boxes owns (cv_decode_instances_f32; two launches, no host wait).
+
+    A box is the grid cell the decode examined as a candidate (``raw["cand_idx"]``); its geometry is formed from
+    ``grid_rot`` / ``grid_scale`` / ``corner`` / ``res`` exactly as the decode formed it, so membership is the decode's
+    own in-box test (eval_joint.py:231-234), with ``support="confident"`` also ``prob > prob_thresh`` (:245);
+    ``support="inside"`` takes every point inside the box (``prob`` may then be None).  A point's owner is the FIRST box of
+    ``cells`` that has it as a member: order the list by priority.
+
+    Single form: grids [X,Y,Z,2] / [X,Y,Z,3], prob [N], ``cells`` a sequence of B cells -> owner [N] int32.
+    Category form: grids [K,X,Y,Z,2|3], prob [K,N], ``cells`` a list of K sequences -> owner [K,N].  scan_points [N,3] is
+    shared.  ``label_of`` (same shape as ``cells``; default: the box's position in its list) is what ``owner`` holds for an
+    owned point, -1 for a point no box has.  ``counts=True`` also returns (count_in, count_owned), int32 [B] or [K,max B]:
+    members of each box, owned or not, and points it owns."""
+    L = _lib.lib()
+    if support not in SUPPORT:
+        raise ValueError("instance_labels: support must be 'confident' or 'inside' (got %r)" % (support,))
+    confident = SUPPORT[support]
+    single = grid_rot.dim() == 4
+    if prob is None and confident:
+        raise ValueError("instance_labels: support='confident' needs prob")
+    for t, name in ((grid_rot, "grid_rot"), (grid_scale, "grid_scale"), (scan_points, "scan_points"), (prob, "prob")):
+        if t is not None and (not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32):
+            raise RuntimeError("%s must be a contiguous float32 CUDA tensor" % name)
+    dev = scan_points.device
+    n = scan_points.shape[0]
+    cells = [cells] if single else list(cells)
+    label_of = None if label_of is None else ([label_of] if single else list(label_of))
+    K = len(cells)
+    shape = tuple(grid_rot.shape[:-1] if single else grid_rot.shape[1:-1])
+    if (len(shape) != 3 or tuple(grid_rot.shape) != (() if single else (K,)) + shape + (2,)
+            or tuple(grid_scale.shape) != (() if single else (K,)) + shape + (3,)
+            or (prob is not None and tuple(prob.shape) != ((n,) if single else (K, n)))):
+        raise RuntimeError("instance_labels: expected grid_rot [K,X,Y,Z,2], grid_scale [K,X,Y,Z,3] and prob [K,N] for the K "
+                           "cell lists (without K for one list)")
+    n_boxes = np.array([len(c) for c in cells], np.int32)
+    B = int(n_boxes.max()) if K else 0
+    h_cells = np.zeros((K, max(B, 1)), np.int64)
+    h_label = np.zeros((K, max(B, 1)), np.int32)
+    for k in range(K):
+        h_cells[k, :n_boxes[k]] = np.asarray(cells[k], np.int64).reshape(-1)
+        h_label[k, :n_boxes[k]] = np.arange(n_boxes[k]) if label_of is None else np.asarray(label_of[k], np.int32).reshape(-1)
+    M = h_cells.shape[1]
+    owner = torch.empty((K, n), dtype=torch.int32, device=dev)
+    cin = torch.zeros((K, M), dtype=torch.int32, device=dev) if counts else None
+    cown = torch.zeros((K, M), dtype=torch.int32, device=dev) if counts else None
+    ws = _lib.scratch(dev, "instances", L.cv_decode_instances_workspace_bytes(K, M))
+    with torch.cuda.device(dev):
+        rc = L.cv_decode_instances_f32(ptr(grid_rot), ptr(grid_scale), (ctypes.c_int * 3)(*shape),
+                                       (ctypes.c_float * 3)(*[float(v) for v in corner]), ctypes.c_float(float(res)),
+                                       ptr(scan_points), ptr(prob), n, K, h_cells.ctypes.data_as(_lib.c_i64_p),
+                                       h_label.ctypes.data_as(_lib.c_i32_p), n_boxes.ctypes.data_as(_lib.c_int_p), M,
+                                       ctypes.c_float(float(prob_thresh)), confident, ptr(owner), ptr(cin), ptr(cown), ptr(ws),
+                                       ws.numel(), stream(dev))
+    _lib.check(rc, "cv_decode_instances_f32")
+    if single:
+        return (owner[0], cin[0, :B], cown[0, :B]) if counts else owner[0]
+    return (owner, cin[:, :B], cown[:, :B]) if counts else owner
+
+
 def get_iou_obb(bbox1, bbox2):
     """utils/calc_map.py:6-21 on two [8,3] corner arrays."""
     a = np.ascontiguousarray(bbox1, np.float32)

@@ -384,6 +384,7 @@ def detect_scene_c(model, hv, coords4, feats, res, nclasses=9, log_scale=True, s
     ``policy``: ScenePolicy of THIS call (None: the thread's / process-wide values).
     Returns (detections, raw decode dict, network output [N, C])."""
     dev = feats.device
+    _keep_begin(keep, res)
     n = coords4.shape[0]
     if scan_points is None:
         scan_points = (coords4[:, 1:].to(dev) * res).float().contiguous()
@@ -399,6 +400,8 @@ def detect_scene_c(model, hv, coords4, feats, res, nclasses=9, log_scale=True, s
         px, ps, pp, pc = predictions
         pc = pc.to(torch.int32).contiguous()
         d.d_xyz_in, d.d_scale_in, d.d_prob_in, d.d_class_in = ptr(px), ptr(ps), ptr(pp), ptr(pc)
+        if keep is not None:
+            keep["decode_prob"] = pp
     _fill_joint_desc(d, host, program, y, nclasses, decode_kw, adaptive_split, events, keep)
     ws = _call_growing(_lib.lib().cv_detect_scene_f32, "cv_detect_scene_f32", d, r, dev, "scene_call", host.ws_hint)
     out = _finish_joint(host, r, keep, y, n, dev, ws)
@@ -451,6 +454,7 @@ def detect_points_c(model, hv, points, feats, res, predictions=None, return_inve
     filled.  A cloud with rejected points raises RuntimeError with their count.
     Returns (detections, raw, y [N, C'], index [N][, inverse [M]])."""
     dev = points.device
+    _keep_begin(keep, res)
     pieces = model.eval_pieces()
     program = model._program(dev, pieces)
     d, r = _lib.PointsDesc(), _lib.PointsResult()
@@ -467,7 +471,8 @@ def detect_points_c(model, hv, points, feats, res, predictions=None, return_inve
     view = lambda p, shape, dt=torch.float32: _device_view(p, shape, dt, dev, ws)
     gathered = lambda: dict(scan_points=view(r.d_points, (n, 3)), feats=view(r.d_feats, (n, d.front.in_channels)),
                             host_us=tuple(r.scene.host_us), host_us_front=float(r.host_us_front),
-                            front_ws_bytes=int(r.front_ws_bytes))
+                            front_ws_bytes=int(r.front_ws_bytes),
+                            **({} if predictions is None else dict(decode_prob=view(r.d_prob_in, (n,)))))
     out = _finish_joint(host, r.scene, keep, y, n, dev, ws, gathered)
     if out is not None:
         return out + tail
@@ -629,6 +634,7 @@ def detect_scene_separate_c(models, hv, coords4, feats, res, predictions=None, p
     dev = feats.device
     n = coords4.shape[0]
     categories, mods = list(models.keys()), list(models.values())
+    _keep_begin(keep, res, categories)
     if scan_points is None:
         scan_points = (coords4[:, 1:].to(dev) * res).float().contiguous()
     K, pieces, G, progs, table = _model_set("detect_scene_separate_c", mods, dev, models_per_pass)
@@ -642,6 +648,8 @@ def detect_scene_separate_c(models, hv, coords4, feats, res, predictions=None, p
     if predictions is not None:
         px, ps, pp = [a.contiguous() for a in predictions]
         d.d_xyz_in, d.d_scale_in, d.d_prob_in = ptr(px), ptr(ps), ptr(pp)
+        if keep is not None:
+            keep["decode_prob"] = pp
     alive = _fill_separate_desc(d, host, progs, table, G, ys, decode_kw, overlap_threshold, events)
     ws = _call_growing(_lib.lib().cv_detect_scene_separate_f32, "cv_detect_scene_separate_f32", d, r, dev,
                        "scene_call_separate", host.ws_hint)
@@ -663,10 +671,12 @@ def detect_points_separate_c(models, hv, points, feats, res, predictions=None, m
     then the K models' scene.  ``predictions`` = (xyz [K, M, 3], scale [K, M, 3], prob [K, M]) aligned with the raw points; the
     other arguments as detect_points_c / detect_scene_separate_c.  The same bits as ME.utils.quantize_device + torch gathers
     + detect_scene_separate_c.  Returns (detections [(category, box[8,3], score)], index [N][, inverse [M]]); ``keep``
-    receives what detect_scene_separate_c's does (``y``: the K outputs' first N rows) plus ``coords4``."""
+    receives what detect_scene_separate_c's does (``y``: the K outputs' first N rows) plus ``coords4`` and ``world_points``
+    [N, 3], the scan points the scene ran on."""
     _separate_defaults(decode_kw)
     dev = points.device
     categories, mods = list(models.keys()), list(models.values())
+    _keep_begin(keep, res, categories)
     K, pieces, G, progs, table = _model_set("detect_points_separate_c", mods, dev, models_per_pass)
     d, r = _lib.PointsSeparateDesc(), _lib.PointsSeparateResult()
     coords4, index, inverse, alive = _points_front(d.front, points, feats, res, recentre_from, predictions, return_inverse, False)
@@ -681,10 +691,12 @@ def detect_points_separate_c(models, hv, points, feats, res, predictions=None, m
     n = int(r.n)
     coords4, index, ys = coords4[:n], index[:n], [y[:n] for y in ys]
     tail = (index, inverse) if return_inverse else (index,)
-    dets = _finish_separate(host, r.scene, keep, categories, ys, n, dev, ws, coords4=coords4)
+    view = lambda p, shape: _device_view(p, shape, torch.float32, dev, ws)
+    fed = {} if predictions is None else dict(decode_prob=view(r.d_prob_in, (K, n)))
+    dets = _finish_separate(host, r.scene, keep, categories, ys, n, dev, ws, coords4=coords4,
+                            world_points=view(r.d_points, (n, 3)), **fed)
     if dets is not None:
         return (dets,) + tail
-    view = lambda p, shape: _device_view(p, shape, torch.float32, dev, ws)
     pred = None
     if predictions is not None:
         pred = (view(r.d_xyz_in, (K, n, 3)), view(r.d_scale_in, (K, n, 3)), view(r.d_prob_in, (K, n)))
@@ -692,3 +704,119 @@ def detect_points_separate_c(models, hv, points, feats, res, predictions=None, m
                                     policy=policy, keep=keep, events=events, log_scale=log_scale,
                                     overlap_threshold=overlap_threshold, max_candidates=M, models_per_pass=models_per_pass,
                                     **decode_kw),) + tail
+
+
+# ---- instance labels --------------------------------------------------------------------------------------------------------------
+
+def _keep_begin(keep, res, categories=None):
+    """What scene_instances needs beyond the call's results: the voxel size and, in separate mode, the category order.  The
+    device views of an earlier call on the same dict are dropped: a scene that is redone call by call hands out none."""
+    if keep is None:
+        return
+    for stale in ("grids", "net_pred", "decode_prob", "world_points"):
+        keep.pop(stale, None)
+    keep["res"] = float(res)
+    if categories is not None:
+        keep["categories"] = list(categories)
+
+
+def _match_accepted(raw, box, used):
+    """position among ``raw``'s accepted boxes of the first unused one whose corner array equals ``box`` exactly"""
+    for i in range(len(raw["boxes"])):
+        if i not in used and np.array_equal(raw["boxes"][i], box):
+            used.add(i)
+            return i
+    raise ValueError("scene_instances: a detection's box is not among the accepted boxes of this scene's decode")
+
+
+def scene_instances(keep, detections, scan_points=None, support="confident", prob_thresh=0.3, counts=False, inverse=None):
+    """Which scan points each detection of a scene owns (decode.instance_labels on what ``keep`` holds).
+
+    ``keep`` is the dict a one-call entry point filled (detect_scene_c, detect_scene_separate_c, detect_points_c,
+    detect_points_separate_c), ``detections`` the list that call returned - or any list of its (class or category, box,
+    score) entries.  ``scan_points`` [N,3]: the scene's world points; None takes the ones a raw-cloud call kept
+    (``keep["scan_points"]``, ``keep["world_points"]`` from detect_points_separate_c).  Each detection is matched to the
+    accepted box of the decode (``cand_idx[verdict == 0]``, acceptance order) whose corner array equals its own exactly -
+    in separate mode among its category's - the first unused match taken; the box is then rebuilt from that grid cell as
+    the decode built it, so membership is the decode's own in-box test (eval_joint.py:231-234) and, with
+    ``support="confident"``, ``prob > prob_thresh`` (:245) on the prob the decode was fed (the call's ``predictions`` if it
+    had any, else ``net_pred``); ``support="inside"`` takes every point inside.  Where boxes overlap, the point goes to the
+    detection with the higher score, ties to the earlier one in ``detections``.  Labels are positions in ``detections``,
+    -1 = no owner.
+
+    Returns a dict: ``owner`` int32 [N] (joint mode) or [K,N] (separate mode, row k = category k's detections only, plus
+    ``merged`` [N]: over all categories the best-scoring detection that has the point); with ``counts`` also ``count_in``
+    / ``count_owned`` int32 [len(detections)] - points inside each detection's box under ``support``, owned or not, and
+    points it owns within its category; with ``inverse`` [M] (``return_inverse`` of a raw-cloud call) also ``raw_owner``
+    [M], the labels of the raw points: ``owner[inverse]`` (``merged[inverse]`` in separate mode).
+
+    Everything is enqueued on the current stream, without a host wait.  ``keep``'s grids and predictions are VIEWS of the
+    stream's scene scratch, which the next scene call on that stream overwrites: enqueue this call before it.  A scene
+    that was redone call by call (a convolution input beyond the fp16 range, a decode walk beyond ``max_candidates``) has
+    no grids in ``keep``: RuntimeError."""
+    if keep is None or "grids" not in keep or "net_pred" not in keep or "raw" not in keep:
+        raise RuntimeError("scene_instances: keep holds no grids - pass keep= to a one-call scene entry point; a scene that "
+                           "was redone call by call (range fallback, truncated decode walk) hands none out")
+    if "res" not in keep:
+        raise RuntimeError("scene_instances: keep holds no res (it was not filled by a one-call scene entry point)")
+    if scan_points is None:
+        scan_points = keep.get("scan_points", keep.get("world_points"))
+        if scan_points is None:
+            raise RuntimeError("scene_instances: scan_points is needed (keep holds none: only the raw-cloud calls keep them)")
+    separate = isinstance(keep["raw"], list)
+    dets = list(detections)
+    D = len(dets)
+    # priority: score descending, ties to the earlier detection
+    order = sorted(range(D), key=lambda p: (-float(dets[p][2]), p))
+    rank = {p: i for i, p in enumerate(order)}
+    raws = keep["raw"] if separate else [keep["raw"]]
+    K = len(raws)
+    accepted = [np.asarray(r["cand_idx"])[np.asarray(r["verdict"]) == 0] for r in raws]
+    used = [set() for _ in range(K)]
+    cat_of = [keep["categories"].index(d[0]) if separate else 0 for d in dets]
+    cell_of = [int(accepted[cat_of[p]][_match_accepted(raws[cat_of[p]], np.asarray(dets[p][1], np.float32), used[cat_of[p]])])
+               for p in range(D)]
+    lists = [[p for p in order if cat_of[p] == k] for k in range(K)]
+    cells = [[cell_of[p] for p in lst] for lst in lists]
+    _, g_rot, g_scale = keep["grids"]
+    prob = keep.get("decode_prob", keep["net_pred"][2])          # what the decode was fed: ``predictions=`` or the heads' own
+    scan_points = scan_points.contiguous()
+    args = (keep["corner"], keep["res"], scan_points)
+    kw = dict(support=support, prob_thresh=prob_thresh, counts=counts)
+    if separate:
+        res_ = decode.instance_labels(g_rot, g_scale, *args, prob, cells, lists, **kw)
+    else:
+        res_ = decode.instance_labels(g_rot, g_scale, *args, prob, cells[0], lists[0], **kw)
+    owner = res_[0] if counts else res_
+    out = dict(owner=owner)
+    dev = owner.device
+    labels = owner
+    if separate:
+        # the best-ranked of a point's K owners (rank D: none)
+        rank_of = torch.tensor([rank[p] for p in range(D)] + [D], dtype=torch.int64, device=dev)      # [-1] -> D
+        best = rank_of[owner.long()].argmin(0, keepdim=True)
+        out["merged"] = labels = owner.gather(0, best)[0]
+    if counts:
+        # list positions -> detection positions
+        pos = torch.tensor([(cat_of[p], lists[cat_of[p]].index(p)) for p in range(D)], dtype=torch.int64, device=dev).reshape(D, 2)
+        for name, c in (("count_in", res_[1]), ("count_owned", res_[2])):
+            c = c if separate else c[None]
+            out[name] = c[pos[:, 0], pos[:, 1]] if D else c.new_zeros(0)
+    if inverse is not None:
+        out["raw_owner"] = labels[inverse.long()]
+    return out
+
+
+def instances_report(detections, out):
+    """One line per detection from scene_instances(..., counts=True): the scan points it owns and the ones inside its box
+    (under the call's support), with ``inverse`` also the raw points it owns.  One host copy."""
+    D = len(detections)
+    cols = [out["count_owned"].cpu().numpy(), out["count_in"].cpu().numpy()]
+    if "raw_owner" in out:
+        r = out["raw_owner"]
+        cols.append(torch.bincount(r[r >= 0].long(), minlength=D)[:D].cpu().numpy() if D else np.zeros(0, np.int64))
+    lines = []
+    for p, (c, _, score) in enumerate(detections):
+        tail = "  raw points owned %7d" % cols[2][p] if len(cols) == 3 else ""
+        lines.append("  det %3d  class %-10s score %.4f  owned %6d  members %6d%s" % (p, c, score, cols[0][p], cols[1][p], tail))
+    return lines

@@ -213,6 +213,30 @@ int cv_decode_cat_f32(float* d_grid_obj, const float* d_grid_rot, const float* d
                       size_t ws_bytes, int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes, float* h_boxes,
                       float* h_scores, int32_t* h_classes, int* h_truncated, void* stream);
 
+/* Instance labels: which scan points each of a list of boxes owns (eval_joint.py:231-245: bbox_mask_world and mask, which
+ * the decode reduces to statistics per candidate and drops).  A box is named by the flat grid cell the decode examined
+ * as a candidate; its geometry is formed from the grids exactly as the decode formed it (rotation by double-rounded
+ * atan2 / cos / sin of the rot cell, scale from the scale cell, centre h_corner3[d] + res * cell_d in fp32), so membership
+ * agrees with the decode's in-box test on every point, the ones on a face included.  A point is a member of a box when
+ * it lies strictly inside it and - with confident_only - d_prob[i] > prob_thresh (strict: a NaN prob is not confident).
+ * Its owner is the FIRST box of the category's list that has it as a member: the list order is the priority.
+ * Grids [K][X][Y][Z][2|3], d_points [n][3] shared by the categories, d_prob [K][n] (may be NULL when confident_only == 0),
+ * h_cells / h_label_of [K][max_boxes] host arrays of which the first h_n_boxes[k] entries of row k are read (they may be
+ * reused as soon as the call returns).  d_owner [K][n] receives h_label_of of the owning box, -1 where no box has the
+ * point (h_n_boxes[k] == 0: -1 everywhere).  d_count_in / d_count_owned [K][max_boxes] (each may be NULL): members of box
+ * j (owned or not) and points owned by it, overwritten for j < h_n_boxes[k], the rest untouched; integer sums, so the
+ * result does not depend on the order of arrival.  With both NULL the walk of a point stops at its first hit.
+ * d_ws: cv_decode_instances_workspace_bytes(num_cats, max_boxes) bytes.  Asynchronous on `stream`, no host wait; n == 0 is
+ * a no-op success.  CV_EINVAL before anything is launched: a NULL grid, points or owner pointer, NULL d_prob with
+ * confident_only, n < 0, num_cats outside 1..CV_MAX_CATEGORIES, h_n_boxes[k] outside 0..max_boxes, a cell outside
+ * [0, X*Y*Z), a workspace that is too small. */
+size_t cv_decode_instances_workspace_bytes(int num_cats, int max_boxes);
+int cv_decode_instances_f32(const float* d_grid_rot, const float* d_grid_scale, const int dims[3],
+                            const float h_corner3[3], float res, const float* d_points, const float* d_prob, int64_t n,
+                            int num_cats, const int64_t* h_cells, const int32_t* h_label_of, const int* h_n_boxes, int max_boxes,
+                            float prob_thresh, int confident_only, int32_t* d_owner, int32_t* d_count_in, int32_t* d_count_owned,
+                            void* d_ws, size_t ws_bytes, void* stream);
+
 /* utils/calc_map.py:6-21 on two [8][3] corner sets (host). */
 double cv_iou_obb(const float* h_box1, const float* h_box2);
 /* eval_joint.py:75-89 (host): greedy NMS, returns the pick count, indices in h_pick. */

@@ -4,13 +4,15 @@ models on one scan -> ONE scene call (plan once, nine networks, nine heads, one 
 axis, NMS per category) per scene, then mAP @0.25 / @0.5.  argparse instead of hydra (absent here).
 
     python scripts/eval_separate.py [--scenes 4] [--points 80000] [--weights-dir DIR] [--teacher] [--config config.yaml]
-                                    [--raw-points [M]]
+                                    [--raw-points [M]] [--instances]
 
 --weights-dir holds one state dict per category, DIR/<category>.pth (reference checkpoints are loaded through
 minkunet.load_reference_checkpoint).  --teacher feeds the vote/decode stage with per-category predictions synthesised from
 the labels (there is no trained checkpoint offline); the networks still run.
 --raw-points (synthetic scenes only): every scene is a RAW cloud of M surface samples (default 300000) that goes through
 pipeline.detect_points_separate_c: voxelised on the device, gathered and detected in one C call.
+--instances (synthetic scenes only): after each scene, the scan points every detection owns within its category and the
+ones inside its box (pipeline.scene_instances; with --raw-points also the raw points it owns over all categories).
 """
 import argparse
 import os
@@ -38,7 +40,13 @@ def teacher_predictions(scene, categories, device):
     return t(np.stack([xyz] * len(categories))), t(np.stack([scale] * len(categories))), t(P)
 
 
-def evaluate(models, dataset, res=0.03, teacher=False, device="cuda", models_per_pass=None):
+def report_instances(id_scan, keep, dets, scan_points=None, inverse=None):
+    print("%s: %d detections" % (id_scan, len(dets)))
+    out = pipeline.scene_instances(keep, dets, scan_points, counts=True, inverse=inverse)
+    print("\n".join(pipeline.instances_report(dets, out)))
+
+
+def evaluate(models, dataset, res=0.03, teacher=False, device="cuda", models_per_pass=None, instances=False):
     hv = HoughVoting(res)
     pred_map_cls, gt_map_cls = {}, {}
     loader = torch.utils.data.DataLoader(dataset, collate_fn=collate_fn, batch_size=1, shuffle=False)
@@ -48,13 +56,18 @@ def evaluate(models, dataset, res=0.03, teacher=False, device="cuda", models_per
         feats[:, -3:] = feats[:, -3:] * 2.0 - 1.0                             # eval_separate.py: colour columns only
         coords = coords.to(device)
         pred = teacher_predictions(dataset.scene(index), list(models), device) if teacher else None
-        pred_map_cls[id_scan] = pipeline.detect_scene_separate_c(models, hv, coords, feats, res, predictions=pred,
-                                                                 models_per_pass=models_per_pass)
+        keep = {} if instances else None
+        pts = (coords[:, 1:] * res).float().contiguous()
+        pred_map_cls[id_scan] = pipeline.detect_scene_separate_c(models, hv, coords, feats, res, predictions=pred, keep=keep,
+                                                                 scan_points=pts, models_per_pass=models_per_pass)
+        if instances:
+            report_instances(id_scan, keep, pred_map_cls[id_scan], pts)
         gt_map_cls[id_scan] = [(c, calc_map.gt_box(*p)) for c, p in dataset.gt(index)]
     return {thr: calc_map.compute_map(pred_map_cls, gt_map_cls, thr) for thr in (0.25, 0.5)}
 
 
-def evaluate_raw(models, n_scenes, n_samples, seed0=100, res=0.03, teacher=False, device="cuda", models_per_pass=None):
+def evaluate_raw(models, n_scenes, n_samples, seed0=100, res=0.03, teacher=False, device="cuda", models_per_pass=None,
+                 instances=False):
     """the synthetic evaluation from raw clouds: one C call per scene (pipeline.detect_points_separate_c)"""
     hv = HoughVoting(res)
     pred_map_cls, gt_map_cls = {}, {}
@@ -63,8 +76,12 @@ def evaluate_raw(models, n_scenes, n_samples, seed0=100, res=0.03, teacher=False
         raw = make_raw_scene(seed0 + index, n_samples)
         id_scan = "synth%04d" % (seed0 + index)
         pred = teacher_predictions(raw, list(models), device) if teacher else None
-        pred_map_cls[id_scan] = pipeline.detect_points_separate_c(models, hv, t(raw.points), t(raw.feats), res, predictions=pred,
-                                                                  recentre_from=0, models_per_pass=models_per_pass)[0]
+        keep = {} if instances else None
+        out = pipeline.detect_points_separate_c(models, hv, t(raw.points), t(raw.feats), res, predictions=pred, keep=keep,
+                                                recentre_from=0, models_per_pass=models_per_pass, return_inverse=instances)
+        pred_map_cls[id_scan] = out[0]
+        if instances:
+            report_instances(id_scan, keep, out[0], inverse=out[-1])
         lines = ["%f %f %f %f %f %f %f %d" % tuple(list(b[:7]) + [int(b[7])]) for b in raw.boxes]
         gt_map_cls[id_scan] = [(c, calc_map.gt_box(*p)) for c, p in parse_gt_lines(lines)]
     return {thr: calc_map.compute_map(pred_map_cls, gt_map_cls, thr) for thr in (0.25, 0.5)}
@@ -84,14 +101,16 @@ def build_parser():
     ap.add_argument("--raw-points", type=int, nargs="?", const=300000, default=0, metavar="M",
                     help="synthetic scenes as raw clouds of M samples: voxelise, gather and detect in one C call "
                          "(pipeline.detect_points_separate_c)")
+    ap.add_argument("--instances", action="store_true",
+                    help="print the scan points each detection owns and has inside its box (pipeline.scene_instances)")
     return ap
 
 
 def main():
     ap = build_parser()
     a = ap.parse_args()
-    if a.raw_points and a.config:
-        ap.error("--raw-points runs on the synthetic scenes only")
+    if (a.raw_points or a.instances) and a.config:
+        ap.error("--raw-points and --instances run on the synthetic scenes only")
     cfg = load_config(a.config, category="all") if a.config else None
     models = {}
     for c in a.categories:
@@ -103,9 +122,11 @@ def main():
         res = evaluate(models, ScanNetXYZProbMultiDataset(cfg, training=False, augment=False), res=cfg.scannet_res,
                        models_per_pass=a.models_per_pass)
     elif a.raw_points:
-        res = evaluate_raw(models, a.scenes, a.raw_points, seed0=100, teacher=a.teacher, models_per_pass=a.models_per_pass)
+        res = evaluate_raw(models, a.scenes, a.raw_points, seed0=100, teacher=a.teacher, models_per_pass=a.models_per_pass,
+                           instances=a.instances)
     else:
-        res = evaluate(models, SyntheticScanDataset(a.scenes, a.points, seed0=100), teacher=a.teacher, models_per_pass=a.models_per_pass)
+        res = evaluate(models, SyntheticScanDataset(a.scenes, a.points, seed0=100), teacher=a.teacher, models_per_pass=a.models_per_pass,
+                       instances=a.instances)
     for thr, r in res.items():
         print("IoU %.2f: mAP %.4f  AR %.4f" % (thr, r["mAP"], r["AR"]))
 
