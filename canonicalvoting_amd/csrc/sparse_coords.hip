@@ -1048,6 +1048,8 @@ int quantize_run(const T* d_points, long long m, long long ld, T q, int floor_on
                  int32_t* d_coords4, int32_t* d_index, int32_t* d_inverse, int32_t* d_counts, int32_t* h_counts, void* d_ws,
                  size_t ws_bytes, void* stream) {
     CV_REQUIRE(d_points && d_coords4 && d_index && d_counts && d_ws, CV_EINVAL, "null pointer argument");
+    CV_REQUIRE((reinterpret_cast<uintptr_t>(d_coords4) & 15) == 0, CV_EINVAL,
+               "d_coords4 must be 16-byte aligned (quantize_emit stores a row as one int4)");
     CV_REQUIRE(m > 0 && m <= (1ll << 29), CV_EINVAL, "bad point count %lld", m);      // (slots and -2 - slot stay in 32 bits)
     CV_REQUIRE(ld >= 3, CV_EINVAL, "bad row stride %lld", ld);
     CV_REQUIRE(floor_only || (q > (T)0 && q <= std::numeric_limits<T>::max()), CV_EINVAL,

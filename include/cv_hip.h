@@ -277,7 +277,9 @@ int cv_sp_build_levels(int32_t* const* d_coords, unsigned long long* const* d_ke
  *   d_coords4 [m][4] int32 (batch, x, y, z), the first N rows written      d_index [m] int32, the first N written:
  *             row of the first point of each voxel, ascending              d_inverse [m] int32 or NULL: output row of every
  *             point's voxel (-1 for a rejected point)
- *   d_counts  int32[2] device: [0] = N, [1] = rejected points.  A point is rejected - counted, kept out of the table and
+ *             d_coords4 must be 16-byte aligned (a row is stored as one 16-byte word), else CV_EINVAL before any launch;
+ *             rows behind N, and d_index entries behind N, are left as they were.
+ *   d_counts int32[2] device: [0] = N, [1] = rejected points.  A point is rejected - counted, kept out of the table and
  *             of every index computation - when a component is not finite or its voxel lies outside the key window of the
  *             coordinate manager (spatial coordinates in [-32704, 32703]); callers treat [1] != 0 as an error.
  *   h_counts  receives the same two ints (one synchronisation of `stream`), or NULL: no host wait.
@@ -1079,7 +1081,8 @@ typedef struct cv_points_front {
     /* optional raw-point-aligned predictions fed to vote + decode (NULL = the network's; all or none): [m][3], [m][3], [m], [m];
      * separate mode: [K][m][3], [K][m][3], [K][m] and d_raw_class NULL */
     const float* d_raw_xyz; const float* d_raw_scale; const float* d_raw_prob; const int32_t* d_raw_class;
-    /* the voxeliser's outputs, caller's buffers: [m][4], [m], [m] (d_inverse may be NULL); the first result.n rows of d_coords4 / d_index */
+    /* the voxeliser's outputs, caller's buffers: [m][4] (16-byte aligned, as cv_sp_quantize_* asks), [m], [m] (d_inverse may be
+     * NULL); the first result.n rows of d_coords4 / d_index */
     int32_t* d_coords4; int32_t* d_index; int32_t* d_inverse;
 } cv_points_front;
 typedef struct cv_points_desc { cv_points_front front; cv_scene_desc scene; } cv_points_desc;

@@ -52,6 +52,8 @@ def test_quantize_call_refuses_bad_arguments_before_touching_the_gpu(built_lib, 
     real = float
     for null in ("points", "coords4", "index", "counts", "ws"):
         assert call(fn, real, **{null: None}) == -22 and b"null pointer" in L.cv_last_error()
+    for off in (4, 8, 12, 1):                     # coords4 rows are stored as 16-byte words
+        assert call(fn, real, coords4=4096 + off) == -22 and b"16-byte aligned" in L.cv_last_error()
     for m in (0, -5):
         assert call(fn, real, m=m) == -22 and b"point count" in L.cv_last_error()
     for q in (0.0, -0.03, float("nan"), float("inf")):
