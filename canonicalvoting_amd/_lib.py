@@ -146,6 +146,32 @@ class SceneResult(ctypes.Structure):
                 ("d_prob", vp), ("d_class", vp), ("host_us", ctypes.c_float * 4)]
 
 
+MAX_SCENES = 16          # CV_MAX_SCENES
+
+
+class DecodeSceneJob(ctypes.Structure):
+    """struct cv_decode_scene_job (include/cv_hip.h)"""
+    _fields_ = [("d_grid_obj", vp), ("d_grid_rot", vp), ("d_grid_scale", vp), ("dims", ctypes.c_int * 3),
+                ("corner", ctypes.c_float * 3), ("row0", ctypes.c_int64), ("n", ctypes.c_int64)]
+
+
+class ScenesDesc(ctypes.Structure):
+    """struct cv_scenes_desc (include/cv_hip.h)"""
+    _fields_ = [("scene", SceneDesc), ("num_scenes", ctypes.c_int)]
+
+
+class ScenesResult(ctypes.Structure):
+    """struct cv_scenes_result (include/cv_hip.h)"""
+    _fields_ = [("n_cand", ctypes.c_int * MAX_SCENES), ("n_boxes", ctypes.c_int * MAX_SCENES), ("n_det", ctypes.c_int * MAX_SCENES),
+                ("truncated", ctypes.c_int * MAX_SCENES), ("dims", ctypes.c_int * 3 * MAX_SCENES),
+                ("corner", ctypes.c_float * 3 * MAX_SCENES), ("row0", ctypes.c_longlong * MAX_SCENES),
+                ("rows", ctypes.c_longlong * MAX_SCENES), ("d_grid_obj", vp * MAX_SCENES), ("d_grid_rot", vp * MAX_SCENES),
+                ("d_grid_scale", vp * MAX_SCENES), ("range_flag", ctypes.c_int), ("duplicates", ctypes.c_int),
+                ("out_of_window", ctypes.c_int), ("scenes_in_flight", ctypes.c_int), ("level_rows", ctypes.c_longlong * 5),
+                ("needed_ws_bytes", ctypes.c_size_t), ("needed_grid_floats", ctypes.c_size_t),
+                ("d_xyz", vp), ("d_scale", vp), ("d_prob", vp), ("d_class", vp), ("host_us", ctypes.c_float * 4)]
+
+
 GATHER_MAX_JOBS = 8      # CV_GATHER_MAX_JOBS
 
 
@@ -299,6 +325,14 @@ SIGNATURES = {
     "cv_decode_cat_f32": (ctypes.c_int, [vp, vp, vp, c_int_p, c_float_p, ctypes.c_float, vp, vp, vp, vp, ctypes.c_int64,
                                          ctypes.c_int, ctypes.POINTER(DecodeParams), ctypes.c_int, vp, ctypes.c_size_t, c_int_p,
                                          c_i64_p, c_i32_p, c_int_p, c_float_p, c_float_p, c_i32_p, c_int_p, vp]),
+    "cv_decode_scenes_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(DecodeSceneJob), ctypes.c_int, ctypes.c_int]),
+    "cv_decode_scenes_f32": (ctypes.c_int, [ctypes.POINTER(DecodeSceneJob), ctypes.c_int, ctypes.c_float, vp, vp, vp, vp,
+                                            ctypes.POINTER(DecodeParams), ctypes.c_int, vp, ctypes.c_size_t, c_int_p, c_i64_p,
+                                            c_i32_p, c_int_p, c_float_p, c_float_p, c_i32_p, c_int_p, vp]),
+    "cv_sizeof_decode_scene_job": (ctypes.c_size_t, []),
+    "cv_detect_scenes_f32": (ctypes.c_int, [ctypes.POINTER(ScenesDesc), ctypes.POINTER(ScenesResult), vp]),
+    "cv_sizeof_scenes_desc": (ctypes.c_size_t, []),
+    "cv_sizeof_scenes_result": (ctypes.c_size_t, []),
     "cv_decode_instances_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "cv_decode_instances_f32": (ctypes.c_int, [vp, vp, c_int_p, c_float_p, ctypes.c_float, vp, vp, ctypes.c_int64, ctypes.c_int,
                                                c_i64_p, c_i32_p, c_int_p, ctypes.c_int, ctypes.c_float, ctypes.c_int, vp, vp, vp,

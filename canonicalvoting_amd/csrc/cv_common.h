@@ -103,6 +103,16 @@ struct DecodeCall {
 };
 // need_class: d_class must not be NULL (the joint model's class vote; the separate models pass none: class 0)
 int cv_decode_run(const DecodeCall& c, int num_cats, bool need_class);
+// The scene axis: the jobs carry grids, dims, corner and row range (c's own are not read); c.d_points / d_xyz / d_prob / d_class
+// are the shared arrays, c.d_ws the B carves in job order.  Scene b's host outputs at b, b * max_iters, b * max_iters * 24.
+int cv_decode_scenes_run(const DecodeCall& c, const cv_decode_scene_job* jobs, int num_scenes);
+// Row ranges and bounds of the B scenes of a batched coordinate set, ONE launch and one copy into pinned memory, no host wait.
+// h_out (PINNED, 16 words per scene, valid once the stream's work up to here is done): [0] first row, [1] end row, [2..7] fp32
+// min xyz / max xyz of d_points over those rows (the values cv_hv_minmax_async_ex lands for the scene alone), [8] != 0 when a
+// row of the range carries another batch index or the ranges do not tile [0, n).  d_ws: cv_hv_minmax_workspace_bytes().
+// d_zero_word / d_fill7f: as cv_hv_minmax_async_ex.
+int cv_hv_scene_bounds_async_ex(const int32_t* d_coords4, const float* d_points, int64_t n, int num_scenes, int32_t* h_out,
+                                void* d_ws, size_t ws_bytes, int32_t* d_zero_word, int32_t* d_fill7f, void* stream);   // hv_vote.hip
 int cv_sp_sort_rows_ex(const int32_t* d_coords, long long n, int32_t* d_sorted, int32_t* d_perm, int32_t* d_inv, void* d_ws,
                        size_t ws_bytes, bool single_batch, void* stream, bool bounds_prefilled);           // sparse_coords.hip
 int cv_sp_scene_plan_ex(const int32_t* d_input, long long n, int32_t* d_perm, int32_t* d_inv, int32_t* const* d_coords,

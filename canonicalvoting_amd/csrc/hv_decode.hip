@@ -119,13 +119,11 @@ __device__ __forceinline__ int lanes_below(uint64_t mask) {
                                      __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
 }
 
-__global__ __launch_bounds__(256) void dec_compact(const float* __restrict__ g_obj,
-                                                   const float* __restrict__ g_rot,
-                                                   const float* __restrict__ g_scale, Geo geo,
-                                                   int64_t G, float thresh, Ws w, CatStride ks) {
-    const int kc = blockIdx.y;
-    g_obj = g_obj + kc * ks.cells; g_rot = g_rot + kc * 2 * ks.cells; g_scale = g_scale + kc * 3 * ks.cells;
-    w = cat(w, ks.ws, kc);
+// (the kernels' bodies are device functions: the category axis and the scene axis differ only in where a workgroup's
+// operands come from - offsets of one set of arguments, or a row of a job table)
+__device__ __forceinline__ void compact_body(const float* __restrict__ g_obj, const float* __restrict__ g_rot,
+                                             const float* __restrict__ g_scale, const Geo& geo, int64_t G, float thresh,
+                                             const Ws& w) {
     const List& L = w.L;
     unsigned* list_n = w.list_n();
     for (int64_t base = blockIdx.x * 256ll; base < G; base += (int64_t)gridDim.x * 256) {
@@ -154,6 +152,16 @@ __global__ __launch_bounds__(256) void dec_compact(const float* __restrict__ g_o
             for (int k = 0; k < 3; ++k) L.geo[(2 + k) * L.cap + p] = g_scale[(int64_t)id * 3 + k];   // :216
         }
     }
+}
+
+__global__ __launch_bounds__(256) void dec_compact(const float* __restrict__ g_obj,
+                                                   const float* __restrict__ g_rot,
+                                                   const float* __restrict__ g_scale, Geo geo,
+                                                   int64_t G, float thresh, Ws w, CatStride ks) {
+    const int kc = blockIdx.y;
+    g_obj = g_obj + kc * ks.cells; g_rot = g_rot + kc * 2 * ks.cells; g_scale = g_scale + kc * 3 * ks.cells;
+    w = cat(w, ks.ws, kc);
+    compact_body(g_obj, g_rot, g_scale, geo, G, thresh, w);
 }
 
 // in-box test shared by grid suppression and back-projection:
@@ -590,22 +598,28 @@ __device__ __forceinline__ void walk_sorted(const Geo& geo, const cv_decode_para
 
 // One walker workgroup per category (blockIdx.y): the K walks run side by side.  The list length is only known on the
 // device, so the kernel picks the walk: lists up to GREEDY_CAP entries in registers + LDS, longer ones over the global arrays
-__global__ __launch_bounds__(GREEDY_T) void dec_greedy_dispatch(Geo geo, cv_decode_params prm, Ws w, int64_t ks_ws) {
-    w = cat(w, ks_ws, blockIdx.y);
+__device__ __forceinline__ void greedy_body(const Geo& geo, const cv_decode_params& prm, const Ws& w) {
     const unsigned n = *w.list_n();
     if (n <= (unsigned)GREEDY_CAP) walk_lds(geo, prm, w, (int)n);
     else walk_global<GREEDY_T>(geo, prm, w, (int)n);
+}
+__global__ __launch_bounds__(GREEDY_T) void dec_greedy_dispatch(Geo geo, cv_decode_params prm, Ws w, int64_t ks_ws) {
+    w = cat(w, ks_ws, blockIdx.y);
+    greedy_body(geo, prm, w);
 }
 // big grids (the host picks this launch from the cell count): 1024 threads, lists up to 24576 cells in registers (a
 // 300k-point scene lists ~21 000 cells) on the sorted walk
 constexpr int GREEDY_T_BIG = 1024;
 constexpr int GREEDY_E_BIG = 24;
 constexpr int GREEDY_G_BIG = 64;
-__global__ __launch_bounds__(GREEDY_T_BIG) void dec_greedy_dispatch_big(Geo geo, cv_decode_params prm, Ws w, int64_t ks_ws) {
-    w = cat(w, ks_ws, blockIdx.y);
+__device__ __forceinline__ void greedy_big_body(const Geo& geo, const cv_decode_params& prm, const Ws& w) {
     const unsigned n = *w.list_n();
     if (n <= (unsigned)(GREEDY_E_BIG * GREEDY_T_BIG)) walk_sorted<GREEDY_T_BIG, GREEDY_E_BIG, GREEDY_G_BIG>(geo, prm, w, (int)n);
     else walk_global<GREEDY_T_BIG>(geo, prm, w, (int)n);
+}
+__global__ __launch_bounds__(GREEDY_T_BIG) void dec_greedy_dispatch_big(Geo geo, cv_decode_params prm, Ws w, int64_t ks_ws) {
+    w = cat(w, ks_ws, blockIdx.y);
+    greedy_big_body(geo, prm, w);
 }
 
 // packed host result: [0]=n_cand [1]=n_boxes [2]=truncated, then arrays sized by max_iters
@@ -680,13 +694,10 @@ __device__ void finalize_block(const Cand* __restrict__ cands, const Stats* __re
     if (threadIdx.x == 0) { hdr[0] = nc; hdr[1] = base; hdr[2] = truncated; hdr[3] = 0; }
 }
 
-__global__ __launch_bounds__(256) void dec_backproject(
-    const float* __restrict__ pts, const float* __restrict__ xyz, const float* __restrict__ prob,
-    const int* __restrict__ cls, int64_t n, float prob_thresh, Ws w, CatStride ks) {
-    // category: blockIdx.z (blockIdx.y strides over the candidate groups)
-    const int kc = blockIdx.z;
-    xyz = xyz + kc * 3 * ks.n; prob = prob + kc * ks.n;
-    w = cat(w, ks.ws, kc);
+// (blockIdx.x: 256 points; blockIdx.y strides over the candidate groups)
+__device__ __forceinline__ void backproject_body(const float* __restrict__ pts, const float* __restrict__ xyz,
+                                                 const float* __restrict__ prob, const int* __restrict__ cls, int64_t n,
+                                                 float prob_thresh, const Ws& w) {
     const Cand* cands = w.cands;
     Stats* stats = w.stats;
     const int64_t i = blockIdx.x * 256ll + threadIdx.x;
@@ -759,6 +770,16 @@ __global__ __launch_bounds__(256) void dec_backproject(
     }
 }
 
+__global__ __launch_bounds__(256) void dec_backproject(
+    const float* __restrict__ pts, const float* __restrict__ xyz, const float* __restrict__ prob,
+    const int* __restrict__ cls, int64_t n, float prob_thresh, Ws w, CatStride ks) {
+    // category: blockIdx.z
+    const int kc = blockIdx.z;
+    xyz = xyz + kc * 3 * ks.n; prob = prob + kc * ks.n;
+    w = cat(w, ks.ws, kc);
+    backproject_body(pts, xyz, prob, cls, n, prob_thresh, w);
+}
+
 // one launch boundary (~2 us) instead of a release fence in each of the thousands of back-projection workgroups (an
 // agent-scope release writes the XCD's L2 back: the fused version ran 4x slower)
 __global__ __launch_bounds__(256) void dec_finalize(Ws w, cv_decode_params prm, char* result, int M, int64_t ks_ws,
@@ -770,10 +791,8 @@ __global__ __launch_bounds__(256) void dec_finalize(Ws w, cv_decode_params prm, 
 }
 
 // optional: replay the zeroing on the real grid (the reference mutates grid_obj in place)
-__global__ __launch_bounds__(256) void dec_apply(float* __restrict__ g_obj, Geo geo,
-                                                 cv_decode_params prm, Ws w, CatStride ks) {
-    g_obj = g_obj + (int64_t)blockIdx.y * ks.cells;
-    w = cat(w, ks.ws, blockIdx.y);
+__device__ __forceinline__ void apply_body(float* __restrict__ g_obj, const Geo& geo, const cv_decode_params& prm,
+                                           const Ws& w) {
     const int k = blockIdx.x;
     if (k >= w.n_cand()[0]) return;
     const Cand& cd = w.cands[k];
@@ -800,10 +819,69 @@ __global__ __launch_bounds__(256) void dec_apply(float* __restrict__ g_obj, Geo 
     }
 }
 
+__global__ __launch_bounds__(256) void dec_apply(float* __restrict__ g_obj, Geo geo,
+                                                 cv_decode_params prm, Ws w, CatStride ks) {
+    g_obj = g_obj + (int64_t)blockIdx.y * ks.cells;
+    w = cat(w, ks.ws, blockIdx.y);
+    apply_body(g_obj, geo, prm, w);
+}
+
 // the counters of K workspace carves zeroed in one launch
 __global__ __launch_bounds__(64) void dec_zero_counters(Ws w, int64_t ks_ws) {
     w = cat(w, ks_ws, blockIdx.y);
     if (threadIdx.x < CTR_WORDS) w.counters[threadIdx.x] = 0u;
+}
+
+// ---- Scene axis (cv_decode_scenes_f32): B jobs that share NOTHING but the parameters - every job has its own grid shape,
+// corner, grid triple, workspace carve and row range [row0, row0 + n) of the shared point / prediction arrays.  The job
+// table travels by value in the kernel arguments (16 x 144 bytes of the 4 KB) and the job index sits where the category index
+// sits above.  Launch extents are the maximum over the jobs: a workgroup beyond its own job's extent returns at once.
+struct SceneJob {
+    Geo geo;
+    int big;                 // the walker workgroup the single call would choose for this grid (CV_DEC_BIG_CELLS)
+    Ws w;
+    float* g_obj; const float* g_rot; const float* g_scale;
+    int64_t row0, n, G;
+};
+struct SceneJobs { SceneJob j[CV_MAX_SCENES]; };
+static_assert(sizeof(SceneJobs) + 64 <= 4096, "the job table is a kernel argument");
+
+__global__ __launch_bounds__(64) void dec_zero_counters_scenes(SceneJobs js) {
+    const SceneJob& j = js.j[blockIdx.y];
+    if (threadIdx.x < CTR_WORDS) j.w.counters[threadIdx.x] = 0u;
+}
+__global__ __launch_bounds__(256) void dec_compact_scenes(SceneJobs js, float thresh) {
+    const SceneJob& j = js.j[blockIdx.y];
+    if (blockIdx.x * 256ll >= j.G) return;
+    compact_body(j.g_obj, j.g_rot, j.g_scale, j.geo, j.G, thresh, j.w);
+}
+__global__ __launch_bounds__(GREEDY_T) void dec_greedy_dispatch_scenes(SceneJobs js, cv_decode_params prm) {
+    const SceneJob& j = js.j[blockIdx.y];
+    if (j.big) return;       // (the other walker's job)
+    greedy_body(j.geo, prm, j.w);
+}
+__global__ __launch_bounds__(GREEDY_T_BIG) void dec_greedy_dispatch_big_scenes(SceneJobs js, cv_decode_params prm) {
+    const SceneJob& j = js.j[blockIdx.y];
+    if (!j.big) return;
+    greedy_big_body(j.geo, prm, j.w);
+}
+__global__ __launch_bounds__(256) void dec_backproject_scenes(const float* __restrict__ pts, const float* __restrict__ xyz,
+                                                              const float* __restrict__ prob, const int* __restrict__ cls,
+                                                              float prob_thresh, SceneJobs js) {
+    const SceneJob& j = js.j[blockIdx.z];
+    if (blockIdx.x * 256ll >= j.n) return;       // (every workgroup of a job adds into that job's own statistics)
+    backproject_body(pts + j.row0 * 3, xyz + j.row0 * 3, prob + j.row0, cls + j.row0, j.n, prob_thresh, j.w);
+}
+__global__ __launch_bounds__(256) void dec_finalize_scenes(SceneJobs js, cv_decode_params prm, char* result, int M,
+                                                           int64_t result_stride) {
+    const SceneJob& j = js.j[blockIdx.y];
+    result += (int64_t)blockIdx.y * result_stride;
+    __shared__ int s_scan[256];
+    finalize_block(j.w.cands, j.w.stats, j.w.n_cand()[0], j.w.n_cand()[1], prm, result, M, s_scan);
+}
+__global__ __launch_bounds__(256) void dec_apply_scenes(SceneJobs js, cv_decode_params prm) {
+    const SceneJob& j = js.j[blockIdx.y];
+    apply_body(j.g_obj, j.geo, prm, j.w);
 }
 
 // the single-category workspace: the list arrays (one slot per grid cell), the counters block, candidates, statistics
@@ -874,6 +952,28 @@ struct PinnedLease {
     PinnedLease& operator=(const PinnedLease&) = delete;
 };
 
+// block k of the pinned results into the caller's arrays at k, k * M, k * M * 24
+int land_result(const DecodeCall& c, const char* hk, const ResultLayout& RL, int k, int M) {
+    const int* hdr = reinterpret_cast<const int*>(hk);
+    const int nc = hdr[0], nb = hdr[1];
+    CV_REQUIRE(nc >= 0 && nc <= M && nb >= 0 && nb <= nc, CV_ERANGE, "corrupt decode result");
+    c.h_n_cand[k] = nc;
+    c.h_n_boxes[k] = nb;
+    if (c.h_truncated) c.h_truncated[k] = hdr[2];
+    std::memcpy(c.h_cand_idx + (size_t)k * M, hk + RL.off_cand, sizeof(int64_t) * nc);
+    std::memcpy(c.h_verdict + (size_t)k * M, hk + RL.off_verdict, sizeof(int32_t) * nc);
+    std::memcpy(c.h_boxes + (size_t)k * M * 24, hk + RL.off_boxes, sizeof(float) * 24 * nb);
+    std::memcpy(c.h_scores + (size_t)k * M, hk + RL.off_scores, sizeof(float) * nb);
+    std::memcpy(c.h_classes + (size_t)k * M, hk + RL.off_classes, sizeof(int32_t) * nb);
+    return CV_OK;
+}
+
+// grids beyond this many cells take the 1024-thread walker (read once per process)
+long long dec_big_cells() {
+    static const long long big_cells = getenv("CV_DEC_BIG_CELLS") ? atoll(getenv("CV_DEC_BIG_CELLS")) : (4ll << 20);
+    return big_cells;
+}
+
 }  // namespace
 
 // (C++ linkage, cv_common.h) K categories; category k's host outputs at k, k * M, k * M * 24
@@ -920,8 +1020,7 @@ int cv_decode_run(const DecodeCall& c, int K, bool need_class) {
     CV_LAUNCH_CHECK();
     // the walk is chosen by the kernel from the list length; the host only chooses the workgroup: grids beyond 4 M cells
     // (300k-point scenes) list more cells than the 512-thread walker keeps in registers
-    static const long long big_cells = getenv("CV_DEC_BIG_CELLS") ? atoll(getenv("CV_DEC_BIG_CELLS")) : (4ll << 20);
-    if (G > big_cells) dec_greedy_dispatch_big<<<dim3(1, K), GREEDY_T_BIG, 0, st>>>(geo, *params, w, ks.ws);
+    if (G > dec_big_cells()) dec_greedy_dispatch_big<<<dim3(1, K), GREEDY_T_BIG, 0, st>>>(geo, *params, w, ks.ws);
     else dec_greedy_dispatch<<<dim3(1, K), GREEDY_T, 0, st>>>(geo, *params, w, ks.ws);
     CV_LAUNCH_CHECK();
     // candidate groups of 8 over blockIdx.y (the count is only known on the device: groups beyond it return at once)
@@ -938,18 +1037,101 @@ int cv_decode_run(const DecodeCall& c, int K, bool need_class) {
     if (c.ev_done) CV_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(c.ev_done), st));
     CV_HIP_CHECK(hipStreamSynchronize(st));
     for (int k = 0; k < K; ++k) {
-        const char* hk = host + (size_t)k * RL.total;
-        const int* hdr = reinterpret_cast<const int*>(hk);
-        const int nc = hdr[0], nb = hdr[1];
-        CV_REQUIRE(nc >= 0 && nc <= M && nb >= 0 && nb <= nc, CV_ERANGE, "corrupt decode result");
-        c.h_n_cand[k] = nc;
-        c.h_n_boxes[k] = nb;
-        if (c.h_truncated) c.h_truncated[k] = hdr[2];
-        std::memcpy(c.h_cand_idx + (size_t)k * M, hk + RL.off_cand, sizeof(int64_t) * nc);
-        std::memcpy(c.h_verdict + (size_t)k * M, hk + RL.off_verdict, sizeof(int32_t) * nc);
-        std::memcpy(c.h_boxes + (size_t)k * M * 24, hk + RL.off_boxes, sizeof(float) * 24 * nb);
-        std::memcpy(c.h_scores + (size_t)k * M, hk + RL.off_scores, sizeof(float) * nb);
-        std::memcpy(c.h_classes + (size_t)k * M, hk + RL.off_classes, sizeof(int32_t) * nb);
+        const int rc = land_result(c, host + (size_t)k * RL.total, RL, k, M);
+        if (rc != CV_OK) return rc;
+    }
+    return CV_OK;
+}
+
+// (C++ linkage, cv_common.h) B scenes; scene b's host outputs at b, b * M, b * M * 24.  c: the shared arrays, the parameters,
+// the workspace (carved in job order, each job its single-call size) and the host outputs; its grid / dims / corner / n fields
+// are not read (the jobs carry them).
+int cv_decode_scenes_run(const DecodeCall& c, const cv_decode_scene_job* jobs, int B) {
+    CV_REQUIRE(B >= 1 && B <= CV_MAX_SCENES, CV_EINVAL, "num_scenes out of range (%d, 1..%d)", B, CV_MAX_SCENES);
+    CV_REQUIRE(jobs && c.d_points && c.d_xyz && c.d_prob && c.d_class && c.params && c.d_ws && c.h_n_cand && c.h_cand_idx &&
+                   c.h_verdict && c.h_n_boxes && c.h_boxes && c.h_scores && c.h_classes,
+               CV_EINVAL, "null pointer argument");
+    const cv_decode_params* params = c.params;
+    hipStream_t st = static_cast<hipStream_t>(c.stream);
+    CV_REQUIRE(c.res > 0.f, CV_EINVAL, "res must be positive");
+    const int M = params->max_iters;
+    CV_REQUIRE(M > 0 && M <= 65536, CV_EINVAL, "max_iters out of range");
+    CV_REQUIRE(params->elimination >= 0, CV_EINVAL, "elimination must be >= 0");
+    CV_REQUIRE(params->thresh_high > 0.f, CV_EINVAL, "thresh_high must be positive");
+    size_t need = 0;
+    for (int b = 0; b < B; ++b) {
+        const cv_decode_scene_job& j = jobs[b];
+        CV_REQUIRE(j.d_grid_obj && j.d_grid_rot && j.d_grid_scale, CV_EINVAL, "scene %d: null grid pointer", b);
+        CV_REQUIRE(j.n > 0 && j.row0 >= 0, CV_EINVAL, "scene %d: bad row range (first row %lld, %lld rows)", b, (long long)j.row0,
+                   (long long)j.n);
+        CV_REQUIRE(j.dims[0] > 0 && j.dims[1] > 0 && j.dims[2] > 0, CV_EINVAL, "scene %d: bad grid dims", b);
+        CV_REQUIRE(j.dims[0] < 65536 && j.dims[1] < 65536 && j.dims[2] < 65536, CV_EINVAL, "scene %d: grid dims must be below 65536", b);
+        CV_REQUIRE((int64_t)j.dims[0] * j.dims[1] * j.dims[2] < (1ll << 31), CV_EINVAL, "scene %d: grid too large", b);
+        need += WsLayout((int64_t)j.dims[0] * j.dims[1] * j.dims[2], M).total;
+    }
+    CV_REQUIRE(c.ws_bytes >= need, CV_ENOMEM, "workspace too small (%zu < %zu)", c.ws_bytes, need);
+    if (B == 1) {       // one scene: the single call's launches, on its row range
+        const cv_decode_scene_job& j = jobs[0];
+        DecodeCall one = c;
+        one.d_grid_obj = j.d_grid_obj; one.d_grid_rot = j.d_grid_rot; one.d_grid_scale = j.d_grid_scale;
+        one.dims = j.dims; one.h_corner3 = j.corner;
+        one.d_points = c.d_points + j.row0 * 3; one.d_xyz = c.d_xyz + j.row0 * 3; one.d_prob = c.d_prob + j.row0;
+        one.d_class = c.d_class + j.row0; one.n = j.n;
+        return cv_decode_run(one, 1, true);
+    }
+    const ResultLayout RL(M);
+    const PinnedLease lease((size_t)B * RL.total);
+    char* host = lease.buf.first;
+    CV_REQUIRE(host != nullptr, CV_ENOMEM, "pinned host buffer of %zu bytes", (size_t)B * RL.total);
+
+    SceneJobs js;
+    std::memset(&js, 0, sizeof(js));
+    int64_t max_G = 0, max_n = 0;
+    bool any_small = false, any_big = false;
+    char* ws = static_cast<char*>(c.d_ws);
+    for (int b = 0; b < B; ++b) {
+        const cv_decode_scene_job& j = jobs[b];
+        SceneJob& o = js.j[b];
+        o.G = (int64_t)j.dims[0] * j.dims[1] * j.dims[2];
+        o.geo = Geo{j.dims[0], j.dims[1], j.dims[2], {j.corner[0], j.corner[1], j.corner[2]}, c.res};
+        o.big = o.G > dec_big_cells() ? 1 : 0;
+        const WsLayout W(o.G, M);
+        o.w = W.at(ws);
+        ws += W.total;
+        o.g_obj = j.d_grid_obj; o.g_rot = j.d_grid_rot; o.g_scale = j.d_grid_scale;
+        o.row0 = j.row0; o.n = j.n;
+        max_G = std::max(max_G, o.G);
+        max_n = std::max(max_n, o.n);
+        (o.big ? any_big : any_small) = true;
+    }
+    dec_zero_counters_scenes<<<dim3(1, B), 64, 0, st>>>(js);
+    CV_LAUNCH_CHECK();
+    const int cblocks = (int)std::min<int64_t>((max_G + 255) / 256, 2048);
+    dec_compact_scenes<<<dim3(cblocks, B), 256, 0, st>>>(js, params->thresh_high);
+    CV_LAUNCH_CHECK();
+    // each scene on the walker the single call would choose for its grid: a batch on both sides of the switch is two launches
+    if (any_small) {
+        dec_greedy_dispatch_scenes<<<dim3(1, B), GREEDY_T, 0, st>>>(js, *params);
+        CV_LAUNCH_CHECK();
+    }
+    if (any_big) {
+        dec_greedy_dispatch_big_scenes<<<dim3(1, B), GREEDY_T_BIG, 0, st>>>(js, *params);
+        CV_LAUNCH_CHECK();
+    }
+    const dim3 bgrid((unsigned)((max_n + 255) / 256), (unsigned)std::min((M + 7) / 8, 8), (unsigned)B);
+    dec_backproject_scenes<<<bgrid, 256, 0, st>>>(c.d_points, c.d_xyz, c.d_prob, c.d_class, params->prob_thresh, js);
+    CV_LAUNCH_CHECK();
+    dec_finalize_scenes<<<dim3(1, B), 256, 0, st>>>(js, *params, host, M, (int64_t)RL.total);
+    CV_LAUNCH_CHECK();
+    if (c.mutate_grid) {
+        dec_apply_scenes<<<dim3(M, B), 256, 0, st>>>(js, *params);
+        CV_LAUNCH_CHECK();
+    }
+    if (c.ev_done) CV_HIP_CHECK(hipEventRecord(static_cast<hipEvent_t>(c.ev_done), st));
+    CV_HIP_CHECK(hipStreamSynchronize(st));
+    for (int b = 0; b < B; ++b) {
+        const int rc = land_result(c, host + (size_t)b * RL.total, RL, b, M);
+        if (rc != CV_OK) return rc;
     }
     return CV_OK;
 }
@@ -1139,6 +1321,29 @@ size_t cv_decode_workspace_bytes(const int dims[3], int64_t n, int max_iters) {
     (void)n;
     return WsLayout((int64_t)dims[0] * dims[1] * dims[2], max_iters).total;
 }
+
+size_t cv_decode_scenes_workspace_bytes(const cv_decode_scene_job* jobs, int num_scenes, int max_iters) {
+    if (!jobs || num_scenes < 1 || num_scenes > CV_MAX_SCENES) return 0;
+    size_t total = 0;
+    for (int b = 0; b < num_scenes; ++b) {
+        const size_t one = cv_decode_workspace_bytes(jobs[b].dims, jobs[b].n, max_iters);
+        if (one == 0) return 0;
+        total += one;
+    }
+    return total;
+}
+
+int cv_decode_scenes_f32(const cv_decode_scene_job* jobs, int num_scenes, float res, const float* d_points, const float* d_xyz,
+                         const float* d_prob, const int32_t* d_class, const cv_decode_params* params, int mutate_grid, void* d_ws,
+                         size_t ws_bytes, int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes, float* h_boxes,
+                         float* h_scores, int32_t* h_classes, int* h_truncated, void* stream) {
+    const DecodeCall c{nullptr, nullptr, nullptr, nullptr, nullptr, res, d_points, d_xyz, d_prob, d_class, 0, params,
+                       mutate_grid, d_ws, ws_bytes, h_n_cand, h_cand_idx, h_verdict, h_n_boxes, h_boxes, h_scores, h_classes,
+                       h_truncated, stream, nullptr};
+    return cv_decode_scenes_run(c, jobs, num_scenes);
+}
+
+size_t cv_sizeof_decode_scene_job(void) { return sizeof(cv_decode_scene_job); }
 
 size_t cv_decode_cat_workspace_bytes(const int dims[3], int64_t n, int max_iters, int num_cats) {
     if (num_cats < 1 || num_cats > CV_MAX_CATEGORIES) return 0;

@@ -142,6 +142,85 @@ __global__ __launch_bounds__(256) void minmax_final(const float* __restrict__ pa
     if (threadIdx.x < 6) out[threadIdx.x] = s[threadIdx.x][0];
 }
 
+// Per-scene row ranges and bounds of a batched coordinate set (cv_detect_scenes_f32): one workgroup per scene, ONE launch.
+// The batch column is expected non-decreasing: the first row with a batch index >= key is found by a 1024-ary search (every
+// thread probes one row of the open interval per round: three rounds cover 2^30 rows).  Scene b's rows are [lower(b),
+// lower(b + 1)) - the same search gives b's end and b + 1's start, so the ranges tile [lower(0), lower(B)) by construction.
+// The workgroup then checks that every row of its range carries b and reduces min / max of the points over it (min and max
+// are exact: the same values minmax_partial / minmax_final give for the scene alone).  out: 16 words per scene.
+constexpr int SB_T = 1024;
+constexpr int SB_WORDS = 16;
+
+__device__ __forceinline__ int64_t batch_lower_bound(const int32_t* __restrict__ coords4, int64_t n, int key) {
+    int64_t lo = 0, hi = n;          // rows below lo are < key, rows from hi on are >= key (for a sorted column)
+    while (lo < hi) {
+        const int64_t chunk = (hi - lo + SB_T - 1) / SB_T;
+        const int64_t p = lo + (int64_t)threadIdx.x * chunk;
+        const int c = __syncthreads_count(p < hi && coords4[p * 4] < key);
+        if (c == 0) hi = lo;
+        else {
+            const int64_t first_false = lo + (int64_t)c * chunk;
+            lo = lo + (int64_t)(c - 1) * chunk + 1;
+            hi = first_false < hi ? first_false : hi;
+        }
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(SB_T) void scene_bounds(const int32_t* __restrict__ coords4, const float* __restrict__ pts,
+                                                     int64_t n, int B, int32_t* __restrict__ out, int* __restrict__ zero_word,
+                                                     int* __restrict__ fill7f) {
+    const int b = blockIdx.x;
+    if (b == 0) {        // (what minmax_final initialises for the scene call's next stages)
+        if (zero_word && threadIdx.x == 32) *zero_word = 0;
+        if (fill7f && threadIdx.x >= 64 && threadIdx.x < 72) fill7f[threadIdx.x - 64] = 0x7f7f7f7f;
+    }
+    const int64_t first = batch_lower_bound(coords4, n, b), end = batch_lower_bound(coords4, n, b + 1);
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool bad = (b == 0 && first != 0) || (b == B - 1 && end != n) || end < first;
+    // four rows per thread and round, their sixteen loads issued together (one workgroup walks the whole scene: a round is a
+    // memory round trip); a row index beyond the range is clamped to its last row, which changes neither min, max nor the check
+    for (int64_t i0 = first + threadIdx.x; i0 < end; i0 += 4 * SB_T) {
+        int bt[4];
+        float v[4][3];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t i = i0 + u * SB_T < end ? i0 + u * SB_T : end - 1;
+            bt[u] = coords4[i * 4];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[u][k] = pts[i * 3 + k];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            bad |= bt[u] != b;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                mn[k] = fminf(mn[k], v[u][k]);
+                mx[k] = fmaxf(mx[k], v[u][k]);
+            }
+        }
+    }
+    __shared__ float s[6][SB_T];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { s[k][threadIdx.x] = mn[k]; s[3 + k][threadIdx.x] = mx[k]; }
+    const int any_bad = __syncthreads_or(bad);
+    for (int st = SB_T / 2; st > 0; st >>= 1) {
+        if (threadIdx.x < st) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                s[k][threadIdx.x] = fminf(s[k][threadIdx.x], s[k][threadIdx.x + st]);
+                s[3 + k][threadIdx.x] = fmaxf(s[3 + k][threadIdx.x], s[3 + k][threadIdx.x + st]);
+            }
+        }
+        __syncthreads();
+    }
+    int32_t* o = out + b * SB_WORDS;
+    if (threadIdx.x < 6) o[2 + threadIdx.x] = __float_as_int(s[threadIdx.x][0]);
+    if (threadIdx.x == 6) o[0] = (int32_t)first;
+    if (threadIdx.x == 7) o[1] = (int32_t)end;
+    if (threadIdx.x == 8) o[8] = any_bad ? 1 : 0;
+}
+
 // ---------------------------------------------------------------------------
 // direct algorithm
 // ---------------------------------------------------------------------------
@@ -1613,6 +1692,23 @@ int cv_hv_minmax_async_ex(const float* d_points, int64_t n, float* h_minmax6, vo
     minmax_final<<<1, 256, 0, st>>>(part, blocks, out, d_zero_word, d_fill7f);
     CV_LAUNCH_CHECK();
     CV_HIP_CHECK(hipMemcpyAsync(h_minmax6, out, 6 * sizeof(float), hipMemcpyDeviceToHost, st));
+    return CV_OK;
+}
+
+// (C++ linkage, cv_common.h) the scene axis of the reduction above: one launch, one copy
+int cv_hv_scene_bounds_async_ex(const int32_t* d_coords4, const float* d_points, int64_t n, int num_scenes, int32_t* h_out,
+                                void* d_ws, size_t ws_bytes, int32_t* d_zero_word, int32_t* d_fill7f, void* stream) {
+    CV_REQUIRE(d_coords4 && d_points && h_out && d_ws, CV_EINVAL, "null pointer argument");
+    CV_REQUIRE(n > 0 && n < (1ll << 31), CV_EINVAL, "n out of range (got %lld)", (long long)n);
+    CV_REQUIRE(num_scenes >= 1 && num_scenes <= CV_MAX_SCENES, CV_EINVAL, "num_scenes out of range (%d, 1..%d)", num_scenes,
+               CV_MAX_SCENES);
+    static_assert(sizeof(int32_t) * SB_WORDS * CV_MAX_SCENES <= sizeof(float) * 6 * MM_BLOCKS, "fits the minmax workspace");
+    CV_REQUIRE(ws_bytes >= cv_hv_minmax_workspace_bytes(), CV_ENOMEM, "workspace too small");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t* out = static_cast<int32_t*>(d_ws);
+    scene_bounds<<<num_scenes, SB_T, 0, st>>>(d_coords4, d_points, n, num_scenes, out, d_zero_word, d_fill7f);
+    CV_LAUNCH_CHECK();
+    CV_HIP_CHECK(hipMemcpyAsync(h_out, out, sizeof(int32_t) * SB_WORDS * num_scenes, hipMemcpyDeviceToHost, st));
     return CV_OK;
 }
 

@@ -88,6 +88,12 @@ struct SceneFront {
         : d_coords4(d->d_coords4), n(d->n), d_points(d->d_points), res(d->res), stem_k(d->stem_k), mask_groups(d->mask_groups),
           masked_min_rows(d->masked_min_rows), max_channels(d->max_channels), h_minmax(static_cast<float*>(d->h_pinned)) {}
 
+    // the scene axis (cv_detect_scenes_f32): B > 1 scenes in the batch column; their row ranges and bounds land in the pinned
+    // block from +256 bytes on (16 words per scene, cv_hv_scene_bounds_async_ex) and the grid shapes are the caller's to derive.
+    // B <= 1: the one scene's front - all rows, bounds in the first six pinned words, the batch column not read
+    int num_scenes = 0;
+    const int32_t* h_bounds() const { return reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(h_minmax) + 256); }
+
     // the first five carves of both modes; false when one of them did not fit
     bool carve(Carver& cv) {
         mm_ws = cv.take<char>(cv_hv_minmax_workspace_bytes());
@@ -103,8 +109,12 @@ struct SceneFront {
     template <class R> int run(int32_t* d_zero_word, R* r, StageClock& clock, void* stream) {
         // ---- bounds of the points (the vote grid's origin and shape): reduced first, read after the plan's own host wait
         // (the one-workgroup final launch of the bounds also fills the eight bound words at the head of the sort's workspace)
-        int rc = cv_hv_minmax_async_ex(d_points, n, h_minmax, mm_ws, cv_hv_minmax_workspace_bytes(), d_zero_word,
-                                       reinterpret_cast<int32_t*>(sort_ws), stream);
+        int rc = num_scenes > 1
+                     ? cv_hv_scene_bounds_async_ex(d_coords4, d_points, n, num_scenes, const_cast<int32_t*>(h_bounds()), mm_ws,
+                                                   cv_hv_minmax_workspace_bytes(), d_zero_word, reinterpret_cast<int32_t*>(sort_ws),
+                                                   stream)
+                     : cv_hv_minmax_async_ex(d_points, n, h_minmax, mm_ws, cv_hv_minmax_workspace_bytes(), d_zero_word,
+                                             reinterpret_cast<int32_t*>(sort_ws), stream);
         if (rc != CV_OK) return rc;
         int32_t *c_coords[5], *c_vals[5];
         unsigned long long* c_keys[5];
@@ -117,7 +127,11 @@ struct SceneFront {
         rc = cv_sp_scene_plan_ex(d_coords4, n, ibuf + lay.perm, ibuf + lay.inv, c_coords, c_keys, c_vals, lay.cap, ibuf + lay.counts,
                                  counts_h, stem_k, mask_groups, masked_min_rows, ibuf + lay.arena, (size_t)(lay.int_words - lay.arena),
                                  &off, sort_ws, lay.sort_ws_bytes, lev_ws, lay.levels_ws_bytes,
-                                 /* one scene: the sort skips its batch digit */ true, stream, /* bound words filled above */ true);
+                                 /* one scene: the sort skips its batch digit */ num_scenes <= 1, stream,
+                                 /* bound words filled above */ true);
+        if (rc != CV_OK) return rc;
+        // (the plan waited for an event recorded behind the bounds reduction: the pinned bounds and row ranges are valid)
+        rc = check_batch_column();
         if (rc != CV_OK) return rc;
         r->duplicates = counts_h[5];
         r->out_of_window = counts_h[6];
@@ -125,18 +139,38 @@ struct SceneFront {
                    "duplicate coordinates (%d) or coordinates outside the 16-bit key window (%d)", counts_h[5], counts_h[6]);
         clock.lap(0);
         for (int i = 0; i < 5; ++i) { rows[i] = counts_h[i]; r->level_rows[i] = counts_h[i]; }
-        // (the plan waited for an event recorded behind the bounds reduction: the pinned bounds are valid)
-        float mx[3];
-        for (int k = 0; k < 3; ++k) { mn[k] = h_minmax[k]; mx[k] = h_minmax[3 + k]; r->corner[k] = mn[k]; }
-        rc = cv_hv_grid_dims_f32(mn, mx, res, dims);
+        rc = one_grid(r);
         if (rc != CV_OK) return rc;
-        for (int k = 0; k < 3; ++k) r->dims[k] = dims[k];
-        cells = (size_t)dims[0] * dims[1] * dims[2];
         // ---- for the network programs: map / order slots (mask orders NULL below masked_min_rows) and the convolution workspace
         int masked[5];
         for (int i = 0; i < 5; ++i) masked[i] = off.mask_perm[i] >= 0;
         conv_ws_b = cv_sp_scene_conv_workspace_bytes(rows, masked, mask_groups, max_channels);
         return cv_sp_scene_plan_slots(&lay, &off, rows, masked_min_rows, ibuf, maps, perms);
+    }
+
+    // corner and shape of the one vote grid from the pinned bounds (the scene axis derives B of them itself)
+    template <class R> int one_grid(R* r) {
+        float mx[3];
+        for (int k = 0; k < 3; ++k) { mn[k] = h_minmax[k]; mx[k] = h_minmax[3 + k]; r->corner[k] = mn[k]; }
+        const int rc = cv_hv_grid_dims_f32(mn, mx, res, dims);
+        if (rc != CV_OK) return rc;
+        for (int k = 0; k < 3; ++k) r->dims[k] = dims[k];
+        cells = (size_t)dims[0] * dims[1] * dims[2];
+        return CV_OK;
+    }
+    int one_grid(cv_scenes_result*) { return CV_OK; }
+
+    // the scene axis: every scene's rows are one run of the batch column, in scene order, and no scene is empty
+    int check_batch_column() const {
+        for (int b = 0; num_scenes > 1 && b < num_scenes; ++b) {
+            const int32_t* w = h_bounds() + 16 * b;
+            const long long first = w[0], end = w[1];
+            CV_REQUIRE(w[8] == 0 && first >= 0 && end >= first && end <= n, CV_EINVAL,
+                       "scene %d: the batch column is not non-decreasing or leaves [0, %d) (rows %lld..%lld)", b, num_scenes, first,
+                       end);
+            CV_REQUIRE(end > first, CV_EINVAL, "scene %d has no rows (batch index %d does not occur in the batch column)", b, b);
+        }
+        return CV_OK;
     }
 };
 
@@ -147,23 +181,60 @@ template <class R> int fixed_part_too_small(R* r, size_t fixed_end) {
     return CV_ENOMEM;
 }
 
+// what cv_detect_scene_f32 and cv_detect_scenes_f32 validate before the first device call
+int check_joint_arrays(const cv_scene_desc* d, size_t pinned_min) {
+    CV_REQUIRE(d->d_coords4 && d->d_feats && d->d_points && d->n > 0 && d->ops && d->bufs && d->n_ops > 0 && d->n_bufs > 0,
+               CV_EINVAL, "bad scene descriptor");
+    CV_REQUIRE(d->d_out_feats && d->out_ld >= d->out_channels && d->out_channels > 0, CV_EINVAL, "bad network output buffer");
+    CV_REQUIRE(d->h_pinned && d->pinned_bytes >= pinned_min && d->d_ws, CV_EINVAL,
+               "pinned scratch (>= %zu bytes) and a device workspace are required", pinned_min);
+    CV_REQUIRE(d->h_boxes && d->h_scores && d->h_classes && d->h_cand_idx && d->h_verdict && d->h_pick && d->max_candidates > 0,
+               CV_EINVAL, "null result arrays");
+    return CV_OK;
+}
+int check_joint_sizing(const cv_scene_desc* d) {
+    CV_REQUIRE(d->conv_split_target >= 0 && d->vote_part_records >= 0, CV_EINVAL, "negative launch sizing");
+    CV_REQUIRE(d->vote_algo >= 0 && d->vote_algo <= 2, CV_EINVAL, "vote_algo out of range (%d: 0 auto, 1 direct, 2 tiles)", d->vote_algo);
+    return CV_OK;
+}
+
+// per-class NMS (eval_joint.py:270-280) of one scene's boxes: kept boxes as indices into the decode's box list, class by class.
+// Returns the number of detections, or a negative error.
+int nms_per_class(const cv_scene_desc* d, int n_boxes, const float* h_boxes, const float* h_scores, const int32_t* h_classes,
+                  int32_t* h_pick) {
+    int n_det = 0;
+    std::vector<float> bc, sc;
+    std::vector<int32_t> idx, pick;
+    for (int c = 0; c < d->nclasses; ++c) {
+        bc.clear(); sc.clear(); idx.clear();
+        for (int i = 0; i < n_boxes; ++i)
+            if (h_classes[i] == c) {
+                bc.insert(bc.end(), h_boxes + (size_t)i * 24, h_boxes + (size_t)i * 24 + 24);
+                sc.push_back(h_scores[i]);
+                idx.push_back(i);
+            }
+        if (idx.empty()) continue;
+        pick.assign(idx.size(), 0);
+        const int k = cv_nms_obb(bc.data(), sc.data(), (int)idx.size(), d->nms_threshold, pick.data());
+        if (k < 0) return k;
+        for (int j = 0; j < k; ++j) h_pick[n_det++] = idx[(size_t)pick[j]];
+    }
+    return n_det;
+}
+
 }  // namespace
 
 extern "C" {
 
 int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream) {
     CV_REQUIRE(d && r, CV_EINVAL, "null scene descriptor / result");
-    CV_REQUIRE(d->d_coords4 && d->d_feats && d->d_points && d->n > 0 && d->ops && d->bufs && d->n_ops > 0 && d->n_bufs > 0,
-               CV_EINVAL, "bad scene descriptor");
-    CV_REQUIRE(d->d_out_feats && d->out_ld >= d->out_channels && d->out_channels > 0, CV_EINVAL, "bad network output buffer");
-    CV_REQUIRE(d->h_pinned && d->pinned_bytes >= 256 && d->d_ws, CV_EINVAL, "pinned scratch (>= 256 bytes) and a device workspace are required");
-    CV_REQUIRE(d->h_boxes && d->h_scores && d->h_classes && d->h_cand_idx && d->h_verdict && d->h_pick && d->max_candidates > 0,
-               CV_EINVAL, "null result arrays");
+    int rc = check_joint_arrays(d, 256);
+    if (rc != CV_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long n = d->n;
     std::memset(r, 0, sizeof(*r));
-    CV_REQUIRE(d->conv_split_target >= 0 && d->vote_part_records >= 0, CV_EINVAL, "negative launch sizing");
-    CV_REQUIRE(d->vote_algo >= 0 && d->vote_algo <= 2, CV_EINVAL, "vote_algo out of range (%d: 0 auto, 1 direct, 2 tiles)", d->vote_algo);
+    rc = check_joint_sizing(d);
+    if (rc != CV_OK) return rc;
     SceneCount in_flight(d->adaptive_split != 0, d->conv_split_target, d->vote_part_records);
     r->scenes_in_flight = in_flight.before + 1;
     Carver cv(d->d_ws, d->ws_bytes);
@@ -180,7 +251,7 @@ int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream
     int32_t* d_flag = cv.take<int32_t>(64);
     if (!plan_fits || !xyz || !scale || !prob || !cls || !d_flag) return fixed_part_too_small(r, cv.off);
     // (the bounds reduction zeroes the range flag: no fill launch)
-    int rc = f.run(d_flag, r, clock, stream);
+    rc = f.run(d_flag, r, clock, stream);
     if (rc != CV_OK) return rc;
     const size_t cells = f.cells;
 
@@ -244,28 +315,148 @@ int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream
     // (the decode waited for the stream: the range flag of the network's convolutions has landed)
     r->range_flag = d->use_range_flag ? *h_flag : 0;
 
-    // ---- per-class NMS (eval_joint.py:270-280): kept boxes as indices into the decode's box list, class by class
-    int n_det = 0;
-    std::vector<float> bc, sc;
-    std::vector<int32_t> idx, pick;
-    for (int c = 0; c < d->nclasses; ++c) {
-        bc.clear(); sc.clear(); idx.clear();
-        for (int i = 0; i < n_boxes; ++i)
-            if (d->h_classes[i] == c) {
-                bc.insert(bc.end(), d->h_boxes + (size_t)i * 24, d->h_boxes + (size_t)i * 24 + 24);
-                sc.push_back(d->h_scores[i]);
-                idx.push_back(i);
-            }
-        if (idx.empty()) continue;
-        pick.assign(idx.size(), 0);
-        const int k = cv_nms_obb(bc.data(), sc.data(), (int)idx.size(), d->nms_threshold, pick.data());
-        if (k < 0) return k;
-        for (int j = 0; j < k; ++j) d->h_pick[n_det++] = idx[(size_t)pick[j]];
-    }
-    r->n_det = n_det;
+    rc = nms_per_class(d, n_boxes, d->h_boxes, d->h_scores, d->h_classes, d->h_pick);
+    if (rc < 0) return rc;
+    r->n_det = rc;
     clock.lap(3);
     return CV_OK;
 }
+
+// B scans in one call: the front, the network and the head over all rows, a vote per scene, one decode over the scene axis.
+int cv_detect_scenes_f32(const cv_scenes_desc* sd, cv_scenes_result* r, void* stream) {
+    CV_REQUIRE(sd && r, CV_EINVAL, "null scene descriptor / result");
+    const cv_scene_desc* d = &sd->scene;
+    const int B = sd->num_scenes;
+    CV_REQUIRE(B >= 1 && B <= CV_MAX_SCENES, CV_EINVAL, "num_scenes out of range (%d, 1..%d)", B, CV_MAX_SCENES);
+    int rc = check_joint_arrays(d, 256 + 64 * (size_t)B);
+    if (rc != CV_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long long n = d->n;
+    const int M = d->max_candidates;
+    std::memset(r, 0, sizeof(*r));
+    rc = check_joint_sizing(d);
+    if (rc != CV_OK) return rc;
+    CV_REQUIRE(n < (1ll << 31), CV_EINVAL, "n out of range (%lld)", n);
+    SceneCount in_flight(d->adaptive_split != 0, d->conv_split_target, d->vote_part_records);
+    r->scenes_in_flight = in_flight.before + 1;
+    Carver cv(d->d_ws, d->ws_bytes);
+    StageClock clock{d->events, st, r->host_us};
+    CV_HIP_CHECK(clock.mark(0));
+
+    SceneFront f(d);
+    f.num_scenes = B;
+    int32_t* h_flag = reinterpret_cast<int32_t*>(static_cast<char*>(d->h_pinned) + 64);      // range flag landing word
+    const bool plan_fits = f.carve(cv);
+    float* xyz = cv.take<float>((size_t)n * 3);
+    float* scale = cv.take<float>((size_t)n * 3);
+    float* prob = cv.take<float>((size_t)n);
+    int32_t* cls = cv.take<int32_t>((size_t)n);
+    int32_t* d_flag = cv.take<int32_t>(64);
+    if (!plan_fits || !xyz || !scale || !prob || !cls || !d_flag) return fixed_part_too_small(r, cv.off);
+    rc = f.run(d_flag, r, clock, stream);        // wait 1: level counts, and with them the scenes' row ranges and bounds
+    if (rc != CV_OK) return rc;
+
+    // ---- per scene: row range, corner, grid shape
+    cv_decode_scene_job jobs[CV_MAX_SCENES];
+    size_t cells[CV_MAX_SCENES], grid_floats = 0, vote_ws_b = 256, dec_ws_b = 0;
+    const int32_t* hb = f.h_bounds();
+    for (int b = 0; b < B; ++b) {
+        // (ranges checked by the front, behind its wait; one scene: all rows, the one-scene call's bounds)
+        const int32_t* w = hb + 16 * b;
+        const long long first = B > 1 ? w[0] : 0, end = B > 1 ? w[1] : n;
+        float mn[3], mx[3];
+        std::memcpy(mn, B > 1 ? reinterpret_cast<const float*>(w + 2) : f.h_minmax, sizeof(mn));
+        std::memcpy(mx, B > 1 ? reinterpret_cast<const float*>(w + 5) : f.h_minmax + 3, sizeof(mx));
+        cv_decode_scene_job& j = jobs[b];
+        rc = cv_hv_grid_dims_f32(mn, mx, d->res, j.dims);
+        if (rc != CV_OK) return rc;
+        for (int k = 0; k < 3; ++k) { j.corner[k] = mn[k]; r->corner[b][k] = mn[k]; r->dims[b][k] = j.dims[k]; }
+        j.row0 = first; j.n = end - first;
+        r->row0[b] = first; r->rows[b] = end - first;
+        cells[b] = (size_t)j.dims[0] * j.dims[1] * j.dims[2];
+        grid_floats += cv_align_up(6 * cells[b], 64);
+        vote_ws_b = std::max(vote_ws_b, cv_hv_forward_workspace_bytes(j.n, d->num_rots, j.dims, d->vote_algo));
+        dec_ws_b += cv_decode_workspace_bytes(j.dims, j.n, M);
+    }
+
+    // ---- what depends on the level sizes and the grid shapes: one arena, ONE vote workspace (the largest scene's: the votes
+    // run one after another on the stream), B decode carves, B grid triples resident together
+    const size_t arena_b = cv_net_arena_bytes(d->bufs, d->n_bufs, f.rows, 5);
+    char* arena = cv.take<char>(arena_b);
+    char* conv_ws = cv.take<char>(f.conv_ws_b);
+    char* vote_ws = cv.take<char>(vote_ws_b);
+    char* dec_ws = cv.take<char>(dec_ws_b);
+    float* grids = d->d_grids ? d->d_grids : cv.take<float>(grid_floats);
+    r->needed_ws_bytes = cv.off + 4096;
+    r->needed_grid_floats = grid_floats;
+    CV_REQUIRE(arena && conv_ws && vote_ws && dec_ws && grids, CV_ENOMEM, "scene workspace too small (needs %zu bytes)", r->needed_ws_bytes);
+    CV_REQUIRE(!d->d_grids || d->grid_capacity_floats >= grid_floats, CV_ENOMEM, "grid buffer too small (needs %zu floats)", grid_floats);
+    for (int b = 0; b < B; ++b) {
+        jobs[b].d_grid_obj = grids;
+        jobs[b].d_grid_rot = grids + cells[b];
+        jobs[b].d_grid_scale = grids + 3 * cells[b];
+        r->d_grid_obj[b] = grids; r->d_grid_rot[b] = grids + cells[b]; r->d_grid_scale[b] = grids + 3 * cells[b];
+        grids += cv_align_up(6 * cells[b], 64);
+    }
+
+    // ---- network forward and head over all rows
+    const void* ext_ptr[2] = {d->d_feats, d->d_out_feats};
+    const int ext_ld[2] = {d->feats_ld, d->out_ld};
+    rc = cv_net_run_ex(d->ops, d->n_ops, d->bufs, d->n_bufs, f.rows, 5, arena, arena_b, ext_ptr, ext_ld, f.maps, CV_NET_MAP_SLOTS,
+                       f.perms, CV_NET_PERM_SLOTS, conv_ws, f.conv_ws_b, d->use_range_flag ? d_flag : nullptr, /* plan_maps */ true, stream);
+    if (rc != CV_OK) return rc;
+    clock.lap(1);
+    CV_HIP_CHECK(clock.mark(1));
+    rc = cv_head_joint_f32(d->d_out_feats, n, d->out_ld, d->nclasses, d->log_scale, xyz, scale, prob, cls, stream);
+    if (rc != CV_OK) return rc;
+    if (d->use_range_flag) CV_HIP_CHECK(hipMemcpyAsync(h_flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    r->d_xyz = xyz; r->d_scale = scale; r->d_prob = prob; r->d_class = cls;
+    CV_HIP_CHECK(clock.mark(2));
+
+    // ---- B votes, each on its scene's rows, corner and shape; then one decode over the scene axis
+    const float* v_xyz = d->d_xyz_in ? d->d_xyz_in : xyz;
+    const float* v_scale = d->d_scale_in ? d->d_scale_in : scale;
+    const float* v_prob = d->d_prob_in ? d->d_prob_in : prob;
+    const int32_t* v_cls = d->d_class_in ? d->d_class_in : cls;
+    for (int b = 0; b < B; ++b) {
+        const cv_decode_scene_job& j = jobs[b];
+        const float* p = d->d_points + j.row0 * 3;
+        const float *px = v_xyz + j.row0 * 3, *ps = v_scale + j.row0 * 3, *pp = v_prob + j.row0;
+        // (the workspace as the single call sizes it for this scene)
+        const size_t ws_b = std::max<size_t>(cv_hv_forward_workspace_bytes(j.n, d->num_rots, j.dims, d->vote_algo), 256);
+        rc = d->peak_quotients
+                 ? cv_hv_forward_peaks_f32(p, px, ps, pp, j.n, d->res, d->num_rots, j.corner, j.dims, j.d_grid_obj,
+                                           const_cast<float*>(j.d_grid_rot), const_cast<float*>(j.d_grid_scale), vote_ws, ws_b,
+                                           d->vote_algo, d->decode.thresh_high, stream)
+                 : cv_hv_forward_f32(p, px, ps, pp, j.n, d->res, d->num_rots, j.corner, j.dims, j.d_grid_obj,
+                                     const_cast<float*>(j.d_grid_rot), const_cast<float*>(j.d_grid_scale), vote_ws, ws_b, d->vote_algo,
+                                     stream);
+        if (rc != CV_OK) return rc;
+    }
+    CV_HIP_CHECK(clock.mark(3));
+    clock.lap(2);
+    cv_decode_params prm = d->decode;
+    prm.max_iters = M;
+    const DecodeCall dc{nullptr, nullptr, nullptr, nullptr, nullptr, d->res, d->d_points, v_xyz, v_prob, v_cls, 0, &prm, 0, dec_ws, dec_ws_b,
+                        r->n_cand, d->h_cand_idx, d->h_verdict, r->n_boxes, d->h_boxes, d->h_scores, d->h_classes, r->truncated, stream,
+                        d->events[4]};
+    rc = cv_decode_scenes_run(dc, jobs, B);       // wait 2
+    if (rc != CV_OK) return rc;
+    r->range_flag = d->use_range_flag ? *h_flag : 0;
+
+    // ---- per scene, per class NMS on the host
+    for (int b = 0; b < B; ++b) {
+        rc = nms_per_class(d, r->n_boxes[b], d->h_boxes + (size_t)b * M * 24, d->h_scores + (size_t)b * M, d->h_classes + (size_t)b * M,
+                           d->h_pick + (size_t)b * M);
+        if (rc < 0) return rc;
+        r->n_det[b] = rc;
+    }
+    clock.lap(3);
+    return CV_OK;
+}
+
+size_t cv_sizeof_scenes_desc(void) { return sizeof(cv_scenes_desc); }
+size_t cv_sizeof_scenes_result(void) { return sizeof(cv_scenes_result); }
 
 // eval_separate.py:162-264 as one call: the coordinate plan once, the K programs on it one after another (one shared arena:
 // they are ordered on the stream) or, with models_per_pass, as launches over a model axis (cv_net_run_models_f32), K heads into [K][n] arrays, ONE vote and ONE decode over the category axis, NMS per category.

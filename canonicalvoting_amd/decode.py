@@ -124,6 +124,56 @@ def decode_boxes_categories(grid_obj, grid_rot, grid_scale, scan_points, xyz_pre
                  p, mutate_grid, allow_truncation)
 
 
+def decode_boxes_scenes(grids, corners, row_ranges, scan_points, xyz_pred, prob_pred, class_pred, res,
+                        thresh_high=thresh_high, thresh_low=thresh_low, valid_ratio=valid_ratio, elimination=elimination,
+                        prob_thresh=0.3, err_thresh=0.3, separate_variant=False, max_candidates=512, mutate_grid=False):
+    """decode_boxes over B scenes with ONE host sync (cv_decode_scenes_f32).  ``grids``: B triples (grid_obj [X,Y,Z],
+    grid_rot [X,Y,Z,2], grid_scale [X,Y,Z,3]) of any shapes, ``corners``: B grid origins, ``row_ranges``: B (first, end) row
+    ranges of the shared scan_points / xyz_pred [N,3], prob_pred / class_pred [N].  Returns a list of B dicts, entry b exactly
+    what ``decode_boxes(..., allow_truncation=True)`` returns for scene b's grids and rows alone: a walk that fills
+    ``max_candidates`` comes back capped and marked ``truncated`` (the caller redoes that scene)."""
+    L = _lib.lib()
+    B = len(grids)
+    dev = scan_points.device
+    for t, name in [(scan_points, "scan_points"), (xyz_pred, "xyz_pred"), (prob_pred, "prob_pred")] + [
+            (g, "grids[%d][%d]" % (b, i)) for b, tri in enumerate(grids) for i, g in enumerate(tri)]:
+        if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32:
+            raise RuntimeError("%s must be a contiguous float32 CUDA tensor" % name)
+    if not (len(corners) == B and len(row_ranges) == B):
+        raise RuntimeError("decode_boxes_scenes: one corner and one row range per grid triple")
+    cls = class_pred.to(torch.int32).contiguous()
+    p = _params(thresh_high, thresh_low, valid_ratio, elimination, prob_thresh, separate_variant, max_candidates, err_thresh)
+    M = p.max_iters
+    jobs = (_lib.DecodeSceneJob * max(B, 1))()
+    for b in range(B):
+        j = jobs[b]
+        j.d_grid_obj, j.d_grid_rot, j.d_grid_scale = (ptr(g) for g in grids[b])
+        j.dims = (ctypes.c_int * 3)(*grids[b][0].shape)
+        j.corner = (ctypes.c_float * 3)(*[float(v) for v in corners[b]])
+        j.row0, j.n = int(row_ranges[b][0]), int(row_ranges[b][1]) - int(row_ranges[b][0])
+        if not 0 <= j.row0 <= j.row0 + j.n <= scan_points.shape[0]:
+            raise RuntimeError("decode_boxes_scenes: row range %d leaves the shared arrays" % b)
+    rows = max(B, 1)
+    ws = _lib.scratch(dev, "decode", max(L.cv_decode_scenes_workspace_bytes(jobs, B, M), 256))
+    n_cand, n_boxes, truncated = np.zeros(rows, np.int32), np.zeros(rows, np.int32), np.zeros(rows, np.int32)
+    cand = np.zeros((rows, M), np.int64)
+    verdict = np.zeros((rows, M), np.int32)
+    boxes = np.zeros((rows, M, 8, 3), np.float32)
+    scores = np.zeros((rows, M), np.float32)
+    classes = np.zeros((rows, M), np.int32)
+    with torch.cuda.device(dev):
+        rc = L.cv_decode_scenes_f32(jobs, B, ctypes.c_float(float(res)), ptr(scan_points), ptr(xyz_pred), ptr(prob_pred), ptr(cls),
+                                    ctypes.byref(p), 1 if mutate_grid else 0, ptr(ws), ws.numel(),
+                                    n_cand.ctypes.data_as(_lib.c_int_p), cand.ctypes.data_as(_lib.c_i64_p),
+                                    verdict.ctypes.data_as(_lib.c_i32_p), n_boxes.ctypes.data_as(_lib.c_int_p),
+                                    boxes.ctypes.data_as(_lib.c_float_p), scores.ctypes.data_as(_lib.c_float_p),
+                                    classes.ctypes.data_as(_lib.c_i32_p), truncated.ctypes.data_as(_lib.c_int_p), stream(dev))
+    _lib.check(rc, "cv_decode_scenes_f32")
+    return [dict(boxes=boxes[b, :n_boxes[b]].copy(), scores=scores[b, :n_boxes[b]].copy(), classes=classes[b, :n_boxes[b]].copy(),
+                 cand_idx=cand[b, :n_cand[b]].copy(), verdict=verdict[b, :n_cand[b]].copy(), truncated=bool(truncated[b]))
+            for b in range(B)]
+
+
 SUPPORT = {"confident": 1, "inside": 0}      # instance_labels' ``support`` -> cv_decode_instances_f32's confident_only
 
 

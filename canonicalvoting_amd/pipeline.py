@@ -182,16 +182,19 @@ class _SceneHost:
     [M] candidates, [K, M] with a category axis - the device scratch size the last calls needed (``ws_hint``) and where the
     last call's host time went (``last_host_us``)."""
 
-    def __init__(self, M, K=None):
-        self.M, self.K = M, K
+    def __init__(self, M, K=None, B=None):
+        self.M, self.K, self.B = M, K, B
         rows = (M,) if K is None else (K, M)
-        self.pinned = torch.empty(256 if K is None else 64 + 64 * _lib.MAX_CATEGORIES, dtype=torch.uint8).pin_memory()
+        if B is not None:   # joint over a scene axis (detect_scenes_c): [B, M]
+            rows = (B, M)
+        pinned = 256 + 64 * _lib.MAX_SCENES if B is not None else 256 if K is None else 64 + 64 * _lib.MAX_CATEGORIES
+        self.pinned = torch.empty(pinned, dtype=torch.uint8).pin_memory()
         self.cand = np.zeros(rows, np.int64)
         self.verdict = np.zeros(rows, np.int32)
         self.boxes = np.zeros(rows + (8, 3), np.float32)
         self.scores = np.zeros(rows, np.float32)
         if K is None:       # joint: the boxes' classes and the NMS picks
-            self.classes, self.pick = np.zeros(M, np.int32), np.zeros(M, np.int32)
+            self.classes, self.pick = np.zeros(rows, np.int32), np.zeros(rows, np.int32)
         else:               # separate: (category, box) of every detection
             self.det_cat, self.det_box = np.zeros(K * M, np.int32), np.zeros(K * M, np.int32)
         self.ws_hint = 0
@@ -203,14 +206,14 @@ _model_tables = {}
 _scene_lock = threading.Lock()
 
 
-def _host(dev, max_candidates, K=None):
-    """the _SceneHost of the calling thread's current stream and of the mode (K None: joint); regrown for more candidates or
-    categories"""
-    key = (dev.index, _lib.stream_handle(dev), K is not None)
+def _host(dev, max_candidates, K=None, B=None):
+    """the _SceneHost of the calling thread's current stream and of the mode (K None: joint; B: joint over a scene axis of
+    up to B scenes); regrown for more candidates, categories or scenes"""
+    key = (dev.index, _lib.stream_handle(dev), K is not None) + (() if B is None else ("scenes",))
     with _scene_lock:
         host = _hosts.get(key)
-        if host is None or host.M < max_candidates or (K is not None and host.K < K):
-            host = _hosts[key] = _SceneHost(max_candidates, K)
+        if host is None or host.M < max_candidates or (K is not None and host.K < K) or (B is not None and host.B < B):
+            host = _hosts[key] = _SceneHost(max_candidates, K, B)
     return host
 
 
@@ -417,6 +420,83 @@ def detect_scene_c(model, hv, coords4, feats, res, nclasses=9, log_scale=True, s
         dets, raw = decode.detect(hv, coords4[:, 1:], pred[0], pred[1], pred[2], pred[3], res, nclasses,
                                   scan_points=scan_points, **decode_kw)
     return dets, raw, yy.F
+
+
+def detect_scenes_c(model, hv, coords4, feats, res, num_scenes, scan_points=None, predictions=None, keep=None, policy=None,
+                    events=None, nclasses=9, log_scale=True, max_candidates=512, adaptive_split=False, **decode_kw):
+    """detect_scene_c for ``num_scenes`` scans in ONE C call (cv_detect_scenes_f32): ``coords4`` / ``feats`` are the scans
+    collated one after another with batch indices 0..B-1 (non-decreasing), ``scan_points`` and ``predictions`` cover all rows.
+    One coordinate plan, one network program and one head launch over all rows, a vote per scene, one decode over the scene
+    axis: two host waits per batch.  Scene b's vote grids, decode and detections are the bits detect_scene_c gives for that
+    scan alone when ``predictions`` are given; on the network's own predictions they follow the batched network output,
+    which agrees with the scan-alone output within the network's tolerance.  A raised fp16-range flag redoes the whole batch
+    call by call on the bf16 triples, a decode walk beyond ``max_candidates`` that scene's decode, as detect_scene_c does.
+    ``keep``: a list that receives B dicts, each what detect_scene_c's ``keep`` holds for that scene (scene_instances takes
+    them unchanged).  Returns ([(detections, raw decode dict)] per scene, network output [N, C])."""
+    dev = feats.device
+    B = int(num_scenes)
+    n = coords4.shape[0]
+    if scan_points is None:
+        scan_points = (coords4[:, 1:].to(dev) * res).float().contiguous()
+    pieces = model.eval_pieces()
+    program = model._program(dev, pieces)
+    coords4 = coords4.to(device=dev, dtype=torch.int32).contiguous()
+    feats = feats.contiguous()
+    y = torch.empty((n, model.final.out_channels), dtype=torch.float32, device=dev)
+    host = _host(dev, max_candidates, B=max(B, 1))
+    d, r = _lib.ScenesDesc(), _lib.ScenesResult()
+    d.num_scenes = B
+    _fill_scene_desc(d.scene, model, hv, coords4, feats, scan_points, res, policy, pieces, max(model.PLANES), log_scale)
+    if predictions is not None:
+        px, ps, pp, pc = predictions
+        pc = pc.to(torch.int32).contiguous()
+        d.scene.d_xyz_in, d.scene.d_scale_in, d.scene.d_prob_in, d.scene.d_class_in = ptr(px), ptr(ps), ptr(pp), ptr(pc)
+    _fill_joint_desc(d.scene, host, program, y, nclasses, decode_kw, adaptive_split, events, keep)
+    call = lambda _d, _r, s: _lib.lib().cv_detect_scenes_f32(ctypes.byref(d), ctypes.byref(r), s)
+    ws = _call_growing(call, "cv_detect_scenes_f32", d.scene, r, dev, "scene_call", host.ws_hint)
+    host.ws_hint = max(host.ws_hint, int(r.needed_ws_bytes))
+    host.last_host_us = tuple(r.host_us)
+    yy = y
+    if r.range_flag:        # rare: a convolution input beyond the fp16 range - the whole batch again on the bf16 triples
+        model.range_fallbacks = getattr(model, "range_fallbacks", 0) + 1
+        with torch.no_grad(), scene_policy(policy):
+            yy = model.program_forward(ME.SparseTensor(feats, coords4, device=dev), pieces=3).F
+    net_pred = head_joint(yy, nclasses, log_scale) if r.range_flag and predictions is None else None
+    view = lambda p, shape, dt=torch.float32: _device_view(p, shape, dt, dev, ws)
+    out, head = [], None
+    if keep is not None:
+        del keep[:]
+    for b in range(B):
+        lo, hi = int(r.row0[b]), int(r.row0[b] + r.rows[b])
+        kb = None
+        if keep is not None:
+            kb = {}
+            _keep_begin(kb, res)
+            keep.append(kb)
+            if predictions is not None:
+                kb["decode_prob"] = pp[lo:hi]
+        if r.range_flag or r.truncated[b]:
+            # this scene's vote and decode call by call, on its rows
+            pred = [t[lo:hi] for t in (predictions if predictions is not None else net_pred or head_joint(yy, nclasses, log_scale))]
+            with torch.no_grad(), scene_policy(policy):
+                dets, raw = decode.detect(hv, coords4[lo:hi, 1:], pred[0], pred[1], pred[2], pred[3], res, nclasses,
+                                          scan_points=scan_points[lo:hi], **decode_kw)
+            out.append((dets, raw))
+            continue
+        k, m = r.n_boxes[b], r.n_cand[b]
+        raw = dict(boxes=host.boxes[b, :k].copy(), scores=host.scores[b, :k].copy(), classes=host.classes[b, :k].copy(),
+                   cand_idx=host.cand[b, :m].copy(), verdict=host.verdict[b, :m].copy(), truncated=False)
+        dets = [(int(raw["classes"][i]), raw["boxes"][i], float(raw["scores"][i])) for i in host.pick[b, :r.n_det[b]]]
+        if kb is not None:
+            X, Y, Z = r.dims[b]
+            if head is None:
+                head = [view(r.d_xyz, (n, 3)), view(r.d_scale, (n, 3)), view(r.d_prob, (n,)), view(r.d_class, (n,), torch.int32)]
+            kb.update(y=y[lo:hi], rows=(lo, hi), dims=(X, Y, Z), corner=tuple(r.corner[b]), level_rows=list(r.level_rows),
+                      grids=(view(r.d_grid_obj[b], (X, Y, Z)), view(r.d_grid_rot[b], (X, Y, Z, 2)),
+                             view(r.d_grid_scale[b], (X, Y, Z, 3))),
+                      net_pred=tuple(t[lo:hi] for t in head), raw=raw)
+        out.append((dets, raw))
+    return out, yy
 
 
 def detect_points(model, hv, points, feats, res, predictions=None, return_inverse=False, **kw):

@@ -57,7 +57,10 @@ extern "C" {
  *    Still 6: cv_row_loss_fwd_f32 / cv_row_loss_bwd_f32 (cv_row_loss_desc) with cv_row_loss_workspace_bytes,
  *    cv_row_loss_chunk_rows and cv_sizeof_row_loss_desc, the per-row training losses of both models (masked squared errors of
  *    the chosen head and the cross entropy) and the validation form of the joint one (additive: no struct or signature moved).
- *    Still 6: a trailing cv_conv_desc.valid_words (appended: a zero-initialised descriptor runs as before). */
+ *    Still 6: a trailing cv_conv_desc.valid_words (appended: a zero-initialised descriptor runs as before).
+ *    Still 6: the scene axis - cv_decode_scenes_f32 (cv_decode_scene_job) with cv_decode_scenes_workspace_bytes,
+ *    cv_detect_scenes_f32 (cv_scenes_desc, cv_scenes_result) and their cv_sizeof_* helpers (additive: no struct or signature
+ *    moved). */
 #define CV_ABI_VERSION 6
 int cv_abi_version(void);
 const char* cv_last_error(void);
@@ -212,6 +215,27 @@ int cv_decode_cat_f32(float* d_grid_obj, const float* d_grid_rot, const float* d
                       const int32_t* d_class, int64_t n, int num_cats, const cv_decode_params* params, int mutate_grid, void* d_ws,
                       size_t ws_bytes, int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes, float* h_boxes,
                       float* h_scores, int32_t* h_classes, int* h_truncated, void* stream);
+
+/* cv_decode_f32 over B = num_scenes scenes with ONE host wait.  Unlike the categories above, scenes share nothing but the
+ * parameters: job b has its own grid shape, corner and grid triple, and its points are the rows [row0, row0 + n) of the shared
+ * d_points / d_xyz [.][3], d_prob / d_class [.] arrays (d_class is required).  1 <= B <= CV_MAX_SCENES.  d_ws:
+ * cv_decode_scenes_workspace_bytes(jobs, B, max_iters) bytes - the sum of the jobs' cv_decode_workspace_bytes, carved in job
+ * order.  Scene b's host outputs land at h_n_cand[b], h_n_boxes[b], h_truncated[b] (may be NULL) and the arrays at
+ * b * max_iters entries (h_boxes: b * max_iters * 24 floats): exactly what cv_decode_f32 returns for that scene alone,
+ * mutate_grid included.  The B greedy walks run side by side, each on the walker workgroup the single call would choose for
+ * its grid.  CV_EINVAL (the message names the scene) before anything is launched.  Synchronises once. */
+#define CV_MAX_SCENES 16
+typedef struct cv_decode_scene_job {
+    float* d_grid_obj; const float* d_grid_rot; const float* d_grid_scale;      /* [X][Y][Z] (+[2], [3]) */
+    int dims[3];
+    float corner[3];
+    int64_t row0, n;              /* the scene's rows of the shared arrays */
+} cv_decode_scene_job;
+size_t cv_decode_scenes_workspace_bytes(const cv_decode_scene_job* jobs, int num_scenes, int max_iters);
+int cv_decode_scenes_f32(const cv_decode_scene_job* jobs, int num_scenes, float res, const float* d_points, const float* d_xyz,
+                         const float* d_prob, const int32_t* d_class, const cv_decode_params* params, int mutate_grid, void* d_ws,
+                         size_t ws_bytes, int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes, float* h_boxes,
+                         float* h_scores, int32_t* h_classes, int* h_truncated, void* stream);
 
 /* Instance labels: which scan points each of a list of boxes owns (eval_joint.py:231-245: bbox_mask_world and mask, which
  * the decode reduces to statistics per candidate and drops).  A box is named by the flat grid cell the decode examined
@@ -999,6 +1023,43 @@ typedef struct cv_scene_result {
 int cv_detect_scene_f32(const cv_scene_desc* desc, cv_scene_result* result, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * B scans in ONE call: cv_detect_scene_f32 over a scene axis.  `scene` describes the batched tensor: d_coords4 [n][4] with the
+ * batch column non-decreasing and in [0, num_scenes) (scans collated one after another), d_feats / d_points / d_out_feats and
+ * the optional d_*_in predictions over all n rows.  One launch reduces the per-scene row ranges and bounds, ONE coordinate
+ * plan and ONE network program run over all rows, one head launch, then per scene a vote on its row range, corner and grid
+ * shape (one after another on the stream) and ONE decode over the scene axis (cv_decode_scenes_f32).  The host waits twice
+ * per BATCH (level counts - the per-scene ranges and bounds arrive with them - and the decode results); NMS per scene and class
+ * on the host.  Scene b is what cv_detect_scene_f32 returns for that scan alone in everything but the network output, which
+ * agrees within the network's own tolerance (the batched plan orders and splits the convolutions' sums differently);
+ * num_scenes == 1 runs cv_detect_scene_f32's launches and gives its bits (like that call it does not read the batch column).
+ * Host result arrays hold num_scenes blocks: scene b's entries at b * max_candidates (h_boxes: b * max_candidates * 24
+ * floats), so their capacity is num_scenes * max_candidates.  h_pinned: >= 256 + 64 * num_scenes bytes.  d_grids (optional):
+ * the scenes' grid triples one after another, each rounded up to 64 floats - result.needed_grid_floats says how many.
+ * CV_EINVAL: num_scenes outside 1..CV_MAX_SCENES and every other bad field before the first device call; after the first
+ * wait a scene without rows or a batch column that is not sorted / leaves [0, num_scenes) (the message names the scene).
+ * CV_ENOMEM / needed_ws_bytes as cv_detect_scene_f32.
+ * ------------------------------------------------------------------------ */
+typedef struct cv_scenes_desc {
+    cv_scene_desc scene;
+    int num_scenes;
+} cv_scenes_desc;
+typedef struct cv_scenes_result {
+    /* per scene */
+    int n_cand[CV_MAX_SCENES], n_boxes[CV_MAX_SCENES], n_det[CV_MAX_SCENES], truncated[CV_MAX_SCENES];
+    int dims[CV_MAX_SCENES][3];
+    float corner[CV_MAX_SCENES][3];
+    long long row0[CV_MAX_SCENES], rows[CV_MAX_SCENES];       /* the scene's rows of the batched tensor */
+    float* d_grid_obj[CV_MAX_SCENES]; float* d_grid_rot[CV_MAX_SCENES]; float* d_grid_scale[CV_MAX_SCENES];
+    /* shared */
+    int range_flag, duplicates, out_of_window, scenes_in_flight;
+    long long level_rows[5];
+    size_t needed_ws_bytes, needed_grid_floats;
+    float* d_xyz; float* d_scale; float* d_prob; int32_t* d_class;      /* the network's head outputs over all rows */
+    float host_us[4];              /* as cv_scene_result, per batch */
+} cv_scenes_result;
+int cv_detect_scenes_f32(const cv_scenes_desc* desc, cv_scenes_result* result, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * One call per SEPARATE-mode scene: eval_separate.py:162-264 (K per-category 8-channel models on one scan) behind one entry
  * point: the coordinate plan once, K network programs (cv_net_run_f32, one after another on the stream, sharing the plan and
  * one arena; or batched over a model axis, see models_per_pass), K heads (cv_head_separate_f32), ONE vote over the category axis (cv_hv_forward_cat_f32), ONE decode over it
@@ -1167,6 +1228,9 @@ size_t cv_sizeof_points_desc(void);
 size_t cv_sizeof_points_separate_desc(void);
 size_t cv_sizeof_points_result(void);
 size_t cv_sizeof_points_separate_result(void);
+size_t cv_sizeof_decode_scene_job(void);
+size_t cv_sizeof_scenes_desc(void);
+size_t cv_sizeof_scenes_result(void);
 
 #ifdef __cplusplus
 }

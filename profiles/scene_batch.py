@@ -1,0 +1,201 @@
+#!/usr/bin/env python
+"""What B scans per C call (pipeline.detect_scenes_c / cv_detect_scenes_f32) buy a host with ONE thread.
+
+    python profiles/scene_batch.py [--points 8000 20000 80000] [--batches 1 2 4 8] [--reps 3] [--out profiles/scene_batch/batch_rate.txt]
+
+Synthetic scans with teacher predictions (bench.py --predictions teacher).  Per scan size, in the same process:
+  * detect_scenes_c with B in --batches from one host thread: scenes/s (median and min..max of --reps repetitions), host
+    microseconds per stage and per CALL (plan + wait, network enqueue, head + votes enqueue, decode + wait + NMS), kernel launches per scene
+    (counted once with the torch profiler; "n/a" where it does not see the library's launches);
+  * baseline 1: a loop of detect_scene_c from one thread;
+  * baseline 2: seven threads of detect_scene_c, a stream each, under policy_for_scenes_in_flight(7) (how bench.py gets its
+    headline).
+Nothing here is a promise: the file holds what was measured."""
+import argparse
+import os
+import statistics
+import sys
+import threading
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from canonicalvoting_amd import pipeline  # noqa: E402
+from canonicalvoting_amd.hough import HoughVoting  # noqa: E402
+from canonicalvoting_amd.minkunet import MinkUNet34C  # noqa: E402
+from canonicalvoting_amd.synth import make_scene, synth_predictions  # noqa: E402
+
+RES, NUM_ROTS, DISTINCT = 0.03, 120, 4
+
+
+def scans(n, dev):
+    out = []
+    for k in range(DISTINCT):
+        sc = make_scene(100 + k, n_points=n)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        c3 = torch.from_numpy(sc.coords).int().to(dev)
+        out.append(dict(c3=c3, feats=(t(sc.feats) * 2 - 1).contiguous(), pts=(c3 * RES).float().contiguous(),
+                        pred=[t(a) for a in synth_predictions(sc)]))
+    return out
+
+
+def one(s, dev):
+    c4 = torch.cat([torch.zeros((len(s["c3"]), 1), dtype=torch.int32, device=dev), s["c3"]], 1).contiguous()
+    return dict(c4=c4, feats=s["feats"], pts=s["pts"], pred=(s["pred"][0], s["pred"][1], s["pred"][2], s["pred"][3].int()))
+
+
+def collate(ss, dev):
+    c4 = torch.cat([torch.cat([torch.full((len(s["c3"]), 1), b, dtype=torch.int32, device=dev), s["c3"]], 1)
+                    for b, s in enumerate(ss)]).contiguous()
+    cat = lambda f: torch.cat([f(s) for s in ss]).contiguous()
+    pred = tuple(cat(lambda s, i=i: s["pred"][i]) for i in range(4))
+    return dict(c4=c4, feats=cat(lambda s: s["feats"]), pts=cat(lambda s: s["pts"]), pred=pred[:3] + (pred[3].int(),))
+
+
+def launches(fn):
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        n = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
+                and "memcpy" not in e.name.lower() and "memset" not in e.name.lower())
+        return n if n else None
+    except Exception:       # noqa: BLE001
+        return None
+
+
+def rate(fn, scenes_per_call, seconds, reps):
+    """median and spread of `reps` repetitions of ~`seconds` each; returns (median, lo, hi) scenes/s"""
+    fn()
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    calls = max(3, int(seconds / max(time.perf_counter() - t0, 1e-4)))
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            fn()
+        torch.cuda.synchronize()
+        out.append(scenes_per_call * calls / (time.perf_counter() - t0))
+    return statistics.median(out), min(out), max(out)
+
+
+def threads_rate(model, dev, items, S, seconds, reps):
+    pol = pipeline.policy_for_scenes_in_flight(S)
+    results, errors = [], []
+    gate = threading.Barrier(S + 1)
+    per_thread = [0]
+
+    def worker(i):
+        try:
+            torch.cuda.set_device(dev)
+            hv = HoughVoting(RES, NUM_ROTS)
+            with torch.cuda.stream(torch.cuda.Stream(dev)):
+                run = lambda k: pipeline.detect_scene_c(model, hv, items[k % len(items)]["c4"], items[k % len(items)]["feats"], RES,
+                                                        scan_points=items[k % len(items)]["pts"],
+                                                        predictions=items[k % len(items)]["pred"], policy=pol)
+                for k in range(3):
+                    run(i + k)
+                for _ in range(reps + 1):
+                    gate.wait()
+                    for k in range(per_thread[0]):
+                        run(i + k)
+                    torch.cuda.current_stream().synchronize()
+                    gate.wait()
+        except BaseException as e:      # noqa: BLE001
+            errors.append(repr(e))
+            gate.abort()
+
+    th = [threading.Thread(target=worker, args=(i,)) for i in range(S)]
+    for t in th:
+        t.start()
+    try:
+        per_thread[0] = 4
+        for rep in range(reps + 1):     # the first round sizes the others
+            gate.wait()
+            t0 = time.perf_counter()
+            gate.wait()
+            dt = time.perf_counter() - t0
+            if rep == 0:
+                per_thread[0] = max(4, int(4 * seconds / dt))
+            else:
+                results.append(S * per_thread[0] / dt)
+            if rep == 0:
+                results.clear()
+    except threading.BrokenBarrierError:
+        pass
+    for t in th:
+        t.join()
+    if errors:
+        raise RuntimeError(errors[0])
+    return statistics.median(results), min(results), max(results)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--points", type=int, nargs="+", default=[8000, 20000, 80000])
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 2, 4, 8])
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--seconds", type=float, default=1.5, help="length of one repetition")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "scene_batch", "batch_rate.txt"))
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model = MinkUNet34C(3, 64).to(dev).eval()
+    hv = HoughVoting(RES, NUM_ROTS)
+    lines = ["# profiles/scene_batch.py: %s, teacher predictions, %d repetitions of ~%.1f s each; scenes/s as median (min..max)"
+             % (torch.cuda.get_device_name(0), a.reps, a.seconds),
+             "# host us per CALL: plan + wait | network enqueue | head + votes enqueue | decode + wait + NMS"]
+    fmt = lambda r: "%8.1f (%7.1f..%7.1f)" % r
+    for n in a.points:
+        ss = scans(n, dev)
+        items = [one(s, dev) for s in ss]
+        k = [0]
+
+        def loop():
+            it = items[k[0] % len(items)]
+            k[0] += 1
+            pipeline.detect_scene_c(model, hv, it["c4"], it["feats"], RES, scan_points=it["pts"], predictions=it["pred"])
+
+        base = rate(loop, 1, a.seconds, a.reps)
+        lines.append("points %6d  detect_scene_c loop, one thread           %s scenes/s  launches/scene %s" % (n, fmt(base), launches(loop)))
+        print(lines[-1], flush=True)
+        for B in a.batches:
+            batches = [collate([ss[(j + b) % DISTINCT] for b in range(B)], dev) for j in range(DISTINCT)]
+
+            def call():
+                it = batches[k[0] % len(batches)]
+                k[0] += 1
+                pipeline.detect_scenes_c(model, hv, it["c4"], it["feats"], RES, B, scan_points=it["pts"], predictions=it["pred"])
+
+            r = rate(call, B, a.seconds, a.reps)
+            host = pipeline._host(dev, 512, B=B)
+            us = [0.0] * 4
+            for _ in range(8):
+                call()
+                us = [u + v / 8 for u, v in zip(us, host.last_host_us)]
+            nl = launches(call)
+            lines.append("points %6d  detect_scenes_c B = %d, one thread          %s scenes/s  launches/scene %s  host us/call %s"
+                         % (n, B, fmt(r), "n/a" if nl is None else "%.1f" % (nl / B), " | ".join("%7.0f" % u for u in us)))
+            print(lines[-1], flush=True)
+            if B == 1:
+                spread = max(base[2] - base[1], r[2] - r[1])
+                lines.append("points %6d  B = 1 against the loop: %+.1f scenes/s (spread of the repetitions %.1f): %s"
+                             % (n, r[0] - base[0], spread, "not slower" if r[0] >= base[0] - spread else "SLOWER"))
+                print(lines[-1], flush=True)
+        t7 = threads_rate(model, dev, items, 7, a.seconds, a.reps)
+        lines.append("points %6d  detect_scene_c, seven threads, policy(7)      %s scenes/s" % (n, fmt(t7)))
+        print(lines[-1], flush=True)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -3,6 +3,7 @@
 decode -> NMS per scene, then mAP @0.25 / @0.5.  argparse instead of hydra (absent here).
 
     python scripts/eval_joint.py [--scenes 4] [--points 80000] [--weights joint.pth] [--teacher] [--raw-points [M]] [--instances]
+                                 [--scenes-per-call B]
 
 --teacher feeds the vote/decode stage with predictions synthesised from the labels (there is no trained
 checkpoint offline); the network forward still runs.
@@ -10,6 +11,8 @@ checkpoint offline); the network forward still runs.
 pipeline.detect_points_c: voxelised on the device, gathered (with the colour recentre) and detected in one C call.
 --instances (synthetic scenes only): after each scene, the scan points every detection owns and the ones inside its box
 (pipeline.scene_instances on the one-call scene's keep; with --raw-points also the raw points it owns).
+--scenes-per-call B (synthetic voxel scenes only): B scans per C call (pipeline.detect_scenes_c: one plan, one network program,
+one decode over the scene axis; two host waits per call instead of two per scan).  The default 1 is the one-scan path.
 """
 import argparse
 import os
@@ -59,6 +62,38 @@ def evaluate(model, dataset, res=0.03, teacher=False, nclasses=9, device="cuda",
     return {thr: calc_map.compute_map(pred_map_cls, gt_map_cls, thr) for thr in (0.25, 0.5)}
 
 
+def evaluate_batched(model, dataset, scenes_per_call, res=0.03, teacher=False, nclasses=9, device="cuda", instances=False):
+    """evaluate() with B = scenes_per_call scans per C call (pipeline.detect_scenes_c): the scans are collated with batch
+    indices 0..B-1, the last call of a pass may be short.  Vote, decode and NMS of a scan are those of the one-scan path."""
+    hv = HoughVoting(res)
+    pred_map_cls, gt_map_cls = {}, {}
+    loader = torch.utils.data.DataLoader(dataset, collate_fn=collate_fn, batch_size=scenes_per_call, shuffle=False)
+    index = 0
+    for ids, coords, feats, _, _, _ in loader:
+        B = len(ids)
+        feats = feats.to(device)
+        feats[:, -3:] = feats[:, -3:] * 2.0 - 1.0                             # eval_joint.py:167-168: colour columns only
+        coords = coords.to(device)
+        pts = (coords[:, 1:] * res).float().contiguous()
+        pred = None
+        if teacher:
+            per = [synth_predictions(dataset.scene(index + b)) for b in range(B)]
+            pred = tuple(torch.from_numpy(np.concatenate([p[i] for p in per])).to(device) for i in range(4))
+        keep = [] if instances else None
+        out, _ = pipeline.detect_scenes_c(model, hv, coords, feats, res, B, scan_points=pts, predictions=pred, keep=keep,
+                                          nclasses=nclasses)
+        for b, id_scan in enumerate(ids):
+            dets = out[b][0]
+            if instances:
+                lo, hi = keep[b]["rows"]
+                print("%s: %d detections" % (id_scan, len(dets)))
+                print("\n".join(pipeline.instances_report(dets, pipeline.scene_instances(keep[b], dets, pts[lo:hi], counts=True))))
+            pred_map_cls[id_scan] = dets
+            gt_map_cls[id_scan] = [(c, calc_map.gt_box(*p)) for c, p in dataset.gt(index + b)]
+        index += B
+    return {thr: calc_map.compute_map(pred_map_cls, gt_map_cls, thr) for thr in (0.25, 0.5)}
+
+
 def evaluate_raw(model, n_scenes, n_samples, seed0=100, res=0.03, teacher=False, nclasses=9, device="cuda", detections=None,
                  instances=False, **scene_kw):
     """the synthetic evaluation from raw clouds: one C call per scene (pipeline.detect_points_c voxelises, gathers - the
@@ -98,9 +133,13 @@ def main():
                     help="synthetic scenes as raw clouds of M samples: voxelise, gather and detect in one C call (pipeline.detect_points_c)")
     ap.add_argument("--instances", action="store_true",
                     help="print the scan points each detection owns and has inside its box (pipeline.scene_instances)")
+    ap.add_argument("--scenes-per-call", type=int, default=1, metavar="B",
+                    help="B scans per C call (pipeline.detect_scenes_c, 1..16); 1: one scan at a time, as before")
     a = ap.parse_args()
     if (a.raw_points or a.instances) and a.config:
         ap.error("--raw-points and --instances run on the synthetic scenes only")
+    if not 1 <= a.scenes_per_call <= 16 or (a.scenes_per_call > 1 and (a.raw_points or a.config)):
+        ap.error("--scenes-per-call takes 1..16 and runs on the synthetic voxel scenes only")
     cfg = load_config(a.config, category="all") if a.config else None
     model = MinkUNet34C(6 if (cfg and cfg.use_xyz) else 3, 6 * 9 + 9 + 1)
     if a.weights:
@@ -110,6 +149,9 @@ def main():
         res = evaluate(model, ScanNetXYZProbMultiDataset(cfg, training=False, augment=False), res=cfg.scannet_res)
     elif a.raw_points:
         res = evaluate_raw(model, a.scenes, a.raw_points, seed0=100, teacher=a.teacher, instances=a.instances)
+    elif a.scenes_per_call > 1:
+        res = evaluate_batched(model, SyntheticScanDataset(a.scenes, a.points, seed0=100), a.scenes_per_call, teacher=a.teacher,
+                               instances=a.instances)
     else:
         res = evaluate(model, SyntheticScanDataset(a.scenes, a.points, seed0=100), teacher=a.teacher, instances=a.instances)
     for thr, r in res.items():
