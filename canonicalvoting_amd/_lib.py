@@ -330,6 +330,12 @@ SIGNATURES = {
                                             ctypes.POINTER(DecodeParams), ctypes.c_int, vp, ctypes.c_size_t, c_int_p, c_i64_p,
                                             c_i32_p, c_int_p, c_float_p, c_float_p, c_i32_p, c_int_p, vp]),
     "cv_sizeof_decode_scene_job": (ctypes.c_size_t, []),
+    "cv_hv_forward_scenes_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(DecodeSceneJob), ctypes.c_int, ctypes.c_int,
+                                                               ctypes.c_int]),
+    "cv_hv_forward_scenes_f32": (ctypes.c_int, [ctypes.POINTER(DecodeSceneJob), ctypes.c_int, vp, vp, vp, vp, ctypes.c_float,
+                                                ctypes.c_int, vp, ctypes.c_size_t, ctypes.c_int, vp]),
+    "cv_hv_forward_peaks_scenes_f32": (ctypes.c_int, [ctypes.POINTER(DecodeSceneJob), ctypes.c_int, vp, vp, vp, vp, ctypes.c_float,
+                                                      ctypes.c_int, vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_float, vp]),
     "cv_detect_scenes_f32": (ctypes.c_int, [ctypes.POINTER(ScenesDesc), ctypes.POINTER(ScenesResult), vp]),
     "cv_sizeof_scenes_desc": (ctypes.c_size_t, []),
     "cv_sizeof_scenes_result": (ctypes.c_size_t, []),

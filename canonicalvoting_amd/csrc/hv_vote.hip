@@ -335,12 +335,12 @@ __device__ __forceinline__ T* cat_el(T* p, int64_t elems) {
     return p + (int64_t)blockIdx.y * elems;
 }
 
-__global__ __launch_bounds__(PREP_THREADS) void hv_prep_count(
+// (the bodies of the vote's kernels are device functions: the category kernels and the scene kernels - further down, behind
+// TilesLayout - differ only in where a workgroup finds its pointers)
+__device__ __forceinline__ void prep_count_body(
     const float* __restrict__ pts, const float* __restrict__ xyz, const float* __restrict__ scl,
-    int64_t n, float res, float corner_y, int Y, int* __restrict__ fy_out, int* __restrict__ ycount, CatStride ks) {
+    int64_t n, float res, float corner_y, int Y, int* __restrict__ fy_out, int* __restrict__ ycount) {
     __shared__ int lh[PREP_MAX_Y];
-    xyz = cat_el(xyz, 3 * ks.n); scl = cat_el(scl, 3 * ks.n);
-    fy_out = cat_ws(fy_out, ks.ws); ycount = cat_ws(ycount, ks.ws);
     const bool use_lds = Y <= PREP_MAX_Y;
     if (use_lds) {
         for (int i = threadIdx.x; i < Y; i += PREP_THREADS) lh[i] = 0;
@@ -360,6 +360,13 @@ __global__ __launch_bounds__(PREP_THREADS) void hv_prep_count(
         for (int i = threadIdx.x; i < Y; i += PREP_THREADS)
             if (lh[i]) atomicAdd(&ycount[i], lh[i]);
     }
+}
+__global__ __launch_bounds__(PREP_THREADS) void hv_prep_count(
+    const float* __restrict__ pts, const float* __restrict__ xyz, const float* __restrict__ scl,
+    int64_t n, float res, float corner_y, int Y, int* __restrict__ fy_out, int* __restrict__ ycount, CatStride ks) {
+    xyz = cat_el(xyz, 3 * ks.n); scl = cat_el(scl, 3 * ks.n);
+    fy_out = cat_ws(fy_out, ks.ws); ycount = cat_ws(ycount, ks.ws);
+    prep_count_body(pts, xyz, scl, n, res, corner_y, Y, fy_out, ycount);
 }
 
 // exclusive scan of ycount[Y] -> ystart[Y+1], cursor[Y] (single workgroup)
@@ -389,15 +396,10 @@ __device__ __forceinline__ int wave_excl_scan(int Y, V value, E emit) {
     }
     return carry;
 }
-__global__ __launch_bounds__(256) void hv_prep_scan(const int* __restrict__ ycount, int Y,
-                                                    int* __restrict__ ystart,
-                                                    int* __restrict__ cursor,
-                                                    int* __restrict__ part_start, int4* __restrict__ q_info, int max_q,
-                                                    int* __restrict__ chunk_start, int* __restrict__ bin_of_chunk,
-                                                    int part_records, int64_t ks_ws) {
-    ycount = cat_ws(ycount, ks_ws); ystart = cat_ws(ystart, ks_ws); cursor = cat_ws(cursor, ks_ws);
-    part_start = cat_ws(part_start, ks_ws); q_info = cat_ws(q_info, ks_ws);
-    chunk_start = cat_ws(chunk_start, ks_ws); bin_of_chunk = cat_ws(bin_of_chunk, ks_ws);
+__device__ __forceinline__ void prep_scan_body(const int* __restrict__ ycount, int Y, int* __restrict__ ystart,
+                                               int* __restrict__ cursor, int* __restrict__ part_start,
+                                               int4* __restrict__ q_info, int max_q, int* __restrict__ chunk_start,
+                                               int* __restrict__ bin_of_chunk, int part_records) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (wave == 0) {
         const int total = wave_excl_scan(Y, [&](int i) { return ycount[i]; },
@@ -430,6 +432,17 @@ __global__ __launch_bounds__(256) void hv_prep_scan(const int* __restrict__ ycou
         if (lane == 0) chunk_start[Y] = total;
     }
 }
+__global__ __launch_bounds__(256) void hv_prep_scan(const int* __restrict__ ycount, int Y,
+                                                    int* __restrict__ ystart,
+                                                    int* __restrict__ cursor,
+                                                    int* __restrict__ part_start, int4* __restrict__ q_info, int max_q,
+                                                    int* __restrict__ chunk_start, int* __restrict__ bin_of_chunk,
+                                                    int part_records, int64_t ks_ws) {
+    ycount = cat_ws(ycount, ks_ws); ystart = cat_ws(ystart, ks_ws); cursor = cat_ws(cursor, ks_ws);
+    part_start = cat_ws(part_start, ks_ws); q_info = cat_ws(q_info, ks_ws);
+    chunk_start = cat_ws(chunk_start, ks_ws); bin_of_chunk = cat_ws(bin_of_chunk, ks_ws);
+    prep_scan_body(ycount, Y, ystart, cursor, part_start, q_info, max_q, chunk_start, bin_of_chunk, part_records);
+}
 
 // Scatters every point with an in-bounds y into its y-bin and writes a compact SoA record
 // (REC_F floats, bin order) so the tile kernel streams coalesced rows instead of gathering
@@ -439,13 +452,11 @@ __global__ __launch_bounds__(256) void hv_prep_scan(const int* __restrict__ ycou
 // of the vote at rotation 0; used only for culling.
 constexpr int REC_F = 13;
 
-__global__ __launch_bounds__(PREP_THREADS) void hv_prep_scatter(
+__device__ __forceinline__ void prep_scatter_body(
     const float* __restrict__ pts, const float* __restrict__ xyz, const float* __restrict__ scl,
     const float* __restrict__ obj, const int* __restrict__ fy_in, int64_t n, int Y, float res,
-    F3 corner, int* __restrict__ cursor, float* __restrict__ rec, int64_t rec_stride, CatStride ks) {
+    F3 corner, int* __restrict__ cursor, float* __restrict__ rec, int64_t rec_stride) {
     __shared__ int lh[PREP_MAX_Y];     // per-workgroup count, then the workgroup's base in the bin
-    xyz = cat_el(xyz, 3 * ks.n); scl = cat_el(scl, 3 * ks.n); obj = cat_el(obj, ks.n);
-    fy_in = cat_ws(fy_in, ks.ws); cursor = cat_ws(cursor, ks.ws); rec = cat_ws(rec, ks.ws);
     const bool use_lds = Y <= PREP_MAX_Y;
     const int64_t c = blockIdx.x * (int64_t)PREP_THREADS + threadIdx.x;
     const int fy = c < n ? fy_in[c] : -1;
@@ -483,6 +494,14 @@ __global__ __launch_bounds__(PREP_THREADS) void hv_prep_scatter(
     r[11 * rec_stride] = sqrtf(cx * cx + cz * cz) / res;
     // vote(theta) = u - r (cos(theta + phi), sin(theta + phi)) with (cx, cz) = r (cos phi, sin phi)
     r[12 * rec_stride] = atan2f(cz, cx) + 3.14159265f;
+}
+__global__ __launch_bounds__(PREP_THREADS) void hv_prep_scatter(
+    const float* __restrict__ pts, const float* __restrict__ xyz, const float* __restrict__ scl,
+    const float* __restrict__ obj, const int* __restrict__ fy_in, int64_t n, int Y, float res,
+    F3 corner, int* __restrict__ cursor, float* __restrict__ rec, int64_t rec_stride, CatStride ks) {
+    xyz = cat_el(xyz, 3 * ks.n); scl = cat_el(scl, 3 * ks.n); obj = cat_el(obj, ks.n);
+    fy_in = cat_ws(fy_in, ks.ws); cursor = cat_ws(cursor, ks.ws); rec = cat_ws(rec, ks.ws);
+    prep_scatter_body(pts, xyz, scl, obj, fy_in, n, Y, res, corner, cursor, rec, rec_stride);
 }
 
 
@@ -540,17 +559,12 @@ __device__ __forceinline__ void ring_arc(float ux, float uz, float a0, int R, fl
 //   hv_list_pass<true>   lists only, the same walk again: entry -> list_start + chunk slot + LDS rank
 // chunk_start[Y + 1] / bin_of_chunk[] come from hv_prep_scan.
 template <bool FILL>
-__global__ __launch_bounds__(1024) void hv_list_pass(const int* __restrict__ ystart, const int* __restrict__ chunk_start,
-                                                     const int* __restrict__ bin_of_chunk, int Y,
-                                                     const float* __restrict__ rec, int64_t rec_stride, int R, int tiles_x,
-                                                     int tiles_z, const int* __restrict__ list_ctl, int* __restrict__ list_cnt,
-                                                     const int* __restrict__ list_start, int* __restrict__ chunk_off,
-                                                     int2* __restrict__ entries, int* __restrict__ tile_w, int want_lists,
-                                                     int64_t ks_ws) {
-    ystart = cat_ws(ystart, ks_ws); chunk_start = cat_ws(chunk_start, ks_ws); bin_of_chunk = cat_ws(bin_of_chunk, ks_ws);
-    rec = cat_ws(rec, ks_ws); list_ctl = cat_ws(list_ctl, ks_ws); list_cnt = cat_ws(list_cnt, ks_ws);
-    list_start = cat_ws(list_start, ks_ws); chunk_off = cat_ws(chunk_off, ks_ws); entries = cat_ws(entries, ks_ws);
-    tile_w = cat_ws(tile_w, ks_ws);
+__device__ __forceinline__ void list_pass_body(const int* __restrict__ ystart, const int* __restrict__ chunk_start,
+                                               const int* __restrict__ bin_of_chunk, int Y, const float* __restrict__ rec,
+                                               int64_t rec_stride, int R, int tiles_x, int tiles_z,
+                                               const int* __restrict__ list_ctl, int* __restrict__ list_cnt,
+                                               const int* __restrict__ list_start, int* __restrict__ chunk_off,
+                                               int2* __restrict__ entries, int* __restrict__ tile_w, int want_lists) {
     __shared__ int cnt[LIST_MAX_TILES];
     __shared__ int wsum[FILL ? 1 : LIST_MAX_TILES];
     const int ntiles = tiles_x * tiles_z;
@@ -599,11 +613,25 @@ __global__ __launch_bounds__(1024) void hv_list_pass(const int* __restrict__ yst
         if (wsum[t]) atomicAdd(&tile_w[(int64_t)bin * ntiles + t], wsum[t]);
     }
 }
+template <bool FILL>
+__global__ __launch_bounds__(1024) void hv_list_pass(const int* __restrict__ ystart, const int* __restrict__ chunk_start,
+                                                     const int* __restrict__ bin_of_chunk, int Y,
+                                                     const float* __restrict__ rec, int64_t rec_stride, int R, int tiles_x,
+                                                     int tiles_z, const int* __restrict__ list_ctl, int* __restrict__ list_cnt,
+                                                     const int* __restrict__ list_start, int* __restrict__ chunk_off,
+                                                     int2* __restrict__ entries, int* __restrict__ tile_w, int want_lists,
+                                                     int64_t ks_ws) {
+    ystart = cat_ws(ystart, ks_ws); chunk_start = cat_ws(chunk_start, ks_ws); bin_of_chunk = cat_ws(bin_of_chunk, ks_ws);
+    rec = cat_ws(rec, ks_ws); list_ctl = cat_ws(list_ctl, ks_ws); list_cnt = cat_ws(list_cnt, ks_ws);
+    list_start = cat_ws(list_start, ks_ws); chunk_off = cat_ws(chunk_off, ks_ws); entries = cat_ws(entries, ks_ws);
+    tile_w = cat_ws(tile_w, ks_ws);
+    list_pass_body<FILL>(ystart, chunk_start, bin_of_chunk, Y, rec, rec_stride, R, tiles_x, tiles_z, list_ctl, list_cnt, list_start,
+                         chunk_off, entries, tile_w, want_lists);
+}
 
 // list_ctl[0] = total entries, list_ctl[1] = overflow flag (zeroed by the caller's fill)
-__global__ __launch_bounds__(1024) void hv_list_scan(const int* __restrict__ list_cnt, int Y, int ntiles, long long list_cap,
-                                                     int* __restrict__ list_ctl, int* __restrict__ list_start, int64_t ks_ws) {
-    list_cnt = cat_ws(list_cnt, ks_ws); list_ctl = cat_ws(list_ctl, ks_ws); list_start = cat_ws(list_start, ks_ws);
+__device__ __forceinline__ void list_scan_body(const int* __restrict__ list_cnt, int Y, int ntiles, long long list_cap,
+                                               int* __restrict__ list_ctl, int* __restrict__ list_start) {
     __shared__ int s[1024];
     __shared__ long long carry_s;      // 64 bits: a total past 2^31 must raise the overflow flag, not wrap
     if (threadIdx.x == 0) carry_s = 0;
@@ -628,6 +656,11 @@ __global__ __launch_bounds__(1024) void hv_list_scan(const int* __restrict__ lis
     }
     if (threadIdx.x == 0) { list_ctl[0] = carry_s < 0x7fffffffll ? (int)carry_s : 0x7fffffff; list_ctl[1] = carry_s > list_cap ? 1 : 0; }
 }
+__global__ __launch_bounds__(1024) void hv_list_scan(const int* __restrict__ list_cnt, int Y, int ntiles, long long list_cap,
+                                                     int* __restrict__ list_ctl, int* __restrict__ list_start, int64_t ks_ws) {
+    list_cnt = cat_ws(list_cnt, ks_ws); list_ctl = cat_ws(list_ctl, ks_ws); list_start = cat_ws(list_start, ks_ws);
+    list_scan_body(list_cnt, Y, ntiles, list_cap, list_ctl, list_start);
+}
 
 // ---- work queue of the tile kernel (round 3) -----------------------------------------------------------------------
 // The launch used to hold (plane, part) x tile workgroups with the parts of a plane sized by the RECORDS of its two
@@ -641,10 +674,8 @@ constexpr int PART_VOTES = 32768;    // arc steps per part: 64 per lane of the w
                                      // scene, 2.01 -> 1.32 ms for the vote stage; never swept on its own)
 constexpr int QUEUE_MAX_PARTS = 32;
 
-__global__ __launch_bounds__(1024) void hv_build_queue(const int* __restrict__ tile_w, int Y, int ntiles, int max_items,
-                                                       int max_slots, int* __restrict__ list_ctl /*[2] = items*/,
-                                                       int4* __restrict__ items, int64_t ks_ws) {
-    tile_w = cat_ws(tile_w, ks_ws); list_ctl = cat_ws(list_ctl, ks_ws); items = cat_ws(items, ks_ws);
+__device__ __forceinline__ void build_queue_body(const int* __restrict__ tile_w, int Y, int ntiles, int max_items, int max_slots,
+                                                 int* __restrict__ list_ctl /*[2] = items*/, int4* __restrict__ items) {
     __shared__ unsigned long long s[1024];
     __shared__ unsigned long long carry_s;
     const int total = Y * ntiles;
@@ -689,6 +720,12 @@ __global__ __launch_bounds__(1024) void hv_build_queue(const int* __restrict__ t
         __syncthreads();
     }
     if (threadIdx.x == 0) list_ctl[2] = min(total, max_items);     // (total <= max_items by construction)
+}
+__global__ __launch_bounds__(1024) void hv_build_queue(const int* __restrict__ tile_w, int Y, int ntiles, int max_items,
+                                                       int max_slots, int* __restrict__ list_ctl /*[2] = items*/,
+                                                       int4* __restrict__ items, int64_t ks_ws) {
+    tile_w = cat_ws(tile_w, ks_ws); list_ctl = cat_ws(list_ctl, ks_ws); items = cat_ws(items, ks_ws);
+    build_queue_body(tile_w, Y, ntiles, max_items, max_slots, list_ctl, items);
 }
 
 __device__ __forceinline__ int lanes_below(uint64_t mask) {
@@ -1377,20 +1414,14 @@ __device__ __forceinline__ void hv_tile_item(
 // launched one workgroup per item of the full launch it spent its time on ~8 000 workgroups that found an empty record
 // (LABNOTES, vote peaks).
 template <bool QUEUE, int MODE>
-__global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
+__device__ __forceinline__ void fwd_tiles_body(
     int R, float res, F3 corner, I3 dims, const float2* __restrict__ tab,
     const int* __restrict__ ystart, const int4* __restrict__ items, const float* __restrict__ rec,
     int64_t rec_stride, int tiles_x, int tiles_z, unsigned long long* __restrict__ partials,
     int* __restrict__ arrivals, float* __restrict__ g_obj, float* __restrict__ g_rot,
     float* __restrict__ g_scale, const int* __restrict__ list_ctl, const int* __restrict__ list_start, const int* __restrict__ list_cnt,
     const int2* __restrict__ entries, int list_mode /* 1: stream the bins, 2: work lists */,
-    const int4* __restrict__ q_info, CatStride ks, int4* __restrict__ hot, float thresh, int4* __restrict__ hot_items) {
-    ystart = cat_ws(ystart, ks.ws); items = cat_ws(items, ks.ws); rec = cat_ws(rec, ks.ws);
-    partials = cat_ws(partials, ks.ws); arrivals = cat_ws(arrivals, ks.ws); list_ctl = cat_ws(list_ctl, ks.ws);
-    list_start = cat_ws(list_start, ks.ws); list_cnt = cat_ws(list_cnt, ks.ws); entries = cat_ws(entries, ks.ws);
-    q_info = cat_ws(q_info, ks.ws);
-    g_obj = cat_el(g_obj, ks.cells); g_rot = cat_el(g_rot, 2 * ks.cells); g_scale = cat_el(g_scale, 3 * ks.cells);
-    if (MODE != VOTE_FULL) { hot = cat_ws(hot, ks.ws); hot_items = cat_ws(hot_items, ks.ws); }
+    const int4* __restrict__ q_info, int4* __restrict__ hot, float thresh, int4* __restrict__ hot_items) {
     const int ntiles = tiles_x * tiles_z;
 #define CV_TILE_ITEM_ARGS R, res, corner, dims, ystart, rec, rec_stride, tiles_x, tiles_z, partials, arrivals, g_obj, g_rot, g_scale, \
                           list_ctl, list_start, list_cnt, entries, list_mode, hot, thresh, hot_items
@@ -1418,6 +1449,24 @@ __global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
     }
     hv_tile_item<QUEUE, MODE>(y, tile, part, nparts, slot0, slot_stride, CV_TILE_ITEM_ARGS, tab);
 #undef CV_TILE_ITEM_ARGS
+}
+template <bool QUEUE, int MODE>
+__global__ __launch_bounds__(TW * 64) void hv_fwd_tiles(
+    int R, float res, F3 corner, I3 dims, const float2* __restrict__ tab,
+    const int* __restrict__ ystart, const int4* __restrict__ items, const float* __restrict__ rec,
+    int64_t rec_stride, int tiles_x, int tiles_z, unsigned long long* __restrict__ partials,
+    int* __restrict__ arrivals, float* __restrict__ g_obj, float* __restrict__ g_rot,
+    float* __restrict__ g_scale, const int* __restrict__ list_ctl, const int* __restrict__ list_start, const int* __restrict__ list_cnt,
+    const int2* __restrict__ entries, int list_mode /* 1: stream the bins, 2: work lists */,
+    const int4* __restrict__ q_info, CatStride ks, int4* __restrict__ hot, float thresh, int4* __restrict__ hot_items) {
+    ystart = cat_ws(ystart, ks.ws); items = cat_ws(items, ks.ws); rec = cat_ws(rec, ks.ws);
+    partials = cat_ws(partials, ks.ws); arrivals = cat_ws(arrivals, ks.ws); list_ctl = cat_ws(list_ctl, ks.ws);
+    list_start = cat_ws(list_start, ks.ws); list_cnt = cat_ws(list_cnt, ks.ws); entries = cat_ws(entries, ks.ws);
+    q_info = cat_ws(q_info, ks.ws);
+    g_obj = cat_el(g_obj, ks.cells); g_rot = cat_el(g_rot, 2 * ks.cells); g_scale = cat_el(g_scale, 3 * ks.cells);
+    if (MODE != VOTE_FULL) { hot = cat_ws(hot, ks.ws); hot_items = cat_ws(hot_items, ks.ws); }
+    fwd_tiles_body<QUEUE, MODE>(R, res, corner, dims, tab, ystart, items, rec, rec_stride, tiles_x, tiles_z, partials, arrivals, g_obj,
+                                g_rot, g_scale, list_ctl, list_start, list_cnt, entries, list_mode, q_info, hot, thresh, hot_items);
 }
 
 // ---------------------------------------------------------------------------
@@ -1555,7 +1604,7 @@ int check_common(const void* a, const void* b, const void* c, int64_t n, float r
 }
 
 // streaming launch (small grids): sum over planes of parts per tile: sum_y ceil(n2_y / PART_RECORDS) <= Y + 2n / PART_RECORDS
-int64_t tiles_q_bound(int64_t n, int Y) { return (int64_t)Y + (2 * n + PART_RECORDS - 1) / PART_RECORDS; }
+__host__ __device__ inline int64_t tiles_q_bound(int64_t n, int Y) { return (int64_t)Y + (2 * n + PART_RECORDS - 1) / PART_RECORDS; }
 // the launch shape: work lists + work queue where a plane has many tiles (measured, bench vote stage: 300k-point scene,
 // 200 tiles: 2.01 -> 1.32 ms; 80k scene, 66 tiles: 0.37 -> 0.40 ms - the weight pass and the queue build cost more than
 // the tile kernel gains there; forced either way in flight: profiles/r3/vote_tile_sweep.txt, r5/knobs_in_flight.txt), the
@@ -1565,17 +1614,19 @@ constexpr int PEAK_WGS = 512;        // workgroups of the VOTE_PEAKS launch (two
 // work queue: partial-tile slots for the (plane, tile) pairs with more than one part (sum of arc lengths <= about
 // 2 * n * num_rots counting both planes of a vote and the slack steps; twice that again as room) and items = one per
 // (plane, tile) + the extra parts; hv_build_queue falls back to one part per tile if either is exceeded
-int64_t queue_max_slots(int64_t n, int num_rots) { return 4 * n * (int64_t)num_rots / PART_VOTES + 256; }
-int64_t queue_max_items(int64_t n, int num_rots, int64_t Y, int64_t ntiles) { return Y * ntiles + queue_max_slots(n, num_rots); }
+__host__ __device__ inline int64_t queue_max_slots(int64_t n, int num_rots) { return 4 * n * (int64_t)num_rots / PART_VOTES + 256; }
+__host__ __device__ inline int64_t queue_max_items(int64_t n, int num_rots, int64_t Y, int64_t ntiles) { return Y * ntiles + queue_max_slots(n, num_rots); }
 // capacity of the work-list array: 40 entries per point on average (a ring of 1.5 m radius crosses ~20 tiles) and never
 // more than every (point, tile) pair; beyond it the tile kernel streams the bins as before
-int64_t list_capacity(int64_t n, int64_t ntiles) { return std::min<int64_t>(n * ntiles, 40 * n + 65536); }
+__host__ __device__ inline int64_t list_capacity(int64_t n, int64_t ntiles) { return n * ntiles < 40 * n + 65536 ? n * ntiles : 40 * n + 65536; }
 
 // The workspace of the tile algorithm, stated ONCE: the launch shape, the bounds derived from it and every array of one
 // category's carve, in carve order, each aligned to 256 bytes.  The size query, the category stride, the CV_ENOMEM check, the
 // zero fill and the launches all read this (base = nullptr: sizes only).  The workspace follows the launch shape actually
 // chosen: the streaming launch (80k-point scenes) takes none of the list / queue arrays (zero-length carves, nothing of it
 // reads them; they were > 60 MB of every stream's 100 MB vote scratch until round 4).
+// Host and device: a scene kernel (below) restates its job's layout from (carve base, n, num_rots, dims) - a table of the
+// pointers themselves, 21 per job and their bounds, would not fit the kernel arguments sixteen times.
 struct TilesLayout {
     bool queue;                    // work queue + work lists (large grids) or the streaming launch
     int tiles_x, tiles_z, ntiles;
@@ -1593,7 +1644,7 @@ struct TilesLayout {
     size_t zero_bytes;             // ... up to the end of arrivals (the streaming launch only needs ycount and arrivals zeroed)
     size_t bytes;                  // end of the last array, rounded up to 256: one category's workspace and the category stride
 };
-TilesLayout tiles_layout(int64_t n, int num_rots, const int* dims, void* base) {
+__host__ __device__ inline TilesLayout tiles_layout(int64_t n, int num_rots, const int* dims, void* base) {
     TilesLayout L{};
     const size_t Y = (size_t)dims[1];
     L.tiles_x = (dims[0] + TX - 1) / TX;
@@ -1647,6 +1698,97 @@ int pick_algo(int algo, int64_t n, int num_rots) {
     if (algo == 1 || algo == 2) return algo;
     if (num_rots <= MAX_R_TILES && n < (1ll << 31)) return 2;
     return 1;
+}
+
+// ---- Scene axis (cv_hv_forward_scenes_f32): B votes that share nothing but res, num_rots and the rotation table.  Job b votes
+// the rows [row0, row0 + n) of the shared point / prediction arrays onto its own corner and shape, into its own grid triple, on
+// its own workspace carve `ws_off` bytes into the call's workspace.  The job table travels by value in the kernel arguments,
+// launch dimension y is the job (as hv_decode.hip's scene axis), and a workgroup restates the TilesLayout of its job - every
+// counter, record, list, partial slot, arrival word and hot-item list is the job's own, and so are Y, the tile counts, max_q and
+// the LDS-histogram choice.  Launch extents are the maximum over the jobs: a workgroup beyond its own job's extent returns as
+// a whole before its first barrier.  The bodies are the category kernels' bodies: a job's grids are the single call's bits.
+struct VoteSceneJob {
+    float* g_obj; float* g_rot; float* g_scale;
+    int64_t ws_off, row0;
+    int n;
+    I3 dims;
+    F3 corner;
+};
+struct VoteScenes {
+    VoteSceneJob j[CV_MAX_SCENES];
+    char* ws;
+    int R;
+};
+static_assert(sizeof(VoteScenes) + 128 <= 4096, "the job table and the other arguments of a scene kernel are kernel arguments");
+
+__device__ __forceinline__ TilesLayout scene_layout(const VoteScenes& js, const VoteSceneJob& j) {
+    const int d[3] = {j.dims.x, j.dims.y, j.dims.z};
+    return tiles_layout(j.n, js.R, d, js.ws + j.ws_off);
+}
+
+// every word the kernels of a job rely on being zero, for all jobs in one launch
+__global__ __launch_bounds__(256) void hv_zero_scenes(VoteScenes js) {
+    const VoteSceneJob& j = js.j[blockIdx.y];
+    const TilesLayout L = scene_layout(js, j);
+    const int64_t words = (int64_t)(L.zero_bytes / 4);
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < words; i += (int64_t)gridDim.x * 256) L.zero_from[i] = 0;
+}
+__global__ __launch_bounds__(PREP_THREADS) void hv_prep_count_scenes(VoteScenes js, const float* __restrict__ pts,
+                                                                     const float* __restrict__ xyz,
+                                                                     const float* __restrict__ scl, float res) {
+    const VoteSceneJob& j = js.j[blockIdx.y];
+    if ((int64_t)blockIdx.x * PREP_THREADS >= j.n) return;
+    const TilesLayout L = scene_layout(js, j);
+    prep_count_body(pts + j.row0 * 3, xyz + j.row0 * 3, scl + j.row0 * 3, j.n, res, j.corner.y, j.dims.y, L.fy, L.ycount);
+}
+__global__ __launch_bounds__(256) void hv_prep_scan_scenes(VoteScenes js, int part_records) {
+    const VoteSceneJob& j = js.j[blockIdx.y];
+    const TilesLayout L = scene_layout(js, j);
+    prep_scan_body(L.ycount, j.dims.y, L.ystart, L.cursor, L.part_start, L.q_info, (int)L.max_q, L.chunk_start, L.bin_of_chunk,
+                   part_records);
+}
+__global__ __launch_bounds__(PREP_THREADS) void hv_prep_scatter_scenes(VoteScenes js, const float* __restrict__ pts,
+                                                                       const float* __restrict__ xyz,
+                                                                       const float* __restrict__ scl,
+                                                                       const float* __restrict__ obj, float res) {
+    const VoteSceneJob& j = js.j[blockIdx.y];
+    if ((int64_t)blockIdx.x * PREP_THREADS >= j.n) return;
+    const TilesLayout L = scene_layout(js, j);
+    prep_scatter_body(pts + j.row0 * 3, xyz + j.row0 * 3, scl + j.row0 * 3, obj + j.row0, L.fy, j.n, j.dims.y, res, j.corner,
+                      L.cursor, L.rec, j.n);
+}
+// (the list and queue passes: jobs on the streaming side of QUEUE_MIN_TILES return at once)
+template <bool FILL>
+__global__ __launch_bounds__(1024) void hv_list_pass_scenes(VoteScenes js) {
+    const VoteSceneJob& j = js.j[blockIdx.y];
+    const TilesLayout L = scene_layout(js, j);
+    if (!L.queue || (int64_t)blockIdx.x >= L.max_chunks) return;
+    list_pass_body<FILL>(L.ystart, L.chunk_start, L.bin_of_chunk, j.dims.y, L.rec, j.n, js.R, L.tiles_x, L.tiles_z, L.list_ctl,
+                         L.list_cnt, L.list_start, L.chunk_off, L.entries, L.tile_w, 1);
+}
+__global__ __launch_bounds__(1024) void hv_build_queue_scenes(VoteScenes js) {
+    const VoteSceneJob& j = js.j[blockIdx.y];
+    const TilesLayout L = scene_layout(js, j);
+    if (!L.queue) return;
+    build_queue_body(L.tile_w, j.dims.y, L.ntiles, (int)L.max_items, (int)L.max_slots, L.list_ctl, L.items);
+}
+__global__ __launch_bounds__(1024) void hv_list_scan_scenes(VoteScenes js) {
+    const VoteSceneJob& j = js.j[blockIdx.y];
+    const TilesLayout L = scene_layout(js, j);
+    if (!L.queue) return;
+    list_scan_body(L.list_cnt, j.dims.y, L.ntiles, L.list_cap, L.list_ctl, L.list_start);
+}
+// one launch per side of QUEUE_MIN_TILES that the batch has jobs on; each returns at once for the other side's jobs
+template <bool QUEUE, int MODE>
+__global__ __launch_bounds__(TW * 64) void hv_fwd_tiles_scenes(VoteScenes js, float res, const float2* __restrict__ tab,
+                                                               float thresh) {
+    const VoteSceneJob& j = js.j[blockIdx.y];
+    const TilesLayout L = scene_layout(js, j);
+    if (L.queue != QUEUE) return;
+    if ((int64_t)blockIdx.x >= (QUEUE ? L.max_items : L.max_q * L.ntiles)) return;
+    fwd_tiles_body<QUEUE, MODE>(js.R, res, j.corner, j.dims, tab, L.ystart, L.items, L.rec, j.n, L.tiles_x, L.tiles_z, L.partials,
+                                L.arrivals, j.g_obj, j.g_rot, j.g_scale, L.list_ctl, L.list_start, L.list_cnt, L.entries,
+                                QUEUE ? 2 : 1, L.q_info, L.hot, thresh, L.hot_items);
 }
 
 }  // namespace
@@ -1919,6 +2061,148 @@ int cv_hv_forward_peaks_cat_f32(const float* d_points, const float* d_xyz, const
     CV_REQUIRE(d_obj && d_grid_obj && d_grid_rot && d_grid_scale, CV_EINVAL, "null pointer argument");
     return hv_forward_cats(d_points, d_xyz, d_scale, d_obj, n, res, num_rots, h_corner3, dims, d_grid_obj, d_grid_rot, d_grid_scale,
                            d_ws, ws_bytes, algo, num_cats, static_cast<hipStream_t>(stream), true, thresh);
+}
+
+// ---- scene axis -------------------------------------------------------------------------------------------------------------
+// The workspace: the jobs' cv_hv_forward_workspace_bytes carved in job order (every one a multiple of 256), no table head.  The
+// query, the CV_ENOMEM check and the carve offsets of the launches all read this; 0: a job the single query refuses.
+static size_t scenes_workspace(const cv_decode_scene_job* jobs, int B, int num_rots, int algo, size_t* offs) {
+    size_t total = 0;
+    for (int b = 0; b < B; ++b) {
+        const size_t one = jobs[b].n < (1ll << 31) ? cv_hv_forward_workspace_bytes(jobs[b].n, num_rots, jobs[b].dims, algo) : 0;
+        if (one == 0) return 0;
+        if (offs) offs[b] = total;
+        total += cv_align_up(one, 256);
+    }
+    return total;
+}
+
+size_t cv_hv_forward_scenes_workspace_bytes(const cv_decode_scene_job* jobs, int num_scenes, int num_rots, int algo) {
+    if (!jobs || num_scenes < 1 || num_scenes > CV_MAX_SCENES) return 0;
+    return scenes_workspace(jobs, num_scenes, num_rots, algo, nullptr);
+}
+
+static int hv_forward_scenes(const cv_decode_scene_job* jobs, int B, const float* d_points, const float* d_xyz, const float* d_scale,
+                             const float* d_obj, float res, int num_rots, void* d_ws, size_t ws_bytes, int algo, hipStream_t st,
+                             bool peaks, float thresh) {
+    // ---- refusals, all of them before the first device call
+    CV_REQUIRE(B >= 1 && B <= CV_MAX_SCENES, CV_EINVAL, "num_scenes out of range (%d, 1..%d)", B, CV_MAX_SCENES);
+    CV_REQUIRE(jobs && d_points && d_xyz && d_scale && d_obj, CV_EINVAL, "null pointer argument");
+    CV_REQUIRE(algo_ok(algo), CV_EINVAL, "algo out of range (%d: 0 auto, 1 direct, 2 tiles)", algo);
+    CV_REQUIRE(!peaks || thresh == thresh, CV_EINVAL, "thresh is not a number");
+    CV_REQUIRE(res > 0.f, CV_EINVAL, "res must be positive");
+    CV_REQUIRE(num_rots > 0 && num_rots <= 4096, CV_EINVAL, "num_rots out of range (%d)", num_rots);
+    int a = 0;
+    for (int b = 0; b < B; ++b) {
+        const cv_decode_scene_job& j = jobs[b];
+        CV_REQUIRE(j.d_grid_obj && j.d_grid_rot && j.d_grid_scale, CV_EINVAL, "scene %d: null grid pointer", b);
+        CV_REQUIRE(j.n > 0 && j.n < (1ll << 31), CV_EINVAL, "scene %d: n out of range (got %lld)", b, (long long)j.n);
+        CV_REQUIRE(j.row0 >= 0, CV_EINVAL, "scene %d: negative row0 (%lld)", b, (long long)j.row0);
+        CV_REQUIRE(j.dims[0] > 0 && j.dims[1] > 0 && j.dims[2] > 0, CV_EINVAL, "scene %d: bad grid dims", b);
+        CV_REQUIRE((int64_t)j.dims[0] * j.dims[1] * j.dims[2] < (1ll << 31), CV_EINVAL, "scene %d: grid too large", b);
+        CV_REQUIRE(j.n * (int64_t)num_rots < (1ll << 40), CV_EINVAL, "scene %d: n*num_rots too large", b);
+        // (pick_algo depends on num_rots and on n < 2^31 alone: one choice for the batch)
+        a = pick_algo(algo, j.n, num_rots);
+        if (a == 2) {
+            CV_REQUIRE(num_rots <= MAX_R_TILES, CV_EINVAL, "tiles algorithm needs num_rots <= %d", MAX_R_TILES);
+            const TilesLayout L = tiles_layout(j.n, num_rots, j.dims, nullptr);
+            CV_REQUIRE((L.queue ? L.max_items : L.max_q * L.ntiles) < (1ll << 31), CV_EINVAL, "scene %d: grid too large", b);
+        }
+    }
+    size_t offs[CV_MAX_SCENES];
+    const size_t need = scenes_workspace(jobs, B, num_rots, algo, offs);
+    CV_REQUIRE(need > 0 && d_ws && ws_bytes >= need, CV_ENOMEM, "workspace too small for %d scenes (needs %zu bytes)", B, need);
+
+    // ---- one scene, or the direct kernel (not the hot path): the single call's launches, job after job
+    if (B == 1 || a == 1) {
+        for (int b = 0; b < B; ++b) {
+            const cv_decode_scene_job& j = jobs[b];
+            const size_t one = (b + 1 < B ? offs[b + 1] : need) - offs[b];
+            const int rc = hv_forward_cats(d_points + j.row0 * 3, d_xyz + j.row0 * 3, d_scale + j.row0 * 3, d_obj + j.row0, j.n, res,
+                                           num_rots, j.corner, j.dims, j.d_grid_obj, const_cast<float*>(j.d_grid_rot),
+                                           const_cast<float*>(j.d_grid_scale), static_cast<char*>(d_ws) + offs[b], one, algo, 1, st,
+                                           peaks, thresh);
+            if (rc) return rc;
+        }
+        return CV_OK;
+    }
+
+    // ---- the tile algorithm over the scene axis
+    const float2* tab = nullptr;
+    const int rc = get_rot_table(num_rots, &tab);
+    if (rc) return rc;
+    VoteScenes js{};
+    js.ws = static_cast<char*>(d_ws);
+    js.R = num_rots;
+    int64_t max_n = 0, zero_words = 0, max_chunks = 0, wgs[2] = {0, 0};       // launch extents: the maximum over the jobs
+    for (int b = 0; b < B; ++b) {
+        const cv_decode_scene_job& j = jobs[b];
+        // (the one place the decode's job struct is written through: the vote fills the grids the decode reads)
+        js.j[b] = VoteSceneJob{j.d_grid_obj, const_cast<float*>(j.d_grid_rot), const_cast<float*>(j.d_grid_scale), (int64_t)offs[b],
+                               j.row0, (int)j.n, I3{j.dims[0], j.dims[1], j.dims[2]}, F3{j.corner[0], j.corner[1], j.corner[2]}};
+        const TilesLayout L = tiles_layout(j.n, num_rots, j.dims, nullptr);
+        max_n = std::max<int64_t>(max_n, j.n);
+        zero_words = std::max<int64_t>(zero_words, (int64_t)(L.zero_bytes / 4));
+        if (L.queue) max_chunks = std::max(max_chunks, L.max_chunks);
+        wgs[L.queue] = std::max(wgs[L.queue], L.queue ? L.max_items : L.max_q * L.ntiles);
+    }
+    const unsigned prep_wgs = (unsigned)((max_n + PREP_THREADS - 1) / PREP_THREADS);
+    const int part_records = (int)(t_part_records > 0 ? t_part_records : g_part_records.load(std::memory_order_relaxed));
+    hv_zero_scenes<<<dim3((unsigned)std::min<int64_t>((zero_words + 255) / 256, 1024), B), 256, 0, st>>>(js);
+    CV_LAUNCH_CHECK();
+    hv_prep_count_scenes<<<dim3(prep_wgs, B), PREP_THREADS, 0, st>>>(js, d_points, d_xyz, d_scale, res);
+    CV_LAUNCH_CHECK();
+    hv_prep_scan_scenes<<<dim3(1, B), 256, 0, st>>>(js, part_records);
+    CV_LAUNCH_CHECK();
+    hv_prep_scatter_scenes<<<dim3(prep_wgs, B), PREP_THREADS, 0, st>>>(js, d_points, d_xyz, d_scale, d_obj, res);
+    CV_LAUNCH_CHECK();
+    if (wgs[1] > 0) {
+        hv_list_pass_scenes<false><<<dim3((unsigned)max_chunks, B), 1024, 0, st>>>(js);
+        CV_LAUNCH_CHECK();
+        hv_build_queue_scenes<<<dim3(1, B), 1024, 0, st>>>(js);
+        CV_LAUNCH_CHECK();
+        hv_list_scan_scenes<<<dim3(1, B), 1024, 0, st>>>(js);
+        CV_LAUNCH_CHECK();
+        hv_list_pass_scenes<true><<<dim3((unsigned)max_chunks, B), 1024, 0, st>>>(js);
+        CV_LAUNCH_CHECK();
+    }
+#define CV_SCENE_TILES(MODE, CAP)                                                                                              \
+    do {                                                                                                                        \
+        if (wgs[0] > 0) {                                                                                                       \
+            hv_fwd_tiles_scenes<false, MODE><<<dim3((unsigned)std::min<int64_t>(wgs[0], CAP), B), TW * 64, 0, st>>>(js, res, tab, \
+                                                                                                                    thresh);     \
+            CV_LAUNCH_CHECK();                                                                                                  \
+        }                                                                                                                       \
+        if (wgs[1] > 0) {                                                                                                       \
+            hv_fwd_tiles_scenes<true, MODE><<<dim3((unsigned)std::min<int64_t>(wgs[1], CAP), B), TW * 64, 0, st>>>(js, res, tab,  \
+                                                                                                                   thresh);      \
+            CV_LAUNCH_CHECK();                                                                                                  \
+        }                                                                                                                       \
+    } while (0)
+    if (t_ev_start) CV_HIP_CHECK(hipEventRecord(t_ev_start, st));
+    if (peaks) {
+        CV_SCENE_TILES(VOTE_OBJ, (int64_t)1 << 31);
+        CV_SCENE_TILES(VOTE_PEAKS, (int64_t)PEAK_WGS);
+    } else {
+        CV_SCENE_TILES(VOTE_FULL, (int64_t)1 << 31);
+    }
+    if (t_ev_stop) CV_HIP_CHECK(hipEventRecord(t_ev_stop, st));
+#undef CV_SCENE_TILES
+    return CV_OK;
+}
+
+int cv_hv_forward_scenes_f32(const cv_decode_scene_job* jobs, int num_scenes, const float* d_points, const float* d_xyz,
+                             const float* d_scale, const float* d_obj, float res, int num_rots, void* d_ws, size_t ws_bytes,
+                             int algo, void* stream) {
+    return hv_forward_scenes(jobs, num_scenes, d_points, d_xyz, d_scale, d_obj, res, num_rots, d_ws, ws_bytes, algo,
+                             static_cast<hipStream_t>(stream), false, 0.f);
+}
+
+int cv_hv_forward_peaks_scenes_f32(const cv_decode_scene_job* jobs, int num_scenes, const float* d_points, const float* d_xyz,
+                                   const float* d_scale, const float* d_obj, float res, int num_rots, void* d_ws, size_t ws_bytes,
+                                   int algo, float thresh, void* stream) {
+    return hv_forward_scenes(jobs, num_scenes, d_points, d_xyz, d_scale, d_obj, res, num_rots, d_ws, ws_bytes, algo,
+                             static_cast<hipStream_t>(stream), true, thresh);
 }
 
 int cv_hv_backward_f32(const float* d_grad_obj, const float* d_points, const float* d_xyz,

@@ -322,7 +322,7 @@ int cv_detect_scene_f32(const cv_scene_desc* d, cv_scene_result* r, void* stream
     return CV_OK;
 }
 
-// B scans in one call: the front, the network and the head over all rows, a vote per scene, one decode over the scene axis.
+// B scans in one call: the front, the network and the head over all rows, one vote and one decode over the scene axis.
 int cv_detect_scenes_f32(const cv_scenes_desc* sd, cv_scenes_result* r, void* stream) {
     CV_REQUIRE(sd && r, CV_EINVAL, "null scene descriptor / result");
     const cv_scene_desc* d = &sd->scene;
@@ -358,7 +358,7 @@ int cv_detect_scenes_f32(const cv_scenes_desc* sd, cv_scenes_result* r, void* st
 
     // ---- per scene: row range, corner, grid shape
     cv_decode_scene_job jobs[CV_MAX_SCENES];
-    size_t cells[CV_MAX_SCENES], grid_floats = 0, vote_ws_b = 256, dec_ws_b = 0;
+    size_t cells[CV_MAX_SCENES], grid_floats = 0, dec_ws_b = 0;
     const int32_t* hb = f.h_bounds();
     for (int b = 0; b < B; ++b) {
         // (ranges checked by the front, behind its wait; one scene: all rows, the one-scene call's bounds)
@@ -375,12 +375,12 @@ int cv_detect_scenes_f32(const cv_scenes_desc* sd, cv_scenes_result* r, void* st
         r->row0[b] = first; r->rows[b] = end - first;
         cells[b] = (size_t)j.dims[0] * j.dims[1] * j.dims[2];
         grid_floats += cv_align_up(6 * cells[b], 64);
-        vote_ws_b = std::max(vote_ws_b, cv_hv_forward_workspace_bytes(j.n, d->num_rots, j.dims, d->vote_algo));
         dec_ws_b += cv_decode_workspace_bytes(j.dims, j.n, M);
     }
 
-    // ---- what depends on the level sizes and the grid shapes: one arena, ONE vote workspace (the largest scene's: the votes
-    // run one after another on the stream), B decode carves, B grid triples resident together
+    // ---- what depends on the level sizes and the grid shapes: one arena, B vote carves (the scenes' votes run side by side in
+    // one launch sequence), B decode carves, B grid triples resident together
+    const size_t vote_ws_b = std::max<size_t>(cv_hv_forward_scenes_workspace_bytes(jobs, B, d->num_rots, d->vote_algo), 256);
     const size_t arena_b = cv_net_arena_bytes(d->bufs, d->n_bufs, f.rows, 5);
     char* arena = cv.take<char>(arena_b);
     char* conv_ws = cv.take<char>(f.conv_ws_b);
@@ -413,26 +413,17 @@ int cv_detect_scenes_f32(const cv_scenes_desc* sd, cv_scenes_result* r, void* st
     r->d_xyz = xyz; r->d_scale = scale; r->d_prob = prob; r->d_class = cls;
     CV_HIP_CHECK(clock.mark(2));
 
-    // ---- B votes, each on its scene's rows, corner and shape; then one decode over the scene axis
+    // ---- one vote over the scene axis, each scene on its rows, corner and shape; then one decode over the same job table
     const float* v_xyz = d->d_xyz_in ? d->d_xyz_in : xyz;
     const float* v_scale = d->d_scale_in ? d->d_scale_in : scale;
     const float* v_prob = d->d_prob_in ? d->d_prob_in : prob;
     const int32_t* v_cls = d->d_class_in ? d->d_class_in : cls;
-    for (int b = 0; b < B; ++b) {
-        const cv_decode_scene_job& j = jobs[b];
-        const float* p = d->d_points + j.row0 * 3;
-        const float *px = v_xyz + j.row0 * 3, *ps = v_scale + j.row0 * 3, *pp = v_prob + j.row0;
-        // (the workspace as the single call sizes it for this scene)
-        const size_t ws_b = std::max<size_t>(cv_hv_forward_workspace_bytes(j.n, d->num_rots, j.dims, d->vote_algo), 256);
-        rc = d->peak_quotients
-                 ? cv_hv_forward_peaks_f32(p, px, ps, pp, j.n, d->res, d->num_rots, j.corner, j.dims, j.d_grid_obj,
-                                           const_cast<float*>(j.d_grid_rot), const_cast<float*>(j.d_grid_scale), vote_ws, ws_b,
-                                           d->vote_algo, d->decode.thresh_high, stream)
-                 : cv_hv_forward_f32(p, px, ps, pp, j.n, d->res, d->num_rots, j.corner, j.dims, j.d_grid_obj,
-                                     const_cast<float*>(j.d_grid_rot), const_cast<float*>(j.d_grid_scale), vote_ws, ws_b, d->vote_algo,
-                                     stream);
-        if (rc != CV_OK) return rc;
-    }
+    rc = d->peak_quotients
+             ? cv_hv_forward_peaks_scenes_f32(jobs, B, d->d_points, v_xyz, v_scale, v_prob, d->res, d->num_rots, vote_ws, vote_ws_b,
+                                              d->vote_algo, d->decode.thresh_high, stream)
+             : cv_hv_forward_scenes_f32(jobs, B, d->d_points, v_xyz, v_scale, v_prob, d->res, d->num_rots, vote_ws, vote_ws_b,
+                                        d->vote_algo, stream);
+    if (rc != CV_OK) return rc;
     CV_HIP_CHECK(clock.mark(3));
     clock.lap(2);
     cv_decode_params prm = d->decode;

@@ -129,7 +129,8 @@ def decode_boxes_scenes(grids, corners, row_ranges, scan_points, xyz_pred, prob_
                         prob_thresh=0.3, err_thresh=0.3, separate_variant=False, max_candidates=512, mutate_grid=False):
     """decode_boxes over B scenes with ONE host sync (cv_decode_scenes_f32).  ``grids``: B triples (grid_obj [X,Y,Z],
     grid_rot [X,Y,Z,2], grid_scale [X,Y,Z,3]) of any shapes, ``corners``: B grid origins, ``row_ranges``: B (first, end) row
-    ranges of the shared scan_points / xyz_pred [N,3], prob_pred / class_pred [N].  Returns a list of B dicts, entry b exactly
+    ranges of the shared scan_points / xyz_pred [N,3], prob_pred / class_pred [N].  ``corners`` None: the origins that
+    hv_cuda.forward_scenes (or forward) remembered on the grids it returned.  Returns a list of B dicts, entry b exactly
     what ``decode_boxes(..., allow_truncation=True)`` returns for scene b's grids and rows alone: a walk that fills
     ``max_candidates`` comes back capped and marked ``truncated`` (the caller redoes that scene)."""
     L = _lib.lib()
@@ -139,6 +140,10 @@ def decode_boxes_scenes(grids, corners, row_ranges, scan_points, xyz_pred, prob_
             (g, "grids[%d][%d]" % (b, i)) for b, tri in enumerate(grids) for i, g in enumerate(tri)]:
         if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32:
             raise RuntimeError("%s must be a contiguous float32 CUDA tensor" % name)
+    if corners is None:
+        corners = [hv_cuda.recent_corner(tri[0]) for tri in grids]
+        if any(c is None for c in corners):
+            raise RuntimeError("decode_boxes_scenes: corners=None needs grids returned by hv_cuda.forward_scenes / forward")
     if not (len(corners) == B and len(row_ranges) == B):
         raise RuntimeError("decode_boxes_scenes: one corner and one row range per grid triple")
     cls = class_pred.to(torch.int32).contiguous()

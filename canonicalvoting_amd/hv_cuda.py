@@ -6,6 +6,8 @@
         -> [d_xyz_labels, d_scale_labels, d_obj_labels]                    (hv_cuda.cpp:47-71)
     forward_categories(points, xyz[K,N,3], scale[K,N,3], obj[K,N], res, num_rots)
         -> [K,...] grids: K separate-mode categories in one launch sequence (no reference counterpart)
+    forward_scenes(points, xyz_labels, scale_labels, obj_labels, row_ranges, res, num_rots[, corners][, thresh])
+        -> B grid triples: B scenes' row ranges of shared arrays in one launch sequence (no reference counterpart)
 
 Same argument meaning, same input checks and messages (``"<name> must be a CUDA tensor"``,
 ``"<name> must be contiguous"``, hv_cuda.cpp:26-28), same fresh writable outputs on the inputs'
@@ -247,6 +249,96 @@ def forward_categories(points, xyz_labels, scale_labels, obj_labels, res, num_ro
     n, res_v, nrot, K = _checked_inputs(points, xyz_labels, scale_labels, obj_labels, res, num_rots, categories=True)
     mn, _, dims = grid_geometry(points, res_v)
     return _vote(points, xyz_labels, scale_labels, obj_labels, res_v, nrot, mn, dims, K)
+
+
+def _scene_bounds(points, row_ranges):
+    """(min[3], max[3]) of every row range with ONE host wait: B reductions enqueued on the stream (the kernels grid_geometry
+    runs, so the values are forward's), each landing in its own pinned buffer, then one wait for all of them."""
+    L = _lib.lib()
+    dev = points.device
+    ws = _lib.scratch(dev, "hv_minmax", L.cv_hv_minmax_workspace_bytes())
+    hosts = [_pinned6() for _ in row_ranges]
+    with torch.cuda.device(dev):
+        for (a, b), host in zip(row_ranges, hosts):
+            # (byte offset of the first row: a slice of a slice keeps the storage offset)
+            first = points.data_ptr() + a * 3 * 4
+            _lib.check(L.cv_hv_minmax_async_f32(first, b - a, _ptr(host), _ptr(ws), ws.numel(), _stream(dev)),
+                       "cv_hv_minmax_async_f32")
+        torch.cuda.current_stream(dev).synchronize()
+    out = []
+    for host in hosts:
+        h = host.tolist()
+        _recycle(host)
+        out.append((h[:3], h[3:]))
+    return out
+
+
+def forward_scenes(points, xyz_labels, scale_labels, obj_labels, row_ranges, res, num_rots, corners=None, thresh=None):
+    """B scenes' votes in ONE launch sequence (cv_hv_forward_scenes_f32): scene i votes the rows ``row_ranges[i] = (a, b)`` of the
+    shared points [N,3], xyz_labels / scale_labels [N,3] and obj_labels [N] onto its own grid.  Returns a list of B
+    ``[grid_obj, grid_rot, grid_scale]``, each bit for bit ``forward(points[a:b], xyz_labels[a:b], ...)`` - with ``corners``
+    (a sequence of B [2,3] boxes) the 7-argument form.  Ranges may come in any order and leave gaps; 1 <= B <= 16.  Without
+    ``corners`` the B bounds cost one host wait for the whole batch.  ``thresh``: the peaks entry point
+    (cv_hv_forward_peaks_scenes_f32) - grid_rot / grid_scale hold values only where grid_obj >= thresh.  Every grid's origin
+    is remembered for the decode, so ``decode.decode_boxes_scenes`` takes the result directly.  ``res`` / ``num_rots`` are
+    0-dim tensors (as forward takes them) or numbers."""
+    named = ((points, "points"), (xyz_labels, "xyz_labels"), (scale_labels, "scale_labels"), (obj_labels, "obj_labels"))
+    for t, name in named + tuple((t, nm) for t, nm in ((res, "res"), (num_rots, "num_rots")) if torch.is_tensor(t)):
+        _check_input(t, name)
+    for t, name in named:
+        if t.dtype != torch.float32:
+            raise RuntimeError("%s must be float32 (got %s)" % (name, t.dtype))
+    n = points.shape[0]
+    if points.dim() != 2 or points.shape[1] != 3 or xyz_labels.shape != (n, 3) or scale_labels.shape != (n, 3) \
+            or obj_labels.shape != (n,):
+        raise RuntimeError("expected points/xyz_labels/scale_labels [N,3] and obj_labels [N]")
+    ranges = [(int(a), int(b)) for a, b in row_ranges]
+    B = len(ranges)
+    if not 1 <= B <= _lib.MAX_SCENES:
+        raise RuntimeError("hv_cuda: expected 1 to %d row ranges (got %d)" % (_lib.MAX_SCENES, B))
+    for i, (a, b) in enumerate(ranges):
+        if not 0 <= a <= b <= n:
+            raise RuntimeError("hv_cuda: row range %d (%d, %d) lies outside the %d rows" % (i, a, b, n))
+        if a == b:
+            raise RuntimeError("hv_cuda: cannot vote with zero points (row range %d)" % i)
+    if corners is not None and len(corners) != B:
+        raise RuntimeError("hv_cuda: expected one corners[2,3] box per row range")
+    res_v = _scalar(res, "f") if torch.is_tensor(res) else float(res)
+    nrot = _scalar(num_rots, "i") if torch.is_tensor(num_rots) else int(num_rots)
+    if corners is None:
+        geo = [(mn, _grid_dims(_f3(mn), _f3(mx), res_v)) for mn, mx in _scene_bounds(points, ranges)]
+    else:
+        geo = []
+        for c in corners:
+            c = c.detach().to("cpu", torch.float32)
+            mn = [float(v) for v in c[0]]
+            geo.append((mn, _grid_dims(_f3(mn), _f3(c[1]), res_v)))
+    L = _lib.lib()
+    dev = points.device
+    jobs = (_lib.DecodeSceneJob * B)()
+    out = []
+    for i, ((a, b), (mn, dims)) in enumerate(zip(ranges, geo)):
+        shape = tuple(dims)
+        grids = [torch.empty(shape + tail, dtype=torch.float32, device=dev) for tail in ((), (2,), (3,))]
+        j = jobs[i]
+        j.d_grid_obj, j.d_grid_rot, j.d_grid_scale = (g.data_ptr() for g in grids)
+        j.dims[:] = dims
+        j.corner[:] = mn
+        j.row0, j.n = a, b - a
+        out.append(grids)
+    wsb = L.cv_hv_forward_scenes_workspace_bytes(jobs, B, nrot, _algo)
+    ws = _lib.scratch(dev, "hv_forward", max(wsb, 256))
+    head = [jobs, B, _ptr(points), _ptr(xyz_labels), _ptr(scale_labels), _ptr(obj_labels), ctypes.c_float(res_v), nrot, _ptr(ws),
+            ws.numel(), _algo]
+    with torch.cuda.device(dev):
+        if thresh is None:
+            _lib.check(L.cv_hv_forward_scenes_f32(*head, _stream(dev)), "cv_hv_forward_scenes_f32")
+        else:
+            _lib.check(L.cv_hv_forward_peaks_scenes_f32(*head, ctypes.c_float(thresh), _stream(dev)),
+                       "cv_hv_forward_peaks_scenes_f32")
+    for grids, (mn, _) in zip(out, geo):
+        _remember_corner(grids[0], mn)
+    return out
 
 
 def backward(grad_grid, points, xyz_labels, scale_labels, obj_labels, res, num_rots, corners=None):

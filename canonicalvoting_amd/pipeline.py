@@ -426,7 +426,7 @@ def detect_scenes_c(model, hv, coords4, feats, res, num_scenes, scan_points=None
                     events=None, nclasses=9, log_scale=True, max_candidates=512, adaptive_split=False, **decode_kw):
     """detect_scene_c for ``num_scenes`` scans in ONE C call (cv_detect_scenes_f32): ``coords4`` / ``feats`` are the scans
     collated one after another with batch indices 0..B-1 (non-decreasing), ``scan_points`` and ``predictions`` cover all rows.
-    One coordinate plan, one network program and one head launch over all rows, a vote per scene, one decode over the scene
+    One coordinate plan, one network program and one head launch over all rows, one vote and one decode over the scene
     axis: two host waits per batch.  Scene b's vote grids, decode and detections are the bits detect_scene_c gives for that
     scan alone when ``predictions`` are given; on the network's own predictions they follow the batched network output,
     which agrees with the scan-alone output within the network's tolerance.  A raised fp16-range flag redoes the whole batch

@@ -60,7 +60,9 @@ extern "C" {
  *    Still 6: a trailing cv_conv_desc.valid_words (appended: a zero-initialised descriptor runs as before).
  *    Still 6: the scene axis - cv_decode_scenes_f32 (cv_decode_scene_job) with cv_decode_scenes_workspace_bytes,
  *    cv_detect_scenes_f32 (cv_scenes_desc, cv_scenes_result) and their cv_sizeof_* helpers (additive: no struct or signature
- *    moved). */
+ *    moved).
+ *    Still 6: the vote's scene axis - cv_hv_forward_scenes_f32 / cv_hv_forward_peaks_scenes_f32 over cv_decode_scene_job with
+ *    cv_hv_forward_scenes_workspace_bytes (additive: no struct or signature moved). */
 #define CV_ABI_VERSION 6
 int cv_abi_version(void);
 const char* cv_last_error(void);
@@ -236,6 +238,25 @@ int cv_decode_scenes_f32(const cv_decode_scene_job* jobs, int num_scenes, float 
                          const float* d_prob, const int32_t* d_class, const cv_decode_params* params, int mutate_grid, void* d_ws,
                          size_t ws_bytes, int* h_n_cand, int64_t* h_cand_idx, int32_t* h_verdict, int* h_n_boxes, float* h_boxes,
                          float* h_scores, int32_t* h_classes, int* h_truncated, void* stream);
+
+/* cv_hv_forward_f32 / cv_hv_forward_peaks_f32 over B = num_scenes scenes in ONE launch sequence whose launch count does not
+ * depend on B, on the job table the decode above takes: a caller builds one table and hands it to the vote and then to the
+ * decode.  The vote WRITES through d_grid_rot / d_grid_scale (declared const for the decode, which reads them).  Job b votes the
+ * rows [row0, row0 + n) of the shared d_points / d_xyz / d_scale [.][3] and d_obj [.] arrays onto its own corner and shape into
+ * its own grid triple; row ranges may come in any order and leave gaps, nothing outside a job's range is read.  Every job's
+ * grids are bit for bit what the single call writes for that scene alone, on every launch shape (all sums are integers).
+ * 1 <= B <= CV_MAX_SCENES; B = 1 is the single call.  d_ws: cv_hv_forward_scenes_workspace_bytes(jobs, B, num_rots, algo)
+ * bytes - the sum of the jobs' cv_hv_forward_workspace_bytes, carved in job order; it may arrive dirty.  When algo resolves to
+ * the direct kernel (more than 256 rotations) the jobs run one after another.  cv_hv_set_kernel_events (around the accumulation
+ * launches) and cv_hv_set_part_records[_thread] (one part size for all jobs) apply as to the single call.  CV_EINVAL (the
+ * message names the scene) before anything is launched.  Asynchronous on `stream`: no host wait, no allocation. */
+size_t cv_hv_forward_scenes_workspace_bytes(const cv_decode_scene_job* jobs, int num_scenes, int num_rots, int algo);
+int cv_hv_forward_scenes_f32(const cv_decode_scene_job* jobs, int num_scenes, const float* d_points, const float* d_xyz,
+                             const float* d_scale, const float* d_obj, float res, int num_rots, void* d_ws, size_t ws_bytes,
+                             int algo, void* stream);
+int cv_hv_forward_peaks_scenes_f32(const cv_decode_scene_job* jobs, int num_scenes, const float* d_points, const float* d_xyz,
+                                   const float* d_scale, const float* d_obj, float res, int num_rots, void* d_ws, size_t ws_bytes,
+                                   int algo, float thresh, void* stream);
 
 /* Instance labels: which scan points each of a list of boxes owns (eval_joint.py:231-245: bbox_mask_world and mask, which
  * the decode reduces to statistics per candidate and drops).  A box is named by the flat grid cell the decode examined
@@ -1026,8 +1047,10 @@ int cv_detect_scene_f32(const cv_scene_desc* desc, cv_scene_result* result, void
  * B scans in ONE call: cv_detect_scene_f32 over a scene axis.  `scene` describes the batched tensor: d_coords4 [n][4] with the
  * batch column non-decreasing and in [0, num_scenes) (scans collated one after another), d_feats / d_points / d_out_feats and
  * the optional d_*_in predictions over all n rows.  One launch reduces the per-scene row ranges and bounds, ONE coordinate
- * plan and ONE network program run over all rows, one head launch, then per scene a vote on its row range, corner and grid
- * shape (one after another on the stream) and ONE decode over the scene axis (cv_decode_scenes_f32).  The host waits twice
+ * plan and ONE network program run over all rows, one head launch, then ONE vote over the scene axis - every scene on its row
+ * range, corner and grid shape, side by side in one launch sequence (cv_hv_forward_scenes_f32, the peaks form under
+ * peak_quotients; the vote workspace is the sum of the scenes') - and ONE decode over the same job table
+ * (cv_decode_scenes_f32).  The host waits twice
  * per BATCH (level counts - the per-scene ranges and bounds arrive with them - and the decode results); NMS per scene and class
  * on the host.  Scene b is what cv_detect_scene_f32 returns for that scan alone in everything but the network output, which
  * agrees within the network's own tolerance (the batched plan orders and splits the convolutions' sums differently);

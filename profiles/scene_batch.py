@@ -6,7 +6,8 @@
 Synthetic scans with teacher predictions (bench.py --predictions teacher).  Per scan size, in the same process:
   * detect_scenes_c with B in --batches from one host thread: scenes/s (median and min..max of --reps repetitions), host
     microseconds per stage and per CALL (plan + wait, network enqueue, head + votes enqueue, decode + wait + NMS), kernel launches per scene
-    (counted once with the torch profiler; "n/a" where it does not see the library's launches);
+    (counted once with the torch profiler, fills and copies not counted; "n/a" where it does not see the library's launches) and
+    the device scratch the call asked for (needed_ws_bytes);
   * baseline 1: a loop of detect_scene_c from one thread;
   * baseline 2: seven threads of detect_scene_c, a stream each, under policy_for_scenes_in_flight(7) (how bench.py gets its
     headline).
@@ -181,8 +182,10 @@ def main():
                 call()
                 us = [u + v / 8 for u, v in zip(us, host.last_host_us)]
             nl = launches(call)
-            lines.append("points %6d  detect_scenes_c B = %d, one thread          %s scenes/s  launches/scene %s  host us/call %s"
-                         % (n, B, fmt(r), "n/a" if nl is None else "%.1f" % (nl / B), " | ".join("%7.0f" % u for u in us)))
+            # (needed_ws_bytes of the calls so far on this host; the scan sizes grow, so it is this size's)
+            lines.append("points %6d  detect_scenes_c B = %d, one thread          %s scenes/s  launches/scene %s  host us/call %s  scratch %.1f MB"
+                         % (n, B, fmt(r), "n/a" if nl is None else "%.1f" % (nl / B), " | ".join("%7.0f" % u for u in us),
+                            host.ws_hint / 1e6))
             print(lines[-1], flush=True)
             if B == 1:
                 spread = max(base[2] - base[1], r[2] - r[1])
